@@ -14,11 +14,16 @@ Multi-GPU: frames shard by sequence, one independent sequence per rank, no data-
  -> "weak" scaling; RCCL carries only the barrier and the max-time / frame-count
 reductions.
 
-Besides the contract's JSON line the script reports
+A plain run sets up, warms up, times the K steps once and prints the contract's JSON line.  With
+--full it also runs the serial calibration pass, times the K-step region three times (median) and
+checks the timed schedule against a serial re-run of its last step, and it reports
   roofline     -- the dominant kernel (longest average duration, HIP events on the launch stream,
                   recorded by the library around every stage of every timed step) priced against
                   the 8 TB/s HBM peak with SURVEY.md 8d's algorithmic bytes;
+  secondary    -- the copy-kernel roofline, the other schedules and the C3 / C4 configurations;
   cpu_baseline -- the CPU oracle ("port" of the reference algorithm) timed on this host, rank 0.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32.
 """
 import argparse
 import json
@@ -134,6 +139,41 @@ def valu_issue_step(frames_per_step, ms_per_step):
         except Exception:
             continue
     return None
+
+
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs may write in all
+
+
+def dump_sample(n, k):
+    """Indices of the frames of a step that --dump-outputs writes: all n up to k, else a fixed seeded sample of k."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(20261016).choice(n, k, replace=False))
+
+
+def valid_rows(per_frame, counts):
+    """per_frame[f, :counts[f]] of every frame f, concatenated: the entries a caller reads (the slots past a frame's
+    count are left from earlier steps)."""
+    return np.concatenate([per_frame[f, :int(c)] for f, c in enumerate(counts)])
+
+
+def keypoint_columns(kps):
+    """[..., 7] orbgpu_keypoint records held in float32 -> x, y, size, angle, response, octave, class_id as float32 values
+    (the two int32 fields converted by value)."""
+    out = np.array(kps, np.float32)
+    out[..., 5:7] = np.ascontiguousarray(kps[..., 5:7]).view(np.int32)
+    return out
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (every value written is exact in float32)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def _cpu_worker(libpath, frames, seconds_budget, want_stages):
@@ -269,15 +309,18 @@ def main_c3_batch(args, rank, local_rank, world):
     cnt = wl.counts.cpu().numpy()
     n_host = wl.nout.cpu().numpy()
     assert n_host.min() > 0 and cnt[:, 0].min() > 0, "benchmark produced empty frames"
-    # the timed region three times (one 41-ms sample has no spread): the contract's K steps each, barrier on
-    # both sides of every repetition; `value` comes from the median repetition
+    # the timed region: the contract's K steps, barrier on both sides.  --full: three times (one 41-ms sample
+    # has no spread), the second with HIP events at the stage boundaries of every 4th step; `value` comes from the median
+    # repetition
     PROF_EVERY = 4
+    NREP = 3 if args.full else 1
     reps = []
-    for r in range(3):
+    for r in range(NREP):
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            wl.ext.set_profiling(r == 1 and i % PROF_EVERY == 0)
+            if args.full:
+                wl.ext.set_profiling(r == 1 and i % PROF_EVERY == 0)
             wl.step()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
@@ -286,12 +329,34 @@ def main_c3_batch(args, rank, local_rank, world):
         torch.cuda.synchronize()
         e_max, total = D.aggregate(elapsed, B * args.steps, world, device="cuda" if args.backend == "nccl" else "cpu")
         reps.append((e_max, total))
-    stage_ms = wl.ext.stage_times()
-    wl.ext.set_profiling(False)
-    order = sorted(range(3), key=lambda r: reps[r][0])
-    e_med, total = reps[order[1]]
+    order = sorted(range(NREP), key=lambda r: reps[r][0])
+    e_med, total = reps[order[NREP // 2]]
+    if rank == 0 and args.dump_outputs:
+        # every sequence works on its own copy of the same frame and map: a sample of them says as much as all
+        idx = torch.as_tensor(dump_sample(B, 32), device=wl.kps.device)
+        n = wl.nout.index_select(0, idx).cpu().numpy()
+        rows = {k: v.index_select(0, idx).cpu().numpy() for k, v in (("kps", wl.kps), ("desc", wl.desc), ("ur", wl.ur),
+                                                                      ("k2m", wl.k2m))}
+        write_outputs(args.dump_outputs, {
+            "keypoints": keypoint_columns(valid_rows(rows["kps"], n)), "descriptors": valid_rows(rows["desc"], n),
+            "keypoint_counts": n, "u_right": valid_rows(rows["ur"], n), "keypoint_to_mappoint": valid_rows(rows["k2m"], n),
+            "search_counts": wl.counts.index_select(0, idx).cpu().numpy(), "sequence_index": idx.cpu().numpy()})
     if rank == 0:
         N = float(n_host.mean())
+        out = {"metric": "frames/sec ORB extract + SearchByProjection (1280x960, 2000 feat, ~10 k local MapPoints)",
+               "value": total / e_med, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": max(args.warmup, 1),
+               "ms_per_step": e_med / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+               "dtype": "u8", "data": "synthetic",
+               "config": {"workload": "C3 (BASELINE.json configs[2]) in throughput mode: synthetic 1280x960 RGB-D, 2000 features, 8 "
+                                      "levels; per step and sequence one frame: extract + frame glue (ComputeStereoFromRGBD, grid) "
+                                      "+ Tracking::SearchLocalPoints (isInFrustum + SearchByProjection th=3) against the sequence's "
+                                      "%d local map points" % wl.M,
+                          "sequences_per_gpu": B, "frames_per_step_per_gpu": B, "sequences": B * world,
+                          "parallelism": "%d sequences per GPU, sequences never cross GPUs" % B, "schedule": "serial, 1 stream"},
+               "keypoints_per_frame": N, "matches_per_frame": float(cnt[:, 0].mean()), "map_points": wl.M}
+    if rank == 0 and args.full:
+        stage_ms = wl.ext.stage_times()
+        wl.ext.set_profiling(False)
         n_cand = float(sum(len(wl.ext.debug_read(G.DBG_CANDIDATES, 0, lvl)[0]) for lvl in range(8)))
         launches = {k: len(v) for k, v in STAGE_KERNELS.items()}
         dom = max(stage_ms, key=lambda k: stage_ms[k] / launches[k])
@@ -299,32 +364,23 @@ def main_c3_batch(args, rank, local_rank, world):
         ach = dom_bytes / (stage_ms[dom] * 1e-3) / 1e9
         alg_m2, alg_ext = wl.algorithmic_bytes(N)
         ext_ms = sum(stage_ms.values())
-        out = {"metric": "frames/sec ORB extract + SearchByProjection (1280x960, 2000 feat, ~10 k local MapPoints)",
-               "value": total / e_med, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": max(args.warmup, 1),
-               "ms_per_step": e_med / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "u8", "data": "synthetic",
-               "timed_region_repeats": {"frames_per_s": [round(t / e, 1) for e, t in reps],
-                                        "spread_pct": round(100 * (max(e for e, _ in reps) - min(e for e, _ in reps)) / e_med, 2),
-                                        "value_is": "median of 3 repetitions of the K-step region"},
-               "config": {"workload": "C3 (BASELINE.json configs[2]) in throughput mode: synthetic 1280x960 RGB-D, 2000 features, 8 "
-                                      "levels; per step and sequence one frame: extract + frame glue (ComputeStereoFromRGBD, grid) "
-                                      "+ Tracking::SearchLocalPoints (isInFrustum + SearchByProjection th=3) against the sequence's "
-                                      "%d local map points" % wl.M,
-                          "sequences_per_gpu": B, "frames_per_step_per_gpu": B, "sequences": B * world,
-                          "parallelism": "%d sequences per GPU, sequences never cross GPUs" % B, "schedule": "serial, 1 stream"},
-               "roofline": {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                            "frac": ach / HBM_PEAK_GBS, "traffic": None,
-                            "traffic_source": "no PMC pass at 1280x960 (the C2 passes under profiles/ are per 640x480 frame)",
-                            "algorithmic_bytes": dom_bytes, "ms_per_launch": stage_ms[dom], "frames_per_launch": B},
-               "stages": {k: {"ms": round(v, 4), "GB/s": round(wl.stage_bytes(k, N, n_cand) * B / (max(v, 1e-6) * 1e-3) / 1e9, 1)}
-                          for k, v in stage_ms.items()},
-               "extract_ms_per_step": round(ext_ms, 4),
-               "extract_roofline": {"achieved": alg_ext / (ext_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                    "frac": alg_ext / (ext_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "algorithmic_bytes": alg_ext},
-               "search_algorithmic_bytes_per_step": alg_m2,
-               "keypoints_per_frame": N, "matches_per_frame": float(cnt[:, 0].mean()), "map_points": wl.M}
+        out.update({
+            "timed_region_repeats": {"frames_per_s": [round(t / e, 1) for e, t in reps],
+                                     "spread_pct": round(100 * (max(e for e, _ in reps) - min(e for e, _ in reps)) / e_med, 2),
+                                     "value_is": "median of 3 repetitions of the K-step region"},
+            "roofline": {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": ach / HBM_PEAK_GBS, "traffic": None,
+                         "traffic_source": "no PMC pass at 1280x960 (the C2 passes under profiles/ are per 640x480 frame)",
+                         "algorithmic_bytes": dom_bytes, "ms_per_launch": stage_ms[dom], "frames_per_launch": B},
+            "stages": {k: {"ms": round(v, 4), "GB/s": round(wl.stage_bytes(k, N, n_cand) * B / (max(v, 1e-6) * 1e-3) / 1e9, 1)}
+                       for k, v in stage_ms.items()},
+            "extract_ms_per_step": round(ext_ms, 4),
+            "extract_roofline": {"achieved": alg_ext / (ext_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                 "frac": alg_ext / (ext_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "algorithmic_bytes": alg_ext},
+            "search_algorithmic_bytes_per_step": alg_m2})
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline_c3(wl)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     D.finalize(world)
 
@@ -337,6 +393,12 @@ def main():
     ap.add_argument("--batch", type=int, default=512,
                     help="frames per step and per GPU (225 k frames/s at 512, 216 k at 256, 197 k at 128: launch tails amortise)")
     ap.add_argument("--pool", type=int, default=1024, help="distinct resident frames cycled through (> Infinity Cache)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the contract line: serial calibration pass (per-kernel times, roofline), three "
+                         "repetitions of the timed region, self-check, secondary configurations and CPU baseline; a plain "
+                         "run sets up, warms up, times the K steps once and prints the contract line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-self-check", action="store_true",
                     help="skip the serial re-run that checks the timed schedule (profiling passes: keeps every launch of a "
@@ -455,9 +517,11 @@ def main():
             D.barrier(world)
         torch.cuda.synchronize()
 
-    # ---- calibration: the serial schedule (one stream, plain handle), HIP events at every stage boundary of every step
-    #      (recorded by the library on the launch stream) and around the matcher.  Outside the timed region.
-    NCAL = 12
+    # ---- calibration (--full): the serial schedule (one stream, plain handle), HIP events at every stage boundary of
+    #      every step (recorded by the library on the launch stream) and around the matcher.  Outside the timed region.
+    #      A plain run keeps only its first two steps, which are not profiled: the handles' first calls (code objects,
+    #      workspaces) stay out of the warm-up and the timed region either way.
+    NCAL = 12 if args.full else 0
     cal_pairs = []
     for i in range(NCAL + 2):
         src = frames[(i * B) % POOL:(i * B) % POOL + B]
@@ -474,10 +538,11 @@ def main():
         desc[0][0].copy_(desc[0][B], non_blocking=True)
         nout[0][0:1].copy_(nout[0][B:B + 1], non_blocking=True)
     torch.cuda.synchronize()
-    stage_ms = ext.stage_times()  # per stage: the launches that cover the B frames of a step, nothing else on the device
-    ext.set_profiling(False)
-    match_ms = sum(a.elapsed_time(b) for a, b in cal_pairs) / len(cal_pairs)
-    match_how = "k_bf_topk + k_bf_resolve of one step, HIP events on the launch stream, serial calibration pass (%d steps)" % NCAL
+    if args.full:
+        stage_ms = ext.stage_times()  # per stage: the launches that cover the B frames of a step, nothing else on the device
+        ext.set_profiling(False)
+        match_ms = sum(a.elapsed_time(b) for a, b in cal_pairs) / len(cal_pairs)
+        match_how = "k_bf_topk + k_bf_resolve of one step, HIP events on the launch stream, serial calibration pass (%d steps)" % NCAL
 
     if cblur:
         for e in parts:
@@ -564,9 +629,9 @@ def main():
 
     run_steps(args.warmup)
     drain()
-    # ---- the timed region, NREP times: EXACTLY K steps each, barrier + synchronize on both sides, the last step's
-    #      matcher inside; max over ranks per repetition; `value` is the MEDIAN repetition
-    NREP = 3
+    # ---- the timed region: EXACTLY K steps, barrier + synchronize on both sides, the last step's matcher inside; max over
+    #      ranks.  --full: NREP = 3 repetitions, `value` is the MEDIAN repetition
+    NREP = 3 if args.full else 1
     reps = []
     for _ in range(NREP):
         barrier()
@@ -585,9 +650,23 @@ def main():
     # sanity of the measured work (rank-local): every frame produced key points and matches
     n_host = nout[0].cpu().numpy()
     nm_host = nmatch.cpu().numpy()
-    sweeps = matcher.last_sweeps(B)
+    sweeps = matcher.last_sweeps(B) if args.full else None
     assert n_host[1:].min() > 0 and nm_host.min() >= 0, "benchmark produced empty frames"
-    if args.steps > 0 and it[0] > 1 and not args.no_self_check:
+    if rank == 0 and args.dump_outputs and it[0] > 0:
+        # the last step's frames (slots 1..B of its output set; slot 0 is the step before's last frame) and the matches
+        # of each of them against the frame before it: match_b row b, entry j = key point of the frame before or -1
+        k_last = (it[0] - 1) % nsets
+        sel = dump_sample(B, 128)
+        idx = torch.as_tensor(sel, device=nmatch.device)
+        n = nout[k_last][1:].index_select(0, idx).cpu().numpy()
+        write_outputs(args.dump_outputs, {
+            "keypoints": keypoint_columns(valid_rows(kps[k_last][1:].index_select(0, idx).cpu().numpy(), n)),
+            "descriptors": valid_rows(desc[k_last][1:].index_select(0, idx).cpu().numpy(), n),
+            "keypoint_counts": n,
+            "matches": valid_rows(match_b.index_select(0, idx).cpu().numpy(), n),
+            "match_counts": nmatch.index_select(0, idx).cpu().numpy(),
+            "frame_index": sel})
+    if args.full and args.steps > 0 and it[0] > 1 and not args.no_self_check:
         # the pipelined schedule must give what a serial schedule gives: redo the last step from the frames, one
         # stream, fresh buffers (previous step's last frame -> slot 0, this step's frames -> slots 1..B), and compare
         last_i = it[0] - 1
@@ -611,7 +690,7 @@ def main():
     # What the other schedules give on this box (informational, after the contract's timed region): the same loop without
     # the concurrent blur (the r03 default); the serial schedule is the calibration pass.
     others = None
-    if world == 1 and not args.no_secondary and P == 1 and cblur and args.steps >= 10:
+    if args.full and world == 1 and not args.no_secondary and P == 1 and cblur and args.steps >= 10:
         ext.set_concurrent_blur(False)
         nup = 30
         run_steps(3)
@@ -632,6 +711,34 @@ def main():
                                                  "each): bench.py --schedule serial times it without the events"}}
 
     if rank == 0:
+        step_ms = elapsed_max / args.steps * 1e3
+        out = {
+            "metric": "frames/sec ORB extract+match (640x480, 1000 feat)",
+            "value": total_frames / elapsed_max,
+            "unit": "frames/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": step_ms,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": "synthetic",
+            "config": {"workload": "C2: synthetic 640x480 RGB-D stream, 1000 features, 8 levels, extract + BF-Hamming "
+                                   "match of consecutive frames", "frames_per_step_per_gpu": B,
+                       "resident_frame_pool": POOL, "sequences": world, "parallelism": "1 sequence per GPU",
+                       "schedule": (("extraction as %d staggered sub-batches on %d streams (orbgpu_pipeline: a part starts when the "
+                                     "previous one has passed its pyramid stage); " % (P, P) if pl else "") +
+                                    ("matcher of step i-1 on a stream of its own, started when extraction i has passed its '%s' stage"
+                                     % args.match_after if args.match_after != "start" else
+                                     "matcher of step i overlapped with extraction of step i+1 (2 streams)") +
+                                    ("; blur of every extraction on a stream of the handle's own next to FAST / quadtree" if cblur else ""))
+                       if overlap else "serial, 1 stream", "schedule_name": sched, "extraction_parts": P},
+            "keypoints_per_frame": n_kp,
+            "matches_per_frame": float(nm_host.mean()),
+        }
+    if rank == 0 and args.full:
         # dominant kernel of the extraction pipeline + its roofline fraction
         # FAST survivors handed to the quadtree (first frame of the self-check batch); prices the NMS / quadtree rows
         n_cand = 13700.0 if args.no_self_check else \
@@ -653,34 +760,11 @@ def main():
         ext_bytes = sum(algorithmic_bytes(k, n_kp, n_cand) for k in ("pyramid", "fast", "blur", "orient", "describe"))
         ext_ms = sum(stage_ms.values())  # serial calibration: the six stages follow each other
         ext_ach = ext_bytes * B / (ext_ms * 1e-3) / 1e9
-        step_ms = elapsed_max / args.steps * 1e3
-        out = {
-            "metric": "frames/sec ORB extract+match (640x480, 1000 feat)",
-            "value": total_frames / elapsed_max,
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": step_ms,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
+        out.update({
             "timed_region_repeats": {"n": NREP, "frames_per_s": [round(t / e, 1) for e, t in reps],
                                      "ms_per_step": [round(e / args.steps * 1e3, 4) for e, _ in reps],
                                      "spread_pct": round(100 * (max(e for e, _ in reps) - min(e for e, _ in reps)) / elapsed_max, 2),
                                      "value_is": "the median repetition; every repetition is K steps between barrier + synchronize"},
-            "config": {"workload": "C2: synthetic 640x480 RGB-D stream, 1000 features, 8 levels, extract + BF-Hamming "
-                                   "match of consecutive frames", "frames_per_step_per_gpu": B,
-                       "resident_frame_pool": POOL, "sequences": world, "parallelism": "1 sequence per GPU",
-                       "schedule": (("extraction as %d staggered sub-batches on %d streams (orbgpu_pipeline: a part starts when the "
-                                     "previous one has passed its pyramid stage); " % (P, P) if pl else "") +
-                                    ("matcher of step i-1 on a stream of its own, started when extraction i has passed its '%s' stage"
-                                     % args.match_after if args.match_after != "start" else
-                                     "matcher of step i overlapped with extraction of step i+1 (2 streams)") +
-                                    ("; blur of every extraction on a stream of the handle's own next to FAST / quadtree" if cblur else ""))
-                       if overlap else "serial, 1 stream", "schedule_name": sched, "extraction_parts": P},
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "algorithmic_bytes": algorithmic_bytes(dom, n_kp, n_cand) * B,
@@ -697,10 +781,8 @@ def main():
                                  "note": "all six extraction stages of one step (serial calibration) against SURVEY.md 8d's 5.74 MB/frame"},
             "fast_candidates_per_frame": n_cand,
             "match_ms_per_step": round(match_ms, 4),
-            "keypoints_per_frame": n_kp,
-            "matches_per_frame": float(nm_host.mean()),
             "bf_sweeps_max": int(sweeps.max()),
-        }
+        })
         if not args.no_secondary and world == 1:
             # free the C2 working set first, then: the practical roofline (plain copy kernel over 2 x 1 GiB, far past
             # the Infinity Cache) and the other single-GPU configurations of BASELINE.json
@@ -723,6 +805,7 @@ def main():
                     out["secondary"][name] = {"error": "%s: %s" % (type(ex).__name__, ex)}
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline([host_pool[i] for i in range(min(POOL, 400))])
+    if rank == 0:
         print(json.dumps(out), flush=True)
     D.finalize(world)
 

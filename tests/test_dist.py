@@ -5,6 +5,8 @@ import zlib
 import numpy as np
 import pytest
 
+KEYPOINT_FIELDS = ("x", "y", "size", "angle", "response", "octave", "class_id")
+
 
 def _worker(rank, world, port, q):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -90,7 +92,7 @@ def test_bench_c3_batch_two_ranks_on_one_gpu():
     on device 0, 4 sequences each; the contract fields, the workload name and the frame count over both ranks."""
     import json
     r = _run_bench(["--gpus", "2", "--backend", "gloo", "--rehearse-on-device0", "--workload", "c3_batch", "--steps", "2",
-                    "--warmup", "1", "--batch", "4", "--no-cpu-baseline"])
+                    "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -106,7 +108,7 @@ def test_bench_c3_batch_two_ranks_on_one_gpu():
 @pytest.mark.gpu
 def test_bench_c3_batch_single_rank_with_cpu_baseline():
     import json
-    r = _run_bench(["--workload", "c3_batch", "--steps", "2", "--warmup", "1", "--batch", "8"])
+    r = _run_bench(["--workload", "c3_batch", "--steps", "2", "--warmup", "1", "--batch", "8", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["config"]["sequences"] == 8
@@ -163,3 +165,66 @@ def test_bench_single_rank_through_rccl():
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["steps"] == 2 and out["value"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_step(gpu, oracle, stream640, tmp_path):
+    """A plain run prints the contract line only; --dump-outputs holds the last timed step, checked against the oracle."""
+    import json
+    r = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "8", "--pool", "16", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["unit"] == "frames/s"
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 8) < 1e-6 * 8  # frames of one step over its time
+    for extra in ("timed_region_repeats", "roofline", "secondary", "cpu_baseline"):
+        assert extra not in out, extra  # --full only
+
+    names = ("keypoints", "descriptors", "keypoint_counts", "matches", "match_counts", "frame_index")
+    assert sorted(os.listdir(tmp_path)) == sorted(k + ".npy" for k in names)
+    d = {k: np.load(str(tmp_path / (k + ".npy"))) for k in names}
+    assert all(a.dtype == np.float32 for a in d.values())
+    assert sum(a.nbytes for a in d.values()) <= 64 << 20
+    # timed steps are numbered after the warm-up: the last one (2) extracts pool frames 0..7 and matches frame 0 against
+    # the last frame of step 1 (pool frame 15)
+    assert d["frame_index"].tolist() == list(range(8))
+    n = d["keypoint_counts"].astype(np.int64)
+    off = np.concatenate([[0], np.cumsum(n)])
+    assert len(d["keypoints"]) == len(d["descriptors"]) == len(d["matches"]) == off[-1]
+    oe = oracle.Extractor(1000)
+    prev = oe.extract(stream640.frame(15)[0])
+    for b in range(8):
+        k, desc = oe.extract(stream640.frame(b)[0])
+        assert n[b] == len(k)
+        kp = d["keypoints"][off[b]:off[b + 1]]
+        for c, f in enumerate(KEYPOINT_FIELDS):
+            assert np.array_equal(kp[:, c], k[f].astype(np.float32)), (b, f)
+        assert np.array_equal(d["descriptors"][off[b]:off[b + 1]], desc.astype(np.float32)), b
+        nm, mb = oracle.match_bf(prev[1], prev[0]["angle"], desc, k["angle"], nnratio=0.7)
+        assert d["match_counts"][b] == nm, b
+        assert np.array_equal(d["matches"][off[b]:off[b + 1]], mb.astype(np.float32)), b
+        prev = (k, desc)
+
+
+@pytest.mark.gpu
+def test_bench_c3_batch_plain_run_dumps_the_last_step(gpu, tmp_path):
+    """--workload c3_batch: the contract line only, and --dump-outputs holds a consistent last step of every sequence."""
+    import json
+    r = _run_bench(["--workload", "c3_batch", "--steps", "2", "--warmup", "1", "--batch", "4", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert out["steps"] == 2 and "1280x960" in out["metric"] and out["ms_per_step"] > 0
+    assert "timed_region_repeats" not in out and "cpu_baseline" not in out and "roofline" not in out
+    names = ("keypoints", "descriptors", "keypoint_counts", "u_right", "keypoint_to_mappoint", "search_counts",
+             "sequence_index")
+    assert sorted(os.listdir(tmp_path)) == sorted(k + ".npy" for k in names)
+    d = {k: np.load(str(tmp_path / (k + ".npy"))) for k in names}
+    assert all(a.dtype == np.float32 for a in d.values())
+    assert d["sequence_index"].tolist() == [0, 1, 2, 3]
+    n = d["keypoint_counts"].astype(np.int64)
+    assert n.min() > 1900 and len(d["keypoints"]) == len(d["descriptors"]) == len(d["keypoint_to_mappoint"]) == n.sum()
+    # every sequence works on its own copy of the same frame and map
+    per_seq = np.split(d["keypoint_to_mappoint"], np.cumsum(n)[:-1])
+    assert all(np.array_equal(s, per_seq[0]) for s in per_seq)
+    assert d["search_counts"][:, 0].min() > 500 and (per_seq[0] >= 0).sum() > 500
