@@ -145,7 +145,8 @@ int orbgpu_extract_batch_device(orbgpu_extractor *h, const uint8_t *d_gray, int3
  * orientation disc and the resize only read the image interior, the blur reflects its own rim) and the library does not
  * make one ("direct mode"); this getter then makes it on demand from the image of the last call.  For the host entry
  * points that is the handle's own staging copy; after orbgpu_extract_batch_device it is the CALLER's device buffer, which
- * must still hold the images when level 0 is asked for (the RGB-D path never asks: only stereo matching reads it). */
+ * must still hold the images when level 0 is asked for (the RGB-D path never asks: only stereo matching reads it).
+ * A call that fails before it launches (ENOMEM, an unsupported size) may leave no last call to read: EINVAL. */
 int orbgpu_extractor_get_pyramid_level(orbgpu_extractor *h, int32_t frame, int32_t level, uint8_t *dst,
                                        size_t dst_stride, int32_t *width, int32_t *height);
 
@@ -155,7 +156,9 @@ enum {
     ORBGPU_DBG_PYRAMID_PADDED = 0, /* u8, (h+38) rows of `pitch` bytes; *n = bytes, aux = pitch   */
     ORBGPU_DBG_BLURRED_PADDED = 1, /* same geometry, only the w x h interior is defined           */
     ORBGPU_DBG_CANDIDATES = 2,     /* int32 triples (x,y,response), vToDistributeKeys order       */
-    ORBGPU_DBG_SELECTED = 3        /* int32 triples (x,y,response), DistributeOctTree list order  */
+    ORBGPU_DBG_SELECTED = 3,       /* int32 triples (x,y,response), DistributeOctTree list order  */
+    ORBGPU_DBG_GRAPH_COUNTS = 4    /* int32 pair: graphs recorded, graph replays of the host entry
+                                      points since creation; *n = 2 (frame / level ignored)        */
 };
 int orbgpu_extractor_debug_read(orbgpu_extractor *h, int32_t what, int32_t frame, int32_t level, void *dst,
                                 size_t dst_bytes, size_t *n, int32_t *aux);

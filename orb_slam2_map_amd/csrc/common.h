@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <mutex>
 
 #include "orbgpu.h"
@@ -74,9 +75,13 @@ struct DevBuf {
             p = nullptr;
             bytes = 0;
         }
-        hipError_t e = hipMalloc(&p, n);
+        // ORBGPU_DEBUG_FAIL_ALLOC_OVER=<bytes> (tests): an allocation larger than that fails as a refused hipMalloc does.
+        // Read here, on the allocating branch only, so that it can be set and cleared between calls of one handle.
+        const char *fail_over = getenv("ORBGPU_DEBUG_FAIL_ALLOC_OVER");
+        hipError_t e = fail_over && n > (size_t)strtoull(fail_over, nullptr, 10) ? hipErrorOutOfMemory : hipMalloc(&p, n);
         if (e != hipSuccess) {
             set_error("hipMalloc(%zu): %s", n, hipGetErrorString(e));
+            (void)hipGetLastError();  // the refusal is reported here; a later launch check must not see it as its own
             p = nullptr;
             return ORBGPU_ENOMEM;
         }

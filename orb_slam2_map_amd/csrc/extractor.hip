@@ -2232,6 +2232,10 @@ struct orbgpu_extractor {
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     uint64_t graph_key = 0;
+    // what launch_pipeline recorded as the last call's bookkeeping while the graph was recorded: a replay restores it
+    Src0 graph_src = {nullptr, 0, 0u, 0};
+    int graph_batch = 0, graph_cap = 0;
+    int graph_records = 0, graph_replays = 0;  // ORBGPU_DBG_GRAPH_COUNTS (tests)
     bool border_fast = false;  // level-0 column table present (width % 4 == 0)
     hipEvent_t stage_signal[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // caller's events
     hipEvent_t pipe_signal[8] = {};  // the same for an orbgpu_pipeline that owns this handle (stagger of its parts)
@@ -2307,6 +2311,28 @@ static void build_tables(orbgpu_extractor *e)
             abort();
 }
 
+// Forgets the recorded graph of the host entry points: the next host call of a configuration launches plainly, the one
+// after it records again.
+static void drop_graph(orbgpu_extractor *e)
+{
+    if (e->graph_exec)
+        (void)hipGraphExecDestroy(e->graph_exec);
+    if (e->graph)
+        (void)hipGraphDestroy(e->graph);
+    e->graph_exec = nullptr;
+    e->graph = nullptr;
+    e->graph_key = 0;
+}
+
+// The getters of the last call have nothing to read (its planes, or the buffer its lazy level 0 would be made from, are
+// being replaced): they answer EINVAL until the next call has launched.
+static void forget_last_call(orbgpu_extractor *e)
+{
+    e->last_batch = e->last_cap = 0;
+    e->last_src = Src0{nullptr, 0, 0u, 0};
+    e->level0_materialized = true;
+}
+
 static inline short sat_short(int v) { return (short)(v < -32768 ? -32768 : v > 32767 ? 32767 : v); }
 
 // Level sizes, FAST cell grid, resize tables, slot layout for one image size.
@@ -2317,6 +2343,12 @@ static int configure(orbgpu_extractor *e, int w, int h, int batch)
     // a real reconfigure rewrites tables that kernels of an earlier call (on the caller's stream) may still read
     if (e->cfg_w != 0)
         ORBGPU_HIP_TRY(hipDeviceSynchronize());
+    // From here on the handle is unconfigured until the end of this function: every return below leaves it so, and the
+    // next call configures again from scratch (a failed reservation has already freed the old buffer).  No recorded graph
+    // outlives the buffers it baked in, and no getter reads a last call whose geometry and planes are being replaced.
+    e->cfg_w = e->cfg_h = e->cfg_batch = 0;
+    drop_graph(e);
+    forget_last_call(e);
     const int nl = e->nlevels;
     std::vector<LevelGeom> geom(nl);
     std::vector<CellDesc> cells;
@@ -3224,6 +3256,10 @@ int orbgpu_extract_batch(orbgpu_extractor *e, const uint8_t *gray, int32_t batch
     if (rc != ORBGPU_OK)
         return rc;
     const size_t img = (size_t)w * h;
+    // growing the staging buffer frees the image the last call's lazy level 0 would be made from (should this call fail
+    // before it launches, nothing may read it)
+    if (img * batch > e->d_in.bytes)
+        forget_last_call(e);
     if ((rc = e->d_in.reserve(img * batch)) != ORBGPU_OK)
         return rc;
     if ((rc = e->d_kps.reserve(sizeof(orbgpu_keypoint) * (size_t)cap * batch)) != ORBGPU_OK)
@@ -3281,10 +3317,17 @@ int orbgpu_extract_batch(orbgpu_extractor *e, const uint8_t *gray, int32_t batch
         key = (key ^ v) * 1099511628211ull;
     bool launched = false;
     if (!e->profiling && e->graph_state >= 0) {
-        if (e->graph_exec && e->graph_key == key) {
+        // (counters left dirty by a failed call: the graph recorded without re-arming them is not replayed, a new one is)
+        if (e->graph_exec && e->graph_key == key && !e->counters_dirty) {
             if (hipGraphLaunch(e->graph_exec, e->stream) == hipSuccess) {
                 launched = true;
-                e->level0_materialized = !e->last_src.direct;  // the replay did what launch_pipeline recorded: no padded level 0 in direct mode
+                // the replay did what launch_pipeline did while recording: its bookkeeping, not that of whatever call
+                // (a device entry point on the caller's buffer, say) came in between
+                e->last_src = e->graph_src;
+                e->last_batch = e->graph_batch;
+                e->last_cap = e->graph_cap;
+                e->level0_materialized = !e->graph_src.direct;
+                e->graph_replays++;
             } else
                 e->graph_state = -1;
         } else if (e->graph_key == key) {  // second call of this configuration: record the graph
@@ -3309,6 +3352,10 @@ int orbgpu_extract_batch(orbgpu_extractor *e, const uint8_t *gray, int32_t batch
                 e->graph = g;
                 e->graph_exec = ge;
                 e->graph_state = 1;
+                e->graph_src = e->last_src;  // (set by the recording launch_pipeline above)
+                e->graph_batch = e->last_batch;
+                e->graph_cap = e->last_cap;
+                e->graph_records++;
                 ok = hipGraphLaunch(e->graph_exec, e->stream) == hipSuccess;
                 launched = ok;
                 e->level0_materialized = !e->last_src.direct;
@@ -3322,11 +3369,8 @@ int orbgpu_extract_batch(orbgpu_extractor *e, const uint8_t *gray, int32_t batch
                 e->graph_state = -1;
             }
         } else {
+            drop_graph(e);
             e->graph_key = key;  // first call of a new configuration: plain launches, the graph next time
-            if (e->graph_exec) {
-                (void)hipGraphExecDestroy(e->graph_exec);
-                e->graph_exec = nullptr;
-            }
         }
     }
     if (!launched) {
@@ -3413,6 +3457,15 @@ int orbgpu_extractor_debug_read(orbgpu_extractor *e, int32_t what, int32_t frame
                                 size_t dst_bytes, size_t *n, int32_t *aux)
 {
     ORBGPU_REQUIRE(e && dst && n, "null argument");
+    if (what == ORBGPU_DBG_GRAPH_COUNTS) {  // handle state, not a frame of the last call
+        ORBGPU_REQUIRE(dst_bytes >= 2 * sizeof(int32_t), "dst too small (%zu needed)", 2 * sizeof(int32_t));
+        const int32_t c[2] = {e->graph_records, e->graph_replays};
+        memcpy(dst, c, sizeof(c));
+        *n = 2;
+        if (aux)
+            *aux = 0;
+        return ORBGPU_OK;
+    }
     ORBGPU_REQUIRE(e->last_batch > 0 && frame >= 0 && frame < e->last_batch && level >= 0 && level < e->nlevels,
                    "no such frame/level in the last call");
     int rc = select_device(e->prm.device_id);

@@ -421,6 +421,27 @@ int orbgpu_mappoint_table_last_unknown(const orbgpu_mappoint_table *t, int32_t *
 // ---------------------------------------------------------------------------------------------------------------------
 // table
 // ---------------------------------------------------------------------------------------------------------------------
+// orbgpu_mappoint_table_destroy without the lifecycle lock: the error path of orbgpu_mappoint_table_create, which holds it
+// (the lock is not recursive).
+static int mappoint_table_destroy_impl(orbgpu_mappoint_table *t)
+{
+    if (!t)
+        return ORBGPU_OK;
+    (void)hipSetDevice(t->device_id);
+    if (t->stream) {
+        (void)hipStreamSynchronize(t->stream);
+        (void)hipStreamDestroy(t->stream);
+    }
+    DevBuf *bufs[] = {&t->world_pos, &t->normal, &t->min_dist, &t->max_dist, &t->desc,    &t->bad,    &t->obs,
+                      &t->id,        &t->d_hkeys, &t->d_hvals, &t->d_stage,  &t->g_block, &t->pos_of_row};
+    for (DevBuf *b : bufs)
+        b->release();
+    t->stage.release();
+    proj_workspace_delete(t->pws);
+    delete t;
+    return ORBGPU_OK;
+}
+
 int orbgpu_mappoint_table_create(int32_t device_id, int32_t initial_rows, orbgpu_mappoint_table **out)
 {
     std::lock_guard<std::mutex> lifecycle(orbgpu::lifecycle_mutex());
@@ -447,7 +468,7 @@ int orbgpu_mappoint_table_create(int32_t device_id, int32_t initial_rows, orbgpu
         return ORBGPU_EHIP;
     }
     if ((rc = table_grow(t, std::max(initial_rows, 1024))) != ORBGPU_OK) {
-        orbgpu_mappoint_table_destroy(t);
+        mappoint_table_destroy_impl(t);
         return rc;
     }
     *out = t;
@@ -457,21 +478,7 @@ int orbgpu_mappoint_table_create(int32_t device_id, int32_t initial_rows, orbgpu
 int orbgpu_mappoint_table_destroy(orbgpu_mappoint_table *t)
 {
     std::lock_guard<std::mutex> lifecycle(orbgpu::lifecycle_mutex());
-    if (!t)
-        return ORBGPU_OK;
-    (void)hipSetDevice(t->device_id);
-    if (t->stream) {
-        (void)hipStreamSynchronize(t->stream);
-        (void)hipStreamDestroy(t->stream);
-    }
-    DevBuf *bufs[] = {&t->world_pos, &t->normal, &t->min_dist, &t->max_dist, &t->desc,    &t->bad,    &t->obs,
-                      &t->id,        &t->d_hkeys, &t->d_hvals, &t->d_stage,  &t->g_block, &t->pos_of_row};
-    for (DevBuf *b : bufs)
-        b->release();
-    t->stage.release();
-    proj_workspace_delete(t->pws);
-    delete t;
-    return ORBGPU_OK;
+    return mappoint_table_destroy_impl(t);
 }
 
 int orbgpu_mappoint_table_rows(const orbgpu_mappoint_table *t, int32_t *rows)

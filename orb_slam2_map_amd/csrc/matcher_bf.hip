@@ -605,6 +605,20 @@ struct orbgpu_matcher {
     int resolve_threads = 1024;  // workgroup size of k_bf_resolve (ORBGPU_DEBUG_BF_RESOLVE_THREADS: 256 / 512 / 1024)
 };
 
+// orbgpu_matcher_destroy without the lifecycle lock: the error paths of orbgpu_matcher_create, which holds it (the lock
+// is not recursive -- taking it again there deadlocked the thread and every later create / destroy of the process).
+static int matcher_destroy_impl(orbgpu_matcher *m)
+{
+    if (!m)
+        return ORBGPU_OK;
+    (void)hipSetDevice(m->device_id);
+    (void)hipDeviceSynchronize();
+    m->d_topk.release();
+    m->d_sweeps.release();
+    delete m;
+    return ORBGPU_OK;
+}
+
 extern "C" {
 
 int orbgpu_matcher_create(int32_t device_id, int32_t max_pairs, int32_t cap, orbgpu_matcher **out)
@@ -631,14 +645,14 @@ int orbgpu_matcher_create(int32_t device_id, int32_t max_pairs, int32_t cap, orb
     const size_t P = (size_t)max_pairs;
     if ((rc = m->d_topk.reserve(sizeof(uint32_t) * std::max<size_t>(P * BF_MIN_SPLIT, BF_MAX_SPLIT) * cap * BF_TOPK)) != ORBGPU_OK ||
         (rc = m->d_sweeps.reserve(sizeof(int) * P)) != ORBGPU_OK) {
-        orbgpu_matcher_destroy(m);
+        matcher_destroy_impl(m);
         return rc;
     }
     hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void *>(k_bf_resolve),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, BF_RESOLVE_MAX_LDS);
     if (he != hipSuccess) {
         set_error("hipFuncSetAttribute: %s", hipGetErrorString(he));
-        orbgpu_matcher_destroy(m);
+        matcher_destroy_impl(m);
         return ORBGPU_EHIP;
     }
     *out = m;
@@ -648,14 +662,7 @@ int orbgpu_matcher_create(int32_t device_id, int32_t max_pairs, int32_t cap, orb
 int orbgpu_matcher_destroy(orbgpu_matcher *m)
 {
     std::lock_guard<std::mutex> lifecycle(orbgpu::lifecycle_mutex());
-    if (!m)
-        return ORBGPU_OK;
-    (void)hipSetDevice(m->device_id);
-    (void)hipDeviceSynchronize();
-    m->d_topk.release();
-    m->d_sweeps.release();
-    delete m;
-    return ORBGPU_OK;
+    return matcher_destroy_impl(m);
 }
 
 static int match_batch_device(orbgpu_matcher *m, int32_t pairs, int32_t cap, const uint8_t *d_desc_a,

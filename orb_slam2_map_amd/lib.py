@@ -22,7 +22,7 @@ KEYPOINT_DTYPE = np.dtype(
      ("octave", "<i4"), ("class_id", "<i4")])
 POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("rgba", "<u4")])
 
-DBG_PYRAMID_PADDED, DBG_BLURRED_PADDED, DBG_CANDIDATES, DBG_SELECTED = 0, 1, 2, 3
+DBG_PYRAMID_PADDED, DBG_BLURRED_PADDED, DBG_CANDIDATES, DBG_SELECTED, DBG_GRAPH_COUNTS = 0, 1, 2, 3, 4
 
 
 class OrbGpuError(RuntimeError):
@@ -385,6 +385,13 @@ class ORBextractor:
         if what in (DBG_PYRAMID_PADDED, DBG_BLURRED_PADDED):
             return buf[:n.value].copy(), aux.value
         return buf[:n.value * 12].view(np.int32).reshape(-1, 3).copy(), 0
+
+    def graph_counts(self):
+        """(graphs recorded, graph replays) of the host entry points on this handle since its creation."""
+        c = np.zeros(2, np.int32)
+        n = C.c_size_t()
+        check(self.L.orbgpu_extractor_debug_read(self.h, DBG_GRAPH_COUNTS, 0, 0, _p(c), c.nbytes, C.byref(n), None))
+        return int(c[0]), int(c[1])
 
     def graph_state(self):
         v = C.c_int32()
