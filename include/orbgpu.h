@@ -320,6 +320,44 @@ int orbgpu_frame_glue_batch_device(int32_t device_id, int32_t batch, int32_t cap
                                    float *d_u_right, float *d_kp_depth, int32_t *d_cell_start,
                                    int32_t *d_cell_items, void *hip_stream);
 
+/* ---- Stereo frames: Frame::ComputeStereoMatches (Frame.cc:466-638) -------------------------------------------------
+ * The stereo Frame constructor (Frame.cc:59-117) extracts both rectified images and matches every left key point along
+ * its row: descriptor search over the right key points listed in the row (octave within +-1, uR in
+ * [uL - maxD, uL + 3]: minD = -3 in this tree, Frame.cc:494), then eleven 11x11 SAD windows on the UNBLURRED pyramid
+ * level of the left key point, a parabola fit, and a cut of the matches whose SAD is >= 2.1 x the median.  Outputs are
+ * mvuRight / mvDepth (-1 where there is no match), bit-exact to the reference's float arithmetic.
+ * Conventions where the reference is undefined:
+ *  - mb is read before the constructor assigns it (Frame.cc:90 against :114): minZ = mb = mbf / fx, maxD = mbf / minZ;
+ *  - no match at all: nothing is cut (the reference reads element 0 of an empty vector);
+ *  - a key point whose row, octave or SAD windows leave the image / level plane gets no match (never a read outside it);
+ *    a right key point with an octave outside [0, nlevels) is never a candidate.  Key points the extractor made always
+ *    lie inside.
+ * The pyramids are those of the handles' LAST extraction call (orbgpu_extractor_get_pyramid_level): `left` and `right`
+ * must have the same levels, scale factor and image size, and may be the same handle.  Level 0 of a call that ran in
+ * direct mode is read from that call's own images -- after orbgpu_extract_batch_device the CALLER's device buffer, which
+ * must still hold them when the stereo kernels run; nothing is materialised and nothing runs on the handles' streams.
+ * The next extraction call on either handle replaces what this reads: order it after the stereo call. */
+
+/* Pair p matches frame left_frame0 + p of the left handle's last call with frame right_frame0 + p of the right handle's
+ * (one orbgpu_extract_batch_device of 2B frames, B left images then B right images, on one handle is the cheapest way to
+ * get B pairs).  Key points / descriptors / counts are device arrays [batch][cap] as orbgpu_extract_batch_device writes
+ * them (a negative count reads as 0); d_u_right / d_depth [batch][cap] receive mvuRight / mvDepth (-1 where no match,
+ * entries past the count included); d_n_stereo [batch] (optional) the matches kept.  Scratch lives on the left handle,
+ * so two calls with the same left handle must be ordered.  EINVAL: null handles or arrays, batch or cap < 0, handles
+ * that differ in levels, scale factor or image size, a handle without a last call, a frame range outside it.  Enqueued
+ * on hip_stream, not synchronised. */
+int orbgpu_stereo_matches_batch_device(const orbgpu_extractor *left, int32_t left_frame0, const orbgpu_extractor *right,
+                                       int32_t right_frame0, int32_t batch, int32_t cap, const orbgpu_keypoint *d_kps_l,
+                                       const int32_t *d_n_l, const uint8_t *d_desc_l, const orbgpu_keypoint *d_kps_r,
+                                       const int32_t *d_n_r, const uint8_t *d_desc_r, float mbf, float fx,
+                                       float *d_u_right, float *d_depth, int32_t *d_n_stereo, void *hip_stream);
+/* Frame::ComputeStereoMatches for one pair, host arrays: frame 0 of each handle's last call (orbgpu_extract), mvKeys /
+ * mDescriptors (n_l), mvKeysRight / mDescriptorsRight (n_r); u_right / depth receive n_l floats.  Synchronises. */
+int orbgpu_compute_stereo_matches(const orbgpu_extractor *left, const orbgpu_extractor *right, int32_t n_l,
+                                  const orbgpu_keypoint *kps_l, const uint8_t *desc_l, int32_t n_r,
+                                  const orbgpu_keypoint *kps_r, const uint8_t *desc_r, float mbf, float fx,
+                                  float *u_right, float *depth);
+
 /* ---- Device-resident Tracking::SearchLocalPoints (Tracking.cc:1447-1497) ----------------------------------
  * = Frame::isInFrustum (Frame.cc:269-325) + MapPoint::PredictScale (MapPoint.cc:385-394) over a MapPoint table
  * kept in HBM, followed by ORBmatcher::SearchByProjection(F, vpMapPoints, th) (ORBmatcher.cc:45-137), for a

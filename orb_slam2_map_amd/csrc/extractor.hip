@@ -14,6 +14,7 @@
 #include <type_traits>
 #include <utility>
 #include "trig_base.h"
+#include "pyramid_view.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -2213,6 +2214,7 @@ struct orbgpu_extractor {
     // device state
     DevBuf d_geom, d_cells, d_xtab, d_ytab, d_yrow, d_pattern, d_rstrip, d_rsel, d_rwt, d_ctab, d_bcol;
     DevBuf d_pyr, d_blur, d_slots, d_cellcnt, d_dkey, d_dnode, d_sel, d_nsel, d_ncand, d_aux;
+    mutable DevBuf d_stereo;  // scratch of the readers of the pyramid view (stereo.hip), created on first use
     DevBuf d_qtaux;  // k_qt_prefilter -> k_quadtree<true> (single frames): QT_AUX_FRAME ints per frame, < QT_BATCH_MIN frames
     bool qt_prefilter = false;  // every level has <= QT_INI_MAX initial nodes
     int max_slots_level = 0;
@@ -3087,6 +3089,41 @@ static int launch_pipeline(orbgpu_extractor *e, const uint8_t *d_gray, int batch
 // =============================================================================================
 // C ABI
 // =============================================================================================
+namespace orbgpu {
+
+// The pyramid of the last call as it stands: nothing is launched, synchronised or materialised (pyramid_view.h).
+int extractor_pyramid_view(const orbgpu_extractor *e, PyramidView *v)
+{
+    ORBGPU_REQUIRE(e && v, "null argument");
+    memset(v, 0, sizeof(*v));
+    v->device_id = e->prm.device_id;
+    v->nlevels = e->nlevels;
+    v->scale_factor = e->prm.scale_factor;
+    v->last_batch = (int)e->geom.size() == e->nlevels ? e->last_batch : 0;
+    for (int l = 0; l < e->nlevels; l++) {
+        v->scale[l] = e->scale[l];
+        v->inv_scale[l] = e->inv_scale[l];
+        if (v->last_batch > 0) {
+            const LevelGeom &g = e->geom[l];
+            v->w[l] = g.w;
+            v->h[l] = g.h;
+            v->pitch[l] = g.pitch;
+            v->plane_off[l] = g.plane_off;
+        }
+    }
+    v->pyr = e->d_pyr.as<uint8_t>();
+    v->frame_pyr = e->frame_pyr;
+    v->border = EDGE;
+    v->direct = v->last_batch > 0 && e->last_src.direct ? 1 : 0;
+    v->l0 = v->direct ? e->last_src.p : nullptr;
+    v->l0_frame_stride = v->direct ? e->last_src.frame_stride : 0;
+    v->l0_pitch = v->direct ? e->last_src.pitch : 0;
+    v->scratch = &e->d_stereo;
+    return ORBGPU_OK;
+}
+
+} // namespace orbgpu
+
 extern "C" {
 
 int orbgpu_extractor_create(const orbgpu_extractor_params *p, orbgpu_extractor **out)
@@ -3152,7 +3189,7 @@ int orbgpu_extractor_destroy(orbgpu_extractor *e)
     DevBuf *bufs[] = {&e->d_geom, &e->d_cells, &e->d_xtab, &e->d_ytab, &e->d_yrow, &e->d_pattern, &e->d_rstrip, &e->d_rsel,
                       &e->d_rwt, &e->d_ctab, &e->d_bcol, &e->d_pyr,
                       &e->d_blur, &e->d_slots, &e->d_cellcnt, &e->d_dkey, &e->d_dnode, &e->d_sel, &e->d_nsel,
-                      &e->d_ncand, &e->d_aux, &e->d_in, &e->d_kps, &e->d_desc, &e->d_nout, &e->d_dbg, &e->d_qtaux};
+                      &e->d_ncand, &e->d_aux, &e->d_in, &e->d_kps, &e->d_desc, &e->d_nout, &e->d_dbg, &e->d_qtaux, &e->d_stereo};
     for (DevBuf *b : bufs)
         b->release();
     for (auto &x : e->ev)

@@ -119,7 +119,8 @@ ABI_SYMBOLS = [
     "orbgpu_pipeline_extract_device", "orbgpu_pipeline_wait",
     "orbgpu_hamming256", "orbgpu_match_bf", "orbgpu_matcher_create", "orbgpu_matcher_destroy",
     "orbgpu_match_bf_batch_device", "orbgpu_matcher_last_sweeps", "orbgpu_assign_features_to_grid",
-    "orbgpu_frame_glue_batch_device", "orbgpu_undistort_points", "orbgpu_search_local_points_device", "orbgpu_search_local_points_batch_device", "orbgpu_search_by_projection_last_device", "orbgpu_projection_last_sweeps", "orbgpu_distinctive_descriptors", "orbgpu_search_by_projection_sim3",
+    "orbgpu_frame_glue_batch_device", "orbgpu_stereo_matches_batch_device", "orbgpu_compute_stereo_matches",
+    "orbgpu_undistort_points", "orbgpu_search_local_points_device", "orbgpu_search_local_points_batch_device", "orbgpu_search_by_projection_last_device", "orbgpu_projection_last_sweeps", "orbgpu_distinctive_descriptors", "orbgpu_search_by_projection_sim3",
     "orbgpu_search_by_projection", "orbgpu_search_by_projection_last", "orbgpu_search_by_projection_keyframe",
     "orbgpu_mappoint_table_create", "orbgpu_mappoint_table_destroy", "orbgpu_mappoint_table_rows",
     "orbgpu_mappoint_table_upsert", "orbgpu_mappoint_table_set_bad", "orbgpu_mappoint_table_set_observations",
@@ -194,6 +195,9 @@ def lib():
         "orbgpu_matcher_last_sweeps": [vp, vp],
         "orbgpu_assign_features_to_grid": [i32, vp, vp, f32, f32, f32, f32, vp, vp],
         "orbgpu_frame_glue_batch_device": [i32, i32, i32, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp],
+        "orbgpu_stereo_matches_batch_device": [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp,
+                                               vp],
+        "orbgpu_compute_stereo_matches": [vp, vp, i32, vp, vp, i32, vp, vp, f32, f32, vp, vp],
         "orbgpu_undistort_points": [i32, vp, vp, vp, i32],
         "orbgpu_search_local_points_device": [vp, vp, vp, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp, vp, vp, i32, vp],
         "orbgpu_projection_last_sweeps": [vp, vp],
@@ -531,6 +535,32 @@ def frame_glue_batch_device(batch, cap, d_kps, d_n, d_depth, depth_stride, depth
     check(lib().orbgpu_frame_glue_batch_device(device_id, batch, cap, d_kps, d_n, d_depth, depth_stride,
                                                depth_frame_stride, C.byref(cam), d_kps_un, d_u_right, d_kp_depth,
                                                d_cell_start, d_cell_items, stream))
+
+
+def compute_stereo_matches(left, right, kps_l, desc_l, kps_r, desc_r, mbf, fx):
+    """Frame::ComputeStereoMatches (Frame.cc:466-638) for frame 0 of the last calls of two ORBextractor handles (`left`
+    may be `right`): (mvuRight, mvDepth) as float32 arrays of len(kps_l), -1 where there is no match
+    (orbgpu_compute_stereo_matches)."""
+    kl = np.ascontiguousarray(kps_l, KEYPOINT_DTYPE)
+    kr = np.ascontiguousarray(kps_r, KEYPOINT_DTYPE)
+    dl = np.ascontiguousarray(desc_l, np.uint8).reshape(-1, 32)
+    dr = np.ascontiguousarray(desc_r, np.uint8).reshape(-1, 32)
+    if len(dl) != len(kl) or len(dr) != len(kr):
+        raise ValueError("key points and descriptors differ in count")
+    u = np.zeros(len(kl), np.float32)
+    d = np.zeros(len(kl), np.float32)
+    check(lib().orbgpu_compute_stereo_matches(left.h, right.h, len(kl), _p(kl), _p(dl), len(kr), _p(kr), _p(dr),
+                                              float(mbf), float(fx), _p(u), _p(d)))
+    return u, d
+
+
+def stereo_matches_batch_device(left, left_frame0, right, right_frame0, batch, cap, d_kps_l, d_n_l, d_desc_l, d_kps_r,
+                                d_n_r, d_desc_r, mbf, fx, d_u_right, d_depth, d_n_stereo=None, stream=0):
+    """Frame::ComputeStereoMatches for `batch` pairs of device-resident frames (orbgpu_stereo_matches_batch_device):
+    pair p = frame left_frame0 + p of `left`'s last call and frame right_frame0 + p of `right`'s."""
+    check(lib().orbgpu_stereo_matches_batch_device(left.h, left_frame0, right.h, right_frame0, batch, cap, d_kps_l, d_n_l,
+                                                   d_desc_l, d_kps_r, d_n_r, d_desc_r, float(mbf), float(fx), d_u_right,
+                                                   d_depth, d_n_stereo, stream))
 
 
 def search_local_points_device(frame_view, table, Tcw, fx, fy, cx, cy, mbf, log_sf, th, nnratio, d_kp_to_mp, d_counts,

@@ -116,6 +116,36 @@ template <typename KeyPointT> class ORBextractorT {
 };
 
 // --------------------------------------------------------------------------------------------
+// Frame::ComputeStereoMatches (reference src/Frame.cc:466-638) for the stereo constructor (Frame.cc:59-117): fills
+// F.mvuRight / F.mvDepth from F.mvKeys, F.mvKeysRight, F.mDescriptors, F.mDescriptorsRight, F.mbf and F.fx, reading
+// the pyramids of the two extractors' last calls (the ones that just extracted F's images) on the device.  mb is read
+// by the reference before the constructor assigns it (Frame.cc:90 against :114): minZ = mbf / fx here.
+// --------------------------------------------------------------------------------------------
+// descriptor rows as N x 32 contiguous bytes: a std::vector<uint8_t> or anything with a `data` pointer (cv::Mat)
+inline const uint8_t *DescriptorBytes(const std::vector<uint8_t> &d) { return d.data(); }
+template <typename MatT> auto DescriptorBytes(const MatT &m) -> decltype((const uint8_t *)m.data)
+{
+    return (const uint8_t *)m.data;
+}
+
+template <typename FrameT, typename KeyPointT>
+void ComputeStereoMatchesT(FrameT &F, ORBextractorT<KeyPointT> &left, ORBextractorT<KeyPointT> &right)
+{
+    const int32_t n = (int32_t)F.mvKeys.size(), nr = (int32_t)F.mvKeysRight.size();
+    F.mvuRight = std::vector<float>(n, -1.0f);  // Frame.cc:468-469
+    F.mvDepth = std::vector<float>(n, -1.0f);
+    if (n == 0)
+        return;
+    check(orbgpu_compute_stereo_matches(left.handle(), right.handle(), n,
+                                        reinterpret_cast<const orbgpu_keypoint *>(F.mvKeys.data()),
+                                        DescriptorBytes(F.mDescriptors), nr,
+                                        reinterpret_cast<const orbgpu_keypoint *>(F.mvKeysRight.data()),
+                                        nr ? DescriptorBytes(F.mDescriptorsRight) : nullptr, F.mbf, F.fx,
+                                        F.mvuRight.data(), F.mvDepth.data()),
+          "Frame::ComputeStereoMatches");
+}
+
+// --------------------------------------------------------------------------------------------
 // ORBVocabulary (reference include/ORBVocabulary.h: DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>)
 // The file readers (loadFromTextFile / loadFromBinaryFile) stay the reference's; after loading, hand the node arrays
 // over once (node i > 0: parent, isLeaf, descriptor row, weight -- m_nodes in index order).

@@ -134,3 +134,54 @@ class Stream:
 def random_descriptors(n, seed):
     rng = np.random.Generator(np.random.PCG64(seed))
     return rng.integers(0, 256, (n, 32), dtype=np.uint8)
+
+
+# Examples/Stereo/KITTI00-02.yaml: fx and the stereo baseline times fx (Camera.bf)
+KITTI_FX, KITTI_BF = 718.856, 386.1448
+
+
+class StereoStream:
+    """Synthetic rectified stereo sequence. frame(t) -> (left u8 HxW, right u8 HxW, disparity f64 HxW).
+
+    The left image is a window of a textured canvas (the Stream canvas of a wider image); the right image samples the
+    same canvas at x + d(x, y) with linear interpolation, so that the point seen at column u on the left is seen at
+    u - d on the right, with sub-pixel disparities.  d = bf / Z for a smooth depth field Z in [zmin, zmax] metres.
+    A rectangle of the right image (`patch` of its width and height) shows unrelated texture instead: its key points
+    have no true counterpart, which gives the descriptor search wrong matches and the median cut something to remove.
+    Each image has its own +-3 sensor noise.  The camera scales KITTI's (fx, bf) with the width."""
+
+    def __init__(self, width=1241, height=376, seed=1234, zmin=6.0, zmax=60.0, patch=0.25):
+        self.w, self.h, self.seed = width, height, seed
+        s = width / 1241.0
+        self.fx = np.float32(KITTI_FX * s)
+        self.bf = np.float32(KITTI_BF * s)
+        self.dmax = float(self.bf) / zmin
+        self.extra = int(np.ceil(self.dmax)) + 2
+        base = Stream(width + self.extra, height, seed)
+        self.canvas = base.canvas
+        rng = np.random.Generator(np.random.PCG64([seed, 31337]))
+        ch, cw = self.canvas.shape
+        self.depth_canvas = zmin + (zmax - zmin) * _value_noise(rng, ch, cw, 192)
+        other = Stream(width, height, seed + 7777)
+        self.other = other.canvas
+        pw, ph = int(width * patch), int(height * patch)
+        self.patch_box = (int(rng.integers(0, max(1, width - pw))), int(rng.integers(0, max(1, height - ph))), pw, ph)
+
+    def offset(self, t):
+        return _tri(5 * t, MARGIN), _tri(3 * t + 17, MARGIN)
+
+    def frame(self, t):
+        ox, oy = self.offset(t)
+        rng = np.random.Generator(np.random.PCG64([self.seed, 7919, t]))
+        left = self.canvas[oy:oy + self.h, ox:ox + self.w] + rng.integers(-3, 4, (self.h, self.w))
+        disp = float(self.bf) / self.depth_canvas[oy:oy + self.h, ox:ox + self.w]
+        xs = np.arange(self.w)[None, :] + ox + disp
+        x0 = np.floor(xs).astype(np.int64)
+        fr = xs - x0
+        rows = np.arange(self.h)[:, None] + oy
+        right = self.canvas[rows, x0] * (1.0 - fr) + self.canvas[rows, x0 + 1] * fr
+        px, py, pw, ph = self.patch_box
+        right[py:py + ph, px:px + pw] = self.other[oy + py:oy + py + ph, ox + px:ox + px + pw]
+        right = right + rng.integers(-3, 4, (self.h, self.w))
+        to8 = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)
+        return to8(left), to8(right), disp
