@@ -577,6 +577,78 @@ int orbgpu_search_by_projection_last_table(const orbgpu_frame *cur, const float 
                                            float cx, float cy, float mbf, float mb, float th, int32_t mono,
                                            int32_t check_orientation, int32_t *kp_to_mp, int32_t *nmatches);
 
+/* ---- Optimizer::PoseOptimization (Optimizer.cc:239-451): motion-only bundle adjustment on the device --------------------
+ * The step Tracking runs between SearchByProjection(Cur, Last) and SearchLocalPoints and again after it (Tracking.cc:1182,
+ * :1059, :1224, :1744-1775): one 6-DoF pose, one unary reprojection edge per key point that holds a map point.  g2o is not
+ * part of the reference tree: its behaviour is restated, NOT read ("g2o unpinned"); tests/pose_model.py is the float64
+ * restatement every result is compared with.  The definition, all in IEEE double unless a float is named:
+ *   set-up (:253-365)   edge iff kp_to_mp[i] >= 0; mono iff mvuRight[i] < 0 (2 residuals, Huber delta (float)sqrt(5.991)),
+ *                       else stereo (3 residuals, delta (float)sqrt(7.815)); information = (double)mvInvLevelSigma2[octave];
+ *                       pose in as Converter::toSE3Quat (Converter.cc:37-47), out as Converter::toCvMat (:49-71); every
+ *                       edge gets mvbOutlier = false; fewer than 3 edges: returns 0, pose untouched
+ *   error               (x, y, z) = R Xw + t;  e = obs - (fx x/z + cx, fy y/z + cy[, fx x/z + cx - bf/z]);
+ *                       chi2 = invSigma2 e'e; no depth-sign test; non-finite values follow IEEE through the steps below
+ *   Jacobian            d e / d (omega, upsilon) of the left update T <- exp(omega, upsilon) T at zero
+ *   optimize(10)        Levenberg-Marquardt on the level-0 edges: H = sum J'(rho1 W)J, b = -sum J'(rho1 W)e with Huber rho
+ *                       (no second-order term); lambda0 = 1e-5 max diag H, nu = 2; per iteration at most 10 trials of
+ *                       (H + lambda I) x = b by Cholesky (not positive definite: the trial fails), T' = exp(x) T,
+ *                       rho = (chi - chi') / (x'(lambda x + b) + 1e-3); accepted iff rho > 0 and chi' finite
+ *                       (lambda *= max(1/3, min(1 - (2 rho - 1)^3, 2/3)), nu = 2), else lambda *= nu, nu *= 2; the
+ *                       iteration's trials end when rho >= 0; optimize ends after 10 iterations, 10 failed trials in a
+ *                       row, rho == 0 or a non-finite lambda
+ *   four rounds (:369-442)  each restarts from the input pose, optimises, then classifies EVERY edge: (float)chi2 >
+ *                       5.991f (mono) / 7.815f (stereo) -> outlier, left out of the next round; after the third round
+ *                       the Huber kernel is dropped; fewer than 10 edges in total: one round only
+ * Two conventions where g2o is loose: (1) an edge is classified at the round's final, KEPT pose (g2o uses the error it
+ * computed last, which after a rejected final trial belongs to the discarded pose); (2) rho at convergence is rounding
+ * noise, so the sums' order can decide a trial: sums over edges run in a fixed order (per-lane partial sums, then a fixed
+ * tree; no floating-point atomics) -- the same problem gives the same bits on every run, alone or anywhere in a batch,
+ * and agrees with the model to a tolerance, not bit for bit. */
+typedef struct orbgpu_pose_result { /* device or host, 8-byte aligned */
+    double Tcw_d[16];    /* the optimised pose before Converter::toCvMat, row-major homogeneous */
+    float Tcw[16];       /* = (float) of Tcw_d entry by entry: what Frame::SetPose receives */
+    int32_t n_initial;   /* nInitialCorrespondences */
+    int32_t n_inliers;   /* the return value (0 and pose = input when n_initial < 3) */
+    int32_t rounds, iterations, trials; /* diagnostics: rounds run, LM iterations, LM trials over all rounds */
+    int32_t n_bad_index; /* edges whose kp_to_mp row or octave was out of range: skipped, reported */
+} orbgpu_pose_result;
+
+typedef struct orbgpu_pose_problem {
+    const orbgpu_device_frame_view *frame; /* cap, n, kps = mvKeysUn (pt, octave), u_right = mvuRight, nlevels; the
+                                              grid, descriptors, scale factors and bounds are not read */
+    const int32_t *d_kp_to_mp;             /* device [cap]: >= 0 row of d_world_pos, < 0 no edge */
+    const float *d_world_pos;              /* device [rows][3]: table / last-frame world_pos as the matchers take them */
+    int32_t rows;
+    const float *Tcw;                      /* HOST 4x4 row-major float: mTcw on entry */
+    const float *inv_level_sigma2;         /* HOST [frame->nlevels]: mvInvLevelSigma2 */
+    float fx, fy, cx, cy, mbf;
+    uint8_t *d_outlier;                    /* device [cap]: mvbOutlier, written for edges only */
+    orbgpu_pose_result *d_result;          /* device */
+} orbgpu_pose_problem;
+
+/* Enqueued on hip_stream, not synchronised; the host arrays (pose, sigma table) are read before the call returns.  Calls
+ * of one host thread share a workspace and must be ordered on one stream.  EINVAL: null pointers, n < 0, cap outside
+ * [0, 16384], nlevels outside [1, ORBGPU_MAX_LEVELS]; EHIP without a device.  A kp_to_mp row >= rows or an octave outside
+ * [0, nlevels) (both undefined reads in the reference) is never read through: the edge is skipped and counted in
+ * n_bad_index.  The batch form is ONE launch, one workgroup per problem. */
+int orbgpu_pose_optimization_device(const orbgpu_pose_problem *p, int32_t device_id, void *hip_stream);
+int orbgpu_pose_optimization_batch_device(int32_t n, const orbgpu_pose_problem *problems, int32_t device_id,
+                                          void *hip_stream);
+/* Host arrays, synchronises: has_mp [n], world_pos [n][3] per key point; Tcw in/out; outlier [n] in/out (written for
+ * edges only); result may be NULL. */
+int orbgpu_pose_optimization(const orbgpu_frame_view *f, const uint8_t *has_mp, const float *world_pos, float *Tcw,
+                             const float *inv_level_sigma2, float fx, float fy, float cx, float cy, float mbf,
+                             uint8_t *outlier, int32_t *n_inliers, orbgpu_pose_result *result, int32_t device_id);
+/* Over the MapPoint table and an uploaded frame: kp_ids [n] = mnId of F.mvpMapPoints[j] or -1; ids the table does not
+ * know are not edges and are counted through orbgpu_mappoint_table_last_unknown, like the search calls.  Synchronises. */
+int orbgpu_pose_optimization_table(const orbgpu_frame *fr, orbgpu_mappoint_table *t, const int64_t *kp_ids, float *Tcw,
+                                   const float *inv_level_sigma2, float fx, float fy, float cx, float cy, float mbf,
+                                   uint8_t *outlier, int32_t *n_inliers, orbgpu_pose_result *result);
+/* Diagnostic: problems of the calling thread's most recent pose optimisation on device_id whose edges did not fit the
+ * workgroup's LDS and went through the global-memory spill (ORBGPU_DEBUG_POSE_LDS_EDGES=<k> lowers the limit for tests).
+ * Synchronises the device. */
+int orbgpu_pose_last_spills(int32_t device_id, int32_t *problems_spilled);
+
 
 /* LastFrame members read by SearchByProjection(CurrentFrame, LastFrame, th, bMono). */
 typedef struct {

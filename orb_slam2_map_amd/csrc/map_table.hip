@@ -1058,4 +1058,59 @@ int orbgpu_search_by_projection_last_table(const orbgpu_frame *cur, const float 
     return ORBGPU_OK;
 }
 
+// Optimizer::PoseOptimization over the table: the frame's associations arrive as ids, the id -> row lookup runs on the
+// host copy of the hash (n <= cap key points), the world positions are the table's own column (pose_opt.hip).
+int orbgpu_pose_optimization_table(const orbgpu_frame *fr, orbgpu_mappoint_table *t, const int64_t *kp_ids, float *Tcw,
+                                   const float *inv_level_sigma2, float fx, float fy, float cx, float cy, float mbf,
+                                   uint8_t *outlier, int32_t *n_inliers, orbgpu_pose_result *result)
+{
+    ORBGPU_REQUIRE(fr && t && Tcw && inv_level_sigma2 && n_inliers, "null argument");
+    ORBGPU_REQUIRE(fr->block.p, "the frame has not been uploaded yet");
+    ORBGPU_REQUIRE(fr->device_id == t->device_id, "frame and table live on different devices");
+    ORBGPU_REQUIRE(fr->n == 0 || (kp_ids && outlier), "null arrays");
+    int rc = select_device(t->device_id);
+    if (rc != ORBGPU_OK)
+        return rc;
+    const int n = fr->n, cap = fr->cap;
+    Carver c;
+    const size_t o_k2m = c.take(4 * (size_t)std::max(cap, 1)), o_out = c.take((size_t)std::max(cap, 1));
+    const size_t o_res = c.take(sizeof(orbgpu_pose_result));
+    if ((rc = t->stage.reserve(c.off)) != ORBGPU_OK || (rc = t->d_stage.reserve(c.off)) != ORBGPU_OK)
+        return rc;
+    uint8_t *h = (uint8_t *)t->stage.p, *d = t->d_stage.as<uint8_t>();
+    int32_t *k2m = (int32_t *)(h + o_k2m);
+    int unknown = 0;
+    for (int j = 0; j < n; j++) {
+        k2m[j] = kp_ids[j] >= 0 ? host_find(t, kp_ids[j]) : -1;
+        unknown += kp_ids[j] >= 0 && k2m[j] < 0;
+    }
+    if (n > 0)
+        std::memcpy(h + o_out, outlier, (size_t)n);
+    t->last_unknown_list = 0, t->last_unknown_kp = unknown;
+    hipStream_t st = t->stream;
+    ORBGPU_HIP_TRY(hipMemcpyAsync(d, h, o_res, hipMemcpyHostToDevice, st));
+    orbgpu_device_frame_view fv;
+    frame_dev_view(fr, &fv);
+    orbgpu_pose_problem p{};
+    p.frame = &fv, p.d_kp_to_mp = (const int32_t *)(d + o_k2m), p.d_world_pos = t->world_pos.as<float>(), p.rows = t->rows;
+    p.Tcw = Tcw, p.inv_level_sigma2 = inv_level_sigma2;
+    p.fx = fx, p.fy = fy, p.cx = cx, p.cy = cy, p.mbf = mbf;
+    p.d_outlier = d + o_out, p.d_result = (orbgpu_pose_result *)(d + o_res);
+    if ((rc = orbgpu_pose_optimization_device(&p, t->device_id, st)) != ORBGPU_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    ORBGPU_HIP_TRY(hipMemcpyAsync(h + o_out, d + o_out, c.off - o_out, hipMemcpyDeviceToHost, st));
+    ORBGPU_HIP_TRY(hipStreamSynchronize(st));
+    orbgpu_pose_result r;
+    std::memcpy(&r, h + o_res, sizeof(r));
+    if (n > 0)
+        std::memcpy(outlier, h + o_out, (size_t)n);
+    std::memcpy(Tcw, r.Tcw, sizeof(r.Tcw));
+    *n_inliers = r.n_inliers;
+    if (result)
+        *result = r;
+    return ORBGPU_OK;
+}
+
 } // extern "C"

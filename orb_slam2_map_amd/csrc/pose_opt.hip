@@ -1,0 +1,737 @@
+// Optimizer::PoseOptimization (Optimizer.cc:239-451) on the device: motion-only bundle adjustment of ONE pose over
+// N unary reprojection edges.  One workgroup per problem runs all four rounds and every Levenberg-Marquardt trial
+// without returning to the host; the definition (g2o restated, "g2o unpinned") is in include/orbgpu.h and
+// tests/pose_model.py.  FP64 throughout, no fused multiply-add (-ffp-contract=off): the per-edge arithmetic is the
+// model's operation for operation, only the order of the sums over edges differs (fixed tree here, sequential there).
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "common.h"
+#include "workspace.h"
+
+namespace orbgpu {
+
+constexpr int PO_THREADS = 256;               // 4 waves: a first guess (DESIGN.md "Pose optimisation"), not a tuned shape
+constexpr int PO_WAVES = PO_THREADS / 64;
+constexpr int PO_LDS_EDGES = 1536;            // 32 B per edge -> 48 KiB of LDS; more edges go through the global spill
+constexpr int PO_SUMS = 28;                   // 21 of symmetric H, 6 of b, 1 robust chi2
+constexpr unsigned PO_STEREO = 1u << 30, PO_LEVEL1 = 1u << 31, PO_KP_MASK = (1u << 24) - 1;
+
+struct PoseProblemDev {
+    const int32_t *n;
+    const orbgpu_keypoint *kps;
+    const float *u_right;
+    const int32_t *kp_to_mp;
+    const float *world_pos;
+    uint8_t *outlier;
+    orbgpu_pose_result *result;
+    float4 *spill;        // [2 * cap], or nullptr when cap <= lds_edges
+    int32_t *spill_count; // problems of this call that took the spill path (diagnostic)
+    int32_t cap, rows, nlevels, lds_edges;
+    float inv_sigma2[ORBGPU_MAX_LEVELS];
+    float Tcw[16];
+    double q0[4], t0[3];  // Converter::toSE3Quat(mTcw)
+    double fx, fy, cx, cy, bf;
+    double delta[2], delta2[2];  // Huber delta (mono, stereo) and its square
+};
+
+struct Cam {
+    double fx, fy, cx, cy, bf;
+};
+
+// ---- SE3Quat (quaternion as x, y, z, w) ------------------------------------------------------------------------------
+__host__ __device__ inline void quat_from_matrix(const double m[9], double q[4])
+{
+    double t = m[0] + m[4] + m[8];
+    if (t > 0) {
+        t = sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[7] - m[5]) * t;
+        q[1] = (m[2] - m[6]) * t;
+        q[2] = (m[3] - m[1]) * t;
+    } else {
+        int i = 0;
+        if (m[4] > m[0])
+            i = 1;
+        if (m[8] > m[4 * i])
+            i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
+        q[i] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
+        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
+        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
+    }
+}
+
+__host__ __device__ inline void quat_normalize(double q[4])
+{
+    if (q[3] < 0)
+        for (int i = 0; i < 4; i++)
+            q[i] = -q[i];
+    const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    for (int i = 0; i < 4; i++)
+        q[i] = q[i] / n;
+}
+
+__host__ __device__ inline void quat_to_matrix(const double q[4], double R[9])
+{
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+    const double twx = tx * w, twy = ty * w, twz = tz * w;
+    const double txx = tx * x, txy = ty * x, txz = tz * x;
+    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    R[0] = 1.0 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
+    R[3] = txy + twz, R[4] = 1.0 - (txx + tzz), R[5] = tyz - twx;
+    R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1.0 - (txx + tyy);
+}
+
+__device__ inline void quat_mul(const double a[4], const double b[4], double o[4])
+{
+    o[0] = ((a[3] * b[0] + a[0] * b[3]) + a[1] * b[2]) - a[2] * b[1];
+    o[1] = ((a[3] * b[1] + a[1] * b[3]) + a[2] * b[0]) - a[0] * b[2];
+    o[2] = ((a[3] * b[2] + a[2] * b[3]) + a[0] * b[1]) - a[1] * b[0];
+    o[3] = ((a[3] * b[3] - a[0] * b[0]) - a[1] * b[1]) - a[2] * b[2];
+}
+
+// T' = exp(x) * T with x = (omega, upsilon): SE3Quat::exp (its small-angle branch kept as is) and operator*
+__device__ inline void pose_update(const double q[4], const double t[3], const double x[6], double qn[4], double tn[3])
+{
+    const double w0 = x[0], w1 = x[1], w2 = x[2];
+    const double th = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
+    const double O[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
+    double O2[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            O2[3 * r + c] = (O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c]) + O[3 * r + 2] * O[6 + c];
+    double R[9], V[9];
+    if (th < 1e-5) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+            R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + O[i]) + O2[i];
+            V[i] = R[i];
+        }
+    } else {
+        const double sn = sin(th), cs = cos(th);
+        const double a = sn / th, b = (1.0 - cs) / (th * th), c = (th - sn) / ((th * th) * th);
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+            const double I = i % 4 == 0 ? 1.0 : 0.0;
+            R[i] = (I + a * O[i]) + b * O2[i];
+            V[i] = (I + b * O[i]) + c * O2[i];
+        }
+    }
+    double dq[4], dR[9];
+    quat_from_matrix(R, dq);
+    quat_normalize(dq);
+    quat_mul(dq, q, qn);
+    quat_normalize(qn);
+    quat_to_matrix(dq, dR);
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        const double dt = (V[3 * r] * x[3] + V[3 * r + 1] * x[4]) + V[3 * r + 2] * x[5];
+        tn[r] = ((dR[3 * r] * t[0] + dR[3 * r + 1] * t[1]) + dR[3 * r + 2] * t[2]) + dt;
+    }
+}
+
+// ---- one edge ----------------------------------------------------------------------------------------------------
+// e = obs - projection (third component 0 for a mono edge), P = R Xw + t, returns chi2 = invSigma2 * e'e
+__device__ inline double edge_error(const double R[9], const double t[3], const Cam &C, const float4 a, const float4 b,
+                                    bool stereo, double e[3], double P[3])
+{
+    const double X0 = (double)a.x, X1 = (double)a.y, X2 = (double)a.z, w = (double)a.w;
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+        P[r] = ((R[3 * r] * X0 + R[3 * r + 1] * X1) + R[3 * r + 2] * X2) + t[r];
+    const double iz = 1.0 / P[2];
+    const double u = (C.fx * P[0]) * iz + C.cx;
+    e[0] = (double)b.x - u;
+    e[1] = (double)b.y - ((C.fy * P[1]) * iz + C.cy);
+    e[2] = stereo ? (double)b.z - (u - C.bf * iz) : 0.0;
+    return w * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+}
+
+// RobustKernelHuber without the second-order term; an edge without kernel keeps chi2
+__device__ inline void huber(double chi2, double delta, double delta2, bool use_kernel, double &rho0, double &rho1)
+{
+    if (chi2 <= delta2 || !use_kernel) {
+        rho0 = chi2;
+        rho1 = 1.0;
+    } else {
+        const double s = sqrt(chi2);
+        rho0 = (2.0 * s) * delta - delta2;
+        rho1 = delta / s;
+    }
+}
+
+// Fixed-order sum over the workgroup: shuffle tree inside each wave, then wave 0 + 1 + 2 + 3 in every lane.  The result
+// is the same bits in every lane, so control flow that branches on it stays workgroup-uniform.
+template <int K> __device__ inline void block_sum(double (&v)[K], double *red)
+{
+#pragma unroll
+    for (int k = 0; k < K; k++)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1)
+            v[k] += __shfl_down(v[k], off, 64);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();  // the previous sum's readers are done with `red`
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < K; k++)
+            red[wave * K + k] = v[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        double s = red[k];
+#pragma unroll
+        for (int wv = 1; wv < PO_WAVES; wv++)
+            s += red[wv * K + k];
+        v[k] = s;
+    }
+}
+
+// (H + lam I) x = b by LL^T; not positive definite (a pivot that is not > 0, NaN included): false and x = 0
+__device__ inline bool cholesky_solve6(const double Hu[21], double lam, const double b[6], double x[6])
+{
+    double A[6][6], L[6][6];
+    {
+        int k = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int c = a; c < 6; c++, k++)
+                A[a][c] = A[c][a] = Hu[k];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        A[i][i] = A[i][i] + lam;
+#pragma unroll
+        for (int j = 0; j < 6; j++)
+            L[i][j] = 0.0;
+        x[i] = 0.0;
+    }
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double d = A[j][j];
+#pragma unroll
+        for (int k = 0; k < j; k++)
+            d = d - L[j][k] * L[j][k];
+        if (!(d > 0.0))
+            ok = false;
+        d = sqrt(d);
+        L[j][j] = d;
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            double s = A[j][i];
+#pragma unroll
+            for (int k = 0; k < j; k++)
+                s = s - L[i][k] * L[j][k];
+            L[i][j] = s / d;
+        }
+    }
+    if (!ok)
+        return false;
+    double y[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        double s = b[i];
+#pragma unroll
+        for (int k = 0; k < i; k++)
+            s = s - L[i][k] * y[k];
+        y[i] = s / L[i][i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; i--) {
+        double s = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; k++)
+            s = s - L[k][i] * x[k];
+        x[i] = s / L[i][i];
+    }
+    return true;
+}
+
+// key point i is an edge (1), has an out-of-range row / octave (2), or holds no map point (0)
+__device__ inline int edge_kind(const PoseProblemDev &P, int i, int n)
+{
+    if (i >= n)
+        return 0;
+    const int r = P.kp_to_mp[i];
+    if (r < 0)
+        return 0;
+    const int o = P.kps[i].octave;
+    return (r >= P.rows || o < 0 || o >= P.nlevels) ? 2 : 1;
+}
+
+__global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblemDev *__restrict__ problems)
+{
+    __shared__ float4 lds_edges[2 * PO_LDS_EDGES];
+    __shared__ double red[PO_WAVES * PO_SUMS];
+    __shared__ int wcount[PO_WAVES][2];
+    __shared__ int icount;
+    const PoseProblemDev &P = problems[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(max(*P.n, 0), P.cap);
+    const Cam C{P.fx, P.fy, P.cx, P.cy, P.bf};
+
+    // pass 1: count the edges (decides LDS or spill) and the skipped ones
+    int ne = 0, nbadidx = 0;
+    for (int base = 0; base < n; base += PO_THREADS) {
+        const int kind = edge_kind(P, base + tid, n);
+        const unsigned long long m1 = __ballot(kind == 1), m2 = __ballot(kind == 2);
+        __syncthreads();
+        if (lane == 0)
+            wcount[wave][0] = __popcll(m1), wcount[wave][1] = __popcll(m2);
+        __syncthreads();
+#pragma unroll
+        for (int wv = 0; wv < PO_WAVES; wv++)
+            ne += wcount[wv][0], nbadidx += wcount[wv][1];
+    }
+    orbgpu_pose_result *res = P.result;
+    // ne <= cap, and the host gives every problem with cap > lds_edges a spill block of 2 * cap records
+    const bool spilled = ne > P.lds_edges;
+    float4 *E = spilled ? P.spill : lds_edges;
+
+    // pass 2: compact the edges in key-point order; all edges get mvbOutlier = false (Optimizer.cc:281, :318)
+    {
+        int at = 0;
+        for (int base = 0; base < n; base += PO_THREADS) {
+            const int i = base + tid;
+            const bool is_edge = edge_kind(P, i, n) == 1;
+            const unsigned long long m1 = __ballot(is_edge);
+            __syncthreads();
+            if (lane == 0)
+                wcount[wave][0] = __popcll(m1);
+            __syncthreads();
+            int before = 0, total = 0;
+#pragma unroll
+            for (int wv = 0; wv < PO_WAVES; wv++) {
+                before += wv < wave ? wcount[wv][0] : 0;
+                total += wcount[wv][0];
+            }
+            if (is_edge) {
+                const int e = at + before + __popcll(m1 & ((1ull << lane) - 1ull));
+                const orbgpu_keypoint kp = P.kps[i];
+                const float *X = P.world_pos + 3 * (size_t)P.kp_to_mp[i];
+                const float ur = P.u_right[i];
+                const unsigned bits = (unsigned)i | (ur < 0.f ? 0u : PO_STEREO);
+                E[2 * e] = make_float4(X[0], X[1], X[2], P.inv_sigma2[kp.octave]);
+                E[2 * e + 1] = make_float4(kp.x, kp.y, ur, __uint_as_float(bits));
+                P.outlier[i] = 0;
+            }
+            at += total;
+        }
+    }
+    __syncthreads();
+
+    if (ne < 3) {  // Optimizer.cc:365-366: return 0, pose untouched
+        if (tid == 0) {
+            for (int i = 0; i < 16; i++) {
+                res->Tcw[i] = P.Tcw[i];
+                res->Tcw_d[i] = (double)P.Tcw[i];
+            }
+            res->n_initial = ne, res->n_inliers = 0, res->rounds = 0, res->iterations = 0, res->trials = 0;
+            res->n_bad_index = nbadidx;
+        }
+        return;
+    }
+    if (tid == 0 && spilled)
+        atomicAdd(P.spill_count, 1);
+
+    // Everything below that steers control flow (lam, nu, rho, the pose, the counters) is computed redundantly by every
+    // lane from block_sum results, hence workgroup-uniform: the barriers inside the loops are reached by all lanes.
+    // Trip counts are bounded by the constants of the definition: 4 rounds x 10 iterations x 10 trials.
+    double q[4], t[3], R[9];
+    int rounds = 0, iterations = 0, trials = 0, n_bad = 0;
+    bool use_kernel = true;
+    for (int rnd = 0; rnd < 4; rnd++) {
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            q[i] = P.q0[i];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+            t[i] = P.t0[i];  // Optimizer.cc:377: every round restarts from the input pose
+        double lam = 0.0, nu = 2.0;
+        for (int it = 0; it < 10; it++) {
+            // errors, robust chi2 and the normal equation at the current pose
+            quat_to_matrix(q, R);
+            double acc[PO_SUMS];
+#pragma unroll
+            for (int k = 0; k < PO_SUMS; k++)
+                acc[k] = 0.0;
+            for (int e = tid; e < ne; e += PO_THREADS) {
+                const float4 ea = E[2 * e], eb = E[2 * e + 1];
+                const unsigned bits = __float_as_uint(eb.w);
+                if (bits & PO_LEVEL1)
+                    continue;
+                const bool stereo = bits & PO_STEREO;
+                double er[3], Pc[3];
+                const double chi2 = edge_error(R, t, C, ea, eb, stereo, er, Pc);
+                double rho0, rho1;
+                huber(chi2, P.delta[stereo], P.delta2[stereo], use_kernel, rho0, rho1);
+                const double x = Pc[0], y = Pc[1], z = Pc[2];
+                const double iz = 1.0 / z, iz2 = iz * iz;
+                double J[3][6];
+                J[0][0] = ((x * y) * iz2) * C.fx;
+                J[0][1] = -(1.0 + (x * x) * iz2) * C.fx;
+                J[0][2] = (y * iz) * C.fx;
+                J[0][3] = -iz * C.fx;
+                J[0][4] = 0.0;
+                J[0][5] = (x * iz2) * C.fx;
+                J[1][0] = (1.0 + (y * y) * iz2) * C.fy;
+                J[1][1] = -((x * y) * iz2) * C.fy;
+                J[1][2] = -(x * iz) * C.fy;
+                J[1][3] = 0.0;
+                J[1][4] = -iz * C.fy;
+                J[1][5] = (y * iz2) * C.fy;
+                if (stereo) {
+                    J[2][0] = J[0][0] - (C.bf * y) * iz2;
+                    J[2][1] = J[0][1] + (C.bf * x) * iz2;
+                    J[2][2] = J[0][2];
+                    J[2][3] = J[0][3];
+                    J[2][4] = 0.0;
+                    J[2][5] = J[0][5] - C.bf * iz2;
+                } else {
+#pragma unroll
+                    for (int a = 0; a < 6; a++)
+                        J[2][a] = 0.0;
+                }
+                const double s = (double)ea.w * rho1;
+                double Jw[3][6];
+#pragma unroll
+                for (int r = 0; r < 3; r++)
+#pragma unroll
+                    for (int a = 0; a < 6; a++)
+                        Jw[r][a] = J[r][a] * s;
+                int k = 0;
+#pragma unroll
+                for (int a = 0; a < 6; a++)
+#pragma unroll
+                    for (int c = a; c < 6; c++, k++)
+                        acc[k] += (Jw[0][a] * J[0][c] + Jw[1][a] * J[1][c]) + Jw[2][a] * J[2][c];
+#pragma unroll
+                for (int a = 0; a < 6; a++)
+                    acc[21 + a] += -((Jw[0][a] * er[0] + Jw[1][a] * er[1]) + Jw[2][a] * er[2]);
+                acc[27] += rho0;
+            }
+            block_sum<PO_SUMS>(acc, red);
+            double Hu[21], b[6];
+#pragma unroll
+            for (int k = 0; k < 21; k++)
+                Hu[k] = acc[k];
+#pragma unroll
+            for (int a = 0; a < 6; a++)
+                b[a] = acc[21 + a];
+            if (it == 0) {
+                double m = 0.0;
+                const int diag[6] = {0, 6, 11, 15, 18, 20};
+#pragma unroll
+                for (int a = 0; a < 6; a++)
+                    if (fabs(Hu[diag[a]]) > m)
+                        m = fabs(Hu[diag[a]]);
+                lam = 1e-5 * m;
+                nu = 2.0;
+            }
+            double cur = acc[27], rho = 0.0;
+            int trial = 0;
+            bool stop = false;
+            iterations++;
+            do {
+                double x[6], qn[4], tn[3], Rn[9];
+                const bool ok = cholesky_solve6(Hu, lam, b, x);
+                pose_update(q, t, x, qn, tn);
+                quat_to_matrix(qn, Rn);
+                double part[1] = {0.0};
+                for (int e = tid; e < ne; e += PO_THREADS) {
+                    const float4 ea = E[2 * e], eb = E[2 * e + 1];
+                    const unsigned bits = __float_as_uint(eb.w);
+                    if (bits & PO_LEVEL1)
+                        continue;
+                    const bool stereo = bits & PO_STEREO;
+                    double er[3], Pc[3], rho0, rho1;
+                    const double chi2 = edge_error(Rn, tn, C, ea, eb, stereo, er, Pc);
+                    huber(chi2, P.delta[stereo], P.delta2[stereo], use_kernel, rho0, rho1);
+                    part[0] += rho0;
+                }
+                block_sum<1>(part, red);
+                const double tmp = ok ? part[0] : DBL_MAX;
+                double scale = 0.0;
+#pragma unroll
+                for (int a = 0; a < 6; a++)
+                    scale = scale + x[a] * (lam * x[a] + b[a]);
+                scale = scale + 1e-3;
+                rho = (cur - tmp) / scale;
+                trials++;
+                if (rho > 0 && isfinite(tmp)) {
+                    const double c = 2.0 * rho - 1.0;
+                    const double alpha = fmin(1.0 - (c * c) * c, 2.0 / 3.0);
+                    lam = lam * fmax(1.0 / 3.0, alpha);
+                    nu = 2.0;
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        q[i] = qn[i];
+#pragma unroll
+                    for (int i = 0; i < 3; i++)
+                        t[i] = tn[i];
+                    cur = tmp;
+                } else {
+                    lam = lam * nu;
+                    nu = nu * 2.0;
+                    if (!isfinite(lam))
+                        stop = true;
+                }
+                trial++;
+            } while (!stop && rho < 0 && trial < 10);
+            if (trial == 10 || rho == 0 || stop)
+                break;
+        }
+        // classification at the round's final pose (Optimizer.cc:384-437)
+        quat_to_matrix(q, R);
+        __syncthreads();
+        if (tid == 0)
+            icount = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int e = tid; e < ne; e += PO_THREADS) {
+            const float4 ea = E[2 * e];
+            float4 eb = E[2 * e + 1];
+            unsigned bits = __float_as_uint(eb.w);
+            const bool stereo = bits & PO_STEREO;
+            double er[3], Pc[3];
+            const double chi2 = edge_error(R, t, C, ea, eb, stereo, er, Pc);
+            const bool out = (float)chi2 > (stereo ? 7.815f : 5.991f);
+            bits = out ? (bits | PO_LEVEL1) : (bits & ~PO_LEVEL1);
+            eb.w = __uint_as_float(bits);
+            E[2 * e + 1] = eb;
+            P.outlier[bits & PO_KP_MASK] = out ? 1 : 0;
+            mine += out ? 1 : 0;
+        }
+        mine = wave_reduce_add(mine);
+        if (lane == 0 && mine)
+            atomicAdd(&icount, mine);
+        __syncthreads();
+        n_bad = icount;
+        rounds = rnd + 1;
+        if (rnd == 2)
+            use_kernel = false;
+        if (ne < 10)  // optimizer.edges().size() < 10: the total, not the active ones (Optimizer.cc:439)
+            break;
+    }
+    if (tid == 0) {
+        quat_to_matrix(q, R);
+        const double T[16] = {R[0], R[1], R[2], t[0], R[3], R[4], R[5], t[1], R[6], R[7], R[8], t[2], 0.0, 0.0, 0.0, 1.0};
+        for (int i = 0; i < 16; i++) {
+            res->Tcw_d[i] = T[i];
+            res->Tcw[i] = (float)T[i];
+        }
+        res->n_initial = ne, res->n_inliers = ne - n_bad, res->rounds = rounds, res->iterations = iterations;
+        res->trials = trials, res->n_bad_index = nbadidx;
+    }
+}
+
+// Per (thread, device) staging of the entry points, like the matchers' workspaces (workspace.h).
+struct PoseWs {
+    int device = -1;
+    hipStream_t stream = nullptr;  // host flavour only
+    DevBuf problems, spill, spill_count;
+    DevBuf h_kps, h_ur, h_k2m, h_wp, h_n, h_out, h_res;  // host flavour: the uploaded problem
+    ~PoseWs()
+    {
+        if (device >= 0 && !process_exiting().load()) {
+            (void)hipSetDevice(device);
+            if (stream) {
+                (void)hipStreamSynchronize(stream);
+                (void)hipStreamDestroy(stream);
+            }
+            DevBuf *bufs[] = {&problems, &spill, &spill_count, &h_kps, &h_ur, &h_k2m, &h_wp, &h_n, &h_out, &h_res};
+            for (DevBuf *b : bufs)
+                b->release();
+        }
+    }
+};
+
+static int lds_edge_limit()
+{
+    // ORBGPU_DEBUG_POSE_LDS_EDGES=<k> (tests): problems with more than k edges take the global spill path
+    const char *s = getenv("ORBGPU_DEBUG_POSE_LDS_EDGES");
+    if (!s)
+        return PO_LDS_EDGES;
+    return std::min(std::max(atoi(s), 0), PO_LDS_EDGES);
+}
+
+static int check_problem(const orbgpu_pose_problem &p, int k)
+{
+    ORBGPU_REQUIRE(p.frame && p.d_kp_to_mp && p.Tcw && p.inv_level_sigma2 && p.d_outlier && p.d_result,
+                   "problem %d: null argument", k);
+    const orbgpu_device_frame_view *f = p.frame;
+    ORBGPU_REQUIRE(f->cap >= 0 && f->cap <= 16384, "problem %d: frame capacity out of range (max 16384)", k);
+    ORBGPU_REQUIRE(f->nlevels >= 1 && f->nlevels <= ORBGPU_MAX_LEVELS, "problem %d: nlevels outside [1, %d]", k,
+                   ORBGPU_MAX_LEVELS);
+    ORBGPU_REQUIRE(f->n && (f->cap == 0 || (f->kps && f->u_right)), "problem %d: null frame arrays", k);
+    ORBGPU_REQUIRE(p.rows >= 0 && (p.rows == 0 || p.d_world_pos), "problem %d: bad map point rows", k);
+    return ORBGPU_OK;
+}
+
+} // namespace orbgpu
+
+using namespace orbgpu;
+
+extern "C" int orbgpu_pose_optimization_batch_device(int32_t n, const orbgpu_pose_problem *problems, int32_t device_id,
+                                                     void *hip_stream)
+{
+    ORBGPU_REQUIRE(n >= 0 && n <= 65535 && (n == 0 || problems), "bad arguments");
+    int rc;
+    for (int k = 0; k < n; k++)
+        if ((rc = check_problem(problems[k], k)) != ORBGPU_OK)
+            return rc;
+    rc = select_device(device_id);
+    if (rc != ORBGPU_OK || n == 0)
+        return rc;
+    PoseWs &ws = per_device_workspace<PoseWs>(device_id);
+    ws.device = device_id;
+    const int lds_edges = lds_edge_limit();
+    size_t spill_edges = 0;
+    for (int k = 0; k < n; k++)
+        if (problems[k].frame->cap > lds_edges)
+            spill_edges += (size_t)problems[k].frame->cap;
+    if ((rc = ws.problems.reserve(sizeof(PoseProblemDev) * (size_t)n)) != ORBGPU_OK ||
+        (rc = ws.spill.reserve(2 * sizeof(float4) * std::max<size_t>(spill_edges, 1))) != ORBGPU_OK ||
+        (rc = ws.spill_count.reserve(sizeof(int32_t))) != ORBGPU_OK)
+        return rc;
+    std::vector<PoseProblemDev> hp((size_t)n);
+    size_t so = 0;
+    for (int k = 0; k < n; k++) {
+        const orbgpu_pose_problem &p = problems[k];
+        const orbgpu_device_frame_view *f = p.frame;
+        PoseProblemDev &D = hp[k];
+        memset(&D, 0, sizeof(D));
+        D.n = f->n, D.kps = f->kps, D.u_right = f->u_right, D.kp_to_mp = p.d_kp_to_mp, D.world_pos = p.d_world_pos;
+        D.outlier = p.d_outlier, D.result = p.d_result;
+        D.cap = f->cap, D.rows = p.rows, D.nlevels = f->nlevels, D.lds_edges = lds_edges;
+        D.spill_count = ws.spill_count.as<int32_t>();
+        if (f->cap > lds_edges) {
+            D.spill = ws.spill.as<float4>() + 2 * so;
+            so += (size_t)f->cap;
+        }
+        for (int l = 0; l < f->nlevels; l++)
+            D.inv_sigma2[l] = p.inv_level_sigma2[l];
+        // Converter::toSE3Quat (Converter.cc:37-47): float 3x3 -> double -> unit quaternion, float t -> double
+        double Rm[9];
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++)
+                Rm[3 * r + c] = (double)p.Tcw[4 * r + c];
+            D.t0[r] = (double)p.Tcw[4 * r + 3];
+        }
+        for (int i = 0; i < 16; i++)
+            D.Tcw[i] = p.Tcw[i];
+        quat_from_matrix(Rm, D.q0);
+        quat_normalize(D.q0);
+        D.fx = (double)p.fx, D.fy = (double)p.fy, D.cx = (double)p.cx, D.cy = (double)p.cy, D.bf = (double)p.mbf;
+        D.delta[0] = (double)(float)std::sqrt(5.991), D.delta[1] = (double)(float)std::sqrt(7.815);
+        D.delta2[0] = D.delta[0] * D.delta[0], D.delta2[1] = D.delta[1] * D.delta[1];
+    }
+    const hipStream_t st = (hipStream_t)hip_stream;
+    ORBGPU_HIP_TRY(hipMemsetAsync(ws.spill_count.p, 0, sizeof(int32_t), st));
+    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.problems.p, hp.data(), sizeof(PoseProblemDev) * (size_t)n, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_pose_opt, dim3(n), dim3(PO_THREADS), 0, st, ws.problems.as<PoseProblemDev>());
+    ORBGPU_HIP_TRY(hipGetLastError());
+    return ORBGPU_OK;
+}
+
+extern "C" int orbgpu_pose_optimization_device(const orbgpu_pose_problem *p, int32_t device_id, void *hip_stream)
+{
+    ORBGPU_REQUIRE(p, "null argument");
+    return orbgpu_pose_optimization_batch_device(1, p, device_id, hip_stream);
+}
+
+extern "C" int orbgpu_pose_last_spills(int32_t device_id, int32_t *problems_spilled)
+{
+    ORBGPU_REQUIRE(problems_spilled, "null argument");
+    int rc = select_device(device_id);
+    if (rc != ORBGPU_OK)
+        return rc;
+    PoseWs &ws = per_device_workspace<PoseWs>(device_id);
+    ORBGPU_REQUIRE(ws.spill_count.p, "no pose optimisation recorded on this thread");
+    ORBGPU_HIP_TRY(hipDeviceSynchronize());
+    ORBGPU_HIP_TRY(hipMemcpy(problems_spilled, ws.spill_count.p, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return ORBGPU_OK;
+}
+
+extern "C" int orbgpu_pose_optimization(const orbgpu_frame_view *f, const uint8_t *has_mp, const float *world_pos,
+                                        float *Tcw, const float *inv_level_sigma2, float fx, float fy, float cx, float cy,
+                                        float mbf, uint8_t *outlier, int32_t *n_inliers, orbgpu_pose_result *result,
+                                        int32_t device_id)
+{
+    ORBGPU_REQUIRE(f && Tcw && inv_level_sigma2 && n_inliers, "null argument");
+    ORBGPU_REQUIRE(f->n >= 0 && f->n <= 16384, "key point count out of range (max 16384)");
+    ORBGPU_REQUIRE(f->nlevels >= 1 && f->nlevels <= ORBGPU_MAX_LEVELS, "nlevels outside [1, %d]", ORBGPU_MAX_LEVELS);
+    ORBGPU_REQUIRE(f->n == 0 || (f->kp_x && f->kp_y && f->kp_octave && f->u_right && has_mp && world_pos && outlier),
+                   "null arrays");
+    int rc = select_device(device_id);
+    if (rc != ORBGPU_OK)
+        return rc;
+    PoseWs &ws = per_device_workspace<PoseWs>(device_id);
+    if (!ws.stream) {
+        hipError_t e = hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking);
+        if (e != hipSuccess) {
+            set_error("hipStreamCreate: %s", hipGetErrorString(e));
+            return ORBGPU_EHIP;
+        }
+        ws.device = device_id;
+    }
+    const int n = f->n, cap = std::max(n, 1);
+    if ((rc = ws.h_kps.reserve(sizeof(orbgpu_keypoint) * cap)) != ORBGPU_OK ||
+        (rc = ws.h_ur.reserve(sizeof(float) * cap)) != ORBGPU_OK || (rc = ws.h_k2m.reserve(sizeof(int32_t) * cap)) != ORBGPU_OK ||
+        (rc = ws.h_wp.reserve(3 * sizeof(float) * cap)) != ORBGPU_OK || (rc = ws.h_n.reserve(sizeof(int32_t))) != ORBGPU_OK ||
+        (rc = ws.h_out.reserve(cap)) != ORBGPU_OK || (rc = ws.h_res.reserve(sizeof(orbgpu_pose_result))) != ORBGPU_OK)
+        return rc;
+    std::vector<orbgpu_keypoint> kps((size_t)cap);
+    std::vector<int32_t> k2m((size_t)cap);
+    for (int i = 0; i < n; i++) {
+        orbgpu_keypoint k{};
+        k.x = f->kp_x[i], k.y = f->kp_y[i], k.octave = f->kp_octave[i], k.class_id = -1;
+        kps[i] = k;
+        k2m[i] = has_mp[i] ? i : -1;
+    }
+    const hipStream_t st = ws.stream;
+    const int32_t n32 = n;
+    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.h_n.p, &n32, sizeof(n32), hipMemcpyHostToDevice, st));
+    if (n > 0) {
+        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.h_kps.p, kps.data(), sizeof(orbgpu_keypoint) * n, hipMemcpyHostToDevice, st));
+        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.h_k2m.p, k2m.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.h_ur.p, f->u_right, sizeof(float) * n, hipMemcpyHostToDevice, st));
+        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.h_wp.p, world_pos, 3 * sizeof(float) * n, hipMemcpyHostToDevice, st));
+        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.h_out.p, outlier, n, hipMemcpyHostToDevice, st));
+    }
+    orbgpu_device_frame_view dv{};
+    dv.cap = n, dv.n = ws.h_n.as<int32_t>(), dv.kps = ws.h_kps.as<orbgpu_keypoint>(), dv.u_right = ws.h_ur.as<float>();
+    dv.nlevels = f->nlevels;
+    orbgpu_pose_problem p{};
+    p.frame = &dv, p.d_kp_to_mp = ws.h_k2m.as<int32_t>(), p.d_world_pos = ws.h_wp.as<float>(), p.rows = n;
+    p.Tcw = Tcw, p.inv_level_sigma2 = inv_level_sigma2;
+    p.fx = fx, p.fy = fy, p.cx = cx, p.cy = cy, p.mbf = mbf;
+    p.d_outlier = ws.h_out.as<uint8_t>(), p.d_result = ws.h_res.as<orbgpu_pose_result>();
+    rc = orbgpu_pose_optimization_batch_device(1, &p, device_id, st);
+    if (rc != ORBGPU_OK) {
+        (void)hipStreamSynchronize(st);  // the uploads read the caller's arrays
+        return rc;
+    }
+    orbgpu_pose_result r;
+    ORBGPU_HIP_TRY(hipMemcpyAsync(&r, ws.h_res.p, sizeof(r), hipMemcpyDeviceToHost, st));
+    if (n > 0)
+        ORBGPU_HIP_TRY(hipMemcpyAsync(outlier, ws.h_out.p, n, hipMemcpyDeviceToHost, st));
+    ORBGPU_HIP_TRY(hipStreamSynchronize(st));
+    memcpy(Tcw, r.Tcw, sizeof(r.Tcw));
+    *n_inliers = r.n_inliers;
+    if (result)
+        *result = r;
+    return ORBGPU_OK;
+}

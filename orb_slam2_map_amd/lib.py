@@ -102,6 +102,23 @@ class LastFrameView(C.Structure):
                 ("kp_angle", C.c_void_p), ("Tcw", C.c_void_p)]
 
 
+class PoseResult(C.Structure):
+    _fields_ = [("Tcw_d", C.c_double * 16), ("Tcw", C.c_float * 16), ("n_initial", C.c_int32), ("n_inliers", C.c_int32),
+                ("rounds", C.c_int32), ("iterations", C.c_int32), ("trials", C.c_int32), ("n_bad_index", C.c_int32)]
+
+    def as_dict(self):
+        return {"Tcw_d": np.array(self.Tcw_d, np.float64).reshape(4, 4), "Tcw": np.array(self.Tcw, np.float32).reshape(4, 4),
+                "n_initial": self.n_initial, "n_inliers": self.n_inliers, "rounds": self.rounds,
+                "iterations": self.iterations, "trials": self.trials, "n_bad_index": self.n_bad_index}
+
+
+class PoseProblem(C.Structure):
+    _fields_ = [("frame", C.c_void_p), ("d_kp_to_mp", C.c_void_p), ("d_world_pos", C.c_void_p), ("rows", C.c_int32),
+                ("Tcw", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("mbf", C.c_float), ("d_outlier", C.c_void_p),
+                ("d_result", C.c_void_p)]
+
+
 _LIB = None
 
 # every symbol include/orbgpu.h declares (checked by tests/test_abi.py against the header text)
@@ -126,6 +143,8 @@ ABI_SYMBOLS = [
     "orbgpu_mappoint_table_upsert", "orbgpu_mappoint_table_set_bad", "orbgpu_mappoint_table_set_observations",
     "orbgpu_mappoint_table_read", "orbgpu_mappoint_table_last_unknown", "orbgpu_mappoint_table_retain", "orbgpu_frame_create", "orbgpu_frame_destroy", "orbgpu_frame_upload",
     "orbgpu_frame_device_view", "orbgpu_search_local_points_table", "orbgpu_search_by_projection_last_table",
+    "orbgpu_pose_optimization", "orbgpu_pose_optimization_device", "orbgpu_pose_optimization_batch_device",
+    "orbgpu_pose_optimization_table", "orbgpu_pose_last_spills",
     "orbgpu_vocabulary_create", "orbgpu_vocabulary_destroy", "orbgpu_vocabulary_size", "orbgpu_bow_transform",
     "orbgpu_bow_transform_batch_device", "orbgpu_search_by_bow", "orbgpu_search_by_bow_batch_device",
     "orbgpu_search_by_bow_keyframes", "orbgpu_search_for_triangulation", "orbgpu_search_for_initialization", "orbgpu_fuse", "orbgpu_fuse_sim3",
@@ -782,6 +801,88 @@ def search_by_projection_last_table(cur, cur_Tcw, last, last_Tcw, table, last_id
                                                    _p(lo) if lo is not None else None, _p(ck) if ck is not None else None,
                                                    fx, fy, cx, cy, mbf, mb, th, int(mono), int(check_ori), _p(out), C.byref(nm)))
     return nm.value, out[:cur.n]
+
+
+def pose_optimization(frame, has_mp, world_pos, Tcw, inv_level_sigma2, fx, fy, cx, cy, mbf, outlier=None, device_id=0):
+    """Optimizer::PoseOptimization on host arrays (orbgpu_pose_optimization).  frame: lib.Frame; has_mp [n], world_pos
+    [n][3] per key point; outlier [n] uint8 or None (zeros): only edges are written.  Returns (n_inliers, Tcw 4x4 float32,
+    outlier, result dict)."""
+    L = lib()
+    v = frame.view()
+    n = frame.n
+    hm = np.ascontiguousarray(has_mp, np.uint8)
+    wp = np.ascontiguousarray(world_pos, np.float32).reshape(-1, 3)
+    if len(hm) != n or len(wp) != n:
+        raise ValueError("has_mp / world_pos must have one entry per key point")
+    T = np.array(Tcw, np.float32).reshape(4, 4).copy()
+    sg = np.ascontiguousarray(inv_level_sigma2, np.float32)
+    v.nlevels = len(sg)
+    out = np.zeros(max(n, 1), np.uint8) if outlier is None else np.array(outlier, np.uint8)
+    ni, res = C.c_int32(), PoseResult()
+    L.orbgpu_pose_optimization.argtypes = [C.c_void_p] * 5 + [C.c_float] * 5 + [C.c_void_p] * 3 + [C.c_int32]
+    check(L.orbgpu_pose_optimization(C.byref(v), _p(hm), _p(wp), _p(T), _p(sg), fx, fy, cx, cy, mbf, _p(out), C.byref(ni),
+                                     C.byref(res), device_id))
+    return ni.value, T, out[:n], res.as_dict()
+
+
+def _pose_problem_array(problems):
+    arr = (PoseProblem * max(len(problems), 1))()
+    keep = []
+    for k, p in enumerate(problems):
+        T = np.ascontiguousarray(p["Tcw"], np.float32)
+        sg = np.ascontiguousarray(p["inv_level_sigma2"], np.float32)
+        keep += [T, sg]
+        arr[k].frame = C.addressof(p["frame"])
+        arr[k].d_kp_to_mp, arr[k].d_world_pos, arr[k].rows = p["d_kp_to_mp"], p["d_world_pos"], int(p["rows"])
+        arr[k].Tcw, arr[k].inv_level_sigma2 = T.ctypes.data, sg.ctypes.data
+        arr[k].fx, arr[k].fy, arr[k].cx, arr[k].cy, arr[k].mbf = p["fx"], p["fy"], p["cx"], p["cy"], p["mbf"]
+        arr[k].d_outlier, arr[k].d_result = p["d_outlier"], p["d_result"]
+    return arr, keep
+
+
+def pose_optimization_batch_device(problems, stream=0, device_id=0):
+    """n independent Optimizer::PoseOptimization problems in one launch (orbgpu_pose_optimization_batch_device); not
+    synchronised.  problems: list of dicts with frame (DeviceFrameView), d_kp_to_mp, d_world_pos, rows, Tcw (4x4),
+    inv_level_sigma2, fx, fy, cx, cy, mbf, d_outlier, d_result (device pointers; d_result holds a PoseResult)."""
+    arr, keep = _pose_problem_array(problems)
+    L = lib()
+    L.orbgpu_pose_optimization_batch_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    check(L.orbgpu_pose_optimization_batch_device(len(problems), arr, device_id, stream))
+
+
+def pose_optimization_device(problem, stream=0, device_id=0):
+    """One problem (orbgpu_pose_optimization_device); see pose_optimization_batch_device."""
+    arr, keep = _pose_problem_array([problem])
+    L = lib()
+    L.orbgpu_pose_optimization_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    check(L.orbgpu_pose_optimization_device(arr, device_id, stream))
+
+
+def pose_optimization_table(dframe, table, kp_ids, Tcw, inv_level_sigma2, fx, fy, cx, cy, mbf, outlier=None):
+    """Optimizer::PoseOptimization over the MapPoint table (orbgpu_pose_optimization_table): dframe a DeviceFrame,
+    kp_ids [n] = mnId of the key point's map point or -1.  Returns (n_inliers, Tcw, outlier, result dict)."""
+    L = lib()
+    n = dframe.n
+    ids = np.ascontiguousarray(kp_ids, np.int64)
+    if len(ids) != n:
+        raise ValueError("kp_ids must have one entry per key point")
+    T = np.array(Tcw, np.float32).reshape(4, 4).copy()
+    sg = np.ascontiguousarray(inv_level_sigma2, np.float32)
+    out = np.zeros(max(n, 1), np.uint8) if outlier is None else np.array(outlier, np.uint8)
+    ni, res = C.c_int32(), PoseResult()
+    L.orbgpu_pose_optimization_table.argtypes = [C.c_void_p] * 5 + [C.c_float] * 5 + [C.c_void_p] * 3
+    check(L.orbgpu_pose_optimization_table(dframe.h, table.h, _p(ids), _p(T), _p(sg), fx, fy, cx, cy, mbf, _p(out),
+                                           C.byref(ni), C.byref(res)))
+    return ni.value, T, out[:n], res.as_dict()
+
+
+def pose_last_spills(device_id=0):
+    """Problems of this thread's most recent pose optimisation that took the global-memory spill path."""
+    L = lib()
+    L.orbgpu_pose_last_spills.argtypes = [C.c_int32, C.c_void_p]
+    v = C.c_int32()
+    check(L.orbgpu_pose_last_spills(device_id, C.byref(v)))
+    return v.value
 
 
 def distinctive_descriptors(groups, device_id=0):

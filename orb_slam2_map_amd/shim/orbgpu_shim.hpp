@@ -966,6 +966,81 @@ template <typename FrameT, typename MapPointT> class ORBmatcherT {
 };
 
 // --------------------------------------------------------------------------------------------
+// Optimizer::PoseOptimization (reference include/Optimizer.h:52, src/Optimizer.cc:239-451): motion-only bundle
+// adjustment of pFrame's pose.  Side effects as in the reference: pFrame->mvbOutlier[i] for every key point with a map
+// point, the optimised pose handed to set_pose (Frame::SetPose), return value = inliers.  g2o is restated, not linked
+// ("g2o unpinned", include/orbgpu.h).  FrameT needs N, mvKeysUn, mvuRight, mvpMapPoints, mvbOutlier, mvInvLevelSigma2,
+// fx, fy, cx, cy, mbf; Tcw(F) returns the 16 floats of mTcw, world_pos(pMP) 3 floats (both valid during the call).
+// --------------------------------------------------------------------------------------------
+template <typename FrameT, typename MapPointT> class OptimizerT {
+  public:
+    // host arrays: one upload per call
+    template <typename TcwOf, typename WorldPos, typename SetPose>
+    static int PoseOptimization(FrameT *pFrame, TcwOf Tcw, WorldPos world_pos, SetPose set_pose, int device_id = 0,
+                                orbgpu_pose_result *result = nullptr)
+    {
+        FrameT &F = *pFrame;
+        const int n = F.N;
+        std::vector<float> x(n), y(n), ur(n), wp(3 * (size_t)n, 0.f);
+        std::vector<int32_t> oct(n);
+        std::vector<uint8_t> has(n), out(n);
+        for (int i = 0; i < n; i++) {
+            x[i] = F.mvKeysUn[i].pt.x, y[i] = F.mvKeysUn[i].pt.y, oct[i] = F.mvKeysUn[i].octave, ur[i] = F.mvuRight[i];
+            MapPointT *p = F.mvpMapPoints[i];
+            has[i] = p != nullptr;
+            out[i] = F.mvbOutlier[i];
+            if (p) {
+                const float *w = world_pos(p);
+                wp[3 * (size_t)i] = w[0], wp[3 * (size_t)i + 1] = w[1], wp[3 * (size_t)i + 2] = w[2];
+            }
+        }
+        orbgpu_frame_view v{};
+        v.n = n, v.kp_x = x.data(), v.kp_y = y.data(), v.kp_octave = oct.data(), v.u_right = ur.data();
+        v.nlevels = (int32_t)F.mvInvLevelSigma2.size();
+        float T[16];
+        std::memcpy(T, Tcw(F), sizeof(T));
+        int32_t inliers = 0;
+        check(orbgpu_pose_optimization(&v, has.data(), wp.data(), T, F.mvInvLevelSigma2.data(), F.fx, F.fy, F.cx, F.cy, F.mbf,
+                                       out.data(), &inliers, result, device_id),
+              "Optimizer::PoseOptimization");
+        for (int i = 0; i < n; i++)
+            if (has[i])
+                F.mvbOutlier[i] = out[i] != 0;
+        set_pose(F, T);
+        return inliers;
+    }
+
+    // device-resident frame + MapPoint table: ids and the pose go up, mvbOutlier and the pose come back
+    template <typename TcwOf, typename SetPose>
+    static int PoseOptimization(FrameT *pFrame, const DeviceFrameT<FrameT> &dF, MapPointTableT<MapPointT> &table, TcwOf Tcw,
+                                SetPose set_pose, orbgpu_pose_result *result = nullptr)
+    {
+        FrameT &F = *pFrame;
+        const int n = F.N;
+        std::vector<int64_t> ids(n);
+        std::vector<uint8_t> out(n);
+        for (int i = 0; i < n; i++) {
+            ids[i] = F.mvpMapPoints[i] ? (int64_t)F.mvpMapPoints[i]->mnId : -1;
+            out[i] = F.mvbOutlier[i];
+        }
+        float T[16];
+        std::memcpy(T, Tcw(F), sizeof(T));
+        int32_t inliers = 0;
+        {
+            std::lock_guard<std::mutex> table_lock(table.mutex());
+            check(orbgpu_pose_optimization_table(dF.handle(), table.handle(), ids.data(), T, F.mvInvLevelSigma2.data(), F.fx,
+                                                 F.fy, F.cx, F.cy, F.mbf, out.data(), &inliers, result),
+                  "Optimizer::PoseOptimization(table)");
+        }
+        for (int i = 0; i < n; i++)
+            if (ids[i] >= 0)
+                F.mvbOutlier[i] = out[i] != 0;
+        set_pose(F, T);
+        return inliers;
+    }
+};
+
+// --------------------------------------------------------------------------------------------
 // PointCloudMapping (reference include/PointCloudMap.h:41-88, src/PointCloudMap.cc)
 // Keeps the reference's thread / condition-variable protocol; the per-key-frame arithmetic runs on
 // the GPU.  KeyFrameT needs mImDep (float depth), mImRGB (8UC3), fx, fy, cx, cy and GetPose();
