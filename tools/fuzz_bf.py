@@ -16,7 +16,7 @@ from test_gpu_matcher_bf import low_entropy
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
-t0, n = time.time(), 0
+t0, n, n_ori = time.time(), 0, 0
 while time.time() - t0 < budget:
     na, nb = int(rng.integers(1, 1300)), int(rng.integers(1, 1300))
     pool = int(rng.choice([4, 20, 100, 1000]))
@@ -40,4 +40,5 @@ while time.time() - t0 < budget:
         print("FAIL bf", dict(na=na, nb=nb, pool=pool, flip=flip, ratio=ratio, th=th, ori=ori), ng, no)
         sys.exit(1)
     n += 1
-print("fuzz ok: %d matches in %.0f s" % (n, time.time() - t0))
+    n_ori += ori
+print("fuzz ok: %d matches, %d with the rotation check on uniform random angles, in %.0f s" % (n, n_ori, time.time() - t0))

@@ -17,7 +17,7 @@ from test_gpu_bow import _features, _same
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
-t0, n = time.time(), 0
+t0, n, n_ori = time.time(), 0, 0
 while time.time() - t0 < budget:
     k, L = int(rng.integers(2, 21)), int(rng.integers(1, 7))
     while k ** L > 200000:
@@ -50,4 +50,5 @@ while time.time() - t0 < budget:
         sys.exit(1)
     gv.close()
     n += 1
-print("fuzz ok: %d vocabularies in %.0f s" % (n, time.time() - t0))
+    n_ori += ori
+print("fuzz ok: %d vocabularies, %d with the rotation check on uniform random angles, in %.0f s" % (n, n_ori, time.time() - t0))
