@@ -649,6 +649,109 @@ int orbgpu_pose_optimization_table(const orbgpu_frame *fr, orbgpu_mappoint_table
  * Synchronises the device. */
 int orbgpu_pose_last_spills(int32_t device_id, int32_t *problems_spilled);
 
+/* ---- Sim3Solver (Sim3Solver.cc, Horn 1987 + RANSAC): the Sim3 of a loop candidate on the device --------------------------
+ * The second of the five steps of LoopClosing::ComputeSim3 (LoopClosing.cc:236-343); its result is the R12 / t12 / s12 that
+ * orbgpu_search_by_sim3 takes.  All hypotheses of a candidate are evaluated at once, one wave each; the reference's
+ * sequential acceptance rule is replayed over the per-hypothesis counts.  OpenCV is not part of the reference tree: every
+ * result is "vs CPU restatement; OpenCV boundary unpinned"; tests/sim3_model.py is the restatement.  Conventions H1-H8
+ * (DESIGN.md section 2), float32 with one rounding per operation unless a double is named:
+ *   H1 rows (:62-103)     row i1 is kept iff valid[i1] != 0 (the caller's verdict on: has a match, both map points exist
+ *                         and are not bad, both indices in their key frame >= 0) and both octaves lie in [0, nlevels); a
+ *                         valid row with an octave outside is not kept and counted in n_bad_index (the reference reads
+ *                         out of range).  Kept rows are compacted in index order (mvnIndices1): N of them.
+ *   H2 points             Xc = Rcw Xw + tcw: products summed left to right, then one add (cv::gemm's small-matrix path);
+ *                         own-image projection invz = 1/z, u = fx*(x*invz) + cx, v = fy*(y*invz) + cy
+ *   H3 thresholds         mvnMaxError is a vector<size_t>: maxError = (float)trunc(9.210 * (double)sigma2[octave]) -- 9,
+ *                         13, 19, ...; a product that is not >= 0 gives 0
+ *   H4 iterations (:114-138)  epsilon = (float)minInliers / N; nIterations = 1 if minInliers == N, else
+ *                         ceil(log(1 - p) / log(1 - pow((double)epsilon, 3))) in double; NaN or outside int counts as larger
+ *                         than maxIterations; max_its = max(1, min(nIterations, maxIterations)); N = 0 gives 1.  Computed
+ *                         on the host (orbgpu_sim3_ransac_iterations).
+ *   H5 minimal sets       the library draws nothing: triples[h][3] index the compacted list, only the first
+ *                         n_use = min(n_hyp, max_its) are used (none if N < minInliers).  orbgpu_shim::Sim3SampleTriples
+ *                         replays the reference's draw (:163-177), its quirk included.
+ *   H6 Horn (:226-337)    centroid = ((a + b) + c) / 3; M = Pr2 Pr1' and N11..N44 with double sums rounded once to float;
+ *                         from here FP64 on the float N: cyclic Jacobi (pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); stop when
+ *                         the off-diagonal square sum is <= 1e-32 x the square sum of all entries, at most 16 sweeps;
+ *                         theta = (aqq - app) / (2 apq), t = sign(theta) / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1),
+ *                         s = t c), eigenvector q of the largest eigenvalue (first on ties), ang = atan2(|v|, q0),
+ *                         vec = 2 ang v / |v|, Rodrigues; R rounded once to float.  P3 = R Pr2 (small-matrix);
+ *                         s = (float)(nom / den) with double sums in row-major order, or 1.0f with fix_scale;
+ *                         t = O1 - s (R O2); T12 = [sR t]; sRinv = (1.0f / s) R'; T21 = [sRinv, -(sRinv t)].
+ *                         No special cases: a degenerate triple gives NaN and, NaN < x being false, 0 inliers.
+ *   H7 inliers (:340-364) X2 through T12 into image 1, X1 through T21 into image 2 (H2); err = (float)((double)dx*dx +
+ *                         (double)dy*dy); inlier iff err1 < maxError1 && err2 < maxError2
+ *   H8 acceptance (:140-207)  N < minInliers: no_more at once.  Iteration h becomes the best iff count >= best so far, and
+ *                         is accepted iff it then has count > minInliers; the scan starts at (start_iteration, best_so_far)
+ *                         and ends at the first acceptance or at n_use; no_more iff it ended at max_its unaccepted. */
+typedef struct orbgpu_sim3_result { /* device or host */
+    int32_t n;              /* N: kept rows */
+    int32_t max_its;        /* mRansacMaxIts (H4) */
+    int32_t n_bad_index;    /* valid rows with an octave outside [0, nlevels): not kept */
+    int32_t n_bad_triple;   /* used hypotheses with an index outside [0, N): never read through, count 0, NaN outputs */
+    int32_t accepted;       /* first accepted iteration (0-based index into triples) or -1 */
+    int32_t n_inliers;      /* its count, 0 if none */
+    int32_t best_inliers;   /* mnBestInliers after the scan */
+    int32_t best_iteration; /* the iteration that holds it (GetEstimated*), -1 if none was scanned and none passed in */
+    int32_t iterations;     /* mnIterations after the scan */
+    int32_t no_more;        /* bNoMore */
+} orbgpu_sim3_result;
+
+/* The array pointers are DEVICE pointers for the *_device entry points and HOST pointers for orbgpu_sim3_solve. */
+typedef struct orbgpu_sim3_problem {
+    int32_t n1;             /* mN1 = vpMatched12.size() */
+    int32_t n_hyp;          /* H: rows of triples */
+    const uint8_t *valid;   /* [n1] (H1) */
+    const float *Xw1;       /* [n1][3] world position of KF1's map point i1 (read for valid rows only) */
+    const float *Xw2;       /* [n1][3] world position of vpMatched12[i1] */
+    const int32_t *octave1; /* [n1] mvKeysUn[indexKF1].octave */
+    const int32_t *octave2; /* [n1] */
+    const int32_t *triples; /* [n_hyp][3] (H5) */
+    float T1w[16], T2w[16]; /* key-frame poses, 4x4 row-major */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    float level_sigma2[ORBGPU_MAX_LEVELS]; /* mvLevelSigma2 */
+    int32_t nlevels;
+    int32_t fix_scale;
+    int32_t min_inliers, max_iterations;
+    double probability;
+    int32_t start_iteration, best_so_far; /* H8: 0, 0 for a fresh solver */
+    /* outputs (orbgpu_sim3_solve ignores them) */
+    int32_t *counts;        /* [n_hyp]: inliers of hypothesis h; 0 for h >= n_use */
+    float *R;               /* [n_hyp][9]  R12, written for h < n_use */
+    float *t;               /* [n_hyp][3] */
+    float *s;               /* [n_hyp] */
+    float *T12;             /* [n_hyp][16] */
+    uint64_t *masks;        /* [n_hyp][(n1 + 63) / 64]: bit i1 % 64 of word i1 / 64 = vbInliers[i1]; written for h < n_use */
+    int32_t *indices1;      /* [n1] mvnIndices1 (compacted -> i1), first N written; may be NULL */
+    orbgpu_sim3_result *result;
+} orbgpu_sim3_problem;
+
+/* H4 on the host; EINVAL for a null pointer or negative n / min_inliers / max_iterations. */
+int orbgpu_sim3_ransac_iterations(int32_t n, double probability, int32_t min_inliers, int32_t max_iterations,
+                                  int32_t *max_its);
+/* Enqueued on hip_stream.  The call waits for the stream TWICE: on entry (the host staging of the thread's previous call
+ * must have left for the device; in effect that call's kernels are waited for too) and between the preparation and the
+ * hypotheses, to read every N and compute max_its on the host (H4).  The hypotheses and the scan of THIS call are
+ * enqueued and not waited for.  Calls of one host thread share a workspace and must be ordered on one stream.  EINVAL: null pointers, n1 outside [0, 65536], n_hyp outside
+ * [0, 4096], nlevels outside [1, ORBGPU_MAX_LEVELS], negative min_inliers / max_iterations / start_iteration /
+ * best_so_far; nothing is launched then.  EHIP without a device.  The batch form is one launch sequence (three kernels) for
+ * all candidates of a ComputeSim3 call. */
+int orbgpu_sim3_solve_device(const orbgpu_sim3_problem *p, int32_t device_id, void *hip_stream);
+int orbgpu_sim3_solve_batch_device(int32_t n, const orbgpu_sim3_problem *problems, int32_t device_id, void *hip_stream);
+/* Host arrays, synchronises.  counts [n_hyp]; R [9], t [3], s [1], T12 [16] of the best iteration (= the accepted one when
+ * one is accepted; untouched if best_iteration is -1 or names an iteration of an earlier call); inliers [n1] bytes of the
+ * accepted iteration (all 0 if none).  counts, R, t, s, T12 and inliers may be NULL.  A triple index outside [0, N) among
+ * the used hypotheses is EINVAL here, before anything is launched.
+ * The host flavours run on a stream of the workspace's own and wait for the whole device on entry, so they may follow a
+ * device-flavour call of the same thread on any stream. */
+int orbgpu_sim3_solve(const orbgpu_sim3_problem *p, int32_t *counts, float *R, float *t, float *s, float *T12,
+                      uint8_t *inliers, orbgpu_sim3_result *result, int32_t device_id);
+/* As orbgpu_sim3_solve, but every hypothesis comes back: counts [n_hyp], R [n_hyp][9], t [n_hyp][3], s [n_hyp], T12
+ * [n_hyp][16], masks [n_hyp][(n1 + 63) / 64] (any may be NULL); hypotheses h >= n_use are zeros.  One upload, one launch
+ * sequence: what a caller needs that serves iterate(n, ...) itself (orbgpu_shim::Sim3SolverT). */
+int orbgpu_sim3_solve_all(const orbgpu_sim3_problem *p, int32_t *counts, float *R, float *t, float *s, float *T12,
+                          uint64_t *masks, orbgpu_sim3_result *result, int32_t device_id);
+
 
 /* LastFrame members read by SearchByProjection(CurrentFrame, LastFrame, th, bMono). */
 typedef struct {

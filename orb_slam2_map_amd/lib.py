@@ -119,6 +119,26 @@ class PoseProblem(C.Structure):
                 ("d_result", C.c_void_p)]
 
 
+class Sim3Result(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n", "max_its", "n_bad_index", "n_bad_triple", "accepted", "n_inliers",
+                                         "best_inliers", "best_iteration", "iterations", "no_more")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Sim3Problem(C.Structure):
+    _fields_ = [("n1", C.c_int32), ("n_hyp", C.c_int32), ("valid", C.c_void_p), ("Xw1", C.c_void_p), ("Xw2", C.c_void_p),
+                ("octave1", C.c_void_p), ("octave2", C.c_void_p), ("triples", C.c_void_p), ("T1w", C.c_float * 16),
+                ("T2w", C.c_float * 16), ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float), ("cy1", C.c_float),
+                ("fx2", C.c_float), ("fy2", C.c_float), ("cx2", C.c_float), ("cy2", C.c_float),
+                ("level_sigma2", C.c_float * MAX_LEVELS), ("nlevels", C.c_int32), ("fix_scale", C.c_int32),
+                ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("probability", C.c_double),
+                ("start_iteration", C.c_int32), ("best_so_far", C.c_int32), ("counts", C.c_void_p), ("R", C.c_void_p),
+                ("t", C.c_void_p), ("s", C.c_void_p), ("T12", C.c_void_p), ("masks", C.c_void_p), ("indices1", C.c_void_p),
+                ("result", C.c_void_p)]
+
+
 _LIB = None
 
 # every symbol include/orbgpu.h declares (checked by tests/test_abi.py against the header text)
@@ -145,6 +165,8 @@ ABI_SYMBOLS = [
     "orbgpu_frame_device_view", "orbgpu_search_local_points_table", "orbgpu_search_by_projection_last_table",
     "orbgpu_pose_optimization", "orbgpu_pose_optimization_device", "orbgpu_pose_optimization_batch_device",
     "orbgpu_pose_optimization_table", "orbgpu_pose_last_spills",
+    "orbgpu_sim3_ransac_iterations", "orbgpu_sim3_solve_device", "orbgpu_sim3_solve_batch_device", "orbgpu_sim3_solve",
+    "orbgpu_sim3_solve_all",
     "orbgpu_vocabulary_create", "orbgpu_vocabulary_destroy", "orbgpu_vocabulary_size", "orbgpu_bow_transform",
     "orbgpu_bow_transform_batch_device", "orbgpu_search_by_bow", "orbgpu_search_by_bow_batch_device",
     "orbgpu_search_by_bow_keyframes", "orbgpu_search_for_triangulation", "orbgpu_search_for_initialization", "orbgpu_fuse", "orbgpu_fuse_sim3",
@@ -883,6 +905,109 @@ def pose_last_spills(device_id=0):
     v = C.c_int32()
     check(L.orbgpu_pose_last_spills(device_id, C.byref(v)))
     return v.value
+
+
+def sim3_ransac_iterations(n, probability, min_inliers, max_iterations):
+    """mRansacMaxIts of Sim3Solver::SetRansacParameters (orbgpu_sim3_ransac_iterations; host only, needs no device)."""
+    L = lib()
+    L.orbgpu_sim3_ransac_iterations.argtypes = [C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_void_p]
+    v = C.c_int32()
+    check(L.orbgpu_sim3_ransac_iterations(n, probability, min_inliers, max_iterations, C.byref(v)))
+    return v.value
+
+
+_SIM3_PTRS = ("valid", "Xw1", "Xw2", "octave1", "octave2", "triples", "counts", "R", "t", "s", "T12", "masks", "indices1",
+              "result")
+
+
+def sim3_problem(p):
+    """A Sim3Problem from a dict: n1, n_hyp, T1w, T2w (4x4), K1, K2 (fx, fy, cx, cy), level_sigma2, fix_scale,
+    probability, min_inliers, max_iterations, optional start_iteration / best_so_far, and the array pointers of
+    include/orbgpu.h as integers (device or host addresses; missing ones are NULL)."""
+    q = Sim3Problem()
+    q.n1, q.n_hyp = int(p["n1"]), int(p["n_hyp"])
+    for k in _SIM3_PTRS:
+        setattr(q, k, p.get(k) or None)
+    q.T1w[:] = np.asarray(p["T1w"], np.float32).reshape(16).tolist()
+    q.T2w[:] = np.asarray(p["T2w"], np.float32).reshape(16).tolist()
+    q.fx1, q.fy1, q.cx1, q.cy1 = (float(k) for k in p["K1"])
+    q.fx2, q.fy2, q.cx2, q.cy2 = (float(k) for k in p["K2"])
+    sg = np.asarray(p["level_sigma2"], np.float32)
+    q.nlevels = int(p.get("nlevels", len(sg)))
+    for l in range(min(len(sg), MAX_LEVELS)):
+        q.level_sigma2[l] = float(sg[l])
+    q.fix_scale, q.min_inliers, q.max_iterations = int(p["fix_scale"]), int(p["min_inliers"]), int(p["max_iterations"])
+    q.probability = float(p["probability"])
+    q.start_iteration, q.best_so_far = int(p.get("start_iteration", 0)), int(p.get("best_so_far", 0))
+    return q
+
+
+def sim3_solve_batch_device(problems, stream=0, device_id=0):
+    """All candidates of a LoopClosing::ComputeSim3 call in one launch sequence (orbgpu_sim3_solve_batch_device).
+    problems: dicts as sim3_problem takes them, with device pointers.  Waits once for the stream (N is read back to compute
+    max_its on the host); the hypotheses and the acceptance scan are enqueued and not waited for."""
+    arr = (Sim3Problem * max(len(problems), 1))()
+    for k, p in enumerate(problems):
+        arr[k] = sim3_problem(p)
+    L = lib()
+    L.orbgpu_sim3_solve_batch_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    check(L.orbgpu_sim3_solve_batch_device(len(problems), arr, device_id, stream))
+
+
+def sim3_solve_device(problem, stream=0, device_id=0):
+    """One candidate (orbgpu_sim3_solve_device); see sim3_solve_batch_device."""
+    q = sim3_problem(problem)
+    L = lib()
+    L.orbgpu_sim3_solve_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    check(L.orbgpu_sim3_solve_device(C.byref(q), device_id, stream))
+
+
+def sim3_solve(valid, Xw1, Xw2, octave1, octave2, T1w, T2w, K1, K2, level_sigma2, triples, fix_scale=False,
+               probability=0.99, min_inliers=6, max_iterations=300, start_iteration=0, best_so_far=0, device_id=0):
+    """Sim3Solver over host arrays (orbgpu_sim3_solve): valid [n1] is the constructor's verdict per correspondence, Xw1 /
+    Xw2 [n1][3] the two map points' world positions, triples [H][3] the minimal sets (indices into the kept rows).
+    Returns a dict: the result record's fields, counts [H], R (3x3), t, s, T12 (4x4) of the best iteration and inliers
+    [n1] of the accepted one."""
+    v = np.ascontiguousarray(valid, np.uint8)
+    n1 = len(v)
+    x1 = np.ascontiguousarray(Xw1, np.float32).reshape(-1, 3)
+    x2 = np.ascontiguousarray(Xw2, np.float32).reshape(-1, 3)
+    o1, o2 = np.ascontiguousarray(octave1, np.int32), np.ascontiguousarray(octave2, np.int32)
+    if not (len(x1) == len(x2) == len(o1) == len(o2) == n1):
+        raise ValueError("one entry per correspondence expected")
+    tr = np.ascontiguousarray(triples, np.int32).reshape(-1, 3)
+    H = len(tr)
+    q = sim3_problem({"n1": n1, "n_hyp": H, "valid": v.ctypes.data, "Xw1": x1.ctypes.data, "Xw2": x2.ctypes.data,
+                      "octave1": o1.ctypes.data, "octave2": o2.ctypes.data, "triples": tr.ctypes.data, "T1w": T1w, "T2w": T2w,
+                      "K1": K1, "K2": K2, "level_sigma2": level_sigma2, "fix_scale": fix_scale, "probability": probability,
+                      "min_inliers": min_inliers, "max_iterations": max_iterations, "start_iteration": start_iteration,
+                      "best_so_far": best_so_far})
+    counts = np.zeros(max(H, 1), np.int32)
+    R, t, s, T12 = np.zeros((3, 3), np.float32), np.zeros(3, np.float32), np.zeros(1, np.float32), np.zeros((4, 4), np.float32)
+    inl, res = np.zeros(max(n1, 1), np.uint8), Sim3Result()
+    L = lib()
+    L.orbgpu_sim3_solve.argtypes = [C.c_void_p] * 8 + [C.c_int32]
+    check(L.orbgpu_sim3_solve(C.byref(q), _p(counts), _p(R), _p(t), _p(s), _p(T12), _p(inl), C.byref(res), device_id))
+    out = res.as_dict()
+    out.update(counts=counts[:H], R=R, t=t, s=float(s[0]), T12=T12, inliers=inl[:n1])
+    return out
+
+
+def sim3_solve_all(problem_host, device_id=0):
+    """Every hypothesis of one candidate over host arrays (orbgpu_sim3_solve_all).  problem_host: a dict as sim3_problem
+    takes it, with HOST addresses.  Returns a dict: the result record's fields, counts [H], R [H][3][3], t [H][3], s [H],
+    T12 [H][4][4], masks [H][words] uint64."""
+    q = sim3_problem(problem_host)
+    H, words = q.n_hyp, (q.n1 + 63) // 64
+    counts = np.zeros(max(H, 1), np.int32)
+    R, t, s = np.zeros((max(H, 1), 3, 3), np.float32), np.zeros((max(H, 1), 3), np.float32), np.zeros(max(H, 1), np.float32)
+    T12, masks, res = np.zeros((max(H, 1), 4, 4), np.float32), np.zeros((max(H, 1), max(words, 1)), np.uint64), Sim3Result()
+    L = lib()
+    L.orbgpu_sim3_solve_all.argtypes = [C.c_void_p] * 8 + [C.c_int32]
+    check(L.orbgpu_sim3_solve_all(C.byref(q), _p(counts), _p(R), _p(t), _p(s), _p(T12), _p(masks), C.byref(res), device_id))
+    out = res.as_dict()
+    out.update(counts=counts[:H], R=R[:H], t=t[:H], s=s[:H], T12=T12[:H], masks=masks[:H, :words])
+    return out
 
 
 def distinctive_descriptors(groups, device_id=0):

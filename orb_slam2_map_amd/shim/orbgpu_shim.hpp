@@ -1041,6 +1041,193 @@ template <typename FrameT, typename MapPointT> class OptimizerT {
 };
 
 // --------------------------------------------------------------------------------------------
+// Sim3Solver (reference include/Sim3Solver.h, src/Sim3Solver.cc): the Sim3 of a loop candidate.  The conventions are H1-H8
+// of include/orbgpu.h.
+// --------------------------------------------------------------------------------------------
+// DUtils::Random::RandomInt over a caller's rand(): int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min
+template <typename Rand> inline int Sim3ReferenceRandomInt(Rand rand_fn, int rand_max, int min, int max)
+{
+    const int d = max - min + 1;
+    return int(((double)rand_fn() / ((double)rand_max + 1.0)) * d) + min;
+}
+
+// The draw of Sim3Solver::iterate (:163-177) replayed for `iterations` iterations over n correspondences: it overwrites
+// vAvailableIndices[idx], not [randi], so one point can be drawn twice, and after the pop it may write at position size()
+// or size() + 1 -- here into an array that keeps n entries.  random_int(min, max) is called three times per iteration.
+// n < 3 (the reference would call RandomInt(0, -1) and read an empty vector) and a random_int outside [min, max] are
+// refused with std::invalid_argument, as tests/sim3_model.py refuses them.
+template <typename RandomInt> inline std::vector<int32_t> Sim3SampleTriples(int n, int iterations, RandomInt random_int)
+{
+    if (n < 3)
+        throw std::invalid_argument("Sim3SampleTriples: fewer than 3 correspondences");
+    std::vector<int32_t> out((size_t)std::max(iterations, 0) * 3, 0);
+    std::vector<int32_t> avail((size_t)n);
+    for (int it = 0; it < iterations; it++) {
+        for (int i = 0; i < n; i++)
+            avail[i] = i;
+        int size = n;
+        for (int i = 0; i < 3; i++) {
+            const int randi = random_int(0, size - 1);
+            if (randi < 0 || randi >= size)
+                throw std::invalid_argument("Sim3SampleTriples: RandomInt outside [min, max]");
+            const int idx = avail[randi];
+            out[3 * (size_t)it + i] = idx;
+            avail[idx] = avail[size - 1];
+            size--;
+        }
+    }
+    return out;
+}
+
+// KeyFrameT needs GetMapPointMatches(), mvKeysUn, mvLevelSigma2, fx, fy, cx, cy; MapPointT isBad() and
+// GetIndexInKeyFrame(KeyFrameT *).  pose(pKF) returns the 16 floats of Tcw, world_pos(pMP) 3 floats (both valid during the
+// constructor); random_int(min, max) stands for DUtils::Random::RandomInt.  The triples of all max_its iterations are
+// drawn up front, the library is called once (orbgpu_sim3_solve_all), on the first iterate, and every iterate(n, ...) is
+// then served from the stored counts, masks and transformations with the reference's persistent state (mnIterations,
+// mnBestInliers).  With fewer than 3 kept correspondences no minimal set exists (the reference reads an empty vector
+// there): iterate reports bNoMore, whatever minInliers is.
+template <typename KeyFrameT, typename MapPointT> class Sim3SolverT {
+  public:
+    template <typename PoseOf, typename WorldPos, typename RandomInt>
+    Sim3SolverT(KeyFrameT *pKF1, KeyFrameT *pKF2, const std::vector<MapPointT *> &vpMatched12, bool bFixScale, PoseOf pose,
+                WorldPos world_pos, RandomInt random_int, int device_id = 0)
+        : random_int_(random_int), device_id_(device_id), fix_scale_(bFixScale)
+    {
+        const std::vector<MapPointT *> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+        mN1 = (int)vpMatched12.size();
+        valid_.assign((size_t)mN1, 0), o1_.assign((size_t)mN1, 0), o2_.assign((size_t)mN1, 0);
+        x1_.assign(3 * (size_t)mN1, 0.f), x2_.assign(3 * (size_t)mN1, 0.f);
+        nlevels_ = (int)std::min(pKF1->mvLevelSigma2.size(), (size_t)ORBGPU_MAX_LEVELS);
+        N = 0;
+        for (int i1 = 0; i1 < mN1; i1++) {
+            MapPointT *pMP1 = vpKeyFrameMP1[i1], *pMP2 = vpMatched12[i1];
+            if (!pMP2 || !pMP1 || pMP1->isBad() || pMP2->isBad())
+                continue;
+            const int indexKF1 = pMP1->GetIndexInKeyFrame(pKF1), indexKF2 = pMP2->GetIndexInKeyFrame(pKF2);
+            if (indexKF1 < 0 || indexKF2 < 0)
+                continue;
+            valid_[i1] = 1;
+            o1_[i1] = pKF1->mvKeysUn[indexKF1].octave, o2_[i1] = pKF2->mvKeysUn[indexKF2].octave;
+            std::memcpy(&x1_[3 * (size_t)i1], world_pos(pMP1), 12);
+            std::memcpy(&x2_[3 * (size_t)i1], world_pos(pMP2), 12);
+            if (o1_[i1] >= 0 && o1_[i1] < nlevels_ && o2_[i1] >= 0 && o2_[i1] < nlevels_)
+                N++;  // H1: the rows the library keeps
+        }
+        std::memset(&p_, 0, sizeof(p_));
+        std::memcpy(p_.T1w, pose(pKF1), 64);
+        std::memcpy(p_.T2w, pose(pKF2), 64);
+        p_.fx1 = pKF1->fx, p_.fy1 = pKF1->fy, p_.cx1 = pKF1->cx, p_.cy1 = pKF1->cy;
+        p_.fx2 = pKF2->fx, p_.fy2 = pKF2->fy, p_.cx2 = pKF2->cx, p_.cy2 = pKF2->cy;
+        for (int l = 0; l < nlevels_; l++)
+            p_.level_sigma2[l] = pKF1->mvLevelSigma2[l];
+        SetRansacParameters();
+    }
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300)
+    {
+        mRansacProb = probability, mRansacMinInliers = minInliers;
+        int32_t its = 1;
+        check(orbgpu_sim3_ransac_iterations(N, probability, minInliers, maxIterations, &its), "Sim3Solver::SetRansacParameters");
+        mRansacMaxIts = its;
+        mnIterations = 0;
+        solved_ = false;  // the triples depend on max_its
+    }
+
+    // cv::Mat-free form of iterate: returns the accepted iteration's T12 (16 floats, valid until the next call) or nullptr
+    const float *iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers)
+    {
+        bNoMore = false;
+        vbInliers.assign((size_t)mN1, false);
+        nInliers = 0;
+        if (N < mRansacMinInliers || N < 3) {
+            bNoMore = true;
+            return nullptr;
+        }
+        if (!solved_)
+            Solve();
+        int nCurrentIterations = 0;
+        while (mnIterations < mRansacMaxIts && nCurrentIterations < nIterations) {
+            nCurrentIterations++;
+            const int it = mnIterations++;
+            if (counts_[it] >= mnBestInliers) {
+                mnBestInliers = counts_[it], best_ = it;
+                if (counts_[it] > mRansacMinInliers) {
+                    nInliers = counts_[it];
+                    const size_t words = ((size_t)mN1 + 63) / 64;
+                    for (int i = 0; i < mN1; i++)
+                        vbInliers[i] = (masks_[(size_t)it * words + ((size_t)i >> 6)] >> (i & 63)) & 1u;
+                    return &T12_[16 * (size_t)it];
+                }
+            }
+        }
+        if (mnIterations >= mRansacMaxIts)
+            bNoMore = true;
+        return nullptr;
+    }
+
+    const float *find(std::vector<bool> &vbInliers12, int &nInliers)
+    {
+        bool bFlag;
+        return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers);
+    }
+
+    // of the best iteration so far (mBestRotation ...); nullptr / 0 before any iteration
+    const float *GetEstimatedRotation() const { return best_ < 0 ? nullptr : &R_[9 * (size_t)best_]; }
+    const float *GetEstimatedTranslation() const { return best_ < 0 ? nullptr : &t_[3 * (size_t)best_]; }
+    float GetEstimatedScale() const { return best_ < 0 ? 0.f : s_[(size_t)best_]; }
+
+    int NumCorrespondences() const { return N; }
+    int MaxIterations() const { return mRansacMaxIts; }
+    int Iterations() const { return mnIterations; }
+    const std::vector<int32_t> &Triples() const { return triples_; }
+
+    // The answer of the library for hypotheses [0, max_its): what Solve() stores.  Public so that a test can serve
+    // iterate() from recorded counts without a device.
+    void LoadResults(const int32_t *counts, const uint64_t *masks, const float *R, const float *t, const float *s,
+                     const float *T12)
+    {
+        const size_t H = (size_t)mRansacMaxIts, words = ((size_t)mN1 + 63) / 64;
+        counts_.assign(counts, counts + H);
+        masks_.assign(masks, masks + H * words);
+        R_.assign(R, R + 9 * H), t_.assign(t, t + 3 * H), s_.assign(s, s + H), T12_.assign(T12, T12 + 16 * H);
+        solved_ = true;
+    }
+
+    void DrawTriples() { triples_ = Sim3SampleTriples(N, mRansacMaxIts, random_int_); }
+
+  private:
+    void Solve()
+    {
+        DrawTriples();
+        const size_t H = (size_t)mRansacMaxIts, words = ((size_t)mN1 + 63) / 64;
+        p_.n1 = mN1, p_.n_hyp = (int32_t)H;
+        p_.valid = valid_.data(), p_.Xw1 = x1_.data(), p_.Xw2 = x2_.data(), p_.octave1 = o1_.data(), p_.octave2 = o2_.data();
+        p_.triples = triples_.data();
+        p_.nlevels = nlevels_, p_.fix_scale = fix_scale_, p_.min_inliers = mRansacMinInliers;
+        p_.max_iterations = mRansacMaxIts, p_.probability = mRansacProb;
+        counts_.assign(H, 0), masks_.assign(H * words, 0);
+        R_.assign(9 * H, 0.f), t_.assign(3 * H, 0.f), s_.assign(H, 0.f), T12_.assign(16 * H, 0.f);
+        orbgpu_sim3_result r;
+        check(orbgpu_sim3_solve_all(&p_, counts_.data(), R_.data(), t_.data(), s_.data(), T12_.data(), masks_.data(), &r,
+                                    device_id_),
+              "Sim3Solver");
+        solved_ = true;
+    }
+
+    std::function<int(int, int)> random_int_;
+    int device_id_ = 0;
+    bool fix_scale_ = false, solved_ = false;
+    int mN1 = 0, N = 0, nlevels_ = 0;
+    double mRansacProb = 0.99;
+    int mRansacMinInliers = 6, mRansacMaxIts = 300, mnIterations = 0, mnBestInliers = 0, best_ = -1;
+    orbgpu_sim3_problem p_;
+    std::vector<uint8_t> valid_;
+    std::vector<int32_t> o1_, o2_, triples_, counts_;
+    std::vector<float> x1_, x2_, R_, t_, s_, T12_;
+    std::vector<uint64_t> masks_;
+};
+
+// --------------------------------------------------------------------------------------------
 // PointCloudMapping (reference include/PointCloudMap.h:41-88, src/PointCloudMap.cc)
 // Keeps the reference's thread / condition-variable protocol; the per-key-frame arithmetic runs on
 // the GPU.  KeyFrameT needs mImDep (float depth), mImRGB (8UC3), fx, fy, cx, cy and GetPose();
