@@ -14,7 +14,7 @@
 // those cached lists and fall back to an exact full scan of a row when its list cannot decide.
 #include "common.h"
 #include "matcher_common.h"
-#include "workspace.h"
+#include "staging.h"
 
 #include <algorithm>
 #include <climits>
@@ -762,76 +762,69 @@ static int match_host(const uint8_t *desc_a, const float *angle_a, const uint8_t
         *nmatches = 0;
         return ORBGPU_OK;
     }
-    // per-thread workspace (matcher handle + staging buffers) reused across calls: the reference builds an
+    // per-thread workspace (matcher handle + staging buffers, staging.h) reused across calls: the reference builds an
     // ORBmatcher on the stack per call site, so allocating per call would dominate the kernel time
-    struct Ws {
-        int device = -1, cap = 0;
+    enum { DA, DB, AA, AB, VA, CNT, MB, NM, NDA, NDB, N_BUF };
+    struct Ws : Staging<N_BUF> {
+        int cap = 0;
         orbgpu_matcher *m = nullptr;
-        hipStream_t st = nullptr;
-        DevBuf da, db, aa, ab, va, cnt, mb, nm, nda, ndb;
-        ~Ws()  // end of the owning thread: release, unless the process is exiting (workspace.h)
+        void drop_matcher()
         {
-            if (device < 0 || process_exiting().load())
-                return;
-            (void)hipSetDevice(device);
-            if (st)
-                (void)hipStreamSynchronize(st);
             if (m)
                 orbgpu_matcher_destroy(m);
-            for (DevBuf *b : {&da, &db, &aa, &ab, &va, &cnt, &mb, &nm, &nda, &ndb})
-                b->release();
-            if (st)
-                (void)hipStreamDestroy(st);
+            m = nullptr;
         }
+        ~Ws() { release([this] { drop_matcher(); }); }
     };
     int rc = select_device(device_id);
     if (rc != ORBGPU_OK)
         return rc;
     Ws &ws = per_device_workspace<Ws>(device_id);  // stream, matcher handle and buffers of THIS device
+    if ((rc = ws.bind(device_id, true)) != ORBGPU_OK)  // before the matcher exists: an unbound workspace owns nothing
+        return rc;
     const int need = std::max(na, nb);
-    if (ws.device != device_id || ws.cap < need) {
-        if (ws.m)
-            orbgpu_matcher_destroy(ws.m);
-        ws.m = nullptr;
-        const int cap = std::min(4096, std::max(need, 1024));
-        if ((rc = orbgpu_matcher_create(device_id, 1, cap, &ws.m)) != ORBGPU_OK)
+    if (ws.cap < need) {
+        ws.drop_matcher();
+        ws.cap = 0;
+        const size_t cap = (size_t)std::min(4096, std::max(need, 1024));
+        if ((rc = orbgpu_matcher_create(device_id, 1, (int32_t)cap, &ws.m)) != ORBGPU_OK)
             return rc;
-        if (!ws.st)
-            ORBGPU_HIP_TRY(hipStreamCreateWithFlags(&ws.st, hipStreamNonBlocking));
-        if ((rc = ws.da.reserve((size_t)cap * 32)) != ORBGPU_OK || (rc = ws.db.reserve((size_t)cap * 32)) != ORBGPU_OK ||
-            (rc = ws.aa.reserve((size_t)cap * 4)) != ORBGPU_OK || (rc = ws.ab.reserve((size_t)cap * 4)) != ORBGPU_OK ||
-            (rc = ws.va.reserve((size_t)cap)) != ORBGPU_OK || (rc = ws.cnt.reserve(8)) != ORBGPU_OK ||
-            (rc = ws.mb.reserve((size_t)cap * 4)) != ORBGPU_OK || (rc = ws.nm.reserve(4)) != ORBGPU_OK ||
-            (rc = ws.nda.reserve((size_t)cap * 4)) != ORBGPU_OK || (rc = ws.ndb.reserve((size_t)cap * 4)) != ORBGPU_OK)
+        for (int i : {DA, DB})
+            ws.reserve(i, cap * 32);
+        for (int i : {AA, AB, MB, NDA, NDB})
+            ws.reserve(i, cap * 4);
+        ws.reserve(VA, cap);
+        ws.reserve(CNT, 8);
+        ws.reserve(NM, 4);
+        if ((rc = ws.status()) != ORBGPU_OK)
             return rc;
-        ws.device = device_id;
-        ws.cap = cap;
+        ws.cap = (int)cap;
     }
-    const int cap = ws.cap;
-    hipStream_t st = ws.st;
-    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.da.p, desc_a, (size_t)na * 32, hipMemcpyHostToDevice, st));
-    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.db.p, desc_b, (size_t)nb * 32, hipMemcpyHostToDevice, st));
+    Ws::FinishOnError on_error{ws};
+    ws.upload(DA, desc_a, (size_t)na * 32);
+    ws.upload(DB, desc_b, (size_t)nb * 32);
     if (check_orientation) {
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.aa.p, angle_a, (size_t)na * 4, hipMemcpyHostToDevice, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.ab.p, angle_b, (size_t)nb * 4, hipMemcpyHostToDevice, st));
+        ws.upload(AA, angle_a, (size_t)na * 4);
+        ws.upload(AB, angle_b, (size_t)nb * 4);
     }
     if (valid_a)
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.va.p, valid_a, (size_t)na, hipMemcpyHostToDevice, st));
+        ws.upload(VA, valid_a, (size_t)na);
     if (node_a) {
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.nda.p, node_a, (size_t)na * 4, hipMemcpyHostToDevice, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.ndb.p, node_b, (size_t)nb * 4, hipMemcpyHostToDevice, st));
+        ws.upload(NDA, node_a, (size_t)na * 4);
+        ws.upload(NDB, node_b, (size_t)nb * 4);
     }
     const int counts[2] = {na, nb};
-    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.cnt.p, counts, 8, hipMemcpyHostToDevice, st));
-    if ((rc = match_batch_device(ws.m, 1, cap, ws.da.as<uint8_t>(), ws.aa.p, valid_a ? ws.va.as<uint8_t>() : nullptr,
-                                 node_a ? ws.nda.as<int>() : nullptr, ws.cnt.as<int>(), ws.db.as<uint8_t>(), ws.ab.p,
-                                 node_a ? ws.ndb.as<int>() : nullptr, ws.cnt.as<int>() + 1, 4, th_low, nnratio,
-                                 check_orientation, ws.mb.as<int>(), ws.nm.as<int>(), st)) != ORBGPU_OK)
+    ws.upload(CNT, counts, 8);
+    if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
-    ORBGPU_HIP_TRY(hipMemcpyAsync(match_b, ws.mb.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-    ORBGPU_HIP_TRY(hipMemcpyAsync(nmatches, ws.nm.p, 4, hipMemcpyDeviceToHost, st));
-    ORBGPU_HIP_TRY(hipStreamSynchronize(st));
-    return ORBGPU_OK;
+    if ((rc = match_batch_device(ws.m, 1, ws.cap, ws.as<uint8_t>(DA), ws.buf[AA].p, valid_a ? ws.as<uint8_t>(VA) : nullptr,
+                                 node_a ? ws.as<int>(NDA) : nullptr, ws.as<int>(CNT), ws.as<uint8_t>(DB), ws.buf[AB].p,
+                                 node_a ? ws.as<int>(NDB) : nullptr, ws.as<int>(CNT) + 1, 4, th_low, nnratio,
+                                 check_orientation, ws.as<int>(MB), ws.as<int>(NM), ws.stream)) != ORBGPU_OK)
+        return rc;
+    ws.download(match_b, MB, (size_t)nb * 4);
+    ws.download(nmatches, NM, 4);
+    return ws.finish();
 }
 
 int orbgpu_match_bf(const uint8_t *desc_a, const float *angle_a, const uint8_t *valid_a, int32_t na,

@@ -15,7 +15,7 @@
 // only a row whose 16 cached candidates cannot decide is walked again with the claim filter.
 #include "common.h"
 #include "matcher_common.h"
-#include "workspace.h"
+#include "staging.h"
 #include "proj_internal.h"
 
 #include <algorithm>
@@ -610,71 +610,28 @@ static inline size_t resolve_lds(int /*m*/, int ncap, int *novf)
 }
 
 // ---- host side -----------------------------------------------------------------------------
-// Per-thread workspace: device buffers that grow on demand and are reused by every call of this host
+// Per-thread workspace (staging.h): device buffers that grow on demand and are reused by every call of this host
 // thread (the reference constructs an ORBmatcher on the stack per call site; allocation per call would
 // dominate the kernel time).
-struct ProjWorkspace {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    unsigned attr_set = 0;  // bit per call site: the dynamic-LDS limit of its kernels has been raised ON THIS DEVICE
-    DevBuf kp_x, kp_y, kp_octave, u_right, desc, cell_start, cell_items, kp_angle;
-    DevBuf queries, row_desc, row_angle, claim_init, topk, match, slow, k2m, out, inv_sigma2, tri, problems, sweeps;
-    void release_device_resources()
-    {
-        DevBuf *bufs[] = {&kp_x,  &kp_y,  &kp_octave, &u_right, &desc, &cell_start, &cell_items, &kp_angle, &queries, &row_desc, &row_angle,
-                          &claim_init, &topk, &match, &slow, &k2m, &out, &inv_sigma2, &tri, &problems, &sweeps};
-        for (DevBuf *b : bufs)
-            b->release();
-        if (stream)
-            (void)hipStreamDestroy(stream);
-        stream = nullptr;
-    }
-    ~ProjWorkspace()
-    {
-        // end of the owning thread (or proj_workspace_delete): give the stream and the buffers back -- unless the process
-        // is exiting, when the HIP runtime may already be gone and everything goes with the process (workspace.h)
-        if (device >= 0 && !process_exiting().load()) {
-            (void)hipSetDevice(device);
-            if (stream)
-                (void)hipStreamSynchronize(stream);
-            release_device_resources();
-        }
-    }
+enum {
+    W_KP_X, W_KP_Y, W_KP_OCTAVE, W_U_RIGHT, W_DESC, W_CELL_START, W_CELL_ITEMS, W_KP_ANGLE,  // the uploaded frame
+    W_QUERIES, W_ROW_DESC, W_ROW_ANGLE, W_CLAIM_INIT, W_TOPK, W_MATCH, W_SLOW, W_K2M, W_OUT, W_INV_SIGMA2, W_TRI,
+    W_PROBLEMS, W_SWEEPS, W_N_BUF
+};
+struct ProjWorkspace : Staging<W_N_BUF> {
+    bool attr_set = false;  // the dynamic-LDS limit of the resolve kernels has been raised ON THIS DEVICE
 };
 
 // A caller that brings its own workspace (the MapPoint table: its calls run on the table's stream and must not share
 // buffers with asynchronous calls the same thread has in flight on another stream) installs it for the duration of a call.
 static thread_local ProjWorkspace *t_ws_override = nullptr;
 ProjWorkspace *proj_workspace_new() { return new (std::nothrow) ProjWorkspace(); }
-void proj_workspace_delete(ProjWorkspace *ws) { delete ws; }  // the destructor releases
+void proj_workspace_delete(ProjWorkspace *ws) { delete ws; }  // the same release as at the end of a thread
 ProjWorkspaceScope::ProjWorkspaceScope(ProjWorkspace *ws) : prev_(t_ws_override) { t_ws_override = ws; }
 ProjWorkspaceScope::~ProjWorkspaceScope() { t_ws_override = prev_; }
 
-static int workspace(int device_id, ProjWorkspace **out)
-{
-    ProjWorkspace &ws = t_ws_override ? *t_ws_override : per_device_workspace<ProjWorkspace>(device_id);  // (the caller has selected device_id)
-    if (ws.device != device_id) {  // first use of this device by this thread
-        ws.device = device_id;
-        hipError_t e = hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            ws.device = -1;
-            set_error("hipStreamCreate: %s", hipGetErrorString(e));
-            return ORBGPU_EHIP;
-        }
-    }
-    *out = &ws;
-    return ORBGPU_OK;
-}
-
-static int put(DevBuf &b, const void *src, size_t bytes, hipStream_t st)
-{
-    int rc = b.reserve(std::max<size_t>(bytes, 16));
-    if (rc != ORBGPU_OK)
-        return rc;
-    if (src && bytes)
-        ORBGPU_HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
-    return ORBGPU_OK;
-}
+// the calling thread's workspace (or the installed one), bound to device_id, which the caller has selected
+static int workspace(int device_id, ProjWorkspace **out);
 
 int validate_frame(const orbgpu_frame_view *f)
 {
@@ -695,91 +652,123 @@ int validate_frame(const orbgpu_frame_view *f)
     return ORBGPU_OK;
 }
 
-#define PJ_TRY(x)                                                                                            \
-    do {                                                                                                     \
-        int rc__ = (x);                                                                                      \
-        if (rc__ != ORBGPU_OK)                                                                               \
-            return rc__;                                                                                     \
-    } while (0)
-
 static int upload_frame(ProjWorkspace &ws, const orbgpu_frame_view *f, FrameDev &F)
 {
     const size_t n = (size_t)f->n;
-    hipStream_t st = ws.stream;
-    PJ_TRY(put(ws.kp_x, f->kp_x, n * 4, st));
-    PJ_TRY(put(ws.kp_y, f->kp_y, n * 4, st));
-    PJ_TRY(put(ws.kp_octave, f->kp_octave, n * 4, st));
-    PJ_TRY(put(ws.u_right, f->u_right, n * 4, st));
-    PJ_TRY(put(ws.desc, f->desc, n * 32, st));
-    PJ_TRY(put(ws.cell_start, f->cell_start, (size_t)(GC * GR + 1) * 4, st));
-    PJ_TRY(put(ws.cell_items, f->cell_items, std::max<size_t>((size_t)f->cell_start[GC * GR], 1) * 4, st));
+    ws.put(W_KP_X, f->kp_x, n * 4);
+    ws.put(W_KP_Y, f->kp_y, n * 4);
+    ws.put(W_KP_OCTAVE, f->kp_octave, n * 4);
+    ws.put(W_U_RIGHT, f->u_right, n * 4);
+    ws.put(W_DESC, f->desc, n * 32);
+    ws.put(W_CELL_START, f->cell_start, (size_t)(GC * GR + 1) * 4);
+    ws.put(W_CELL_ITEMS, f->cell_items, std::max<size_t>((size_t)f->cell_start[GC * GR], 1) * 4);
     F.n = f->n;
     F.n_dev = nullptr;
     F.kp_stride = 1;
-    F.kp_x = ws.kp_x.as<float>();
-    F.kp_y = ws.kp_y.as<float>();
-    F.kp_octave = ws.kp_octave.as<int>();
-    F.u_right = ws.u_right.as<float>();
-    F.desc = ws.desc.as<uint8_t>();
+    F.kp_x = ws.as<float>(W_KP_X);
+    F.kp_y = ws.as<float>(W_KP_Y);
+    F.kp_octave = ws.as<int>(W_KP_OCTAVE);
+    F.u_right = ws.as<float>(W_U_RIGHT);
+    F.desc = ws.as<uint8_t>(W_DESC);
     F.min_x = f->min_x;
     F.min_y = f->min_y;
     F.inv_w = f->grid_inv_w;
     F.inv_h = f->grid_inv_h;
-    F.cell_start = ws.cell_start.as<int>();
-    F.cell_items = ws.cell_items.as<int>();
+    F.cell_start = ws.as<int>(W_CELL_START);
+    F.cell_items = ws.as<int>(W_CELL_ITEMS);
     F.inv_sigma2 = nullptr;
-    return ORBGPU_OK;
+    return ws.status();
 }
 
-// Runs pass 1 + pass 2 for prepared queries. kp_to_mp (host, in/out).
+// a frame straight out of the extractor: device arrays, device-resident count
+static FrameDev device_frame(const orbgpu_device_frame_view &f)
+{
+    FrameDev F;
+    F.n = f.cap;
+    F.n_dev = f.n;
+    F.kp_stride = (int)(sizeof(orbgpu_keypoint) / sizeof(float));
+    F.kp_x = reinterpret_cast<const float *>(f.kps);
+    F.kp_y = F.kp_x + 1;
+    F.kp_octave = reinterpret_cast<const int *>(f.kps) + 5;
+    F.u_right = f.u_right, F.desc = f.desc;
+    F.min_x = f.min_x, F.min_y = f.min_y;
+    F.inv_w = (float)GC / (f.max_x - f.min_x);  // Frame.cc:155-156
+    F.inv_h = (float)GR / (f.max_y - f.min_y);
+    F.cell_start = f.cell_start, F.cell_items = f.cell_items;
+    F.inv_sigma2 = nullptr;
+    return F;
+}
+
+// what the device flavours need for m rows against cap key point slots
+static int reserve_rows(ProjWorkspace &ws, size_t m, size_t cap)
+{
+    ws.reserve(W_QUERIES, sizeof(Query) * m);
+    ws.reserve(W_CLAIM_INIT, sizeof(int) * cap);
+    ws.reserve(W_TOPK, sizeof(uint32_t) * PJ_LIST * m);
+    ws.reserve(W_MATCH, sizeof(int) * m);
+    ws.reserve(W_SLOW, sizeof(int) * m);
+    ws.reserve(W_OUT, 4 * sizeof(int));
+    return ws.status();
+}
+
+// Uploads the frame and runs pass 1 + pass 2 for prepared queries on the calling thread's workspace (the caller has
+// selected device_id). kp_to_mp (host, in/out).  inv_sigma2: Fuse's gates (Query::gate).
 template <int MODE>
-static int run_projection(ProjWorkspace &ws, const FrameDev &F, const std::vector<Query> &queries,
+static int run_projection(int device_id, const orbgpu_frame_view *f, const std::vector<Query> &queries,
                           const uint8_t *row_desc_host, const float *row_angle_host, const float *kp_angle_host,
                           const std::vector<int> &claim_init, float nnratio, int th_dist, int check_orientation,
-                          int32_t *kp_to_mp, int32_t *nmatches, int32_t *row_match = nullptr)
+                          int32_t *kp_to_mp, int32_t *nmatches, int32_t *row_match = nullptr,
+                          const float *inv_sigma2 = nullptr)
 {
-    const int m = (int)queries.size(), n = F.n;
+    const int m = (int)queries.size(), n = f->n;
     if (m == 0 || n == 0) {
         *nmatches = 0;
         for (int i = 0; row_match && i < m; i++)
             row_match[i] = -1;
         return ORBGPU_OK;
     }
+    ProjWorkspace *wsp = nullptr;
+    int rc = workspace(device_id, &wsp);
+    if (rc != ORBGPU_OK)
+        return rc;
+    ProjWorkspace &ws = *wsp;
+    ProjWorkspace::FinishOnError on_error{ws};
+    FrameDev F;
+    if ((rc = upload_frame(ws, f, F)) != ORBGPU_OK)
+        return rc;
+    if (inv_sigma2) {
+        ws.put(W_INV_SIGMA2, inv_sigma2, sizeof(float) * f->nlevels);
+        F.inv_sigma2 = ws.as<float>(W_INV_SIGMA2);
+    }
     hipStream_t st = ws.stream;
-    PJ_TRY(put(ws.queries, queries.data(), sizeof(Query) * m, st));
-    PJ_TRY(put(ws.row_desc, row_desc_host, (size_t)m * 32, st));
-    PJ_TRY(put(ws.claim_init, claim_init.data(), sizeof(int) * n, st));
-    PJ_TRY(put(ws.k2m, kp_to_mp, sizeof(int) * n, st));
-    PJ_TRY(ws.topk.reserve(sizeof(uint32_t) * PJ_LIST * (size_t)m));
-    PJ_TRY(ws.match.reserve(sizeof(int) * m));
-    PJ_TRY(ws.slow.reserve(sizeof(int) * m));
-    PJ_TRY(ws.out.reserve(4 * sizeof(int)));
+    ws.put(W_QUERIES, queries.data(), sizeof(Query) * m);
+    ws.put(W_ROW_DESC, row_desc_host, (size_t)m * 32);
+    ws.put(W_CLAIM_INIT, claim_init.data(), sizeof(int) * n);
+    ws.put(W_K2M, kp_to_mp, sizeof(int) * n);
+    ws.reserve(W_TOPK, sizeof(uint32_t) * PJ_LIST * (size_t)m);
+    ws.reserve(W_MATCH, sizeof(int) * m);
+    ws.reserve(W_SLOW, sizeof(int) * m);
+    ws.reserve(W_OUT, 4 * sizeof(int));
     if (check_orientation) {
-        PJ_TRY(put(ws.row_angle, row_angle_host, sizeof(float) * m, st));
-        PJ_TRY(put(ws.kp_angle, kp_angle_host, sizeof(float) * n, st));
+        ws.put(W_ROW_ANGLE, row_angle_host, sizeof(float) * m);
+        ws.put(W_KP_ANGLE, kp_angle_host, sizeof(float) * n);
     }
-    if (!(ws.attr_set & 1u)) {
-        ORBGPU_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_proj_resolve<0>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)PJ_RESOLVE_MAX_LDS + 64));
-        ORBGPU_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_proj_resolve<1>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)PJ_RESOLVE_MAX_LDS + 64));
-        ws.attr_set |= 1u;
-    }
-    hipLaunchKernelGGL(k_proj_lists, dim3((m + PJ_ROWS_PER_BLOCK - 1) / PJ_ROWS_PER_BLOCK), dim3(256), 0, st, m, ws.queries.as<Query>(),
-                       ws.row_desc.as<uint8_t>(), F, ws.topk.as<uint32_t>());
+    if (ws.status() != ORBGPU_OK)
+        return ws.status();
+    hipLaunchKernelGGL(k_proj_lists, dim3((m + PJ_ROWS_PER_BLOCK - 1) / PJ_ROWS_PER_BLOCK), dim3(256), 0, st, m, ws.as<Query>(W_QUERIES),
+                       ws.as<uint8_t>(W_ROW_DESC), F, ws.as<uint32_t>(W_TOPK));
     int novf = 0;
     const size_t lds = resolve_lds(m, n, &novf);
-    hipLaunchKernelGGL(k_proj_resolve<MODE>, dim3(1), dim3(1024), lds, st, m, ws.queries.as<Query>(),
-                       ws.row_desc.as<uint8_t>(), F, nnratio, th_dist, ws.claim_init.as<int>(), ws.topk.as<uint32_t>(),
-                       ws.match.as<int>(), ws.slow.as<int>(), ws.row_angle.as<float>(), 1, ws.kp_angle.as<float>(),
-                       check_orientation, ws.k2m.as<int>(), ws.out.as<int>(), ws.out.as<int>() + 1, novf);
+    hipLaunchKernelGGL(k_proj_resolve<MODE>, dim3(1), dim3(1024), lds, st, m, ws.as<Query>(W_QUERIES),
+                       ws.as<uint8_t>(W_ROW_DESC), F, nnratio, th_dist, ws.as<int>(W_CLAIM_INIT), ws.as<uint32_t>(W_TOPK),
+                       ws.as<int>(W_MATCH), ws.as<int>(W_SLOW), ws.as<float>(W_ROW_ANGLE), 1, ws.as<float>(W_KP_ANGLE),
+                       check_orientation, ws.as<int>(W_K2M), ws.as<int>(W_OUT), ws.as<int>(W_OUT) + 1, novf);
     ORBGPU_HIP_TRY(hipGetLastError());
-    ORBGPU_HIP_TRY(hipMemcpyAsync(kp_to_mp, ws.k2m.p, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-    ORBGPU_HIP_TRY(hipMemcpyAsync(nmatches, ws.out.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    ws.download(kp_to_mp, W_K2M, sizeof(int) * n);
+    ws.download(nmatches, W_OUT, sizeof(int));
     if (row_match)  // the decision of every row (key point index or -1): what the claim-free matchers return
-        ORBGPU_HIP_TRY(hipMemcpyAsync(row_match, ws.match.p, sizeof(int) * m, hipMemcpyDeviceToHost, st));
-    ORBGPU_HIP_TRY(hipStreamSynchronize(st));
-    return ORBGPU_OK;
+        ws.download(row_match, W_MATCH, sizeof(int) * m);
+    return ws.finish();
 }
 
 // cv::Mat 3x3 * 3x1 + 3x1 (CV_32F): cv::gemm small-matrix path -> float products summed left to
@@ -1013,6 +1002,23 @@ __global__ __launch_bounds__(1024) void k_proj_resolve_batch(const ProjProblem *
         return;
     proj_resolve_body<0>(p.m, p.q, p.desc, p.F, p.nnratio, (int)ORBGPU_TH_HIGH, p.claim_init, p.lists, p.match, p.slow,
                          (const float *)nullptr, 1, (const float *)nullptr, 0, p.kp_to_mp, p.counts, p.sweeps, p.novf);
+}
+
+// (defined here, below the last of the three kernels it names)
+static int workspace(int device_id, ProjWorkspace **out)
+{
+    ProjWorkspace &ws = t_ws_override ? *t_ws_override : per_device_workspace<ProjWorkspace>(device_id);
+    int rc = ws.bind(device_id, true);
+    if (rc != ORBGPU_OK)
+        return rc;
+    if (!ws.attr_set) {  // first use of this device by this workspace: the resolve kernels may take their full LDS
+        for (const void *k : {reinterpret_cast<const void *>(k_proj_resolve<0>), reinterpret_cast<const void *>(k_proj_resolve<1>),
+                              reinterpret_cast<const void *>(k_proj_resolve_batch)})
+            ORBGPU_HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PJ_RESOLVE_MAX_LDS + 64));
+        ws.attr_set = true;
+    }
+    *out = &ws;
+    return ORBGPU_OK;
 }
 
 // ---- device-resident ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (:1328-1470) --------
@@ -1327,13 +1333,7 @@ int orbgpu_search_by_projection(const orbgpu_frame_view *f, const orbgpu_mappoin
         const bool held = v == -2 || (v >= 0 && (mp->obs_pos ? mp->obs_pos[v] != 0 : true));
         init[j] = held ? -1 : INT_MAX;
     }
-    ProjWorkspace *ws = nullptr;
-    if ((rc = workspace(device_id, &ws)) != ORBGPU_OK)
-        return rc;
-    FrameDev F;
-    if ((rc = upload_frame(*ws, f, F)) != ORBGPU_OK)
-        return rc;
-    return run_projection<0>(*ws, F, q, mp->desc, nullptr, nullptr, init, nnratio, ORBGPU_TH_HIGH, 0, kp_to_mp, nmatches);
+    return run_projection<0>(device_id, f, q, mp->desc, nullptr, nullptr, init, nnratio, ORBGPU_TH_HIGH, 0, kp_to_mp, nmatches);
 }
 
 int orbgpu_search_local_points_device(const orbgpu_device_frame_view *f, const orbgpu_device_mappoint_table *mp,
@@ -1375,12 +1375,8 @@ int orbgpu::search_local_points_device_impl(const orbgpu_device_frame_view *f, c
     if ((rc = workspace(device_id, &ws)) != ORBGPU_OK)
         return rc;
     const int m = mp->m, cap = f->cap;
-    PJ_TRY(ws->queries.reserve(sizeof(Query) * (size_t)m));
-    PJ_TRY(ws->claim_init.reserve(sizeof(int) * (size_t)cap));
-    PJ_TRY(ws->topk.reserve(sizeof(uint32_t) * PJ_LIST * (size_t)m));
-    PJ_TRY(ws->match.reserve(sizeof(int) * (size_t)m));
-    PJ_TRY(ws->slow.reserve(sizeof(int) * (size_t)m));
-    PJ_TRY(ws->out.reserve(4 * sizeof(int)));
+    if ((rc = reserve_rows(*ws, (size_t)m, (size_t)cap)) != ORBGPU_OK)
+        return rc;
     FrustumParams P{};
     if (!scratch) {
         for (int r = 0; r < 3; r++)
@@ -1394,45 +1390,25 @@ int orbgpu::search_local_points_device_impl(const orbgpu_device_frame_view *f, c
     P.nlevels = f->nlevels;
     for (int l = 0; l < ORBGPU_MAX_LEVELS; l++)
         P.scale_factors[l] = l < f->nlevels ? f->scale_factors[l] : 0.f;
-    FrameDev F;
-    F.n = cap;
-    F.n_dev = f->n;
-    F.kp_stride = (int)(sizeof(orbgpu_keypoint) / sizeof(float));
-    F.kp_x = reinterpret_cast<const float *>(f->kps);
-    F.kp_y = F.kp_x + 1;
-    F.kp_octave = reinterpret_cast<const int *>(f->kps) + 5;
-    F.u_right = f->u_right;
-    F.desc = f->desc;
-    F.min_x = f->min_x;
-    F.min_y = f->min_y;
-    F.inv_w = (float)GC / (f->max_x - f->min_x);  // Frame.cc:155-156
-    F.inv_h = (float)GR / (f->max_y - f->min_y);
-    F.cell_start = f->cell_start;
-    F.cell_items = f->cell_items;
-    F.inv_sigma2 = nullptr;
-    if (!(ws->attr_set & 2u)) {
-        ORBGPU_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_proj_resolve<0>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)PJ_RESOLVE_MAX_LDS + 64));
-        ws->attr_set |= 2u;
-    }
+    const FrameDev F = device_frame(*f);
     orbgpu_track_scratch none{};
     const int cover = std::max(m, cap);
     if (scratch)
         hipLaunchKernelGGL(k_scratch_queries, dim3((cover + 255) / 256), dim3(256), 0, st, m, *scratch, mp->skip, mp->obs_pos,
-                           th, f->nlevels, P, ws->queries.as<Query>(), cap, d_kp_to_mp, ws->claim_init.as<int>(),
+                           th, f->nlevels, P, ws->as<Query>(W_QUERIES), cap, d_kp_to_mp, ws->as<int>(W_CLAIM_INIT),
                            d_counts + 1);
     else
         hipLaunchKernelGGL(k_frustum_queries, dim3((cover + 255) / 256), dim3(256), 0, st, m, mp->world_pos, mp->normal,
-                           mp->min_dist, mp->max_dist, mp->skip, mp->obs_pos, P, ws->queries.as<Query>(), cap, d_kp_to_mp,
-                           ws->claim_init.as<int>(), d_track ? *d_track : none, d_counts + 1);
-    hipLaunchKernelGGL(k_proj_lists, dim3((m + PJ_ROWS_PER_BLOCK - 1) / PJ_ROWS_PER_BLOCK), dim3(256), 0, st, m, ws->queries.as<Query>(), mp->desc, F,
-                       ws->topk.as<uint32_t>());
+                           mp->min_dist, mp->max_dist, mp->skip, mp->obs_pos, P, ws->as<Query>(W_QUERIES), cap, d_kp_to_mp,
+                           ws->as<int>(W_CLAIM_INIT), d_track ? *d_track : none, d_counts + 1);
+    hipLaunchKernelGGL(k_proj_lists, dim3((m + PJ_ROWS_PER_BLOCK - 1) / PJ_ROWS_PER_BLOCK), dim3(256), 0, st, m, ws->as<Query>(W_QUERIES), mp->desc, F,
+                       ws->as<uint32_t>(W_TOPK));
     int novf = 0;
     const size_t lds = resolve_lds(m, cap, &novf);
-    hipLaunchKernelGGL(k_proj_resolve<0>, dim3(1), dim3(1024), lds, st, m, ws->queries.as<Query>(), mp->desc,
-                       F, nnratio, (int)ORBGPU_TH_HIGH, ws->claim_init.as<int>(), ws->topk.as<uint32_t>(),
-                       ws->match.as<int>(), ws->slow.as<int>(), (const float *)nullptr, 1, (const float *)nullptr, 0,
-                       d_kp_to_mp, d_counts, ws->out.as<int>() + 1, novf);
+    hipLaunchKernelGGL(k_proj_resolve<0>, dim3(1), dim3(1024), lds, st, m, ws->as<Query>(W_QUERIES), mp->desc,
+                       F, nnratio, (int)ORBGPU_TH_HIGH, ws->as<int>(W_CLAIM_INIT), ws->as<uint32_t>(W_TOPK),
+                       ws->as<int>(W_MATCH), ws->as<int>(W_SLOW), (const float *)nullptr, 1, (const float *)nullptr, 0,
+                       d_kp_to_mp, d_counts, ws->as<int>(W_OUT) + 1, novf);
     ORBGPU_HIP_TRY(hipGetLastError());
     return ORBGPU_OK;
 }
@@ -1464,12 +1440,8 @@ int orbgpu_search_by_projection_last_device(const orbgpu_device_frame_view *cur,
     if ((rc = workspace(device_id, &ws)) != ORBGPU_OK)
         return rc;
     const int m = last->cap, cap = cur->cap;
-    PJ_TRY(ws->queries.reserve(sizeof(Query) * (size_t)m));
-    PJ_TRY(ws->claim_init.reserve(sizeof(int) * (size_t)cap));
-    PJ_TRY(ws->topk.reserve(sizeof(uint32_t) * PJ_LIST * (size_t)m));
-    PJ_TRY(ws->match.reserve(sizeof(int) * (size_t)m));
-    PJ_TRY(ws->slow.reserve(sizeof(int) * (size_t)m));
-    PJ_TRY(ws->out.reserve(4 * sizeof(int)));
+    if ((rc = reserve_rows(*ws, (size_t)m, (size_t)cap)) != ORBGPU_OK)
+        return rc;
     // :1339-1349 forward / backward motion from the two poses (host: 2 x 12 floats)
     float twc[3], tlc[3];
     minus_rt_t(cur_Tcw, twc);
@@ -1486,41 +1458,21 @@ int orbgpu_search_by_projection_last_device(const orbgpu_device_frame_view *cur,
     P.nlevels = cur->nlevels;
     for (int l = 0; l < ORBGPU_MAX_LEVELS; l++)
         P.scale_factors[l] = l < cur->nlevels ? cur->scale_factors[l] : 0.f;
-    FrameDev F;
-    F.n = cap;
-    F.n_dev = cur->n;
-    F.kp_stride = (int)(sizeof(orbgpu_keypoint) / sizeof(float));
-    F.kp_x = reinterpret_cast<const float *>(cur->kps);
-    F.kp_y = F.kp_x + 1;
-    F.kp_octave = reinterpret_cast<const int *>(cur->kps) + 5;
-    F.u_right = cur->u_right;
-    F.desc = cur->desc;
-    F.min_x = cur->min_x;
-    F.min_y = cur->min_y;
-    F.inv_w = (float)GC / (cur->max_x - cur->min_x);  // Frame.cc:155-156
-    F.inv_h = (float)GR / (cur->max_y - cur->min_y);
-    F.cell_start = cur->cell_start;
-    F.cell_items = cur->cell_items;
-    F.inv_sigma2 = nullptr;
-    if (!(ws->attr_set & 4u)) {
-        ORBGPU_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_proj_resolve<1>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)PJ_RESOLVE_MAX_LDS + 64));
-        ws->attr_set |= 4u;
-    }
+    const FrameDev F = device_frame(*cur);
     const int cover = std::max(m, cap);
     const int kstride = (int)(sizeof(orbgpu_keypoint) / sizeof(float));
     hipLaunchKernelGGL(k_project_last_queries, dim3((cover + 255) / 256), dim3(256), 0, st, m, last->n, last->kps,
-                       last->has_mp, last->outlier, last->obs_pos, last->world_pos, P, ws->queries.as<Query>(), cap,
-                       d_kp_to_mp, ws->claim_init.as<int>(), d_counts + 1);
-    hipLaunchKernelGGL(k_proj_lists, dim3((m + PJ_ROWS_PER_BLOCK - 1) / PJ_ROWS_PER_BLOCK), dim3(256), 0, st, m, ws->queries.as<Query>(), last->desc, F,
-                       ws->topk.as<uint32_t>());
+                       last->has_mp, last->outlier, last->obs_pos, last->world_pos, P, ws->as<Query>(W_QUERIES), cap,
+                       d_kp_to_mp, ws->as<int>(W_CLAIM_INIT), d_counts + 1);
+    hipLaunchKernelGGL(k_proj_lists, dim3((m + PJ_ROWS_PER_BLOCK - 1) / PJ_ROWS_PER_BLOCK), dim3(256), 0, st, m, ws->as<Query>(W_QUERIES), last->desc, F,
+                       ws->as<uint32_t>(W_TOPK));
     int novf = 0;
     const size_t lds = resolve_lds(m, cap, &novf);
-    hipLaunchKernelGGL(k_proj_resolve<1>, dim3(1), dim3(1024), lds, st, m, ws->queries.as<Query>(),
-                       last->desc, F, 0.f, (int)ORBGPU_TH_HIGH, ws->claim_init.as<int>(), ws->topk.as<uint32_t>(),
-                       ws->match.as<int>(), ws->slow.as<int>(), reinterpret_cast<const float *>(last->kps) + 3, kstride,
+    hipLaunchKernelGGL(k_proj_resolve<1>, dim3(1), dim3(1024), lds, st, m, ws->as<Query>(W_QUERIES),
+                       last->desc, F, 0.f, (int)ORBGPU_TH_HIGH, ws->as<int>(W_CLAIM_INIT), ws->as<uint32_t>(W_TOPK),
+                       ws->as<int>(W_MATCH), ws->as<int>(W_SLOW), reinterpret_cast<const float *>(last->kps) + 3, kstride,
                        reinterpret_cast<const float *>(cur->kps) + 3, check_orientation ? 1 : 0, d_kp_to_mp, d_counts,
-                       ws->out.as<int>() + 1, novf);
+                       ws->as<int>(W_OUT) + 1, novf);
     ORBGPU_HIP_TRY(hipGetLastError());
     return ORBGPU_OK;
 }
@@ -1558,14 +1510,10 @@ int orbgpu_search_local_points_batch_device(int32_t n, const orbgpu_local_points
         max_cover = std::max(max_cover, std::max(mp->m, f->cap));
         lds = std::max(lds, resolve_lds(mp->m, f->cap, &novfs[k]));
     }
-    PJ_TRY(ws->queries.reserve(sizeof(Query) * tot_m));
-    PJ_TRY(ws->claim_init.reserve(sizeof(int) * tot_cap));
-    PJ_TRY(ws->topk.reserve(sizeof(uint32_t) * PJ_LIST * tot_m));
-    PJ_TRY(ws->match.reserve(sizeof(int) * tot_m));
-    PJ_TRY(ws->slow.reserve(sizeof(int) * tot_m));
-    PJ_TRY(ws->sweeps.reserve(sizeof(int) * 2 * (size_t)n));
-    PJ_TRY(ws->problems.reserve(sizeof(ProjProblem) * (size_t)n));
-    PJ_TRY(ws->out.reserve(4 * sizeof(int)));
+    ws->reserve(W_SWEEPS, sizeof(int) * 2 * (size_t)n);
+    ws->reserve(W_PROBLEMS, sizeof(ProjProblem) * (size_t)n);
+    if ((rc = reserve_rows(*ws, tot_m, tot_cap)) != ORBGPU_OK)
+        return rc;
     std::vector<ProjProblem> hp((size_t)n);
     size_t om = 0, oc = 0;
     for (int k = 0; k < n; k++) {
@@ -1587,25 +1535,13 @@ int orbgpu_search_local_points_batch_device(int32_t n, const orbgpu_local_points
         P.P.nlevels = f->nlevels;
         for (int l = 0; l < ORBGPU_MAX_LEVELS; l++)
             P.P.scale_factors[l] = l < f->nlevels ? f->scale_factors[l] : 0.f;
-        P.F.n = f->cap;
-        P.F.n_dev = f->n;
-        P.F.kp_stride = (int)(sizeof(orbgpu_keypoint) / sizeof(float));
-        P.F.kp_x = reinterpret_cast<const float *>(f->kps);
-        P.F.kp_y = P.F.kp_x + 1;
-        P.F.kp_octave = reinterpret_cast<const int *>(f->kps) + 5;
-        P.F.u_right = f->u_right;
-        P.F.desc = f->desc;
-        P.F.min_x = f->min_x, P.F.min_y = f->min_y;
-        P.F.inv_w = (float)GC / (f->max_x - f->min_x);
-        P.F.inv_h = (float)GR / (f->max_y - f->min_y);
-        P.F.cell_start = f->cell_start, P.F.cell_items = f->cell_items;
-        P.F.inv_sigma2 = nullptr;
-        P.q = ws->queries.as<Query>() + om;
-        P.lists = ws->topk.as<uint32_t>() + om * PJ_LIST;
-        P.match = ws->match.as<int>() + om;
-        P.slow = ws->slow.as<int>() + om;
-        P.claim_init = ws->claim_init.as<int>() + oc;
-        P.sweeps = ws->sweeps.as<int>() + 2 * (size_t)k;
+        P.F = device_frame(*f);
+        P.q = ws->as<Query>(W_QUERIES) + om;
+        P.lists = ws->as<uint32_t>(W_TOPK) + om * PJ_LIST;
+        P.match = ws->as<int>(W_MATCH) + om;
+        P.slow = ws->as<int>(W_SLOW) + om;
+        P.claim_init = ws->as<int>(W_CLAIM_INIT) + oc;
+        P.sweeps = ws->as<int>(W_SWEEPS) + 2 * (size_t)k;
         P.kp_to_mp = pr.d_kp_to_mp;
         P.counts = pr.d_counts;
         P.nnratio = nnratio;
@@ -1614,13 +1550,8 @@ int orbgpu_search_local_points_batch_device(int32_t n, const orbgpu_local_points
         om += (size_t)std::max(mp->m, 1);
         oc += (size_t)f->cap;
     }
-    ORBGPU_HIP_TRY(hipMemcpyAsync(ws->problems.p, hp.data(), sizeof(ProjProblem) * (size_t)n, hipMemcpyHostToDevice, st));
-    if (!(ws->attr_set & 8u)) {
-        ORBGPU_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_proj_resolve_batch),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)PJ_RESOLVE_MAX_LDS + 64));
-        ws->attr_set |= 8u;
-    }
-    const ProjProblem *dp = ws->problems.as<ProjProblem>();
+    ORBGPU_HIP_TRY(hipMemcpyAsync(ws->buf[W_PROBLEMS].p, hp.data(), sizeof(ProjProblem) * (size_t)n, hipMemcpyHostToDevice, st));
+    const ProjProblem *dp = ws->as<ProjProblem>(W_PROBLEMS);
     hipLaunchKernelGGL(k_batch_zero_counts, dim3((n + 255) / 256), dim3(256), 0, st, dp, n);
     if (max_m > 0) {
         hipLaunchKernelGGL(k_frustum_queries_batch, dim3((max_cover + 255) / 256, n), dim3(256), 0, st, dp);
@@ -1635,18 +1566,16 @@ int orbgpu_projection_last_sweeps(int32_t *sweeps, int32_t *rewalked_rows)
 {
     // convergence diagnostics of the calling thread's most recent projection match (any of the four entry points)
     ORBGPU_REQUIRE(sweeps && rewalked_rows, "null argument");
-    static thread_local int dummy;
-    (void)dummy;
     ProjWorkspace *ws = nullptr;
     int dev = 0;
     ORBGPU_HIP_TRY(hipGetDevice(&dev));
     int rc = workspace(dev, &ws);
     if (rc != ORBGPU_OK)
         return rc;
-    ORBGPU_REQUIRE(ws->out.p, "no projection match recorded on this thread");
+    ORBGPU_REQUIRE(ws->buf[W_OUT].p, "no projection match recorded on this thread");
     ORBGPU_HIP_TRY(hipDeviceSynchronize());
     int h[2] = {0, 0};
-    ORBGPU_HIP_TRY(hipMemcpy(h, ws->out.as<int>() + 1, sizeof(h), hipMemcpyDeviceToHost));
+    ORBGPU_HIP_TRY(hipMemcpy(h, ws->as<int>(W_OUT) + 1, sizeof(h), hipMemcpyDeviceToHost));
     *sweeps = h[0];
     *rewalked_rows = h[1];
     return ORBGPU_OK;
@@ -1728,13 +1657,7 @@ int orbgpu_search_by_projection_last(const orbgpu_frame_view *cur, const float *
         const bool held = v == -2 || (v >= 0 && (last->obs_pos ? last->obs_pos[v] != 0 : true));
         init[j] = held ? -1 : INT_MAX;
     }
-    ProjWorkspace *ws = nullptr;
-    if ((rc = workspace(device_id, &ws)) != ORBGPU_OK)
-        return rc;
-    FrameDev F;
-    if ((rc = upload_frame(*ws, cur, F)) != ORBGPU_OK)
-        return rc;
-    return run_projection<1>(*ws, F, q, last->desc, last->kp_angle, cur->kp_angle, init, 0.f, ORBGPU_TH_HIGH,
+    return run_projection<1>(device_id, cur, q, last->desc, last->kp_angle, cur->kp_angle, init, 0.f, ORBGPU_TH_HIGH,
                              check_orientation, kp_to_mp, nmatches);
 }
 
@@ -1804,13 +1727,7 @@ int orbgpu_search_by_projection_keyframe(const orbgpu_frame_view *cur, const flo
     for (int j = 0; j < cur->n; j++)
         init[j] = kp_to_mp[j] == -1 ? INT_MAX : -1;
     // the matcher writes indices of `kf` rows; occupied key points keep their value
-    ProjWorkspace *ws = nullptr;
-    if ((rc = workspace(device_id, &ws)) != ORBGPU_OK)
-        return rc;
-    FrameDev F;
-    if ((rc = upload_frame(*ws, cur, F)) != ORBGPU_OK)
-        return rc;
-    return run_projection<1>(*ws, F, q, kf->desc, kf->kp_angle, cur->kp_angle, init, 0.f, orb_dist, check_orientation,
+    return run_projection<1>(device_id, cur, q, kf->desc, kf->kp_angle, cur->kp_angle, init, 0.f, orb_dist, check_orientation,
                              kp_to_mp, nmatches);
 }
 
@@ -1896,13 +1813,7 @@ int orbgpu_search_by_projection_sim3(const orbgpu_frame_view *kf, const float *S
     std::vector<int> init((size_t)std::max(kf->n, 1));
     for (int j = 0; j < kf->n; j++)
         init[j] = kp_to_mp[j] == -1 ? INT_MAX : -1;  // :373 vpMatched[idx] set: skipped
-    ProjWorkspace *ws = nullptr;
-    if ((rc = workspace(device_id, &ws)) != ORBGPU_OK)
-        return rc;
-    FrameDev F;
-    if ((rc = upload_frame(*ws, kf, F)) != ORBGPU_OK)
-        return rc;
-    return run_projection<1>(*ws, F, q, pts->desc, nullptr, nullptr, init, 0.f, ORBGPU_TH_LOW, 0, kp_to_mp, nmatches);
+    return run_projection<1>(device_id, kf, q, pts->desc, nullptr, nullptr, init, 0.f, ORBGPU_TH_LOW, 0, kp_to_mp, nmatches);
 }
 
 // ---- claim-free "best key point in the window" matchers: Fuse, Fuse(Sim3), SearchBySim3 ---------------------
@@ -1963,21 +1874,11 @@ static int validate_points(const orbgpu_points_view *pts, bool need_normal)
 static int best_rows(const orbgpu_frame_view *kf, std::vector<Query> &q, const uint8_t *row_desc, int th_dist,
                      const float *inv_sigma2, int32_t *best_idx, int32_t device_id)
 {
-    ProjWorkspace *ws = nullptr;
-    int rc = workspace(device_id, &ws);
-    if (rc != ORBGPU_OK)
-        return rc;
-    FrameDev F;
-    if ((rc = upload_frame(*ws, kf, F)) != ORBGPU_OK)
-        return rc;
-    if (inv_sigma2) {
-        PJ_TRY(put(ws->inv_sigma2, inv_sigma2, sizeof(float) * kf->nlevels, ws->stream));
-        F.inv_sigma2 = ws->inv_sigma2.as<float>();
-    }
     std::vector<int> init((size_t)std::max(kf->n, 1), INT_MAX);  // nothing is claimed, nobody blocks
     std::vector<int32_t> k2m((size_t)std::max(kf->n, 1), -1);
     int32_t nm = 0;
-    return run_projection<1>(*ws, F, q, row_desc, nullptr, nullptr, init, 0.f, th_dist, 0, k2m.data(), &nm, best_idx);
+    return run_projection<1>(device_id, kf, q, row_desc, nullptr, nullptr, init, 0.f, th_dist, 0, k2m.data(), &nm, best_idx,
+                             inv_sigma2);
 }
 
 } // namespace
@@ -2208,29 +2109,31 @@ int orbgpu_search_for_triangulation(const orbgpu_frame_view *kf1, const uint8_t 
     const size_t w1 = (size_t)n1, w2 = (size_t)n2;
     const size_t off_desc1 = 0, off_desc2 = 32 * w1, off_arr = 32 * (w1 + w2), off_f1 = off_arr + 4 * (5 * w1 + 6 * w2),
                  off_f2 = off_f1 + w1, off_out = ((off_f2 + w2 + 15) / 16) * 16, total = off_out + 4 * w1 + 16;
-    PJ_TRY(ws->tri.reserve(total));
-    uint8_t *base = ws->tri.as<uint8_t>();
-    auto up = [&](size_t off, const void *src, size_t bytes) -> int {
-        ORBGPU_HIP_TRY(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, st));
-        return ORBGPU_OK;
-    };
+    ws->reserve(W_TRI, total);
+    if ((rc = ws->status()) != ORBGPU_OK)
+        return rc;
+    ProjWorkspace::FinishOnError on_error{*ws};
+    uint8_t *base = ws->as<uint8_t>(W_TRI);
+    auto up = [&](size_t off, const void *src, size_t bytes) { ws->upload(W_TRI, src, bytes, off); };
     std::vector<float> zeros(std::max(w1, w2), 0.f);
     size_t o = off_arr;
-    const size_t o_x1 = o; PJ_TRY(up(o, kf1->kp_x, 4 * w1)); o += 4 * w1;
-    const size_t o_y1 = o; PJ_TRY(up(o, kf1->kp_y, 4 * w1)); o += 4 * w1;
-    const size_t o_u1 = o; PJ_TRY(up(o, kf1->u_right, 4 * w1)); o += 4 * w1;
-    const size_t o_n1 = o; PJ_TRY(up(o, node1, 4 * w1)); o += 4 * w1;
-    const size_t o_a1 = o; PJ_TRY(up(o, check_orientation ? kf1->kp_angle : zeros.data(), 4 * w1)); o += 4 * w1;
-    const size_t o_x2 = o; PJ_TRY(up(o, kf2->kp_x, 4 * w2)); o += 4 * w2;
-    const size_t o_y2 = o; PJ_TRY(up(o, kf2->kp_y, 4 * w2)); o += 4 * w2;
-    const size_t o_u2 = o; PJ_TRY(up(o, kf2->u_right, 4 * w2)); o += 4 * w2;
-    const size_t o_n2 = o; PJ_TRY(up(o, node2, 4 * w2)); o += 4 * w2;
-    const size_t o_o2 = o; PJ_TRY(up(o, kf2->kp_octave, 4 * w2)); o += 4 * w2;
-    const size_t o_a2 = o; PJ_TRY(up(o, check_orientation ? kf2->kp_angle : zeros.data(), 4 * w2)); o += 4 * w2;
-    PJ_TRY(up(off_desc1, kf1->desc, 32 * w1));
-    PJ_TRY(up(off_desc2, kf2->desc, 32 * w2));
-    PJ_TRY(up(off_f1, has_mp1, w1));
-    PJ_TRY(up(off_f2, has_mp2, w2));
+    const size_t o_x1 = o; up(o, kf1->kp_x, 4 * w1); o += 4 * w1;
+    const size_t o_y1 = o; up(o, kf1->kp_y, 4 * w1); o += 4 * w1;
+    const size_t o_u1 = o; up(o, kf1->u_right, 4 * w1); o += 4 * w1;
+    const size_t o_n1 = o; up(o, node1, 4 * w1); o += 4 * w1;
+    const size_t o_a1 = o; up(o, check_orientation ? kf1->kp_angle : zeros.data(), 4 * w1); o += 4 * w1;
+    const size_t o_x2 = o; up(o, kf2->kp_x, 4 * w2); o += 4 * w2;
+    const size_t o_y2 = o; up(o, kf2->kp_y, 4 * w2); o += 4 * w2;
+    const size_t o_u2 = o; up(o, kf2->u_right, 4 * w2); o += 4 * w2;
+    const size_t o_n2 = o; up(o, node2, 4 * w2); o += 4 * w2;
+    const size_t o_o2 = o; up(o, kf2->kp_octave, 4 * w2); o += 4 * w2;
+    const size_t o_a2 = o; up(o, check_orientation ? kf2->kp_angle : zeros.data(), 4 * w2); o += 4 * w2;
+    up(off_desc1, kf1->desc, 32 * w1);
+    up(off_desc2, kf2->desc, 32 * w2);
+    up(off_f1, has_mp1, w1);
+    up(off_f2, has_mp2, w2);
+    if ((rc = ws->status()) != ORBGPU_OK)
+        return rc;
     TriParams P;
     for (int k = 0; k < 9; k++)
         P.F12[k] = F12[k];
@@ -2250,10 +2153,9 @@ int orbgpu_search_for_triangulation(const orbgpu_frame_view *kf1, const uint8_t 
 #undef TRI_F
 #undef TRI_I
     ORBGPU_HIP_TRY(hipGetLastError());
-    ORBGPU_HIP_TRY(hipMemcpyAsync(match12, d_match, 4 * w1, hipMemcpyDeviceToHost, st));
-    ORBGPU_HIP_TRY(hipMemcpyAsync(nmatches, d_n, 4, hipMemcpyDeviceToHost, st));
-    ORBGPU_HIP_TRY(hipStreamSynchronize(st));
-    return ORBGPU_OK;
+    ws->download(match12, W_TRI, 4 * w1, off_out);
+    ws->download(nmatches, W_TRI, 4, off_out + 4 * w1);
+    return ws->finish();
 }
 
 int orbgpu_search_for_initialization(const orbgpu_frame_view *f1, const orbgpu_frame_view *f2, float *prev_matched,
@@ -2297,22 +2199,27 @@ int orbgpu_search_for_initialization(const orbgpu_frame_view *f1, const orbgpu_f
     ProjWorkspace *ws = nullptr;
     if ((rc = workspace(device_id, &ws)) != ORBGPU_OK)
         return rc;
+    ProjWorkspace::FinishOnError on_error{*ws};
     FrameDev F;
     if ((rc = upload_frame(*ws, f2, F)) != ORBGPU_OK)
         return rc;
     hipStream_t st = ws->stream;
     const int cap = n2;
-    PJ_TRY(put(ws->queries, q.data(), sizeof(Query) * rows, st));
-    PJ_TRY(put(ws->row_desc, rdesc.data(), (size_t)rows * 32, st));
-    PJ_TRY(ws->tri.reserve(sizeof(uint64_t) * (size_t)rows * cap + sizeof(int) * (size_t)rows + 64));
-    uint64_t *d_keys = ws->tri.as<uint64_t>();
+    ws->put(W_QUERIES, q.data(), sizeof(Query) * rows);
+    ws->put(W_ROW_DESC, rdesc.data(), (size_t)rows * 32);
+    ws->reserve(W_TRI, sizeof(uint64_t) * (size_t)rows * cap + sizeof(int) * (size_t)rows + 64);
+    if ((rc = ws->status()) != ORBGPU_OK)
+        return rc;
+    uint64_t *d_keys = ws->as<uint64_t>(W_TRI);
     int *d_counts = reinterpret_cast<int *>(d_keys + (size_t)rows * cap);
-    hipLaunchKernelGGL(k_window_candidates, dim3((rows + 3) / 4), dim3(256), 0, st, rows, ws->queries.as<Query>(),
-                       ws->row_desc.as<uint8_t>(), F, cap, d_keys, d_counts);
+    hipLaunchKernelGGL(k_window_candidates, dim3((rows + 3) / 4), dim3(256), 0, st, rows, ws->as<Query>(W_QUERIES),
+                       ws->as<uint8_t>(W_ROW_DESC), F, cap, d_keys, d_counts);
     ORBGPU_HIP_TRY(hipGetLastError());
     std::vector<int> counts((size_t)rows);
-    ORBGPU_HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, sizeof(int) * (size_t)rows, hipMemcpyDeviceToHost, st));
-    ORBGPU_HIP_TRY(hipStreamSynchronize(st));
+    const size_t off_counts = sizeof(uint64_t) * (size_t)rows * cap;
+    ws->download(counts.data(), W_TRI, sizeof(int) * (size_t)rows, off_counts);
+    if ((rc = ws->finish()) != ORBGPU_OK)
+        return rc;
     std::vector<size_t> off((size_t)rows + 1, 0);
     for (int r = 0; r < rows; r++) {
         ORBGPU_REQUIRE(counts[r] <= cap, "window candidate list overflow");  // cannot happen: cap = all key points
@@ -2321,9 +2228,9 @@ int orbgpu_search_for_initialization(const orbgpu_frame_view *f1, const orbgpu_f
     std::vector<uint64_t> keys(std::max<size_t>(off[rows], 1));
     for (int r = 0; r < rows; r++)
         if (counts[r])
-            ORBGPU_HIP_TRY(hipMemcpyAsync(&keys[off[r]], d_keys + (size_t)r * cap, sizeof(uint64_t) * (size_t)counts[r],
-                                          hipMemcpyDeviceToHost, st));
-    ORBGPU_HIP_TRY(hipStreamSynchronize(st));
+            ws->download(&keys[off[r]], W_TRI, sizeof(uint64_t) * (size_t)counts[r], sizeof(uint64_t) * (size_t)r * cap);
+    if ((rc = ws->finish()) != ORBGPU_OK)
+        return rc;
     // ---- the sequential part of the reference, verbatim, over the device-computed distances (:414-517)
     std::vector<int> vMatchedDistance((size_t)n2, INT_MAX), vnMatches21((size_t)n2, -1);
     std::vector<std::pair<int, int>> pushes;  // (bin, i1) in push order

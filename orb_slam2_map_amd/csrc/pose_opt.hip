@@ -10,7 +10,7 @@
 #include <vector>
 
 #include "common.h"
-#include "workspace.h"
+#include "staging.h"
 
 namespace orbgpu {
 
@@ -537,26 +537,10 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblemDev *_
     }
 }
 
-// Per (thread, device) staging of the entry points, like the matchers' workspaces (workspace.h).
-struct PoseWs {
-    int device = -1;
-    hipStream_t stream = nullptr;  // host flavour only
-    DevBuf problems, spill, spill_count;
-    DevBuf h_kps, h_ur, h_k2m, h_wp, h_n, h_out, h_res;  // host flavour: the uploaded problem
-    ~PoseWs()
-    {
-        if (device >= 0 && !process_exiting().load()) {
-            (void)hipSetDevice(device);
-            if (stream) {
-                (void)hipStreamSynchronize(stream);
-                (void)hipStreamDestroy(stream);
-            }
-            DevBuf *bufs[] = {&problems, &spill, &spill_count, &h_kps, &h_ur, &h_k2m, &h_wp, &h_n, &h_out, &h_res};
-            for (DevBuf *b : bufs)
-                b->release();
-        }
-    }
-};
+// Per (thread, device) staging of the entry points (staging.h); the stream and the H_* buffers (the uploaded problem)
+// are the host flavour's.
+enum { PROBLEMS, SPILL, SPILL_COUNT, H_KPS, H_UR, H_K2M, H_WP, H_N, H_OUT, H_RES, N_BUF };
+struct PoseWs : Staging<N_BUF> {};
 
 static int lds_edge_limit()
 {
@@ -596,15 +580,17 @@ extern "C" int orbgpu_pose_optimization_batch_device(int32_t n, const orbgpu_pos
     if (rc != ORBGPU_OK || n == 0)
         return rc;
     PoseWs &ws = per_device_workspace<PoseWs>(device_id);
-    ws.device = device_id;
+    if ((rc = ws.bind(device_id, false)) != ORBGPU_OK)
+        return rc;
     const int lds_edges = lds_edge_limit();
     size_t spill_edges = 0;
     for (int k = 0; k < n; k++)
         if (problems[k].frame->cap > lds_edges)
             spill_edges += (size_t)problems[k].frame->cap;
-    if ((rc = ws.problems.reserve(sizeof(PoseProblemDev) * (size_t)n)) != ORBGPU_OK ||
-        (rc = ws.spill.reserve(2 * sizeof(float4) * std::max<size_t>(spill_edges, 1))) != ORBGPU_OK ||
-        (rc = ws.spill_count.reserve(sizeof(int32_t))) != ORBGPU_OK)
+    ws.reserve(PROBLEMS, sizeof(PoseProblemDev) * (size_t)n);
+    ws.reserve(SPILL, 2 * sizeof(float4) * std::max<size_t>(spill_edges, 1));
+    ws.reserve(SPILL_COUNT, sizeof(int32_t));
+    if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
     std::vector<PoseProblemDev> hp((size_t)n);
     size_t so = 0;
@@ -616,9 +602,9 @@ extern "C" int orbgpu_pose_optimization_batch_device(int32_t n, const orbgpu_pos
         D.n = f->n, D.kps = f->kps, D.u_right = f->u_right, D.kp_to_mp = p.d_kp_to_mp, D.world_pos = p.d_world_pos;
         D.outlier = p.d_outlier, D.result = p.d_result;
         D.cap = f->cap, D.rows = p.rows, D.nlevels = f->nlevels, D.lds_edges = lds_edges;
-        D.spill_count = ws.spill_count.as<int32_t>();
+        D.spill_count = ws.as<int32_t>(SPILL_COUNT);
         if (f->cap > lds_edges) {
-            D.spill = ws.spill.as<float4>() + 2 * so;
+            D.spill = ws.as<float4>(SPILL) + 2 * so;
             so += (size_t)f->cap;
         }
         for (int l = 0; l < f->nlevels; l++)
@@ -639,9 +625,9 @@ extern "C" int orbgpu_pose_optimization_batch_device(int32_t n, const orbgpu_pos
         D.delta2[0] = D.delta[0] * D.delta[0], D.delta2[1] = D.delta[1] * D.delta[1];
     }
     const hipStream_t st = (hipStream_t)hip_stream;
-    ORBGPU_HIP_TRY(hipMemsetAsync(ws.spill_count.p, 0, sizeof(int32_t), st));
-    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.problems.p, hp.data(), sizeof(PoseProblemDev) * (size_t)n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_pose_opt, dim3(n), dim3(PO_THREADS), 0, st, ws.problems.as<PoseProblemDev>());
+    ORBGPU_HIP_TRY(hipMemsetAsync(ws.buf[SPILL_COUNT].p, 0, sizeof(int32_t), st));
+    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.buf[PROBLEMS].p, hp.data(), sizeof(PoseProblemDev) * (size_t)n, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_pose_opt, dim3(n), dim3(PO_THREADS), 0, st, ws.as<PoseProblemDev>(PROBLEMS));
     ORBGPU_HIP_TRY(hipGetLastError());
     return ORBGPU_OK;
 }
@@ -659,9 +645,9 @@ extern "C" int orbgpu_pose_last_spills(int32_t device_id, int32_t *problems_spil
     if (rc != ORBGPU_OK)
         return rc;
     PoseWs &ws = per_device_workspace<PoseWs>(device_id);
-    ORBGPU_REQUIRE(ws.spill_count.p, "no pose optimisation recorded on this thread");
+    ORBGPU_REQUIRE(ws.buf[SPILL_COUNT].p, "no pose optimisation recorded on this thread");
     ORBGPU_HIP_TRY(hipDeviceSynchronize());
-    ORBGPU_HIP_TRY(hipMemcpy(problems_spilled, ws.spill_count.p, sizeof(int32_t), hipMemcpyDeviceToHost));
+    ORBGPU_HIP_TRY(hipMemcpy(problems_spilled, ws.buf[SPILL_COUNT].p, sizeof(int32_t), hipMemcpyDeviceToHost));
     return ORBGPU_OK;
 }
 
@@ -679,56 +665,55 @@ extern "C" int orbgpu_pose_optimization(const orbgpu_frame_view *f, const uint8_
     if (rc != ORBGPU_OK)
         return rc;
     PoseWs &ws = per_device_workspace<PoseWs>(device_id);
-    if (!ws.stream) {
-        hipError_t e = hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            set_error("hipStreamCreate: %s", hipGetErrorString(e));
-            return ORBGPU_EHIP;
-        }
-        ws.device = device_id;
-    }
-    const int n = f->n, cap = std::max(n, 1);
-    if ((rc = ws.h_kps.reserve(sizeof(orbgpu_keypoint) * cap)) != ORBGPU_OK ||
-        (rc = ws.h_ur.reserve(sizeof(float) * cap)) != ORBGPU_OK || (rc = ws.h_k2m.reserve(sizeof(int32_t) * cap)) != ORBGPU_OK ||
-        (rc = ws.h_wp.reserve(3 * sizeof(float) * cap)) != ORBGPU_OK || (rc = ws.h_n.reserve(sizeof(int32_t))) != ORBGPU_OK ||
-        (rc = ws.h_out.reserve(cap)) != ORBGPU_OK || (rc = ws.h_res.reserve(sizeof(orbgpu_pose_result))) != ORBGPU_OK)
+    if ((rc = ws.bind(device_id, true)) != ORBGPU_OK)
         return rc;
-    std::vector<orbgpu_keypoint> kps((size_t)cap);
-    std::vector<int32_t> k2m((size_t)cap);
+    const int n = f->n;
+    const size_t cap = (size_t)std::max(n, 1);
+    ws.reserve(H_KPS, sizeof(orbgpu_keypoint) * cap);
+    ws.reserve(H_UR, sizeof(float) * cap);
+    ws.reserve(H_K2M, sizeof(int32_t) * cap);
+    ws.reserve(H_WP, 3 * sizeof(float) * cap);
+    ws.reserve(H_N, sizeof(int32_t));
+    ws.reserve(H_OUT, cap);
+    ws.reserve(H_RES, sizeof(orbgpu_pose_result));
+    if ((rc = ws.status()) != ORBGPU_OK)
+        return rc;
+    std::vector<orbgpu_keypoint> kps(cap);
+    std::vector<int32_t> k2m(cap);
     for (int i = 0; i < n; i++) {
         orbgpu_keypoint k{};
         k.x = f->kp_x[i], k.y = f->kp_y[i], k.octave = f->kp_octave[i], k.class_id = -1;
         kps[i] = k;
         k2m[i] = has_mp[i] ? i : -1;
     }
-    const hipStream_t st = ws.stream;
+    PoseWs::FinishOnError on_error{ws};
     const int32_t n32 = n;
-    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.h_n.p, &n32, sizeof(n32), hipMemcpyHostToDevice, st));
+    ws.upload(H_N, &n32, sizeof(n32));
     if (n > 0) {
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.h_kps.p, kps.data(), sizeof(orbgpu_keypoint) * n, hipMemcpyHostToDevice, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.h_k2m.p, k2m.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.h_ur.p, f->u_right, sizeof(float) * n, hipMemcpyHostToDevice, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.h_wp.p, world_pos, 3 * sizeof(float) * n, hipMemcpyHostToDevice, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.h_out.p, outlier, n, hipMemcpyHostToDevice, st));
+        ws.upload(H_KPS, kps.data(), sizeof(orbgpu_keypoint) * n);
+        ws.upload(H_K2M, k2m.data(), sizeof(int32_t) * n);
+        ws.upload(H_UR, f->u_right, sizeof(float) * n);
+        ws.upload(H_WP, world_pos, 3 * sizeof(float) * n);
+        ws.upload(H_OUT, outlier, n);
     }
+    if ((rc = ws.status()) != ORBGPU_OK)
+        return rc;
     orbgpu_device_frame_view dv{};
-    dv.cap = n, dv.n = ws.h_n.as<int32_t>(), dv.kps = ws.h_kps.as<orbgpu_keypoint>(), dv.u_right = ws.h_ur.as<float>();
+    dv.cap = n, dv.n = ws.as<int32_t>(H_N), dv.kps = ws.as<orbgpu_keypoint>(H_KPS), dv.u_right = ws.as<float>(H_UR);
     dv.nlevels = f->nlevels;
     orbgpu_pose_problem p{};
-    p.frame = &dv, p.d_kp_to_mp = ws.h_k2m.as<int32_t>(), p.d_world_pos = ws.h_wp.as<float>(), p.rows = n;
+    p.frame = &dv, p.d_kp_to_mp = ws.as<int32_t>(H_K2M), p.d_world_pos = ws.as<float>(H_WP), p.rows = n;
     p.Tcw = Tcw, p.inv_level_sigma2 = inv_level_sigma2;
     p.fx = fx, p.fy = fy, p.cx = cx, p.cy = cy, p.mbf = mbf;
-    p.d_outlier = ws.h_out.as<uint8_t>(), p.d_result = ws.h_res.as<orbgpu_pose_result>();
-    rc = orbgpu_pose_optimization_batch_device(1, &p, device_id, st);
-    if (rc != ORBGPU_OK) {
-        (void)hipStreamSynchronize(st);  // the uploads read the caller's arrays
+    p.d_outlier = ws.as<uint8_t>(H_OUT), p.d_result = ws.as<orbgpu_pose_result>(H_RES);
+    if ((rc = orbgpu_pose_optimization_batch_device(1, &p, device_id, ws.stream)) != ORBGPU_OK)
         return rc;
-    }
     orbgpu_pose_result r;
-    ORBGPU_HIP_TRY(hipMemcpyAsync(&r, ws.h_res.p, sizeof(r), hipMemcpyDeviceToHost, st));
+    ws.download(&r, H_RES, sizeof(r));
     if (n > 0)
-        ORBGPU_HIP_TRY(hipMemcpyAsync(outlier, ws.h_out.p, n, hipMemcpyDeviceToHost, st));
-    ORBGPU_HIP_TRY(hipStreamSynchronize(st));
+        ws.download(outlier, H_OUT, n);
+    if ((rc = ws.finish()) != ORBGPU_OK)
+        return rc;
     memcpy(Tcw, r.Tcw, sizeof(r.Tcw));
     *n_inliers = r.n_inliers;
     if (result)

@@ -9,7 +9,7 @@
 #include <vector>
 
 #include "common.h"
-#include "workspace.h"
+#include "staging.h"
 
 namespace orbgpu {
 
@@ -391,26 +391,13 @@ __global__ void k_sim3_select(const Sim3ProblemDev *__restrict__ problems, int n
     r->iterations = it, r->no_more = no_more;
 }
 
-struct Sim3Ws {
-    int device = -1;
-    hipStream_t stream = nullptr;  // host flavour only
-    DevBuf problems, rec, map, ctl;
-    DevBuf h_in, h_out;            // host flavour: the uploaded problem and its outputs
+// Per (thread, device) staging of the entry points (staging.h); the stream and the two H_* blocks (the uploaded
+// problem and its outputs) are the host flavour's.
+enum { PROBLEMS, REC, MAP, CTL, H_IN, H_OUT, N_BUF };
+struct Sim3Ws : Staging<N_BUF> {
     std::vector<Sim3ProblemDev> h_problems;  // sources of asynchronous uploads: they outlive the call
     std::vector<Sim3Ctl> h_ctl;
-    ~Sim3Ws()
-    {
-        if (device >= 0 && !process_exiting().load()) {
-            (void)hipSetDevice(device);
-            if (stream) {
-                (void)hipStreamSynchronize(stream);
-                (void)hipStreamDestroy(stream);
-            }
-            DevBuf *bufs[] = {&problems, &rec, &map, &ctl, &h_in, &h_out};
-            for (DevBuf *b : bufs)
-                b->release();
-        }
-    }
+    ~Sim3Ws() { release(); }  // the stream is waited for while the vectors are still there
 };
 
 static int ransac_iterations(int n, double probability, int min_inliers, int max_iterations)
@@ -476,17 +463,19 @@ extern "C" int orbgpu_sim3_solve_batch_device(int32_t n, const orbgpu_sim3_probl
     if (rc != ORBGPU_OK || n == 0)
         return rc;
     Sim3Ws &ws = per_device_workspace<Sim3Ws>(device_id);
-    ws.device = device_id;
+    if ((rc = ws.bind(device_id, false)) != ORBGPU_OK)
+        return rc;
     size_t rows = 0;
     int max_hyp = 0;
     for (int k = 0; k < n; k++) {
         rows += (size_t)problems[k].n1;
         max_hyp = std::max(max_hyp, (int)problems[k].n_hyp);
     }
-    if ((rc = ws.problems.reserve(sizeof(Sim3ProblemDev) * (size_t)n)) != ORBGPU_OK ||
-        (rc = ws.rec.reserve(3 * sizeof(float4) * std::max<size_t>(rows, 1))) != ORBGPU_OK ||
-        (rc = ws.map.reserve(sizeof(int32_t) * std::max<size_t>(rows, 1))) != ORBGPU_OK ||
-        (rc = ws.ctl.reserve(sizeof(Sim3Ctl) * (size_t)n)) != ORBGPU_OK)
+    ws.reserve(PROBLEMS, sizeof(Sim3ProblemDev) * (size_t)n);
+    ws.reserve(REC, 3 * sizeof(float4) * std::max<size_t>(rows, 1));
+    ws.reserve(MAP, sizeof(int32_t) * std::max<size_t>(rows, 1));
+    ws.reserve(CTL, sizeof(Sim3Ctl) * (size_t)n);
+    if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
     std::vector<Sim3ProblemDev> &hp = ws.h_problems;
     std::vector<Sim3Ctl> &ctl = ws.h_ctl;
@@ -501,7 +490,7 @@ extern "C" int orbgpu_sim3_solve_batch_device(int32_t n, const orbgpu_sim3_probl
         D.counts = p.counts, D.R = p.R, D.t = p.t, D.s = p.s, D.T12 = p.T12;
         D.masks = reinterpret_cast<unsigned long long *>(p.masks);
         D.indices1 = p.indices1, D.result = p.result;
-        D.rec = ws.rec.as<float4>() + 3 * ro, D.map = ws.map.as<int32_t>() + ro, D.ctl = ws.ctl.as<Sim3Ctl>() + k;
+        D.rec = ws.as<float4>(REC) + 3 * ro, D.map = ws.as<int32_t>(MAP) + ro, D.ctl = ws.as<Sim3Ctl>(CTL) + k;
         ro += (size_t)p.n1;
         D.n1 = p.n1, D.n_hyp = p.n_hyp, D.nlevels = p.nlevels, D.fix_scale = p.fix_scale, D.min_inliers = p.min_inliers;
         D.start_iteration = p.start_iteration, D.best_so_far = p.best_so_far;
@@ -515,10 +504,10 @@ extern "C" int orbgpu_sim3_solve_batch_device(int32_t n, const orbgpu_sim3_probl
         }
     }
     const hipStream_t st = (hipStream_t)hip_stream;
-    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.problems.p, hp.data(), sizeof(Sim3ProblemDev) * (size_t)n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_sim3_prepare, dim3(n), dim3(S3_THREADS), 0, st, ws.problems.as<Sim3ProblemDev>());
+    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.buf[PROBLEMS].p, hp.data(), sizeof(Sim3ProblemDev) * (size_t)n, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_sim3_prepare, dim3(n), dim3(S3_THREADS), 0, st, ws.as<Sim3ProblemDev>(PROBLEMS));
     ORBGPU_HIP_TRY(hipGetLastError());
-    ORBGPU_HIP_TRY(hipMemcpyAsync(ctl.data(), ws.ctl.p, sizeof(Sim3Ctl) * (size_t)n, hipMemcpyDeviceToHost, st));
+    ORBGPU_HIP_TRY(hipMemcpyAsync(ctl.data(), ws.buf[CTL].p, sizeof(Sim3Ctl) * (size_t)n, hipMemcpyDeviceToHost, st));
     ORBGPU_HIP_TRY(hipStreamSynchronize(st));
     for (int k = 0; k < n; k++) {
         const orbgpu_sim3_problem &p = problems[k];
@@ -527,13 +516,13 @@ extern "C" int orbgpu_sim3_solve_batch_device(int32_t n, const orbgpu_sim3_probl
         c.n_use = c.n < p.min_inliers ? 0 : std::min((int)p.n_hyp, c.max_its);
         c.pad = 0;
     }
-    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.ctl.p, ctl.data(), sizeof(Sim3Ctl) * (size_t)n, hipMemcpyHostToDevice, st));
+    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.buf[CTL].p, ctl.data(), sizeof(Sim3Ctl) * (size_t)n, hipMemcpyHostToDevice, st));
     if (max_hyp > 0) {
         hipLaunchKernelGGL(k_sim3_hypotheses, dim3((max_hyp + S3_WAVES - 1) / S3_WAVES, n), dim3(S3_THREADS), 0, st,
-                           ws.problems.as<Sim3ProblemDev>());
+                           ws.as<Sim3ProblemDev>(PROBLEMS));
         ORBGPU_HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_sim3_select, dim3((n + 63) / 64), dim3(64), 0, st, ws.problems.as<Sim3ProblemDev>(), n);
+    hipLaunchKernelGGL(k_sim3_select, dim3((n + 63) / 64), dim3(64), 0, st, ws.as<Sim3ProblemDev>(PROBLEMS), n);
     ORBGPU_HIP_TRY(hipGetLastError());
     return ORBGPU_OK;
 }
@@ -572,14 +561,8 @@ static int solve_host(const orbgpu_sim3_problem *p, int32_t *counts, float *R, f
     // enqueued through them on other streams must have left it
     ORBGPU_HIP_TRY(hipDeviceSynchronize());
     Sim3Ws &ws = per_device_workspace<Sim3Ws>(device_id);
-    if (!ws.stream) {
-        hipError_t e = hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            set_error("hipStreamCreate: %s", hipGetErrorString(e));
-            return ORBGPU_EHIP;
-        }
-        ws.device = device_id;
-    }
+    if ((rc = ws.bind(device_id, true)) != ORBGPU_OK)
+        return rc;
     // one staging block each way; every segment starts on a multiple of 16 bytes
     auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t words = (size_t)(n1 + 63) / 64, c1 = (size_t)std::max(n1, 1), cH = (size_t)std::max(H, 1);
@@ -588,21 +571,25 @@ static int solve_host(const orbgpu_sim3_problem *p, int32_t *counts, float *R, f
     const size_t o_res = 0, o_cnt = o_res + pad(sizeof(orbgpu_sim3_result)), o_R = o_cnt + pad(4 * cH), o_t = o_R + pad(36 * cH),
                  o_s = o_t + pad(12 * cH), o_T = o_s + pad(4 * cH), o_m = o_T + pad(64 * cH),
                  out_bytes = o_m + pad(8 * cH * std::max<size_t>(words, 1));
-    if ((rc = ws.h_in.reserve(in_bytes)) != ORBGPU_OK || (rc = ws.h_out.reserve(out_bytes)) != ORBGPU_OK)
+    ws.reserve(H_IN, in_bytes);
+    ws.reserve(H_OUT, out_bytes);
+    if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
-    char *din = ws.h_in.as<char>(), *dout = ws.h_out.as<char>();
-    const hipStream_t st = ws.stream;
+    char *din = ws.as<char>(H_IN), *dout = ws.as<char>(H_OUT);
+    Sim3Ws::FinishOnError on_error{ws};
     if (n1 > 0) {
-        ORBGPU_HIP_TRY(hipMemcpyAsync(din + i_valid, p->valid, (size_t)n1, hipMemcpyHostToDevice, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(din + i_x1, p->Xw1, 12 * (size_t)n1, hipMemcpyHostToDevice, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(din + i_x2, p->Xw2, 12 * (size_t)n1, hipMemcpyHostToDevice, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(din + i_o1, p->octave1, 4 * (size_t)n1, hipMemcpyHostToDevice, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(din + i_o2, p->octave2, 4 * (size_t)n1, hipMemcpyHostToDevice, st));
+        ws.upload(H_IN, p->valid, (size_t)n1, i_valid);
+        ws.upload(H_IN, p->Xw1, 12 * (size_t)n1, i_x1);
+        ws.upload(H_IN, p->Xw2, 12 * (size_t)n1, i_x2);
+        ws.upload(H_IN, p->octave1, 4 * (size_t)n1, i_o1);
+        ws.upload(H_IN, p->octave2, 4 * (size_t)n1, i_o2);
     }
     if (H > 0)
-        ORBGPU_HIP_TRY(hipMemcpyAsync(din + i_tr, p->triples, 12 * (size_t)H, hipMemcpyHostToDevice, st));
+        ws.upload(H_IN, p->triples, 12 * (size_t)H, i_tr);
+    if ((rc = ws.status()) != ORBGPU_OK)
+        return rc;
     if (all)  // hypotheses beyond n_use are not written by the kernels: they come back as zeros
-        ORBGPU_HIP_TRY(hipMemsetAsync(dout, 0, out_bytes, st));
+        ORBGPU_HIP_TRY(hipMemsetAsync(dout, 0, out_bytes, ws.stream));
     orbgpu_sim3_problem d = *p;
     d.valid = reinterpret_cast<const uint8_t *>(din + i_valid);
     d.Xw1 = reinterpret_cast<const float *>(din + i_x1), d.Xw2 = reinterpret_cast<const float *>(din + i_x2);
@@ -613,28 +600,26 @@ static int solve_host(const orbgpu_sim3_problem *p, int32_t *counts, float *R, f
     d.t = reinterpret_cast<float *>(dout + o_t), d.s = reinterpret_cast<float *>(dout + o_s);
     d.T12 = reinterpret_cast<float *>(dout + o_T), d.masks = reinterpret_cast<uint64_t *>(dout + o_m);
     d.indices1 = nullptr;
-    rc = orbgpu_sim3_solve_batch_device(1, &d, device_id, st);
-    if (rc != ORBGPU_OK) {
-        (void)hipStreamSynchronize(st);  // the uploads read the caller's arrays
+    if ((rc = orbgpu_sim3_solve_batch_device(1, &d, device_id, ws.stream)) != ORBGPU_OK)
         return rc;
-    }
     orbgpu_sim3_result r;
-    ORBGPU_HIP_TRY(hipMemcpyAsync(&r, dout + o_res, sizeof(r), hipMemcpyDeviceToHost, st));
+    ws.download(&r, H_OUT, sizeof(r), o_res);
     if (counts && H > 0)
-        ORBGPU_HIP_TRY(hipMemcpyAsync(counts, dout + o_cnt, 4 * (size_t)H, hipMemcpyDeviceToHost, st));
+        ws.download(counts, H_OUT, 4 * (size_t)H, o_cnt);
     if (all && H > 0) {
         if (R)
-            ORBGPU_HIP_TRY(hipMemcpyAsync(R, dout + o_R, 36 * (size_t)H, hipMemcpyDeviceToHost, st));
+            ws.download(R, H_OUT, 36 * (size_t)H, o_R);
         if (t)
-            ORBGPU_HIP_TRY(hipMemcpyAsync(t, dout + o_t, 12 * (size_t)H, hipMemcpyDeviceToHost, st));
+            ws.download(t, H_OUT, 12 * (size_t)H, o_t);
         if (s)
-            ORBGPU_HIP_TRY(hipMemcpyAsync(s, dout + o_s, 4 * (size_t)H, hipMemcpyDeviceToHost, st));
+            ws.download(s, H_OUT, 4 * (size_t)H, o_s);
         if (T12)
-            ORBGPU_HIP_TRY(hipMemcpyAsync(T12, dout + o_T, 64 * (size_t)H, hipMemcpyDeviceToHost, st));
+            ws.download(T12, H_OUT, 64 * (size_t)H, o_T);
         if (masks && words > 0)
-            ORBGPU_HIP_TRY(hipMemcpyAsync(masks, dout + o_m, 8 * words * (size_t)H, hipMemcpyDeviceToHost, st));
+            ws.download(masks, H_OUT, 8 * words * (size_t)H, o_m);
     }
-    ORBGPU_HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = ws.finish()) != ORBGPU_OK)
+        return rc;
     if (all) {
         *result = r;
         return ORBGPU_OK;
@@ -642,19 +627,19 @@ static int solve_host(const orbgpu_sim3_problem *p, int32_t *counts, float *R, f
     const int b = r.best_iteration;
     if (b >= 0 && b < H) {
         if (R)
-            ORBGPU_HIP_TRY(hipMemcpyAsync(R, dout + o_R + 36 * (size_t)b, 36, hipMemcpyDeviceToHost, st));
+            ws.download(R, H_OUT, 36, o_R + 36 * (size_t)b);
         if (t)
-            ORBGPU_HIP_TRY(hipMemcpyAsync(t, dout + o_t + 12 * (size_t)b, 12, hipMemcpyDeviceToHost, st));
+            ws.download(t, H_OUT, 12, o_t + 12 * (size_t)b);
         if (s)
-            ORBGPU_HIP_TRY(hipMemcpyAsync(s, dout + o_s + 4 * (size_t)b, 4, hipMemcpyDeviceToHost, st));
+            ws.download(s, H_OUT, 4, o_s + 4 * (size_t)b);
         if (T12)
-            ORBGPU_HIP_TRY(hipMemcpyAsync(T12, dout + o_T + 64 * (size_t)b, 64, hipMemcpyDeviceToHost, st));
+            ws.download(T12, H_OUT, 64, o_T + 64 * (size_t)b);
     }
     std::vector<uint64_t> mask(std::max<size_t>(words, 1), 0);
     if (r.accepted >= 0 && words > 0)
-        ORBGPU_HIP_TRY(hipMemcpyAsync(mask.data(), dout + o_m + 8 * words * (size_t)r.accepted, 8 * words, hipMemcpyDeviceToHost,
-                                      st));
-    ORBGPU_HIP_TRY(hipStreamSynchronize(st));
+        ws.download(mask.data(), H_OUT, 8 * words, o_m + 8 * words * (size_t)r.accepted);
+    if ((rc = ws.finish()) != ORBGPU_OK)
+        return rc;
     if (inliers)
         for (int i = 0; i < n1; i++)
             inliers[i] = (uint8_t)((mask[(size_t)i >> 6] >> (i & 63)) & 1u);

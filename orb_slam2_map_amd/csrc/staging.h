@@ -1,0 +1,133 @@
+// The staging workspace of the stateless entry points: what a (thread, device) workspace (workspace.h) owns on the
+// device -- an optional non-blocking stream and N grow-only buffers -- with the one binding, the one release and the one
+// error rule all of them follow.  Each unit names its buffers once, in an enum that ends in the count:
+//     enum { H_KPS, H_UR, ..., N_BUF };  struct PoseWs : Staging<N_BUF> {};
+// so a new buffer is one new enumerator and the release covers it by construction.
+#pragma once
+
+#include <algorithm>
+
+#include "common.h"
+#include "workspace.h"
+
+namespace orbgpu {
+
+template <int N> struct Staging {
+    int device = -1;               // -1: unbound, owns nothing
+    hipStream_t stream = nullptr;  // the host flavours' own stream; the device flavours run on the caller's
+    bool pending = false;          // something was enqueued on `stream` since the last finish()
+    int rc = ORBGPU_OK;            // first failure of a staging step since bind()
+    DevBuf buf[N];
+
+    Staging() = default;
+    Staging(const Staging &) = delete;
+    Staging &operator=(const Staging &) = delete;
+    ~Staging() { release(); }
+
+    // Every entry point calls this after select_device(device_id).  First use of this (thread, device) records the
+    // device; own_stream asks for the stream as well (created once).  On failure nothing new is owned.
+    int bind(int device_id, bool own_stream)
+    {
+        rc = ORBGPU_OK;
+        if (own_stream && !stream) {
+            hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+            if (e != hipSuccess) {
+                stream = nullptr;
+                set_error("hipStreamCreate: %s", hipGetErrorString(e));
+                return ORBGPU_EHIP;
+            }
+        }
+        device = device_id;
+        return ORBGPU_OK;
+    }
+
+    // Reserve, upload, download: the first failure sticks (status()), later steps do nothing, so a run of them needs no
+    // check per line -- one status() before the first launch that reads the buffers, and finish() at the end.
+    template <typename T> T *as(int i) const { return buf[i].template as<T>(); }
+    int status() const { return rc; }
+    void reserve(int i, size_t bytes)
+    {
+        if (rc == ORBGPU_OK)
+            rc = buf[i].reserve(bytes);
+    }
+    // host -> buf[i] + offset on the own stream; the buffer has been reserved
+    void upload(int i, const void *src, size_t bytes, size_t offset = 0) { copy(i, offset, const_cast<void *>(src), bytes, true); }
+    void download(void *dst, int i, size_t bytes, size_t offset = 0) { copy(i, offset, dst, bytes, false); }
+    // reserve, then upload: never less than 16 bytes (the kernels read with vector loads), nothing copied from a null
+    // or empty source
+    void put(int i, const void *src, size_t bytes)
+    {
+        reserve(i, std::max<size_t>(bytes, 16));
+        if (src && bytes)
+            upload(i, src, bytes);
+    }
+    // Waits for the own stream and returns the first failure, if any.
+    int finish()
+    {
+        if (rc == ORBGPU_OK || pending) {
+            hipError_t e = hipStreamSynchronize(stream);
+            if (e != hipSuccess && rc == ORBGPU_OK) {
+                set_error("hipStreamSynchronize: %s", hipGetErrorString(e));
+                rc = ORBGPU_EHIP;
+            }
+        }
+        pending = false;
+        return rc;
+    }
+
+    // The error rule: a host flavour that has enqueued anything on the own stream waits for it before it returns a
+    // non-OK code -- the copies read and write the caller's arrays.  The entry declares one of these once it holds the
+    // workspace; a success path ends in finish(), after which this does nothing.
+    struct FinishOnError {
+        Staging &s;
+        ~FinishOnError()
+        {
+            if (s.pending)
+                (void)s.finish();
+        }
+    };
+
+    // End of the owning thread (or of the owner of a workspace that is not the thread's), in workspace.h's order.
+    // owner_hook releases what the owner keeps beside the buffers (the brute-force matcher's handle).
+    template <typename Hook> void release(Hook owner_hook)
+    {
+        struct Ops {
+            Staging &s;
+            Hook &hook;
+            void set_device() { (void)hipSetDevice(s.device); }
+            void sync_stream() { (void)hipStreamSynchronize(s.stream); }
+            void owner_hook() { hook(); }
+            void free_buffers()
+            {
+                for (DevBuf &b : s.buf)
+                    b.release();
+            }
+            void destroy_stream() { (void)hipStreamDestroy(s.stream); }
+        } ops{*this, owner_hook};
+        release_workspace(device >= 0, stream != nullptr, ops);
+        device = -1, stream = nullptr, pending = false;
+    }
+    void release() { release([] {}); }
+
+  private:
+    void copy(int i, size_t offset, void *host, size_t bytes, bool to_device)
+    {
+        if (rc != ORBGPU_OK)
+            return;
+        if (!stream || offset + bytes > buf[i].bytes) {
+            set_error("staging copy outside buffer %d (%zu + %zu of %zu bytes)", i, offset, bytes, buf[i].bytes);
+            rc = ORBGPU_EINVAL;
+            return;
+        }
+        pending = true;
+        char *dev = buf[i].template as<char>() + offset;
+        hipError_t e = to_device ? hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream)
+                                 : hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream);
+        if (e != hipSuccess) {
+            set_error("hipMemcpyAsync (staging buffer %d): %s", i, hipGetErrorString(e));
+            rc = ORBGPU_EHIP;
+        }
+    }
+};
+
+} // namespace orbgpu

@@ -14,7 +14,7 @@
 // outside the plane); a right key point with an octave outside [0, nlevels) is never a candidate.
 #include "common.h"
 #include "pyramid_view.h"
-#include "workspace.h"
+#include "staging.h"
 
 #include <algorithm>
 #include <climits>
@@ -393,25 +393,9 @@ static void planes_of(const PyramidView &v, int frame0, StPlanes &P)
     }
 }
 
-// Host-entry staging: per (thread, device), like the matchers' workspaces (workspace.h).
-struct StereoHostWs {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    DevBuf kps_l, kps_r, desc_l, desc_r, n, ur, dz;
-    ~StereoHostWs()
-    {
-        if (device >= 0 && !process_exiting().load()) {
-            (void)hipSetDevice(device);
-            if (stream)
-                (void)hipStreamSynchronize(stream);
-            DevBuf *bufs[] = {&kps_l, &kps_r, &desc_l, &desc_r, &n, &ur, &dz};
-            for (DevBuf *b : bufs)
-                b->release();
-            if (stream)
-                (void)hipStreamDestroy(stream);
-        }
-    }
-};
+// Host-entry staging: per (thread, device), on the one type of the stateless entry points (staging.h).
+enum { KPS_L, KPS_R, DESC_L, DESC_R, COUNTS, UR, DZ, N_BUF };
+struct StereoHostWs : Staging<N_BUF> {};
 
 // Everything the entry points check before they touch the device.
 static int check_pair(const orbgpu_extractor *left, int lf0, const orbgpu_extractor *right, int rf0, int batch,
@@ -517,44 +501,38 @@ extern "C" int orbgpu_compute_stereo_matches(const orbgpu_extractor *left, const
     if (rc != ORBGPU_OK)
         return rc;
     StereoHostWs &ws = per_device_workspace<StereoHostWs>(vl.device_id);
-    if (ws.device != vl.device_id) {
-        hipError_t e = hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            set_error("hipStreamCreate: %s", hipGetErrorString(e));
-            return ORBGPU_EHIP;
-        }
-        ws.device = vl.device_id;
-    }
-    const int cap = std::max(std::max(n_l, n_r), 1);
-    if ((rc = ws.kps_l.reserve(sizeof(orbgpu_keypoint) * cap)) != ORBGPU_OK ||
-        (rc = ws.kps_r.reserve(sizeof(orbgpu_keypoint) * cap)) != ORBGPU_OK ||
-        (rc = ws.desc_l.reserve((size_t)32 * cap)) != ORBGPU_OK || (rc = ws.desc_r.reserve((size_t)32 * cap)) != ORBGPU_OK ||
-        (rc = ws.n.reserve(sizeof(int) * 2)) != ORBGPU_OK || (rc = ws.ur.reserve(sizeof(float) * cap)) != ORBGPU_OK ||
-        (rc = ws.dz.reserve(sizeof(float) * cap)) != ORBGPU_OK)
+    if ((rc = ws.bind(vl.device_id, true)) != ORBGPU_OK)
         return rc;
+    const size_t cap = (size_t)std::max(std::max(n_l, n_r), 1);
+    ws.reserve(KPS_L, sizeof(orbgpu_keypoint) * cap);
+    ws.reserve(KPS_R, sizeof(orbgpu_keypoint) * cap);
+    ws.reserve(DESC_L, 32 * cap);
+    ws.reserve(DESC_R, 32 * cap);
+    ws.reserve(COUNTS, sizeof(int) * 2);
+    ws.reserve(UR, sizeof(float) * cap);
+    ws.reserve(DZ, sizeof(float) * cap);
+    if ((rc = ws.status()) != ORBGPU_OK)
+        return rc;
+    StereoHostWs::FinishOnError on_error{ws};
     const int32_t counts[2] = {n_l, n_r};
-    const hipStream_t st = ws.stream;
-    ORBGPU_HIP_TRY(hipMemcpyAsync(ws.n.p, counts, sizeof(counts), hipMemcpyHostToDevice, st));
+    ws.upload(COUNTS, counts, sizeof(counts));
     if (n_l > 0) {
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.kps_l.p, kps_l, sizeof(orbgpu_keypoint) * n_l, hipMemcpyHostToDevice, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.desc_l.p, desc_l, (size_t)32 * n_l, hipMemcpyHostToDevice, st));
+        ws.upload(KPS_L, kps_l, sizeof(orbgpu_keypoint) * n_l);
+        ws.upload(DESC_L, desc_l, (size_t)32 * n_l);
     }
     if (n_r > 0) {
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.kps_r.p, kps_r, sizeof(orbgpu_keypoint) * n_r, hipMemcpyHostToDevice, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(ws.desc_r.p, desc_r, (size_t)32 * n_r, hipMemcpyHostToDevice, st));
+        ws.upload(KPS_R, kps_r, sizeof(orbgpu_keypoint) * n_r);
+        ws.upload(DESC_R, desc_r, (size_t)32 * n_r);
     }
-    rc = orbgpu_stereo_matches_batch_device(left, 0, right, 0, 1, cap, ws.kps_l.as<orbgpu_keypoint>(), ws.n.as<int32_t>(),
-                                            ws.desc_l.as<uint8_t>(), ws.kps_r.as<orbgpu_keypoint>(),
-                                            ws.n.as<int32_t>() + 1, ws.desc_r.as<uint8_t>(), mbf, fx,
-                                            ws.ur.as<float>(), ws.dz.as<float>(), nullptr, st);
-    if (rc != ORBGPU_OK) {
-        (void)hipStreamSynchronize(st);  // the uploads read the caller's arrays
+    if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
-    }
-    if (n_l > 0) {
-        ORBGPU_HIP_TRY(hipMemcpyAsync(u_right, ws.ur.p, sizeof(float) * n_l, hipMemcpyDeviceToHost, st));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(depth, ws.dz.p, sizeof(float) * n_l, hipMemcpyDeviceToHost, st));
-    }
-    ORBGPU_HIP_TRY(hipStreamSynchronize(st));
-    return ORBGPU_OK;
+    rc = orbgpu_stereo_matches_batch_device(left, 0, right, 0, 1, (int32_t)cap, ws.as<orbgpu_keypoint>(KPS_L), ws.as<int32_t>(COUNTS),
+                                            ws.as<uint8_t>(DESC_L), ws.as<orbgpu_keypoint>(KPS_R), ws.as<int32_t>(COUNTS) + 1,
+                                            ws.as<uint8_t>(DESC_R), mbf, fx, ws.as<float>(UR), ws.as<float>(DZ), nullptr,
+                                            ws.stream);
+    if (rc != ORBGPU_OK)
+        return rc;
+    ws.download(u_right, UR, sizeof(float) * n_l);  // n_l > 0 here
+    ws.download(depth, DZ, sizeof(float) * n_l);
+    return ws.finish();
 }

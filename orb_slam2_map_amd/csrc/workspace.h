@@ -19,11 +19,26 @@ namespace orbgpu {
 // The one moment it must NOT touch HIP is process exit, when the runtime may already be torn down: the library
 // registers an atexit handler at load time (runtime.hip) that raises this flag; libamdhip64 was loaded before
 // liborbgpu (it is a dependency), so its own handlers ran their registration earlier and run their teardown LATER than
-// ours.  Workspace destructors release their device resources iff the flag is still down.
+// ours.  A workspace releases its device resources iff the flag is still down.
 inline std::atomic<bool> &process_exiting()
 {
     static std::atomic<bool> flag{false};
     return flag;
+}
+
+// The release rule, in this order and in no other.  staging.h implements it for every workspace of the library (Ops =
+// the HIP calls); tests/workspace_test.cpp runs the same sequence over a recording stand-in.
+template <typename Ops> void release_workspace(bool bound, bool has_stream, Ops &ops)
+{
+    if (!bound || process_exiting().load())
+        return;  // owns nothing / the runtime may be gone: everything goes with the process
+    ops.set_device();
+    if (has_stream)
+        ops.sync_stream();
+    ops.owner_hook();  // what the owner keeps beside the buffers
+    ops.free_buffers();
+    if (has_stream)
+        ops.destroy_stream();
 }
 
 template <typename W> W &per_device_workspace(int device_id)

@@ -311,6 +311,124 @@ def test_batch_size_sequence(gpu, oracle, stream640, first):
     s.stages(pool[7], 7, "batch of 8 after the sequence")
 
 
+def _in_fresh_thread(fn):
+    """fn() on a host thread of its own: its stateless calls find workspaces that own nothing yet."""
+    import threading
+    box = {}
+
+    def body():
+        try:
+            box["value"] = fn()
+        except BaseException as ex:  # noqa: BLE001 -- re-raised by the caller
+            box["error"] = ex
+
+    t = threading.Thread(target=body)
+    t.start()
+    t.join(120)
+    assert not t.is_alive()
+    if "error" in box:
+        raise box["error"]
+    return box["value"]
+
+
+def _stateless_families(gpu, oracle):
+    """(name, limit, call, check) per family of stateless entry points, on inputs of a few hundred rows: under
+    ORBGPU_DEBUG_FAIL_ALLOC_OVER=limit a staging allocation of the call fails in a fresh thread; check(result) holds the
+    result of the repeated call against the oracle or the model."""
+    import scenario
+    import pose_model
+    import sim3_model
+    import stereo_model
+    tools = os.path.join(ROOT, "tools")
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
+    import fuzz_pose
+    import fuzz_sim3
+    from orb_slam2_map_amd.synth import Stream, StereoStream
+    st = Stream(640, 480, 77)
+    oe = oracle.Extractor(300)
+    (ka, da), (kb, db) = oe.extract(st.frame(1)[0]), oe.extract(st.frame(2)[0])
+    fam = []
+    # brute force: the matcher the workspace creates is refused first (the workspace is bound by then)
+    want_bf = oracle.match_bf(da, ka["angle"], db, kb["angle"], nnratio=0.7)
+    fam.append(("bf", 0, lambda: gpu.ORBmatcher(0.7, True).MatchBruteForce(da, ka["angle"], db, kb["angle"]),
+                lambda got: got[0] == want_bf[0] and np.array_equal(got[1], want_bf[1])))
+    # projection: the 4-byte frame arrays (1.2 KB) are uploaded, the descriptors (9.6 KB) refused: an error after an enqueue
+    sf = np.asarray(oe.scale_factors(), np.float32)
+    Tcw, rng = scenario.rigid(), np.random.default_rng(5)
+    (px, py), (ox, oy) = st.offset(1), st.offset(2)
+    P, _ = scenario.world_points_from_prev(ka, st.frame(1)[2], (ox - px, oy - py), st, Tcw, rng)
+    mp = scenario.local_map(oracle, st, Tcw, P, da, ka["octave"], sf, rng, obs_zero_frac=0.1)
+    of = scenario.make_frame(oracle, kb, db, st.frame(2)[2], st, sf)
+    gf = gpu.Frame(of.kp_x, of.kp_y, of.octave, of.angle, of.u_right, of.desc, float(of.max_x), float(of.max_y), of.scale_factors)
+    k0 = np.full(of.n, -1, np.int32)
+    want_pj = oracle.search_by_projection(of, mp, 3.0, 0.8, k0)
+    assert 4 * of.n < 5000 < 32 * of.n
+    fam.append(("projection", 5000, lambda: gpu.ORBmatcher(0.8, True).SearchByProjection(gf, mp, 3.0, k0),
+                lambda got: got[0] == want_pj[0] and np.array_equal(got[1], want_pj[1])))
+    # pose: the first staging buffer is refused
+    sc = pose_model.make_scene(300, 4243)
+    n = sc["n"]
+    has, wp = (sc["kp_to_mp"] >= 0).astype(np.uint8), sc["world_pos"][sc["kp_to_mp"].clip(0)]
+    fr = gpu.Frame(sc["kps_xy"][:, 0], sc["kps_xy"][:, 1], sc["octave"], np.zeros(n, np.float32), sc["u_right"],
+                   np.zeros((n, 32), np.uint8), 640, 480, np.ones(pose_model.NLEVELS, np.float32))
+    fx, fy, cx, cy, bf = (float(k) for k in sc["K"])
+
+    def check_pose(got):
+        rep = fuzz_pose.compare([sc], [(b"", got[3], got[2])])
+        return rep["compared"] == 1 and not rep["mismatches"]
+
+    fam.append(("pose", 0, lambda: gpu.pose_optimization(fr, has, wp, sc["Tcw"], sc["inv_level_sigma2"], fx, fy, cx, cy, bf,
+                                                         outlier=np.full(n, fuzz_pose.SENTINEL, np.uint8)), check_pose))
+    # sim3: the two host blocks (7 KB, 8 KB) are uploaded, the device flavour's records (48 n1 = 9.6 KB) refused: an
+    # error after an enqueue
+    s3 = sim3_model.make_scene(120, 31, n1=200, n_hyp=50)
+    models, spread = fuzz_sim3.model_pass([s3])
+    m = models[0]
+    keep = ~fuzz_sim3.left_out(m, fuzz_sim3.MARGIN_FACTOR * fuzz_sim3.BOUND_FACTOR * spread)
+    assert keep[:m["iterations"]].all(), "the scene must leave no scanned hypothesis to the margins"
+
+    def check_sim3(got):
+        u = m["n_use"]
+        return (np.array_equal(got["counts"][:u][keep], m["counts"][:u][keep]) and
+                all(got[k] == int(m[k]) for k in ("accepted", "n_inliers", "no_more", "best_inliers", "best_iteration", "iterations")))
+
+    fam.append(("sim3", 9000, lambda: gpu.sim3_solve(s3["valid"], s3["Xw1"], s3["Xw2"], s3["octave1"], s3["octave2"], s3["T1w"],
+                                                     s3["T2w"], s3["K1"], s3["K2"], s3["level_sigma2"], s3["triples"],
+                                                     s3["fix_scale"], s3["probability"], s3["min_inliers"], s3["max_iterations"]),
+                check_sim3))
+    # stereo: the first staging buffer is refused
+    ss = StereoStream(320, 240, 12)
+    left, right, _ = ss.frame(1)
+    gl, gr, ol, orr = gpu.ORBextractor(300), gpu.ORBextractor(300), oracle.Extractor(300), oracle.Extractor(300)
+    (kl, dl), (kr, dr) = gl(left), gr(right)
+    ol.extract(left), orr.extract(right)
+    u, d, _ = stereo_model.stereo_matches(kl, dl, kr, dr, stereo_model.oracle_planes(ol), stereo_model.oracle_planes(orr),
+                                          ol.scale_factors(), ol.inv_scale_factors(), ss.bf, ss.fx)
+    bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.int32)  # noqa: E731
+    fam.append(("stereo", 0, lambda: gpu.compute_stereo_matches(gl, gr, kl, dl, kr, dr, ss.bf, ss.fx),
+                lambda got: np.array_equal(bits(got[0]), bits(u)) and np.array_equal(bits(got[1]), bits(d))))
+    return fam
+
+
+def test_stateless_entry_points_recover_from_a_refused_staging_allocation(gpu, oracle, monkeypatch):
+    """One host entry of each family of stateless entry points (brute force, projection, pose, sim3, stereo), each on a
+    fresh thread, whose workspace owns nothing yet: under ORBGPU_DEBUG_FAIL_ALLOC_OVER a staging allocation is refused
+    and the call returns ENOMEM -- for projection and sim3 after uploads from the caller's arrays were enqueued, which
+    the entry waits for before it returns; with the hook cleared the same call on the same thread, so on the workspace
+    the failure left behind, gives the oracle's (the model's) result."""
+    for name, limit, call, check in _stateless_families(gpu, oracle):
+        def case():
+            monkeypatch.setenv("ORBGPU_DEBUG_FAIL_ALLOC_OVER", str(limit))
+            with pytest.raises(gpu.OrbGpuError) as ei:
+                call()
+            monkeypatch.delenv("ORBGPU_DEBUG_FAIL_ALLOC_OVER")
+            assert ei.value.status == gpu.ENOMEM and "hipMalloc(" in str(ei.value), "%s: %s" % (name, ei.value)
+            return call()
+
+        assert check(_in_fresh_thread(case)), "%s: the call after the refused one differs from the reference" % name
+
+
 CHILD = r"""
 import ctypes as C, os, sys
 sys.path.insert(0, sys.argv[1])

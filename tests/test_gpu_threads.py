@@ -155,21 +155,58 @@ def test_first_calls_on_fresh_handles_from_fresh_threads(gpu, stream640):
     assert not bad, bad[:8]
 
 
-def test_short_lived_worker_threads_give_their_workspaces_back(gpu, stream640):
-    """A caller that matches from short-lived worker threads: every thread's workspace (a stream, ~20 device buffers, a
-    matcher handle) is released when the thread ends (csrc/workspace.h), so device memory does not grow with the number
-    of threads that ever called in."""
+def test_short_lived_worker_threads_give_their_workspaces_back(gpu, oracle, stream640):
+    """A caller that matches from short-lived worker threads: every thread's workspaces -- one per family of stateless
+    entry points, each a stream and its device buffers (csrc/staging.h), the brute-force one a matcher handle as well --
+    are released when the thread ends, so device memory does not grow with the number of threads that ever called in."""
     import torch
+    import sim3_model
     st = stream640
     ge = gpu.ORBextractor(1000, max_batch=2)
     (ka, kb), (da, db) = ge.extract_batch(np.stack([st.frame(3)[0], st.frame(4)[0]]))
-    want = gpu.ORBmatcher(0.7, True).MatchBruteForce(da, ka["angle"], db, kb["angle"])
+    bf = lambda: gpu.ORBmatcher(0.7, True).MatchBruteForce(da, ka["angle"], db, kb["angle"])  # noqa: E731
+    # projection: frame 3's key points as map points seen from frame 4, the rows four times over (about 4096)
+    sf = np.asarray(ge.GetScaleFactors(), np.float32)
+    Tcw, rng = scenario.rigid(), np.random.default_rng(3)
+    (px, py), (ox, oy) = st.offset(3), st.offset(4)
+    P, _ = scenario.world_points_from_prev(ka, st.frame(3)[2], (ox - px, oy - py), st, Tcw, rng)
+    mp1 = scenario.local_map(oracle, st, Tcw, P, da, ka["octave"], sf, rng, obs_zero_frac=0.1)
+    mp = {k: np.concatenate([v] * 4) for k, v in mp1.items()}
+    assert 3000 <= len(mp["level"]) <= 4400
+    of = scenario.make_frame(oracle, kb, db, st.frame(4)[2], st, sf)
+    gf = gpu.Frame(of.kp_x, of.kp_y, of.octave, of.angle, of.u_right, of.desc, float(of.max_x), float(of.max_y), of.scale_factors)
+    k0 = np.full(of.n, -1, np.int32)
+    proj = lambda: gpu.ORBmatcher(0.8, True).SearchByProjection(gf, mp, 3.0, k0)  # noqa: E731
+    n_proj, k2m = proj()
+    assert n_proj > 100
+    # pose optimisation over that frame's key points and the map points the projection gave them
+    has, wp = (k2m >= 0).astype(np.uint8), np.ascontiguousarray(P[k2m.clip(0) % len(P)], np.float32)
+    pose = lambda: gpu.pose_optimization(gf, has, wp, Tcw, 1.0 / (sf * sf), float(st.fx), float(st.fy), float(st.cx),  # noqa: E731
+                                         float(st.cy), float(st.bf))
+    sc = sim3_model.make_scene(1000, 77, n1=1500, n_hyp=300)
+    sim3 = lambda: gpu.sim3_solve(sc["valid"], sc["Xw1"], sc["Xw2"], sc["octave1"], sc["octave2"], sc["T1w"], sc["T2w"],  # noqa: E731
+                                  sc["K1"], sc["K2"], sc["level_sigma2"], sc["triples"], sc["fix_scale"], sc["probability"],
+                                  sc["min_inliers"], sc["max_iterations"])
+    gl, gr = gpu.ORBextractor(1000), gpu.ORBextractor(1000)
+    (kl, dl), (kr, dr) = gl(st.frame(3)[0]), gr(st.frame(4)[0])
+    stereo = lambda: gpu.compute_stereo_matches(gl, gr, kl, dl, kr, dr, float(st.bf), float(st.fx))  # noqa: E731
+
+    def same(a, b):
+        if isinstance(a, dict):
+            return a.keys() == b.keys() and all(same(a[k], b[k]) for k in a)
+        if isinstance(a, (tuple, list)):
+            return len(a) == len(b) and all(same(x, y) for x, y in zip(a, b))
+        return np.asarray(a).tobytes() == np.asarray(b).tobytes()
+
+    calls = {"bf": bf, "projection": proj, "pose": pose, "sim3": sim3, "stereo": stereo}
+    want = {k: f() for k, f in calls.items()}  # once, on the main thread
+    assert want["sim3"]["accepted"] >= 0 and want["pose"][0] > 50 and (want["stereo"][0] >= 0).sum() > 50
     errors = []
 
     def worker():
         try:
-            got = gpu.ORBmatcher(0.7, True).MatchBruteForce(da, ka["angle"], db, kb["angle"])
-            assert got[0] == want[0] and np.array_equal(got[1], want[1])
+            for k, f in calls.items():
+                assert same(f(), want[k]), "%s differs from the main thread's result" % k
             d = gpu.ORBmatcher.DescriptorDistance(da[:64], db[:64])
             assert len(d) == 64
         except Exception as ex:  # noqa: BLE001
@@ -189,5 +226,11 @@ def test_short_lived_worker_threads_give_their_workspaces_back(gpu, stream640):
     torch.cuda.synchronize()
     free1, _ = torch.cuda.mem_get_info()
     assert not errors, errors
-    # one brute-force workspace is ~0.5 MB of buffers + a matcher handle; 40 leaked ones would be tens of MB
+    # What one thread's five workspaces hold, from the reserve sizes in csrc (n = 1000 key points, m = 4000 rows):
+    #   brute force  cap 1024: 2 x 32 cap + 5 x 4 cap + cap + 12 = 87 KB, and the matcher handle's 4 x 16 x cap x 4 = 262 KB
+    #   projection   frame 52 n + 12 KB = 64 KB; rows (40 + 32 + 4 + 4 + 4 x 16) m = 576 KB; claim / k2m 8 n = 8 KB
+    #   pose         (28 + 4 + 4 + 12 + 1) n = 49 KB
+    #   sim3         n1 1500, 300 hypotheses: in 53 KB, out 94 KB, records 48 n1 = 72 KB, map 6 KB
+    #   stereo       (2 x 28 + 2 x 32 + 2 x 4) cap = 128 KB
+    # = 1.4 MB: 40 leaked threads would be 56 MB, seven times the bound
     assert free0 - free1 < 8 << 20, "device memory shrank by %.1f MB over 40 worker threads" % ((free0 - free1) / 2**20)

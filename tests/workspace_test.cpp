@@ -4,25 +4,53 @@
 #include "workspace.h"
 
 #include <cstdio>
+#include <string>
 #include <thread>
 
+// The shape of staging.h's Staging<N> without HIP: the same release_workspace() sequence over operations that record
+// themselves ('d' set device, 's' synchronise the stream, 'h' owner hook, 'f' free the buffers, 'x' destroy the stream).
 struct Fake {
-    static int live, released, dropped;
+    static int live, released, dropped, sub_resources;
+    static std::string last_order;
     int device = -1;
-    int stream_of_device = -1;  // stands for the hipStream_t / DevBufs created on `device`
+    int stream_of_device = -1;  // stands for the hipStream_t created on `device`; -1: bound without a stream
+    bool has_sub_resource = false;  // stands for the brute-force matcher's handle
+    std::string order;
     Fake() { live++; }
-    ~Fake()  // the shape of ProjWorkspace / the brute-force Ws: release on thread exit, never while the process exits
+    void set_device() { order += 'd'; }
+    void sync_stream() { order += 's'; }
+    void owner_hook()
+    {
+        order += 'h';
+        if (has_sub_resource)
+            sub_resources--;
+        has_sub_resource = false;
+    }
+    void free_buffers() { order += 'f'; }
+    void destroy_stream() { order += 'x'; }
+    bool acquire_sub_resource()  // only a bound workspace may own one: its release is the only one there is
+    {
+        if (device < 0)
+            return false;
+        has_sub_resource = true;
+        sub_resources++;
+        return true;
+    }
+    ~Fake()  // release on thread exit, never while the process exits
     {
         live--;
+        orbgpu::release_workspace(device >= 0, stream_of_device >= 0, *this);
+        last_order = order;
         if (device < 0)
             return;
         if (orbgpu::process_exiting().load())
             dropped++;
         else
-            released++;  // "hipSetDevice(device); hipStreamDestroy(stream); hipFree(...)"
+            released++;
     }
 };
-int Fake::live = 0, Fake::released = 0, Fake::dropped = 0;
+int Fake::live = 0, Fake::released = 0, Fake::dropped = 0, Fake::sub_resources = 0;
+std::string Fake::last_order;
 
 static Fake &use(int device)
 {
@@ -74,7 +102,28 @@ int main()
         std::thread w([&] { (void)orbgpu::per_device_workspace<Fake>(5); });
         w.join();
     }
-    CHECK(Fake::released == 17);
+    CHECK(Fake::released == 17 && Fake::last_order.empty());
+    // the release order: device, wait for the stream, owner hook, buffers, stream last
+    {
+        std::thread w([&] { use(1).acquire_sub_resource(); });
+        w.join();
+    }
+    CHECK(Fake::last_order == "dshfx" && Fake::sub_resources == 0 && Fake::released == 18);
+    // a workspace whose binding failed (the stream could not be created: `device` stays -1) cannot have acquired a
+    // sub-resource, so it releases nothing and leaks nothing
+    {
+        bool acquired = true;
+        std::thread w([&] { acquired = orbgpu::per_device_workspace<Fake>(6).acquire_sub_resource(); });
+        w.join();
+        CHECK(!acquired);
+    }
+    CHECK(Fake::last_order.empty() && Fake::sub_resources == 0 && Fake::released == 18);
+    // a workspace bound without a stream (the device flavours) releases its buffers and destroys no stream
+    {
+        std::thread w([&] { orbgpu::per_device_workspace<Fake>(2).device = 2; });
+        w.join();
+    }
+    CHECK(Fake::last_order == "dhf" && Fake::released == 19);
     // process exit: the library's atexit handler raises the flag before the HIP runtime is torn down; a thread that
     // ends after that must not touch the device any more
     orbgpu::process_exiting().store(true);
@@ -82,7 +131,7 @@ int main()
         std::thread w([&] { use(4); });
         w.join();
     }
-    CHECK(Fake::released == 17 && Fake::dropped == 1);
+    CHECK(Fake::released == 19 && Fake::dropped == 1 && Fake::last_order.empty());
     orbgpu::process_exiting().store(false);
     std::printf("workspace_test ok\n");
     return 0;
