@@ -1,11 +1,19 @@
-// Device helpers shared by the matcher kernels.
+// Helpers shared by the matcher kernels; the rotation check also runs on the host (orbgpu_search_for_initialization),
+// so this header compiles without HIP as well (tests/proj_boundary_test.cpp).
 #pragma once
+#ifdef __HIPCC__
 #include "common.h"
+#define ORBGPU_HD __host__ __device__
+#else
+#include <cmath>
+#include "orbgpu.h"
+#define ORBGPU_HD
+#endif
 
 namespace orbgpu {
 
 // ORBmatcher::ComputeThreeMaxima, ORBmatcher.cc:1601-1642
-__device__ inline void three_maxima(const int *histo, int L, int &ind1, int &ind2, int &ind3)
+ORBGPU_HD inline void three_maxima(const int *histo, int L, int &ind1, int &ind2, int &ind3)
 {
     int max1 = 0, max2 = 0, max3 = 0;
     ind1 = ind2 = ind3 = -1;
@@ -37,7 +45,7 @@ __device__ inline void three_maxima(const int *histo, int L, int &ind1, int &ind
 }
 
 // rotation bin, ORBmatcher.cc:238-243
-__device__ __forceinline__ int rot_bin(float angle_a, float angle_b)
+ORBGPU_HD inline int rot_bin(float angle_a, float angle_b)
 {
     const float factor = 1.0f / ORBGPU_HISTO_LENGTH;
     float rot = angle_a - angle_b;

@@ -17,6 +17,7 @@
 #include "matcher_common.h"
 #include "staging.h"
 #include "proj_internal.h"
+#include "proj_boundary.h"  // struct Query and everything that fills one on the host
 
 #include <algorithm>
 #include <climits>
@@ -28,16 +29,6 @@
 namespace orbgpu {
 
 constexpr int GC = ORBGPU_GRID_COLS, GR = ORBGPU_GRID_ROWS;
-
-struct Query {  // one row of the matcher: a projected map point
-    float x, y, r;      // window centre and half-size (r already multiplied by the level scale)
-    float ur;           // predicted right coordinate (mTrackProjXR / u - mbf*invz)
-    int min_level, max_level;
-    int active;         // 0: the reference `continue`s before the candidate loop
-    int blocking;       // a claim by this row hides the key point from later rows
-    int check_ur;       // apply the mvuRight gate (ORBmatcher.cc:91-96 / 1407-1413); off for :1472-1599
-    int gate;           // 1: Fuse's reprojection-error gates (ORBmatcher.cc:908-933) against F.inv_sigma2
-};
 
 struct FrameDev {
     int n;             // key point count, or the array capacity when n_dev is set
@@ -652,6 +643,13 @@ int validate_frame(const orbgpu_frame_view *f)
     return ORBGPU_OK;
 }
 
+// a builder's ORBGPU_ELEVEL as the library's error; fmt names the row, its level and the level count
+static int level_error(const Built &b, const char *fmt, int nlevels)
+{
+    set_error(fmt, b.row, b.level, nlevels);
+    return b.status;
+}
+
 static int upload_frame(ProjWorkspace &ws, const orbgpu_frame_view *f, FrameDev &F)
 {
     const size_t n = (size_t)f->n;
@@ -769,29 +767,6 @@ static int run_projection(int device_id, const orbgpu_frame_view *f, const std::
     if (row_match)  // the decision of every row (key point index or -1): what the claim-free matchers return
         ws.download(row_match, W_MATCH, sizeof(int) * m);
     return ws.finish();
-}
-
-// cv::Mat 3x3 * 3x1 + 3x1 (CV_32F): cv::gemm small-matrix path -> float products summed left to
-// right, then one add of the C term (adopted convention, DESIGN.md "float conventions").
-static void rt_apply(const float *T, const float *p, float *out)
-{
-    for (int i = 0; i < 3; i++) {
-        volatile float a = T[4 * i + 0] * p[0];
-        volatile float b = T[4 * i + 1] * p[1];
-        volatile float c = T[4 * i + 2] * p[2];
-        volatile float t0 = a + b;
-        volatile float t1 = t0 + c;
-        out[i] = t1 + T[4 * i + 3];
-    }
-}
-static void minus_rt_t(const float *T, float *out)
-{
-    for (int i = 0; i < 3; i++) {
-        double s = 0;
-        for (int k = 0; k < 3; k++)
-            s += (double)T[4 * k + i] * (double)T[4 * k + 3];
-        out[i] = (float)(s * -1.0);
-    }
 }
 
 // ---- device-resident Tracking::SearchLocalPoints (Tracking.cc:1447-1497) -----------------------------
@@ -1298,41 +1273,15 @@ int orbgpu_search_by_projection(const orbgpu_frame_view *f, const orbgpu_mappoin
     if (mp->m > 0)
         ORBGPU_REQUIRE(mp->in_view && mp->level && mp->view_cos && mp->proj_x && mp->proj_y && mp->proj_xr && mp->desc,
                        "null map point arrays");
-    rc = select_device(device_id);
-    if (rc != ORBGPU_OK)
+    if ((rc = select_device(device_id)) != ORBGPU_OK)
         return rc;
-    const bool bFactor = th != 1.0;
-    std::vector<Query> q((size_t)mp->m);
-    for (int i = 0; i < mp->m; i++) {
-        Query &Q = q[i];
-        Q = Query{};
-        Q.blocking = mp->obs_pos ? (mp->obs_pos[i] != 0) : 1;
-        if (!mp->in_view[i] || (mp->bad && mp->bad[i]))
-            continue;
-        const int lvl = mp->level[i];
-        if (lvl < 0 || lvl >= f->nlevels) {
-            set_error("map point %d: predicted level %d outside [0,%d)", i, lvl, f->nlevels);
-            return ORBGPU_ELEVEL;  // H5
-        }
-        float r = (double)mp->view_cos[i] > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos, :131-137
-        if (bFactor)
-            r *= th;
-        Q.r = r * f->scale_factors[lvl];
-        Q.x = mp->proj_x[i];
-        Q.y = mp->proj_y[i];
-        Q.ur = mp->proj_xr[i];
-        Q.min_level = lvl - 1;
-        Q.max_level = lvl;
-        Q.check_ur = 1;
-        Q.active = 1;
-    }
-    std::vector<int> init((size_t)std::max(f->n, 1));
-    for (int j = 0; j < f->n; j++) {
-        const int v = kp_to_mp[j];
-        ORBGPU_REQUIRE(v >= -2 && v < mp->m, "kp_to_mp[%d] = %d out of range", j, v);
-        const bool held = v == -2 || (v >= 0 && (mp->obs_pos ? mp->obs_pos[v] != 0 : true));
-        init[j] = held ? -1 : INT_MAX;
-    }
+    std::vector<Query> q;
+    const Built b = queries_local(f, mp, th, q);
+    if (b.status != ORBGPU_OK)
+        return level_error(b, "map point %d: predicted level %d outside [0,%d)", f->nlevels);
+    std::vector<int> init;
+    const int j = claim_init_observed(kp_to_mp, f->n, mp->m, mp->obs_pos, init);
+    ORBGPU_REQUIRE(j < 0, "kp_to_mp[%d] = %d out of range", j, kp_to_mp[j]);
     return run_projection<0>(device_id, f, q, mp->desc, nullptr, nullptr, init, nnratio, ORBGPU_TH_HIGH, 0, kp_to_mp, nmatches);
 }
 
@@ -1442,10 +1391,8 @@ int orbgpu_search_by_projection_last_device(const orbgpu_device_frame_view *cur,
     const int m = last->cap, cap = cur->cap;
     if ((rc = reserve_rows(*ws, (size_t)m, (size_t)cap)) != ORBGPU_OK)
         return rc;
-    // :1339-1349 forward / backward motion from the two poses (host: 2 x 12 floats)
-    float twc[3], tlc[3];
-    minus_rt_t(cur_Tcw, twc);
-    rt_apply(last_Tcw, twc, tlc);
+    bool forward, backward;  // from the two poses (host: 2 x 12 floats)
+    last_motion(cur_Tcw, last_Tcw, mb, mono, forward, backward);
     LastParams P;
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 4; c++)
@@ -1453,8 +1400,7 @@ int orbgpu_search_by_projection_last_device(const orbgpu_device_frame_view *cur,
     P.fx = fx, P.fy = fy, P.cx = cx, P.cy = cy, P.mbf = mbf;
     P.min_x = cur->min_x, P.max_x = cur->max_x, P.min_y = cur->min_y, P.max_y = cur->max_y;
     P.th = th;
-    P.forward = (tlc[2] > mb && !mono) ? 1 : 0;
-    P.backward = (-tlc[2] > mb && !mono) ? 1 : 0;
+    P.forward = forward, P.backward = backward;
     P.nlevels = cur->nlevels;
     for (int l = 0; l < ORBGPU_MAX_LEVELS; l++)
         P.scale_factors[l] = l < cur->nlevels ? cur->scale_factors[l] : 0.f;
@@ -1595,68 +1541,15 @@ int orbgpu_search_by_projection_last(const orbgpu_frame_view *cur, const float *
         ORBGPU_REQUIRE(last->has_mp && last->world_pos && last->desc && last->kp_octave, "null last-frame arrays");
     ORBGPU_REQUIRE(!check_orientation || ((last->n == 0 || last->kp_angle) && (cur->n == 0 || cur->kp_angle)),
                    "orientation check needs angles");
-    rc = select_device(device_id);
-    if (rc != ORBGPU_OK)
+    if ((rc = select_device(device_id)) != ORBGPU_OK)
         return rc;
-    // :1339-1349 forward / backward motion
-    float twc[3], tlc[3];
-    minus_rt_t(cur_Tcw, twc);
-    rt_apply(last->Tcw, twc, tlc);
-    const bool bForward = tlc[2] > mb && !mono;
-    const bool bBackward = -tlc[2] > mb && !mono;
-    std::vector<Query> q((size_t)last->n);
-    for (int i = 0; i < last->n; i++) {
-        Query &Q = q[i];
-        Q = Query{};
-        Q.blocking = last->obs_pos ? (last->obs_pos[i] != 0) : 1;
-        if (!last->has_mp[i] || (last->outlier && last->outlier[i]))
-            continue;
-        // :1360-1376 projection (per-point float arithmetic of the boundary, O(n))
-        float xc3[3];
-        rt_apply(cur_Tcw, last->world_pos + 3 * (size_t)i, xc3);
-        const float invzc = (float)(1.0 / (double)xc3[2]);
-        if (invzc < 0)
-            continue;
-        volatile float ux = fx * xc3[0];
-        volatile float ux2 = ux * invzc;
-        const float u = ux2 + cx;
-        volatile float vy = fy * xc3[1];
-        volatile float vy2 = vy * invzc;
-        const float v = vy2 + cy;
-        if (u < cur->min_x || u > cur->max_x)
-            continue;
-        if (v < cur->min_y || v > cur->max_y)
-            continue;
-        const int oct = last->kp_octave[i];
-        if (oct < 0 || oct >= cur->nlevels) {
-            set_error("last-frame key point %d: octave %d outside [0,%d)", i, oct, cur->nlevels);
-            return ORBGPU_ELEVEL;
-        }
-        Q.r = th * cur->scale_factors[oct];
-        Q.x = u;
-        Q.y = v;
-        volatile float bz = mbf * invzc;
-        Q.ur = u - bz;
-        if (bForward) {
-            Q.min_level = oct;
-            Q.max_level = -1;
-        } else if (bBackward) {
-            Q.min_level = 0;
-            Q.max_level = oct;
-        } else {
-            Q.min_level = oct - 1;
-            Q.max_level = oct + 1;
-        }
-        Q.check_ur = 1;
-        Q.active = 1;
-    }
-    std::vector<int> init((size_t)std::max(cur->n, 1));
-    for (int j = 0; j < cur->n; j++) {
-        const int v = kp_to_mp[j];
-        ORBGPU_REQUIRE(v >= -2 && v < last->n, "kp_to_mp[%d] = %d out of range", j, v);
-        const bool held = v == -2 || (v >= 0 && (last->obs_pos ? last->obs_pos[v] != 0 : true));
-        init[j] = held ? -1 : INT_MAX;
-    }
+    std::vector<Query> q;
+    const Built b = queries_last(cur, cur_Tcw, Pinhole{fx, fy, cx, cy, mbf}, mb, last, th, mono, q);
+    if (b.status != ORBGPU_OK)
+        return level_error(b, "last-frame key point %d: octave %d outside [0,%d)", cur->nlevels);
+    std::vector<int> init;
+    const int j = claim_init_observed(kp_to_mp, cur->n, last->n, last->obs_pos, init);
+    ORBGPU_REQUIRE(j < 0, "kp_to_mp[%d] = %d out of range", j, kp_to_mp[j]);
     return run_projection<1>(device_id, cur, q, last->desc, last->kp_angle, cur->kp_angle, init, 0.f, ORBGPU_TH_HIGH,
                              check_orientation, kp_to_mp, nmatches);
 }
@@ -1677,55 +1570,14 @@ int orbgpu_search_by_projection_keyframe(const orbgpu_frame_view *cur, const flo
     ORBGPU_REQUIRE(!check_orientation || ((kf->n == 0 || kf->kp_angle) && (cur->n == 0 || cur->kp_angle)),
                    "orientation check needs angles");
     ORBGPU_REQUIRE(log_scale_factor > 0, "log_scale_factor must be positive");
-    rc = select_device(device_id);
-    if (rc != ORBGPU_OK)
+    if ((rc = select_device(device_id)) != ORBGPU_OK)
         return rc;
-    float Ow[3];
-    minus_rt_t(cur_Tcw, Ow);  // :1478
-    std::vector<Query> q((size_t)kf->n);
-    for (int i = 0; i < kf->n; i++) {
-        Query &Q = q[i];
-        Q = Query{};
-        Q.blocking = 1;  // :1540-1541: any association hides the key point
-        if (!kf->has_mp[i] || (kf->bad && kf->bad[i]) || (kf->already_found && kf->already_found[i]))
-            continue;
-        const float *Pw = kf->world_pos + 3 * (size_t)i;
-        float xc3[3];
-        rt_apply(cur_Tcw, Pw, xc3);
-        const float invzc = (float)(1.0 / (double)xc3[2]);
-        volatile float ux = fx * xc3[0];
-        volatile float ux2 = ux * invzc;
-        const float u = ux2 + cx;
-        volatile float vy = fy * xc3[1];
-        volatile float vy2 = vy * invzc;
-        const float v = vy2 + cy;
-        if (u < cur->min_x || u > cur->max_x)
-            continue;
-        if (v < cur->min_y || v > cur->max_y)
-            continue;
-        const float PO[3] = {Pw[0] - Ow[0], Pw[1] - Ow[1], Pw[2] - Ow[2]};
-        // cv::norm accumulates in double
-        const float dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
-        const float maxDistance = kf->max_dist_inv[i], minDistance = kf->min_dist_inv[i];
-        if (dist3D < minDistance || dist3D > maxDistance)
-            continue;
-        const float ratio = kf->max_dist[i] / dist3D;
-        const int lvl = (int)ceilf(logf(ratio) / log_scale_factor);  // MapPoint::PredictScale
-        if (lvl < 0 || lvl >= cur->nlevels) {
-            set_error("key-frame map point %d: predicted level %d outside [0,%d)", i, lvl, cur->nlevels);
-            return ORBGPU_ELEVEL;
-        }
-        Q.r = th * cur->scale_factors[lvl];
-        Q.x = u;
-        Q.y = v;
-        Q.min_level = lvl - 1;
-        Q.max_level = lvl + 1;
-        Q.check_ur = 0;
-        Q.active = 1;
-    }
-    std::vector<int> init((size_t)std::max(cur->n, 1));
-    for (int j = 0; j < cur->n; j++)
-        init[j] = kp_to_mp[j] == -1 ? INT_MAX : -1;
+    std::vector<Query> q;
+    const Built b = queries_keyframe(cur, cur_Tcw, Pinhole{fx, fy, cx, cy, 0.f}, log_scale_factor, kf, th, q);
+    if (b.status != ORBGPU_OK)
+        return level_error(b, "key-frame map point %d: predicted level %d outside [0,%d)", cur->nlevels);
+    std::vector<int> init;
+    claim_init_free(kp_to_mp, cur->n, init);
     // the matcher writes indices of `kf` rows; occupied key points keep their value
     return run_projection<1>(device_id, cur, q, kf->desc, kf->kp_angle, cur->kp_angle, init, 0.f, orb_dist, check_orientation,
                              kp_to_mp, nmatches);
@@ -1743,76 +1595,19 @@ int orbgpu_search_by_projection_sim3(const orbgpu_frame_view *kf, const float *S
     if (pts->m > 0)
         ORBGPU_REQUIRE(pts->world_pos && pts->normal && pts->min_dist && pts->max_dist && pts->desc, "null point arrays");
     ORBGPU_REQUIRE(log_scale_factor > 0, "log_scale_factor must be positive");
-    rc = select_device(device_id);
-    if (rc != ORBGPU_OK)
+    if ((rc = select_device(device_id)) != ORBGPU_OK)
         return rc;
-    // Scw = [s R | s t] decomposed as ORBmatcher.cc:299-303 does: scw from the first row (double dot), then
-    // cv::Mat / scalar (float multiply by (float)(1/scw)), Ow = -Rcw^T tcw
-    float T[16] = {0}, Ow[3];
-    {
-        const double d = (double)Scw[0] * Scw[0] + (double)Scw[1] * Scw[1] + (double)Scw[2] * Scw[2];
-        const float scw = (float)sqrt(d);
-        ORBGPU_REQUIRE(scw > 0.f, "degenerate Scw");
-        const float alpha = (float)(1.0 / (double)scw);
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 4; c++) {
-                volatile float v = Scw[4 * r + c] * alpha;
-                T[4 * r + c] = v;
-            }
-        minus_rt_t(T, Ow);
-    }
-    // spAlreadyFound (:306-307): points some key point of the key frame already holds
-    std::vector<uint8_t> found((size_t)std::max(pts->m, 1), 0);
-    for (int j = 0; j < kf->n; j++) {
-        const int v = kp_to_mp[j];
-        ORBGPU_REQUIRE(v >= -2 && v < pts->m, "kp_to_mp[%d] = %d out of range", j, v);
-        if (v >= 0)
-            found[v] = 1;
-    }
-    std::vector<Query> q((size_t)pts->m);
-    for (int i = 0; i < pts->m; i++) {
-        Query &Q = q[i];
-        Q = Query{};
-        Q.blocking = 1;  // :394 vpMatched[bestIdx] = pMP hides the key point from every later point
-        if ((pts->bad && pts->bad[i]) || found[i])
-            continue;
-        const float *Pw = pts->world_pos + 3 * (size_t)i;
-        float pc[3];
-        rt_apply(T, Pw, pc);
-        if (pc[2] < 0.0f)
-            continue;
-        const float invz = 1 / pc[2];
-        volatile float x = pc[0] * invz, y = pc[1] * invz;
-        volatile float ux = fx * x, vy = fy * y;
-        const float u = ux + cx, v = vy + cy;
-        if (!(u >= kf->min_x && u < kf->max_x && v >= kf->min_y && v < kf->max_y))  // KeyFrame::IsInImage
-            continue;
-        const float maxDistance = 1.2f * pts->max_dist[i], minDistance = 0.8f * pts->min_dist[i];
-        const float PO[3] = {Pw[0] - Ow[0], Pw[1] - Ow[1], Pw[2] - Ow[2]};
-        const float dist = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
-        if (dist < minDistance || dist > maxDistance)
-            continue;
-        const float *Pn = pts->normal + 3 * (size_t)i;
-        const double dot = (double)PO[0] * Pn[0] + (double)PO[1] * Pn[1] + (double)PO[2] * Pn[2];
-        if (dot < 0.5 * dist)  // viewing angle below 60 degrees (:352)
-            continue;
-        const float ratio = pts->max_dist[i] / dist;
-        const int lvl = (int)ceilf(logf(ratio) / log_scale_factor);  // MapPoint::PredictScale
-        if (lvl < 0 || lvl >= kf->nlevels) {
-            set_error("point %d: predicted level %d outside [0,%d)", i, lvl, kf->nlevels);
-            return ORBGPU_ELEVEL;
-        }
-        Q.r = (float)th * kf->scale_factors[lvl];
-        Q.x = u;
-        Q.y = v;
-        Q.min_level = lvl - 1;
-        Q.max_level = lvl;
-        Q.check_ur = 0;
-        Q.active = 1;
-    }
-    std::vector<int> init((size_t)std::max(kf->n, 1));
-    for (int j = 0; j < kf->n; j++)
-        init[j] = kp_to_mp[j] == -1 ? INT_MAX : -1;  // :373 vpMatched[idx] set: skipped
+    float T[16], Ow[3];
+    ORBGPU_REQUIRE(sim3_to_rt(Scw, T, Ow), "degenerate Scw");
+    std::vector<int> init;       // :373 vpMatched[idx] set: skipped
+    std::vector<uint8_t> found;  // spAlreadyFound (:306-307): points some key point of the key frame already holds
+    const int j = claim_init_free(kp_to_mp, kf->n, init, pts->m, &found);
+    ORBGPU_REQUIRE(j < 0, "kp_to_mp[%d] = %d out of range", j, kp_to_mp[j]);
+    std::vector<Query> q;  // blocking: :394 vpMatched[bestIdx] = pMP hides the key point from every later point
+    const Built b = queries_points(kf, T, Ow, Pinhole{fx, fy, cx, cy, 0.f}, log_scale_factor, pts, found.data(), (float)th,
+                                   Recip::Float, 1, 0, q);
+    if (b.status != ORBGPU_OK)
+        return level_error(b, "point %d: predicted level %d outside [0,%d)", kf->nlevels);
     return run_projection<1>(device_id, kf, q, pts->desc, nullptr, nullptr, init, 0.f, ORBGPU_TH_LOW, 0, kp_to_mp, nmatches);
 }
 
@@ -1820,47 +1615,6 @@ int orbgpu_search_by_projection_sim3(const orbgpu_frame_view *kf, const float *S
 // Host side = the O(m) projection of the boundary in the reference's float conventions; device side = the same
 // window walk / ranking as the projection matchers with rows that never block, so every row keeps the first
 // candidate of least distance (`dist < bestDist`), subject to the distance threshold.
-namespace {
-
-struct PointGate {  // outcome of the per-point tests up to the window search
-    bool ok = false;
-    float u = 0, v = 0, ur = 0;
-    int lvl = 0;
-};
-
-// common tail of the per-point tests: image bounds (KeyFrame::IsInImage), scale-invariance range, viewing angle
-// (optional), PredictScale.  Returns ORBGPU_ELEVEL through rc when the level is out of range.
-static PointGate point_gate(const float pc[3], float invz, float fx, float fy, float cx, float cy, float bf,
-                            const orbgpu_frame_view *kf, float dist3D, const float *PO, const float *Pn, float min_dist,
-                            float max_dist, float log_sf, int &rc, int i)
-{
-    PointGate g;
-    volatile float x = pc[0] * invz, y = pc[1] * invz;
-    volatile float ux = fx * x, vy = fy * y;
-    const float u = ux + cx, v = vy + cy;
-    if (!(u >= kf->min_x && u < kf->max_x && v >= kf->min_y && v < kf->max_y))
-        return g;
-    const float maxDistance = 1.2f * max_dist, minDistance = 0.8f * min_dist;
-    if (dist3D < minDistance || dist3D > maxDistance)
-        return g;
-    if (Pn) {
-        const double dot = (double)PO[0] * Pn[0] + (double)PO[1] * Pn[1] + (double)PO[2] * Pn[2];
-        if (dot < 0.5 * dist3D)
-            return g;
-    }
-    const float ratio = max_dist / dist3D;
-    const int lvl = (int)ceilf(logf(ratio) / log_sf);  // MapPoint::PredictScale
-    if (lvl < 0 || lvl >= kf->nlevels) {
-        set_error("point %d: predicted level %d outside [0,%d)", i, lvl, kf->nlevels);
-        rc = ORBGPU_ELEVEL;
-        return g;
-    }
-    volatile float bz = bf * invz;
-    g.ok = true;
-    g.u = u, g.v = v, g.ur = u - bz, g.lvl = lvl;
-    return g;
-}
-
 static int validate_points(const orbgpu_points_view *pts, bool need_normal)
 {
     ORBGPU_REQUIRE(pts && pts->m >= 0, "bad point view");
@@ -1870,18 +1624,22 @@ static int validate_points(const orbgpu_points_view *pts, bool need_normal)
     return ORBGPU_OK;
 }
 
-// queries -> best key point per row (first of least distance, <= th_dist), -1 otherwise
-static int best_rows(const orbgpu_frame_view *kf, std::vector<Query> &q, const uint8_t *row_desc, int th_dist,
-                     const float *inv_sigma2, int32_t *best_idx, int32_t device_id)
+// the rows a builder made (or its level error) -> best key point per row (first of least distance, <= th_dist), -1
+// otherwise; n_found (optional): how many rows have one
+static int best_rows(const Built &b, const orbgpu_frame_view *kf, std::vector<Query> &q, const uint8_t *row_desc, int th_dist,
+                     const float *inv_sigma2, int32_t *best_idx, int32_t *n_found, int32_t device_id)
 {
+    if (b.status != ORBGPU_OK)
+        return level_error(b, "point %d: predicted level %d outside [0,%d)", kf->nlevels);
     std::vector<int> init((size_t)std::max(kf->n, 1), INT_MAX);  // nothing is claimed, nobody blocks
     std::vector<int32_t> k2m((size_t)std::max(kf->n, 1), -1);
     int32_t nm = 0;
-    return run_projection<1>(device_id, kf, q, row_desc, nullptr, nullptr, init, 0.f, th_dist, 0, k2m.data(), &nm, best_idx,
-                             inv_sigma2);
+    const int rc = run_projection<1>(device_id, kf, q, row_desc, nullptr, nullptr, init, 0.f, th_dist, 0, k2m.data(), &nm,
+                                     best_idx, inv_sigma2);
+    if (rc == ORBGPU_OK && n_found)
+        *n_found = (int32_t)std::count_if(best_idx, best_idx + q.size(), [](int32_t idx) { return idx >= 0; });
+    return rc;
 }
-
-} // namespace
 
 int orbgpu_fuse(const orbgpu_frame_view *kf, const float *Tcw, float fx, float fy, float cx, float cy, float bf,
                 float log_scale_factor, const orbgpu_points_view *pts, float th, const float *inv_level_sigma2,
@@ -1896,39 +1654,10 @@ int orbgpu_fuse(const orbgpu_frame_view *kf, const float *Tcw, float fx, float f
         return rc;
     float Ow[3];
     minus_rt_t(Tcw, Ow);
-    std::vector<Query> q((size_t)pts->m);
-    for (int i = 0; i < pts->m; i++) {
-        Query &Q = q[i];
-        Q = Query{};
-        if (pts->bad && pts->bad[i])
-            continue;
-        const float *Pw = pts->world_pos + 3 * (size_t)i;
-        float pc[3];
-        rt_apply(Tcw, Pw, pc);
-        if (pc[2] < 0.0f)
-            continue;
-        const float invz = 1 / pc[2];  // :857 (float division)
-        const float PO[3] = {Pw[0] - Ow[0], Pw[1] - Ow[1], Pw[2] - Ow[2]};
-        const float dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
-        const PointGate g = point_gate(pc, invz, fx, fy, cx, cy, bf, kf, dist3D, PO, pts->normal + 3 * (size_t)i,
-                                       pts->min_dist[i], pts->max_dist[i], log_scale_factor, rc, i);
-        if (rc != ORBGPU_OK)
-            return rc;
-        if (!g.ok)
-            continue;
-        Q.r = th * kf->scale_factors[g.lvl];
-        Q.x = g.u, Q.y = g.v, Q.ur = g.ur;
-        Q.min_level = g.lvl - 1, Q.max_level = g.lvl;
-        Q.gate = 1;
-        Q.active = 1;
-    }
-    if ((rc = best_rows(kf, q, pts->desc, ORBGPU_TH_LOW, inv_level_sigma2, best_idx, device_id)) != ORBGPU_OK)
-        return rc;
-    int n = 0;
-    for (int i = 0; i < pts->m; i++)
-        n += best_idx[i] >= 0;
-    *n_candidates = n;
-    return ORBGPU_OK;
+    std::vector<Query> q;  // :859 float division, ur = u - bf*invz, the chi-square gates
+    const Built b = queries_points(kf, Tcw, Ow, Pinhole{fx, fy, cx, cy, bf}, log_scale_factor, pts, nullptr, th, Recip::Float,
+                                   0, 1, q);
+    return best_rows(b, kf, q, pts->desc, ORBGPU_TH_LOW, inv_level_sigma2, best_idx, n_candidates, device_id);
 }
 
 int orbgpu_fuse_sim3(const orbgpu_frame_view *kf, const float *Scw, float fx, float fy, float cx, float cy,
@@ -1942,89 +1671,22 @@ int orbgpu_fuse_sim3(const orbgpu_frame_view *kf, const float *Scw, float fx, fl
     ORBGPU_REQUIRE(log_scale_factor > 0, "log_scale_factor must be positive");
     if ((rc = select_device(device_id)) != ORBGPU_OK)
         return rc;
-    float T[16] = {0}, Ow[3];
-    {  // :985-989, as orbgpu_search_by_projection_sim3
-        const double d = (double)Scw[0] * Scw[0] + (double)Scw[1] * Scw[1] + (double)Scw[2] * Scw[2];
-        const float scw = (float)sqrt(d);
-        ORBGPU_REQUIRE(scw > 0.f, "degenerate Scw");
-        const float alpha = (float)(1.0 / (double)scw);
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 4; c++) {
-                volatile float v = Scw[4 * r + c] * alpha;
-                T[4 * r + c] = v;
-            }
-        minus_rt_t(T, Ow);
-    }
-    std::vector<Query> q((size_t)pts->m);
-    for (int i = 0; i < pts->m; i++) {
-        Query &Q = q[i];
-        Q = Query{};
-        if (pts->bad && pts->bad[i])
-            continue;
-        const float *Pw = pts->world_pos + 3 * (size_t)i;
-        float pc[3];
-        rt_apply(T, Pw, pc);
-        if (pc[2] < 0.0f)
-            continue;
-        const float invz = (float)(1.0 / (double)pc[2]);  // :1017
-        const float PO[3] = {Pw[0] - Ow[0], Pw[1] - Ow[1], Pw[2] - Ow[2]};
-        const float dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
-        const PointGate g = point_gate(pc, invz, fx, fy, cx, cy, 0.f, kf, dist3D, PO, pts->normal + 3 * (size_t)i,
-                                       pts->min_dist[i], pts->max_dist[i], log_scale_factor, rc, i);
-        if (rc != ORBGPU_OK)
-            return rc;
-        if (!g.ok)
-            continue;
-        Q.r = th * kf->scale_factors[g.lvl];
-        Q.x = g.u, Q.y = g.v;
-        Q.min_level = g.lvl - 1, Q.max_level = g.lvl;
-        Q.active = 1;
-    }
-    if ((rc = best_rows(kf, q, pts->desc, ORBGPU_TH_LOW, nullptr, best_idx, device_id)) != ORBGPU_OK)
-        return rc;
-    int n = 0;
-    for (int i = 0; i < pts->m; i++)
-        n += best_idx[i] >= 0;
-    *n_candidates = n;
-    return ORBGPU_OK;
+    float T[16], Ow[3];
+    ORBGPU_REQUIRE(sim3_to_rt(Scw, T, Ow), "degenerate Scw");  // :985-989
+    std::vector<Query> q;  // :1019 double division
+    const Built b = queries_points(kf, T, Ow, Pinhole{fx, fy, cx, cy, 0.f}, log_scale_factor, pts, nullptr, th,
+                                   Recip::ViaDouble, 0, 0, q);
+    return best_rows(b, kf, q, pts->desc, ORBGPU_TH_LOW, nullptr, best_idx, n_candidates, device_id);
 }
 
 // one direction of SearchBySim3 (:1143-1227 / :1229-1307)
-static int sim3_direction(const orbgpu_frame_view *kfB, const float *Taw, const float sR[9], const float t[3], float fx,
-                          float fy, float cx, float cy, float log_sfB, const orbgpu_points_view *ptsA,
-                          const uint8_t *skipA, float th, int32_t *match, int32_t device_id)
+static int sim3_direction(const orbgpu_frame_view *kfB, const float *Taw, const float sR[9], const float t[3],
+                          const Pinhole &K, float log_sfB, const orbgpu_points_view *ptsA, const uint8_t *skipA, float th,
+                          int32_t *match, int32_t device_id)
 {
-    int rc = ORBGPU_OK;
-    std::vector<Query> q((size_t)ptsA->m);
-    for (int i = 0; i < ptsA->m; i++) {
-        Query &Q = q[i];
-        Q = Query{};
-        if ((ptsA->bad && ptsA->bad[i]) || (skipA && skipA[i]))
-            continue;
-        float pa[3], pb[3];
-        rt_apply(Taw, ptsA->world_pos + 3 * (size_t)i, pa);
-        for (int r = 0; r < 3; r++) {
-            volatile float a = sR[3 * r] * pa[0], b = sR[3 * r + 1] * pa[1], c = sR[3 * r + 2] * pa[2];
-            volatile float t0 = a + b;
-            volatile float t1 = t0 + c;
-            pb[r] = t1 + t[r];
-        }
-        if ((double)pb[2] < 0.0)
-            continue;
-        const float invz = (float)(1.0 / (double)pb[2]);
-        const float dist3D = (float)sqrt((double)pb[0] * pb[0] + (double)pb[1] * pb[1] + (double)pb[2] * pb[2]);
-        const PointGate g = point_gate(pb, invz, fx, fy, cx, cy, 0.f, kfB, dist3D, nullptr, nullptr, ptsA->min_dist[i],
-                                       ptsA->max_dist[i], log_sfB, rc, i);
-        if (rc != ORBGPU_OK)
-            return rc;
-        if (!g.ok)
-            continue;
-        Q.r = th * kfB->scale_factors[g.lvl];
-        Q.x = g.u, Q.y = g.v;
-        Q.min_level = g.lvl - 1, Q.max_level = g.lvl;
-        Q.active = 1;
-    }
-    return best_rows(kfB, q, ptsA->desc, ORBGPU_TH_HIGH, nullptr, match, device_id);
+    std::vector<Query> q;
+    const Built b = queries_sim3_direction(kfB, Taw, sR, t, K, log_sfB, ptsA, skipA, th, q);
+    return best_rows(b, kfB, q, ptsA->desc, ORBGPU_TH_HIGH, nullptr, match, nullptr, device_id);
 }
 
 int orbgpu_search_by_sim3(const orbgpu_frame_view *kf1, const orbgpu_frame_view *kf2, const float *T1w, const float *T2w,
@@ -2043,23 +1705,11 @@ int orbgpu_search_by_sim3(const orbgpu_frame_view *kf1, const orbgpu_frame_view 
     if ((rc = select_device(device_id)) != ORBGPU_OK)
         return rc;
     float sR12[9], sR21[9], t21[3];
-    const double inv_s = 1.0 / (double)s12;
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) {
-            volatile float a = s12 * R12[3 * r + c];  // :1121
-            sR12[3 * r + c] = a;
-            sR21[3 * r + c] = (float)((double)R12[3 * c + r] * inv_s);  // :1122 (1.0/s12)*R12.t()
-        }
-    for (int r = 0; r < 3; r++) {  // :1123 t21 = -sR21*t12
-        volatile float a = sR21[3 * r] * t12[0], b = sR21[3 * r + 1] * t12[1], c = sR21[3 * r + 2] * t12[2];
-        volatile float t0 = a + b;
-        volatile float t1 = t0 + c;
-        t21[r] = -t1;
-    }
+    sim3_pair(s12, R12, t12, sR12, sR21, t21);
     std::vector<int32_t> m1((size_t)std::max(pts1->m, 1), -1), m2((size_t)std::max(pts2->m, 1), -1);
-    if ((rc = sim3_direction(kf2, T1w, sR21, t21, fx, fy, cx, cy, log_sf2, pts1, already1, th, m1.data(), device_id)) != ORBGPU_OK)
-        return rc;
-    if ((rc = sim3_direction(kf1, T2w, sR12, t12, fx, fy, cx, cy, log_sf1, pts2, already2, th, m2.data(), device_id)) != ORBGPU_OK)
+    const Pinhole K{fx, fy, cx, cy, 0.f};
+    if ((rc = sim3_direction(kf2, T1w, sR21, t21, K, log_sf2, pts1, already1, th, m1.data(), device_id)) != ORBGPU_OK ||
+        (rc = sim3_direction(kf1, T2w, sR12, t12, K, log_sf1, pts2, already2, th, m2.data(), device_id)) != ORBGPU_OK)
         return rc;
     int n = 0;
     for (int i1 = 0; i1 < pts1->m; i1++) {  // :1309-1323 agreement of the two directions
@@ -2177,22 +1827,10 @@ int orbgpu_search_for_initialization(const orbgpu_frame_view *f1, const orbgpu_f
         matches12[i] = -1;
     if (n1 == 0 || n2 == 0)
         return ORBGPU_OK;
-    // rows = the level-0 key points of F1 (:419-422)
     std::vector<int> row_of;
     std::vector<Query> q;
     std::vector<uint8_t> rdesc;
-    for (int i1 = 0; i1 < n1; i1++) {
-        if (f1->kp_octave[i1] > 0)
-            continue;
-        Query Q{};
-        Q.x = prev_matched[2 * i1], Q.y = prev_matched[2 * i1 + 1];
-        Q.r = (float)window_size;
-        Q.min_level = f1->kp_octave[i1], Q.max_level = f1->kp_octave[i1];  // GetFeaturesInArea(.., level1, level1)
-        Q.active = 1;
-        row_of.push_back(i1);
-        q.push_back(Q);
-        rdesc.insert(rdesc.end(), f1->desc + (size_t)i1 * 32, f1->desc + (size_t)i1 * 32 + 32);
-    }
+    queries_initialization(f1, prev_matched, window_size, row_of, q, rdesc);
     const int rows = (int)row_of.size();
     if (rows == 0)
         return ORBGPU_OK;
@@ -2236,7 +1874,6 @@ int orbgpu_search_for_initialization(const orbgpu_frame_view *f1, const orbgpu_f
     std::vector<std::pair<int, int>> pushes;  // (bin, i1) in push order
     int histo[ORBGPU_HISTO_LENGTH] = {0};
     int nm = 0;
-    const float factor = 1.0f / ORBGPU_HISTO_LENGTH;
     for (int r = 0; r < rows; r++) {
         const int i1 = row_of[r];
         uint64_t *b = &keys[off[r]], *e = b + counts[r];
@@ -2266,35 +1903,15 @@ int orbgpu_search_for_initialization(const orbgpu_frame_view *f1, const orbgpu_f
             vMatchedDistance[bestIdx2] = bestDist;
             nm++;
             if (check_orientation) {
-                float rot = f1->kp_angle[i1] - f2->kp_angle[bestIdx2];
-                if (rot < 0.0)
-                    rot += 360.0f;
-                int bin = (int)roundf(rot * factor);
-                if (bin == ORBGPU_HISTO_LENGTH)
-                    bin = 0;
+                const int bin = rot_bin(f1->kp_angle[i1], f2->kp_angle[bestIdx2]);
                 pushes.emplace_back(bin, i1);
                 histo[bin]++;
             }
         }
     }
     if (check_orientation) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;  // ComputeThreeMaxima, :1601-1642
-        for (int i = 0; i < ORBGPU_HISTO_LENGTH; i++) {
-            const int sz = histo[i];
-            if (sz > max1) {
-                max3 = max2, max2 = max1, max1 = sz;
-                ind3 = ind2, ind2 = ind1, ind1 = i;
-            } else if (sz > max2) {
-                max3 = max2, max2 = sz;
-                ind3 = ind2, ind2 = i;
-            } else if (sz > max3) {
-                max3 = sz, ind3 = i;
-            }
-        }
-        if ((float)max2 < 0.1f * (float)max1)
-            ind2 = ind3 = -1;
-        else if ((float)max3 < 0.1f * (float)max1)
-            ind3 = -1;
+        int ind1, ind2, ind3;
+        three_maxima(histo, ORBGPU_HISTO_LENGTH, ind1, ind2, ind3);
         for (const auto &pr : pushes) {
             if (pr.first == ind1 || pr.first == ind2 || pr.first == ind3)
                 continue;

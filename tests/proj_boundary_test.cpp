@@ -1,0 +1,333 @@
+// CPU-side unit test of the host boundary of the projection matchers (orb_slam2_map_amd/csrc/proj_boundary.h) and of the
+// rotation check's host build (matcher_common.h).  Plain g++ under ASan + UBSan, no HIP.  The camera and the points are
+// exact in float, so every expected value below is worked out by hand, never by the code under test:
+//   identity Tcw, fx = fy = 512, cx = 320, cy = 240, bounds [0,640] x [0,480], 8 levels of 1.2;
+//   A = (0,0,2) -> (320,240), B = (1.25,0,2) -> u = 640 = max_x, C = (-1.25,0,2) -> u = 0 = min_x, D = (0,0,-2) behind;
+//   |A| = 2, and max_dist = 3 gives ratio 1.5: log(1.5)/log(1.2) = 2.22 -> level 3; max_dist = 8 gives ratio 4:
+//   log(4)/log(1.2) = 7.60 -> level 8 = nlevels; |B| = |C| = 2.358, ratio 1.272 -> 1.32 -> level 2.
+#include "matcher_common.h"
+#include "proj_boundary.h"
+
+#include <cstdio>
+#include <cstring>
+
+#include "orb_oracle.h"
+
+using namespace orbgpu;
+
+static int failures = 0;
+#define CHECK(cond)                                                     \
+    do {                                                                \
+        if (!(cond)) {                                                  \
+            printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);    \
+            failures++;                                                 \
+        }                                                               \
+    } while (0)
+
+static const float I44[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+static const float I33[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+static const float ZERO3[3] = {0, 0, 0};
+static const Pinhole K{512.f, 512.f, 320.f, 240.f, 0.f};
+static const Pinhole K_STEREO{512.f, 512.f, 320.f, 240.f, 40.f};
+static const float A[3] = {0, 0, 2}, B[3] = {1.25f, 0, 2}, C[3] = {-1.25f, 0, 2}, D[3] = {0, 0, -2};
+static const float TOWARDS[3] = {0, 0, 1};  // a normal along the viewing ray of A
+static float SF[8], LOG_SF;
+static orbgpu_frame_view FRAME;
+
+struct Points {  // rows of an orbgpu_points_view / orbgpu_keyframe_view / orbgpu_lastframe_view, grown point by point
+    std::vector<float> pos, normal, min_dist, max_dist;
+    std::vector<uint8_t> yes, bad;
+    std::vector<int32_t> octave;
+    void add(const float *p, float mn = 0.5f, float mx = 3.f, const float *n = TOWARDS, int is_bad = 0)
+    {
+        pos.insert(pos.end(), p, p + 3);
+        normal.insert(normal.end(), n, n + 3);
+        min_dist.push_back(mn), max_dist.push_back(mx);
+        yes.push_back(1), bad.push_back((uint8_t)is_bad), octave.push_back(3);
+    }
+    orbgpu_points_view points() const
+    {
+        return orbgpu_points_view{(int32_t)yes.size(), bad.data(), pos.data(), normal.data(), min_dist.data(), max_dist.data(),
+                                  nullptr};
+    }
+    // min_dist / max_dist stand for the pre-scaled Get{Min,Max}DistanceInvariance; PredictScale's numerator is 3
+    orbgpu_keyframe_view keyframe(const std::vector<float> &numerator) const
+    {
+        return orbgpu_keyframe_view{(int32_t)yes.size(), yes.data(), nullptr, bad.data(), pos.data(), min_dist.data(),
+                                    max_dist.data(), numerator.data(), nullptr, nullptr};
+    }
+    orbgpu_lastframe_view last(const float *Tlw, const uint8_t *obs_pos = nullptr) const
+    {
+        return orbgpu_lastframe_view{(int32_t)yes.size(), yes.data(), bad.data(), obs_pos, pos.data(), nullptr, octave.data(),
+                                     nullptr, Tlw};
+    }
+};
+
+static bool row_is(const Query &Q, float x, float y, float r, int lo, int hi)
+{
+    return Q.active == 1 && Q.x == x && Q.y == y && Q.r == r && Q.min_level == lo && Q.max_level == hi;
+}
+
+static bool is_level_error(const Built &b, int row, int level)
+{
+    return b.status == ORBGPU_ELEVEL && b.row == row && b.level == level;
+}
+
+// the builders that take world points: all three flavours of queries_points and one direction of SearchBySim3
+enum Flavour { SIM3_PROJECTION, FUSE, FUSE_SIM3, SIM3_DIRECTION, N_FLAVOURS };
+static Built build(Flavour f, const Points &P, std::vector<Query> &q, const uint8_t *skip = nullptr, float th = 3.f)
+{
+    const orbgpu_points_view pts = P.points();
+    float Ow[3];
+    minus_rt_t(I44, Ow);
+    switch (f) {
+    case SIM3_PROJECTION: return queries_points(&FRAME, I44, Ow, K, LOG_SF, &pts, skip, th, Recip::Float, 1, 0, q);
+    case FUSE: return queries_points(&FRAME, I44, Ow, K_STEREO, LOG_SF, &pts, skip, th, Recip::Float, 0, 1, q);
+    case FUSE_SIM3: return queries_points(&FRAME, I44, Ow, K, LOG_SF, &pts, skip, th, Recip::ViaDouble, 0, 0, q);
+    default: return queries_sim3_direction(&FRAME, I44, I33, ZERO3, K, LOG_SF, &pts, skip, th, q);
+    }
+}
+
+static void test_bounds_and_behind()
+{
+    Points P;
+    P.add(B), P.add(C), P.add(D), P.add(A);
+    P.min_dist.assign(4, 0.5f), P.max_dist.assign(4, 10.f);  // as invariance bounds for the key-frame flavour
+    std::vector<Query> q;
+    const orbgpu_lastframe_view last = P.last(I44);
+    CHECK(queries_last(&FRAME, I44, K, 0.f, &last, 1.f, 1, q).status == ORBGPU_OK);
+    CHECK(q[0].active && q[0].x == 640.f && q[1].active && q[1].x == 0.f);  // both ends inclusive (:1373)
+    CHECK(!q[2].active && q[3].active);                                    // invzc < 0 (:1367)
+    const std::vector<float> three(4, 3.f);
+    const orbgpu_keyframe_view kf = P.keyframe(three);
+    CHECK(queries_keyframe(&FRAME, I44, K, LOG_SF, &kf, 1.f, q).status == ORBGPU_OK);
+    CHECK(q[0].active && q[0].x == 640.f && q[1].active && q[1].x == 0.f && q[3].active);
+    // ORBmatcher.cc:1502-1510 has no behind-camera test: D projects to 512*0*(-0.5) + 320 = 320 and stays a row, as in the
+    // reference and as before this header existed
+    CHECK(row_is(q[2], 320.f, 240.f, SF[3], 2, 4));
+    P.max_dist.assign(4, 3.f);
+    for (int f = 0; f < N_FLAVOURS; f++) {
+        CHECK(build((Flavour)f, P, q).status == ORBGPU_OK);
+        CHECK(!q[0].active);                   // KeyFrame::IsInImage: u < max_x
+        CHECK(q[1].active && q[1].x == 0.f);   // u >= min_x
+        CHECK(!q[2].active && q[3].active);    // z < 0
+    }
+}
+
+static void test_distance_range_and_normal()
+{
+    // |A| = 2 against 0.8*min_dist and 1.2*max_dist: 0.8*2.51 = 2.008 > 2, 0.8*2.49 = 1.992; 1.2*1.66 = 1.992 < 2,
+    // 1.2*1.67 = 2.004 (the margins are 1e4 times the rounding of the float product)
+    const float away[3] = {0.875f, 0, 0.484375f};  // 61 degrees from the ray: PO.n = 0.96875 < 0.5*|PO| = 1
+    const float at60[3] = {0.75f, 0, 0.5f};        // PO.n = 1: `<` does not reject the bound itself
+    Points P;
+    P.add(A, 2.51f, 3.f), P.add(A, 2.49f, 3.f), P.add(A, 0.5f, 1.66f), P.add(A, 0.5f, 1.67f), P.add(A, 0.5f, 3.f, away),
+        P.add(A, 0.5f, 3.f, at60);
+    std::vector<Query> q;
+    for (int f = 0; f < N_FLAVOURS; f++) {
+        CHECK(build((Flavour)f, P, q).status == ORBGPU_OK);
+        CHECK(!q[0].active && q[1].active && !q[2].active && q[3].active);
+        CHECK(q[3].min_level == -1 && q[3].max_level == 0);  // ratio 0.835: log < 0, ceil(-0.99) = 0
+        CHECK(q[4].active == (f == SIM3_DIRECTION));         // SearchBySim3 tests no normal
+        CHECK(q[5].active);
+    }
+    // the key-frame flavour compares with the caller's pre-scaled bounds as they are
+    Points R;
+    R.add(A, 2.f, 10.f), R.add(A, nextafterf(2.f, 3.f), 10.f), R.add(A, 0.5f, 2.f), R.add(A, 0.5f, nextafterf(2.f, 0.f));
+    const std::vector<float> three(4, 3.f);
+    const orbgpu_keyframe_view kf = R.keyframe(three);
+    CHECK(queries_keyframe(&FRAME, I44, K, LOG_SF, &kf, 1.f, q).status == ORBGPU_OK);
+    CHECK(q[0].active && !q[1].active && q[2].active && !q[3].active);
+}
+
+static void test_levels_and_flags()
+{
+    std::vector<Query> q;
+    {  // queries_local: [lvl-1, lvl], check_ur, radius by viewing cosine, th only when != 1
+        const uint8_t in_view[4] = {1, 1, 0, 1}, is_bad[4] = {0, 0, 0, 1}, obs_pos[4] = {0, 1, 1, 0};
+        const int32_t level[4] = {3, 0, 3, 3};
+        const float view_cos[4] = {0.999f, 0.9f, 0.999f, 0.999f}, x[4] = {10, 20, 30, 40}, y[4] = {11, 21, 31, 41},
+                    xr[4] = {5, -1, 6, 7};
+        const orbgpu_mappoint_view mp{4, in_view, is_bad, obs_pos, level, view_cos, x, y, xr, nullptr};
+        CHECK(queries_local(&FRAME, &mp, 1.f, q).status == ORBGPU_OK);
+        CHECK(row_is(q[0], 10.f, 11.f, 2.5f * SF[3], 2, 3) && q[0].ur == 5.f && q[0].check_ur == 1 && q[0].blocking == 0);
+        CHECK(row_is(q[1], 20.f, 21.f, 4.0f, -1, 0) && q[1].blocking == 1 && q[1].gate == 0);
+        CHECK(!q[2].active && q[2].blocking == 1 && !q[3].active && q[3].blocking == 0);  // not in view, isBad()
+        CHECK(queries_local(&FRAME, &mp, 2.f, q).status == ORBGPU_OK && q[0].r == 5.0f * SF[3]);
+    }
+    {  // queries_last: tlc = Rlw*twc + tlw = tlw for an identity current pose; its z against the baseline mb = 0.5
+        Points P;
+        P.add(A), P.add(A, 0.5f, 3.f, TOWARDS, 1);
+        const uint8_t obs_pos[2] = {0, 1};
+        float ahead[16], back[16];
+        memcpy(ahead, I44, sizeof(I44)), memcpy(back, I44, sizeof(I44));
+        ahead[11] = 1.f, back[11] = -1.f;
+        const float r = 7.f * SF[3];
+        const struct { const float *Tlw; int mono, lo, hi; } cases[] = {
+            {I44, 0, 2, 4}, {ahead, 0, 3, -1}, {back, 0, 0, 3}, {ahead, 1, 2, 4}, {back, 1, 2, 4}};
+        for (const auto &c : cases) {
+            const orbgpu_lastframe_view last = P.last(c.Tlw, obs_pos);
+            CHECK(queries_last(&FRAME, I44, K_STEREO, 0.5f, &last, 7.f, c.mono, q).status == ORBGPU_OK);
+            CHECK(row_is(q[0], 320.f, 240.f, r, c.lo, c.hi));
+            CHECK(q[0].ur == 300.f && q[0].check_ur == 1 && q[0].blocking == 0 && q[0].gate == 0);  // 320 - 40*0.5
+            CHECK(!q[1].active && q[1].blocking == 1);                                              // mvbOutlier
+        }
+    }
+    {  // queries_keyframe: [lvl-1, lvl+1], no mvuRight gate, every row blocks
+        Points P;
+        P.add(A, 0.5f, 10.f), P.add(A, 0.5f, 10.f, TOWARDS, 1);
+        const std::vector<float> three(2, 3.f);
+        const orbgpu_keyframe_view kf = P.keyframe(three);
+        CHECK(queries_keyframe(&FRAME, I44, K_STEREO, LOG_SF, &kf, 7.f, q).status == ORBGPU_OK);
+        CHECK(row_is(q[0], 320.f, 240.f, 7.f * SF[3], 2, 4) && q[0].check_ur == 0 && q[0].blocking == 1 && q[0].gate == 0);
+        CHECK(!q[1].active && q[1].blocking == 1);  // sAlreadyFound
+    }
+    Points P;
+    P.add(A), P.add(A, 0.5f, 3.f, TOWARDS, 1), P.add(A), P.add(C);
+    const uint8_t found[4] = {0, 0, 1, 0};
+    for (int f = 0; f < N_FLAVOURS; f++) {
+        CHECK(build((Flavour)f, P, q, found).status == ORBGPU_OK);
+        const int blocking = f == SIM3_PROJECTION, gate = f == FUSE;
+        CHECK(row_is(q[0], 320.f, 240.f, 3.f * SF[3], 2, 3) && row_is(q[3], 0.f, 240.f, 3.f * SF[2], 1, 2));
+        CHECK(q[0].ur == (gate ? 300.f : 0.f));  // Fuse: ur = u - bf*invz = 320 - 40*0.5
+        for (int i = 0; i < 4; i++)
+            CHECK(q[i].blocking == blocking && q[i].gate == (gate && q[i].active) && q[i].check_ur == 0);
+        CHECK(!q[1].active && !q[2].active);  // isBad(), spAlreadyFound / the caller's skip list
+    }
+}
+
+static void test_level_out_of_range()
+{
+    std::vector<Query> q;
+    Points P;
+    P.add(A), P.add(A, 0.5f, 8.f);  // row 1: ratio 4 -> level 8 of 8
+    for (int f = 0; f < N_FLAVOURS; f++) {
+        CHECK(is_level_error(build((Flavour)f, P, q), 1, 8));
+    }
+    const std::vector<float> numerator = {3.f, 8.f};
+    P.max_dist.assign(2, 10.f);
+    const orbgpu_keyframe_view kf = P.keyframe(numerator);
+    CHECK(is_level_error(queries_keyframe(&FRAME, I44, K, LOG_SF, &kf, 1.f, q), 1, 8));
+    P.octave[1] = 8;
+    const orbgpu_lastframe_view last = P.last(I44);
+    CHECK(is_level_error(queries_last(&FRAME, I44, K, 0.f, &last, 1.f, 1, q), 1, 8));
+    const uint8_t in_view[2] = {1, 1};
+    const int32_t level[2] = {7, -1};
+    const float f2[2] = {1, 1};
+    const orbgpu_mappoint_view mp{2, in_view, nullptr, nullptr, level, f2, f2, f2, f2, nullptr};
+    CHECK(is_level_error(queries_local(&FRAME, &mp, 1.f, q), 1, -1));
+}
+
+static void test_claim_init()
+{
+    std::vector<int> init;
+    const int32_t k2m[5] = {-1, -2, 0, 1, 2};
+    const uint8_t obs_pos[2] = {1, 0};
+    CHECK(claim_init_observed(k2m, 4, 2, obs_pos, init) == -1);
+    CHECK(init == std::vector<int>({INT_MAX, -1, -1, INT_MAX}));
+    CHECK(claim_init_observed(k2m, 4, 2, nullptr, init) == -1 && init == std::vector<int>({INT_MAX, -1, -1, -1}));
+    CHECK(claim_init_observed(k2m, 5, 2, obs_pos, init) == 4);  // 2 is no row of [0, 2)
+    const int32_t low[2] = {-1, -3};
+    CHECK(claim_init_observed(low, 2, 2, obs_pos, init) == 1);
+    CHECK(claim_init_observed(k2m, 0, 2, obs_pos, init) == -1 && init.size() == 1);  // never an empty upload
+    const int32_t any[4] = {-1, -2, 0, 7};
+    CHECK(claim_init_free(any, 4, init) == -1 && init == std::vector<int>({INT_MAX, -1, -1, -1}));
+    std::vector<uint8_t> found;
+    CHECK(claim_init_free(any, 3, init, 3, &found) == -1 && found == std::vector<uint8_t>({1, 0, 0}));
+    CHECK(init == std::vector<int>({INT_MAX, -1, -1}));
+    CHECK(claim_init_free(any, 4, init, 3, &found) == 3);
+}
+
+static void test_sim3_to_rt()
+{
+    const float c = 0.8f, s = 0.6f;  // a rotation about z by atan2(0.6, 0.8), then about x by the same angle
+    const float R[9] = {c, -s, 0, c * s, c * c, -s, s * s, s * c, c};
+    const float scales[4] = {0.5f, 1.f, 3.7f, 1.3f};
+    for (int k = 0; k < 4; k++) {
+        float Scw[16] = {0};
+        const float t[3] = {1.f, -2.f, 3.5f};
+        for (int r = 0; r < 3; r++) {
+            for (int col = 0; col < 3; col++)
+                Scw[4 * r + col] = scales[k] * (k == 3 ? R[3 * r + col] : I33[3 * r + col]);
+            Scw[4 * r + 3] = scales[k] * t[r];
+        }
+        Scw[15] = 1.f;
+        float T[16], Ow[3], T34[12], Ow_ref[3];
+        CHECK(sim3_to_rt(Scw, T, Ow));
+        ora_sim3_decompose(Scw, T34, Ow_ref);
+        CHECK(memcmp(T, T34, sizeof(T34)) == 0 && memcmp(Ow, Ow_ref, sizeof(Ow)) == 0);
+        CHECK(T[12] == 0 && T[13] == 0 && T[14] == 0 && T[15] == 0);
+        if (k < 2)  // powers of two: every step is exact
+            CHECK(T[3] == 1.f && T[7] == -2.f && T[11] == 3.5f && Ow[0] == -1.f && Ow[1] == 2.f && Ow[2] == -3.5f &&
+                  T[0] == 1.f && T[5] == 1.f && T[10] == 1.f && T[1] == 0.f);
+    }
+    float zero[16] = {0}, T[16], Ow[3];
+    zero[3] = 1.f;
+    CHECK(!sim3_to_rt(zero, T, Ow));  // scw == 0
+}
+
+static void test_rotation_check_on_the_host()
+{
+    int histo[ORBGPU_HISTO_LENGTH] = {0}, i1, i2, i3;
+    histo[0] = 100, histo[2] = 50, histo[3] = 9;  // [10, 0, 5, 0.9, ...] x 10: 50 >= 10, 9 < 10
+    three_maxima(histo, ORBGPU_HISTO_LENGTH, i1, i2, i3);
+    CHECK(i1 == 0 && i2 == 2 && i3 == -1);
+    histo[3] = 10;  // 10 < 0.1f*100 is false: the third maximum stays
+    three_maxima(histo, ORBGPU_HISTO_LENGTH, i1, i2, i3);
+    CHECK(i1 == 0 && i2 == 2 && i3 == 3);
+    histo[2] = 9, histo[3] = 9;  // the second is cut, and the third with it
+    three_maxima(histo, ORBGPU_HISTO_LENGTH, i1, i2, i3);
+    CHECK(i1 == 0 && i2 == -1 && i3 == -1);
+    int tie[ORBGPU_HISTO_LENGTH] = {0};
+    tie[4] = tie[7] = tie[9] = tie[11] = 6;  // `>` keeps the first index of equal bins, in order
+    three_maxima(tie, ORBGPU_HISTO_LENGTH, i1, i2, i3);
+    CHECK(i1 == 4 && i2 == 7 && i3 == 9);
+    int none[ORBGPU_HISTO_LENGTH] = {0};
+    three_maxima(none, ORBGPU_HISTO_LENGTH, i1, i2, i3);
+    CHECK(i1 == -1 && i2 == -1 && i3 == -1);
+    // factor = 1/HISTO_LENGTH (:238-243), so bins are 30 degrees wide and angles of [0, 360) end in bins 0..12
+    CHECK(rot_bin(10.f, 20.f) == 12);   // -10 + 360 = 350 -> round(11.67)
+    CHECK(rot_bin(359.9f, 0.f) == 12);  // round(11.997)
+    CHECK(rot_bin(20.f, 10.f) == 0 && rot_bin(100.f, 10.f) == 3);
+    CHECK(rot_bin(900.f, 0.f) == 0);    // round(30.0) = HISTO_LENGTH wraps to bin 0
+}
+
+static void test_initialization_rows()
+{
+    const int32_t octave[3] = {0, 1, 0};
+    std::vector<uint8_t> desc(3 * 32);
+    for (size_t i = 0; i < desc.size(); i++)
+        desc[i] = (uint8_t)i;
+    orbgpu_frame_view f1 = FRAME;
+    f1.n = 3, f1.kp_octave = octave, f1.desc = desc.data();
+    const float prev[6] = {1, 2, 3, 4, 5, 6};
+    std::vector<int> row_of;
+    std::vector<Query> q;
+    std::vector<uint8_t> rdesc;
+    queries_initialization(&f1, prev, 100, row_of, q, rdesc);
+    CHECK(row_of == std::vector<int>({0, 2}) && q.size() == 2 && rdesc.size() == 64);
+    CHECK(row_is(q[0], 1.f, 2.f, 100.f, 0, 0) && row_is(q[1], 5.f, 6.f, 100.f, 0, 0) && q[1].blocking == 0);
+    CHECK(rdesc[0] == 0 && rdesc[32] == 64 && rdesc[63] == 95);
+}
+
+int main()
+{
+    SF[0] = 1.f;
+    for (int l = 1; l < 8; l++)
+        SF[l] = SF[l - 1] * 1.2f;  // ORBextractor.cc:421
+    LOG_SF = logf(1.2f);
+    FRAME = orbgpu_frame_view{};
+    FRAME.min_x = 0, FRAME.max_x = 640, FRAME.min_y = 0, FRAME.max_y = 480;
+    FRAME.scale_factors = SF, FRAME.nlevels = 8;
+    test_bounds_and_behind();
+    test_distance_range_and_normal();
+    test_levels_and_flags();
+    test_level_out_of_range();
+    test_claim_init();
+    test_sim3_to_rt();
+    test_rotation_check_on_the_host();
+    test_initialization_rows();
+    if (failures == 0)
+        printf("proj_boundary_test ok\n");
+    return failures != 0;
+}

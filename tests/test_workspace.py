@@ -1,4 +1,5 @@
-"""(thread, device) lookup of the stateless matchers' workspaces: compiled with plain g++ and run on the CPU."""
+"""Host-only headers of the library ((thread, device) workspace lookup, id hash, the projection matchers' host boundary):
+compiled with plain g++ and run on the CPU."""
 import os
 import subprocess
 
@@ -43,3 +44,27 @@ def test_id_hash_and_pointer_index(tmp_path):
                    check=True)
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0 and "id_hash ok" in r.stdout and "ptr_index ok" in r.stdout, r.stdout
+
+
+def test_projection_boundary_on_the_host(tmp_path):
+    """The host half of the projection matchers (proj_boundary.h: projections, gates, levels and flags per flavour, claim
+    tables, the Sim3 decomposition against the oracle's, bit for bit) and the rotation check's host build, on hand-derived
+    values under AddressSanitizer + UBSan."""
+    san = ["-O1", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined"]
+    inc = ["-I" + os.path.join(ROOT, d) for d in (os.path.join("orb_slam2_map_amd", "csrc"), "include", "oracle")]
+    obj, exe = str(tmp_path / "orb_oracle_match.o"), str(tmp_path / "proj_boundary_test")
+    subprocess.run(["gcc", "-std=c11", "-Wno-unused-parameter"] + san + inc +
+                   ["-c", os.path.join(ROOT, "oracle", "orb_oracle_match.c"), "-o", obj], check=True)
+    subprocess.run(["g++", "-std=c++17"] + san + inc + [os.path.join(ROOT, "tests", "proj_boundary_test.cpp"), obj, "-o", exe],
+                   check=True)
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0 and "proj_boundary_test ok" in r.stdout, r.stdout
+
+
+def test_projection_float_conventions_live_in_the_boundary_header():
+    """Every `volatile` temporary that pins a float convention of the projection matchers' host side is in proj_boundary.h,
+    which stays compilable without HIP."""
+    csrc = os.path.join(ROOT, "orb_slam2_map_amd", "csrc")
+    assert "volatile" not in open(os.path.join(csrc, "matcher_proj.hip")).read()
+    boundary = open(os.path.join(csrc, "proj_boundary.h")).read()
+    assert "volatile" in boundary and "#include <hip" not in boundary and '#include "common.h"' not in boundary
