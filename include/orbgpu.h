@@ -984,6 +984,60 @@ int orbgpu_statistical_outlier_removal(const orbgpu_point_xyzrgba *in, int64_t n
                                        int32_t device_id);
 
 /* ======================================================================================
+ * KeyFrameDatabase  (reference include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:33-309)
+ * ======================================================================================
+ * The BoW candidate search that starts relocalisation (Tracking::Relocalization, Tracking.cc:1652) and loop detection
+ * (LoopClosing::DetectLoop, LoopClosing.cc:125-142), device-resident and keyed by KeyFrame::mnId.  A key frame is a row
+ * with its BoW vector (ascending word ids, double values) and up to 10 neighbour ids (GetBestCovisibilityKeyFrames(10),
+ * stored as ids and resolved when a query runs); a query streams all vectors once instead of walking the reference's
+ * per-word lists.  Conventions K1-K9: candidates come back in the reference's order, scores are
+ * L1Scoring::score's bits.  "vs CPU restatement; DBoW2 boundary unpinned": tests/kfdb_model.py is the restatement.
+ *   add             KeyFrameDatabase::add (:40-46; LoopClosing.cc:117 / 147 / 216)
+ *   erase           KeyFrameDatabase::erase (:48-67; KeyFrame.cc:582); forgets the key frame's neighbour list
+ *   clear           KeyFrameDatabase::clear (:69-73; Tracking.cc:1828); forgets the neighbour lists as well
+ *   set_covisibles  hook at the end of KeyFrame::UpdateBestCovisibles; accepts an id that is not in the database (yet):
+ *                   the list is kept for when it is added
+ *   score           mpORBVocabulary->score(CurrentBowVec, pKF->mBowVec) of LoopClosing.cc:128-139 (NaN for unknown ids)
+ *   detect_loop     DetectLoopCandidates (:76-197); connected_ids = pKF->GetConnectedKeyFrames()
+ *   detect_reloc    DetectRelocalizationCandidates (:199-309).  The only state a query leaves behind: the score of every
+ *                   row it scored (KeyFrame::mRelocScore), which a later reloc query adds for a neighbour it does not
+ *                   score itself (:273-276); 0.0f before the first write (uninitialised in the reference).
+ * All arrays are HOST arrays.  Refused with ORBGPU_EINVAL, nothing changed and no device needed: an id that is present,
+ * word ids not strictly ascending or outside [0, n_words), values that are not finite, more than 10 neighbours or a
+ * negative neighbour id, a min_score that is not finite, a scoring type other than 0 (L1_NORM, the ORB vocabulary's).  Erasing an unknown id is ignored and not counted in *known.
+ * *n_candidates is always the full count: if `capacity` is smaller the call writes `capacity` ids and still returns
+ * ORBGPU_OK.  The device is bound by the first call that computes or stores; without one those calls return ORBGPU_EHIP
+ * (no CPU fallback).  A database is used by ONE host thread at a time (KeyFrameDatabaseT serialises); every call returns
+ * synchronised.  Limits: 2^24 rows between two clears (an erased row is dead, rows and pool space come back on clear),
+ * 2^24 entries per vector, 2^30 entries in all. */
+typedef struct orbgpu_keyframe_db orbgpu_keyframe_db;
+int orbgpu_keyframe_db_create(int32_t n_words, int32_t scoring, int32_t device_id, int32_t initial_rows,
+                              orbgpu_keyframe_db **out);
+int orbgpu_keyframe_db_destroy(orbgpu_keyframe_db *db);
+int orbgpu_keyframe_db_clear(orbgpu_keyframe_db *db);
+/* Key frames in the database (added and not erased). */
+int orbgpu_keyframe_db_size(const orbgpu_keyframe_db *db, int32_t *alive);
+int orbgpu_keyframe_db_add(orbgpu_keyframe_db *db, int64_t id, int32_t n_bow, const int32_t *bow_ids, const double *bow_vals);
+int orbgpu_keyframe_db_erase(orbgpu_keyframe_db *db, int32_t n, const int64_t *ids, int32_t *known);
+int orbgpu_keyframe_db_set_covisibles(orbgpu_keyframe_db *db, int64_t id, int32_t n, const int64_t *neighbour_ids);
+int orbgpu_keyframe_db_score(orbgpu_keyframe_db *db, int32_t n_bow, const int32_t *bow_ids, const double *bow_vals, int32_t n,
+                             const int64_t *ids, float *scores);
+int orbgpu_keyframe_db_detect_loop(orbgpu_keyframe_db *db, int32_t n_bow, const int32_t *bow_ids, const double *bow_vals,
+                                   int32_t n_connected, const int64_t *connected_ids, float min_score, int32_t capacity,
+                                   int64_t *candidate_ids, int32_t *n_candidates);
+int orbgpu_keyframe_db_detect_reloc(orbgpu_keyframe_db *db, int32_t n_bow, const int32_t *bow_ids, const double *bow_vals,
+                                    int32_t capacity, int64_t *candidate_ids, int32_t *n_candidates);
+/* Tests, debugging: lKFsSharingWords of the most recent detect call, in the reference's order (K1), until the next clear.
+ * words = mnLoopWords / mnRelocWords, first_word = the query word at which the row was met, score = NaN for a row that was
+ * not scored, acc = NaN and best_id = -1 for a row that did not enter the accumulation.  Any output may be NULL; *n is the
+ * full count, at most `capacity` records are written. */
+int orbgpu_keyframe_db_last_query(orbgpu_keyframe_db *db, int32_t capacity, int64_t *ids, int32_t *words, int32_t *first_word,
+                                  float *score, float *acc, int64_t *best_id, int32_t *n);
+/* Tests: how many score launches of this handle read the query from global memory (a query longer than the LDS staging, or
+ * ORBGPU_DEBUG_KFDB_LDS_WORDS=<k> in the environment: a query of more than k words takes that path). */
+int orbgpu_keyframe_db_debug_global_queries(const orbgpu_keyframe_db *db, int64_t *n);
+
+/* ======================================================================================
  * On-disk formats of the end-of-run artefacts: host serialisers, byte for byte.
  * ====================================================================================== */
 /* Map::_WriteMapPoint (Map.cc:123-130): id (u64) + world position (3 x f32) = 20 bytes. */

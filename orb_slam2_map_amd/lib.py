@@ -167,6 +167,10 @@ ABI_SYMBOLS = [
     "orbgpu_pose_optimization_table", "orbgpu_pose_last_spills",
     "orbgpu_sim3_ransac_iterations", "orbgpu_sim3_solve_device", "orbgpu_sim3_solve_batch_device", "orbgpu_sim3_solve",
     "orbgpu_sim3_solve_all",
+    "orbgpu_keyframe_db_create", "orbgpu_keyframe_db_destroy", "orbgpu_keyframe_db_clear", "orbgpu_keyframe_db_size",
+    "orbgpu_keyframe_db_add", "orbgpu_keyframe_db_erase", "orbgpu_keyframe_db_set_covisibles", "orbgpu_keyframe_db_score",
+    "orbgpu_keyframe_db_detect_loop", "orbgpu_keyframe_db_detect_reloc", "orbgpu_keyframe_db_last_query",
+    "orbgpu_keyframe_db_debug_global_queries",
     "orbgpu_vocabulary_create", "orbgpu_vocabulary_destroy", "orbgpu_vocabulary_size", "orbgpu_bow_transform",
     "orbgpu_bow_transform_batch_device", "orbgpu_search_by_bow", "orbgpu_search_by_bow_batch_device",
     "orbgpu_search_by_bow_keyframes", "orbgpu_search_for_triangulation", "orbgpu_search_for_initialization", "orbgpu_fuse", "orbgpu_fuse_sim3",
@@ -262,6 +266,18 @@ def lib():
         "orbgpu_voxel_filter": [vp, C.c_int64, C.c_double, vp, C.c_int64, vp, vp, i32],
         "orbgpu_cloud_remove_outliers": [vp, i32, C.c_double, vp],
         "orbgpu_statistical_outlier_removal": [vp, C.c_int64, i32, C.c_double, vp, C.c_int64, vp, vp, i32],
+        "orbgpu_keyframe_db_create": [i32, i32, i32, i32, vp],
+        "orbgpu_keyframe_db_destroy": [vp],
+        "orbgpu_keyframe_db_clear": [vp],
+        "orbgpu_keyframe_db_size": [vp, vp],
+        "orbgpu_keyframe_db_add": [vp, C.c_int64, i32, vp, vp],
+        "orbgpu_keyframe_db_erase": [vp, i32, vp, vp],
+        "orbgpu_keyframe_db_set_covisibles": [vp, C.c_int64, i32, vp],
+        "orbgpu_keyframe_db_score": [vp, i32, vp, vp, i32, vp, vp],
+        "orbgpu_keyframe_db_detect_loop": [vp, i32, vp, vp, i32, vp, f32, i32, vp, vp],
+        "orbgpu_keyframe_db_detect_reloc": [vp, i32, vp, vp, i32, vp, vp],
+        "orbgpu_keyframe_db_last_query": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
+        "orbgpu_keyframe_db_debug_global_queries": [vp, vp],
     }
     for name, args in sigs.items():
         fn = getattr(L, name, None)
@@ -1418,6 +1434,104 @@ class ORBVocabulary:
     def transform_batch_device(self, d_desc, batch, cap, d_n, levelsup, d_word, d_weight, d_node, stream=0):
         check(self.L_.orbgpu_bow_transform_batch_device(self.h, d_desc, batch, cap, d_n, levelsup, d_word, d_weight,
                                                         d_node, stream))
+
+
+class KeyFrameDatabase:
+    """Device-resident KeyFrameDatabase keyed by KeyFrame::mnId (orbgpu_keyframe_db_*): BoW candidate search for loop
+    detection and relocalisation.  BoW vectors are (ascending int32 word ids, float64 values) as ORBVocabulary.transform
+    returns them.  The device is bound by the first call that needs it."""
+
+    def __init__(self, n_words, scoring=L1_NORM, initial_rows=0, device_id=0):
+        self.L = lib()
+        self.h = C.c_void_p()
+        check(self.L.orbgpu_keyframe_db_create(int(n_words), int(scoring), device_id, int(initial_rows), C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.orbgpu_keyframe_db_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _vec(ids, vals):
+        ids = np.ascontiguousarray(ids, np.int32)
+        vals = np.ascontiguousarray(vals, np.float64)
+        if ids.ndim != 1 or ids.shape != vals.shape:
+            raise ValueError("a BoW vector is two 1-d arrays of one length")
+        return ids, vals
+
+    def clear(self):
+        check(self.L.orbgpu_keyframe_db_clear(self.h))
+
+    def size(self):
+        v = C.c_int32()
+        check(self.L.orbgpu_keyframe_db_size(self.h, C.byref(v)))
+        return v.value
+
+    def add(self, kf_id, bow_ids, bow_vals):
+        ids, vals = self._vec(bow_ids, bow_vals)
+        check(self.L.orbgpu_keyframe_db_add(self.h, int(kf_id), len(ids), _p(ids), _p(vals)))
+
+    def erase(self, kf_ids):
+        """returns how many of the ids were in the database"""
+        kf_ids = np.ascontiguousarray(np.atleast_1d(kf_ids), np.int64)
+        k = C.c_int32()
+        check(self.L.orbgpu_keyframe_db_erase(self.h, len(kf_ids), _p(kf_ids), C.byref(k)))
+        return k.value
+
+    def set_covisibles(self, kf_id, neighbour_ids):
+        nb = np.ascontiguousarray(neighbour_ids, np.int64).reshape(-1)
+        check(self.L.orbgpu_keyframe_db_set_covisibles(self.h, int(kf_id), len(nb), _p(nb)))
+
+    def score(self, bow_ids, bow_vals, kf_ids):
+        ids, vals = self._vec(bow_ids, bow_vals)
+        kf_ids = np.ascontiguousarray(kf_ids, np.int64).reshape(-1)
+        out = np.zeros(len(kf_ids), np.float32)
+        check(self.L.orbgpu_keyframe_db_score(self.h, len(ids), _p(ids), _p(vals), len(kf_ids), _p(kf_ids), _p(out)))
+        return out
+
+    def DetectLoopCandidates(self, bow_ids, bow_vals, connected_ids, min_score, capacity=None):
+        """candidate ids in the reference's order; with a capacity: (ids written, full count)"""
+        ids, vals = self._vec(bow_ids, bow_vals)
+        conn = np.ascontiguousarray(connected_ids, np.int64).reshape(-1)
+        cap = max(self.size(), 1) if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 1), np.int64)
+        n = C.c_int32()
+        check(self.L.orbgpu_keyframe_db_detect_loop(self.h, len(ids), _p(ids), _p(vals), len(conn), _p(conn), float(min_score),
+                                                    cap, _p(out), C.byref(n)))
+        got = out[:min(n.value, cap)].copy()
+        return got if capacity is None else (got, n.value)
+
+    def DetectRelocalizationCandidates(self, bow_ids, bow_vals, capacity=None):
+        ids, vals = self._vec(bow_ids, bow_vals)
+        cap = max(self.size(), 1) if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 1), np.int64)
+        n = C.c_int32()
+        check(self.L.orbgpu_keyframe_db_detect_reloc(self.h, len(ids), _p(ids), _p(vals), cap, _p(out), C.byref(n)))
+        got = out[:min(n.value, cap)].copy()
+        return got if capacity is None else (got, n.value)
+
+    def debug_global_queries(self):
+        """score launches of this handle that read the query from global memory, not from LDS"""
+        n = C.c_int64()
+        check(self.L.orbgpu_keyframe_db_debug_global_queries(self.h, C.byref(n)))
+        return n.value
+
+    def last_query(self):
+        """the sharing list of the most recent detect call (K1 order): dict of id, words, first_word, score, acc, best_id"""
+        n = C.c_int32()
+        check(self.L.orbgpu_keyframe_db_last_query(self.h, 0, None, None, None, None, None, None, C.byref(n)))
+        m = max(n.value, 1)
+        cols = dict(id=np.zeros(m, np.int64), words=np.zeros(m, np.int32), first_word=np.zeros(m, np.int32),
+                    score=np.zeros(m, np.float32), acc=np.zeros(m, np.float32), best_id=np.zeros(m, np.int64))
+        check(self.L.orbgpu_keyframe_db_last_query(self.h, n.value, _p(cols["id"]), _p(cols["words"]), _p(cols["first_word"]),
+                                                   _p(cols["score"]), _p(cols["acc"]), _p(cols["best_id"]), C.byref(n)))
+        return {k: v[:n.value] for k, v in cols.items()}
 
 
 def search_by_bow(desc_kf, angle_kf, valid_kf, node_kf, desc_f, angle_f, node_f, th_low=TH_LOW, nnratio=0.7,

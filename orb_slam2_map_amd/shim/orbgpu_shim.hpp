@@ -17,6 +17,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -1225,6 +1226,164 @@ template <typename KeyFrameT, typename MapPointT> class Sim3SolverT {
     std::vector<int32_t> o1_, o2_, triples_, counts_;
     std::vector<float> x1_, x2_, R_, t_, s_, T12_;
     std::vector<uint64_t> masks_;
+};
+
+// --------------------------------------------------------------------------------------------
+// KeyFrameDatabase (reference include/KeyFrameDatabase.h:45-75, src/KeyFrameDatabase.cc) on the device
+// (orbgpu_keyframe_db_*): add / erase / clear / DetectLoopCandidates / DetectRelocalizationCandidates with the
+// reference's signatures, candidates in the reference's order.  KeyFrameT needs mnId, mBowVec (DBoW2::BowVector: an
+// ordered map word id -> value), GetConnectedKeyFrames() (std::set<KeyFrameT *>) and GetBestCovisibilityKeyFrames(int);
+// the frame passed to DetectRelocalizationCandidates needs mBowVec.  Neighbours are stored as ids: call
+// UpdateCovisibles(pKF, ordered) where KeyFrame::UpdateBestCovisibles ends (INTEGRATION.md lists the hook sites).
+// Lock order: a key frame's mMutexConnections may be held when this class's mutex is taken, never the other way round --
+// no member calls into a key frame while it holds the class's mutex.  The class has its own mutex, like
+// KeyFrameDatabase::mMutex, and keeps id -> KeyFrameT * so that the returned vectors hold the caller's pointers.
+// --------------------------------------------------------------------------------------------
+// id -> the caller's object (host only): what turns the ids a query returns back into KeyFrame pointers
+template <typename T> class IdPtrMap {
+  public:
+    void put(int64_t id, T *p) { m_[id] = p; }
+    void erase(int64_t id) { m_.erase(id); }
+    void clear() { m_.clear(); }
+    size_t size() const { return m_.size(); }
+    // the pointers of ids[0..n) in order; an id the map does not hold is skipped
+    std::vector<T *> Resolve(const int64_t *ids, size_t n) const
+    {
+        std::vector<T *> out;
+        out.reserve(n);
+        for (size_t i = 0; i < n; i++) {
+            const auto it = m_.find(ids[i]);
+            if (it != m_.end())
+                out.push_back(it->second);
+        }
+        return out;
+    }
+
+  private:
+    std::map<int64_t, T *> m_;
+};
+
+template <typename KeyFrameT> class KeyFrameDatabaseT {
+  public:
+    // n_words = voc.size() (KeyFrameDatabase.cc:36); the ORB vocabulary scores with L1_NORM (0), others are refused
+    explicit KeyFrameDatabaseT(int n_words, int scoring = 0, int device_id = 0, int initial_rows = 0)
+    {
+        check(orbgpu_keyframe_db_create(n_words, scoring, device_id, initial_rows, &h_), "KeyFrameDatabase");
+    }
+    ~KeyFrameDatabaseT() { orbgpu_keyframe_db_destroy(h_); }
+    KeyFrameDatabaseT(const KeyFrameDatabaseT &) = delete;
+    KeyFrameDatabaseT &operator=(const KeyFrameDatabaseT &) = delete;
+    orbgpu_keyframe_db *handle() const { return h_; }
+
+    // DBoW2::BowVector -> the ABI's arrays (ascending word ids by the map's order)
+    template <typename BowVectorT> static void Flatten(const BowVectorT &v, std::vector<int32_t> &ids, std::vector<double> &vals)
+    {
+        ids.clear(), vals.clear();
+        ids.reserve(v.size()), vals.reserve(v.size());
+        for (const auto &kv : v) {
+            ids.push_back((int32_t)kv.first);
+            vals.push_back((double)kv.second);
+        }
+    }
+
+    void add(KeyFrameT *pKF)  // KeyFrameDatabase.cc:40-46
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        Flatten(pKF->mBowVec, ids_, vals_);
+        check(orbgpu_keyframe_db_add(h_, (int64_t)pKF->mnId, (int32_t)ids_.size(), ids_.data(), vals_.data()),
+              "KeyFrameDatabase::add");
+        kfs_.put((int64_t)pKF->mnId, pKF);
+    }
+    void erase(KeyFrameT *pKF)  // :48-67
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        const int64_t id = (int64_t)pKF->mnId;
+        check(orbgpu_keyframe_db_erase(h_, 1, &id, nullptr), "KeyFrameDatabase::erase");
+        kfs_.erase(id);
+    }
+    void clear()  // :69-73
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        check(orbgpu_keyframe_db_clear(h_), "KeyFrameDatabase::clear");
+        kfs_.clear();
+    }
+    int size() const
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        int32_t n = 0;
+        check(orbgpu_keyframe_db_size(h_, &n), "KeyFrameDatabase::size");
+        return n;
+    }
+    // hook: the end of KeyFrame::UpdateBestCovisibles (and of UpdateConnections, which fills the same vectors), INSIDE the
+    // function, where mMutexConnections is held: it takes the list just built (mvpOrderedConnectedKeyFrames, of which the
+    // first ten are GetBestCovisibilityKeyFrames(10)) and does not call back into the key frame.
+    void UpdateCovisibles(KeyFrameT *pKF, const std::vector<KeyFrameT *> &ordered)
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        nb_.clear();
+        for (size_t i = 0; i < ordered.size() && i < 10; i++)
+            nb_.push_back((int64_t)ordered[i]->mnId);
+        check(orbgpu_keyframe_db_set_covisibles(h_, (int64_t)pKF->mnId, (int32_t)nb_.size(), nb_.data()),
+              "KeyFrameDatabase::UpdateCovisibles");
+    }
+    // the same from a place where mMutexConnections is NOT held (GetBestCovisibilityKeyFrames takes it, and it is not
+    // recursive): after UpdateBestCovisibles / UpdateConnections has returned
+    void UpdateCovisibles(KeyFrameT *pKF) { UpdateCovisibles(pKF, pKF->GetBestCovisibilityKeyFrames(10)); }
+    // LoopClosing.cc:128-139: mpORBVocabulary->score(CurrentBowVec, pKF->mBowVec) of every key frame in one call (NaN for
+    // one that is not in the database); minScore is the smallest of the non-bad ones
+    std::vector<float> Score(KeyFrameT *pKF, const std::vector<KeyFrameT *> &others)
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        Flatten(pKF->mBowVec, ids_, vals_);
+        nb_.clear();
+        for (KeyFrameT *p : others)
+            nb_.push_back((int64_t)p->mnId);
+        std::vector<float> out(others.size());
+        check(orbgpu_keyframe_db_score(h_, (int32_t)ids_.size(), ids_.data(), vals_.data(), (int32_t)nb_.size(), nb_.data(),
+                                       out.data()),
+              "KeyFrameDatabase::Score");
+        return out;
+    }
+    std::vector<KeyFrameT *> DetectLoopCandidates(KeyFrameT *pKF, float minScore)  // :76-197
+    {
+        const std::set<KeyFrameT *> connected = pKF->GetConnectedKeyFrames();
+        std::lock_guard<std::mutex> g(mu_);
+        Flatten(pKF->mBowVec, ids_, vals_);
+        nb_.clear();
+        for (KeyFrameT *p : connected)
+            nb_.push_back((int64_t)p->mnId);
+        const std::vector<int64_t> conn = nb_;
+        return Candidates([&](int32_t cap, int64_t *out, int32_t *n) {
+            return orbgpu_keyframe_db_detect_loop(h_, (int32_t)ids_.size(), ids_.data(), vals_.data(), (int32_t)conn.size(),
+                                                  conn.data(), minScore, cap, out, n);
+        }, "KeyFrameDatabase::DetectLoopCandidates");
+    }
+    template <typename FrameT> std::vector<KeyFrameT *> DetectRelocalizationCandidates(FrameT *F)  // :199-309
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        Flatten(F->mBowVec, ids_, vals_);
+        return Candidates([&](int32_t cap, int64_t *out, int32_t *n) {
+            return orbgpu_keyframe_db_detect_reloc(h_, (int32_t)ids_.size(), ids_.data(), vals_.data(), cap, out, n);
+        }, "KeyFrameDatabase::DetectRelocalizationCandidates");
+    }
+
+  private:
+    // Candidates never outnumber the key frames of the database, so one call with that capacity returns all of them
+    // (a query changes the reloc score register, so it is not run twice).
+    template <typename Call> std::vector<KeyFrameT *> Candidates(Call call, const char *what)
+    {
+        nb_.assign(std::max<size_t>(kfs_.size(), 1), -1);
+        int32_t n = 0;
+        check(call((int32_t)nb_.size(), nb_.data(), &n), what);
+        return kfs_.Resolve(nb_.data(), (size_t)std::min<int64_t>(n, (int64_t)nb_.size()));
+    }
+
+    orbgpu_keyframe_db *h_ = nullptr;
+    mutable std::mutex mu_;
+    IdPtrMap<KeyFrameT> kfs_;
+    std::vector<int32_t> ids_;
+    std::vector<double> vals_;
+    std::vector<int64_t> nb_;
 };
 
 // --------------------------------------------------------------------------------------------
