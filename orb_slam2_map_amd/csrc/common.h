@@ -105,6 +105,24 @@ int select_device(int device_id);
 // the GPU suite) with two threads inside orbgpu_extractor_destroy at the same moment.  Nothing on a per-frame path takes it.
 std::mutex &lifecycle_mutex();
 
+// The device operations of an id table's growth transaction (id_table.h) on the table's stream: 0, or non-zero after
+// leaving the message; drain() waits and reports nothing.
+struct TableStreamOps {
+    hipStream_t stream;
+    const char *what;
+    int done(hipError_t e) const
+    {
+        if (e != hipSuccess)
+            set_error("%s: %s", what, hipGetErrorString(e));
+        return e != hipSuccess;
+    }
+    int zero(void *p, size_t n) const { return done(hipMemsetAsync(p, 0, n, stream)); }
+    int copy(void *d, const void *s, size_t n) const { return done(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, stream)); }
+    int upload(void *d, const void *s, size_t n) const { return done(hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, stream)); }
+    int sync() const { return done(hipStreamSynchronize(stream)); }
+    void drain() const { (void)hipStreamSynchronize(stream); }
+};
+
 // ---- device helpers -------------------------------------------------------------------------
 __device__ __forceinline__ int wave_reduce_add(int v)
 {

@@ -1,5 +1,6 @@
-// id -> row hash of the MapPoint table (map_table.hip), host side.  Pure C++ (tests/id_hash_test.cpp builds it with g++ and
-// the sanitizers); the device kernels probe a byte-identical copy of `keys` / `vals` with the same hash function.
+// id -> row hash of the id-keyed device tables (MapPoint table, key-frame database; id_table.h grows them).  Pure C++
+// (tests/id_hash_test.cpp builds it with g++ and the sanitizers); the device kernels probe a byte-identical copy of
+// `keys` / `vals` with id_hash_lookup, the function IdHash::find runs on the host.
 //
 // Open addressing, linear probing, capacity 2^log2cap with a load factor <= 1/2 (the owner grows it before it fills up),
 // multiplicative hash.  Entries are never removed -- except the ones a refused call has just inserted, which are taken
@@ -7,6 +8,7 @@
 // that an older entry depends on.
 #pragma once
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -25,6 +27,32 @@ ORBGPU_HD inline uint32_t id_hash_slot(int64_t id, int log2cap)
     return (uint32_t)(((uint64_t)id * 0x9E3779B97F4A7C15ull) >> (64 - log2cap));
 }
 
+// row of `id` in a hash of capacity 2^log2cap, -1 if absent (ids are >= 0; log2cap 0: no hash yet)
+ORBGPU_HD inline int id_hash_lookup(const int64_t *__restrict__ hkeys, const int32_t *__restrict__ hvals, int log2cap, int64_t id)
+{
+    if (id < 0 || log2cap <= 0)
+        return -1;
+    const uint32_t mask = (1u << log2cap) - 1u;
+    uint32_t s = id_hash_slot(id, log2cap);
+    for (uint32_t probe = 0; probe <= mask; probe++, s = (s + 1) & mask) {  // (load <= 1/2: an empty slot ends every chain)
+        const int64_t k = hkeys[s];
+        if (k == id)
+            return hvals[s];
+        if (k == ID_HASH_EMPTY)
+            return -1;
+    }
+    return -1;
+}
+
+// hash capacity for `rows` rows: the smallest l2 >= 1 with 2^l2 >= 2 * rows (load factor <= 1/2)
+inline int id_hash_log2cap(int64_t rows)
+{
+    int l2 = 1;
+    while (((int64_t)1 << l2) < 2 * rows)
+        l2++;
+    return l2;
+}
+
 struct IdHash {
     std::vector<int64_t> keys;  // ID_HASH_EMPTY = free slot
     std::vector<int32_t> vals;
@@ -32,30 +60,30 @@ struct IdHash {
 
     size_t capacity() const { return keys.size(); }
 
-    // row of `id`, -1 if absent (ids are >= 0)
-    int find(int64_t id) const
-    {
-        if (log2cap == 0 || id < 0)
-            return -1;
-        const uint32_t mask = (1u << log2cap) - 1u;
-        for (uint32_t s = id_hash_slot(id, log2cap);; s = (s + 1) & mask) {
-            if (keys[s] == id)
-                return vals[s];
-            if (keys[s] == ID_HASH_EMPTY)
-                return -1;
-        }
-    }
-    // inserts an id that is NOT in the table (the caller has looked it up) and returns its slot; the table must have a
-    // free slot (load factor)
-    uint32_t insert(int64_t id, int32_t row)
+    // row of `id`, -1 if absent
+    int find(int64_t id) const { return id_hash_lookup(keys.data(), vals.data(), log2cap, id); }
+    // slot that holds `id`, or the free slot an insertion of it would take; the table must have a free slot (load factor)
+    uint32_t slot_for(int64_t id) const
     {
         const uint32_t mask = (1u << log2cap) - 1u;
         uint32_t s = id_hash_slot(id, log2cap);
-        while (keys[s] != ID_HASH_EMPTY)
+        while (keys[s] != id && keys[s] != ID_HASH_EMPTY)
             s = (s + 1) & mask;
+        return s;
+    }
+    // inserts an id that is NOT in the table (the caller has looked it up) and returns its slot
+    uint32_t insert(int64_t id, int32_t row)
+    {
+        const uint32_t s = slot_for(id);
         keys[s] = id;
         vals[s] = row;
         return s;
+    }
+    // every slot empty, the capacity as it is
+    void clear()
+    {
+        std::fill(keys.begin(), keys.end(), ID_HASH_EMPTY);
+        std::fill(vals.begin(), vals.end(), -1);
     }
     // undoes the n most recent insertions (their slots, in any order)
     void rollback(const int32_t *slots, int n)

@@ -19,7 +19,7 @@
 // entry point.  Every call returns synchronised; the caller serialises (KeyFrameDatabaseT does).  The device is bound at
 // the first call that needs it, so that refusals (K8) are answered without one.
 #include "common.h"
-#include "id_hash.h"
+#include "id_table.h"
 
 #include <algorithm>
 #include <climits>
@@ -59,23 +59,6 @@ struct KfSurvivor {
     int32_t pad;
     int64_t best_id;
 };
-
-__device__ __forceinline__ int kf_lookup(const int64_t *__restrict__ hkeys, const int32_t *__restrict__ hvals, int log2cap,
-                                         int64_t id)
-{
-    if (id < 0 || log2cap <= 0)
-        return -1;
-    const uint32_t mask = (1u << log2cap) - 1u;
-    uint32_t s = id_hash_slot(id, log2cap);
-    for (uint32_t probe = 0; probe <= mask; probe++, s = (s + 1) & mask) {  // (load <= 1/2: an empty slot ends every chain)
-        const int64_t k = hkeys[s];
-        if (k == id)
-            return hvals[s];
-        if (k == ID_HASH_EMPTY)
-            return -1;
-    }
-    return -1;
-}
 
 __global__ __launch_bounds__(256) void k_kfdb_mark(int n, const int32_t *__restrict__ list, int n_rows,
                                                    int32_t *__restrict__ excl, int stamp)
@@ -186,7 +169,7 @@ __global__ __launch_bounds__(256) void k_kfdb_acc(int n_rows, const KfRow *__res
                 b = rows[r].id;
                 const int nn = min(max(rows[r].nn, 0), KF_MAX_NB);
                 for (int k = 0; k < nn; k++) {
-                    const int r2 = kf_lookup(hkeys, hvals, log2cap, rows[r].nb[k]);
+                    const int r2 = id_hash_lookup(hkeys, hvals, log2cap, rows[r].nb[k]);
                     if (r2 < 0 || r2 >= n_rows || !rows[r2].alive || words[r2] <= 0)
                         continue;  // not in the database (K7) or not in the sharing list
                     float s2;
@@ -246,6 +229,8 @@ __global__ __launch_bounds__(KF_SELECT_BLOCK) void k_kfdb_select(int n_rows, KfR
     }
 }
 
+constexpr int KF_ROW_COLS = 9;  // the per-row arrays of orbgpu_keyframe_db
+
 } // namespace orbgpu
 
 using namespace orbgpu;
@@ -256,8 +241,14 @@ struct orbgpu_keyframe_db {
     hipStream_t stream = nullptr;
     int rows = 0, row_cap = 0, alive = 0;
     int64_t pool_used = 0, pool_cap = 0, next_seq = 0;
-    // per row
+    // per row: named once with their bytes per row (growth carries all of them over: the last query's columns are read
+    // afterwards).  The list points into the handle, which is therefore never copied.
     DevBuf d_rows, d_words, d_first, d_score, d_acc, d_best, d_flag, d_excl, d_surv;
+    const IdColumn<DevBuf> row_cols[KF_ROW_COLS] = {{&d_rows, sizeof(KfRow)}, {&d_words, 4}, {&d_first, 4},
+                                                    {&d_score, 4},            {&d_acc, 4},   {&d_best, 8},
+                                                    {&d_flag, 1},             {&d_excl, 4},  {&d_surv, sizeof(KfSurvivor)}};
+    orbgpu_keyframe_db() = default;
+    orbgpu_keyframe_db(const orbgpu_keyframe_db &) = delete;
     DevBuf d_pool_ids, d_pool_vals, d_hkeys, d_hvals, d_stage, d_ctr;
     IdHash hash;  // id -> most recent row of the id (dead or alive); the device holds a byte-identical copy
     std::vector<KfRow> h_rows;
@@ -297,29 +288,8 @@ static int alive_row(const orbgpu_keyframe_db *db, int64_t id)
     return r >= 0 && db->h_rows[(size_t)r].alive ? r : -1;
 }
 
-// slot that holds `id`, or the free slot an insertion of it would take
-static uint32_t hash_slot_for(const IdHash &h, int64_t id)
-{
-    const uint32_t mask = (1u << h.log2cap) - 1u;
-    uint32_t s = id_hash_slot(id, h.log2cap);
-    while (h.keys[s] != id && h.keys[s] != ID_HASH_EMPTY)
-        s = (s + 1) & mask;
-    return s;
-}
-
-struct RowBuf {
-    DevBuf orbgpu_keyframe_db::*buf;
-    size_t elt;
-};
-static const RowBuf ROW_BUFS[] = {{&orbgpu_keyframe_db::d_rows, sizeof(KfRow)}, {&orbgpu_keyframe_db::d_words, 4},
-                                  {&orbgpu_keyframe_db::d_first, 4},            {&orbgpu_keyframe_db::d_score, 4},
-                                  {&orbgpu_keyframe_db::d_acc, 4},              {&orbgpu_keyframe_db::d_best, 8},
-                                  {&orbgpu_keyframe_db::d_flag, 1},             {&orbgpu_keyframe_db::d_excl, 4},
-                                  {&orbgpu_keyframe_db::d_surv, sizeof(KfSurvivor)}};
-constexpr int N_ROW_BUFS = sizeof(ROW_BUFS) / sizeof(ROW_BUFS[0]);
-
-// Row capacity `want`: every per-row array and the hash (capacity >= 2 * rows) are re-allocated, contents carried over.
-// Either everything has grown or nothing has.
+// Row capacity `want`: every per-row array and the hash are re-allocated, contents carried over -- the transaction of
+// id_table.h: either everything has grown or nothing has.
 static int grow_rows(orbgpu_keyframe_db *db, int want)
 {
     if (want <= db->row_cap)
@@ -328,58 +298,9 @@ static int grow_rows(orbgpu_keyframe_db *db, int want)
     int ncap = std::max(db->row_cap, 1);
     while (ncap < want)
         ncap *= 2;
-    int l2 = 1;
-    while (((size_t)1 << l2) < 2 * (size_t)ncap)
-        l2++;
-    DevBuf nb[N_ROW_BUFS + 2];
-    int rc = ORBGPU_OK;
-    for (int i = 0; i < N_ROW_BUFS && rc == ORBGPU_OK; i++)
-        rc = nb[i].reserve(ROW_BUFS[i].elt * (size_t)ncap);
-    if (rc == ORBGPU_OK)
-        rc = nb[N_ROW_BUFS].reserve(sizeof(int64_t) << l2);
-    if (rc == ORBGPU_OK)
-        rc = nb[N_ROW_BUFS + 1].reserve(sizeof(int32_t) << l2);
-    IdHash nh;
-    if (rc == ORBGPU_OK) {
-        nh = db->hash;
-        nh.rebuild(l2);
-    }
-    hipError_t he = hipSuccess;
-    for (int i = 0; i < N_ROW_BUFS && rc == ORBGPU_OK && he == hipSuccess; i++) {
-        he = hipMemsetAsync(nb[i].p, 0, ROW_BUFS[i].elt * (size_t)ncap, db->stream);
-        if (he == hipSuccess && db->rows > 0)
-            he = hipMemcpyAsync(nb[i].p, (db->*ROW_BUFS[i].buf).p, ROW_BUFS[i].elt * (size_t)db->rows, hipMemcpyDeviceToDevice,
-                                db->stream);
-    }
-    if (rc == ORBGPU_OK && he == hipSuccess)
-        he = hipMemcpyAsync(nb[N_ROW_BUFS].p, nh.keys.data(), sizeof(int64_t) << l2, hipMemcpyHostToDevice, db->stream);
-    if (rc == ORBGPU_OK && he == hipSuccess)
-        he = hipMemcpyAsync(nb[N_ROW_BUFS + 1].p, nh.vals.data(), sizeof(int32_t) << l2, hipMemcpyHostToDevice, db->stream);
-    if (rc == ORBGPU_OK && he == hipSuccess)
-        he = hipStreamSynchronize(db->stream);
-    if (rc == ORBGPU_OK && he != hipSuccess) {
-        set_error("growing the key-frame database: %s", hipGetErrorString(he));
-        rc = ORBGPU_EHIP;
-    }
-    if (rc != ORBGPU_OK) {
-        (void)hipStreamSynchronize(db->stream);  // nothing enqueued above may still write into what is freed here
-        for (DevBuf &b : nb)
-            b.release();
-        return rc;
-    }
-    for (int i = 0; i < N_ROW_BUFS; i++) {
-        std::swap(db->*ROW_BUFS[i].buf, nb[i]);
-        nb[i].release();
-    }
-    std::swap(db->d_hkeys, nb[N_ROW_BUFS]);
-    std::swap(db->d_hvals, nb[N_ROW_BUFS + 1]);
-    nb[N_ROW_BUFS].release();
-    nb[N_ROW_BUFS + 1].release();
-    db->hash.keys.swap(nh.keys);
-    db->hash.vals.swap(nh.vals);
-    db->hash.log2cap = l2;
-    db->row_cap = ncap;
-    return ORBGPU_OK;
+    TableStreamOps ops{db->stream, "growing the key-frame database"};
+    const IdTableParts<DevBuf> parts{db->row_cols, KF_ROW_COLS, KF_ROW_COLS, &db->d_hkeys, &db->d_hvals, &db->hash, &db->row_cap};
+    return id_table_grow(parts, db->rows, ncap, ops);
 }
 
 static int grow_pool(orbgpu_keyframe_db *db, int64_t want)
@@ -420,22 +341,17 @@ static int grow_pool(orbgpu_keyframe_db *db, int64_t want)
     return ORBGPU_OK;
 }
 
-// Growth after the first call allocates and frees device memory, which creation and destruction of every handle do under
-// the lifecycle lock (common.h); it takes the same lock, on the growing branch only.
+// Growth after the first call: under the lifecycle lock, on the growing branch only (id_table.h).
 static int grow_locked(orbgpu_keyframe_db *db, int rows, int64_t pool)
 {
-    if (rows <= db->row_cap && pool <= db->pool_cap)
-        return ORBGPU_OK;
-    std::lock_guard<std::mutex> lifecycle(lifecycle_mutex());
-    const int rc = grow_rows(db, rows);
-    return rc != ORBGPU_OK ? rc : grow_pool(db, pool);
+    return lifecycle_locked_unless(rows <= db->row_cap && pool <= db->pool_cap, lifecycle_mutex(), [&] {
+        const int rc = grow_rows(db, rows);
+        return rc != ORBGPU_OK ? rc : grow_pool(db, pool);
+    });
 }
 static int reserve_locked(DevBuf &b, size_t bytes)
 {
-    if (bytes <= b.bytes)
-        return ORBGPU_OK;
-    std::lock_guard<std::mutex> lifecycle(lifecycle_mutex());
-    return b.reserve(bytes);
+    return lifecycle_locked_unless(bytes <= b.bytes, lifecycle_mutex(), [&] { return b.reserve(bytes); });
 }
 
 // first call that needs the device: select it, create the stream, allocate for initial_rows
@@ -476,16 +392,6 @@ static int sync_or_fail(orbgpu_keyframe_db *db, hipError_t he, const char *what)
     return ORBGPU_OK;
 }
 
-struct Carve {
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 static void launch_score(orbgpu_keyframe_db *db, int n_items, const int32_t *sel, int nq, const int32_t *q_ids,
                          const double *q_vals, int32_t *words, int32_t *first, float *score, int32_t *max_words)
 {
@@ -524,7 +430,7 @@ static int detect(orbgpu_keyframe_db *db, bool reloc, int32_t nq, const int32_t 
             conn_rows.push_back(r);
     }
     const int nc = (int)conn_rows.size();
-    Carve c;
+    Carver c;
     const size_t o_vals = c.take(8 * (size_t)nq), o_ids = c.take(4 * (size_t)nq), o_conn = c.take(4 * (size_t)std::max(nc, 1));
     if ((rc = reserve_locked(db->d_stage, c.off)) != ORBGPU_OK)
         return rc;
@@ -604,8 +510,8 @@ static int destroy_impl(orbgpu_keyframe_db *db)
             (void)hipStreamSynchronize(db->stream);
             (void)hipStreamDestroy(db->stream);
         }
-        for (int i = 0; i < N_ROW_BUFS; i++)
-            (db->*ROW_BUFS[i].buf).release();
+        for (const IdColumn<DevBuf> &c : db->row_cols)
+            c.buf->release();
         for (DevBuf *b : {&db->d_pool_ids, &db->d_pool_vals, &db->d_hkeys, &db->d_hvals, &db->d_stage, &db->d_ctr})
             b->release();
     }
@@ -653,8 +559,7 @@ int orbgpu_keyframe_db_clear(orbgpu_keyframe_db *db)
         if ((rc = sync_or_fail(db, he, "clearing the key-frame database")) != ORBGPU_OK)
             return rc;
     }
-    std::fill(db->hash.keys.begin(), db->hash.keys.end(), ID_HASH_EMPTY);
-    std::fill(db->hash.vals.begin(), db->hash.vals.end(), -1);
+    db->hash.clear();
     db->h_rows.clear();
     db->h_seq.clear();
     db->covis.clear();
@@ -693,7 +598,7 @@ int orbgpu_keyframe_db_add(orbgpu_keyframe_db *db, int64_t id, int32_t n_bow, co
         std::copy(it->second.begin(), it->second.end(), row.nb);
     }
     const int r = db->rows;
-    const uint32_t slot = hash_slot_for(db->hash, id);
+    const uint32_t slot = db->hash.slot_for(id);
     hipError_t he = hipSuccess;
     if (n_bow > 0) {
         he = hipMemcpyAsync(db->d_pool_ids.as<int32_t>() + db->pool_used, bow_ids, 4 * (size_t)n_bow, hipMemcpyHostToDevice,
@@ -797,7 +702,7 @@ int orbgpu_keyframe_db_score(orbgpu_keyframe_db *db, int32_t n_bow, const int32_
         return rc;
     if (n == 0)
         return ORBGPU_OK;
-    Carve c;
+    Carver c;
     const size_t o_vals = c.take(8 * (size_t)std::max(n_bow, 1)), o_ids = c.take(4 * (size_t)std::max(n_bow, 1)),
                  o_sel = c.take(4 * (size_t)n), in_bytes = c.off, o_words = c.take(4 * (size_t)n), o_first = c.take(4 * (size_t)n),
                  o_score = c.take(4 * (size_t)n);

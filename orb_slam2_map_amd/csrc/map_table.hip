@@ -14,7 +14,7 @@
 // rows when points are inserted, the device copy (patched slot by slot after every insert) serves the per-frame lookups.
 #include "common.h"
 #include "proj_internal.h"
-#include "id_hash.h"
+#include "id_table.h"
 
 #include <algorithm>
 #include <climits>
@@ -24,33 +24,22 @@
 
 namespace orbgpu {
 
-constexpr int64_t MT_EMPTY = ID_HASH_EMPTY;
 constexpr int MT_MAX_CALL = 1 << 26;  // ids per call
 constexpr int MT_MAX_ROWS = 1 << 27;  // rows of a table (82 B each)
-__host__ __device__ __forceinline__ uint32_t mt_hash(int64_t id, int log2cap) { return id_hash_slot(id, log2cap); }
-
-__device__ __forceinline__ int mt_lookup(const int64_t *__restrict__ hkeys, const int32_t *__restrict__ hvals, int log2cap,
-                                         int64_t id)
-{
-    if (id < 0)
-        return -1;
-    const uint32_t mask = (1u << log2cap) - 1u;
-    uint32_t s = mt_hash(id, log2cap);
-    for (uint32_t probe = 0; probe <= mask; probe++, s = (s + 1) & mask) {  // (the table is never full: load <= 1/2)
-        const int64_t k = hkeys[s];
-        if (k == id)
-            return hvals[s];
-        if (k == MT_EMPTY)
-            return -1;
-    }
-    return -1;
-}
 
 struct TableDev {  // device arrays, one row per map point
     float *world_pos, *normal, *min_dist, *max_dist;
     uint8_t *desc, *bad, *obs;
     int64_t *id;
 };
+
+constexpr int MT_CARRIED = 8, MT_COLS = 9;  // TableDev's arrays, and pos_of_row
+// TableDev over columns 0 .. MT_CARRIED-1 of orbgpu_mappoint_table::cols, whose order is TableDev's (p(i): column i's array)
+template <typename At> static TableDev table_dev(At p)
+{
+    return TableDev{(float *)p(0), (float *)p(1), (float *)p(2), (float *)p(3), (uint8_t *)p(4), (uint8_t *)p(5), (uint8_t *)p(6),
+                    (int64_t *)p(7)};
+}
 
 struct UpsertDev {  // staged attribute arrays of one upsert call (nullptr: keep what the row has)
     const int32_t *row;
@@ -157,7 +146,7 @@ __global__ __launch_bounds__(256) void k_table_gather(int m, const int64_t *__re
     if (i >= m)
         return;
     const int64_t id = ids[i];
-    const int r = mt_lookup(hkeys, hvals, log2cap, id);
+    const int r = id_hash_lookup(hkeys, hvals, log2cap, id);
     if (g.has)
         g.has[i] = r >= 0 ? 1 : 0;
     if (r < 0) {
@@ -198,7 +187,7 @@ __global__ __launch_bounds__(256) void k_table_kp(int n, int cap, int m, const i
         return;
     int v = -1;
     if (j < n && kp_ids[j] >= 0) {
-        const int r = mt_lookup(hkeys, hvals, log2cap, kp_ids[j]);
+        const int r = id_hash_lookup(hkeys, hvals, log2cap, kp_ids[j]);
         if (r < 0) {
             atomicAdd(unknown, 1);
             v = -2;
@@ -254,17 +243,6 @@ struct Pinned {  // grow-only pinned staging buffer
     }
 };
 
-// carve sub-arrays out of one staging block (host and device blocks share the layout)
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 } // namespace orbgpu
 
 using namespace orbgpu;
@@ -274,6 +252,13 @@ struct orbgpu_mappoint_table {
     hipStream_t stream = nullptr;
     int rows = 0, cap = 0;
     DevBuf world_pos, normal, min_dist, max_dist, desc, bad, obs, id;
+    DevBuf pos_of_row;  // [cap] list position of every table row in the current call
+    // the columns, named once with their bytes per row (growth, retain and destroy go by this list): TableDev's, in its
+    // order, then the scratch one.  The list points into the handle, which is therefore never copied.
+    const IdColumn<DevBuf> cols[MT_COLS] = {{&world_pos, 12}, {&normal, 12}, {&min_dist, 4}, {&max_dist, 4}, {&desc, 32},
+                                            {&bad, 1},        {&obs, 1},     {&id, 8},       {&pos_of_row, 4}};
+    orbgpu_mappoint_table() = default;
+    orbgpu_mappoint_table(const orbgpu_mappoint_table &) = delete;
     IdHash hash;                 // host copy of the id -> row hash (id_hash.h)
     std::vector<int32_t> stamp;  // per row: last upsert call that touched it (duplicate ids inside one call are refused)
     int call_no = 0;
@@ -281,14 +266,13 @@ struct orbgpu_mappoint_table {
     Pinned stage;       // host staging of a call's inputs / outputs
     DevBuf d_stage;     // its device twin
     DevBuf g_block;     // the call's gathered local map + translation tables + results
-    DevBuf pos_of_row;  // [cap] list position of every table row in the current call
     ProjWorkspace *pws = nullptr;  // the matchers' scratch for calls over this table (they run on `stream`)
     int32_t last_unknown_list = 0, last_unknown_kp = 0;  // ids of the last search call the table had never been told about
     TableDev dev() const
     {
-        return TableDev{world_pos.as<float>(), normal.as<float>(), min_dist.as<float>(), max_dist.as<float>(),
-                        desc.as<uint8_t>(), bad.as<uint8_t>(), obs.as<uint8_t>(), id.as<int64_t>()};
+        return table_dev([this](int i) { return cols[i].buf->p; });
     }
+    IdTableParts<DevBuf> parts() { return {cols, MT_CARRIED, MT_COLS, &d_hkeys, &d_hvals, &hash, &cap}; }
 };
 
 struct orbgpu_frame {
@@ -307,7 +291,8 @@ namespace orbgpu {
 static int host_find(const orbgpu_mappoint_table *t, int64_t id) { return t->hash.find(id); }
 static uint32_t host_insert(orbgpu_mappoint_table *t, int64_t id, int row) { return t->hash.insert(id, row); }
 
-// row capacity `want`, hash capacity >= 2 * want; existing rows are carried over on the device
+// row capacity `want` (the hash follows: id_table.h); existing rows are carried over on the device.  Without the lifecycle
+// lock: orbgpu_mappoint_table_create holds it.
 static int table_grow(orbgpu_mappoint_table *t, int want)
 {
     if (want <= t->cap)
@@ -315,46 +300,11 @@ static int table_grow(orbgpu_mappoint_table *t, int want)
     int ncap = std::max(t->cap * 2, 1024);
     while (ncap < want)
         ncap *= 2;
-    ORBGPU_HIP_TRY(hipStreamSynchronize(t->stream));
-    struct Item {
-        DevBuf *b;
-        size_t elt;
-    } items[] = {{&t->world_pos, 12}, {&t->normal, 12}, {&t->min_dist, 4}, {&t->max_dist, 4},
-                 {&t->desc, 32},      {&t->bad, 1},     {&t->obs, 1},      {&t->id, 8}};
-    for (const Item &it : items) {
-        DevBuf nb;
-        int rc = nb.reserve(it.elt * (size_t)ncap);
-        if (rc != ORBGPU_OK)
-            return rc;
-        hipError_t he = hipMemsetAsync(nb.p, 0, it.elt * (size_t)ncap, t->stream);
-        if (he == hipSuccess && t->rows > 0)
-            he = hipMemcpyAsync(nb.p, it.b->p, it.elt * (size_t)t->rows, hipMemcpyDeviceToDevice, t->stream);
-        if (he == hipSuccess)
-            he = hipStreamSynchronize(t->stream);
-        if (he != hipSuccess) {  // the array being replaced stays as it was; the fresh one must not leak
-            nb.release();
-            set_error("MapPoint table growth to %d rows: %s", ncap, hipGetErrorString(he));
-            return ORBGPU_EHIP;
-        }
-        it.b->release();
-        *it.b = nb;
-    }
-    int rc = t->pos_of_row.reserve(sizeof(int32_t) * (size_t)ncap);
-    if (rc != ORBGPU_OK)
-        return rc;
-    t->stamp.resize((size_t)ncap, 0);
-    t->cap = ncap;
-    // hash: load factor <= 1/2, rebuilt from the rows' ids
-    int l2 = 1;
-    while ((1 << l2) < 2 * ncap)
-        l2++;
-    t->hash.rebuild(l2);
-    if ((rc = t->d_hkeys.reserve(sizeof(int64_t) << l2)) != ORBGPU_OK || (rc = t->d_hvals.reserve(sizeof(int32_t) << l2)) != ORBGPU_OK)
-        return rc;
-    ORBGPU_HIP_TRY(hipMemcpyAsync(t->d_hkeys.p, t->hash.keys.data(), sizeof(int64_t) << l2, hipMemcpyHostToDevice, t->stream));
-    ORBGPU_HIP_TRY(hipMemcpyAsync(t->d_hvals.p, t->hash.vals.data(), sizeof(int32_t) << l2, hipMemcpyHostToDevice, t->stream));
-    ORBGPU_HIP_TRY(hipStreamSynchronize(t->stream));
-    return ORBGPU_OK;
+    TableStreamOps ops{t->stream, "MapPoint table growth"};
+    const int rc = id_table_grow(t->parts(), t->rows, ncap, ops);
+    if (rc == ORBGPU_OK)
+        t->stamp.resize((size_t)ncap, 0);
+    return rc;
 }
 
 static void frame_dev_view(const orbgpu_frame *fr, orbgpu_device_frame_view *v)
@@ -432,9 +382,9 @@ static int mappoint_table_destroy_impl(orbgpu_mappoint_table *t)
         (void)hipStreamSynchronize(t->stream);
         (void)hipStreamDestroy(t->stream);
     }
-    DevBuf *bufs[] = {&t->world_pos, &t->normal, &t->min_dist, &t->max_dist, &t->desc,    &t->bad,    &t->obs,
-                      &t->id,        &t->d_hkeys, &t->d_hvals, &t->d_stage,  &t->g_block, &t->pos_of_row};
-    for (DevBuf *b : bufs)
+    for (const IdColumn<DevBuf> &c : t->cols)
+        c.buf->release();
+    for (DevBuf *b : {&t->d_hkeys, &t->d_hvals, &t->d_stage, &t->g_block})
         b->release();
     t->stage.release();
     proj_workspace_delete(t->pws);
@@ -456,18 +406,17 @@ int orbgpu_mappoint_table_create(int32_t device_id, int32_t initial_rows, orbgpu
     }
     t->device_id = device_id;
     t->pws = proj_workspace_new();
+    hipError_t he = hipSuccess;
     if (!t->pws) {
         set_error("out of host memory");
-        delete t;
-        return ORBGPU_ENOMEM;
-    }
-    hipError_t he = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
-    if (he != hipSuccess) {
+        rc = ORBGPU_ENOMEM;
+    } else if ((he = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking)) != hipSuccess) {
+        t->stream = nullptr;
         set_error("hipStreamCreate: %s", hipGetErrorString(he));
-        delete t;
-        return ORBGPU_EHIP;
-    }
-    if ((rc = table_grow(t, std::max(initial_rows, 1024))) != ORBGPU_OK) {
+        rc = ORBGPU_EHIP;
+    } else
+        rc = table_grow(t, std::max(initial_rows, 1024));
+    if (rc != ORBGPU_OK) {
         mappoint_table_destroy_impl(t);
         return rc;
     }
@@ -505,7 +454,8 @@ int orbgpu_mappoint_table_upsert(orbgpu_mappoint_table *t, int32_t n, const int6
         unknown += host_find(t, ids[i]) < 0;
     }
     ORBGPU_REQUIRE((int64_t)t->rows + unknown <= MT_MAX_ROWS, "the MapPoint table is limited to %d rows", MT_MAX_ROWS);
-    if (unknown && (rc = table_grow(t, t->rows + (int)unknown)) != ORBGPU_OK)  // an update of known points never grows the table
+    const int want = t->rows + (int)unknown;  // an update of known points never grows the table
+    if ((rc = lifecycle_locked_unless(want <= t->cap, lifecycle_mutex(), [&] { return table_grow(t, want); })) != ORBGPU_OK)
         return rc;
     // staging layout
     Carver cv;
@@ -660,75 +610,31 @@ int orbgpu_mappoint_table_retain(orbgpu_mappoint_table *t, int32_t n, const int6
     int ncap = 1024;
     while (ncap < m)
         ncap *= 2;
-    ORBGPU_HIP_TRY(hipStreamSynchronize(t->stream));
-    // new arrays first; the table is only switched over when everything has succeeded
-    DevBuf nb[8], nsrc;
-    const size_t elt[8] = {12, 12, 4, 4, 32, 1, 1, 8};
-    auto drop = [&] {
-        for (DevBuf &b : nb)
-            b.release();
-        nsrc.release();
-    };
-    for (int k = 0; k < 8; k++)
-        if ((rc = nb[k].reserve(elt[k] * (size_t)ncap)) != ORBGPU_OK) {
-            drop();
-            return rc;
+    // the transaction of id_table.h: the kept rows compacted into new arrays, the hash of the kept ids.  d_stage, which
+    // carries the row list, is per-call scratch outside the transaction: every call reserves it again, so a refusal that
+    // leaves it empty changes nothing of the table.
+    TableStreamOps ops{t->stream, "MapPoint table retain"};
+    auto fill = [&](const DevBuf *nb, int l2, IdHash &nh) -> int {
+        int rc = ORBGPU_OK;
+        if (m > 0) {
+            if ((rc = t->d_stage.reserve(sizeof(int32_t) * (size_t)m)) != ORBGPU_OK)
+                return rc;
+            if (ops.upload(t->d_stage.p, src.data(), sizeof(int32_t) * (size_t)m))
+                return ORBGPU_EHIP;
+            hipLaunchKernelGGL(k_table_compact, dim3((m + 255) / 256), dim3(256), 0, t->stream, m, t->d_stage.as<int32_t>(), t->dev(),
+                               table_dev([nb](int i) { return nb[i].p; }));
+            if (ops.done(hipGetLastError()))
+                return ORBGPU_EHIP;
         }
-    if ((rc = nsrc.reserve(sizeof(int32_t) * (size_t)std::max(m, 1))) != ORBGPU_OK) {
-        drop();
+        nh.rebuild(l2);
+        for (int i = 0; i < m; i++)
+            nh.insert(kept[(size_t)i], i);
         return rc;
-    }
-    hipError_t he = hipSuccess;
-    for (int k = 0; k < 8 && he == hipSuccess; k++)
-        he = hipMemsetAsync(nb[k].p, 0, elt[k] * (size_t)ncap, t->stream);
-    if (he == hipSuccess && m > 0)
-        he = hipMemcpyAsync(nsrc.p, src.data(), sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, t->stream);
-    if (he == hipSuccess && m > 0) {
-        TableDev d{nb[0].as<float>(), nb[1].as<float>(), nb[2].as<float>(), nb[3].as<float>(),
-                   nb[4].as<uint8_t>(), nb[5].as<uint8_t>(), nb[6].as<uint8_t>(), nb[7].as<int64_t>()};
-        hipLaunchKernelGGL(k_table_compact, dim3((m + 255) / 256), dim3(256), 0, t->stream, m, nsrc.as<int32_t>(), t->dev(), d);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess)
-        he = hipStreamSynchronize(t->stream);
-    // the id -> row hash of the kept ids, host and device
-    int l2 = 1;
-    while ((1 << l2) < 2 * ncap)
-        l2++;
-    IdHash nh;
-    nh.rebuild(l2);
-    for (int i = 0; i < m; i++)
-        nh.insert(kept[(size_t)i], i);
-    DevBuf nk, nv;
-    if (he == hipSuccess && ((rc = nk.reserve(sizeof(int64_t) << l2)) != ORBGPU_OK || (rc = nv.reserve(sizeof(int32_t) << l2)) != ORBGPU_OK ||
-                             (rc = t->pos_of_row.reserve(sizeof(int32_t) * (size_t)ncap)) != ORBGPU_OK)) {
-        nk.release(), nv.release();
-        drop();
+    };
+    // (retain always re-allocates: there is no branch that finds enough capacity, so it always takes the lock)
+    if ((rc = lifecycle_locked_unless(false, lifecycle_mutex(), [&] { return id_table_replace(t->parts(), ncap, ops, fill); })) != ORBGPU_OK)
         return rc;
-    }
-    if (he == hipSuccess)
-        he = hipMemcpyAsync(nk.p, nh.keys.data(), sizeof(int64_t) << l2, hipMemcpyHostToDevice, t->stream);
-    if (he == hipSuccess)
-        he = hipMemcpyAsync(nv.p, nh.vals.data(), sizeof(int32_t) << l2, hipMemcpyHostToDevice, t->stream);
-    if (he == hipSuccess)
-        he = hipStreamSynchronize(t->stream);
-    if (he != hipSuccess) {
-        set_error("MapPoint table retain: %s", hipGetErrorString(he));
-        nk.release(), nv.release();
-        drop();
-        return ORBGPU_EHIP;
-    }
-    DevBuf *cur[8] = {&t->world_pos, &t->normal, &t->min_dist, &t->max_dist, &t->desc, &t->bad, &t->obs, &t->id};
-    for (int k = 0; k < 8; k++) {
-        cur[k]->release();
-        *cur[k] = nb[k];
-    }
-    nsrc.release();
-    t->d_hkeys.release(), t->d_hvals.release();
-    t->d_hkeys = nk, t->d_hvals = nv;
-    t->hash = nh;
     t->rows = m;
-    t->cap = ncap;
     t->stamp.assign((size_t)ncap, 0);
     t->call_no = 0;
     if (dropped)

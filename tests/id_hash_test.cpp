@@ -1,4 +1,4 @@
-// CPU unit test of the MapPoint table's id -> row hash (orb_slam2_map_amd/csrc/id_hash.h) and of the shim's pointer index
+// CPU unit test of the id tables' id -> row hash (orb_slam2_map_amd/csrc/id_hash.h) and of the shim's pointer index
 // (orbgpu_shim::PtrIndex): plain g++ with the sanitizers, no HIP, nothing linked.
 #include "id_hash.h"
 #include "orbgpu_shim.hpp"
@@ -28,12 +28,12 @@ static int test_id_hash()
         cap_rows = std::max(cap_rows * 2, 16);
         while (cap_rows < want)
             cap_rows *= 2;
-        int l2 = 1;
-        while ((1 << l2) < 2 * cap_rows)
-            l2++;
-        h.rebuild(l2);
+        h.rebuild(orbgpu::id_hash_log2cap(cap_rows));
     };
+    // the function the kernels run, over the arrays they would be given
+    auto lookup = [&](int64_t id) { return orbgpu::id_hash_lookup(h.keys.data(), h.vals.data(), h.log2cap, id); };
     CHECK(h.find(5) == -1);  // empty table
+    CHECK(orbgpu::id_hash_lookup(h.keys.data(), h.vals.data(), 0, 5) == -1);
     for (int round = 0; round < 200; round++) {
         const int n = 1 + (int)(rng() % 700);
         ensure(rows + n);
@@ -51,8 +51,12 @@ static int test_id_hash()
                 break;
             }
             batch.push_back(id);
-            if (h.find(id) < 0)
+            if (h.find(id) < 0) {
+                const uint32_t free_slot = h.slot_for(id);  // an absent id: the slot its insertion then takes
+                CHECK(h.keys[free_slot] == orbgpu::ID_HASH_EMPTY);
                 slots.push_back((int32_t)h.insert(id, rows++));
+                CHECK((uint32_t)slots.back() == free_slot);
+            }
         }
         if (dup) {
             h.rollback(slots.data(), (int)slots.size());
@@ -66,14 +70,18 @@ static int test_id_hash()
         }
         // every id ever accepted is found with its row, rolled-back and never-seen ids are absent
         if (round % 10 == 0 || dup) {
-            for (const auto &kv : ref)
+            for (const auto &kv : ref) {
                 CHECK(h.find(kv.first) == kv.second);
+                CHECK(lookup(kv.first) == kv.second);
+                CHECK(h.keys[h.slot_for(kv.first)] == kv.first && h.vals[h.slot_for(kv.first)] == kv.second);
+            }
             if (dup)
                 for (int64_t id : batch)
                     CHECK(h.find(id) == (ref.count(id) ? ref[id] : -1));
             for (int k = 0; k < 200; k++) {
                 const int64_t id = (int64_t)(rng() >> 12);
                 CHECK(h.find(id) == (ref.count(id) ? ref[id] : -1));
+                CHECK(lookup(id) == h.find(id) && lookup(-id - 1) == -1);
             }
         }
         // load factor invariant
@@ -82,7 +90,20 @@ static int test_id_hash()
             used += k != orbgpu::ID_HASH_EMPTY;
         CHECK(used == ref.size() && 2 * used <= h.capacity());
     }
-    CHECK(h.find(-1) == -1 && h.find(-12345) == -1);
+    CHECK(h.find(-1) == -1 && h.find(-12345) == -1 && lookup(-1) == -1 && lookup(-12345) == -1);
+    const struct {
+        int64_t rows;
+        int l2;
+    } caps[] = {{0, 1}, {1, 1}, {2, 2}, {3, 3}, {512, 10}, {513, 11}, {1 << 24, 25}};
+    for (const auto &c : caps)
+        CHECK(orbgpu::id_hash_log2cap(c.rows) == c.l2);
+    const size_t capacity = h.capacity();
+    h.clear();
+    CHECK(h.capacity() == capacity && h.keys.size() == capacity && h.vals.size() == capacity);
+    for (const auto &kv : ref)
+        CHECK(h.find(kv.first) == -1 && lookup(kv.first) == -1);
+    for (size_t s = 0; s < capacity; s++)
+        CHECK(h.keys[s] == orbgpu::ID_HASH_EMPTY && h.vals[s] == -1);
     std::printf("id_hash ok: %zu ids, capacity %zu\n", ref.size(), h.capacity());
     return 0;
 }

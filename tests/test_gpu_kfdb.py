@@ -1,6 +1,7 @@
 """The device KeyFrameDatabase against tests/kfdb_model.py (vs CPU restatement; DBoW2 boundary unpinned): candidate id
 lists equal and in order, the records of the sharing list equal with scores and sums bit-equal.  Every
 database starts with initial_rows = 2, so rows, pool and hash grow in every test that adds more."""
+import ctypes as C
 import os
 import sys
 
@@ -345,3 +346,69 @@ def test_a_small_capacity_still_reports_the_full_count(F):
                 assert n == 6 and got.tolist() == full.tolist()[:cap]
     finally:
         pair.close()
+
+
+class KfRowMirror(C.Structure):
+    """the device row of kfdb.hip (KfRow), for its size"""
+    _fields_ = [("id", C.c_int64), ("off", C.c_int32), ("len", C.c_int32), ("alive", C.c_int32), ("reg", C.c_float),
+                ("nn", C.c_int32), ("pad", C.c_int32), ("nb", C.c_int64 * 10)]
+
+
+@pytest.mark.parametrize("what", ["rows", "pool"])
+def test_a_refused_growth_leaves_the_database_as_it_was(gpu, monkeypatch, what):
+    """The growth transaction of id_table.h (rows and hash) and grow_pool under ORBGPU_DEBUG_FAIL_ALLOC_OVER, on a database
+    created with initial_rows = 2 (2 rows, a pool of 1024 entries).  rows: the third key frame needs 4 rows; the limit is one
+    byte under the 4-row KfRow column, the largest allocation of that growth and its first.  pool: one key frame holds 1000
+    entries, the next needs 100 more, so the pool doubles: the limit lets its id array (4 * 2048 bytes) through and refuses
+    the value array (8 * 2048).  The add returns ENOMEM; size, relocalisation and loop candidates and the sharing list's
+    scores and sums are what they were, bit for bit; then the add succeeds and the new key frame scores."""
+    hook = "ORBGPU_DEBUG_FAIL_ALLOC_OVER"
+    monkeypatch.delenv(hook, raising=False)
+    rng = np.random.default_rng(9)
+    n_words = 100000
+    q = M.random_vector(rng, n_words, 60)
+    if what == "rows":
+        first = [(11, M.vector_from(rng, q[0], q[1], 40, n_words, 30)), (5, M.vector_from(rng, q[0], q[1], 20, n_words, 100))]
+        new = (8, M.vector_from(rng, q[0], q[1], 30, n_words, 10))
+        nbytes = 4 * C.sizeof(KfRowMirror)  # (a mirror that drifts from KfRow misses the hipMalloc size asserted below)
+        limit = nbytes - 1
+    else:
+        first = [(11, M.vector_from(rng, q[0], q[1], 40, n_words, 960))]
+        new = (8, M.vector_from(rng, q[0], q[1], 30, n_words, 70))
+        assert len(first[0][1][0]) == 1000 and len(new[1][0]) == 100
+        nbytes = 8 * 2048
+        limit = 4 * 2048
+    db = gpu.KeyFrameDatabase(n_words, initial_rows=2)
+    for kf_id, v in first:
+        db.add(kf_id, *v)
+    db.set_covisibles(11, [5, 8, 77])
+    db.set_covisibles(5, [11])
+    db.set_covisibles(8, [11, 5])  # kept for the id until it is added
+
+    def state():
+        reloc = db.DetectRelocalizationCandidates(*q)
+        reloc_list = db.last_query()
+        loop = db.DetectLoopCandidates(q[0], q[1], [], 0.0)
+        return [reloc, loop] + [reloc_list[k] for k in sorted(reloc_list)] + [v for _, v in sorted(db.last_query().items())]
+
+    def same(a, b):
+        return len(a) == len(b) and all(x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes() for x, y in zip(a, b))
+
+    state()  # (the first relocalisation query writes the score registers the next ones read: K5)
+    before = state()
+    assert len(before[0]) >= 1 and len(before[1]) >= 1 and same(before, state())
+    monkeypatch.setenv(hook, str(limit))
+    with pytest.raises(gpu.OrbGpuError) as ei:
+        db.add(new[0], *new[1])
+    monkeypatch.delenv(hook)
+    assert ei.value.status == gpu.ENOMEM and "hipMalloc(%d)" % nbytes in str(ei.value), str(ei.value)
+    assert db.size() == len(first)
+    assert np.isnan(db.score(q[0], q[1], [new[0]])[0])
+    assert same(state(), before)
+    db.add(new[0], *new[1])
+    assert db.size() == len(first) + 1
+    got = db.score(q[0], q[1], [new[0], 11])
+    want = np.array([M.l1_score(q[0], q[1], *new[1]), M.l1_score(q[0], q[1], *first[0][1])], np.float32)
+    assert np.array_equal(bits(got), bits(want))
+    assert new[0] in db.DetectRelocalizationCandidates(*q).tolist() + db.last_query()["id"].tolist()
+    db.close()

@@ -267,3 +267,98 @@ def test_search_by_projection_last_frame_over_the_table(gpu, oracle, th, mono, o
     ng2, kg2 = gpu.search_by_projection_last_table(dl, Tlast, dc, Tcw, tbl, np.full(n1, -1, np.int64), fx, fy, cx, cy, bf, mb, th,
                                                    mono, True)
     assert ng2 == 0 and np.all(kg2 == -1)
+
+
+def test_refused_growth_and_retain_leave_the_table_as_it_was(gpu, oracle, monkeypatch):
+    """The growth transaction of id_table.h on the device: a table of exactly 1024 rows (its first capacity), an upsert of one
+    new id under ORBGPU_DEBUG_FAIL_ALLOC_OVER=40000 -- at 2048 rows only the descriptor column (65536 bytes) is over the
+    limit: positions and normals take 24576, the hash keys 32768 -- and a retain of 900 ids under a limit of 20000 (capacity
+    1024: only the descriptor column, 32768 bytes, is over it; the hash keys take 16384).  Both return ENOMEM and leave the
+    rows, a search over the table and its unknown-id counts as they were; then both succeed."""
+    hook = "ORBGPU_DEBUG_FAIL_ALLOC_OVER"
+    monkeypatch.delenv(hook, raising=False)
+    st, sf, Tcw, wp, mp, of, rng = local_map_scenario(gpu, oracle, 640, 480, 600, 1, 0.1, 21)
+    m, n = len(wp), 1024
+    assert 100 < m < 850
+    ids = rng.permutation(10 * n)[:n].astype(np.int64) * 7919 + 11  # the list points are rows 0 .. m-1
+    extra = n - m
+    A = {"world_pos": np.concatenate([wp, rng.normal(0, 2, (extra, 3)).astype(np.float32)]),
+         "normal": np.concatenate([mp["normal"], rng.normal(0, 1, (extra, 3)).astype(np.float32)]),
+         "min_dist": np.concatenate([mp["min_dist"], rng.uniform(0.1, 1, extra).astype(np.float32)]),
+         "max_dist": np.concatenate([mp["max_dist"], rng.uniform(2, 9, extra).astype(np.float32)]),
+         "desc": np.concatenate([mp["desc"], rng.integers(0, 256, (extra, 32), dtype=np.uint8)]),
+         "n_obs": np.concatenate([mp["obs_pos"].astype(np.int32) * 3, (np.arange(extra) % 2).astype(np.int32)])}
+    tbl = gpu.MapPointTable(initial_rows=0)
+    tbl.upsert(ids, **A)
+    assert tbl.rows() == n
+    assert tbl.set_bad(ids[:m][mp["bad"] != 0]) == int((mp["bad"] != 0).sum())
+    # the call: three listed ids and five key-point ids the table does not know, associations to list and outside points
+    listed = ids[:m].copy()
+    listed[[5, 50, 90]] = 4242424242 + np.arange(3)
+    kp_ids = np.full(of.n, -1, np.int64)
+    pre = rng.choice(of.n, 65, replace=False)
+    kp_ids[pre[:30]] = ids[rng.integers(0, m, 30)]
+    kp_ids[pre[30:60]] = ids[m:m + 30]
+    kp_ids[pre[60:]] = 777000000 + np.arange(5)
+    fx, fy, cx, cy, bf = (float(v) for v in (st.fx, st.fy, st.cx, st.cy, st.bf))
+    log_sf = float(np.log(np.float32(sf[1])))
+    dfr = gpu.DeviceFrame().upload(make_gframe(gpu, of))
+
+    def search():
+        nm, k2m, trk = gpu.search_local_points_table(dfr, tbl, listed, Tcw, fx, fy, cx, cy, bf, log_sf, 3.0, 0.8, kp_ids=kp_ids,
+                                                     want_track=True)
+        return nm, k2m.copy(), trk, tbl.last_unknown()
+
+    def same_search(a, b):
+        return (a[0] == b[0] and np.array_equal(a[1], b[1]) and a[3] == b[3] and
+                all(np.array_equal(a[2][k].view(np.uint8), b[2][k].view(np.uint8)) for k in a[2]))
+
+    def same_row(a, b):
+        return all(np.array_equal(a[k], b[k]) for k in a)
+
+    def row(i):
+        return {"world_pos": A["world_pos"][i], "normal": A["normal"][i], "min_dist": A["min_dist"][i], "max_dist": A["max_dist"][i],
+                "desc": A["desc"][i], "has_observations": int(A["n_obs"][i] > 0), "bad": int(i < m and mp["bad"][i] != 0)}
+
+    before = search()
+    assert before[0] > 20 and before[3] == (3, 5)
+    for i in (0, 511, 1023):
+        assert same_row(tbl.read(ids[i]), row(i)), i
+
+    def refused(call, limit, nbytes):
+        monkeypatch.setenv(hook, str(limit))
+        with pytest.raises(gpu.OrbGpuError) as ei:
+            call()
+        monkeypatch.delenv(hook)
+        assert ei.value.status == gpu.ENOMEM and "hipMalloc(%d)" % nbytes in str(ei.value), str(ei.value)
+
+    def unchanged(rows):
+        assert tbl.rows() == rows and tbl.last_unknown() == before[3]
+        for i in (0, 511, 1023):
+            assert same_row(tbl.read(ids[i]), row(i)), i
+        assert same_search(search(), before)
+
+    new_id = np.array([99999999999], np.int64)
+    new = {"world_pos": np.full((1, 3), 2.5, np.float32), "normal": np.full((1, 3), 0.5, np.float32),
+           "min_dist": np.array([0.25], np.float32), "max_dist": np.array([8], np.float32),
+           "desc": np.full((1, 32), 0xA5, np.uint8), "n_obs": np.array([2], np.int32)}
+    refused(lambda: tbl.upsert(new_id, **new), 40000, 32 * 2048)
+    unchanged(n)
+    with pytest.raises(RuntimeError, match="not in the table"):
+        tbl.read(int(new_id[0]))
+    tbl.upsert(new_id, **new)
+    got = tbl.read(int(new_id[0]))
+    assert tbl.rows() == n + 1 and np.array_equal(got["world_pos"], new["world_pos"][0]) and np.array_equal(got["desc"], new["desc"][0])
+    assert got["max_dist"] == 8 and got["has_observations"] == 1 and got["bad"] == 0
+    unchanged(n + 1)
+    # retain: rows 0 .. 899 in shuffled order and row 1023 -- every list point and every point a key point holds
+    keep = np.concatenate([rng.permutation(899), [1023]])
+    refused(lambda: tbl.retain(ids[keep]), 20000, 32 * 1024)
+    unchanged(n + 1)
+    assert np.array_equal(tbl.read(int(new_id[0]))["desc"], new["desc"][0])
+    assert tbl.retain(ids[keep]) == n + 1 - 900
+    unchanged(900)
+    for i in (900, 1022):
+        with pytest.raises(RuntimeError, match="not in the table"):
+            tbl.read(ids[i])
+    tbl.close()

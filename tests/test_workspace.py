@@ -1,5 +1,5 @@
-"""Host-only headers of the library ((thread, device) workspace lookup, id hash, the projection matchers' host boundary):
-compiled with plain g++ and run on the CPU."""
+"""Host-only headers of the library ((thread, device) workspace lookup, id hash, the id tables' growth transaction, the
+projection matchers' host boundary): compiled with plain g++ and run on the CPU."""
 import os
 import subprocess
 
@@ -35,8 +35,9 @@ def test_stateless_entry_points_use_the_lookup():
 
 
 def test_id_hash_and_pointer_index(tmp_path):
-    """The MapPoint table's host-side id -> row hash (insert, lookup, growth, the rollback of a refused call) and the shim's
-    pointer index against std::map / a linear search, under AddressSanitizer + UBSan."""
+    """The id tables' id -> row hash (insert, find and the lookup the kernels run, slot_for, the capacity rule, growth,
+    clear, the rollback of a refused call) and the shim's pointer index against std::map / a linear search, under
+    AddressSanitizer + UBSan."""
     exe = str(tmp_path / "id_hash_test")
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                     "-I" + os.path.join(ROOT, "orb_slam2_map_amd", "csrc"), "-I" + os.path.join(ROOT, "orb_slam2_map_amd", "shim"),
@@ -44,6 +45,39 @@ def test_id_hash_and_pointer_index(tmp_path):
                    check=True)
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0 and "id_hash ok" in r.stdout and "ptr_index ok" in r.stdout, r.stdout
+
+
+def test_id_table_growth_transaction(tmp_path):
+    """id_table.h over malloc-backed buffers and recording operations, under AddressSanitizer + UBSan: growth and a
+    retain-style compaction of a small table with every allocation and every operation failed once -- the code returned,
+    the table bit for bit what it was, a sync before the first new buffer is freed, no leak -- and then unfailed: contents
+    carried over, every id found by id_hash_lookup over the uploaded copy, the old buffers freed exactly once."""
+    exe = str(tmp_path / "id_table_test")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-pthread", "-fsanitize=address,undefined",
+                    "-I" + os.path.join(ROOT, "orb_slam2_map_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "id_table_test.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0 and "id_table_test ok" in r.stdout, r.stdout
+
+
+def test_id_tables_share_one_core():
+    """map_table.hip and kfdb.hip keep no lookup, no carve-out, no capacity loop and no growth of their own: the hash is
+    id_hash.h's, the transaction id_table.h's, which stays compilable without HIP."""
+    import re
+    csrc = os.path.join(ROOT, "orb_slam2_map_amd", "csrc")
+    for name in ("map_table.hip", "kfdb.hip"):
+        src = open(os.path.join(csrc, name)).read()
+        assert "id_hash_lookup(" in src and '#include "id_table.h"' in src, name
+        assert not re.search(r"\b\w+_lookup\s*\([^;{]*\)\s*\{", src), name      # a function definition named *_lookup
+        assert not re.search(r"struct\s+Carve", src), name
+        assert not re.search(r"while\s*\(\s*\(.*<<\s*l2\s*\)\s*<", src) and "l2++" not in src, name  # the capacity loop
+        assert "hash_slot_for" not in src, name
+        assert "id_table_grow(" in src, name
+    table = open(os.path.join(csrc, "map_table.hip")).read()
+    assert "id_table_replace(" in table and table.count("&world_pos") == 1 and table.count("&t->world_pos") == 0
+    core = open(os.path.join(csrc, "id_table.h")).read()
+    assert "#include <hip" not in core and '#include "common.h"' not in core and "struct Carver" in core
+    assert "l2++" in open(os.path.join(csrc, "id_hash.h")).read()
 
 
 def test_projection_boundary_on_the_host(tmp_path):
