@@ -15,6 +15,7 @@
 #include <utility>
 #include "trig_base.h"
 #include "pyramid_view.h"
+#include "resize_tables.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -26,6 +27,7 @@
 namespace orbgpu {
 
 constexpr int EDGE = 19;           // EDGE_THRESHOLD, ORBextractor.cc:74
+static_assert(EDGE == RS_EDGE, "resize_tables.h builds its tables for this border");
 constexpr int BORDER0 = EDGE - 3;  // minBorderX/Y, ORBextractor.cc:775-776
 constexpr int HALF_PATCH = 15;     // HALF_PATCH_SIZE, ORBextractor.cc:73
 constexpr int PATCH = 31;          // PATCH_SIZE
@@ -63,18 +65,6 @@ struct CellDesc {
     int pad[1];
 };
 static_assert(sizeof(CellDesc) == 32, "CellDesc is read as two 16-byte words");
-
-struct XTab {  // cv::resize horizontal table entry (A2)
-    uint16_t sx, sx1, a0, a1;
-};
-struct YTab {
-    uint16_t sy0, sy1;
-    int16_t b0, b1;
-};
-struct YRow {  // the same per PADDED output row (border rows = the entry of the row they reflect to), as four ints: one
-    int sy0, sy1, b0, b1;  // 16-byte load, no reflection and no field extraction in k_resize_fast's row loop
-};
-
 
 // packed FAST key: y[31:20] x[19:8] response[7:0]; x,y relative to (minBorderX,minBorderY)
 __host__ __device__ __forceinline__ uint32_t pack_key(int x, int y, int resp)
@@ -267,23 +257,145 @@ __global__ __launch_bounds__(256) void k_resize_level(uint8_t *__restrict__ pyr,
     *reinterpret_cast<uint32_t *>(pyr + (size_t)f * frame_pyr + g.plane_off + rowoff(py, g.pitch) + x4) = v;
 }
 
-// Fast path of K1b: one thread per aligned output dword (4 pixels) of the padded plane.  The 8 source
+// Fast path of K1b: one thread per aligned output dword (4 pixels), rows 0 .. h-1 and the dword columns that hold the
+// image and RS_RING = 3 border columns on either side (resize_tables.h).  No extractor stage reads the 19-px border
+//  except k_blur, which reads 3 px of it: the first and last dwords of a row produce those columns as a
+// full-plane pass would (the resize evaluated at the reflected coordinate), and rows 1..3 and h-4..h-2 are stored a
+// second time as the border rows they reflect to.  The rest of the border is written when mvImagePyramid[l] is handed
+// out (k_ring_fill).  The 8 source
 // bytes the 4 outputs need per source row lie inside one 12-byte aligned window (true for scale
 // factors <= 2; checked on the host, otherwise k_resize_level runs), which is fetched with 3 dword
 // loads and shifted by the column's byte offset (two v_alignbyte) so that they lie in one 8-byte pair; v_perm_b32 with
 // host-precomputed selectors forms (left tap | right tap << 16) pairs and v_dot2_u32_u16 applies the 11-bit weights.
 // Same integer arithmetic as k_resize_level.
-struct ResizeStrip {  // per padded output dword column of a level
-    uint32_t base_q;  // bits 0..15: window base (padded source column, multiple of 4); bits 16..17: byte shift of the window;
-                      // bit 18 (direct level-0 source only): the window is the last 12 bytes of the row and the pair comes from its dwords 1, 2
+typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+
+// The 8-pixel form of k_resize_fast (batches; levels whose taps fit, resize_tables.h): an item is two adjacent output
+// dwords x PYR_ROWS rows.  Per source row ONE 16-byte window, shifted once (run byte j = window byte shift + j): half 0
+// takes its taps from run bytes 0..7, half 1 from run bytes 4 + e .. 11 + e.  The horizontal sums are kept already
+// shifted by 4 (what the vertical pass multiplies); the vertical pass works on pairs of pixels -- the high halves of two
+// 24-bit products packed by one v_perm, the sum, the rounding and the final shift as packed 16-bit operations, and one
+// v_perm per four pixels packs the bytes.  The window of the next row is requested before the arithmetic of this one.
+struct __attribute__((packed, aligned(4))) RsWin {
+    uint32_t d[4];
 };
 
-typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+template <bool DIRECT, bool SHARE>
+__device__ __forceinline__ void resize_h8(const RsWin &wn, uint32_t sh, uint32_t e, bool rot1, bool rot2, bool share,
+                                          const uint32_t (&selv)[8], const uint32_t (&wv)[8], uint32_t (&u)[8])
+{
+    uint32_t d0 = wn.d[0], d1 = wn.d[1], d2 = wn.d[2];
+    const uint32_t d3 = wn.d[3];
+    if (DIRECT) {  // at the end of an image row: the window is the row's last 16 bytes and the run starts in its dword 1 or 2
+        d0 = rot2 ? d2 : rot1 ? d1 : d0;
+        d1 = rot2 ? d3 : rot1 ? d2 : d1;
+        d2 = rot1 ? d3 : d2;
+    }
+    const uint32_t r0 = __builtin_amdgcn_alignbyte(d1, d0, sh), r1 = __builtin_amdgcn_alignbyte(d2, d1, sh),
+                   r2 = __builtin_amdgcn_alignbyte(d3, d2, sh), r3 = __builtin_amdgcn_alignbyte(d3, d3, sh);
+    uint32_t lo1 = __builtin_amdgcn_alignbyte(r2, r1, e), hi1 = __builtin_amdgcn_alignbyte(r3, r2, e);
+    if (SHARE) {  // R8_SHARE: half 1's taps lie in half 0's eight bytes
+        lo1 = share ? r0 : lo1;
+        hi1 = share ? r1 : hi1;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint32_t p0 = __builtin_amdgcn_perm(r1, r0, selv[k]), p1 = __builtin_amdgcn_perm(hi1, lo1, selv[4 + k]);
+        // (sum >> 4 as the 24-bit field the multiplies of the vertical pass read: one form for the compiler to keep)
+        u[k] = __builtin_amdgcn_ubfe(__builtin_amdgcn_udot2(__builtin_bit_cast(us2, p0), __builtin_bit_cast(us2, wv[k]), 0u, false), 4u, 24u);
+        u[4 + k] = __builtin_amdgcn_ubfe(__builtin_amdgcn_udot2(__builtin_bit_cast(us2, p1), __builtin_bit_cast(us2, wv[4 + k]), 0u, false), 4u, 24u);
+    }
+}
+
+template <bool DIRECT, bool SHARE>
+__device__ __forceinline__ void resize_fast8(uint8_t *__restrict__ pyr, size_t frame_pyr, const LevelGeom &g,
+                                             const LevelGeom &gs, const uint32_t *__restrict__ items,
+                                             const uint4 *__restrict__ sels, const uint4 *__restrict__ wts,
+                                             const YRow *__restrict__ yrows, int item_off, const Src0 &s0)
+{
+    const int n8 = resize_n8(g.w);
+    int bx, f;
+    xcd_frame_block(bx, f);
+    const int item = bx * 256 + threadIdx.x;  // (row group, item of the row), flattened
+    const int rg = item / n8;
+    const int ci = item - rg * n8;
+    if (rg * PYR_ROWS >= g.h)
+        return;
+    const uint32_t bq = items[item_off + ci];
+    const uint32_t sh = (bq >> R8_SHIFT_LSB) & 3u, e = (bq >> R8_E_LSB) & 3u;
+    const bool rot1 = DIRECT && ((bq >> R8_ROT_LSB) & 3u) == 1u, rot2 = DIRECT && ((bq >> R8_ROT_LSB) & 3u) == 2u;
+    const bool share = SHARE && (bq & R8_SHARE) != 0u;
+    const uint4 q0 = sels[2 * (item_off + ci)], q1 = sels[2 * (item_off + ci) + 1];
+    const uint4 w0 = wts[2 * (item_off + ci)], w1 = wts[2 * (item_off + ci) + 1];
+    const uint32_t selv[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+    const uint32_t wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+    uint8_t *fb = pyr + (size_t)f * frame_pyr;
+    const uint8_t *sb = DIRECT ? s0.p + (size_t)f * s0.frame_stride : fb;
+    const int spitch = DIRECT ? (int)s0.pitch : gs.pitch;
+    const uint32_t base = (DIRECT ? 0u : (uint32_t)gs.plane_off + (uint32_t)EDGE * (uint32_t)gs.pitch) + (bq & R8_BASE_MASK);
+    uint32_t doff = (uint32_t)g.plane_off + (uint32_t)(RESIZE_DW0 * 4 + ci * 8) + rowoff(rg * PYR_ROWS + EDGE, g.pitch);
+    YRow yts[PYR_ROWS];  // (rows past the last one: the last one's entry, so that every window address is a real row)
+#pragma unroll
+    for (int rr = 0; rr < PYR_ROWS; rr++)
+        yts[rr] = yrows[g.yrow_off + EDGE + min(rg * PYR_ROWS + rr, g.h - 1)];
+    RsWin nx = *reinterpret_cast<const RsWin *>(sb + (base + rowoff(yts[0].sy1, spitch)));
+    int kept_row = -1;
+    uint32_t kept[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // border rows -1 .. -RS_RING and h .. h-1+RS_RING: the items that hold the rows they reflect store them twice
+    const bool ring_top = rg == 0, ring_bot = (rg + 1) * PYR_ROWS >= g.h - 1 - RS_RING;
+    const uint32_t dtop = (uint32_t)g.plane_off + (uint32_t)(RESIZE_DW0 * 4 + ci * 8) + rowoff(EDGE, g.pitch);  // row 0
+#pragma unroll
+    for (int rr = 0; rr < PYR_ROWS; rr++) {
+        const int y = rg * PYR_ROWS + rr;
+        if (y >= g.h)
+            break;
+        const YRow yt = yts[rr];
+        const RsWin cur = nx;
+        if (rr + 1 < PYR_ROWS)
+            nx = *reinterpret_cast<const RsWin *>(sb + (base + rowoff(yts[rr + 1].sy1, spitch)));
+        uint32_t u0[8], u1[8];
+        if (yt.sy0 != kept_row) {
+            const RsWin up = *reinterpret_cast<const RsWin *>(sb + (base + rowoff(yt.sy0, spitch)));
+            resize_h8<DIRECT, SHARE>(up, sh, e, rot1, rot2, share, selv, wv, u0);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                u0[k] = kept[k];
+        }
+        resize_h8<DIRECT, SHARE>(cur, sh, e, rot1, rot2, share, selv, wv, u1);
+        // o = (((b0 * u0) >> 16) + ((b1 * u1) >> 16) + 2) >> 2 with 0 <= b <= 2048 (host-checked), u <= 255 * 128; the
+        // rounding 2 rides on the first product (2 << 16: it lands in the high half the v_perm takes)
+        const uint32_t b0 = (uint32_t)yt.b0, b1 = (uint32_t)yt.b1;
+        const us2 two = {2, 2};
+        uint32_t sp[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t a = __builtin_amdgcn_perm(__umul24(b0, u0[2 * j + 1]) + (2u << 16), __umul24(b0, u0[2 * j]) + (2u << 16), 0x07060302u);
+            const uint32_t b = __builtin_amdgcn_perm(__umul24(b1, u1[2 * j + 1]), __umul24(b1, u1[2 * j]), 0x07060302u);
+            sp[j] = __builtin_bit_cast(uint32_t, (us2)((__builtin_bit_cast(us2, a) + __builtin_bit_cast(us2, b)) >> two));
+        }
+        uint2 o;
+        o.x = __builtin_amdgcn_perm(sp[1], sp[0], 0x06040200u);
+        o.y = __builtin_amdgcn_perm(sp[3], sp[2], 0x06040200u);
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            kept[k] = u1[k];
+        kept_row = yt.sy1;
+        *reinterpret_cast<uint2 *>(fb + doff) = o;
+        doff += (uint32_t)g.pitch;
+        if (ring_top && rr >= 1 && rr <= RS_RING)  // (rg == 0: y = rr)
+            *reinterpret_cast<uint2 *>(fb + (dtop - (uint32_t)rr * (uint32_t)g.pitch)) = o;
+        if (ring_bot && y >= g.h - 1 - RS_RING && y <= g.h - 2)
+            *reinterpret_cast<uint2 *>(fb + (dtop + rowoff(2 * (g.h - 1) - y, g.pitch))) = o;
+    }
+}
 
 // REUSE: keep a source row's horizontal interpolation for the next output row (pays on the large levels).
 // DIRECT: level 1 from the caller's image (Src0) instead of the padded level-0 plane; the strip tables are built for
 // unpadded source columns and a window that would run past the end of an image row re-reads its second dword.
-template <bool REUSE, bool DIRECT>
+// PX: pixels per item and row: 4 as described above, or 8 (resize_fast8; `strips` are then the item words, REUSE and
+// PYR_ROWS rows are implied).  SHARE (PX = 8): some item of the level has R8_SHARE set.
+template <bool REUSE, bool DIRECT, int PX, bool SHARE = false>
 __global__ __launch_bounds__(256) void k_resize_fast(uint8_t *__restrict__ pyr, size_t frame_pyr,
                                                      const LevelGeom *__restrict__ geom, int level,
                                                      const ResizeStrip *__restrict__ strips,
@@ -292,13 +404,17 @@ __global__ __launch_bounds__(256) void k_resize_fast(uint8_t *__restrict__ pyr, 
 {
     const LevelGeom g = geom[level];
     const LevelGeom gs = geom[level - 1];
-    const int ndw = g.pitch >> 2;
+    if constexpr (PX == 8) {
+        resize_fast8<DIRECT, SHARE>(pyr, frame_pyr, g, gs, reinterpret_cast<const uint32_t *>(strips), sels, wts, yrows, strip_off, s0);
+        return;
+    }
+    const int ndw = resize_ndw(g.w);
     int bx, f;
     xcd_frame_block(bx, f);
     const int item = bx * 256 + threadIdx.x;  // (row group, output dword column), flattened
     const int rg = item / ndw;
-    const int sdw = item - rg * ndw;
-    if (rg * rows >= g.h + 2 * EDGE)
+    const int sdw = RESIZE_DW0 + item - rg * ndw;
+    if (rg * rows >= g.h)
         return;
     const uint32_t bq = strips[strip_off + sdw].base_q;
     const uint32_t sh = (bq >> 16) & 3u;  // byte shift of the 12-byte window (0..3)
@@ -319,14 +435,16 @@ __global__ __launch_bounds__(256) void k_resize_fast(uint8_t *__restrict__ pyr, 
     YRow yts[PYR_ROWS];
 #pragma unroll
     for (int rr = 0; rr < PYR_ROWS; rr++)
-        yts[rr] = yrows[g.yrow_off + min(rg * rows + rr, g.h + 2 * EDGE - 1)];
+        yts[rr] = yrows[g.yrow_off + EDGE + min(rg * rows + rr, g.h - 1)];
     // consecutive output rows share a source row (row y's lower tap row is usually row y+1's upper one): its horizontal
     // interpolation is kept instead of being loaded and computed again
     int kept_row = -1, kept[4] = {0, 0, 0, 0};
+    // border rows -1 .. -RS_RING and h .. h-1+RS_RING: the items that hold the rows they reflect
+    const bool ring_top = rg * rows <= RS_RING, ring_bot = (rg + 1) * rows >= g.h - 1 - RS_RING;
 #pragma unroll
     for (int rr = 0; rr < PYR_ROWS; rr++) {
-        const int py = rg * rows + rr;
-        if (rr >= rows || py >= g.h + 2 * EDGE)
+        const int y = rg * rows + rr;
+        if (rr >= rows || y >= g.h)
             break;
         const YRow yt = yts[rr];
         const uint32_t *S1 = reinterpret_cast<const uint32_t *>(sb + (base + rowoff(yt.sy1, spitch)));
@@ -367,8 +485,50 @@ __global__ __launch_bounds__(256) void k_resize_fast(uint8_t *__restrict__ pyr, 
             kept[k] = t1;
         }
         kept_row = yt.sy1;
-        *reinterpret_cast<uint32_t *>(fb + (dst + rowoff(py, g.pitch))) = v;
+        *reinterpret_cast<uint32_t *>(fb + (dst + rowoff(y + EDGE, g.pitch))) = v;
+        if (ring_top && y >= 1 && y <= RS_RING)
+            *reinterpret_cast<uint32_t *>(fb + (dst + rowoff(EDGE - y, g.pitch))) = v;
+        if (ring_bot && y >= g.h - 1 - RS_RING && y <= g.h - 2)
+            *reinterpret_cast<uint32_t *>(fb + (dst + rowoff(2 * (g.h - 1) - y + EDGE, g.pitch))) = v;
     }
+}
+
+// The `ring`-pixel frame around the interior of levels 1 .. n-1 of every frame, as copyMakeBorder(REFLECT_101) makes it:
+// plain copies of the plane's own interior pixels.  One thread per frame pixel: the 2 ring rows above and below the image
+// (corners included), then the 2 ring columns beside every image row.  Not on the hot path (k_resize_fast writes the
+// 3 px the blur reads itself): ring = EDGE when a full padded plane is handed out.
+struct RingGeom {
+    int first[ORBGPU_MAX_LEVELS + 1];  // first item of level l (first[1] = 0); first[nlevels] = items per frame
+    int nlevels;
+};
+__global__ __launch_bounds__(256) void k_ring_fill(uint8_t *__restrict__ pyr, size_t frame_pyr,
+                                                    const LevelGeom *__restrict__ geom, RingGeom rgm, int ring)
+{
+    const int item = blockIdx.x * 256 + threadIdx.x;
+    if (item >= rgm.first[rgm.nlevels])
+        return;
+    int level = 1;
+#pragma unroll
+    for (int l = 2; l < ORBGPU_MAX_LEVELS; l++)
+        level += (l < rgm.nlevels && item >= rgm.first[l]) ? 1 : 0;
+    const LevelGeom g = geom[level];
+    int local = item - rgm.first[level];
+    const int w2 = g.w + 2 * ring, nband = 2 * ring * w2;
+    int x, y;
+    if (local < nband) {
+        const int r = local / w2;
+        x = local - r * w2 - ring;
+        y = r < ring ? r - ring : g.h + (r - ring);
+    } else {
+        local -= nband;
+        y = local / (2 * ring);
+        const int k = local - y * (2 * ring);
+        x = k < ring ? k - ring : g.w + (k - ring);
+    }
+    // -ring <= x < w + ring, -ring <= y < h + ring with ring <= EDGE: inside the padded plane
+    uint8_t *pl = pyr + (size_t)blockIdx.y * frame_pyr + g.plane_off;
+    pl[rowoff(y + EDGE, g.pitch) + (uint32_t)(x + EDGE)] =
+        pl[rowoff(reflect101(y, g.h) + EDGE, g.pitch) + (uint32_t)(reflect101(x, g.w) + EDGE)];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1667,6 +1827,7 @@ struct UMax {
 // Integer moments: exact in any summation order.
 constexpr int OR_ITERS = 4;  // key points per half wave for full batches (1 below OR_BATCH_MIN frames: latency)
 constexpr int OR_BATCH_MIN = 32;
+constexpr int PYR_BATCH_MIN = 32;  // frames per call from which every level of the resize chain runs PYR_ROWS rows per item (REUSE)
 
 __global__ __launch_bounds__(256) void k_orient(const uint8_t *__restrict__ pyr, size_t frame_pyr,
                                                 const LevelGeom *__restrict__ geom, int nlevels,
@@ -2187,7 +2348,6 @@ extern "C" void orbgpu_qt_dbg_dump()
 #else
 static long long *qt_dbg() { return nullptr; }
 #endif
-static inline int cv_round_host(double v) { return (int)lrint(v); }
 
 } // namespace orbgpu
 
@@ -2258,9 +2418,17 @@ struct orbgpu_extractor {
     int direct0_min_batch = 8;     // frames per call from which direct mode is used (ORBGPU_DEBUG_DIRECT0_MIN)
     bool no_direct0 = false;       // ORBGPU_DEBUG_NO_DIRECT0 (read at creation): always make the padded copy (tests, A/B)
     int rs_off_direct = 0;         // level 1's strip tables for the unpadded source
+    int r8_off[ORBGPU_MAX_LEVELS] = {};  // 8-pixel form of k_resize_fast: first item of the level, -1 = the level keeps the 4-pixel form
+    int r8_off_direct = -1;              // ... of level 1 for the unpadded source
+    bool r8_share[ORBGPU_MAX_LEVELS] = {}, r8_share_direct = false;  // some item of the level has R8_SHARE set
+    DevBuf d_r8item, d_r8sel, d_r8wt;
     DetectGeom det_geom_direct;    // k_fast_detect's strips with level 0 aligned to the image
     Src0 last_src = {nullptr, 0, 0u, 0};  // level-0 source of the last call (direct != 0: the call ran in direct mode)
     bool level0_materialized = true;      // d_pyr holds level 0 of the last call (false after a direct-mode call until a getter asks)
+    // k_resize_fast writes plane interiors and the 3 px of border the blur reads; k_ring_fill the full border on demand
+    bool interior_resize = false;      // some level >= 1 of the configured geometry goes through k_resize_fast
+    bool borders_materialized = true;  // the planes of levels >= 1 hold their whole 19-px border (false after a call until a getter asks)
+    bool poison_pyramid = false;       // ORBGPU_DEBUG_POISON_PYRAMID (read at creation): 0xA5 over both plane buffers before every call (tests)
     TrigTable trig = {nullptr, nullptr, nullptr, 0u};  // the host libm's cosf / sinf exceptions (trig.hip); none in ORBGPU_TRIG_ROUNDED_DOUBLE mode
 
 };
@@ -2333,9 +2501,9 @@ static void forget_last_call(orbgpu_extractor *e)
     e->last_batch = e->last_cap = 0;
     e->last_src = Src0{nullptr, 0, 0u, 0};
     e->level0_materialized = true;
+    e->borders_materialized = true;
 }
 
-static inline short sat_short(int v) { return (short)(v < -32768 ? -32768 : v > 32767 ? 32767 : v); }
 
 // Level sizes, FAST cell grid, resize tables, slot layout for one image size.
 static int configure(orbgpu_extractor *e, int w, int h, int batch)
@@ -2354,11 +2522,8 @@ static int configure(orbgpu_extractor *e, int w, int h, int batch)
     const int nl = e->nlevels;
     std::vector<LevelGeom> geom(nl);
     std::vector<CellDesc> cells;
-    std::vector<XTab> xtab;
-    std::vector<YTab> ytab;
-    std::vector<YRow> yrow;
-    std::vector<ResizeStrip> rstrip;
-    std::vector<uint4> rsel, rwt;
+    ResizeTables rt;
+    std::vector<ResizeLevel> rlev(nl);
     size_t plane_off = 0;
     int slot_off = 0, sel_off = 0, max_cells_level = 0, ncap = 0;
     for (int l = 0; l < nl; l++) {
@@ -2432,124 +2597,29 @@ static int configure(orbgpu_extractor *e, int w, int h, int batch)
         g.sel_off = sel_off;
         sel_off += g.sel_cap;
         ncap = std::max(ncap, g.sel_cap);
-        // resize tables (cv::resize INTER_LINEAR 8U, A2)
-        g.xtab_off = (int)xtab.size();
-        g.ytab_off = (int)ytab.size();
+        // resize tables (cv::resize INTER_LINEAR 8U, A2) and the item tables of k_resize_fast: resize_tables.h
         if (l > 0) {
-            const int sw = geom[l - 1].w, sh = geom[l - 1].h;
-            const double scale_x = 1. / ((double)g.w / sw), scale_y = 1. / ((double)g.h / sh);
-            for (int dx = 0; dx < g.w; dx++) {
-                float fx = (float)((dx + 0.5) * scale_x - 0.5);
-                int sx = (int)floor(fx);
-                fx -= sx;
-                if (sx < 0) {
-                    fx = 0;
-                    sx = 0;
-                }
-                if (sx >= sw - 1) {
-                    fx = 0;
-                    sx = sw - 1;
-                }
-                XTab t;
-                t.sx = (uint16_t)sx;
-                t.sx1 = (uint16_t)std::min(sx + 1, sw - 1);
-                t.a0 = (uint16_t)sat_short(cv_round_host((1.f - fx) * 2048));
-                t.a1 = (uint16_t)sat_short(cv_round_host(fx * 2048));
-                xtab.push_back(t);
-            }
-            for (int dy = 0; dy < g.h; dy++) {
-                float fy = (float)((dy + 0.5) * scale_y - 0.5);
-                int sy = (int)floor(fy);
-                fy -= sy;
-                YTab t;
-                t.sy0 = (uint16_t)std::min(std::max(sy, 0), sh - 1);
-                t.sy1 = (uint16_t)std::min(std::max(sy + 1, 0), sh - 1);
-                t.b0 = sat_short(cv_round_host((1.f - fy) * 2048));
-                t.b1 = sat_short(cv_round_host(fy * 2048));
-                ytab.push_back(t);
-            }
-            g.yrow_off = (int)yrow.size();
-            for (int py = 0; py < g.h + 2 * EDGE; py++) {
-                const YTab &t = ytab[g.ytab_off + reflect101(py - EDGE, g.h)];
-                yrow.push_back(YRow{(int)t.sy0, (int)t.sy1, (int)t.b0, (int)t.b1});
-            }
-            // fast-path strip tables: one entry per aligned output dword of the padded row
-            g.rs_off = (int)rstrip.size();
-            g.rs_fast = 1;
-            for (int sdw = 0; sdw < g.pitch / 4; sdw++) {
-                int cl[4], cr[4];
-                const XTab *xt[4];
-                int mn = 1 << 30;
-                for (int k = 0; k < 4; k++) {
-                    const int px = std::min(sdw * 4 + k, g.w + 2 * EDGE - 1);
-                    const int dx = reflect101(px - EDGE, g.w);
-                    xt[k] = &xtab[g.xtab_off + dx];
-                    cl[k] = xt[k]->sx + EDGE;
-                    cr[k] = xt[k]->sx1 + EDGE;
-                    mn = std::min(mn, cl[k]);
-                }
-                // the 12-byte window starts at the aligned column wbase; the kernel shifts it by sh = mn - wbase bytes (two
-                // v_alignbyte per source row) so that all eight taps of the four outputs lie in ONE 8-byte pair
-                const int wbase = mn & ~3, sh = mn - wbase;
-                ResizeStrip rsx;
-                rsx.base_q = (uint32_t)wbase | ((uint32_t)sh << 16);
-                uint32_t sel[4], wt[4];
-                for (int k = 0; k < 4; k++) {
-                    const int ol = cl[k] - mn, orr = cr[k] - mn;
-                    if (ol < 0 || orr < ol || orr > 7)
-                        g.rs_fast = 0;
-                    sel[k] = (uint32_t)(ol & 7) | 0x0c00u | ((uint32_t)(orr & 7) << 16) | 0x0c000000u;
-                    wt[k] = (uint32_t)xt[k]->a0 | ((uint32_t)xt[k]->a1 << 16);
-                }
-                rstrip.push_back(rsx);
-                rsel.push_back(uint4{sel[0], sel[1], sel[2], sel[3]});
-                rwt.push_back(uint4{wt[0], wt[1], wt[2], wt[3]});
-            }
+            rlev[l] = resize_add_level(rt, geom[l - 1].w, geom[l - 1].h, geom[l - 1].pitch, g.w, g.h, g.pitch);
+            g.xtab_off = rlev[l].xtab_off;
+            g.ytab_off = rlev[l].ytab_off;
+            g.yrow_off = rlev[l].yrow_off;
+            g.rs_off = rlev[l].rs_off;
+            g.rs_fast = rlev[l].fast4 ? 1 : 0;
         }
     }
-    // direct mode: level 1's strips once more, for source columns counted from the image's own column 0 (Src0).  A window
-    // that would run past the end of an image row (the next row, or -- last row of the last frame -- the end of the
-    // caller's buffer) is placed on the row's last 12 bytes and the pair is cut from its second and third dword (bit 18).
+    // direct mode: level 1's items once more, for source columns counted from the image's own column 0 (Src0)
     bool direct_ok = nl >= 2 && w % 8 == 0 && w >= 64 && geom[std::min(1, nl - 1)].rs_fast != 0;
-    int rs_off_direct = 0;
+    ResizeLevel rdirect;
     if (direct_ok) {
-        const LevelGeom &g = geom[1];
-        const int sw = geom[0].w;
-        rs_off_direct = (int)rstrip.size();
-        for (int sdw = 0; sdw < g.pitch / 4 && direct_ok; sdw++) {
-            int cl[4], cr[4], mn = 1 << 30;
-            const XTab *xt[4];
-            for (int k = 0; k < 4; k++) {
-                const int px = std::min(sdw * 4 + k, g.w + 2 * EDGE - 1);
-                xt[k] = &xtab[g.xtab_off + reflect101(px - EDGE, g.w)];
-                cl[k] = xt[k]->sx;
-                cr[k] = xt[k]->sx1;
-                mn = std::min(mn, cl[k]);
-            }
-            int wbase = mn & ~3, ps = mn;  // ps: first byte of the 8-byte pair the selectors index
-            int pbase = wbase;             // first byte of the two dwords the pair is cut from
-            uint32_t edge = 0;
-            if (wbase + 12 > sw) {  // the window would pass the end of the row: the row's last 12 bytes, pair from dwords 1 and 2
-                wbase = sw - 12;
-                pbase = sw - 8;
-                ps = std::min(mn, pbase + 3);
-                edge = 1u << 18;
-            }
-            const int sh = ps - pbase;
-            uint32_t sel[4], wt[4];
-            for (int k = 0; k < 4; k++) {
-                const int ol = cl[k] - ps, orr = cr[k] - ps;
-                // inside the pair, and -- at a row end -- inside its valid part (the bytes above 7 - sh come from the re-read dword)
-                if (sh < 0 || sh > 3 || wbase < 0 || ol < 0 || orr < ol || orr > (edge ? 7 - sh : 7))
-                    direct_ok = false;
-                sel[k] = (uint32_t)(ol & 7) | 0x0c00u | ((uint32_t)(orr & 7) << 16) | 0x0c000000u;
-                wt[k] = (uint32_t)xt[k]->a0 | ((uint32_t)xt[k]->a1 << 16);
-            }
-            rstrip.push_back(ResizeStrip{(uint32_t)wbase | ((uint32_t)sh << 16) | edge});
-            rsel.push_back(uint4{sel[0], sel[1], sel[2], sel[3]});
-            rwt.push_back(uint4{wt[0], wt[1], wt[2], wt[3]});
-        }
+        rdirect = resize_add_direct(rt, rlev[1], geom[0].w, geom[1].w, geom[1].pitch);
+        direct_ok = rdirect.fast4;
     }
+    const int rs_off_direct = rdirect.rs_off;
+    const std::vector<XTab> &xtab = rt.xtab;
+    const std::vector<YTab> &ytab = rt.ytab;
+    const std::vector<YRow> &yrow = rt.yrow;
+    const std::vector<ResizeStrip> &rstrip = rt.strip;
+    const std::vector<RsQuad> &rsel = rt.sel, &rwt = rt.wt;
     ncap = std::max(ncap, (max_cells_level + 3) / 4);  // the cell scan reuses the [ncap*4] child-count array
     ncap = ((ncap + 7) / 8) * 8;
     const size_t qt_lds = (size_t)ncap * (2 * sizeof(short4) + 2 * sizeof(int) + 8 * sizeof(int) + 2 * sizeof(int) +
@@ -2687,6 +2757,16 @@ static int configure(orbgpu_extractor *e, int w, int h, int batch)
         direct_ok = build_detect(true, e->det_geom_direct);
     e->direct0_ok = direct_ok;
     e->rs_off_direct = rs_off_direct;
+    for (int l = 0; l < ORBGPU_MAX_LEVELS; l++)
+        e->r8_off[l] = l >= 1 && l < nl && rlev[l].fast8 ? rlev[l].r8_off : -1;
+    e->r8_off_direct = direct_ok && rdirect.fast8 ? rdirect.r8_off : -1;
+    for (int l = 0; l < ORBGPU_MAX_LEVELS; l++)
+        e->r8_share[l] = l >= 1 && l < nl && rlev[l].share8;
+    e->r8_share_direct = rdirect.share8;
+    e->interior_resize = false;
+    for (int l = 1; l < nl; l++)
+        e->interior_resize = e->interior_resize || geom[l].rs_fast != 0;
+    e->borders_materialized = true;
     e->geom = geom;  // (with the cell-grid fields filled in above)
     // k_border0_fast: per aligned dword of the padded level-0 row, the two adjacent source dwords and the byte selector
     std::vector<BorderCol> bcol;
@@ -2734,6 +2814,9 @@ static int configure(orbgpu_extractor *e, int w, int h, int batch)
     RSV(e->d_rstrip, sizeof(ResizeStrip) * std::max<size_t>(rstrip.size(), 1));
     RSV(e->d_rsel, sizeof(uint4) * std::max<size_t>(rsel.size(), 1));
     RSV(e->d_rwt, sizeof(uint4) * std::max<size_t>(rwt.size(), 1));
+    RSV(e->d_r8item, sizeof(uint32_t) * std::max<size_t>(rt.item8.size(), 1));
+    RSV(e->d_r8sel, sizeof(RsQuad) * std::max<size_t>(rt.sel8.size(), 1));
+    RSV(e->d_r8wt, sizeof(RsQuad) * std::max<size_t>(rt.wt8.size(), 1));
     RSV(e->d_pattern, 1024 + 2 * 4 * 16 * 9 * sizeof(uint32_t));  // rBRIEF pattern, then k_orient's weight tables
     const size_t B = (size_t)batch;
     RSV(e->d_pyr, e->frame_pyr * B);
@@ -2765,6 +2848,11 @@ static int configure(orbgpu_extractor *e, int w, int h, int batch)
         ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_rstrip.p, rstrip.data(), sizeof(ResizeStrip) * rstrip.size(), hipMemcpyHostToDevice, e->stream));
         ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_rsel.p, rsel.data(), sizeof(uint4) * rsel.size(), hipMemcpyHostToDevice, e->stream));
         ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_rwt.p, rwt.data(), sizeof(uint4) * rwt.size(), hipMemcpyHostToDevice, e->stream));
+        if (!rt.item8.empty()) {
+            ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_r8item.p, rt.item8.data(), sizeof(uint32_t) * rt.item8.size(), hipMemcpyHostToDevice, e->stream));
+            ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_r8sel.p, rt.sel8.data(), sizeof(RsQuad) * rt.sel8.size(), hipMemcpyHostToDevice, e->stream));
+            ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_r8wt.p, rt.wt8.data(), sizeof(RsQuad) * rt.wt8.size(), hipMemcpyHostToDevice, e->stream));
+        }
     }
     ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_pattern.p, k_pattern_host, 1024, hipMemcpyHostToDevice, e->stream));
     {
@@ -2836,10 +2924,10 @@ struct Launcher {
         kp.extra = nullptr;
         add([&](hipGraphNode_t *n, const hipGraphNode_t *dep, size_t ndep) { return hipGraphAddKernelNode(n, graph, dep, ndep, &kp); });
     }
-    int memset32(void *dst, size_t bytes)  // zero `bytes` (a multiple of 4) at dst
+    int memset32(void *dst, size_t bytes, uint8_t byte = 0)  // `bytes` (a multiple of 4) at dst = byte (zero)
     {
         if (!graph) {
-            ORBGPU_HIP_TRY(hipMemsetAsync(dst, 0, bytes, st));
+            ORBGPU_HIP_TRY(hipMemsetAsync(dst, byte, bytes, st));
             return ORBGPU_OK;
         }
         hipMemsetParams mp = {};
@@ -2848,7 +2936,7 @@ struct Launcher {
         mp.width = bytes / 4;
         mp.height = 1;
         mp.pitch = bytes;
-        mp.value = 0;
+        mp.value = 0x01010101u * byte;
         add([&](hipGraphNode_t *n, const hipGraphNode_t *dep, size_t ndep) { return hipGraphAddMemsetNode(n, graph, dep, ndep, &mp); });
         return ORBGPU_OK;
     }
@@ -2888,6 +2976,18 @@ static int materialize_level0(orbgpu_extractor *e, const Src0 &s0, int batch, La
     if (!L.graph)
         ORBGPU_HIP_TRY(hipGetLastError());
     return ORBGPU_OK;
+}
+
+// REFLECT_101 frame of `ring` pixels around the interiors k_resize_fast wrote (levels >= 1)
+static void launch_ring_fill(orbgpu_extractor *e, int batch, Launcher &L, int ring)
+{
+    RingGeom rg = {};
+    rg.nlevels = e->nlevels;
+    for (int l = 1; l < e->nlevels; l++)
+        rg.first[l + 1] = rg.first[l] + 2 * ring * (e->geom[l].w + 2 * ring) + 2 * ring * e->geom[l].h;
+    if (rg.first[e->nlevels] > 0)
+        L.launch(k_ring_fill, dim3((rg.first[e->nlevels] + 255) / 256, batch), dim3(256), 0, e->d_pyr.as<uint8_t>(),
+                 e->frame_pyr, e->d_geom.as<LevelGeom>(), rg, ring);
 }
 
 // the blur of all levels: one launch, or -- direct mode -- level 0 from the image (k_blur0_direct) + the other levels
@@ -2953,6 +3053,14 @@ static int launch_pipeline(orbgpu_extractor *e, const uint8_t *d_gray, int batch
     const Src0 s0{d_gray, frame_stride, (uint32_t)stride, direct ? 1 : 0};
     e->last_src = s0;
     e->level0_materialized = !direct;
+    e->borders_materialized = !e->interior_resize;
+    if (e->poison_pyramid) {  // a stage that reads a pixel this call does not write reads 0xA5
+        int rcp = L.memset32(pyr, e->frame_pyr * batch, 0xA5);
+        if (rcp == ORBGPU_OK)
+            rcp = L.memset32(blur, e->frame_pyr * batch, 0xA5);
+        if (rcp != ORBGPU_OK)
+            return rcp;
+    }
     BEGIN(ST_PYRAMID, st);
     // concurrent blur in direct mode: level 0's blur depends on the image only -- it starts on the side stream now, next
     // to the resize chain (seven dependent launches whose small levels leave most of the device idle)
@@ -2975,14 +3083,26 @@ static int launch_pipeline(orbgpu_extractor *e, const uint8_t *d_gray, int batch
         for (int l = 1; l < nl; l++) {
             const LevelGeom &gl = e->geom[l];
             dim3 gr((gl.pitch / 4 + 255) / 256, gl.h + 2 * EDGE, batch);
-            // rows per thread: 8 on the large levels; the small ones get more (shorter) threads to hide latency with
+            // rows per thread: 8 on the large levels; the small ones of a few frames get more (shorter) threads to hide
+            // latency with.  A batch has threads enough: every level takes full items and keeps its horizontal passes.
             const int ndw_l = (gl.pitch / 4) * (gl.h + 2 * EDGE);
-            const int rows = ndw_l >= 32768 ? PYR_ROWS : ndw_l >= 16384 ? PYR_ROWS / 2 : PYR_ROWS / 4;
-            dim3 grf(((gl.pitch / 4) * ((gl.h + 2 * EDGE + rows - 1) / rows) + 255) / 256, batch);
+            const int rows = batch >= PYR_BATCH_MIN || ndw_l >= 32768 ? PYR_ROWS : ndw_l >= 16384 ? PYR_ROWS / 2 : PYR_ROWS / 4;
+            dim3 grf((resize_ndw(gl.w) * ((gl.h + rows - 1) / rows) + 255) / 256, batch);
             if (gl.rs_fast) {
                 const bool dir1 = direct && l == 1;  // level 1 straight from the image
-                auto kern = dir1 ? (rows == PYR_ROWS ? k_resize_fast<true, true> : k_resize_fast<false, true>)
-                                 : (rows == PYR_ROWS ? k_resize_fast<true, false> : k_resize_fast<false, false>);
+                // a batch: eight pixels per item where the level's taps fit the 16-byte window (resize_tables.h)
+                const int r8 = batch >= PYR_BATCH_MIN ? (dir1 ? e->r8_off_direct : e->r8_off[l]) : -1;
+                if (r8 >= 0) {
+                    dim3 gr8((resize_n8(gl.w) * ((gl.h + PYR_ROWS - 1) / PYR_ROWS) + 255) / 256, batch);
+                    const bool shr = dir1 ? e->r8_share_direct : e->r8_share[l];
+                    L.launch(dir1 ? (shr ? k_resize_fast<true, true, 8, true> : k_resize_fast<true, true, 8, false>)
+                                  : (shr ? k_resize_fast<true, false, 8, true> : k_resize_fast<true, false, 8, false>), gr8, dim3(256), 0, pyr,
+                             e->frame_pyr, dg, l, e->d_r8item.as<ResizeStrip>(), e->d_r8sel.as<uint4>(), e->d_r8wt.as<uint4>(),
+                             e->d_yrow.as<YRow>(), r8, PYR_ROWS, s0);
+                    continue;
+                }
+                auto kern = dir1 ? (rows == PYR_ROWS ? k_resize_fast<true, true, 4> : k_resize_fast<false, true, 4>)
+                                 : (rows == PYR_ROWS ? k_resize_fast<true, false, 4> : k_resize_fast<false, false, 4>);
                 L.launch(kern, grf, dim3(256), 0, pyr, e->frame_pyr, dg, l, e->d_rstrip.as<ResizeStrip>(),
                                    e->d_rsel.as<uint4>(), e->d_rwt.as<uint4>(), e->d_yrow.as<YRow>(),
                                    dir1 ? e->rs_off_direct : gl.rs_off, rows, s0);
@@ -3151,6 +3271,7 @@ int orbgpu_extractor_create(const orbgpu_extractor_params *p, orbgpu_extractor *
     if (const char *q = getenv("ORBGPU_DEBUG_QT_KEYS"))  // test hook, read here like the others (configure() runs at the first extraction)
         e->qt_keys_hook = std::max(atoi(q), 0);
     e->no_direct0 = getenv("ORBGPU_DEBUG_NO_DIRECT0") != nullptr;
+    e->poison_pyramid = getenv("ORBGPU_DEBUG_POISON_PYRAMID") != nullptr;
     e->no_early_blur0 = getenv("ORBGPU_DEBUG_NO_EARLY_BLUR0") != nullptr;
     if (const char *q = getenv("ORBGPU_DEBUG_DIRECT0_MIN"))
         e->direct0_min_batch = std::max(atoi(q), 1);
@@ -3364,6 +3485,7 @@ int orbgpu_extract_batch(orbgpu_extractor *e, const uint8_t *gray, int32_t batch
                 e->last_batch = e->graph_batch;
                 e->last_cap = e->graph_cap;
                 e->level0_materialized = !e->graph_src.direct;
+                e->borders_materialized = !e->interior_resize;
                 e->graph_replays++;
             } else
                 e->graph_state = -1;
@@ -3396,6 +3518,7 @@ int orbgpu_extract_batch(orbgpu_extractor *e, const uint8_t *gray, int32_t batch
                 ok = hipGraphLaunch(e->graph_exec, e->stream) == hipSuccess;
                 launched = ok;
                 e->level0_materialized = !e->last_src.direct;
+                e->borders_materialized = !e->interior_resize;
             }
             if (!ok) {
                 (void)hipGetLastError();
@@ -3467,6 +3590,21 @@ static int ensure_level0(orbgpu_extractor *e)
     return ORBGPU_OK;
 }
 
+// Likewise the 19-px borders of levels >= 1: the hot path writes 3 px of them (k_resize_fast), the rest when a padded
+// plane is handed out.
+static int ensure_borders(orbgpu_extractor *e)
+{
+    if (e->borders_materialized)
+        return ORBGPU_OK;
+    ORBGPU_HIP_TRY(hipDeviceSynchronize());
+    Launcher L0(nullptr);
+    launch_ring_fill(e, e->last_batch, L0, EDGE);
+    ORBGPU_HIP_TRY(hipGetLastError());
+    ORBGPU_HIP_TRY(hipDeviceSynchronize());
+    e->borders_materialized = true;
+    return ORBGPU_OK;
+}
+
 int orbgpu_extractor_get_pyramid_level(orbgpu_extractor *e, int32_t frame, int32_t level, uint8_t *dst,
                                        size_t dst_stride, int32_t *width, int32_t *height)
 {
@@ -3479,6 +3617,8 @@ int orbgpu_extractor_get_pyramid_level(orbgpu_extractor *e, int32_t frame, int32
     if (rc != ORBGPU_OK)
         return rc;
     if (level == 0 && (rc = ensure_level0(e)) != ORBGPU_OK)
+        return rc;
+    if (level > 0 && (rc = ensure_borders(e)) != ORBGPU_OK)
         return rc;
     const uint8_t *src = e->d_pyr.as<uint8_t>() + e->frame_pyr * frame + g.plane_off + (size_t)EDGE * g.pitch + EDGE;
     ORBGPU_HIP_TRY(hipDeviceSynchronize());
@@ -3514,6 +3654,8 @@ int orbgpu_extractor_debug_read(orbgpu_extractor *e, int32_t what, int32_t frame
         const size_t bytes = (size_t)g.pitch * (g.h + 2 * EDGE);
         ORBGPU_REQUIRE(dst_bytes >= bytes, "dst too small (%zu needed)", bytes);
         if (what == ORBGPU_DBG_PYRAMID_PADDED && level == 0 && (rc = ensure_level0(e)) != ORBGPU_OK)
+            return rc;
+        if (what == ORBGPU_DBG_PYRAMID_PADDED && level > 0 && (rc = ensure_borders(e)) != ORBGPU_OK)
             return rc;
         const uint8_t *base = (what == ORBGPU_DBG_PYRAMID_PADDED ? e->d_pyr : e->d_blur).as<uint8_t>();
         ORBGPU_HIP_TRY(hipMemcpy(dst, base + e->frame_pyr * frame + g.plane_off, bytes, hipMemcpyDeviceToHost));

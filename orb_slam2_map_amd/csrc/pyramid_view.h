@@ -1,6 +1,9 @@
 // Read-only view of an extractor handle's pyramid of the LAST call, for units outside extractor.hip that read
 // mvImagePyramid (Frame::ComputeStereoMatches, stereo.hip).  Filled by extractor_pyramid_view (extractor.hip) without
 // touching the device: in direct mode level 0 is NOT materialised, the view points at the last call's own image.
+// What the view guarantees of a padded plane is its w x h interior and 3 px of REFLECT_101 border around it: the resize
+// chain writes no more (the rest of the 19-px border exists only after a getter of mvImagePyramid asked for it).  Readers
+// stay inside the image (stereo.hip checks every window against w and h before it reads).
 #pragma once
 
 #include "common.h"
