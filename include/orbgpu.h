@@ -752,6 +752,133 @@ int orbgpu_sim3_solve(const orbgpu_sim3_problem *p, int32_t *counts, float *R, f
 int orbgpu_sim3_solve_all(const orbgpu_sim3_problem *p, int32_t *counts, float *R, float *t, float *s, float *T12,
                           uint64_t *masks, orbgpu_sim3_result *result, int32_t device_id);
 
+/* ---- PnPsolver (PnPsolver.cc, EPnP + RANSAC): the pose of a relocalisation candidate on the device ----------------------
+ * The third of the six steps Tracking::Relocalization runs per candidate key frame (Tracking.cc:1645-1810), between
+ * orbgpu_search_by_bow and orbgpu_pose_optimization.  All hypotheses of a candidate are evaluated at once, one wave each;
+ * the reference's sequential acceptance rule, its Refine included, is replayed over the per-hypothesis counts.  Every
+ * result is "vs CPU restatement; OpenCV boundary unpinned"; tests/pnp_model.py is the restatement.  Conventions P1-P10
+ * (DESIGN.md section 2):
+ *   P1 rows (:67-101)     row i is kept iff valid[i] != 0 (the caller's verdict on: has a map point that is not bad) and
+ *                         octave[i] lies in [0, nlevels); a valid row with an octave outside is not kept and counted in
+ *                         n_bad_index.  Kept rows are compacted in index order: N of them.  kp[i] = mvKeysUn[i].pt,
+ *                         Xw[i] the float world position.
+ *   P2 thresholds (:154-156)  maxError = level_sigma2[octave] * th2, one float product
+ *   P3 parameters (:121-152)  on the host (orbgpu_pnp_ransac_parameters): nMinInliers = (int)((float)N * epsilon), raised
+ *                         to min_inliers, then to min_set; epsilon raised to (float)nMinInliers / N; nIterations = 1 if
+ *                         nMinInliers == N, else ceil(log(1 - p) / log(1 - pow((double)epsilon, 3))) in double -- the
+ *                         exponent is 3 whatever min_set is; NaN or outside int counts as larger than max_iterations (H4);
+ *                         max_its = max(1, min(nIterations, max_iterations)); N = 0 gives 1.
+ *   P4 minimal sets       the library draws nothing: sets[h][min_set] index the compacted list.  The first
+ *                         n_use = min(n_hyp, max(max_its, start_iteration + n_iterations)) are used (none if N <
+ *                         nMinInliers).  orbgpu_shim::PnPSampleSets replays the reference's draw (:188-201), its quirk
+ *                         included (position idx, not randi, is overwritten: an index may repeat within a set).  A used set
+ *                         with an index outside [0, N) is never read through: count 0, NaN Tcw, counted in n_bad_set.  A
+ *                         set with a repeated index is computed like any other.
+ *   P5 EPnP (:375-525, :651-858)  FP64, one rounding per operation, only + - * / sqrt.  A sum over the points of a set is
+ *                         a wave sum: lane l of 64 adds the terms l, l + 64, ... from +0.0, then the partial sums are folded
+ *                         by halves (l += l + 32, 16, ... 1).  Symmetric eigenproblems (3x3 PCA, 12x12 M'M, the normal
+ *                         matrices below, abt'abt) use cyclic Jacobi: pairs row by row, at most 30 sweeps, H6's stopping
+ *                         rule and rotation formulas; where an order matters eigenvalues are sorted descending with a
+ *                         stable sort and every eigenvector is flipped so that its component of largest magnitude (lowest
+ *                         index on ties) is positive.  Control points: centroid + sqrt(max(lambda_i, 0) / n) u_i.  The
+ *                         inverse of CC = U diag(k_i) is diag(1 / k_i) U' with 1 / k_i = 0 when k_i <= 1e-6 k_0 (coplanar
+ *                         sets).  Null-space basis: for k = max(0, 12 - 2n) > 0 the k smallest eigenvectors are replaced by
+ *                         the canonical basis of their span -- the projector's columns orthonormalised by pivoted
+ *                         Gram-Schmidt (largest remaining column, lowest index on ties), sign rule as above; the others
+ *                         are the plain eigenvectors.  L, rho and the three beta approximations as the reference; their
+ *                         least-squares solves go through the Jacobi of L'L, eigenvalues <= 1e-12 x the largest dropped
+ *                         (minimum-norm solution).  Gauss-Newton: 5 iterations, Householder QR, the column scale taken
+ *                         over all remaining rows; a zero pivot column gives x = 0.  R = U V' of abt = U S V' with V from
+ *                         the Jacobi of abt'abt and u_k = abt v_k / |abt v_k|; the third ROW is flipped when det < 0
+ *                         (:618-622).  Among the three solutions the mean reprojection error decides by strict <.  No
+ *                         special cases beyond these: NaN follows IEEE and ends in count 0.
+ *   P6 inliers (:308-339) Xc, Yc: double expressions rounded to float; invZc = (float)(1.0 / double expression); ue, ve
+ *                         double; distX, distY, error2 float; inlier iff error2 < maxError
+ *   P7 refine (:260-305)  EPnP over the best inlier set in index order, then P6; successful iff the refined count >
+ *                         nMinInliers (strict; the gate before it is >=)
+ *   P8 acceptance (:165-258)  N < nMinInliers: no_more at once.  Scanning from (start_iteration, best_so_far), hypothesis h
+ *                         sets a record iff count >= nMinInliers && count > best; only records are refined (only a record
+ *                         changes what Refine reads).  The scan ends at the first successful refine, or when
+ *                         iterations >= max_its AND this call has scanned at least n_iterations hypotheses (the
+ *                         reference's || in :182: the first iterate(5, ...) runs to max_its); no_more iff it ended that
+ *                         way, and then the result is the best record's own pose and mask if this call set one.  A scan
+ *                         that reaches n_use first ends with no_more = 0: draw further sets and call again.
+ *   P9 outputs            Tcw = the float of R, t entry by entry in a 4x4 identity; masks one bit per original row i
+ *   P10 limits            n1 in [0, 16384], n_hyp in [0, 4096], min_set in [4, 64], nlevels in [1, ORBGPU_MAX_LEVELS];
+ *                         every device loop has a fixed bound */
+typedef struct orbgpu_pnp_result { /* device or host */
+    int32_t n;              /* N: kept rows */
+    int32_t min_inliers;    /* mRansacMinInliers after P3 */
+    int32_t max_its;        /* mRansacMaxIts (P3) */
+    int32_t n_bad_index;    /* valid rows with an octave outside [0, nlevels): not kept */
+    int32_t n_bad_set;      /* used sets with an index outside [0, N) */
+    int32_t accepted;       /* the iteration whose Refine succeeded (0-based index into sets) or -1 */
+    int32_t n_inliers;      /* nInliers: the refined count, or the best record's with the fallback of no_more, else 0 */
+    int32_t best_inliers;   /* mnBestInliers after the scan */
+    int32_t best_iteration; /* the record that holds it, -1 if this call set none */
+    int32_t iterations;     /* mnIterations after the scan */
+    int32_t no_more;        /* bNoMore */
+    int32_t pad_;
+    float Tcw[16];          /* the returned pose (refined, or the fallback's); zeros if none */
+} orbgpu_pnp_result;
+
+/* The array pointers are DEVICE pointers for the *_device entry points and HOST pointers for the host flavours. */
+typedef struct orbgpu_pnp_problem {
+    int32_t n1;             /* vpMapPointMatches.size() */
+    int32_t n_hyp;          /* H: rows of sets */
+    const uint8_t *valid;   /* [n1] (P1) */
+    const float *Xw;        /* [n1][3] world position of the map point of key point i (read for valid rows only) */
+    const float *kp;        /* [n1][2] mvKeysUn[i].pt */
+    const int32_t *octave;  /* [n1] mvKeysUn[i].octave */
+    const int32_t *sets;    /* [n_hyp][min_set] (P4) */
+    float fx, fy, cx, cy;
+    float level_sigma2[ORBGPU_MAX_LEVELS]; /* mvLevelSigma2 */
+    int32_t nlevels;
+    int32_t min_set, min_inliers, max_iterations; /* SetRansacParameters' arguments */
+    float epsilon, th2;
+    double probability;
+    int32_t start_iteration, best_so_far; /* P8: 0, 0 for a fresh solver */
+    int32_t n_iterations;   /* iterate's argument; 0: scan to max_its */
+    int32_t pad_;
+    /* outputs (the host flavours ignore them) */
+    int32_t *counts;        /* [n_hyp]: inliers of hypothesis h; 0 for h >= n_use */
+    float *Tcw;             /* [n_hyp][16], written for h < n_use */
+    uint64_t *masks;        /* [n_hyp][(n1 + 63) / 64]: bit i % 64 of word i / 64; written for h < n_use */
+    uint64_t *refined_mask; /* [(n1 + 63) / 64]: vbInliers of the returned pose; zeros if none */
+    int32_t *indices;       /* [n1] mvKeyPointIndices (compacted -> i), first N written; may be NULL */
+    orbgpu_pnp_result *result;
+} orbgpu_pnp_problem;
+
+/* P3 on the host; EINVAL for a null pointer or a negative n / min_inliers / max_iterations / min_set. */
+int orbgpu_pnp_ransac_parameters(int32_t n, double probability, int32_t min_inliers, int32_t max_iterations, int32_t min_set,
+                                 float epsilon, int32_t *adjusted_min_inliers, int32_t *max_its);
+/* Enqueued on hip_stream; synchronisation, workspace and error rules as orbgpu_sim3_solve_device: the call waits for the
+ * stream on entry and between the preparation and the hypotheses (N is read back for P3); the hypotheses and the scan are
+ * enqueued and not waited for.  EINVAL: null pointers, a P10 violation, negative min_inliers / max_iterations /
+ * start_iteration / best_so_far / n_iterations; nothing is launched then.  EHIP without a device.  The batch form is one
+ * launch sequence (three kernels) for all candidates of a Relocalization call. */
+int orbgpu_pnp_solve_device(const orbgpu_pnp_problem *p, int32_t device_id, void *hip_stream);
+int orbgpu_pnp_solve_batch_device(int32_t n, const orbgpu_pnp_problem *problems, int32_t device_id, void *hip_stream);
+/* Host arrays, synchronises.  counts [n_hyp]; Tcw [16] the returned pose (= result->Tcw); inliers [n1] bytes of the
+ * returned pose (all 0 if none).  counts, Tcw and inliers may be NULL.  A set index outside [0, N) among the used
+ * hypotheses is EINVAL here, before anything is launched. */
+int orbgpu_pnp_solve(const orbgpu_pnp_problem *p, int32_t *counts, float *Tcw, uint8_t *inliers, orbgpu_pnp_result *result,
+                     int32_t device_id);
+/* As orbgpu_pnp_solve, but every hypothesis comes back: counts [n_hyp], Tcw [n_hyp][16], masks [n_hyp][(n1 + 63) / 64],
+ * refined_mask [(n1 + 63) / 64] (any may be NULL); hypotheses h >= n_use are zeros (orbgpu_shim::PnPsolverT). */
+int orbgpu_pnp_solve_all(const orbgpu_pnp_problem *p, int32_t *counts, float *Tcw, uint64_t *masks, uint64_t *refined_mask,
+                         orbgpu_pnp_result *result, int32_t device_id);
+/* Over the MapPoint table and an uploaded frame: kp_ids [n] = mnId of vpMapPointMatches[i] or -1.  The rows of P1 are built
+ * on the device: row i is valid iff its id is known and the point is not bad, Xw is the table's world position, kp and
+ * octave the frame's key point.  Ids the table does not know are not rows and are counted through
+ * orbgpu_mappoint_table_last_unknown, as orbgpu_pose_optimization_table does.  params: the scalar members of the problem
+ * and n_hyp / sets (a HOST array); n1 and the other array pointers are ignored (n1 = the frame's key points).  counts
+ * [n_hyp], Tcw [16] and inliers [n] as orbgpu_pnp_solve (any may be NULL).  A set index outside [0, N) is counted in
+ * n_bad_set, as in the device flavours (N depends on the table's bad flags).  Synchronises. */
+int orbgpu_pnp_solve_table(const orbgpu_frame *fr, orbgpu_mappoint_table *t, const int64_t *kp_ids,
+                           const orbgpu_pnp_problem *params, int32_t *counts, float *Tcw, uint8_t *inliers,
+                           orbgpu_pnp_result *result);
+
 
 /* LastFrame members read by SearchByProjection(CurrentFrame, LastFrame, th, bMono). */
 typedef struct {

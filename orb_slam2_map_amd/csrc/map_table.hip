@@ -291,6 +291,27 @@ namespace orbgpu {
 static int host_find(const orbgpu_mappoint_table *t, int64_t id) { return t->hash.find(id); }
 static uint32_t host_insert(orbgpu_mappoint_table *t, int64_t id, int row) { return t->hash.insert(id, row); }
 
+int pnp_check_host_problem(const orbgpu_pnp_problem &p);  // pnp.hip: P10 and the scalar arguments; array pointers are not looked at
+
+// P1's inputs for orbgpu_pnp_solve_table: key point j holds table row k2m[j] (or none); a bad point is no row
+__global__ void k_pnp_table_rows(int n, const int32_t *__restrict__ k2m, const float *__restrict__ world_pos,
+                                 const uint8_t *__restrict__ bad, const orbgpu_keypoint *__restrict__ kps,
+                                 uint8_t *__restrict__ valid, float *__restrict__ Xw, float *__restrict__ kp,
+                                 int32_t *__restrict__ octave)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n)
+        return;
+    const int row = k2m[j];
+    const bool ok = row >= 0 && !bad[row];
+    valid[j] = ok;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+        Xw[3 * (size_t)j + a] = ok ? world_pos[3 * (size_t)row + a] : 0.f;
+    kp[2 * (size_t)j] = kps[j].x, kp[2 * (size_t)j + 1] = kps[j].y;
+    octave[j] = kps[j].octave;
+}
+
 // row capacity `want` (the hash follows: id_table.h); existing rows are carried over on the device.  Without the lifecycle
 // lock: orbgpu_mappoint_table_create holds it.
 static int table_grow(orbgpu_mappoint_table *t, int want)
@@ -1016,6 +1037,82 @@ int orbgpu_pose_optimization_table(const orbgpu_frame *fr, orbgpu_mappoint_table
     *n_inliers = r.n_inliers;
     if (result)
         *result = r;
+    return ORBGPU_OK;
+}
+
+// PnPsolver over the table: the frame's associations arrive as ids, the id -> row lookup runs on the host copy of the
+// hash, the rows of P1 are gathered on the device (world position from the table's column, key point from the frame) and
+// the solver's device flavour runs on them (pnp.hip).
+int orbgpu_pnp_solve_table(const orbgpu_frame *fr, orbgpu_mappoint_table *t, const int64_t *kp_ids,
+                           const orbgpu_pnp_problem *params, int32_t *counts, float *Tcw, uint8_t *inliers,
+                           orbgpu_pnp_result *result)
+{
+    ORBGPU_REQUIRE(fr && t && params && result, "null argument");
+    ORBGPU_REQUIRE(fr->block.p, "the frame has not been uploaded yet");
+    ORBGPU_REQUIRE(fr->device_id == t->device_id, "frame and table live on different devices");
+    ORBGPU_REQUIRE(fr->n == 0 || kp_ids, "null key-point ids");
+    const int n = fr->n, H = params->n_hyp, ms = params->min_set;
+    orbgpu_pnp_problem d = *params;
+    d.n1 = n;
+    int rc = pnp_check_host_problem(d);  // P10 and the scalars, before anything is launched
+    if (rc != ORBGPU_OK)
+        return rc;
+    if ((rc = select_device(t->device_id)) != ORBGPU_OK)
+        return rc;
+    const size_t c1 = (size_t)std::max(n, 1), cH = (size_t)std::max(H, 1), words = ((size_t)n + 63) / 64, w1 = std::max<size_t>(words, 1);
+    Carver ci;
+    const size_t i_k2m = ci.take(4 * c1), i_sets = ci.take(4 * cH * (size_t)ms);
+    Carver cg;
+    const size_t g_valid = cg.take(c1), g_xw = cg.take(12 * c1), g_kp = cg.take(8 * c1), g_oct = cg.take(4 * c1);
+    const size_t r_beg = cg.off;
+    const size_t r_res = cg.take(sizeof(orbgpu_pnp_result)), r_cnt = cg.take(4 * cH), r_rm = cg.take(8 * w1);
+    const size_t r_end = cg.off;
+    const size_t g_tcw = cg.take(64 * cH), g_masks = cg.take(8 * cH * w1);
+    if ((rc = t->stage.reserve(std::max(ci.off, r_end - r_beg))) != ORBGPU_OK || (rc = t->d_stage.reserve(ci.off)) != ORBGPU_OK ||
+        (rc = t->g_block.reserve(cg.off)) != ORBGPU_OK)
+        return rc;
+    uint8_t *h = (uint8_t *)t->stage.p, *dv = t->d_stage.as<uint8_t>(), *g = t->g_block.as<uint8_t>();
+    int32_t *k2m = (int32_t *)(h + i_k2m);
+    int unknown = 0;
+    for (int j = 0; j < n; j++) {
+        k2m[j] = kp_ids[j] >= 0 ? host_find(t, kp_ids[j]) : -1;
+        unknown += kp_ids[j] >= 0 && k2m[j] < 0;
+    }
+    if (H > 0)
+        std::memcpy(h + i_sets, params->sets, 4 * (size_t)H * (size_t)ms);
+    t->last_unknown_list = 0, t->last_unknown_kp = unknown;
+    hipStream_t st = t->stream;
+    ORBGPU_HIP_TRY(hipMemcpyAsync(dv, h, ci.off, hipMemcpyHostToDevice, st));
+    orbgpu_device_frame_view fv;
+    frame_dev_view(fr, &fv);
+    if (n > 0) {
+        hipLaunchKernelGGL(k_pnp_table_rows, dim3((n + 255) / 256), dim3(256), 0, st, n, (const int32_t *)(dv + i_k2m),
+                           t->world_pos.as<float>(), t->bad.as<uint8_t>(), fv.kps, g + g_valid, (float *)(g + g_xw),
+                           (float *)(g + g_kp), (int32_t *)(g + g_oct));
+        ORBGPU_HIP_TRY(hipGetLastError());
+    }
+    d.valid = g + g_valid, d.Xw = (const float *)(g + g_xw), d.kp = (const float *)(g + g_kp), d.octave = (const int32_t *)(g + g_oct);
+    d.sets = (const int32_t *)(dv + i_sets);
+    d.counts = (int32_t *)(g + r_cnt), d.Tcw = (float *)(g + g_tcw), d.masks = (uint64_t *)(g + g_masks);
+    d.refined_mask = (uint64_t *)(g + r_rm), d.indices = nullptr, d.result = (orbgpu_pnp_result *)(g + r_res);
+    if ((rc = orbgpu_pnp_solve_batch_device(1, &d, t->device_id, st)) != ORBGPU_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    ORBGPU_HIP_TRY(hipMemcpyAsync(h, g + r_beg, r_end - r_beg, hipMemcpyDeviceToHost, st));
+    ORBGPU_HIP_TRY(hipStreamSynchronize(st));
+    orbgpu_pnp_result r;
+    std::memcpy(&r, h + (r_res - r_beg), sizeof(r));
+    if (counts && H > 0)
+        std::memcpy(counts, h + (r_cnt - r_beg), 4 * (size_t)H);
+    if (Tcw)
+        std::memcpy(Tcw, r.Tcw, sizeof(r.Tcw));
+    if (inliers) {
+        const uint64_t *mask = (const uint64_t *)(h + (r_rm - r_beg));
+        for (int i = 0; i < n; i++)
+            inliers[i] = (uint8_t)((mask[(size_t)i >> 6] >> (i & 63)) & 1u);
+    }
+    *result = r;
     return ORBGPU_OK;
 }
 

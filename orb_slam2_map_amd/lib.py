@@ -139,6 +139,27 @@ class Sim3Problem(C.Structure):
                 ("result", C.c_void_p)]
 
 
+class PnpResult(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n", "min_inliers", "max_its", "n_bad_index", "n_bad_set", "accepted", "n_inliers",
+                                         "best_inliers", "best_iteration", "iterations", "no_more", "pad_")] + \
+               [("Tcw", C.c_float * 16)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_[:11]}
+        d["Tcw"] = np.array(self.Tcw, np.float32).reshape(4, 4)
+        return d
+
+
+class PnpProblem(C.Structure):
+    _fields_ = [("n1", C.c_int32), ("n_hyp", C.c_int32), ("valid", C.c_void_p), ("Xw", C.c_void_p), ("kp", C.c_void_p),
+                ("octave", C.c_void_p), ("sets", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("level_sigma2", C.c_float * MAX_LEVELS), ("nlevels", C.c_int32), ("min_set", C.c_int32),
+                ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("epsilon", C.c_float), ("th2", C.c_float),
+                ("probability", C.c_double), ("start_iteration", C.c_int32), ("best_so_far", C.c_int32),
+                ("n_iterations", C.c_int32), ("pad_", C.c_int32), ("counts", C.c_void_p), ("Tcw", C.c_void_p),
+                ("masks", C.c_void_p), ("refined_mask", C.c_void_p), ("indices", C.c_void_p), ("result", C.c_void_p)]
+
+
 _LIB = None
 
 # every symbol include/orbgpu.h declares (checked by tests/test_abi.py against the header text)
@@ -167,6 +188,8 @@ ABI_SYMBOLS = [
     "orbgpu_pose_optimization_table", "orbgpu_pose_last_spills",
     "orbgpu_sim3_ransac_iterations", "orbgpu_sim3_solve_device", "orbgpu_sim3_solve_batch_device", "orbgpu_sim3_solve",
     "orbgpu_sim3_solve_all",
+    "orbgpu_pnp_ransac_parameters", "orbgpu_pnp_solve_device", "orbgpu_pnp_solve_batch_device", "orbgpu_pnp_solve",
+    "orbgpu_pnp_solve_all", "orbgpu_pnp_solve_table",
     "orbgpu_keyframe_db_create", "orbgpu_keyframe_db_destroy", "orbgpu_keyframe_db_clear", "orbgpu_keyframe_db_size",
     "orbgpu_keyframe_db_add", "orbgpu_keyframe_db_erase", "orbgpu_keyframe_db_set_covisibles", "orbgpu_keyframe_db_score",
     "orbgpu_keyframe_db_detect_loop", "orbgpu_keyframe_db_detect_reloc", "orbgpu_keyframe_db_last_query",
@@ -1023,6 +1046,139 @@ def sim3_solve_all(problem_host, device_id=0):
     check(L.orbgpu_sim3_solve_all(C.byref(q), _p(counts), _p(R), _p(t), _p(s), _p(T12), _p(masks), C.byref(res), device_id))
     out = res.as_dict()
     out.update(counts=counts[:H], R=R[:H], t=t[:H], s=s[:H], T12=T12[:H], masks=masks[:H, :words])
+    return out
+
+
+def pnp_ransac_parameters(n, probability, min_inliers, max_iterations, min_set, epsilon):
+    """(mRansacMinInliers, mRansacMaxIts) of PnPsolver::SetRansacParameters (orbgpu_pnp_ransac_parameters; host only)."""
+    L = lib()
+    L.orbgpu_pnp_ransac_parameters.argtypes = [C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                               C.c_void_p]
+    a, b = C.c_int32(), C.c_int32()
+    check(L.orbgpu_pnp_ransac_parameters(n, probability, min_inliers, max_iterations, min_set, epsilon, C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+_PNP_PTRS = ("valid", "Xw", "kp", "octave", "sets", "counts", "Tcw", "masks", "refined_mask", "indices", "result")
+
+
+def pnp_problem(p):
+    """A PnpProblem from a dict: n1, n_hyp, K (fx, fy, cx, cy), level_sigma2, min_set, min_inliers, max_iterations,
+    epsilon, th2, probability, optional nlevels / start_iteration / best_so_far / n_iterations, and the array pointers
+    of include/orbgpu.h as integers (device or host addresses; missing ones are NULL)."""
+    q = PnpProblem()
+    q.n1, q.n_hyp = int(p["n1"]), int(p["n_hyp"])
+    for k in _PNP_PTRS:
+        setattr(q, k, p.get(k) or None)
+    q.fx, q.fy, q.cx, q.cy = (float(k) for k in p["K"])
+    sg = np.asarray(p["level_sigma2"], np.float32)
+    q.nlevels = int(p.get("nlevels", len(sg)))
+    for l in range(min(len(sg), MAX_LEVELS)):
+        q.level_sigma2[l] = float(sg[l])
+    q.min_set, q.min_inliers, q.max_iterations = int(p["min_set"]), int(p["min_inliers"]), int(p["max_iterations"])
+    q.epsilon, q.th2, q.probability = float(p["epsilon"]), float(p["th2"]), float(p["probability"])
+    q.start_iteration, q.best_so_far = int(p.get("start_iteration", 0)), int(p.get("best_so_far", 0))
+    q.n_iterations = int(p.get("n_iterations", 0))
+    return q
+
+
+def pnp_solve_batch_device(problems, stream=0, device_id=0):
+    """All candidates of a Tracking::Relocalization call in one launch sequence (orbgpu_pnp_solve_batch_device).
+    problems: dicts as pnp_problem takes them, with device pointers.  Waits once for the stream (N is read back for the
+    RANSAC parameters); the hypotheses and the acceptance scan are enqueued and not waited for."""
+    arr = (PnpProblem * max(len(problems), 1))()
+    for k, p in enumerate(problems):
+        arr[k] = pnp_problem(p)
+    L = lib()
+    L.orbgpu_pnp_solve_batch_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    check(L.orbgpu_pnp_solve_batch_device(len(problems), arr, device_id, stream))
+
+
+def pnp_solve_device(problem, stream=0, device_id=0):
+    """One candidate (orbgpu_pnp_solve_device); see pnp_solve_batch_device."""
+    q = pnp_problem(problem)
+    L = lib()
+    L.orbgpu_pnp_solve_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    check(L.orbgpu_pnp_solve_device(C.byref(q), device_id, stream))
+
+
+def _pnp_host_problem(sc, keep, **over):
+    """PnpProblem over the host arrays of a scene dict (valid, Xw, kp, octave, sets, K, level_sigma2, min_set, ...)"""
+    v = np.ascontiguousarray(sc["valid"], np.uint8)
+    n1 = len(v)
+    x = np.ascontiguousarray(sc["Xw"], np.float32).reshape(-1, 3)
+    kp = np.ascontiguousarray(sc["kp"], np.float32).reshape(-1, 2)
+    o = np.ascontiguousarray(sc["octave"], np.int32)
+    if not (len(x) == len(kp) == len(o) == n1):
+        raise ValueError("one entry per key point expected")
+    st = np.ascontiguousarray(sc["sets"], np.int32).reshape(-1, int(sc["min_set"]))
+    keep += [v, x, kp, o, st]
+    p = {k: sc[k] for k in ("K", "level_sigma2", "min_set", "min_inliers", "max_iterations", "epsilon", "th2", "probability")}
+    for k in ("nlevels", "start_iteration", "best_so_far", "n_iterations"):
+        if k in sc:
+            p[k] = sc[k]
+    p.update(n1=n1, n_hyp=len(st), valid=v.ctypes.data, Xw=x.ctypes.data, kp=kp.ctypes.data, octave=o.ctypes.data,
+             sets=st.ctypes.data)
+    p.update(over)
+    return pnp_problem(p)
+
+
+def pnp_solve(sc, device_id=0, **over):
+    """PnPsolver over host arrays (orbgpu_pnp_solve).  sc: a dict with valid [n1], Xw [n1][3], kp [n1][2], octave [n1],
+    sets [H][min_set], K, level_sigma2, min_set, min_inliers, max_iterations, epsilon, th2, probability (and optionally
+    start_iteration, best_so_far, n_iterations).  Returns a dict: the result record's fields, counts [H], inliers [n1]."""
+    keep = []
+    q = _pnp_host_problem(sc, keep, **over)
+    H, n1 = q.n_hyp, q.n1
+    counts, T = np.zeros(max(H, 1), np.int32), np.zeros((4, 4), np.float32)
+    inl, res = np.zeros(max(n1, 1), np.uint8), PnpResult()
+    L = lib()
+    L.orbgpu_pnp_solve.argtypes = [C.c_void_p] * 5 + [C.c_int32]
+    check(L.orbgpu_pnp_solve(C.byref(q), _p(counts), _p(T), _p(inl), C.byref(res), device_id))
+    out = res.as_dict()
+    out.update(counts=counts[:H], inliers=inl[:n1], Tcw_out=T)
+    return out
+
+
+def pnp_solve_all(sc, device_id=0, **over):
+    """Every hypothesis of one candidate over host arrays (orbgpu_pnp_solve_all); sc as pnp_solve takes it.  Returns a
+    dict: the result record's fields, counts [H], Tcw_all [H][4][4], masks [H][words], refined_mask [words]."""
+    keep = []
+    q = _pnp_host_problem(sc, keep, **over)
+    H, words = q.n_hyp, (q.n1 + 63) // 64
+    counts, T = np.zeros(max(H, 1), np.int32), np.zeros((max(H, 1), 4, 4), np.float32)
+    masks, rm, res = np.zeros((max(H, 1), max(words, 1)), np.uint64), np.zeros(max(words, 1), np.uint64), PnpResult()
+    L = lib()
+    L.orbgpu_pnp_solve_all.argtypes = [C.c_void_p] * 6 + [C.c_int32]
+    check(L.orbgpu_pnp_solve_all(C.byref(q), _p(counts), _p(T), _p(masks), _p(rm), C.byref(res), device_id))
+    out = res.as_dict()
+    out.update(counts=counts[:H], Tcw_all=T[:H], masks=masks[:H, :words], refined_mask=rm[:words])
+    return out
+
+
+def pnp_solve_table(dframe, table, kp_ids, sc):
+    """PnPsolver over the MapPoint table (orbgpu_pnp_solve_table): dframe a DeviceFrame, kp_ids [n] = mnId of the key
+    point's map point or -1, sc a dict with sets [H][min_set], K, level_sigma2 and the RANSAC parameters as pnp_solve
+    takes them.  Returns a dict: the result record's fields, counts [H], inliers [n]."""
+    n = dframe.n
+    ids = np.ascontiguousarray(kp_ids, np.int64)
+    if len(ids) != n:
+        raise ValueError("kp_ids must have one entry per key point")
+    st = np.ascontiguousarray(sc["sets"], np.int32).reshape(-1, int(sc["min_set"]))
+    p = {k: sc[k] for k in ("K", "level_sigma2", "min_set", "min_inliers", "max_iterations", "epsilon", "th2", "probability")}
+    for k in ("nlevels", "start_iteration", "best_so_far", "n_iterations"):
+        if k in sc:
+            p[k] = sc[k]
+    p.update(n1=0, n_hyp=len(st), sets=st.ctypes.data)
+    q = pnp_problem(p)
+    H = len(st)
+    counts, T = np.zeros(max(H, 1), np.int32), np.zeros((4, 4), np.float32)
+    inl, res = np.zeros(max(n, 1), np.uint8), PnpResult()
+    L = lib()
+    L.orbgpu_pnp_solve_table.argtypes = [C.c_void_p] * 8
+    check(L.orbgpu_pnp_solve_table(dframe.h, table.h, _p(ids), C.byref(q), _p(counts), _p(T), _p(inl), C.byref(res)))
+    out = res.as_dict()
+    out.update(counts=counts[:H], inliers=inl[:n], Tcw_out=T)
     return out
 
 

@@ -1229,6 +1229,187 @@ template <typename KeyFrameT, typename MapPointT> class Sim3SolverT {
 };
 
 // --------------------------------------------------------------------------------------------
+// PnPsolver (reference include/PnPsolver.h, src/PnPsolver.cc): the pose of a relocalisation candidate.  The conventions are
+// P1-P10 of include/orbgpu.h.
+// --------------------------------------------------------------------------------------------
+// The draw of PnPsolver::iterate (:188-201) replayed for `iterations` iterations over n correspondences, min_set indices
+// each: it overwrites vAvailableIndices[idx], not [randi], so one index can be drawn twice within a set.  random_int(min,
+// max) is called min_set times per iteration.  n < min_set and a random_int outside [min, max] are refused with
+// std::invalid_argument, as tests/pnp_model.py refuses them.
+template <typename RandomInt>
+inline std::vector<int32_t> PnPSampleSets(int n, int iterations, int min_set, RandomInt random_int)
+{
+    if (min_set < 1 || n < min_set)
+        throw std::invalid_argument("PnPSampleSets: fewer correspondences than the minimal set");
+    std::vector<int32_t> out((size_t)std::max(iterations, 0) * (size_t)min_set, 0);
+    std::vector<int32_t> avail((size_t)n);
+    for (int it = 0; it < iterations; it++) {
+        for (int i = 0; i < n; i++)
+            avail[i] = i;
+        int size = n;
+        for (int i = 0; i < min_set; i++) {
+            const int randi = random_int(0, size - 1);
+            if (randi < 0 || randi >= size)
+                throw std::invalid_argument("PnPSampleSets: RandomInt outside [min, max]");
+            const int idx = avail[randi];
+            out[(size_t)it * min_set + i] = idx;
+            avail[idx] = avail[size - 1];
+            size--;
+        }
+    }
+    return out;
+}
+
+// FrameT needs mvKeysUn, mvLevelSigma2, fx, fy, cx, cy; MapPointT isBad().  world_pos(pMP) returns 3 floats (valid during
+// the constructor); random_int(min, max) stands for DUtils::Random::RandomInt.  The acceptance scan (P8) runs in the
+// library; this class carries its state (mnIterations, mnBestInliers, the best record's pose and inliers) between calls.
+// Every iterate(n, ...) draws the sets its scan can reach and that are not drawn yet -- up to max(max_its, mnIterations + n),
+// in the reference's order over the one RandomInt stream, so a scan that runs past what was drawn gets further sets --
+// and asks the library once (orbgpu_pnp_solve_all, resumed at (mnIterations, mnBestInliers)).  cv::Mat stays
+// outside: iterate returns the 16 floats of Tcw (valid until the next call) or nullptr.
+template <typename FrameT, typename MapPointT> class PnPsolverT {
+  public:
+    // (problem, counts, Tcw [H][16], masks, refined_mask, result) -> status: orbgpu_pnp_solve_all on this device
+    typedef std::function<int(const orbgpu_pnp_problem *, int32_t *, float *, uint64_t *, uint64_t *, orbgpu_pnp_result *)> Solver;
+
+    template <typename WorldPos, typename RandomInt>
+    PnPsolverT(const FrameT &F, const std::vector<MapPointT *> &vpMapPointMatches, WorldPos world_pos, RandomInt random_int,
+               int device_id = 0)
+        : random_int_(random_int)
+    {
+        solver_ = [device_id](const orbgpu_pnp_problem *p, int32_t *counts, float *Tcw, uint64_t *masks, uint64_t *refined,
+                              orbgpu_pnp_result *r) { return orbgpu_pnp_solve_all(p, counts, Tcw, masks, refined, r, device_id); };
+        n1_ = (int)vpMapPointMatches.size();
+        valid_.assign((size_t)n1_, 0), octave_.assign((size_t)n1_, 0);
+        xw_.assign(3 * (size_t)n1_, 0.f), kp_.assign(2 * (size_t)n1_, 0.f);
+        nlevels_ = (int)std::min(F.mvLevelSigma2.size(), (size_t)ORBGPU_MAX_LEVELS);
+        N = 0;
+        for (int i = 0; i < n1_; i++) {
+            MapPointT *pMP = vpMapPointMatches[i];
+            if (!pMP || pMP->isBad())
+                continue;
+            valid_[i] = 1;
+            octave_[i] = F.mvKeysUn[i].octave;
+            kp_[2 * (size_t)i] = F.mvKeysUn[i].pt.x, kp_[2 * (size_t)i + 1] = F.mvKeysUn[i].pt.y;
+            std::memcpy(&xw_[3 * (size_t)i], world_pos(pMP), 12);
+            if (octave_[i] >= 0 && octave_[i] < nlevels_)
+                N++;  // P1: the rows the library keeps
+        }
+        std::memset(&p_, 0, sizeof(p_));
+        p_.fx = F.fx, p_.fy = F.fy, p_.cx = F.cx, p_.cy = F.cy;
+        for (int l = 0; l < nlevels_; l++)
+            p_.level_sigma2[l] = F.mvLevelSigma2[l];
+        SetRansacParameters();
+    }
+
+    // A fresh search: the iteration count, the best record and the drawn sets are reset.
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4,
+                             float epsilon = 0.4f, float th2 = 5.991f)
+    {
+        int32_t mi = 0, its = 1;
+        check(orbgpu_pnp_ransac_parameters(N, probability, minInliers, maxIterations, minSet, epsilon, &mi, &its),
+              "PnPsolver::SetRansacParameters");
+        mRansacMinInliers = mi, mRansacMaxIts = its, mRansacMinSet = minSet;
+        p_.probability = probability, p_.min_inliers = minInliers, p_.max_iterations = maxIterations, p_.min_set = minSet;
+        p_.epsilon = epsilon, p_.th2 = th2;
+        mnIterations = 0, mnBestInliers = 0;
+        sets_.clear(), best_mask_.clear();
+        have_best_ = false;
+    }
+
+    const float *iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers)
+    {
+        bNoMore = false;
+        vbInliers.clear();
+        nInliers = 0;
+        if (N < mRansacMinInliers || N < mRansacMinSet) {
+            bNoMore = true;
+            return nullptr;
+        }
+        const size_t words = ((size_t)n1_ + 63) / 64;
+        // every set the scan of this call can reach: the reference's loop runs while mnIterations < max_its OR fewer than
+        // nIterations were done in this call
+        const long long reach = std::max<long long>(mRansacMaxIts, (long long)mnIterations + std::max(nIterations, 0));
+        const int H = (int)std::min<long long>(reach, 4096);  // P10; a search that long ends without bNoMore
+        Draw(H);
+        p_.n1 = n1_, p_.n_hyp = H;
+        p_.valid = valid_.data(), p_.Xw = xw_.data(), p_.kp = kp_.data(), p_.octave = octave_.data(), p_.sets = sets_.data();
+        p_.nlevels = nlevels_;
+        p_.start_iteration = mnIterations, p_.best_so_far = mnBestInliers, p_.n_iterations = std::max(nIterations, 0);
+        counts_.assign((size_t)H, 0), tcw_.assign(16 * (size_t)H, 0.f), masks_.assign((size_t)H * words, 0);
+        refined_.assign(std::max<size_t>(words, 1), 0);
+        orbgpu_pnp_result r;
+        check(solver_(&p_, counts_.data(), tcw_.data(), masks_.data(), refined_.data(), &r), "PnPsolver");
+        mnIterations = r.iterations, mnBestInliers = r.best_inliers;
+        if (r.best_iteration >= 0) {  // mBestTcw, mvbBestInliers
+            std::memcpy(best_tcw_, &tcw_[16 * (size_t)r.best_iteration], 64);
+            best_mask_.assign(masks_.begin() + (ptrdiff_t)((size_t)r.best_iteration * words),
+                              masks_.begin() + (ptrdiff_t)(((size_t)r.best_iteration + 1) * words));
+            have_best_ = true;
+        }
+        if (r.accepted >= 0) {
+            nInliers = r.n_inliers;
+            Expand(refined_, vbInliers);
+            std::memcpy(out_tcw_, r.Tcw, 64);
+            return out_tcw_;
+        }
+        if (r.no_more) {
+            bNoMore = true;
+            if (have_best_ && mnBestInliers >= mRansacMinInliers) {
+                nInliers = mnBestInliers;
+                Expand(best_mask_, vbInliers);
+                std::memcpy(out_tcw_, best_tcw_, 64);
+                return out_tcw_;
+            }
+        }
+        return nullptr;
+    }
+
+    const float *find(std::vector<bool> &vbInliers, int &nInliers)
+    {
+        bool bFlag;
+        return iterate(mRansacMaxIts, bFlag, vbInliers, nInliers);
+    }
+
+    int NumCorrespondences() const { return N; }
+    int MinInliers() const { return mRansacMinInliers; }
+    int MaxIterations() const { return mRansacMaxIts; }
+    int Iterations() const { return mnIterations; }
+    int BestInliers() const { return mnBestInliers; }
+    const std::vector<int32_t> &Sets() const { return sets_; }
+    // a test serves the calls from recorded counts without a device
+    void SetSolver(Solver s) { solver_ = s; }
+
+  private:
+    void Draw(int H)
+    {
+        const int have = (int)(sets_.size() / (size_t)mRansacMinSet);
+        if (H <= have)
+            return;
+        const std::vector<int32_t> more = PnPSampleSets(N, H - have, mRansacMinSet, random_int_);
+        sets_.insert(sets_.end(), more.begin(), more.end());
+    }
+    void Expand(const std::vector<uint64_t> &mask, std::vector<bool> &vbInliers) const
+    {
+        vbInliers.assign((size_t)n1_, false);
+        for (int i = 0; i < n1_; i++)
+            vbInliers[i] = (mask[(size_t)i >> 6] >> (i & 63)) & 1u;
+    }
+
+    std::function<int(int, int)> random_int_;
+    Solver solver_;
+    int n1_ = 0, N = 0, nlevels_ = 0;
+    int mRansacMinInliers = 8, mRansacMaxIts = 300, mRansacMinSet = 4, mnIterations = 0, mnBestInliers = 0;
+    bool have_best_ = false;
+    float best_tcw_[16] = {0}, out_tcw_[16] = {0};
+    orbgpu_pnp_problem p_;
+    std::vector<uint8_t> valid_;
+    std::vector<int32_t> octave_, sets_, counts_;
+    std::vector<float> xw_, kp_, tcw_;
+    std::vector<uint64_t> masks_, refined_, best_mask_;
+};
+
+// --------------------------------------------------------------------------------------------
 // KeyFrameDatabase (reference include/KeyFrameDatabase.h:45-75, src/KeyFrameDatabase.cc) on the device
 // (orbgpu_keyframe_db_*): add / erase / clear / DetectLoopCandidates / DetectRelocalizationCandidates with the
 // reference's signatures, candidates in the reference's order.  KeyFrameT needs mnId, mBowVec (DBoW2::BowVector: an
