@@ -752,6 +752,117 @@ int orbgpu_sim3_solve(const orbgpu_sim3_problem *p, int32_t *counts, float *R, f
 int orbgpu_sim3_solve_all(const orbgpu_sim3_problem *p, int32_t *counts, float *R, float *t, float *s, float *T12,
                           uint64_t *masks, orbgpu_sim3_result *result, int32_t device_id);
 
+/* ---- Optimizer::OptimizeSim3 (Optimizer.cc:1079-1236): 7-DoF refinement of a loop candidate's Sim3 on the device -----------
+ * The fourth of the five steps of LoopClosing::ComputeSim3 (LoopClosing.cc:326-336), between orbgpu_search_by_sim3 and
+ * orbgpu_search_by_projection_sim3: ONE Sim3 vertex, two reprojection edges per correspondence (map point of key frame 2
+ * into image 1, map point of key frame 1 into image 2), the map points fixed.  g2o is not part of the reference tree: its
+ * behaviour is restated, NOT read ("vs CPU restatement; g2o boundary unpinned"); tests/sim3opt_model.py is the float64
+ * restatement every result is compared with.  Conventions O1-O9, all arithmetic IEEE double and
+ * unfused unless a float is named; three-term sums run left to right:
+ *   O1 rows (:1099-1137)  row i in [0, n1) is a correspondence iff valid[i] != 0 (the caller's verdict on: vpMatches1[i]
+ *                         exists, both map points exist and are not bad, i2 >= 0) and both octaves lie in [0, nlevels); a
+ *                         valid row with an octave outside is not a correspondence and is counted in n_bad_index (the
+ *                         reference reads out of range).  Correspondences keep index order: N = nCorrespondences.
+ *   O2 points             X1c = R1w Xw1 + t1w, X2c = R2w Xw2 + t2w in FLOAT exactly as H2 of the Sim3Solver (products summed
+ *                         left to right, then one add), then widened to double (Converter::toVector3d)
+ *   O3 edges              S X = s (R X) + t with R = the matrix of the state's quaternion; S^-1 = (r', R'((-1/s) t), 1/s);
+ *                         cam(X) = ((x / z) fx + cx, (y / z) fy + cy);  e12 = obs1 - cam1(S12 X2c),
+ *                         e21 = obs2 - cam2(S12^-1 X1c); obs1 = mvKeysUn1[i].pt, obs2 = mvKeysUn2[i2].pt as floats widened;
+ *                         information w = (double)inv_level_sigma2[octave], chi2 = w (e0 e0 + e1 e1); both edges carry a
+ *                         Huber kernel with delta = (double)(float)sqrt(th2) (sqrt of the float, :1095) in BOTH stages;
+ *                         no depth-sign test; non-finite values follow IEEE through the steps below
+ *   O4 state, update      state (q, t, s): q = quat_from_matrix((double)R12) normalised once on entry (w >= 0, unit norm),
+ *                         t and s the float inputs widened.  S <- exp(x) S: q = q_x q, t = s_x (R_x t) + t_x, s = s_x s with
+ *                         R_x the matrix of q_x; NO renormalisation afterwards (g2o's Sim3 does none).  With fix_scale
+ *                         x[6] is set to 0 before exp.
+ *   O5 exp(x)             x = (omega, upsilon, sigma), theta = |omega|, Om = [omega]x, s_x = exp(sigma), eps = 1e-5:
+ *                           |sigma| <  eps, theta <  eps: C = 1, A = 1/2, B = 1/6, R = (I + Om) + Om Om
+ *                           |sigma| <  eps, theta >= eps: C = 1, A = (1 - cos theta) / theta^2, B = (theta - sin theta) / theta^3,
+ *                                                         R = (I + (sin theta / theta) Om) + ((1 - cos theta) / theta^2) Om Om
+ *                           |sigma| >= eps, theta <  eps: C = (s_x - 1) / sigma, A = ((sigma - 1) s_x + 1) / sigma^2,
+ *                                                         B = ((sigma^2 / 2 - sigma + 1) s_x) / sigma^3, R as in the first
+ *                           |sigma| >= eps, theta >= eps: C as in the third, R as in the second; a = s_x sin theta,
+ *                                                         b = s_x cos theta, c = theta^2 + sigma^2,
+ *                                                         A = (a sigma + (1 - b) theta) / (theta c),
+ *                                                         B = (C - ((b - 1) sigma + a theta) / c) / theta^2
+ *                         t_x = ((A Om + B Om Om) + C I) upsilon, q_x = quat_from_matrix(R) (not normalised).  These are the
+ *                         branches as g2o publishes them, recalled, not read.
+ *   O6 Jacobian           NUMERIC, as g2o differentiates these two edge types (BaseBinaryEdge::linearizeOplus):
+ *                         d e / d x_k = (e(exp(+d 1_k) S) - e(exp(-d 1_k) S)) (1 / (2 d)), d = 1e-9, k = 0..6, through O4's
+ *                         update -- with fix_scale column 6 is exactly 0.  The point vertices are fixed.
+ *   O7 optimize(k)        the Levenberg-Marquardt loop of orbgpu_pose_optimization with 7 unknowns: H = sum J'(rho1 w)J,
+ *                         b = -sum J'(rho1 w)e over the active edges; lambda0 = 1e-5 max diag H, nu = 2 at the first
+ *                         iteration of EACH optimize call; per iteration at most 10 trials of (H + lambda I) x = b by LL'
+ *                         (a pivot that is not > 0 fails the trial); rho = (chi - chi') / (x'(lambda x + b) + 1e-3);
+ *                         acceptance, lambda / nu rule and stop conditions as there; at most k iterations
+ *   O8 stages (:1181-1234)  stage 1: optimize(5) over all 2N edges, then every correspondence is classified at the stage's
+ *                         final KEPT state: bad iff chi2_12 > (double)th2 || chi2_21 > (double)th2 (compared in double);
+ *                         bad correspondences are cleared in inlier[], their edges leave, nBad counts them.
+ *                         N - nBad < 10: returns 0, S12 out = the entry state, inlier[] keeps the clearing, stages = 1.
+ *                         Stage 2: optimize(nBad > 0 ? 10 : 5) over the remaining edges from the stage-1 state, then the
+ *                         remaining correspondences are classified again; n_inliers = those that pass, S12 out = the final
+ *                         state.  N = 0: returns 0, nothing is written to inlier[], stages = 0.
+ *   O9 outputs            R12_d = the matrix of q, t12_d, s12_d; R12 / t12 / s12 their entry-wise float casts;
+ *                         T12 = Converter::toCvMat(Sim3): (float)(s R), (float)t, last row 0 0 0 1;
+ *                         Scw (LoopClosing.cc:334-336) = toCvMat(S12 Smw) with Smw = (quat_normalize(quat_from_matrix(
+ *                         (double)R2w)), (double)t2w, 1): the Scw argument of orbgpu_search_by_projection_sim3.
+ * Sums over edges run in a fixed order (lane l takes correspondences l, l + 256, ..., e12 before e21, then a fixed tree; no
+ * floating-point atomics): the same problem gives the same bytes on every run, alone or anywhere in a batch, and agrees
+ * with the model to a tolerance, not bit for bit. */
+typedef struct orbgpu_sim3_opt_result { /* device or host, 8-byte aligned */
+    double R12_d[9], t12_d[3], s12_d; /* the refined Sim3 (O9) */
+    float R12[9], t12[3], s12;        /* = (float) of the doubles entry by entry: what orbgpu_search_by_sim3 takes */
+    float T12[16];                    /* Converter::toCvMat(g2oS12) */
+    float Scw[16];                    /* toCvMat(S12 Smw) */
+    int32_t n_correspondences;        /* N (O1) */
+    int32_t n_bad;                    /* nBad of stage 1 */
+    int32_t n_inliers;                /* the return value */
+    int32_t stages;                   /* 0 (N = 0), 1 (fewer than 10 left after stage 1) or 2 */
+    int32_t iterations, trials;       /* diagnostics: LM iterations and trials over both stages */
+    int32_t n_bad_index;              /* valid rows with an octave outside [0, nlevels): not correspondences */
+} orbgpu_sim3_opt_result;
+
+/* The array pointers are DEVICE pointers for the *_device entry points and HOST pointers for orbgpu_sim3_optimize; the
+ * row arrays are those of orbgpu_sim3_problem, so a ComputeSim3 caller passes the same buffers on. */
+typedef struct orbgpu_sim3_opt_problem {
+    int32_t n1;             /* vpMatches1.size() */
+    int32_t nlevels;
+    const uint8_t *valid;   /* [n1] (O1) */
+    const float *Xw1;       /* [n1][3] world position of KF1's map point i (read for valid rows only) */
+    const float *Xw2;       /* [n1][3] world position of vpMatches1[i] */
+    const int32_t *octave1; /* [n1] mvKeysUn1[i].octave */
+    const int32_t *octave2; /* [n1] mvKeysUn2[i2].octave */
+    const float *kp1_xy;    /* [n1][2] mvKeysUn1[i].pt */
+    const float *kp2_xy;    /* [n1][2] mvKeysUn2[i2].pt, gathered by the caller */
+    float T1w[16], T2w[16]; /* key-frame poses, 4x4 row-major */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    float inv_level_sigma2[ORBGPU_MAX_LEVELS]; /* mvInvLevelSigma2 */
+    float R12[9], t12[3], s12; /* the Sim3 on entry (x1 = s12 R12 x2 + t12) */
+    float th2;
+    int32_t fix_scale;
+    int32_t pad_;
+    /* outputs (orbgpu_sim3_optimize ignores them) */
+    uint8_t *inlier;        /* [n1]: 1 for a correspondence that stays, 0 for a cleared one; other rows are not written */
+    orbgpu_sim3_opt_result *result;
+} orbgpu_sim3_opt_problem;
+
+/* Enqueued on hip_stream, not synchronised, no host round trip; the problem structs are read before the call returns.
+ * Calls of one host thread share a workspace and must be ordered on one stream.  EINVAL without touching the device: null
+ * pointers, n < 0, n1 outside [0, 65536], nlevels outside [1, ORBGPU_MAX_LEVELS]; EHIP without a device.  An octave
+ * outside [0, nlevels) is never read through (O1).  The batch form is ONE launch, one workgroup per candidate. */
+int orbgpu_sim3_optimize_device(const orbgpu_sim3_opt_problem *p, int32_t device_id, void *hip_stream);
+int orbgpu_sim3_optimize_batch_device(int32_t n, const orbgpu_sim3_opt_problem *problems, int32_t device_id,
+                                      void *hip_stream);
+/* Host arrays, synchronises: inlier [n1] in/out (written for correspondences only; may be NULL when n1 == 0), n_inliers
+ * the return value of OptimizeSim3, result may be NULL.  Runs on a stream of the workspace's own and waits for the whole
+ * device on entry, like the other host flavours. */
+int orbgpu_sim3_optimize(const orbgpu_sim3_opt_problem *p, uint8_t *inlier, int32_t *n_inliers,
+                         orbgpu_sim3_opt_result *result, int32_t device_id);
+/* Diagnostic: problems of the calling thread's most recent Sim3 optimisation on device_id whose correspondences did not
+ * fit the workgroup's LDS and went through the global-memory spill (ORBGPU_DEBUG_SIM3OPT_LDS_PAIRS=<k> lowers the limit
+ * for tests).  Synchronises the device. */
+int orbgpu_sim3_opt_last_spills(int32_t device_id, int32_t *problems_spilled);
+
 /* ---- PnPsolver (PnPsolver.cc, EPnP + RANSAC): the pose of a relocalisation candidate on the device ----------------------
  * The third of the six steps Tracking::Relocalization runs per candidate key frame (Tracking.cc:1645-1810), between
  * orbgpu_search_by_bow and orbgpu_pose_optimization.  All hypotheses of a candidate are evaluated at once, one wave each;

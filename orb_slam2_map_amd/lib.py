@@ -139,6 +139,31 @@ class Sim3Problem(C.Structure):
                 ("result", C.c_void_p)]
 
 
+class Sim3OptResult(C.Structure):
+    _fields_ = [("R12_d", C.c_double * 9), ("t12_d", C.c_double * 3), ("s12_d", C.c_double), ("R12", C.c_float * 9),
+                ("t12", C.c_float * 3), ("s12", C.c_float), ("T12", C.c_float * 16), ("Scw", C.c_float * 16)] + \
+               [(k, C.c_int32) for k in ("n_correspondences", "n_bad", "n_inliers", "stages", "iterations", "trials",
+                                         "n_bad_index")]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_[8:]}
+        d.update(R12_d=np.array(self.R12_d, np.float64).reshape(3, 3), t12_d=np.array(self.t12_d, np.float64),
+                 s12_d=np.float64(self.s12_d), R12=np.array(self.R12, np.float32).reshape(3, 3),
+                 t12=np.array(self.t12, np.float32), s12=np.float32(self.s12),
+                 T12=np.array(self.T12, np.float32).reshape(4, 4), Scw=np.array(self.Scw, np.float32).reshape(4, 4))
+        return d
+
+
+class Sim3OptProblem(C.Structure):
+    _fields_ = [("n1", C.c_int32), ("nlevels", C.c_int32), ("valid", C.c_void_p), ("Xw1", C.c_void_p), ("Xw2", C.c_void_p),
+                ("octave1", C.c_void_p), ("octave2", C.c_void_p), ("kp1_xy", C.c_void_p), ("kp2_xy", C.c_void_p),
+                ("T1w", C.c_float * 16), ("T2w", C.c_float * 16), ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float),
+                ("cy1", C.c_float), ("fx2", C.c_float), ("fy2", C.c_float), ("cx2", C.c_float), ("cy2", C.c_float),
+                ("inv_level_sigma2", C.c_float * MAX_LEVELS), ("R12", C.c_float * 9), ("t12", C.c_float * 3),
+                ("s12", C.c_float), ("th2", C.c_float), ("fix_scale", C.c_int32), ("pad_", C.c_int32),
+                ("inlier", C.c_void_p), ("result", C.c_void_p)]
+
+
 class PnpResult(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n", "min_inliers", "max_its", "n_bad_index", "n_bad_set", "accepted", "n_inliers",
                                          "best_inliers", "best_iteration", "iterations", "no_more", "pad_")] + \
@@ -188,6 +213,8 @@ ABI_SYMBOLS = [
     "orbgpu_pose_optimization_table", "orbgpu_pose_last_spills",
     "orbgpu_sim3_ransac_iterations", "orbgpu_sim3_solve_device", "orbgpu_sim3_solve_batch_device", "orbgpu_sim3_solve",
     "orbgpu_sim3_solve_all",
+    "orbgpu_sim3_optimize", "orbgpu_sim3_optimize_device", "orbgpu_sim3_optimize_batch_device",
+    "orbgpu_sim3_opt_last_spills",
     "orbgpu_pnp_ransac_parameters", "orbgpu_pnp_solve_device", "orbgpu_pnp_solve_batch_device", "orbgpu_pnp_solve",
     "orbgpu_pnp_solve_all", "orbgpu_pnp_solve_table",
     "orbgpu_keyframe_db_create", "orbgpu_keyframe_db_destroy", "orbgpu_keyframe_db_clear", "orbgpu_keyframe_db_size",
@@ -1047,6 +1074,92 @@ def sim3_solve_all(problem_host, device_id=0):
     out = res.as_dict()
     out.update(counts=counts[:H], R=R[:H], t=t[:H], s=s[:H], T12=T12[:H], masks=masks[:H, :words])
     return out
+
+
+_SIM3OPT_PTRS = ("valid", "Xw1", "Xw2", "octave1", "octave2", "kp1_xy", "kp2_xy", "inlier", "result")
+
+
+def sim3_opt_problem(p):
+    """A Sim3OptProblem from a dict: n1, T1w, T2w (4x4), K1, K2 (fx, fy, cx, cy), inv_level_sigma2, R12 (3x3), t12, s12,
+    th2, fix_scale, optional nlevels, and the array pointers of include/orbgpu.h as integers (device or host addresses;
+    missing ones are NULL)."""
+    q = Sim3OptProblem()
+    q.n1 = int(p["n1"])
+    for k in _SIM3OPT_PTRS:
+        setattr(q, k, p.get(k) or None)
+    q.T1w[:] = np.asarray(p["T1w"], np.float32).reshape(16).tolist()
+    q.T2w[:] = np.asarray(p["T2w"], np.float32).reshape(16).tolist()
+    q.fx1, q.fy1, q.cx1, q.cy1 = (float(k) for k in p["K1"])
+    q.fx2, q.fy2, q.cx2, q.cy2 = (float(k) for k in p["K2"])
+    sg = np.asarray(p["inv_level_sigma2"], np.float32)
+    q.nlevels = int(p.get("nlevels", len(sg)))
+    for l in range(min(len(sg), MAX_LEVELS)):
+        q.inv_level_sigma2[l] = float(sg[l])
+    q.R12[:] = np.asarray(p["R12"], np.float32).reshape(9).tolist()
+    q.t12[:] = np.asarray(p["t12"], np.float32).reshape(3).tolist()
+    q.s12, q.th2, q.fix_scale = float(np.float32(p["s12"])), float(np.float32(p["th2"])), int(bool(p["fix_scale"]))
+    return q
+
+
+def sim3_optimize_batch_device(problems, stream=0, device_id=0):
+    """All candidates of a LoopClosing::ComputeSim3 call in ONE launch (orbgpu_sim3_optimize_batch_device); enqueued, not
+    synchronised.  problems: dicts as sim3_opt_problem takes them, with device pointers; result holds a Sim3OptResult."""
+    arr = (Sim3OptProblem * max(len(problems), 1))()
+    for k, p in enumerate(problems):
+        arr[k] = sim3_opt_problem(p)
+    L = lib()
+    L.orbgpu_sim3_optimize_batch_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    check(L.orbgpu_sim3_optimize_batch_device(len(problems), arr, device_id, stream))
+
+
+def sim3_optimize_device(problem, stream=0, device_id=0):
+    """One candidate (orbgpu_sim3_optimize_device); see sim3_optimize_batch_device."""
+    q = sim3_opt_problem(problem)
+    L = lib()
+    L.orbgpu_sim3_optimize_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    check(L.orbgpu_sim3_optimize_device(C.byref(q), device_id, stream))
+
+
+def sim3_optimize(valid, Xw1, Xw2, octave1, octave2, kp1_xy, kp2_xy, T1w, T2w, K1, K2, inv_level_sigma2, R12, t12, s12,
+                  th2=10.0, fix_scale=False, inlier=None, nlevels=None, device_id=0):
+    """Optimizer::OptimizeSim3 over host arrays (orbgpu_sim3_optimize): valid [n1] is the caller's verdict per row of
+    vpMatches1, Xw1 / Xw2 [n1][3] the two map points' world positions, kp1_xy / kp2_xy [n1][2] their key points
+    (mvKeysUn1[i].pt, mvKeysUn2[i2].pt), (R12, t12, s12) the Sim3 to refine.  inlier [n1] is in/out (rows that are no
+    correspondence keep what they held; zeros if not given).  Returns (n_inliers, inlier, result dict): the dict holds the
+    refined Sim3 (R12_d / t12_d / s12_d and their float casts), T12, Scw and the counts."""
+    v = np.ascontiguousarray(valid, np.uint8)
+    n1 = len(v)
+    x1 = np.ascontiguousarray(Xw1, np.float32).reshape(-1, 3)
+    x2 = np.ascontiguousarray(Xw2, np.float32).reshape(-1, 3)
+    o1, o2 = np.ascontiguousarray(octave1, np.int32), np.ascontiguousarray(octave2, np.int32)
+    k1 = np.ascontiguousarray(kp1_xy, np.float32).reshape(-1, 2)
+    k2 = np.ascontiguousarray(kp2_xy, np.float32).reshape(-1, 2)
+    if not (len(x1) == len(x2) == len(o1) == len(o2) == len(k1) == len(k2) == n1):
+        raise ValueError("one entry per row of vpMatches1 expected")
+    out = np.zeros(max(n1, 1), np.uint8)
+    if inlier is not None:
+        out[:n1] = np.asarray(inlier, np.uint8)
+    d = {"n1": n1, "valid": v.ctypes.data, "Xw1": x1.ctypes.data, "Xw2": x2.ctypes.data, "octave1": o1.ctypes.data,
+         "octave2": o2.ctypes.data, "kp1_xy": k1.ctypes.data, "kp2_xy": k2.ctypes.data, "T1w": T1w, "T2w": T2w, "K1": K1,
+         "K2": K2, "inv_level_sigma2": inv_level_sigma2, "R12": R12, "t12": t12, "s12": s12, "th2": th2,
+         "fix_scale": fix_scale}
+    if nlevels is not None:
+        d["nlevels"] = nlevels
+    q = sim3_opt_problem(d)
+    ni, res = C.c_int32(), Sim3OptResult()
+    L = lib()
+    L.orbgpu_sim3_optimize.argtypes = [C.c_void_p] * 4 + [C.c_int32]
+    check(L.orbgpu_sim3_optimize(C.byref(q), _p(out), C.byref(ni), C.byref(res), device_id))
+    return ni.value, out[:n1], res.as_dict()
+
+
+def sim3_opt_last_spills(device_id=0):
+    """Problems of this thread's most recent Sim3 optimisation that took the global-memory spill path."""
+    L = lib()
+    L.orbgpu_sim3_opt_last_spills.argtypes = [C.c_int32, C.c_void_p]
+    v = C.c_int32()
+    check(L.orbgpu_sim3_opt_last_spills(device_id, C.byref(v)))
+    return v.value
 
 
 def pnp_ransac_parameters(n, probability, min_inliers, max_iterations, min_set, epsilon):

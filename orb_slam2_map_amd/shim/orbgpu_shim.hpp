@@ -973,6 +973,101 @@ template <typename FrameT, typename MapPointT> class ORBmatcherT {
 // ("g2o unpinned", include/orbgpu.h).  FrameT needs N, mvKeysUn, mvuRight, mvpMapPoints, mvbOutlier, mvInvLevelSigma2,
 // fx, fy, cx, cy, mbf; Tcw(F) returns the 16 floats of mTcw, world_pos(pMP) 3 floats (both valid during the call).
 // --------------------------------------------------------------------------------------------
+// A plain stand-in for g2o::Sim3 at the boundary of OptimizerT::OptimizeSim3 (g2o stays outside the shim):
+//     orbgpu_shim::Sim3 a;  const Eigen::Quaterniond &q = g.rotation();  a.r[0] = q.x(), a.r[1] = q.y(), a.r[2] = q.z(),
+//         a.r[3] = q.w();  for (int i = 0; i < 3; i++) a.t[i] = g.translation()[i];  a.s = g.scale();
+//     g2o::Sim3 g(Eigen::Quaterniond(a.r[3], a.r[0], a.r[1], a.r[2]), Eigen::Vector3d(a.t[0], a.t[1], a.t[2]), a.s);
+struct Sim3 {
+    double r[4] = {0.0, 0.0, 0.0, 1.0};  // quaternion x, y, z, w
+    double t[3] = {0.0, 0.0, 0.0};
+    double s = 1.0;
+
+    Sim3() = default;
+    // g2o::Sim3(Converter::toMatrix3d(R), Converter::toVector3d(t), s) over the floats of a cv::Mat (row-major 3x3, 3)
+    Sim3(const float *R, const float *t_, float s_)
+    {
+        double m[9];
+        for (int i = 0; i < 9; i++)
+            m[i] = (double)R[i];
+        const double td[3] = {(double)t_[0], (double)t_[1], (double)t_[2]};
+        Set(m, td, (double)s_);
+    }
+    // from a row-major rotation matrix (Eigen's Quaterniond(Matrix3d), then normalised with w >= 0)
+    void Set(const double m[9], const double t_[3], double s_)
+    {
+        double tr = m[0] + m[4] + m[8];
+        if (tr > 0) {
+            tr = std::sqrt(tr + 1.0);
+            r[3] = 0.5 * tr;
+            tr = 0.5 / tr;
+            r[0] = (m[7] - m[5]) * tr, r[1] = (m[2] - m[6]) * tr, r[2] = (m[3] - m[1]) * tr;
+        } else {
+            int i = 0;
+            if (m[4] > m[0])
+                i = 1;
+            if (m[8] > m[4 * i])
+                i = 2;
+            const int j = (i + 1) % 3, k = (j + 1) % 3;
+            tr = std::sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
+            r[i] = 0.5 * tr;
+            tr = 0.5 / tr;
+            r[3] = (m[3 * k + j] - m[3 * j + k]) * tr;
+            r[j] = (m[3 * j + i] + m[3 * i + j]) * tr;
+            r[k] = (m[3 * k + i] + m[3 * i + k]) * tr;
+        }
+        const double n = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]) * (r[3] < 0 ? -1.0 : 1.0);
+        for (int i = 0; i < 4; i++)
+            r[i] /= n;
+        for (int i = 0; i < 3; i++)
+            t[i] = t_[i];
+        s = s_;
+    }
+    void RotationMatrix(double R[9]) const
+    {
+        const double x = r[0], y = r[1], z = r[2], w = r[3];
+        R[0] = 1.0 - 2.0 * (y * y + z * z), R[1] = 2.0 * (x * y - z * w), R[2] = 2.0 * (x * z + y * w);
+        R[3] = 2.0 * (x * y + z * w), R[4] = 1.0 - 2.0 * (x * x + z * z), R[5] = 2.0 * (y * z - x * w);
+        R[6] = 2.0 * (x * z - y * w), R[7] = 2.0 * (y * z + x * w), R[8] = 1.0 - 2.0 * (x * x + y * y);
+    }
+};
+
+// The rows of orbgpu_sim3_opt_problem from two key frames and the matches of key frame 1, exactly as Optimizer.cc:1099-1137
+// walks them (O1): valid[i] iff vpMatches1[i] and KF1's own map point i exist, neither is bad, and the match has an index
+// i2 >= 0 in KF2; then obs1 = mvKeysUn1[i] (index i itself, :1142), obs2 = mvKeysUn2[i2] (:1159).  in_range[i]: both octaves
+// lie inside pKF1's sigma table -- what the library requires of a correspondence on top of valid[i].
+template <typename KeyFrameT, typename MapPointT> struct Sim3OptRows {
+    std::vector<uint8_t> valid, in_range;
+    std::vector<int32_t> o1, o2;
+    std::vector<float> x1, x2, k1, k2;
+
+    template <typename WorldPos>
+    Sim3OptRows(KeyFrameT *pKF1, KeyFrameT *pKF2, const std::vector<MapPointT *> &vpMatches1, WorldPos world_pos)
+    {
+        const size_t N = vpMatches1.size();
+        const std::vector<MapPointT *> vpMapPoints1 = pKF1->GetMapPointMatches();
+        const int nlevels = (int)std::min(pKF1->mvInvLevelSigma2.size(), (size_t)ORBGPU_MAX_LEVELS);
+        valid.assign(N + 1, 0), in_range.assign(N + 1, 0), o1.assign(N + 1, 0), o2.assign(N + 1, 0);
+        x1.assign(3 * N + 3, 0.f), x2.assign(3 * N + 3, 0.f), k1.assign(2 * N + 2, 0.f), k2.assign(2 * N + 2, 0.f);
+        for (size_t i = 0; i < N; i++) {
+            MapPointT *pMP2 = vpMatches1[i];
+            if (!pMP2)
+                continue;
+            MapPointT *pMP1 = i < vpMapPoints1.size() ? vpMapPoints1[i] : nullptr;
+            const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+            if (!pMP1 || pMP1->isBad() || pMP2->isBad() || i2 < 0)
+                continue;
+            valid[i] = 1;
+            o1[i] = pKF1->mvKeysUn[i].octave, o2[i] = pKF2->mvKeysUn[i2].octave;
+            in_range[i] = o1[i] >= 0 && o1[i] < nlevels && o2[i] >= 0 && o2[i] < nlevels;
+            k1[2 * i] = pKF1->mvKeysUn[i].pt.x, k1[2 * i + 1] = pKF1->mvKeysUn[i].pt.y;
+            k2[2 * i] = pKF2->mvKeysUn[i2].pt.x, k2[2 * i + 1] = pKF2->mvKeysUn[i2].pt.y;
+            std::memcpy(&x1[3 * i], world_pos(pMP1), 12);
+            std::memcpy(&x2[3 * i], world_pos(pMP2), 12);
+        }
+        valid.resize(N), in_range.resize(N);  // the arrays keep one spare row so that data() is never null
+    }
+};
+
 template <typename FrameT, typename MapPointT> class OptimizerT {
   public:
     // host arrays: one upload per call
@@ -1037,6 +1132,60 @@ template <typename FrameT, typename MapPointT> class OptimizerT {
             if (ids[i] >= 0)
                 F.mvbOutlier[i] = out[i] != 0;
         set_pose(F, T);
+        return inliers;
+    }
+
+    // Optimizer::OptimizeSim3 (include/Optimizer.h:58, src/Optimizer.cc:1054-1241): refines S12 over the matches of a loop
+    // candidate.  Side effects as in the reference: vpMatches1[i] = NULL for every correspondence the optimisation
+    // clears, S12 replaced by the refined Sim3 (left as it came when fewer than 10 correspondences survive stage 1), return
+    // value = inliers.  The conventions are O1-O9 of include/orbgpu.h ("g2o unpinned").  KeyFrameT needs
+    // GetMapPointMatches(), mvKeysUn, mvInvLevelSigma2 (pKF1's table serves both key frames: one extractor), fx, fy, cx,
+    // cy; MapPointT isBad() and GetIndexInKeyFrame(KeyFrameT *).  pose(pKF) returns the 16 floats of Tcw, world_pos(pMP) 3
+    // floats.  R12_float: the float rotation S12 was built from (ComputeSim3 holds it: the solver's R); when given it is
+    // passed on as it is, so the entry state is the reference's bit for bit -- otherwise the matrix of S12.r is rounded.
+    // result (optional) also carries Scw = toCvMat(S12 * Smw), what LoopClosing.cc:334-336 computes next.
+    template <typename KeyFrameT, typename PoseOf, typename WorldPos>
+    static int OptimizeSim3(KeyFrameT *pKF1, KeyFrameT *pKF2, std::vector<MapPointT *> &vpMatches1, Sim3 &S12, const float th2,
+                            const bool bFixScale, PoseOf pose, WorldPos world_pos, int device_id = 0,
+                            orbgpu_sim3_opt_result *result = nullptr, const float *R12_float = nullptr)
+    {
+        const Sim3OptRows<KeyFrameT, MapPointT> rows(pKF1, pKF2, vpMatches1, world_pos);
+        orbgpu_sim3_opt_problem p;
+        std::memset(&p, 0, sizeof(p));
+        p.n1 = (int32_t)rows.valid.size();
+        p.nlevels = (int32_t)std::min(pKF1->mvInvLevelSigma2.size(), (size_t)ORBGPU_MAX_LEVELS);
+        p.valid = rows.valid.data(), p.Xw1 = rows.x1.data(), p.Xw2 = rows.x2.data();
+        p.octave1 = rows.o1.data(), p.octave2 = rows.o2.data(), p.kp1_xy = rows.k1.data(), p.kp2_xy = rows.k2.data();
+        std::memcpy(p.T1w, pose(pKF1), 64);
+        std::memcpy(p.T2w, pose(pKF2), 64);
+        p.fx1 = pKF1->fx, p.fy1 = pKF1->fy, p.cx1 = pKF1->cx, p.cy1 = pKF1->cy;
+        p.fx2 = pKF2->fx, p.fy2 = pKF2->fy, p.cx2 = pKF2->cx, p.cy2 = pKF2->cy;
+        for (int l = 0; l < p.nlevels; l++)
+            p.inv_level_sigma2[l] = pKF1->mvInvLevelSigma2[l];
+        if (R12_float) {
+            std::memcpy(p.R12, R12_float, sizeof(p.R12));
+        } else {
+            double R[9];
+            S12.RotationMatrix(R);
+            for (int i = 0; i < 9; i++)
+                p.R12[i] = (float)R[i];
+        }
+        for (int i = 0; i < 3; i++)
+            p.t12[i] = (float)S12.t[i];
+        p.s12 = (float)S12.s;
+        p.th2 = th2, p.fix_scale = bFixScale ? 1 : 0;
+        std::vector<uint8_t> inlier(rows.valid.size() + 1, 0);
+        int32_t inliers = 0;
+        orbgpu_sim3_opt_result r;
+        check(orbgpu_sim3_optimize(&p, inlier.data(), &inliers, &r, device_id), "Optimizer::OptimizeSim3");
+        // rows that are no correspondence keep their 0 but are not touched: only correspondences can be cleared
+        for (size_t i = 0; i < rows.valid.size(); i++)
+            if (rows.valid[i] && rows.in_range[i] && inlier[i] == 0)
+                vpMatches1[i] = static_cast<MapPointT *>(nullptr);
+        if (r.stages == 2)
+            S12.Set(r.R12_d, r.t12_d, r.s12_d);
+        if (result)
+            *result = r;
         return inliers;
     }
 };
