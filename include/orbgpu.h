@@ -268,6 +268,11 @@ int orbgpu_match_bf_batch_device(orbgpu_matcher *m, int32_t pairs, int32_t cap, 
                                  void *hip_stream);
 /* Fixpoint sweeps the last batched call needed (diagnostic). */
 int orbgpu_matcher_last_sweeps(orbgpu_matcher *m, int32_t *sweeps);
+/* Launch shape of the last batched call (diagnostic; host values, no device access): the number of B row ranges
+ * with a candidate list of their own (1, 2, 4, 8 or 16), whether the exact full scan read the B descriptors from
+ * LDS (1) or from global memory (0), and the workgroup size of the resolve kernel.  ORBGPU_EINVAL before the
+ * first call. */
+int orbgpu_matcher_last_launch(orbgpu_matcher *m, int32_t *nsplit, int32_t *stage_b, int32_t *resolve_threads);
 
 /* SoA view of the Frame members the projection matchers read (Frame.h:100-190):
  * mvKeysUn (pt, octave, angle), mvuRight, mDescriptors, image bounds, grid metrics, the

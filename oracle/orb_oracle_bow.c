@@ -299,7 +299,9 @@ int ora_search_by_bow(const uint8_t *desc_kf, const float *angle_kf, const uint8
                         bestDist2 = dist;
                     }
                 }
-                if (bestDist1 <= th_low) {
+                /* bestIdxF < 0: every frame feature of the node is taken; only a th_low >= 256 gets past the first
+                 * test then (as in ora_match_bf) */
+                if (bestDist1 <= th_low && bestIdxF >= 0) {
                     if ((float)bestDist1 < nnratio * (float)bestDist2) {
                         match_f[bestIdxF] = realIdxKF;
                         if (check_orientation) {

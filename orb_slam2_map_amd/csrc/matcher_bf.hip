@@ -603,6 +603,7 @@ struct orbgpu_matcher {
     DevBuf d_topk, d_sweeps;
     int last_pairs = 0;
     int resolve_threads = 1024;  // workgroup size of k_bf_resolve (ORBGPU_DEBUG_BF_RESOLVE_THREADS: 256 / 512 / 1024)
+    int last_nsplit = 0, last_stage_b = 0;  // launch shape of the last call (orbgpu_matcher_last_launch)
 };
 
 // orbgpu_matcher_destroy without the lifecycle lock: the error paths of orbgpu_matcher_create, which holds it (the lock
@@ -707,6 +708,8 @@ static int match_batch_device(orbgpu_matcher *m, int32_t pairs, int32_t cap, con
                        d_nmatches, m->d_sweeps.as<int>(), stage_b, nsplit, d_node_a, d_node_b);
     ORBGPU_HIP_TRY(hipGetLastError());
     m->last_pairs = pairs;
+    m->last_nsplit = nsplit;
+    m->last_stage_b = stage_b;
     return ORBGPU_OK;
 }
 
@@ -741,6 +744,16 @@ int orbgpu_matcher_last_sweeps(orbgpu_matcher *m, int32_t *sweeps)
         return rc;
     ORBGPU_HIP_TRY(hipDeviceSynchronize());
     ORBGPU_HIP_TRY(hipMemcpy(sweeps, m->d_sweeps.p, sizeof(int) * m->last_pairs, hipMemcpyDeviceToHost));
+    return ORBGPU_OK;
+}
+
+int orbgpu_matcher_last_launch(orbgpu_matcher *m, int32_t *nsplit, int32_t *stage_b, int32_t *resolve_threads)
+{
+    ORBGPU_REQUIRE(m && nsplit && stage_b && resolve_threads, "null argument");
+    ORBGPU_REQUIRE(m->last_pairs > 0, "no call recorded");
+    *nsplit = m->last_nsplit;
+    *stage_b = m->last_stage_b;
+    *resolve_threads = m->resolve_threads;
     return ORBGPU_OK;
 }
 

@@ -201,7 +201,8 @@ ABI_SYMBOLS = [
     "orbgpu_pipeline_create", "orbgpu_pipeline_destroy", "orbgpu_pipeline_parts", "orbgpu_pipeline_part",
     "orbgpu_pipeline_extract_device", "orbgpu_pipeline_wait",
     "orbgpu_hamming256", "orbgpu_match_bf", "orbgpu_matcher_create", "orbgpu_matcher_destroy",
-    "orbgpu_match_bf_batch_device", "orbgpu_matcher_last_sweeps", "orbgpu_assign_features_to_grid",
+    "orbgpu_match_bf_batch_device", "orbgpu_matcher_last_sweeps", "orbgpu_matcher_last_launch",
+    "orbgpu_assign_features_to_grid",
     "orbgpu_frame_glue_batch_device", "orbgpu_stereo_matches_batch_device", "orbgpu_compute_stereo_matches",
     "orbgpu_undistort_points", "orbgpu_search_local_points_device", "orbgpu_search_local_points_batch_device", "orbgpu_search_by_projection_last_device", "orbgpu_projection_last_sweeps", "orbgpu_distinctive_descriptors", "orbgpu_search_by_projection_sim3",
     "orbgpu_search_by_projection", "orbgpu_search_by_projection_last", "orbgpu_search_by_projection_keyframe",
@@ -288,6 +289,9 @@ def lib():
         "orbgpu_matcher_destroy": [vp],
         "orbgpu_match_bf_batch_device": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, i32, f32, i32, vp, vp, vp],
         "orbgpu_matcher_last_sweeps": [vp, vp],
+        "orbgpu_matcher_last_launch": [vp, vp, vp, vp],
+        "orbgpu_search_by_bow_batch_device": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, f32, i32, vp, vp,
+                                              vp],
         "orbgpu_assign_features_to_grid": [i32, vp, vp, f32, f32, f32, f32, vp, vp],
         "orbgpu_frame_glue_batch_device": [i32, i32, i32, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp],
         "orbgpu_stereo_matches_batch_device": [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp,
@@ -1593,10 +1597,24 @@ class BatchMatcher:
                                                   d_angle_b, d_nb, angle_stride, th_low, nnratio, int(check_ori),
                                                   d_match_b, d_nmatches, stream))
 
+    def search_by_bow(self, pairs, cap, d_desc_a, d_angle_a, d_valid_a, d_node_a, d_na, d_desc_b, d_angle_b, d_node_b,
+                      d_nb, angle_stride, th_low, nnratio, check_ori, d_match_b, d_nmatches, stream=0):
+        """The node-wise matcher on the same layout (orbgpu_search_by_bow_batch_device): d_node_a / d_node_b are
+        [pairs][cap] int32 node ids, < 0 = not in the feature vector."""
+        check(self.L.orbgpu_search_by_bow_batch_device(self.h, pairs, cap, d_desc_a, d_angle_a, d_valid_a, d_node_a, d_na,
+                                                       d_desc_b, d_angle_b, d_node_b, d_nb, angle_stride, th_low, nnratio,
+                                                       int(check_ori), d_match_b, d_nmatches, stream))
+
     def last_sweeps(self, pairs):
         out = np.zeros(pairs, np.int32)
         check(self.L.orbgpu_matcher_last_sweeps(self.h, _p(out)))
         return out
+
+    def last_launch(self):
+        """Launch shape of the last call: dict of nsplit, stage_b, resolve_threads (orbgpu_matcher_last_launch)."""
+        v = [C.c_int32() for _ in range(3)]
+        check(self.L.orbgpu_matcher_last_launch(self.h, *[C.byref(x) for x in v]))
+        return dict(nsplit=v[0].value, stage_b=v[1].value, resolve_threads=v[2].value)
 
 
 # --------------------------------------------------------------------------------------------
