@@ -1,0 +1,214 @@
+// The FP64 arithmetic the device optimisers share (pose_opt.hip, sim3_opt.hip): quaternions as g2o's SE3Quat / Sim3 use
+// them, the Huber weights, the dense LL^T solve of the damped normal equation, its initial damping and the fixed-order
+// workgroup sum.  The definition of every function is its namesake in tests/pose_model.py, operation for operation;
+// tests/opt_math_test.cpp builds this header with g++ and tests/test_opt_math.py compares the two bit for bit.  No fused
+// multiply-add (-ffp-contract=off), and no expression may be re-associated: parity of the optimisers with their models
+// rests on the order written here.  Pure C++ except block_sum, which needs the wave shuffles.
+#pragma once
+
+#include <cmath>
+
+#if defined(__HIPCC__)
+#define ORBGPU_HD __host__ __device__
+#define ORBGPU_UNROLL _Pragma("unroll")
+#else
+#define ORBGPU_HD
+#define ORBGPU_UNROLL
+#endif
+
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif  // gcc: build with -ffp-contract=off
+
+namespace orbgpu {
+
+// ---- quaternions (x, y, z, w) ------------------------------------------------------------------------------------------
+// Eigen's Quaterniond(Matrix3d)
+ORBGPU_HD inline void quat_from_matrix(const double m[9], double q[4])
+{
+    double t = m[0] + m[4] + m[8];
+    if (t > 0) {
+        t = sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[7] - m[5]) * t;
+        q[1] = (m[2] - m[6]) * t;
+        q[2] = (m[3] - m[1]) * t;
+    } else {
+        int i = 0;
+        if (m[4] > m[0])
+            i = 1;
+        if (m[8] > m[4 * i])
+            i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
+        q[i] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
+        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
+        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
+    }
+}
+
+// SE3Quat::normalizeRotation: w >= 0, unit norm
+ORBGPU_HD inline void quat_normalize(double q[4])
+{
+    if (q[3] < 0)
+        for (int i = 0; i < 4; i++)
+            q[i] = -q[i];
+    const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    for (int i = 0; i < 4; i++)
+        q[i] = q[i] / n;
+}
+
+ORBGPU_HD inline void quat_to_matrix(const double q[4], double R[9])
+{
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+    const double twx = tx * w, twy = ty * w, twz = tz * w;
+    const double txx = tx * x, txy = ty * x, txz = tz * x;
+    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    R[0] = 1.0 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
+    R[3] = txy + twz, R[4] = 1.0 - (txx + tzz), R[5] = tyz - twx;
+    R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1.0 - (txx + tyy);
+}
+
+ORBGPU_HD inline void quat_mul(const double a[4], const double b[4], double o[4])
+{
+    o[0] = ((a[3] * b[0] + a[0] * b[3]) + a[1] * b[2]) - a[2] * b[1];
+    o[1] = ((a[3] * b[1] + a[1] * b[3]) + a[2] * b[0]) - a[0] * b[2];
+    o[2] = ((a[3] * b[2] + a[2] * b[3]) + a[0] * b[1]) - a[1] * b[0];
+    o[3] = ((a[3] * b[3] - a[0] * b[0]) - a[1] * b[1]) - a[2] * b[2];
+}
+
+// The entry state of an optimiser (Converter::toSE3Quat, Converter.cc:37-47): the float 3x3 at the head of rows of
+// `stride` floats -> double -> unit quaternion
+inline void unit_quat_from_floats(const float *m, int stride, double q[4])
+{
+    double R[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++)
+            R[3 * r + c] = (double)m[stride * r + c];
+    quat_from_matrix(R, q);
+    quat_normalize(q);
+}
+
+// RobustKernelHuber without the second-order term; an edge without kernel keeps chi2
+ORBGPU_HD inline void huber(double chi2, double delta, double delta2, double &rho0, double &rho1, bool use_kernel = true)
+{
+    if (chi2 <= delta2 || !use_kernel) {
+        rho0 = chi2;
+        rho1 = 1.0;
+    } else {
+        const double s = sqrt(chi2);
+        rho0 = (2.0 * s) * delta - delta2;
+        rho1 = delta / s;
+    }
+}
+
+// (H + lam I) x = b by LL^T, H as its upper triangle packed row by row; not positive definite (a pivot that is not > 0,
+// NaN included): false and x = 0
+template <int N>
+ORBGPU_HD inline bool cholesky_solve(const double (&Hu)[N * (N + 1) / 2], double lam, const double (&b)[N], double (&x)[N])
+{
+    double A[N][N], L[N][N];
+    {
+        int k = 0;
+        ORBGPU_UNROLL
+        for (int a = 0; a < N; a++)
+            ORBGPU_UNROLL
+            for (int c = a; c < N; c++, k++)
+                A[a][c] = A[c][a] = Hu[k];
+    }
+    ORBGPU_UNROLL
+    for (int i = 0; i < N; i++) {
+        A[i][i] = A[i][i] + lam;
+        ORBGPU_UNROLL
+        for (int j = 0; j < N; j++)
+            L[i][j] = 0.0;
+        x[i] = 0.0;
+    }
+    bool ok = true;
+    ORBGPU_UNROLL
+    for (int j = 0; j < N; j++) {
+        double d = A[j][j];
+        ORBGPU_UNROLL
+        for (int k = 0; k < j; k++)
+            d = d - L[j][k] * L[j][k];
+        if (!(d > 0.0))
+            ok = false;
+        d = sqrt(d);
+        L[j][j] = d;
+        ORBGPU_UNROLL
+        for (int i = j + 1; i < N; i++) {
+            double s = A[j][i];
+            ORBGPU_UNROLL
+            for (int k = 0; k < j; k++)
+                s = s - L[i][k] * L[j][k];
+            L[i][j] = s / d;
+        }
+    }
+    if (!ok)
+        return false;
+    double y[N];
+    ORBGPU_UNROLL
+    for (int i = 0; i < N; i++) {
+        double s = b[i];
+        ORBGPU_UNROLL
+        for (int k = 0; k < i; k++)
+            s = s - L[i][k] * y[k];
+        y[i] = s / L[i][i];
+    }
+    ORBGPU_UNROLL
+    for (int i = N - 1; i >= 0; i--) {
+        double s = y[i];
+        ORBGPU_UNROLL
+        for (int k = i + 1; k < N; k++)
+            s = s - L[k][i] * x[k];
+        x[i] = s / L[i][i];
+    }
+    return true;
+}
+
+// ---- Levenberg-Marquardt bookkeeping (g2o's OptimizationAlgorithmLevenberg) ----------------------------------------------
+// the first iteration's damping: 1e-5 * max |diag H|
+template <int N> ORBGPU_HD inline double lm_initial_lambda(const double (&Hu)[N * (N + 1) / 2])
+{
+    double m = 0.0;
+    ORBGPU_UNROLL
+    for (int a = 0, k = 0; a < N; k += N - a, a++)
+        if (fabs(Hu[k]) > m)
+            m = fabs(Hu[k]);
+    return 1e-5 * m;
+}
+
+#if defined(__HIPCC__)
+// Fixed-order sum over a workgroup of WAVES waves: shuffle tree inside each wave, then wave 0 + 1 + ... in every lane.
+// The result is the same bits in every lane, so control flow that branches on it stays workgroup-uniform.
+// red: WAVES * K doubles of LDS.
+template <int WAVES, int K> __device__ inline void block_sum(double (&v)[K], double *red)
+{
+#pragma unroll
+    for (int k = 0; k < K; k++)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1)
+            v[k] += __shfl_down(v[k], off, 64);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();  // the previous sum's readers are done with `red`
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < K; k++)
+            red[wave * K + k] = v[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        double s = red[k];
+#pragma unroll
+        for (int wv = 1; wv < WAVES; wv++)
+            s += red[wv * K + k];
+        v[k] = s;
+    }
+}
+#endif
+
+} // namespace orbgpu

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "opt_math.h"
 #include "staging.h"
 
 namespace orbgpu {
@@ -41,63 +42,6 @@ struct PoseProblemDev {
 struct Cam {
     double fx, fy, cx, cy, bf;
 };
-
-// ---- SE3Quat (quaternion as x, y, z, w) ------------------------------------------------------------------------------
-__host__ __device__ inline void quat_from_matrix(const double m[9], double q[4])
-{
-    double t = m[0] + m[4] + m[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (m[7] - m[5]) * t;
-        q[1] = (m[2] - m[6]) * t;
-        q[2] = (m[3] - m[1]) * t;
-    } else {
-        int i = 0;
-        if (m[4] > m[0])
-            i = 1;
-        if (m[8] > m[4 * i])
-            i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
-        q[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
-        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
-        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
-    }
-}
-
-__host__ __device__ inline void quat_normalize(double q[4])
-{
-    if (q[3] < 0)
-        for (int i = 0; i < 4; i++)
-            q[i] = -q[i];
-    const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    for (int i = 0; i < 4; i++)
-        q[i] = q[i] / n;
-}
-
-__host__ __device__ inline void quat_to_matrix(const double q[4], double R[9])
-{
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w;
-    const double txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1.0 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
-    R[3] = txy + twz, R[4] = 1.0 - (txx + tzz), R[5] = tyz - twx;
-    R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1.0 - (txx + tyy);
-}
-
-__device__ inline void quat_mul(const double a[4], const double b[4], double o[4])
-{
-    o[0] = ((a[3] * b[0] + a[0] * b[3]) + a[1] * b[2]) - a[2] * b[1];
-    o[1] = ((a[3] * b[1] + a[1] * b[3]) + a[2] * b[0]) - a[0] * b[2];
-    o[2] = ((a[3] * b[2] + a[2] * b[3]) + a[0] * b[1]) - a[1] * b[0];
-    o[3] = ((a[3] * b[3] - a[0] * b[0]) - a[1] * b[1]) - a[2] * b[2];
-}
 
 // T' = exp(x) * T with x = (omega, upsilon): SE3Quat::exp (its small-angle branch kept as is) and operator*
 __device__ inline void pose_update(const double q[4], const double t[3], const double x[6], double qn[4], double tn[3])
@@ -156,107 +100,6 @@ __device__ inline double edge_error(const double R[9], const double t[3], const 
     e[1] = (double)b.y - ((C.fy * P[1]) * iz + C.cy);
     e[2] = stereo ? (double)b.z - (u - C.bf * iz) : 0.0;
     return w * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-}
-
-// RobustKernelHuber without the second-order term; an edge without kernel keeps chi2
-__device__ inline void huber(double chi2, double delta, double delta2, bool use_kernel, double &rho0, double &rho1)
-{
-    if (chi2 <= delta2 || !use_kernel) {
-        rho0 = chi2;
-        rho1 = 1.0;
-    } else {
-        const double s = sqrt(chi2);
-        rho0 = (2.0 * s) * delta - delta2;
-        rho1 = delta / s;
-    }
-}
-
-// Fixed-order sum over the workgroup: shuffle tree inside each wave, then wave 0 + 1 + 2 + 3 in every lane.  The result
-// is the same bits in every lane, so control flow that branches on it stays workgroup-uniform.
-template <int K> __device__ inline void block_sum(double (&v)[K], double *red)
-{
-#pragma unroll
-    for (int k = 0; k < K; k++)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-            v[k] += __shfl_down(v[k], off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();  // the previous sum's readers are done with `red`
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; k++)
-            red[wave * K + k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        double s = red[k];
-#pragma unroll
-        for (int wv = 1; wv < PO_WAVES; wv++)
-            s += red[wv * K + k];
-        v[k] = s;
-    }
-}
-
-// (H + lam I) x = b by LL^T; not positive definite (a pivot that is not > 0, NaN included): false and x = 0
-__device__ inline bool cholesky_solve6(const double Hu[21], double lam, const double b[6], double x[6])
-{
-    double A[6][6], L[6][6];
-    {
-        int k = 0;
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-            for (int c = a; c < 6; c++, k++)
-                A[a][c] = A[c][a] = Hu[k];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        A[i][i] = A[i][i] + lam;
-#pragma unroll
-        for (int j = 0; j < 6; j++)
-            L[i][j] = 0.0;
-        x[i] = 0.0;
-    }
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double d = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++)
-            d = d - L[j][k] * L[j][k];
-        if (!(d > 0.0))
-            ok = false;
-        d = sqrt(d);
-        L[j][j] = d;
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-            double s = A[j][i];
-#pragma unroll
-            for (int k = 0; k < j; k++)
-                s = s - L[i][k] * L[j][k];
-            L[i][j] = s / d;
-        }
-    }
-    if (!ok)
-        return false;
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double s = b[i];
-#pragma unroll
-        for (int k = 0; k < i; k++)
-            s = s - L[i][k] * y[k];
-        y[i] = s / L[i][i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++)
-            s = s - L[k][i] * x[k];
-        x[i] = s / L[i][i];
-    }
-    return true;
 }
 
 // key point i is an edge (1), has an out-of-range row / octave (2), or holds no map point (0)
@@ -376,7 +219,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblemDev *_
                 double er[3], Pc[3];
                 const double chi2 = edge_error(R, t, C, ea, eb, stereo, er, Pc);
                 double rho0, rho1;
-                huber(chi2, P.delta[stereo], P.delta2[stereo], use_kernel, rho0, rho1);
+                huber(chi2, P.delta[stereo], P.delta2[stereo], rho0, rho1, use_kernel);
                 const double x = Pc[0], y = Pc[1], z = Pc[2];
                 const double iz = 1.0 / z, iz2 = iz * iz;
                 double J[3][6];
@@ -422,7 +265,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblemDev *_
                     acc[21 + a] += -((Jw[0][a] * er[0] + Jw[1][a] * er[1]) + Jw[2][a] * er[2]);
                 acc[27] += rho0;
             }
-            block_sum<PO_SUMS>(acc, red);
+            block_sum<PO_WAVES>(acc, red);
             double Hu[21], b[6];
 #pragma unroll
             for (int k = 0; k < 21; k++)
@@ -431,13 +274,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblemDev *_
             for (int a = 0; a < 6; a++)
                 b[a] = acc[21 + a];
             if (it == 0) {
-                double m = 0.0;
-                const int diag[6] = {0, 6, 11, 15, 18, 20};
-#pragma unroll
-                for (int a = 0; a < 6; a++)
-                    if (fabs(Hu[diag[a]]) > m)
-                        m = fabs(Hu[diag[a]]);
-                lam = 1e-5 * m;
+                lam = lm_initial_lambda<6>(Hu);
                 nu = 2.0;
             }
             double cur = acc[27], rho = 0.0;
@@ -446,7 +283,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblemDev *_
             iterations++;
             do {
                 double x[6], qn[4], tn[3], Rn[9];
-                const bool ok = cholesky_solve6(Hu, lam, b, x);
+                const bool ok = cholesky_solve<6>(Hu, lam, b, x);
                 pose_update(q, t, x, qn, tn);
                 quat_to_matrix(qn, Rn);
                 double part[1] = {0.0};
@@ -458,10 +295,10 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblemDev *_
                     const bool stereo = bits & PO_STEREO;
                     double er[3], Pc[3], rho0, rho1;
                     const double chi2 = edge_error(Rn, tn, C, ea, eb, stereo, er, Pc);
-                    huber(chi2, P.delta[stereo], P.delta2[stereo], use_kernel, rho0, rho1);
+                    huber(chi2, P.delta[stereo], P.delta2[stereo], rho0, rho1, use_kernel);
                     part[0] += rho0;
                 }
-                block_sum<1>(part, red);
+                block_sum<PO_WAVES>(part, red);
                 const double tmp = ok ? part[0] : DBL_MAX;
                 double scale = 0.0;
 #pragma unroll
@@ -542,15 +379,6 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblemDev *_
 enum { PROBLEMS, SPILL, SPILL_COUNT, H_KPS, H_UR, H_K2M, H_WP, H_N, H_OUT, H_RES, N_BUF };
 struct PoseWs : Staging<N_BUF> {};
 
-static int lds_edge_limit()
-{
-    // ORBGPU_DEBUG_POSE_LDS_EDGES=<k> (tests): problems with more than k edges take the global spill path
-    const char *s = getenv("ORBGPU_DEBUG_POSE_LDS_EDGES");
-    if (!s)
-        return PO_LDS_EDGES;
-    return std::min(std::max(atoi(s), 0), PO_LDS_EDGES);
-}
-
 static int check_problem(const orbgpu_pose_problem &p, int k)
 {
     ORBGPU_REQUIRE(p.frame && p.d_kp_to_mp && p.Tcw && p.inv_level_sigma2 && p.d_outlier && p.d_result,
@@ -582,7 +410,8 @@ extern "C" int orbgpu_pose_optimization_batch_device(int32_t n, const orbgpu_pos
     PoseWs &ws = per_device_workspace<PoseWs>(device_id);
     if ((rc = ws.bind(device_id, false)) != ORBGPU_OK)
         return rc;
-    const int lds_edges = lds_edge_limit();
+    // ORBGPU_DEBUG_POSE_LDS_EDGES=<k> (tests): problems with more than k edges take the global spill path
+    const int lds_edges = debug_limit("ORBGPU_DEBUG_POSE_LDS_EDGES", PO_LDS_EDGES);
     size_t spill_edges = 0;
     for (int k = 0; k < n; k++)
         if (problems[k].frame->cap > lds_edges)
@@ -610,16 +439,11 @@ extern "C" int orbgpu_pose_optimization_batch_device(int32_t n, const orbgpu_pos
         for (int l = 0; l < f->nlevels; l++)
             D.inv_sigma2[l] = p.inv_level_sigma2[l];
         // Converter::toSE3Quat (Converter.cc:37-47): float 3x3 -> double -> unit quaternion, float t -> double
-        double Rm[9];
-        for (int r = 0; r < 3; r++) {
-            for (int c = 0; c < 3; c++)
-                Rm[3 * r + c] = (double)p.Tcw[4 * r + c];
+        unit_quat_from_floats(p.Tcw, 4, D.q0);
+        for (int r = 0; r < 3; r++)
             D.t0[r] = (double)p.Tcw[4 * r + 3];
-        }
         for (int i = 0; i < 16; i++)
             D.Tcw[i] = p.Tcw[i];
-        quat_from_matrix(Rm, D.q0);
-        quat_normalize(D.q0);
         D.fx = (double)p.fx, D.fy = (double)p.fy, D.cx = (double)p.cx, D.cy = (double)p.cy, D.bf = (double)p.mbf;
         D.delta[0] = (double)(float)std::sqrt(5.991), D.delta[1] = (double)(float)std::sqrt(7.815);
         D.delta2[0] = D.delta[0] * D.delta[0], D.delta2[1] = D.delta[1] * D.delta[1];
@@ -640,15 +464,7 @@ extern "C" int orbgpu_pose_optimization_device(const orbgpu_pose_problem *p, int
 
 extern "C" int orbgpu_pose_last_spills(int32_t device_id, int32_t *problems_spilled)
 {
-    ORBGPU_REQUIRE(problems_spilled, "null argument");
-    int rc = select_device(device_id);
-    if (rc != ORBGPU_OK)
-        return rc;
-    PoseWs &ws = per_device_workspace<PoseWs>(device_id);
-    ORBGPU_REQUIRE(ws.buf[SPILL_COUNT].p, "no pose optimisation recorded on this thread");
-    ORBGPU_HIP_TRY(hipDeviceSynchronize());
-    ORBGPU_HIP_TRY(hipMemcpy(problems_spilled, ws.buf[SPILL_COUNT].p, sizeof(int32_t), hipMemcpyDeviceToHost));
-    return ORBGPU_OK;
+    return last_spills<PoseWs>(device_id, SPILL_COUNT, "no pose optimisation recorded on this thread", problems_spilled);
 }
 
 extern "C" int orbgpu_pose_optimization(const orbgpu_frame_view *f, const uint8_t *has_mp, const float *world_pos,

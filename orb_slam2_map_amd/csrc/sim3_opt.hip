@@ -3,7 +3,9 @@
 // returning to the host; the definition (g2o restated, "g2o unpinned", conventions O1-O9) is in include/orbgpu.h and
 // tests/sim3opt_model.py.  FP64 throughout, no fused multiply-add (-ffp-contract=off): the per-edge arithmetic is the
 // model's operation for operation, only the order of the sums over edges differs (fixed tree here, sequential there).
-// The small helpers (quaternions, Cholesky, the reduction tree) are this file's own copies of pose_opt.hip's.
+// The quaternions, the Huber weights, the Cholesky solve, the initial damping and the reduction tree are opt_math.h's,
+// shared with pose_opt.hip; the rest of the Levenberg-Marquardt bookkeeping and the two compaction passes are written out
+// in both kernels, because moving them changed the generated code.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -11,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "opt_math.h"
 #include "staging.h"
 
 namespace orbgpu {
@@ -48,63 +51,6 @@ struct Sim3OptProblemDev {
 struct Xf {
     double R[9], t[3], s, is, ti[3];
 };
-
-// ---- quaternions (x, y, z, w) ------------------------------------------------------------------------------------------
-__host__ __device__ inline void quat_from_matrix(const double m[9], double q[4])
-{
-    double t = m[0] + m[4] + m[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (m[7] - m[5]) * t;
-        q[1] = (m[2] - m[6]) * t;
-        q[2] = (m[3] - m[1]) * t;
-    } else {
-        int i = 0;
-        if (m[4] > m[0])
-            i = 1;
-        if (m[8] > m[4 * i])
-            i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
-        q[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
-        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
-        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
-    }
-}
-
-__host__ __device__ inline void quat_normalize(double q[4])
-{
-    if (q[3] < 0)
-        for (int i = 0; i < 4; i++)
-            q[i] = -q[i];
-    const double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    for (int i = 0; i < 4; i++)
-        q[i] = q[i] / n;
-}
-
-__host__ __device__ inline void quat_to_matrix(const double q[4], double R[9])
-{
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w;
-    const double txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1.0 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
-    R[3] = txy + twz, R[4] = 1.0 - (txx + tzz), R[5] = tyz - twx;
-    R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1.0 - (txx + tyy);
-}
-
-__device__ inline void quat_mul(const double a[4], const double b[4], double o[4])
-{
-    o[0] = ((a[3] * b[0] + a[0] * b[3]) + a[1] * b[2]) - a[2] * b[1];
-    o[1] = ((a[3] * b[1] + a[1] * b[3]) + a[2] * b[0]) - a[0] * b[2];
-    o[2] = ((a[3] * b[2] + a[2] * b[3]) + a[0] * b[1]) - a[1] * b[0];
-    o[3] = ((a[3] * b[3] - a[0] * b[0]) - a[1] * b[1]) - a[2] * b[2];
-}
 
 // S' = exp(x) * S (O4, O5); nothing is renormalised
 __device__ inline void sim3_update(const double q[4], const double t[3], double s, const double x[7], bool fix_scale,
@@ -236,19 +182,6 @@ __device__ inline void pair_errors(const Xf &F, const double K1[4], const double
     e21[1] = p.o2[1] - ((Q[1] / Q[2]) * K2[1] + K2[3]);
 }
 
-// RobustKernelHuber without the second-order term
-__device__ inline void huber(double chi2, double delta, double delta2, double &rho0, double &rho1)
-{
-    if (chi2 <= delta2) {
-        rho0 = chi2;
-        rho1 = 1.0;
-    } else {
-        const double s = sqrt(chi2);
-        rho0 = (2.0 * s) * delta - delta2;
-        rho1 = delta / s;
-    }
-}
-
 // one edge's share of H (upper triangle, row-major), b and the robust chi2
 __device__ inline void accumulate(double (&acc)[SO_SUMS], const double J[2][7], const double e[2], double w, double delta,
                                   double delta2)
@@ -273,94 +206,6 @@ __device__ inline void accumulate(double (&acc)[SO_SUMS], const double J[2][7], 
     for (int a = 0; a < 7; a++)
         acc[28 + a] += -(Jw[0][a] * e[0] + Jw[1][a] * e[1]);
     acc[35] += rho0;
-}
-
-// Fixed-order sum over the workgroup: shuffle tree inside each wave, then wave 0 + 1 + 2 + 3 in every lane.  The result
-// is the same bits in every lane, so control flow that branches on it stays workgroup-uniform.
-template <int K> __device__ inline void block_sum(double (&v)[K], double *red)
-{
-#pragma unroll
-    for (int k = 0; k < K; k++)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-            v[k] += __shfl_down(v[k], off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();  // the previous sum's readers are done with `red`
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; k++)
-            red[wave * K + k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        double s = red[k];
-#pragma unroll
-        for (int wv = 1; wv < SO_WAVES; wv++)
-            s += red[wv * K + k];
-        v[k] = s;
-    }
-}
-
-// (H + lam I) x = b by LL^T; not positive definite (a pivot that is not > 0, NaN included): false and x = 0
-__device__ inline bool cholesky_solve7(const double Hu[28], double lam, const double b[7], double x[7])
-{
-    double A[7][7], L[7][7];
-    {
-        int k = 0;
-#pragma unroll
-        for (int a = 0; a < 7; a++)
-#pragma unroll
-            for (int c = a; c < 7; c++, k++)
-                A[a][c] = A[c][a] = Hu[k];
-    }
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-        A[i][i] = A[i][i] + lam;
-#pragma unroll
-        for (int j = 0; j < 7; j++)
-            L[i][j] = 0.0;
-        x[i] = 0.0;
-    }
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 7; j++) {
-        double d = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++)
-            d = d - L[j][k] * L[j][k];
-        if (!(d > 0.0))
-            ok = false;
-        d = sqrt(d);
-        L[j][j] = d;
-#pragma unroll
-        for (int i = j + 1; i < 7; i++) {
-            double s = A[j][i];
-#pragma unroll
-            for (int k = 0; k < j; k++)
-                s = s - L[i][k] * L[j][k];
-            L[i][j] = s / d;
-        }
-    }
-    if (!ok)
-        return false;
-    double y[7];
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-        double s = b[i];
-#pragma unroll
-        for (int k = 0; k < i; k++)
-            s = s - L[i][k] * y[k];
-        y[i] = s / L[i][i];
-    }
-#pragma unroll
-    for (int i = 6; i >= 0; i--) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 7; k++)
-            s = s - L[k][i] * x[k];
-        x[i] = s / L[i][i];
-    }
-    return true;
 }
 
 // row i is a correspondence (1), a valid row with an octave out of range (2), or nothing (0)  (O1)
@@ -553,7 +398,7 @@ __global__ __launch_bounds__(SO_THREADS) void k_sim3_opt(const Sim3OptProblemDev
                 accumulate(acc, J12, e12, pr.w1, delta, delta2);
                 accumulate(acc, J21, e21, pr.w2, delta, delta2);
             }
-            block_sum<SO_SUMS>(acc, red);
+            block_sum<SO_WAVES>(acc, red);
             double Hu[28], b[7];
 #pragma unroll
             for (int k = 0; k < 28; k++)
@@ -562,13 +407,7 @@ __global__ __launch_bounds__(SO_THREADS) void k_sim3_opt(const Sim3OptProblemDev
             for (int a = 0; a < 7; a++)
                 b[a] = acc[28 + a];
             if (it == 0) {
-                double m = 0.0;
-                const int diag[7] = {0, 7, 13, 18, 22, 25, 27};
-#pragma unroll
-                for (int a = 0; a < 7; a++)
-                    if (fabs(Hu[diag[a]]) > m)
-                        m = fabs(Hu[diag[a]]);
-                lam = 1e-5 * m;
+                lam = lm_initial_lambda<7>(Hu);
                 nu = 2.0;
             }
             double cur = acc[35], rho = 0.0;
@@ -577,7 +416,7 @@ __global__ __launch_bounds__(SO_THREADS) void k_sim3_opt(const Sim3OptProblemDev
             iterations++;
             do {
                 double x[7], qn[4], tn[3], sn;
-                const bool ok = cholesky_solve7(Hu, lam, b, x);
+                const bool ok = cholesky_solve<7>(Hu, lam, b, x);
                 sim3_update(q, t, s, x, fix_scale, qn, tn, sn);
                 Xf F;
                 make_xf(qn, tn, sn, F);
@@ -594,7 +433,7 @@ __global__ __launch_bounds__(SO_THREADS) void k_sim3_opt(const Sim3OptProblemDev
                     huber(pr.w2 * (e21[0] * e21[0] + e21[1] * e21[1]), delta, delta2, rho0, rho1);
                     part[0] += rho0;
                 }
-                block_sum<1>(part, red);
+                block_sum<SO_WAVES>(part, red);
                 const double tmp = ok ? part[0] : DBL_MAX;
                 double scale = 0.0;
 #pragma unroll
@@ -677,15 +516,6 @@ __global__ __launch_bounds__(SO_THREADS) void k_sim3_opt(const Sim3OptProblemDev
 enum { PROBLEMS, SPILL, SPILL_COUNT, H_IN, H_OUT, N_BUF };
 struct Sim3OptWs : Staging<N_BUF> {};
 
-static int lds_pair_limit()
-{
-    // ORBGPU_DEBUG_SIM3OPT_LDS_PAIRS=<k> (tests): problems with more than k correspondences take the global spill path
-    const char *s = getenv("ORBGPU_DEBUG_SIM3OPT_LDS_PAIRS");
-    if (!s)
-        return SO_LDS_PAIRS;
-    return std::min(std::max(atoi(s), 0), SO_LDS_PAIRS);
-}
-
 static int check_common(const orbgpu_sim3_opt_problem &p, int k)
 {
     ORBGPU_REQUIRE(p.n1 >= 0 && p.n1 <= SO_MAX_N1, "problem %d: n1 outside [0, %d]", k, SO_MAX_N1);
@@ -725,7 +555,8 @@ extern "C" int orbgpu_sim3_optimize_batch_device(int32_t n, const orbgpu_sim3_op
     Sim3OptWs &ws = per_device_workspace<Sim3OptWs>(device_id);
     if ((rc = ws.bind(device_id, false)) != ORBGPU_OK)
         return rc;
-    const int lds_pairs = lds_pair_limit();
+    // ORBGPU_DEBUG_SIM3OPT_LDS_PAIRS=<k> (tests): problems with more than k correspondences take the global spill path
+    const int lds_pairs = debug_limit("ORBGPU_DEBUG_SIM3OPT_LDS_PAIRS", SO_LDS_PAIRS);
     size_t spill_rows = 0;
     for (int k = 0; k < n; k++)
         if (problems[k].n1 > lds_pairs)
@@ -756,15 +587,8 @@ extern "C" int orbgpu_sim3_optimize_batch_device(int32_t n, const orbgpu_sim3_op
         D.K1[0] = (double)p.fx1, D.K1[1] = (double)p.fy1, D.K1[2] = (double)p.cx1, D.K1[3] = (double)p.cy1;
         D.K2[0] = (double)p.fx2, D.K2[1] = (double)p.fy2, D.K2[2] = (double)p.cx2, D.K2[3] = (double)p.cy2;
         // O4: float R12 -> double -> unit quaternion; O9: Smw from the float pose of key frame 2
-        double Rm[9], Rw[9];
-        for (int i = 0; i < 9; i++) {
-            Rm[i] = (double)p.R12[i];
-            Rw[i] = (double)p.T2w[4 * (i / 3) + i % 3];
-        }
-        quat_from_matrix(Rm, D.q0);
-        quat_normalize(D.q0);
-        quat_from_matrix(Rw, D.qmw);
-        quat_normalize(D.qmw);
+        unit_quat_from_floats(p.R12, 3, D.q0);
+        unit_quat_from_floats(p.T2w, 4, D.qmw);
         for (int r = 0; r < 3; r++) {
             D.t0[r] = (double)p.t12[r];
             D.tmw[r] = (double)p.T2w[4 * r + 3];
@@ -790,15 +614,7 @@ extern "C" int orbgpu_sim3_optimize_device(const orbgpu_sim3_opt_problem *p, int
 
 extern "C" int orbgpu_sim3_opt_last_spills(int32_t device_id, int32_t *problems_spilled)
 {
-    ORBGPU_REQUIRE(problems_spilled, "null argument");
-    int rc = select_device(device_id);
-    if (rc != ORBGPU_OK)
-        return rc;
-    Sim3OptWs &ws = per_device_workspace<Sim3OptWs>(device_id);
-    ORBGPU_REQUIRE(ws.buf[SPILL_COUNT].p, "no Sim3 optimisation recorded on this thread");
-    ORBGPU_HIP_TRY(hipDeviceSynchronize());
-    ORBGPU_HIP_TRY(hipMemcpy(problems_spilled, ws.buf[SPILL_COUNT].p, sizeof(int32_t), hipMemcpyDeviceToHost));
-    return ORBGPU_OK;
+    return last_spills<Sim3OptWs>(device_id, SPILL_COUNT, "no Sim3 optimisation recorded on this thread", problems_spilled);
 }
 
 extern "C" int orbgpu_sim3_optimize(const orbgpu_sim3_opt_problem *p, uint8_t *inlier, int32_t *n_inliers,

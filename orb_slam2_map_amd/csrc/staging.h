@@ -130,4 +130,28 @@ template <int N> struct Staging {
     }
 };
 
+// ---- the two test hooks of the device optimisers (pose_opt.hip, sim3_opt.hip) -------------------------------------------
+// A capacity of `max` records in LDS, lowered to k (clamped to [0, max]) while the environment variable `name` is set
+// to k; read on every call, so that a test can set and clear it between calls.
+inline int debug_limit(const char *name, int max)
+{
+    const char *s = getenv(name);
+    return s ? std::min(std::max(atoi(s), 0), max) : max;
+}
+
+// The body of an *_last_spills entry point: buffer `counter` of this thread's workspace Ws, which the most recent
+// optimisation zeroed and its kernel counted in, once the device has finished.
+template <typename Ws> int last_spills(int32_t device_id, int counter, const char *none_recorded, int32_t *problems_spilled)
+{
+    ORBGPU_REQUIRE(problems_spilled, "null argument");
+    int rc = select_device(device_id);
+    if (rc != ORBGPU_OK)
+        return rc;
+    Ws &ws = per_device_workspace<Ws>(device_id);
+    ORBGPU_REQUIRE(ws.buf[counter].p, "%s", none_recorded);
+    ORBGPU_HIP_TRY(hipDeviceSynchronize());
+    ORBGPU_HIP_TRY(hipMemcpy(problems_spilled, ws.buf[counter].p, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return ORBGPU_OK;
+}
+
 } // namespace orbgpu

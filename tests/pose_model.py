@@ -190,37 +190,38 @@ def seq_sum(a, order):
 TRI = [(a, b) for a in range(6) for b in range(a, 6)]
 
 
-def cholesky_solve6(H, lam, b):
-    """(H + lam I) x = b by LL^T on the upper triangle of H; (ok, x).  Not positive definite (a pivot that is not > 0,
-    NaN included): ok = False and x = 0."""
+def cholesky_solve(H, lam, b):
+    """(H + lam I) x = b by LL^T on the upper triangle of H, of any size (6 here, 7 in sim3opt_model); (ok, x).  Not
+    positive definite (a pivot that is not > 0, NaN included): ok = False and x = 0."""
+    n = len(H)
     A = H.copy()
-    for i in range(6):
+    for i in range(n):
         A[i, i] = A[i, i] + lam
-    L = np.zeros((6, 6))
+    L = np.zeros((n, n))
     with np.errstate(all="ignore"):
-        for j in range(6):
+        for j in range(n):
             d = A[j, j]
             for k in range(j):
                 d = d - L[j, k] * L[j, k]
             if not d > 0.0:
-                return False, np.zeros(6)
+                return False, np.zeros(n)
             d = np.sqrt(d)
             L[j, j] = d
-            for i in range(j + 1, 6):
+            for i in range(j + 1, n):
                 s = A[j, i]
                 for k in range(j):
                     s = s - L[i, k] * L[j, k]
                 L[i, j] = s / d
-        y = np.zeros(6)
-        for i in range(6):
+        y = np.zeros(n)
+        for i in range(n):
             s = b[i]
             for k in range(i):
                 s = s - L[i, k] * y[k]
             y[i] = s / L[i, i]
-        x = np.zeros(6)
-        for i in range(5, -1, -1):
+        x = np.zeros(n)
+        for i in range(n - 1, -1, -1):
             s = y[i]
-            for k in range(i + 1, 6):
+            for k in range(i + 1, n):
                 s = s - L[k, i] * x[k]
             x[i] = s / L[i, i]
     return True, x
@@ -309,7 +310,7 @@ def pose_optimization(kps_xy, octave, u_right, kp_to_mp, world_pos, Tcw, inv_lev
             rho, trial, stop = 0.0, 0, False
             out["iterations"] += 1
             while True:
-                ok, x = cholesky_solve6(H, lam, b)
+                ok, x = cholesky_solve(H, lam, b)
                 qn, tn = pose_update(q, t, x)
                 tmp = robust_chi(qn, tn)
                 if not ok:

@@ -12,7 +12,8 @@ does to the result; `libm_nudge` moves every result of exp, sin and cos by that 
 libm's rounding does through the 1e-9 difference quotient."""
 import numpy as np
 
-from pose_model import huber, quat_from_matrix, quat_mul, quat_normalize, quat_to_matrix, seq_sum, mat_vec, skew
+from pose_model import (cholesky_solve, huber, quat_from_matrix, quat_mul, quat_normalize, quat_to_matrix, seq_sum, mat_vec,
+                        skew)
 import sim3_model
 from sim3_model import rt_apply
 
@@ -172,41 +173,6 @@ def numeric_jacobian(state, pb, fix_scale, delta=DELTA, libm_nudge=0):
         return np.stack([(e[2 * k] - e[2 * k + 1]) * scale for k in range(7)], 2)
 
 
-def cholesky_solve7(H, lam, b):
-    """(H + lam I) x = b by LL^T; (ok, x).  A pivot that is not > 0 (NaN included): ok = False and x = 0."""
-    A = H.copy()
-    for i in range(7):
-        A[i, i] = A[i, i] + lam
-    L = np.zeros((7, 7))
-    with np.errstate(all="ignore"):
-        for j in range(7):
-            d = A[j, j]
-            for k in range(j):
-                d = d - L[j, k] * L[j, k]
-            if not d > 0.0:
-                return False, np.zeros(7)
-            d = np.sqrt(d)
-            L[j, j] = d
-            for i in range(j + 1, 7):
-                s = A[j, i]
-                for k in range(j):
-                    s = s - L[i, k] * L[j, k]
-                L[i, j] = s / d
-        y = np.zeros(7)
-        for i in range(7):
-            s = b[i]
-            for k in range(i):
-                s = s - L[i, k] * y[k]
-            y[i] = s / L[i, i]
-        x = np.zeros(7)
-        for i in range(6, -1, -1):
-            s = y[i]
-            for k in range(i + 1, 7):
-                s = s - L[k, i] * x[k]
-            x[i] = s / L[i, i]
-    return True, x
-
-
 # ---- the optimisation (O7, O8) -----------------------------------------------------------------------------------------
 def optimize(state, pb, active, budget, fix_scale, delta_huber, order, libm_nudge, out):
     """optimize(budget) over the edges of the active correspondences; returns the kept state."""
@@ -248,7 +214,7 @@ def optimize(state, pb, active, budget, fix_scale, delta_huber, order, libm_nudg
         rho, trial, stop = 0.0, 0, False
         out["iterations"] += 1
         while True:
-            ok, x = cholesky_solve7(H, lam, b)
+            ok, x = cholesky_solve(H, lam, b)
             cand = sim3_update(state, x, fix_scale, libm_nudge)
             tmp = robust_chi(cand)
             if not ok:

@@ -80,13 +80,13 @@ def test_cholesky_solves_and_refuses():
     A = rng.normal(0, 1, (6, 6))
     H = A @ A.T + np.eye(6)
     b = rng.normal(0, 1, 6)
-    ok, x = M.cholesky_solve6(H, 0.5, b)
+    ok, x = M.cholesky_solve(H, 0.5, b)
     assert ok and np.abs((H + 0.5 * np.eye(6)) @ x - b).max() < 1e-12
-    ok, x = M.cholesky_solve6(-H, 0.0, b)
+    ok, x = M.cholesky_solve(-H, 0.0, b)
     assert not ok and not x.any()
     Hn = H.copy()
     Hn[2, 2] = np.nan
-    ok, x = M.cholesky_solve6(Hn, 0.0, b)
+    ok, x = M.cholesky_solve(Hn, 0.0, b)
     assert not ok and not x.any()
 
 
