@@ -18,6 +18,7 @@
 // on the growing branch only (lifecycle_locked_unless); creation, which holds it already, calls the unlocked form.
 #pragma once
 
+#include "carve.h"
 #include "id_hash.h"
 #include "orbgpu.h"
 
@@ -26,17 +27,6 @@
 #include <vector>
 
 namespace orbgpu {
-
-// carve sub-arrays out of one staging block (host and device blocks share the layout)
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
 
 template <typename Grow> int lifecycle_locked_unless(bool enough, std::mutex &lifecycle, Grow grow)
 {

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "proj_internal.h"
 #include "id_table.h"
+#include "ransac_host.h"
 
 #include <algorithm>
 #include <climits>
@@ -1107,11 +1108,8 @@ int orbgpu_pnp_solve_table(const orbgpu_frame *fr, orbgpu_mappoint_table *t, con
         std::memcpy(counts, h + (r_cnt - r_beg), 4 * (size_t)H);
     if (Tcw)
         std::memcpy(Tcw, r.Tcw, sizeof(r.Tcw));
-    if (inliers) {
-        const uint64_t *mask = (const uint64_t *)(h + (r_rm - r_beg));
-        for (int i = 0; i < n; i++)
-            inliers[i] = (uint8_t)((mask[(size_t)i >> 6] >> (i & 63)) & 1u);
-    }
+    if (inliers)
+        mask_to_bytes((const uint64_t *)(h + (r_rm - r_beg)), n, inliers);
     *result = r;
     return ORBGPU_OK;
 }

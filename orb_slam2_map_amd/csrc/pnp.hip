@@ -13,7 +13,9 @@
 #include <cstring>
 #include <vector>
 
+#include "carve.h"
 #include "common.h"
+#include "ransac_host.h"
 #include "staging.h"
 
 namespace orbgpu {
@@ -845,25 +847,11 @@ static void ransac_parameters(int n, double probability, int min_inliers, int ma
                               int &mi, int &max_its)
 {
     const float v = (float)n * epsilon;
-    int nmin = (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : INT_MAX;
-    nmin = std::max(nmin, std::max(min_inliers, min_set));
-    mi = nmin;
-    if (n == 0) {
-        max_its = 1;
-        return;
-    }
-    float eps = epsilon;
-    const float ratio = (float)nmin / (float)n;
-    if (eps < ratio)
-        eps = ratio;
-    int nit;
-    if (nmin == n) {
-        nit = 1;
-    } else {
-        const double w = std::ceil(std::log(1.0 - probability) / std::log(1.0 - std::pow((double)eps, 3.0)));
-        nit = (w >= -2147483648.0 && w <= 2147483647.0) ? (int)w : INT_MAX;  // NaN, +-inf: larger than max_iterations
-    }
-    max_its = std::max(1, std::min(nit, max_iterations));
+    mi = (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : INT_MAX;
+    mi = std::max(mi, std::max(min_inliers, min_set));
+    const float ratio = (float)mi / (float)n;  // n == 0: not used
+    const float eps = epsilon < ratio ? ratio : epsilon;
+    max_its = ransac_max_iterations(n, mi, eps, probability, max_iterations);
 }
 
 static int n_use_of(const orbgpu_pnp_problem &p, int N, int mi, int max_its)
@@ -925,17 +913,11 @@ extern "C" int orbgpu_pnp_ransac_parameters(int32_t n, double probability, int32
 
 extern "C" int orbgpu_pnp_solve_batch_device(int32_t n, const orbgpu_pnp_problem *problems, int32_t device_id, void *hip_stream)
 {
-    ORBGPU_REQUIRE(n >= 0 && n <= 65535 && (n == 0 || problems), "bad arguments");
-    int rc;
-    for (int k = 0; k < n; k++)
-        if ((rc = check_device_problem(problems[k], k)) != ORBGPU_OK)
-            return rc;
-    rc = select_device(device_id);
-    if (rc != ORBGPU_OK || n == 0)
+    PnpWs *wsp;
+    int rc = batch_begin(n, problems, check_device_problem, device_id, wsp);
+    if (rc != ORBGPU_OK || !wsp)
         return rc;
-    PnpWs &ws = per_device_workspace<PnpWs>(device_id);
-    if ((rc = ws.bind(device_id, false)) != ORBGPU_OK)
-        return rc;
+    PnpWs &ws = *wsp;
     size_t rows = 0;
     int max_hyp = 0;
     for (int k = 0; k < n; k++) {
@@ -1026,24 +1008,16 @@ static int solve_host(const orbgpu_pnp_problem *p, int32_t *counts, float *Tcw, 
         for (int k = 0; k < ms; k++)
             ORBGPU_REQUIRE(p->sets[(size_t)h * ms + k] >= 0 && p->sets[(size_t)h * ms + k] < N, "set %d: index %d outside [0, %d)", h,
                            p->sets[(size_t)h * ms + k], N);
-    rc = select_device(device_id);
-    if (rc != ORBGPU_OK)
-        return rc;
-    ORBGPU_HIP_TRY(hipDeviceSynchronize());  // see sim3.hip: the thread's workspace is shared with the device flavours
-    PnpWs &ws = per_device_workspace<PnpWs>(device_id);
-    if ((rc = ws.bind(device_id, true)) != ORBGPU_OK)
-        return rc;
-    auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t words = (size_t)(n1 + 63) / 64, c1 = (size_t)std::max(n1, 1), cH = (size_t)std::max(H, 1), w1 = std::max<size_t>(words, 1);
-    const size_t i_valid = 0, i_x = i_valid + pad(c1), i_kp = i_x + pad(12 * c1), i_o = i_kp + pad(8 * c1), i_s = i_o + pad(4 * c1),
-                 in_bytes = i_s + pad(4 * cH * (size_t)ms);
-    const size_t o_res = 0, o_cnt = o_res + pad(sizeof(orbgpu_pnp_result)), o_T = o_cnt + pad(4 * cH), o_rm = o_T + pad(64 * cH),
-                 o_m = o_rm + pad(8 * w1), out_bytes = o_m + pad(8 * cH * w1);
-    ws.reserve(H_IN, in_bytes);
-    ws.reserve(H_OUT, out_bytes);
-    if ((rc = ws.status()) != ORBGPU_OK)
+    Carver in(16), out(16);
+    const size_t i_valid = in.take(c1), i_x = in.take(12 * c1), i_kp = in.take(8 * c1), i_o = in.take(4 * c1),
+                 i_s = in.take(4 * cH * (size_t)ms);
+    const size_t o_res = out.take(sizeof(orbgpu_pnp_result)), o_cnt = out.take(4 * cH), o_T = out.take(64 * cH),
+                 o_rm = out.take(8 * w1), o_m = out.take(8 * cH * w1);
+    PnpWs *wsp;
+    if ((rc = host_begin(device_id, H_IN, in.off, H_OUT, out.off, wsp)) != ORBGPU_OK)
         return rc;
-    char *din = ws.as<char>(H_IN), *dout = ws.as<char>(H_OUT);
+    PnpWs &ws = *wsp;
     PnpWs::FinishOnError on_error{ws};
     if (n1 > 0) {
         ws.upload(H_IN, p->valid, (size_t)n1, i_valid);
@@ -1055,14 +1029,12 @@ static int solve_host(const orbgpu_pnp_problem *p, int32_t *counts, float *Tcw, 
         ws.upload(H_IN, p->sets, 4 * (size_t)H * (size_t)ms, i_s);
     if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
-    ORBGPU_HIP_TRY(hipMemsetAsync(dout, 0, out_bytes, ws.stream));  // hypotheses beyond n_use come back as zeros
+    ORBGPU_HIP_TRY(hipMemsetAsync(ws.as<char>(H_OUT), 0, out.off, ws.stream));  // hypotheses beyond n_use come back as zeros
     orbgpu_pnp_problem d = *p;
-    d.valid = reinterpret_cast<const uint8_t *>(din + i_valid);
-    d.Xw = reinterpret_cast<const float *>(din + i_x), d.kp = reinterpret_cast<const float *>(din + i_kp);
-    d.octave = reinterpret_cast<const int32_t *>(din + i_o), d.sets = reinterpret_cast<const int32_t *>(din + i_s);
-    d.result = reinterpret_cast<orbgpu_pnp_result *>(dout + o_res);
-    d.counts = reinterpret_cast<int32_t *>(dout + o_cnt), d.Tcw = reinterpret_cast<float *>(dout + o_T);
-    d.refined_mask = reinterpret_cast<uint64_t *>(dout + o_rm), d.masks = reinterpret_cast<uint64_t *>(dout + o_m);
+    d.valid = ws.at<uint8_t>(H_IN, i_valid), d.Xw = ws.at<float>(H_IN, i_x), d.kp = ws.at<float>(H_IN, i_kp);
+    d.octave = ws.at<int32_t>(H_IN, i_o), d.sets = ws.at<int32_t>(H_IN, i_s);
+    d.result = ws.at<orbgpu_pnp_result>(H_OUT, o_res), d.counts = ws.at<int32_t>(H_OUT, o_cnt), d.Tcw = ws.at<float>(H_OUT, o_T);
+    d.refined_mask = ws.at<uint64_t>(H_OUT, o_rm), d.masks = ws.at<uint64_t>(H_OUT, o_m);
     d.indices = nullptr;
     if ((rc = orbgpu_pnp_solve_batch_device(1, &d, device_id, ws.stream)) != ORBGPU_OK)
         return rc;
@@ -1089,8 +1061,7 @@ static int solve_host(const orbgpu_pnp_problem *p, int32_t *counts, float *Tcw, 
         if (Tcw)
             memcpy(Tcw, r.Tcw, sizeof(r.Tcw));
         if (inliers)
-            for (int i = 0; i < n1; i++)
-                inliers[i] = (uint8_t)((mask[(size_t)i >> 6] >> (i & 63)) & 1u);
+            mask_to_bytes(mask.data(), n1, inliers);
     }
     *result = r;
     return ORBGPU_OK;

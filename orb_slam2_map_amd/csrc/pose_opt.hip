@@ -399,17 +399,11 @@ using namespace orbgpu;
 extern "C" int orbgpu_pose_optimization_batch_device(int32_t n, const orbgpu_pose_problem *problems, int32_t device_id,
                                                      void *hip_stream)
 {
-    ORBGPU_REQUIRE(n >= 0 && n <= 65535 && (n == 0 || problems), "bad arguments");
-    int rc;
-    for (int k = 0; k < n; k++)
-        if ((rc = check_problem(problems[k], k)) != ORBGPU_OK)
-            return rc;
-    rc = select_device(device_id);
-    if (rc != ORBGPU_OK || n == 0)
+    PoseWs *wsp;
+    int rc = batch_begin(n, problems, check_problem, device_id, wsp);
+    if (rc != ORBGPU_OK || !wsp)
         return rc;
-    PoseWs &ws = per_device_workspace<PoseWs>(device_id);
-    if ((rc = ws.bind(device_id, false)) != ORBGPU_OK)
-        return rc;
+    PoseWs &ws = *wsp;
     // ORBGPU_DEBUG_POSE_LDS_EDGES=<k> (tests): problems with more than k edges take the global spill path
     const int lds_edges = debug_limit("ORBGPU_DEBUG_POSE_LDS_EDGES", PO_LDS_EDGES);
     size_t spill_edges = 0;

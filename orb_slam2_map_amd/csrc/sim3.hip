@@ -3,12 +3,13 @@
 // (H1-H8, "OpenCV boundary unpinned") is in include/orbgpu.h and tests/sim3_model.py; the arithmetic below is the
 // model's operation for operation (-ffp-contract=off), only atan2 / sin / cos come from another libm.
 #include <algorithm>
-#include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "carve.h"
 #include "common.h"
+#include "ransac_host.h"
 #include "staging.h"
 
 namespace orbgpu {
@@ -402,17 +403,7 @@ struct Sim3Ws : Staging<N_BUF> {
 
 static int ransac_iterations(int n, double probability, int min_inliers, int max_iterations)
 {
-    if (n == 0)
-        return 1;
-    int nit;
-    if (min_inliers == n) {
-        nit = 1;
-    } else {
-        const float epsilon = (float)min_inliers / (float)n;
-        const double v = std::ceil(std::log(1.0 - probability) / std::log(1.0 - std::pow((double)epsilon, 3.0)));
-        nit = (v >= -2147483648.0 && v <= 2147483647.0) ? (int)v : INT_MAX;  // NaN, +-inf: larger than max_iterations
-    }
-    return std::max(1, std::min(nit, max_iterations));
+    return ransac_max_iterations(n, min_inliers, (float)min_inliers / (float)n, probability, max_iterations);
 }
 
 static int check_common(const orbgpu_sim3_problem &p, int k)
@@ -454,17 +445,11 @@ extern "C" int orbgpu_sim3_ransac_iterations(int32_t n, double probability, int3
 extern "C" int orbgpu_sim3_solve_batch_device(int32_t n, const orbgpu_sim3_problem *problems, int32_t device_id,
                                               void *hip_stream)
 {
-    ORBGPU_REQUIRE(n >= 0 && n <= 65535 && (n == 0 || problems), "bad arguments");
-    int rc;
-    for (int k = 0; k < n; k++)
-        if ((rc = check_device_problem(problems[k], k)) != ORBGPU_OK)
-            return rc;
-    rc = select_device(device_id);
-    if (rc != ORBGPU_OK || n == 0)
+    Sim3Ws *wsp;
+    int rc = batch_begin(n, problems, check_device_problem, device_id, wsp);
+    if (rc != ORBGPU_OK || !wsp)
         return rc;
-    Sim3Ws &ws = per_device_workspace<Sim3Ws>(device_id);
-    if ((rc = ws.bind(device_id, false)) != ORBGPU_OK)
-        return rc;
+    Sim3Ws &ws = *wsp;
     size_t rows = 0;
     int max_hyp = 0;
     for (int k = 0; k < n; k++) {
@@ -554,28 +539,18 @@ static int solve_host(const orbgpu_sim3_problem *p, int32_t *counts, float *R, f
         for (int k = 0; k < 3; k++)
             ORBGPU_REQUIRE(p->triples[3 * h + k] >= 0 && p->triples[3 * h + k] < N, "triple %d: index %d outside [0, %d)", h,
                            p->triples[3 * h + k], N);
-    rc = select_device(device_id);
-    if (rc != ORBGPU_OK)
-        return rc;
-    // this call runs on a stream of its own and shares the thread's workspace with the device flavours: whatever the thread
-    // enqueued through them on other streams must have left it
-    ORBGPU_HIP_TRY(hipDeviceSynchronize());
-    Sim3Ws &ws = per_device_workspace<Sim3Ws>(device_id);
-    if ((rc = ws.bind(device_id, true)) != ORBGPU_OK)
-        return rc;
     // one staging block each way; every segment starts on a multiple of 16 bytes
-    auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t words = (size_t)(n1 + 63) / 64, c1 = (size_t)std::max(n1, 1), cH = (size_t)std::max(H, 1);
-    const size_t i_valid = 0, i_x1 = i_valid + pad(c1), i_x2 = i_x1 + pad(12 * c1), i_o1 = i_x2 + pad(12 * c1),
-                 i_o2 = i_o1 + pad(4 * c1), i_tr = i_o2 + pad(4 * c1), in_bytes = i_tr + pad(12 * cH);
-    const size_t o_res = 0, o_cnt = o_res + pad(sizeof(orbgpu_sim3_result)), o_R = o_cnt + pad(4 * cH), o_t = o_R + pad(36 * cH),
-                 o_s = o_t + pad(12 * cH), o_T = o_s + pad(4 * cH), o_m = o_T + pad(64 * cH),
-                 out_bytes = o_m + pad(8 * cH * std::max<size_t>(words, 1));
-    ws.reserve(H_IN, in_bytes);
-    ws.reserve(H_OUT, out_bytes);
-    if ((rc = ws.status()) != ORBGPU_OK)
+    Carver in(16), out(16);
+    const size_t i_valid = in.take(c1), i_x1 = in.take(12 * c1), i_x2 = in.take(12 * c1), i_o1 = in.take(4 * c1),
+                 i_o2 = in.take(4 * c1), i_tr = in.take(12 * cH);
+    const size_t o_res = out.take(sizeof(orbgpu_sim3_result)), o_cnt = out.take(4 * cH), o_R = out.take(36 * cH),
+                 o_t = out.take(12 * cH), o_s = out.take(4 * cH), o_T = out.take(64 * cH),
+                 o_m = out.take(8 * cH * std::max<size_t>(words, 1));
+    Sim3Ws *wsp;
+    if ((rc = host_begin(device_id, H_IN, in.off, H_OUT, out.off, wsp)) != ORBGPU_OK)
         return rc;
-    char *din = ws.as<char>(H_IN), *dout = ws.as<char>(H_OUT);
+    Sim3Ws &ws = *wsp;
     Sim3Ws::FinishOnError on_error{ws};
     if (n1 > 0) {
         ws.upload(H_IN, p->valid, (size_t)n1, i_valid);
@@ -589,16 +564,13 @@ static int solve_host(const orbgpu_sim3_problem *p, int32_t *counts, float *R, f
     if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
     if (all)  // hypotheses beyond n_use are not written by the kernels: they come back as zeros
-        ORBGPU_HIP_TRY(hipMemsetAsync(dout, 0, out_bytes, ws.stream));
+        ORBGPU_HIP_TRY(hipMemsetAsync(ws.as<char>(H_OUT), 0, out.off, ws.stream));
     orbgpu_sim3_problem d = *p;
-    d.valid = reinterpret_cast<const uint8_t *>(din + i_valid);
-    d.Xw1 = reinterpret_cast<const float *>(din + i_x1), d.Xw2 = reinterpret_cast<const float *>(din + i_x2);
-    d.octave1 = reinterpret_cast<const int32_t *>(din + i_o1), d.octave2 = reinterpret_cast<const int32_t *>(din + i_o2);
-    d.triples = reinterpret_cast<const int32_t *>(din + i_tr);
-    d.result = reinterpret_cast<orbgpu_sim3_result *>(dout + o_res);
-    d.counts = reinterpret_cast<int32_t *>(dout + o_cnt), d.R = reinterpret_cast<float *>(dout + o_R);
-    d.t = reinterpret_cast<float *>(dout + o_t), d.s = reinterpret_cast<float *>(dout + o_s);
-    d.T12 = reinterpret_cast<float *>(dout + o_T), d.masks = reinterpret_cast<uint64_t *>(dout + o_m);
+    d.valid = ws.at<uint8_t>(H_IN, i_valid), d.Xw1 = ws.at<float>(H_IN, i_x1), d.Xw2 = ws.at<float>(H_IN, i_x2);
+    d.octave1 = ws.at<int32_t>(H_IN, i_o1), d.octave2 = ws.at<int32_t>(H_IN, i_o2), d.triples = ws.at<int32_t>(H_IN, i_tr);
+    d.result = ws.at<orbgpu_sim3_result>(H_OUT, o_res), d.counts = ws.at<int32_t>(H_OUT, o_cnt);
+    d.R = ws.at<float>(H_OUT, o_R), d.t = ws.at<float>(H_OUT, o_t), d.s = ws.at<float>(H_OUT, o_s);
+    d.T12 = ws.at<float>(H_OUT, o_T), d.masks = ws.at<uint64_t>(H_OUT, o_m);
     d.indices1 = nullptr;
     if ((rc = orbgpu_sim3_solve_batch_device(1, &d, device_id, ws.stream)) != ORBGPU_OK)
         return rc;
@@ -641,8 +613,7 @@ static int solve_host(const orbgpu_sim3_problem *p, int32_t *counts, float *R, f
     if ((rc = ws.finish()) != ORBGPU_OK)
         return rc;
     if (inliers)
-        for (int i = 0; i < n1; i++)
-            inliers[i] = (uint8_t)((mask[(size_t)i >> 6] >> (i & 63)) & 1u);
+        mask_to_bytes(mask.data(), n1, inliers);
     *result = r;
     return ORBGPU_OK;
 }

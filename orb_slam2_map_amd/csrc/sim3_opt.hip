@@ -12,6 +12,7 @@
 #include <cstring>
 #include <vector>
 
+#include "carve.h"
 #include "common.h"
 #include "opt_math.h"
 #include "staging.h"
@@ -544,17 +545,11 @@ using namespace orbgpu::sim3opt;
 extern "C" int orbgpu_sim3_optimize_batch_device(int32_t n, const orbgpu_sim3_opt_problem *problems, int32_t device_id,
                                                  void *hip_stream)
 {
-    ORBGPU_REQUIRE(n >= 0 && n <= 65535 && (n == 0 || problems), "bad arguments");
-    int rc;
-    for (int k = 0; k < n; k++)
-        if ((rc = check_device_problem(problems[k], k)) != ORBGPU_OK)
-            return rc;
-    rc = select_device(device_id);
-    if (rc != ORBGPU_OK || n == 0)
+    Sim3OptWs *wsp;
+    int rc = batch_begin(n, problems, check_device_problem, device_id, wsp);
+    if (rc != ORBGPU_OK || !wsp)
         return rc;
-    Sim3OptWs &ws = per_device_workspace<Sim3OptWs>(device_id);
-    if ((rc = ws.bind(device_id, false)) != ORBGPU_OK)
-        return rc;
+    Sim3OptWs &ws = *wsp;
     // ORBGPU_DEBUG_SIM3OPT_LDS_PAIRS=<k> (tests): problems with more than k correspondences take the global spill path
     const int lds_pairs = debug_limit("ORBGPU_DEBUG_SIM3OPT_LDS_PAIRS", SO_LDS_PAIRS);
     size_t spill_rows = 0;
@@ -625,27 +620,17 @@ extern "C" int orbgpu_sim3_optimize(const orbgpu_sim3_opt_problem *p, uint8_t *i
     if (rc != ORBGPU_OK)
         return rc;
     ORBGPU_REQUIRE(p->n1 == 0 || inlier, "null inlier array");
-    rc = select_device(device_id);
-    if (rc != ORBGPU_OK)
-        return rc;
-    // this call runs on a stream of its own and shares the thread's workspace with the device flavours: whatever the thread
-    // enqueued through them on other streams must have left it
-    ORBGPU_HIP_TRY(hipDeviceSynchronize());
-    Sim3OptWs &ws = per_device_workspace<Sim3OptWs>(device_id);
-    if ((rc = ws.bind(device_id, true)) != ORBGPU_OK)
-        return rc;
     // one staging block each way; every segment starts on a multiple of 16 bytes
-    auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const int n1 = p->n1;
     const size_t c1 = (size_t)std::max(n1, 1);
-    const size_t i_valid = 0, i_x1 = i_valid + pad(c1), i_x2 = i_x1 + pad(12 * c1), i_o1 = i_x2 + pad(12 * c1),
-                 i_o2 = i_o1 + pad(4 * c1), i_k1 = i_o2 + pad(4 * c1), i_k2 = i_k1 + pad(8 * c1), in_bytes = i_k2 + pad(8 * c1);
-    const size_t o_res = 0, o_inl = o_res + pad(sizeof(orbgpu_sim3_opt_result)), out_bytes = o_inl + pad(c1);
-    ws.reserve(H_IN, in_bytes);
-    ws.reserve(H_OUT, out_bytes);
-    if ((rc = ws.status()) != ORBGPU_OK)
+    Carver in(16), out(16);
+    const size_t i_valid = in.take(c1), i_x1 = in.take(12 * c1), i_x2 = in.take(12 * c1), i_o1 = in.take(4 * c1),
+                 i_o2 = in.take(4 * c1), i_k1 = in.take(8 * c1), i_k2 = in.take(8 * c1);
+    const size_t o_res = out.take(sizeof(orbgpu_sim3_opt_result)), o_inl = out.take(c1);
+    Sim3OptWs *wsp;
+    if ((rc = host_begin(device_id, H_IN, in.off, H_OUT, out.off, wsp)) != ORBGPU_OK)
         return rc;
-    char *din = ws.as<char>(H_IN), *dout = ws.as<char>(H_OUT);
+    Sim3OptWs &ws = *wsp;
     Sim3OptWs::FinishOnError on_error{ws};
     if (n1 > 0) {
         ws.upload(H_IN, p->valid, (size_t)n1, i_valid);
@@ -660,12 +645,10 @@ extern "C" int orbgpu_sim3_optimize(const orbgpu_sim3_opt_problem *p, uint8_t *i
     if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
     orbgpu_sim3_opt_problem d = *p;
-    d.valid = reinterpret_cast<const uint8_t *>(din + i_valid);
-    d.Xw1 = reinterpret_cast<const float *>(din + i_x1), d.Xw2 = reinterpret_cast<const float *>(din + i_x2);
-    d.octave1 = reinterpret_cast<const int32_t *>(din + i_o1), d.octave2 = reinterpret_cast<const int32_t *>(din + i_o2);
-    d.kp1_xy = reinterpret_cast<const float *>(din + i_k1), d.kp2_xy = reinterpret_cast<const float *>(din + i_k2);
-    d.inlier = reinterpret_cast<uint8_t *>(dout + o_inl);
-    d.result = reinterpret_cast<orbgpu_sim3_opt_result *>(dout + o_res);
+    d.valid = ws.at<uint8_t>(H_IN, i_valid), d.Xw1 = ws.at<float>(H_IN, i_x1), d.Xw2 = ws.at<float>(H_IN, i_x2);
+    d.octave1 = ws.at<int32_t>(H_IN, i_o1), d.octave2 = ws.at<int32_t>(H_IN, i_o2);
+    d.kp1_xy = ws.at<float>(H_IN, i_k1), d.kp2_xy = ws.at<float>(H_IN, i_k2);
+    d.inlier = ws.at<uint8_t>(H_OUT, o_inl), d.result = ws.at<orbgpu_sim3_opt_result>(H_OUT, o_res);
     if ((rc = orbgpu_sim3_optimize_batch_device(1, &d, device_id, ws.stream)) != ORBGPU_OK)
         return rc;
     orbgpu_sim3_opt_result r;

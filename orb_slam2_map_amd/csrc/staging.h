@@ -44,6 +44,8 @@ template <int N> struct Staging {
     // Reserve, upload, download: the first failure sticks (status()), later steps do nothing, so a run of them needs no
     // check per line -- one status() before the first launch that reads the buffers, and finish() at the end.
     template <typename T> T *as(int i) const { return buf[i].template as<T>(); }
+    // the segment of buf[i] that starts `offset` bytes in (carve.h hands out the offsets)
+    template <typename T> T *at(int i, size_t offset) const { return reinterpret_cast<T *>(as<char>(i) + offset); }
     int status() const { return rc; }
     void reserve(int i, size_t bytes)
     {
@@ -120,7 +122,7 @@ template <int N> struct Staging {
             return;
         }
         pending = true;
-        char *dev = buf[i].template as<char>() + offset;
+        char *dev = at<char>(i, offset);
         hipError_t e = to_device ? hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream)
                                  : hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream);
         if (e != hipSuccess) {
@@ -129,6 +131,40 @@ template <int N> struct Staging {
         }
     }
 };
+
+// ---- how the solver and optimiser entry points (pose_opt.hip, sim3.hip, sim3_opt.hip, pnp.hip) begin ----------------------
+// A *_batch_device entry: at most 65535 problems (the grid's y extent), each accepted by check(problem, index); then this
+// thread's workspace, bound without a stream.  ws stays null for an empty batch, which only selects the device.
+template <typename Ws, typename Problem, typename Check>
+int batch_begin(int32_t n, const Problem *problems, Check check, int32_t device_id, Ws *&ws)
+{
+    ws = nullptr;
+    ORBGPU_REQUIRE(n >= 0 && n <= 65535 && (n == 0 || problems), "bad arguments");
+    int rc = ORBGPU_OK;
+    for (int k = 0; k < n && rc == ORBGPU_OK; k++)
+        rc = check(problems[k], k);
+    if (rc != ORBGPU_OK || (rc = select_device(device_id)) != ORBGPU_OK || n == 0)
+        return rc;
+    ws = &per_device_workspace<Ws>(device_id);
+    return ws->bind(device_id, false);
+}
+
+// A host flavour that stages its problem in one carved block each way (sim3.hip, sim3_opt.hip, pnp.hip).  It runs on a
+// stream of its own and shares the thread's workspace with the device flavours: whatever the thread enqueued through them
+// on other streams must have left it, hence the device-wide wait (pose_opt.hip's does not wait: DESIGN.md 9.21).
+template <typename Ws> int host_begin(int32_t device_id, int in, size_t in_bytes, int out, size_t out_bytes, Ws *&ws)
+{
+    int rc = select_device(device_id);
+    if (rc != ORBGPU_OK)
+        return rc;
+    ORBGPU_HIP_TRY(hipDeviceSynchronize());
+    ws = &per_device_workspace<Ws>(device_id);
+    if ((rc = ws->bind(device_id, true)) != ORBGPU_OK)
+        return rc;
+    ws->reserve(in, in_bytes);
+    ws->reserve(out, out_bytes);
+    return ws->status();
+}
 
 // ---- the two test hooks of the device optimisers (pose_opt.hip, sim3_opt.hip) -------------------------------------------
 // A capacity of `max` records in LDS, lowered to k (clamped to [0, max]) while the environment variable `name` is set

@@ -351,6 +351,47 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+# What the solver and optimiser families (pose_optimization, sim3_solve, sim3_optimize, pnp_solve) share: the two device
+# flavours' calls, and the setters of their *_problem builders.
+def _batch_device(family, cls, make, problems, stream, device_id):
+    """orbgpu_<family>_batch_device over make(p), a cls structure, of every problem."""
+    arr = (cls * max(len(problems), 1))(*[make(p) for p in problems])
+    fn = getattr(lib(), "orbgpu_%s_batch_device" % family)
+    fn.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    check(fn(len(problems), arr, device_id, stream))
+
+
+def _one_device(family, q, stream, device_id):
+    """orbgpu_<family>_device over the problem structure q."""
+    fn = getattr(lib(), "orbgpu_%s_device" % family)
+    fn.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    check(fn(C.byref(q), device_id, stream))
+
+
+def _set_pointers(q, p, names):
+    for k in names:
+        setattr(q, k, p.get(k) or None)
+
+
+def _set_floats(field, a):
+    """A float array field of a structure (4x4, 3x3, a vector) from anything of that many elements."""
+    field[:] = np.asarray(a, np.float32).reshape(len(field)).tolist()
+
+
+def _set_intrinsics(q, K, suffix=""):
+    fx, fy, cx, cy = (float(k) for k in K)
+    for name, v in (("fx", fx), ("fy", fy), ("cx", cx), ("cy", cy)):
+        setattr(q, name + suffix, v)
+
+
+def _set_levels(q, p, field):
+    """q.<field>[l] per pyramid level from p[field]; nlevels from p, by default the array's length."""
+    sg = np.asarray(p[field], np.float32)
+    q.nlevels = int(p.get("nlevels", len(sg)))
+    for l in range(min(len(sg), MAX_LEVELS)):
+        getattr(q, field)[l] = float(sg[l])
+
+
 def device_count():
     return lib().orbgpu_device_count()
 
@@ -917,37 +958,32 @@ def pose_optimization(frame, has_mp, world_pos, Tcw, inv_level_sigma2, fx, fy, c
     return ni.value, T, out[:n], res.as_dict()
 
 
-def _pose_problem_array(problems):
-    arr = (PoseProblem * max(len(problems), 1))()
-    keep = []
-    for k, p in enumerate(problems):
-        T = np.ascontiguousarray(p["Tcw"], np.float32)
-        sg = np.ascontiguousarray(p["inv_level_sigma2"], np.float32)
-        keep += [T, sg]
-        arr[k].frame = C.addressof(p["frame"])
-        arr[k].d_kp_to_mp, arr[k].d_world_pos, arr[k].rows = p["d_kp_to_mp"], p["d_world_pos"], int(p["rows"])
-        arr[k].Tcw, arr[k].inv_level_sigma2 = T.ctypes.data, sg.ctypes.data
-        arr[k].fx, arr[k].fy, arr[k].cx, arr[k].cy, arr[k].mbf = p["fx"], p["fy"], p["cx"], p["cy"], p["mbf"]
-        arr[k].d_outlier, arr[k].d_result = p["d_outlier"], p["d_result"]
-    return arr, keep
+def _pose_problem(p, keep):
+    """A PoseProblem from a dict; keep takes the host arrays it points to."""
+    q = PoseProblem()
+    T = np.ascontiguousarray(p["Tcw"], np.float32)
+    sg = np.ascontiguousarray(p["inv_level_sigma2"], np.float32)
+    keep += [T, sg]
+    q.frame = C.addressof(p["frame"])
+    q.d_kp_to_mp, q.d_world_pos, q.rows = p["d_kp_to_mp"], p["d_world_pos"], int(p["rows"])
+    q.Tcw, q.inv_level_sigma2 = T.ctypes.data, sg.ctypes.data
+    q.fx, q.fy, q.cx, q.cy, q.mbf = p["fx"], p["fy"], p["cx"], p["cy"], p["mbf"]
+    q.d_outlier, q.d_result = p["d_outlier"], p["d_result"]
+    return q
 
 
 def pose_optimization_batch_device(problems, stream=0, device_id=0):
     """n independent Optimizer::PoseOptimization problems in one launch (orbgpu_pose_optimization_batch_device); not
     synchronised.  problems: list of dicts with frame (DeviceFrameView), d_kp_to_mp, d_world_pos, rows, Tcw (4x4),
     inv_level_sigma2, fx, fy, cx, cy, mbf, d_outlier, d_result (device pointers; d_result holds a PoseResult)."""
-    arr, keep = _pose_problem_array(problems)
-    L = lib()
-    L.orbgpu_pose_optimization_batch_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-    check(L.orbgpu_pose_optimization_batch_device(len(problems), arr, device_id, stream))
+    keep = []
+    _batch_device("pose_optimization", PoseProblem, lambda p: _pose_problem(p, keep), problems, stream, device_id)
 
 
 def pose_optimization_device(problem, stream=0, device_id=0):
     """One problem (orbgpu_pose_optimization_device); see pose_optimization_batch_device."""
-    arr, keep = _pose_problem_array([problem])
-    L = lib()
-    L.orbgpu_pose_optimization_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-    check(L.orbgpu_pose_optimization_device(arr, device_id, stream))
+    keep = []
+    _one_device("pose_optimization", _pose_problem(problem, keep), stream, device_id)
 
 
 def pose_optimization_table(dframe, table, kp_ids, Tcw, inv_level_sigma2, fx, fy, cx, cy, mbf, outlier=None):
@@ -996,16 +1032,10 @@ def sim3_problem(p):
     include/orbgpu.h as integers (device or host addresses; missing ones are NULL)."""
     q = Sim3Problem()
     q.n1, q.n_hyp = int(p["n1"]), int(p["n_hyp"])
-    for k in _SIM3_PTRS:
-        setattr(q, k, p.get(k) or None)
-    q.T1w[:] = np.asarray(p["T1w"], np.float32).reshape(16).tolist()
-    q.T2w[:] = np.asarray(p["T2w"], np.float32).reshape(16).tolist()
-    q.fx1, q.fy1, q.cx1, q.cy1 = (float(k) for k in p["K1"])
-    q.fx2, q.fy2, q.cx2, q.cy2 = (float(k) for k in p["K2"])
-    sg = np.asarray(p["level_sigma2"], np.float32)
-    q.nlevels = int(p.get("nlevels", len(sg)))
-    for l in range(min(len(sg), MAX_LEVELS)):
-        q.level_sigma2[l] = float(sg[l])
+    _set_pointers(q, p, _SIM3_PTRS)
+    _set_floats(q.T1w, p["T1w"]), _set_floats(q.T2w, p["T2w"])
+    _set_intrinsics(q, p["K1"], "1"), _set_intrinsics(q, p["K2"], "2")
+    _set_levels(q, p, "level_sigma2")
     q.fix_scale, q.min_inliers, q.max_iterations = int(p["fix_scale"]), int(p["min_inliers"]), int(p["max_iterations"])
     q.probability = float(p["probability"])
     q.start_iteration, q.best_so_far = int(p.get("start_iteration", 0)), int(p.get("best_so_far", 0))
@@ -1016,20 +1046,12 @@ def sim3_solve_batch_device(problems, stream=0, device_id=0):
     """All candidates of a LoopClosing::ComputeSim3 call in one launch sequence (orbgpu_sim3_solve_batch_device).
     problems: dicts as sim3_problem takes them, with device pointers.  Waits once for the stream (N is read back to compute
     max_its on the host); the hypotheses and the acceptance scan are enqueued and not waited for."""
-    arr = (Sim3Problem * max(len(problems), 1))()
-    for k, p in enumerate(problems):
-        arr[k] = sim3_problem(p)
-    L = lib()
-    L.orbgpu_sim3_solve_batch_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-    check(L.orbgpu_sim3_solve_batch_device(len(problems), arr, device_id, stream))
+    _batch_device("sim3_solve", Sim3Problem, sim3_problem, problems, stream, device_id)
 
 
 def sim3_solve_device(problem, stream=0, device_id=0):
     """One candidate (orbgpu_sim3_solve_device); see sim3_solve_batch_device."""
-    q = sim3_problem(problem)
-    L = lib()
-    L.orbgpu_sim3_solve_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-    check(L.orbgpu_sim3_solve_device(C.byref(q), device_id, stream))
+    _one_device("sim3_solve", sim3_problem(problem), stream, device_id)
 
 
 def sim3_solve(valid, Xw1, Xw2, octave1, octave2, T1w, T2w, K1, K2, level_sigma2, triples, fix_scale=False,
@@ -1089,18 +1111,11 @@ def sim3_opt_problem(p):
     missing ones are NULL)."""
     q = Sim3OptProblem()
     q.n1 = int(p["n1"])
-    for k in _SIM3OPT_PTRS:
-        setattr(q, k, p.get(k) or None)
-    q.T1w[:] = np.asarray(p["T1w"], np.float32).reshape(16).tolist()
-    q.T2w[:] = np.asarray(p["T2w"], np.float32).reshape(16).tolist()
-    q.fx1, q.fy1, q.cx1, q.cy1 = (float(k) for k in p["K1"])
-    q.fx2, q.fy2, q.cx2, q.cy2 = (float(k) for k in p["K2"])
-    sg = np.asarray(p["inv_level_sigma2"], np.float32)
-    q.nlevels = int(p.get("nlevels", len(sg)))
-    for l in range(min(len(sg), MAX_LEVELS)):
-        q.inv_level_sigma2[l] = float(sg[l])
-    q.R12[:] = np.asarray(p["R12"], np.float32).reshape(9).tolist()
-    q.t12[:] = np.asarray(p["t12"], np.float32).reshape(3).tolist()
+    _set_pointers(q, p, _SIM3OPT_PTRS)
+    _set_floats(q.T1w, p["T1w"]), _set_floats(q.T2w, p["T2w"])
+    _set_intrinsics(q, p["K1"], "1"), _set_intrinsics(q, p["K2"], "2")
+    _set_levels(q, p, "inv_level_sigma2")
+    _set_floats(q.R12, p["R12"]), _set_floats(q.t12, p["t12"])
     q.s12, q.th2, q.fix_scale = float(np.float32(p["s12"])), float(np.float32(p["th2"])), int(bool(p["fix_scale"]))
     return q
 
@@ -1108,20 +1123,12 @@ def sim3_opt_problem(p):
 def sim3_optimize_batch_device(problems, stream=0, device_id=0):
     """All candidates of a LoopClosing::ComputeSim3 call in ONE launch (orbgpu_sim3_optimize_batch_device); enqueued, not
     synchronised.  problems: dicts as sim3_opt_problem takes them, with device pointers; result holds a Sim3OptResult."""
-    arr = (Sim3OptProblem * max(len(problems), 1))()
-    for k, p in enumerate(problems):
-        arr[k] = sim3_opt_problem(p)
-    L = lib()
-    L.orbgpu_sim3_optimize_batch_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-    check(L.orbgpu_sim3_optimize_batch_device(len(problems), arr, device_id, stream))
+    _batch_device("sim3_optimize", Sim3OptProblem, sim3_opt_problem, problems, stream, device_id)
 
 
 def sim3_optimize_device(problem, stream=0, device_id=0):
     """One candidate (orbgpu_sim3_optimize_device); see sim3_optimize_batch_device."""
-    q = sim3_opt_problem(problem)
-    L = lib()
-    L.orbgpu_sim3_optimize_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-    check(L.orbgpu_sim3_optimize_device(C.byref(q), device_id, stream))
+    _one_device("sim3_optimize", sim3_opt_problem(problem), stream, device_id)
 
 
 def sim3_optimize(valid, Xw1, Xw2, octave1, octave2, kp1_xy, kp2_xy, T1w, T2w, K1, K2, inv_level_sigma2, R12, t12, s12,
@@ -1185,13 +1192,9 @@ def pnp_problem(p):
     of include/orbgpu.h as integers (device or host addresses; missing ones are NULL)."""
     q = PnpProblem()
     q.n1, q.n_hyp = int(p["n1"]), int(p["n_hyp"])
-    for k in _PNP_PTRS:
-        setattr(q, k, p.get(k) or None)
-    q.fx, q.fy, q.cx, q.cy = (float(k) for k in p["K"])
-    sg = np.asarray(p["level_sigma2"], np.float32)
-    q.nlevels = int(p.get("nlevels", len(sg)))
-    for l in range(min(len(sg), MAX_LEVELS)):
-        q.level_sigma2[l] = float(sg[l])
+    _set_pointers(q, p, _PNP_PTRS)
+    _set_intrinsics(q, p["K"])
+    _set_levels(q, p, "level_sigma2")
     q.min_set, q.min_inliers, q.max_iterations = int(p["min_set"]), int(p["min_inliers"]), int(p["max_iterations"])
     q.epsilon, q.th2, q.probability = float(p["epsilon"]), float(p["th2"]), float(p["probability"])
     q.start_iteration, q.best_so_far = int(p.get("start_iteration", 0)), int(p.get("best_so_far", 0))
@@ -1203,20 +1206,12 @@ def pnp_solve_batch_device(problems, stream=0, device_id=0):
     """All candidates of a Tracking::Relocalization call in one launch sequence (orbgpu_pnp_solve_batch_device).
     problems: dicts as pnp_problem takes them, with device pointers.  Waits once for the stream (N is read back for the
     RANSAC parameters); the hypotheses and the acceptance scan are enqueued and not waited for."""
-    arr = (PnpProblem * max(len(problems), 1))()
-    for k, p in enumerate(problems):
-        arr[k] = pnp_problem(p)
-    L = lib()
-    L.orbgpu_pnp_solve_batch_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-    check(L.orbgpu_pnp_solve_batch_device(len(problems), arr, device_id, stream))
+    _batch_device("pnp_solve", PnpProblem, pnp_problem, problems, stream, device_id)
 
 
 def pnp_solve_device(problem, stream=0, device_id=0):
     """One candidate (orbgpu_pnp_solve_device); see pnp_solve_batch_device."""
-    q = pnp_problem(problem)
-    L = lib()
-    L.orbgpu_pnp_solve_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-    check(L.orbgpu_pnp_solve_device(C.byref(q), device_id, stream))
+    _one_device("pnp_solve", pnp_problem(problem), stream, device_id)
 
 
 def _pnp_host_problem(sc, keep, **over):

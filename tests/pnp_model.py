@@ -10,6 +10,8 @@ import math
 
 import numpy as np
 
+from sim3_model import _log, iteration_cap, reference_random_int  # noqa: F401  (what the two solvers' models share)
+
 f32, f64 = np.float32, np.float64
 NLEVELS = 8
 SIGMA2 = (f32(1.2) ** np.arange(NLEVELS, dtype=f32)) ** 2
@@ -24,10 +26,6 @@ PAIRS6 = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
 
 
 # ---- P3 ----------------------------------------------------------------------------------------------------------------
-def _log(x):
-    return math.nan if (x != x or x < 0) else (-math.inf if x == 0 else math.log(x))
-
-
 def ransac_parameters(n, probability, min_inliers, max_iterations, min_set, epsilon):
     """SetRansacParameters (:121-152).  Returns (adjusted min_inliers, max_its)."""
     with np.errstate(all="ignore"):
@@ -40,27 +38,11 @@ def ransac_parameters(n, probability, min_inliers, max_iterations, min_set, epsi
     ratio = f32(nmin) / f32(n)
     if eps < ratio:
         eps = ratio
-    if nmin == n:
-        nit = 1
-    else:
-        with np.errstate(all="ignore"):
-            try:
-                pw = math.pow(float(eps), 3.0)
-            except OverflowError:
-                pw = math.inf
-            v = np.ceil(f64(_log(1.0 - probability)) / f64(_log(1.0 - pw)))
-        nit = int(v) if np.isfinite(v) and -2 ** 31 <= v <= INT_MAX else INT_MAX
+    nit = 1 if nmin == n else iteration_cap(probability, eps)
     return nmin, max(1, min(nit, max_iterations))
 
 
-# ---- P4 ----------------------------------------------------------------------------------------------------------------
-def reference_random_int(rand, rand_max=2147483647):
-    def f(lo, hi):
-        d = hi - lo + 1
-        return int((float(rand()) / (float(rand_max) + 1.0)) * d) + lo
-    return f
-
-
+# ---- P4 (reference_random_int: sim3_model.py) --------------------------------------------------------------------------
 def sample_sets(n, iterations, min_set, random_int):
     """The draw of PnPsolver::iterate (:188-201) replayed: position idx, not randi, is overwritten with the last entry,
     so an index can come twice.  random_int(lo, hi) is called min_set times per iteration.  n < min_set and a random_int

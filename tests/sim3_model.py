@@ -70,16 +70,21 @@ def _log(x):
     return math.nan if (x != x or x < 0) else (-math.inf if x == 0 else math.log(x))
 
 
+def iteration_cap(probability, eps):
+    """ceil(log(1 - p) / log(1 - eps^3)) as an int, for both solvers (pnp_model.py); eps: a float32's value."""
+    with np.errstate(all="ignore"):  # libm's log and pow as the C++ side calls them; the division and ceil in IEEE
+        try:
+            pw = math.pow(float(eps), 3.0)
+        except OverflowError:  # C's pow returns inf
+            pw = math.inf
+        v = np.ceil(f64(_log(1.0 - probability)) / f64(_log(1.0 - pw)))
+    return int(v) if np.isfinite(v) and -2 ** 31 <= v <= INT_MAX else INT_MAX  # NaN, +-inf: larger than max_iterations
+
+
 def ransac_iterations(n, probability, min_inliers, max_iterations):
     if n == 0:
         return 1
-    if min_inliers == n:
-        nit = 1
-    else:
-        eps = float(f32(min_inliers) / f32(n))
-        with np.errstate(all="ignore"):  # libm's log and pow as the C++ side calls them; the division and ceil in IEEE
-            v = np.ceil(f64(_log(1.0 - probability)) / f64(_log(1.0 - math.pow(eps, 3.0))))
-        nit = int(v) if np.isfinite(v) and -2 ** 31 <= v <= INT_MAX else INT_MAX  # NaN, +-inf: larger than max_iterations
+    nit = 1 if min_inliers == n else iteration_cap(probability, f32(min_inliers) / f32(n))
     return max(1, min(nit, max_iterations))
 
 
