@@ -995,6 +995,115 @@ int orbgpu_pnp_solve_table(const orbgpu_frame *fr, orbgpu_mappoint_table *t, con
                            const orbgpu_pnp_problem *params, int32_t *counts, float *Tcw, uint8_t *inliers,
                            orbgpu_pnp_result *result);
 
+/* ---- Initializer (Initializer.cc, H / F RANSAC and two-view reconstruction): the monocular bootstrap on the device ------
+ * The consumer of orbgpu_search_for_initialization (Tracking.cc:891): all homography and fundamental-matrix hypotheses at
+ * once, one wave each; the reference's scans, its branch, the 8 (Faugeras) or 4 (DecomposeE) motions, CheckRT with a
+ * per-lane triangulation, and its accept rule.  Every result is "vs CPU restatement; OpenCV boundary unpinned";
+ * tests/init_model.py is the restatement.  Conventions I1-I10:
+ *   I1 rows (:54-63)      pair i is kept iff 0 <= matches12[i] < n2; a value >= n2 is not kept and counted in n_bad_index.
+ *                         N kept pairs, compacted in index order.
+ *   I2 sets (:78-97)      the library draws nothing: sets[h][8] index the compacted list (orbgpu_shim replays the draw).  A
+ *                         set with an index outside [0, N) is never read through: score 0, empty mask, cannot be selected,
+ *                         counted (once) in n_bad_set; EINVAL in the host flavours before anything is launched.  N < 8:
+ *                         nothing is computed, success = 0, every output zero.  A repeated index is computed like any other.
+ *   I3 Normalize (:749-795)  over ALL key points of a frame: the reference's running float sums in index order (mean, then
+ *                         mean absolute deviation), mean = sum / (float)n, sX = (float)(1.0 / (double)meanDevX), the
+ *                         normalised point (x - meanX) * sX, T = [sX 0 -meanX*sX; 0 sY -meanY*sY; 0 0 1] in float.
+ *   I4 DLT, 3x3 products  A's entries are the reference's float products (:239-257, :281-289); A'A accumulated in FP64 in
+ *                         row order; cyclic Jacobi, stopping rule, stable descending sort and sign rule as P5 / H6; the null
+ *                         vector (smallest eigenvalue) is rounded to float.  3x3 products are FP64 over the float entries,
+ *                         (a b + c d) + e f per entry, left product first, each entry rounded to float once: inv(T2) Hn T1
+ *                         (inv(T2) written out: 1 / sX, -t / sX), H12 = adj(H21) / det(H21), T2' Fn T1, K' F K and
+ *                         inv(K) H K (inv(K) written out).  A 3x3 SVD A = U diag(d) V': V from the Jacobi of A'A (sorted,
+ *                         sign rule), u_k = A v_k / |A v_k| and d_k = |A v_k| for k = 0, 1; u_2 = u_0 x u_1 normalised,
+ *                         d_2 = |A v_2|; for ReconstructH u_2 is flipped when u_2 . (A v_2) < 0 (a proper SVD, s depends on
+ *                         it), for DecomposeE by the sign rule (A v_2 is rounding noise there).  F's rank-2 projection is
+ *                         (d_0 u_0) v_0' + (d_1 u_1) v_1' in FP64, rounded to float.
+ *   I5 checks (:305-468)  float, one rounding per operation, the reference's expression order; 1.0 / x is a double division
+ *                         of the float expression rounded to float, invSigmaSquare likewise; thresholds 5.991f, 3.841f.
+ *                         A term is an inlier's iff chiSquare <= th (a NaN chiSquare is an outlier's and adds nothing: it
+ *                         would poison every score in the reference).  The score is the running float sum in index order,
+ *                         term 1 before term 2.  Mask bit e = compacted pair e.
+ *   I6 selection          h ascending, strict > from 0.0f; a NaN score never wins; no winner: best = -1, empty mask, zero
+ *                         matrix (the F branch then has N = 0 inliers and fails, the quirk of :178 restated).
+ *   I7 branch (:112-118)  RH = SH / (SH + SF) in float, H iff (double)RH > 0.40; NaN takes the F branch.
+ *   I8 motions (:470-732, :909-929)  SVDs as I4, rounded to float; everything after in float in the reference's order, 3x3
+ *                         float products (a b + c d) + e f, left product first; determinants cv::determinant's double
+ *                         expression over the float entries; s = (float)(det(U) det(Vt)); ratio tests
+ *                         (double)(d1 / d2) < 1.00001; cv::norm an FP64 sum and sqrt rounded to float; the eight motions in
+ *                         the reference's order, F's as (R1,t) (R2,t) (R1,-t) (R2,-t) with DecomposeE's determinant flips;
+ *                         nMinGood = max((int)(0.9 * N), min_triangulated) and the 0.7 / 0.75 / 0.9 products in double;
+ *                         first wins on ties exactly as the two if chains are written (H: > scan with a second best; F: the
+ *                         == chain, which stops at the first motion that has maxGood whether its parallax passes or not).
+ *   I9 CheckRT, Triangulate (:734-747, :798-907)  A's rows the reference's float expressions, P2 = K [R|t] a float product;
+ *                         the eigenvector of the smallest eigenvalue of the 4x4 A'A (FP64, Jacobi as I4) rounded to float
+ *                         and divided by its fourth component in float; isfinite checked; normal . normal an FP64 sum,
+ *                         cosParallax = (float)(dot / (double)(dist1 * dist2)); both depth tests use
+ *                         (double)cosParallax < 0.99998; reprojection tests in float, th2 = (float)(4.0 * sigma * sigma);
+ *                         P3D and triangulated have n1 entries indexed by pair.first.  A pair that passes every test with
+ *                         cosParallax >= 0.99998 writes its point and counts in nGood but is not triangulated.  The parallax
+ *                         cosine of a motion is the element of rank min(50, nGood - 1) in ascending order (order of the
+ *                         sign-magnitude float keys); 1.0f for nGood = 0 (the reference's parallax = 0).
+ *   I10 parallax          no acosf on the device: the entry point computes, with the host's acosf and a bisection over the
+ *                         float's bits, the largest cosines for which (float)(acosf(c) * 180 / CV_PI) > min_parallax (F)
+ *                         and >= min_parallax (H) hold (NaN if none does); the kernel compares cosines.  cos_parallax[] is
+ *                         carried in the result; the host flavours fill parallax_deg with the reference's expression.
+ *   Limits                n1, n2 in [0, 16384], n_hyp in [0, 4096], sigma > 0, min_triangulated >= 0; every device loop has
+ *                         a fixed bound. */
+typedef struct orbgpu_init_result { /* device or host */
+    int32_t n;                  /* N: kept pairs */
+    int32_t n_bad_index;        /* matches12[i] >= n2 */
+    int32_t n_bad_set;          /* sets with an index outside [0, N) */
+    int32_t best_h, best_f;     /* the winning hypotheses or -1 */
+    float SH, SF, RH;
+    int32_t used_homography;    /* the branch of I7 */
+    int32_t n_inliers;          /* the N of Reconstruct*: inliers of the selected model */
+    int32_t n_good[8];          /* nGood per motion (F: four, the rest 0) */
+    float cos_parallax[8];      /* I9's cosine per motion; 0 for a motion that was not checked */
+    int32_t best_motion;        /* H: bestSolutionIdx; F: the first motion with maxGood; -1 if none */
+    int32_t second_best_good;   /* H: secondBestGood; F: nsimilar */
+    int32_t success;            /* Initialize's return value */
+    float parallax_deg;         /* host flavours only: the reference's parallax of best_motion; 0 otherwise */
+    float H21[9], F21[9];       /* the selected matrices (zeros if none won) */
+    float R21[9], t21[3];       /* the motion on success, zeros otherwise */
+} orbgpu_init_result;
+
+/* The array pointers are DEVICE pointers for the *_device entry points and HOST pointers for the host flavours. */
+typedef struct orbgpu_init_problem {
+    int32_t n1, n2;             /* key points of the reference (1) and the current (2) frame */
+    const float *kp1, *kp2;     /* [n1][2], [n2][2] mvKeysUn[i].pt */
+    const int32_t *matches12;   /* [n1] (I1) */
+    const int32_t *sets;        /* [n_hyp][8] (I2) */
+    int32_t n_hyp;
+    float fx, fy, cx, cy;
+    float sigma, min_parallax;  /* 1.0, 1.0 in Tracking.cc */
+    int32_t min_triangulated;   /* 50 */
+    /* outputs (the host flavours ignore them) */
+    float *scores_h, *scores_f; /* [n_hyp] */
+    uint64_t *masks_h, *masks_f; /* [n_hyp][(n1 + 63) / 64], bit e of a row = compacted pair e */
+    float *R21, *t21;           /* [9], [3]; may be NULL (the result holds them too) */
+    float *P3D;                 /* [n1][3] vIniP3D, zeros unless success */
+    uint8_t *triangulated;      /* [n1] vbTriangulated, zeros unless success */
+    orbgpu_init_result *result;
+} orbgpu_init_problem;
+
+/* I10 on the host: the two cosine limits of min_parallax (F's strict one, H's); EINVAL for a null pointer. */
+int orbgpu_initializer_cos_limits(float min_parallax, float *limit_f, float *limit_h);
+/* Enqueued on hip_stream; workspace and error rules as orbgpu_pnp_solve_device.  The call waits for the stream on entry
+ * only (N stays on the device).  EINVAL: null pointers, a limit violated, sigma <= 0 or NaN, min_triangulated < 0; nothing
+ * is launched then.  EHIP without a device.  The batch form is one launch sequence (five kernels) for all problems. */
+int orbgpu_initializer_device(const orbgpu_init_problem *p, int32_t device_id, void *hip_stream);
+int orbgpu_initializer_batch_device(int32_t n, const orbgpu_init_problem *problems, int32_t device_id, void *hip_stream);
+/* Host arrays, synchronises.  P3D [n1][3] and triangulated [n1] may be NULL.  A set index outside [0, N) is EINVAL here
+ * (when N >= 8), before anything is launched. */
+int orbgpu_initializer(const orbgpu_init_problem *p, float *P3D, uint8_t *triangulated, orbgpu_init_result *result,
+                       int32_t device_id);
+/* As orbgpu_initializer, but every hypothesis comes back: scores_h, scores_f [n_hyp], masks_h, masks_f
+ * [n_hyp][(n1 + 63) / 64] (any may be NULL). */
+int orbgpu_initializer_all(const orbgpu_init_problem *p, float *scores_h, float *scores_f, uint64_t *masks_h,
+                           uint64_t *masks_f, float *P3D, uint8_t *triangulated, orbgpu_init_result *result,
+                           int32_t device_id);
+
 
 /* LastFrame members read by SearchByProjection(CurrentFrame, LastFrame, th, bMono). */
 typedef struct {

@@ -185,6 +185,35 @@ class PnpProblem(C.Structure):
                 ("masks", C.c_void_p), ("refined_mask", C.c_void_p), ("indices", C.c_void_p), ("result", C.c_void_p)]
 
 
+class InitResult(C.Structure):
+    _fields_ = [("n", C.c_int32), ("n_bad_index", C.c_int32), ("n_bad_set", C.c_int32), ("best_h", C.c_int32),
+                ("best_f", C.c_int32), ("SH", C.c_float), ("SF", C.c_float), ("RH", C.c_float), ("used_homography", C.c_int32),
+                ("n_inliers", C.c_int32), ("n_good", C.c_int32 * 8), ("cos_parallax", C.c_float * 8), ("best_motion", C.c_int32),
+                ("second_best_good", C.c_int32), ("success", C.c_int32), ("parallax_deg", C.c_float), ("H21", C.c_float * 9),
+                ("F21", C.c_float * 9), ("R21", C.c_float * 9), ("t21", C.c_float * 3)]
+
+    def as_dict(self):
+        d = {}
+        for k, t in self._fields_:
+            v = getattr(self, k)
+            if k in ("n_good", "cos_parallax", "t21"):
+                d[k] = np.array(v, np.int32 if k == "n_good" else np.float32)
+            elif k in ("H21", "F21", "R21"):
+                d[k] = np.array(v, np.float32).reshape(3, 3)
+            else:
+                d[k] = np.float32(v) if t is C.c_float else v
+        return d
+
+
+class InitProblem(C.Structure):
+    _fields_ = [("n1", C.c_int32), ("n2", C.c_int32), ("kp1", C.c_void_p), ("kp2", C.c_void_p), ("matches12", C.c_void_p),
+                ("sets", C.c_void_p), ("n_hyp", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("sigma", C.c_float), ("min_parallax", C.c_float), ("min_triangulated", C.c_int32),
+                ("scores_h", C.c_void_p), ("scores_f", C.c_void_p), ("masks_h", C.c_void_p), ("masks_f", C.c_void_p),
+                ("R21", C.c_void_p), ("t21", C.c_void_p), ("P3D", C.c_void_p), ("triangulated", C.c_void_p),
+                ("result", C.c_void_p)]
+
+
 _LIB = None
 
 # every symbol include/orbgpu.h declares (checked by tests/test_abi.py against the header text)
@@ -218,6 +247,8 @@ ABI_SYMBOLS = [
     "orbgpu_sim3_opt_last_spills",
     "orbgpu_pnp_ransac_parameters", "orbgpu_pnp_solve_device", "orbgpu_pnp_solve_batch_device", "orbgpu_pnp_solve",
     "orbgpu_pnp_solve_all", "orbgpu_pnp_solve_table",
+    "orbgpu_initializer_cos_limits", "orbgpu_initializer_device", "orbgpu_initializer_batch_device", "orbgpu_initializer",
+    "orbgpu_initializer_all",
     "orbgpu_keyframe_db_create", "orbgpu_keyframe_db_destroy", "orbgpu_keyframe_db_clear", "orbgpu_keyframe_db_size",
     "orbgpu_keyframe_db_add", "orbgpu_keyframe_db_erase", "orbgpu_keyframe_db_set_covisibles", "orbgpu_keyframe_db_score",
     "orbgpu_keyframe_db_detect_loop", "orbgpu_keyframe_db_detect_reloc", "orbgpu_keyframe_db_last_query",
@@ -351,7 +382,7 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
-# What the solver and optimiser families (pose_optimization, sim3_solve, sim3_optimize, pnp_solve) share: the two device
+# What the solver and optimiser families (pose_optimization, sim3_solve, sim3_optimize, pnp_solve, initializer) share: the two device
 # flavours' calls, and the setters of their *_problem builders.
 def _batch_device(family, cls, make, problems, stream, device_id):
     """orbgpu_<family>_batch_device over make(p), a cls structure, of every problem."""
@@ -1291,6 +1322,90 @@ def pnp_solve_table(dframe, table, kp_ids, sc):
     check(L.orbgpu_pnp_solve_table(dframe.h, table.h, _p(ids), C.byref(q), _p(counts), _p(T), _p(inl), C.byref(res)))
     out = res.as_dict()
     out.update(counts=counts[:H], inliers=inl[:n], Tcw_out=T)
+    return out
+
+
+_INIT_PTRS = ("kp1", "kp2", "matches12", "sets", "scores_h", "scores_f", "masks_h", "masks_f", "R21", "t21", "P3D",
+              "triangulated", "result")
+
+
+def initializer_cos_limits(min_parallax):
+    """I10: the largest cosines for which the reference's parallax is > (ReconstructF) and >= (ReconstructH)
+    min_parallax (orbgpu_initializer_cos_limits; host only).  NaN where none is."""
+    L = lib()
+    L.orbgpu_initializer_cos_limits.argtypes = [C.c_float, C.c_void_p, C.c_void_p]
+    a, b = C.c_float(), C.c_float()
+    check(L.orbgpu_initializer_cos_limits(min_parallax, C.byref(a), C.byref(b)))
+    return np.float32(a.value), np.float32(b.value)
+
+
+def init_problem(p):
+    """An InitProblem from a dict: n1, n2, n_hyp, K (fx, fy, cx, cy), optional sigma (1.0), min_parallax (1.0),
+    min_triangulated (50), and the array pointers of include/orbgpu.h as integers (missing ones are NULL)."""
+    q = InitProblem()
+    q.n1, q.n2, q.n_hyp = int(p["n1"]), int(p["n2"]), int(p["n_hyp"])
+    _set_pointers(q, p, _INIT_PTRS)
+    _set_intrinsics(q, p["K"])
+    q.sigma, q.min_parallax = float(p.get("sigma", 1.0)), float(p.get("min_parallax", 1.0))
+    q.min_triangulated = int(p.get("min_triangulated", 50))
+    return q
+
+
+def initializer_batch_device(problems, stream=0, device_id=0):
+    """Independent Initializer::Initialize problems in one launch sequence (orbgpu_initializer_batch_device).  problems:
+    dicts as init_problem takes them, with device pointers.  Enqueued, not waited for."""
+    _batch_device("initializer", InitProblem, init_problem, problems, stream, device_id)
+
+
+def initializer_device(problem, stream=0, device_id=0):
+    """One problem (orbgpu_initializer_device); see initializer_batch_device."""
+    _one_device("initializer", init_problem(problem), stream, device_id)
+
+
+def _init_host_problem(sc, keep, **over):
+    """InitProblem over the host arrays of a scene dict (kp1 [n1][2], kp2 [n2][2], matches12 [n1], sets [H][8], K, ...)"""
+    k1 = np.ascontiguousarray(sc["kp1"], np.float32).reshape(-1, 2)
+    k2 = np.ascontiguousarray(sc["kp2"], np.float32).reshape(-1, 2)
+    m = np.ascontiguousarray(sc["matches12"], np.int32)
+    if len(m) != len(k1):
+        raise ValueError("one match entry per key point of frame 1 expected")
+    st = np.ascontiguousarray(sc["sets"], np.int32).reshape(-1, 8)
+    keep += [k1, k2, m, st]
+    p = {k: sc[k] for k in ("K", "sigma", "min_parallax", "min_triangulated") if k in sc}
+    p.update(n1=len(k1), n2=len(k2), n_hyp=len(st), kp1=k1.ctypes.data, kp2=k2.ctypes.data, matches12=m.ctypes.data,
+             sets=st.ctypes.data)
+    p.update(over)
+    return init_problem(p)
+
+
+def initializer(sc, device_id=0, **over):
+    """Initializer::Initialize over host arrays (orbgpu_initializer).  Returns a dict: the result record's fields,
+    P3D [n1][3], triangulated [n1]."""
+    keep = []
+    q = _init_host_problem(sc, keep, **over)
+    n1 = q.n1
+    P, tri, res = np.zeros((max(n1, 1), 3), np.float32), np.zeros(max(n1, 1), np.uint8), InitResult()
+    L = lib()
+    L.orbgpu_initializer.argtypes = [C.c_void_p] * 4 + [C.c_int32]
+    check(L.orbgpu_initializer(C.byref(q), _p(P), _p(tri), C.byref(res), device_id))
+    out = res.as_dict()
+    out.update(P3D=P[:n1], triangulated=tri[:n1])
+    return out
+
+
+def initializer_all(sc, device_id=0, **over):
+    """As initializer, with every hypothesis (orbgpu_initializer_all): scores_h, scores_f [H], masks_h, masks_f [H][words]."""
+    keep = []
+    q = _init_host_problem(sc, keep, **over)
+    n1, H, words = q.n1, q.n_hyp, (q.n1 + 63) // 64
+    P, tri, res = np.zeros((max(n1, 1), 3), np.float32), np.zeros(max(n1, 1), np.uint8), InitResult()
+    sh, sf = np.zeros(max(H, 1), np.float32), np.zeros(max(H, 1), np.float32)
+    mh, mf = (np.zeros((max(H, 1), max(words, 1)), np.uint64) for _ in range(2))
+    L = lib()
+    L.orbgpu_initializer_all.argtypes = [C.c_void_p] * 8 + [C.c_int32]
+    check(L.orbgpu_initializer_all(C.byref(q), _p(sh), _p(sf), _p(mh), _p(mf), _p(P), _p(tri), C.byref(res), device_id))
+    out = res.as_dict()
+    out.update(P3D=P[:n1], triangulated=tri[:n1], scores_h=sh[:H], scores_f=sf[:H], masks_h=mh[:H, :words], masks_f=mf[:H, :words])
     return out
 
 

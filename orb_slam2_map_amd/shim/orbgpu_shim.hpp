@@ -1559,6 +1559,124 @@ template <typename FrameT, typename MapPointT> class PnPsolverT {
 };
 
 // --------------------------------------------------------------------------------------------
+// Initializer (reference include/Initializer.h, src/Initializer.cc): the monocular bootstrap.  The conventions are I1-I10
+// of include/orbgpu.h.
+// --------------------------------------------------------------------------------------------
+// The draw of Initializer::Initialize (:82-97) replayed for `iterations` sets of 8 over n matches: WITHOUT replacement -- the
+// back element moves into position randi (not PnPsolver's quirk).  random_int(min, max) is called 8 times per iteration.
+// n < 8 and a random_int outside [min, max] are refused with std::invalid_argument, as tests/init_model.py refuses them.
+template <typename RandomInt> inline std::vector<int32_t> InitializerSampleSets(int n, int iterations, RandomInt random_int)
+{
+    if (n < 8)
+        throw std::invalid_argument("InitializerSampleSets: fewer matches than the minimal set");
+    std::vector<int32_t> out((size_t)std::max(iterations, 0) * 8, 0);
+    std::vector<int32_t> avail;
+    for (int it = 0; it < iterations; it++) {
+        avail.resize((size_t)n);
+        for (int i = 0; i < n; i++)
+            avail[i] = i;
+        for (int j = 0; j < 8; j++) {
+            const int randi = random_int(0, (int)avail.size() - 1);
+            if (randi < 0 || randi >= (int)avail.size())
+                throw std::invalid_argument("InitializerSampleSets: RandomInt outside [min, max]");
+            out[(size_t)it * 8 + j] = avail[randi];
+            avail[randi] = avail.back();
+            avail.pop_back();
+        }
+    }
+    return out;
+}
+
+// FrameT needs mvKeysUn, fx, fy, cx, cy.  The reference's constructor (ReferenceFrame, sigma, iterations) with the
+// generator behind it: random_int(min, max) stands for DUtils::Random::RandomInt (the reference seeds it with
+// SeedRandOnce(0)).  Initialize has the reference's arguments and return value; MatT is cv::Mat (create(rows, cols, type)
+// and ptr<float>(row) are used), Point3T cv::Point3f.  Fewer than 8 matches return false without a draw (the reference
+// would call RandomInt(0, -1); Tracking.cc asks for 100 matches).  At most 4096 iterations (the library's limit).
+template <typename FrameT> class InitializerT {
+  public:
+    // (problem, P3D [n1][3], triangulated [n1], result) -> status: orbgpu_initializer on this device
+    typedef std::function<int(const orbgpu_init_problem *, float *, uint8_t *, orbgpu_init_result *)> Solver;
+
+    template <typename RandomInt>
+    InitializerT(const FrameT &ReferenceFrame, float sigma, int iterations, RandomInt random_int, int device_id = 0)
+        : random_int_(random_int), mSigma(sigma), mMaxIterations(std::min(std::max(iterations, 0), 4096))
+    {
+        solver_ = [device_id](const orbgpu_init_problem *p, float *P3D, uint8_t *tri, orbgpu_init_result *r) {
+            return orbgpu_initializer(p, P3D, tri, r, device_id);
+        };
+        std::memset(&p_, 0, sizeof(p_));
+        p_.fx = ReferenceFrame.fx, p_.fy = ReferenceFrame.fy, p_.cx = ReferenceFrame.cx, p_.cy = ReferenceFrame.cy;
+        Keys(ReferenceFrame, kp1_);
+        std::memset(&result_, 0, sizeof(result_));
+    }
+
+    template <typename MatT, typename Point3T>
+    bool Initialize(const FrameT &CurrentFrame, const std::vector<int> &vMatches12, MatT &R21, MatT &t21,
+                    std::vector<Point3T> &vP3D, std::vector<bool> &vbTriangulated, float minParallax = 1.0f,
+                    int minTriangulated = 50)
+    {
+        const size_t n1 = kp1_.size() / 2;
+        if (vMatches12.size() != n1)
+            throw std::invalid_argument("Initializer::Initialize: one match entry per key point of the reference frame");
+        Keys(CurrentFrame, kp2_);
+        const int n2 = (int)(kp2_.size() / 2);
+        matches_.assign(vMatches12.begin(), vMatches12.end());
+        int N = 0;  // I1
+        for (size_t i = 0; i < n1; i++)
+            N += matches_[i] >= 0 && matches_[i] < n2;
+        std::memset(&result_, 0, sizeof(result_));
+        result_.n = N, result_.best_h = result_.best_f = result_.best_motion = -1;
+        N_ = N;
+        if (N < 8)
+            return false;
+        sets_ = InitializerSampleSets(N, mMaxIterations, random_int_);
+        p_.n1 = (int32_t)n1, p_.n2 = n2, p_.kp1 = kp1_.data(), p_.kp2 = kp2_.data(), p_.matches12 = matches_.data();
+        p_.sets = sets_.data(), p_.n_hyp = mMaxIterations;
+        p_.sigma = mSigma, p_.min_parallax = minParallax, p_.min_triangulated = minTriangulated;
+        p3d_.assign(3 * std::max<size_t>(n1, 1), 0.f), tri_.assign(std::max<size_t>(n1, 1), 0);
+        check(solver_(&p_, p3d_.data(), tri_.data(), &result_), "Initializer");
+        if (!result_.success)
+            return false;
+        R21.create(3, 3, 5), t21.create(3, 1, 5);  // CV_32F
+        for (int i = 0; i < 3; i++) {
+            std::memcpy(R21.template ptr<float>(i), result_.R21 + 3 * i, 12);
+            *t21.template ptr<float>(i) = result_.t21[i];
+        }
+        vP3D.resize(n1), vbTriangulated.assign(n1, false);
+        for (size_t i = 0; i < n1; i++) {
+            vP3D[i].x = p3d_[3 * i], vP3D[i].y = p3d_[3 * i + 1], vP3D[i].z = p3d_[3 * i + 2];
+            vbTriangulated[i] = tri_[i] != 0;
+        }
+        return true;
+    }
+
+    const orbgpu_init_result &Result() const { return result_; }  // of the last Initialize
+    int NumMatches() const { return N_; }                         // I1's N of the last Initialize
+    const std::vector<int32_t> &Sets() const { return sets_; }
+    int MaxIterations() const { return mMaxIterations; }
+    // a test serves the call from a recorded result without a device
+    void SetSolver(Solver s) { solver_ = s; }
+
+  private:
+    static void Keys(const FrameT &F, std::vector<float> &kp)
+    {
+        kp.resize(2 * F.mvKeysUn.size());
+        for (size_t i = 0; i < F.mvKeysUn.size(); i++)
+            kp[2 * i] = F.mvKeysUn[i].pt.x, kp[2 * i + 1] = F.mvKeysUn[i].pt.y;
+    }
+
+    std::function<int(int, int)> random_int_;
+    Solver solver_;
+    float mSigma;
+    int mMaxIterations, N_ = 0;
+    orbgpu_init_problem p_;
+    orbgpu_init_result result_;
+    std::vector<float> kp1_, kp2_, p3d_;
+    std::vector<int32_t> matches_, sets_;
+    std::vector<uint8_t> tri_;
+};
+
+// --------------------------------------------------------------------------------------------
 // KeyFrameDatabase (reference include/KeyFrameDatabase.h:45-75, src/KeyFrameDatabase.cc) on the device
 // (orbgpu_keyframe_db_*): add / erase / clear / DetectLoopCandidates / DetectRelocalizationCandidates with the
 // reference's signatures, candidates in the reference's order.  KeyFrameT needs mnId, mBowVec (DBoW2::BowVector: an

@@ -1,0 +1,214 @@
+"""The Initializer on the device (orbgpu_initializer*) against the restatement in init_model.py -- vs CPU restatement;
+OpenCV boundary unpinned.  Discrete outputs are compared exactly, except hypotheses the model alone calls not
+well-conditioned (a repeated index, an eigenvalue gap below GAP) or that hold a near-threshold pair (MARGIN_FACTOR x the
+bound); continuous outputs within 16 x the model's own spread between its Jacobi and numpy.linalg.eigh / the same steps.
+The reasoning for the constants is next to them in tests/init_model.py and tests/pnp_model.py; the figures of a run go to
+profiles/init_parity.json."""
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for p in (HERE, os.path.join(ROOT, "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import init_model as M  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+FIGURES = {}
+
+
+@pytest.fixture(scope="module")
+def G():
+    from orb_slam2_map_amd import lib
+    if lib.device_count() < 1:
+        pytest.skip("no HIP device")
+    return lib
+
+
+@pytest.fixture(scope="module")
+def torch():
+    return pytest.importorskip("torch")
+
+
+@pytest.fixture(scope="module")
+def F(G):
+    import fuzz_init
+    return fuzz_init
+
+
+@pytest.fixture(scope="module")
+def base(G, torch, F):
+    """one scene and its device result, shared by the tests that vary it"""
+    sc = M.make_scene(120, 77, "general", n_hyp=24)
+    return sc, F.run_batch(torch, [sc])[0]
+
+
+def record():
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "init_parity.json"), "w") as f:
+        json.dump({"note": "vs CPU restatement; OpenCV boundary unpinned", "gap": M.GAP, "bound_factor": M.BOUND_FACTOR,
+                   "margin_factor": M.MARGIN_FACTOR, "model_spread_jacobi_vs_eigh": max(v["spread"] for v in FIGURES.values()),
+                   "device_max_deviation": max(v["device_dev"] for v in FIGURES.values()),
+                   "largest_left_out_share": max(v["left_out"] for v in FIGURES.values()),
+                   "by_scene": {k: FIGURES[k] for k in FIGURES}}, f, indent=1)
+
+
+def parity(F, torch, key, sc):
+    ps = M.model_pass(sc)
+    got = F.run_batch(torch, [sc])[0]
+    rep = F.compare([sc], [got], [ps])
+    print("init parity %s: spread %.3e, bound %.3e, device deviation %.3e, left out %d of %d, compared to the end %d" % (
+        key, rep["spread"], rep["bound"], rep["device_dev"], rep["hypotheses_left_out"], rep["hypotheses"], rep["downstream_compared"]))
+    FIGURES[key] = {k: rep[k] for k in ("spread", "bound", "margin", "device_dev", "left_out", "hypotheses", "hypotheses_left_out",
+                                        "downstream_compared")}
+    FIGURES[key]["mismatches"] = rep["mismatches"][:5]
+    FIGURES[key].update(used_homography=int(got["used_homography"]), success=int(got["success"]), n_good=got["n_good"].tolist())
+    record()
+    assert rep["left_out"] <= M.LEFT_OUT_CAP
+    assert not rep["mismatches"], rep["mismatches"][:10]
+    assert rep["downstream_compared"] == (1 if rep["hypotheses_left_out"] == 0 else 0)
+    return ps[0], got
+
+
+@pytest.mark.parametrize("key", list(M.PARITY_SCENES))
+def test_parity_with_the_model(G, torch, F, key):
+    n, _, kind, n_hyp = M.PARITY_SCENES[key]
+    sc = M.parity_scene(key)
+    m, got = parity(F, torch, key, sc)
+    assert got["n"] == n == m["N"] and len(sc["kp1"]) > n and len(sc["kp2"]) != len(sc["kp1"]) and len(sc["sets"]) == n_hyp
+    assert (sc["matches12"] < 0).any()
+    use_h, success = M.VERDICTS[kind]
+    if n >= 300:
+        assert got["success"] == success and (use_h is None or got["used_homography"] == use_h)
+
+
+@pytest.mark.parametrize("n_good", [50, 51, 52])
+def test_parallax_rank_on_both_sides_of_the_clamp(G, torch, F, n_good):
+    sc = M.ngood_scene(n_good)
+    m, got = parity(F, torch, "ngood%d" % n_good, sc)
+    b = got["best_motion"]
+    assert got["success"] == 1 and got["n_good"][b] == n_good
+    cosines = np.sort(M.check_rt(m["prep"], m["motions"][0][b], m["motions"][1][b], _inliers(m), sc["K"], sc["sigma"], "jacobi")["cosines"])
+    assert got["cos_parallax"][b] == cosines[min(50, n_good - 1)]
+    assert (min(50, n_good - 1) == n_good - 1) == (n_good <= 51)
+
+
+def _inliers(m):
+    words = m["masks_h" if m["used_homography"] else "masks_f"][m["best_h"] if m["used_homography"] else m["best_f"]]
+    bits = np.unpackbits(words.view(np.uint8), bitorder="little")
+    return bits[:m["N"]].astype(bool)
+
+
+def test_too_few_matches(G, torch, F):
+    for n in (7, 0):
+        sc = M.make_scene(n, 5 + n, "general", n_hyp=6, n1=12, n2=9)
+        r = F.run_batch(torch, [sc])[0]
+        m = M.initialize(sc)
+        assert r["n"] == n == m["N"] and r["success"] == 0 and r["n_bad_set"] == 0 and r["best_h"] == r["best_f"] == -1
+        assert not r["scores_h"].any() and not r["scores_f"].any() and not r["masks_h"].any() and not r["masks_f"].any()
+        assert not r["P3D"].any() and not r["triangulated"].any() and not r["n_good"].any() and not r["R21"].any() and not r["t21"].any()
+        assert np.isnan(r["RH"]) and r["used_homography"] == 0 and r["best_motion"] == -1
+        h = G.initializer(sc)
+        assert h["n"] == n and h["success"] == 0 and not h["P3D"].any()
+    sc0 = dict(sc, kp1=np.zeros((0, 2), np.float32), matches12=np.zeros(0, np.int32))
+    r = F.run_batch(torch, [sc0])[0]
+    assert r["n"] == 0 and r["success"] == 0
+    r = F.run_batch(torch, [dict(M.make_scene(40, 3), sets=np.zeros((0, 8), np.int32))])[0]
+    assert r["n"] == 40 and r["success"] == 0 and r["best_h"] == -1 and np.isnan(r["RH"])
+    G.initializer_batch_device([])
+
+
+def test_degenerate_and_hostile_input(G, torch, F, base):
+    sc, ref = base
+    H = len(sc["sets"])
+    assert ref["n"] == 120 and ref["n_bad_set"] == 0 and ref["n_bad_index"] == 0
+    # a set naming one pair eight times: computed like any other, nothing else moves
+    sc2 = dict(sc, sets=sc["sets"].copy())
+    sc2["sets"][2] = 8
+    got, m2 = F.run_batch(torch, [sc2])[0], M.initialize(sc2)
+    assert m2["repeated"][2] and got["n_bad_set"] == 0
+    keep = np.arange(H) != 2
+    for k in ("scores_h", "scores_f", "masks_h", "masks_f"):
+        assert got[k][keep].tobytes() == ref[k][keep].tobytes(), k
+    # a set index of N (and a negative one): counted, never read through, cannot be selected; EINVAL in the host flavours
+    bad = dict(sc, sets=sc["sets"].copy())
+    bad["sets"][3, 1] = 120
+    for fn in (G.initializer, G.initializer_all):
+        with pytest.raises(G.OrbGpuError) as ei:
+            fn(bad)
+        assert ei.value.status == G.EINVAL
+    bad["sets"][5, 0] = -1
+    r, mb = F.run_batch(torch, [bad])[0], M.initialize(bad)
+    assert r["n_bad_set"] == 2 == mb["n_bad_set"] and r["best_h"] not in (3, 5) and r["best_f"] not in (3, 5)
+    for k in ("scores_h", "scores_f", "masks_h", "masks_f"):
+        assert not r[k][[3, 5]].any(), k
+        keep = ~np.isin(np.arange(H), (3, 5))
+        assert r[k][keep].tobytes() == ref[k][keep].tobytes(), k
+    # matches12 >= n2: not kept, and counted
+    sc4 = dict(sc, matches12=sc["matches12"].copy())
+    rows = np.flatnonzero(sc["matches12"] >= 0)
+    sc4["matches12"][rows[-1]], sc4["matches12"][rows[-2]] = len(sc["kp2"]), len(sc["kp2"]) + 7
+    got4, m4 = F.run_batch(torch, [sc4])[0], M.initialize(sc4)
+    assert got4["n_bad_index"] == 2 == m4["n_bad_index"] and got4["n"] == 118 == m4["N"]
+    # a NaN key point of frame 1 in a matched row: Normalize runs over all key points (I3), so every hypothesis is NaN;
+    # a NaN chiSquare is an outlier's (I5): every score is 0, nothing wins, nowhere is a pair an inlier
+    sc3 = dict(sc, kp1=sc["kp1"].copy())
+    sc3["kp1"][rows[int(sc["sets"][0, 0])]] = np.nan
+    got3, m3 = F.run_batch(torch, [sc3])[0], M.initialize(sc3)
+    assert got3["n"] == 120 == m3["N"] and got3["success"] == 0 == m3["success"]
+    for k in ("scores_h", "scores_f", "masks_h", "masks_f"):
+        assert not got3[k].any() and not m3[k].any(), k
+    assert got3["best_h"] == got3["best_f"] == -1 and not got3["triangulated"].any()
+
+
+def test_same_bytes_in_a_batch_and_through_every_flavour(G, torch, F):
+    sc = M.parity_scene("300")
+    rng = np.random.default_rng(1)
+    kinds = ["general", "planar", "rotation", "few"]
+    others = [M.make_scene(int(n), 6000 + i, kinds[i % 4], n_hyp=int(rng.choice([1, 5, 24]))) for i, n in enumerate(rng.integers(3, 200, 31))]
+    alone, again = (F.result_bytes(F.run_batch(torch, [sc])[0]) for _ in range(2))
+    assert alone == again
+    for pos in (0, 15, 31):
+        batch = others[:pos] + [sc] + others[pos:]
+        got = F.run_batch(torch, batch + [sc])
+        assert F.result_bytes(got[pos]) == alone and F.result_bytes(got[-1]) == alone, pos
+    p, d = F.upload(torch, sc)
+    G.initializer_device(p, stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    one = F.download(d, sc)
+    assert F.result_bytes(one) == alone and one["success"] == 1
+    a = G.initializer_all(sc)
+    assert a["parallax_deg"] == M.parallax_of(one["cos_parallax"][one["best_motion"]]) > 1.0
+    assert F.result_bytes(a) == alone
+    h = G.initializer(sc)
+    assert all(int(h[k]) == int(one[k]) for k in F.RESULT_KEYS)
+    for k in ("P3D", "triangulated", "n_good", "cos_parallax", "H21", "F21", "R21", "t21", "SH", "SF", "RH", "parallax_deg"):
+        assert np.ascontiguousarray(h[k]).tobytes() == np.ascontiguousarray(a[k]).tobytes(), k
+    assert h["triangulated"].sum() > 200 and (h["P3D"][h["triangulated"] != 0][:, 2] > 0).all()
+
+
+def test_argument_errors_launch_nothing(G, torch, F):
+    sc = M.make_scene(40, 5, n_hyp=8)
+    L = G.lib()
+    L.orbgpu_initializer_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.orbgpu_initializer_batch_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    assert L.orbgpu_initializer_device(None, 0, None) == G.EINVAL
+    p, d = F.upload(torch, sc)
+    assert L.orbgpu_initializer_batch_device(-1, C.byref(G.init_problem(p)), 0, None) == G.EINVAL
+    assert L.orbgpu_initializer_batch_device(1, None, 0, None) == G.EINVAL
+    for over in ({"kp1": 0}, {"kp2": 0}, {"matches12": 0}, {"sets": 0}, {"scores_h": 0}, {"scores_f": 0}, {"masks_h": 0},
+                 {"masks_f": 0}, {"P3D": 0}, {"triangulated": 0}, {"result": 0}, {"n1": -1}, {"n2": -1}, {"n_hyp": -1},
+                 {"n1": 16385}, {"n2": 16385}, {"n_hyp": 4097}, {"sigma": 0.0}, {"sigma": -1.0}, {"sigma": float("nan")},
+                 {"min_triangulated": -1}):
+        q = G.init_problem(dict(p, **over))
+        assert L.orbgpu_initializer_device(C.byref(q), 0, None) == G.EINVAL, over
+    torch.cuda.synchronize()
+    assert (d["scores_h"].cpu().numpy() == -7).all() and (d["triangulated"].cpu().numpy() == 7).all()  # nothing ran
