@@ -3,7 +3,11 @@ OpenCV boundary unpinned.  Discrete outputs are compared exactly, except hypothe
 well-conditioned (a repeated index, an eigenvalue gap below GAP) or that hold a near-threshold pair (MARGIN_FACTOR x the
 bound); continuous outputs within 16 x the model's own spread between its Jacobi and numpy.linalg.eigh / the same steps.
 The reasoning for the constants is next to them in tests/init_model.py and tests/pnp_model.py; the figures of a run go to
-profiles/init_parity.json."""
+profiles/init_parity.json.
+
+This parity is bit for bit on curated seeds: the committed scenes are the ones on which the model's two eigen-paths agree
+in every float.  On other seeds the rules above leave most hypotheses out; there the device is held to float64 stage by
+stage, on its own output of the stage before (test_gpu_init_fp64.py, tests/init_fp64.py)."""
 import ctypes as C
 import json
 import os

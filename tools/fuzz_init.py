@@ -83,19 +83,24 @@ def _clear_winner(scores, best, bound):
     return bound == 0.0 or not len(others) or s[best] - others.max() > 2.0 * bound * max(1.0, abs(s[best]))
 
 
-def compare(scenes, got, passes=None):
+def compare(scenes, got, passes=None, fp64=None):
     """Model against device.  passes: [(model, spread)] from M.model_pass, computed here if missing.  Per hypothesis and
     model (H, F): mask words byte-equal and the score within the bound, outside the hypotheses M.left_out names.  The
     results that follow from the selection (best_h / best_f, the branch, n_good, best_motion, success, triangulated
     exactly; the matrices, R21, t21, P3D within the bound) are compared when no hypothesis is left out, the winners are
     clear of the bound, and no eigenvalue gap or threshold of the reconstruction is closer than GAP / the margin.
+    fp64: the module tests/init_fp64.py; main() and the fuzz test pass it (the tool itself needs nothing of tests/ but the
+    model).  A scene where something is left out is then held to float64 instead, stage by stage on its own result (rungs
+    3, 4, 6 and 7; the winners' matrices are in the result, so nothing more is launched): fp64_scenes counts them,
+    fp64_hypotheses the left-out hypotheses in them.
     Returns a dict: spread, bound, margin (the largest of the scenes; each scene is compared within its own), device_dev,
     left_out (largest share of a scene), mismatches (strings)."""
     if passes is None:
         passes = [M.model_pass(sc) for sc in scenes]
     spread = max([s for _, s in passes] + [0.0])
     rep = {"spread": spread, "bound": M.BOUND_FACTOR * spread, "margin": M.MARGIN_FACTOR * M.BOUND_FACTOR * spread, "device_dev": 0.0,
-           "left_out": 0.0, "hypotheses": 0, "hypotheses_left_out": 0, "downstream_compared": 0, "mismatches": []}
+           "left_out": 0.0, "hypotheses": 0, "hypotheses_left_out": 0, "downstream_compared": 0, "fp64_scenes": 0,
+           "fp64_hypotheses": 0, "mismatches": []}
     bad = rep["mismatches"]
     for i, (sc, (m, own), r) in enumerate(zip(scenes, passes, got)):
         tag = "scene %d (%s, N %d): " % (i, sc.get("kind", "?"), m["N"])
@@ -116,6 +121,11 @@ def compare(scenes, got, passes=None):
             rep["left_out"] = max(rep["left_out"], share)
             if share > M.LEFT_OUT_CAP:
                 bad.append(tag + "%d of %d hypotheses left out" % (n_out, 2 * H))
+        if n_out and fp64 is not None:
+            rungs = fp64.ladder(sc, r, None, G.initializer_cos_limits(sc.get("min_parallax", 1.0)), only=("rung3", "rung4", "rung6", "rung7"))
+            bad += [tag + "float64 " + v for v in fp64.violations(rungs)]
+            rep["fp64_scenes"] += 1
+            rep["fp64_hypotheses"] += n_out
         for out, name in zip(outs, "hf"):
             keep = ~out
             if not np.array_equal(r["masks_" + name][keep], m["masks_" + name][keep]):
@@ -156,20 +166,20 @@ def draw_scene(rng):
                         noise_px=float(rng.uniform(0.1, 1.0)), outlier_frac=float(rng.choice([0.0, 0.1, 0.3])))
 
 
-def run(seconds, seed, batch=4):
+def run(seconds, seed, batch=4, fp64=None):
     import torch
     rng = np.random.default_rng(seed)
-    tot = {"rounds": 0, "scenes": 0, "hypotheses": 0, "hypotheses_left_out": 0, "downstream_compared": 0, "spread": 0.0,
-           "device_dev": 0.0, "left_out": 0.0, "mismatches": []}
+    tot = {"rounds": 0, "scenes": 0, "hypotheses": 0, "hypotheses_left_out": 0, "downstream_compared": 0, "fp64_scenes": 0,
+           "fp64_hypotheses": 0, "spread": 0.0, "device_dev": 0.0, "left_out": 0.0, "mismatches": []}
     t_end = time.time() + seconds
     while True:
         scenes = [draw_scene(rng) for _ in range(batch)]
-        rep = compare(scenes, run_batch(torch, scenes))
+        rep = compare(scenes, run_batch(torch, scenes), fp64=fp64)
         tot["rounds"] += 1
         tot["scenes"] += len(scenes)
         # a drawn scene may leave out more than the cap (the committed parity scenes may not): that is reported, not failed
         tot["mismatches"] += [m for m in rep["mismatches"] if "hypotheses left out" not in m]
-        for k in ("hypotheses", "hypotheses_left_out", "downstream_compared"):
+        for k in ("hypotheses", "hypotheses_left_out", "downstream_compared", "fp64_scenes", "fp64_hypotheses"):
             tot[k] += rep[k]
         for k in ("spread", "device_dev", "left_out"):
             tot[k] = max(tot[k], rep[k])
@@ -182,11 +192,15 @@ def report(tot):
             "mismatches %d" % (tot["rounds"], tot["scenes"], tot["downstream_compared"], tot["hypotheses"],
                                tot["hypotheses_left_out"], tot["left_out"], len(tot["mismatches"])),
             "model spread <= %.3e, device deviation <= %.3e (vs CPU restatement; OpenCV boundary unpinned)" % (
-                tot["spread"], tot["device_dev"])] + ["  " + m for m in tot["mismatches"][:20]]
+                tot["spread"], tot["device_dev"]),
+            "float64 by stage (checks of the winners, selection, CheckRT, accept rule) on the %d scenes that left something out: "
+            "they hold %d of the %d left-out hypotheses" % (tot["fp64_scenes"], tot["fp64_hypotheses"], tot["hypotheses_left_out"])] + [
+                "  " + m for m in tot["mismatches"][:20]]
 
 
 def main():
-    tot = run(float(sys.argv[1]), int(sys.argv[2]))
+    import init_fp64
+    tot = run(float(sys.argv[1]), int(sys.argv[2]), fp64=init_fp64)
     print("\n".join(report(tot)))
     sys.exit(1 if tot["mismatches"] else 0)
 
