@@ -654,6 +654,113 @@ int orbgpu_pose_optimization_table(const orbgpu_frame *fr, orbgpu_mappoint_table
  * Synchronises the device. */
 int orbgpu_pose_last_spills(int32_t device_id, int32_t *problems_spilled);
 
+/* ---- Optimizer::LocalBundleAdjustment (Optimizer.cc:453-778): local bundle adjustment on the device -----------------------
+ * The most expensive call of LocalMapping (LocalMapping.cc:85): the poses of the local key frames and the positions of the
+ * points they see, over every observation of those points; the other key frames that see them are fixed cameras.  g2o is
+ * not part of the reference tree: its behaviour (OptimizationAlgorithmLevenberg over BlockSolver_6_3, points marginalised)
+ * is restated, NOT read ("g2o unpinned"); tests/lba_model.py is the float64 restatement every result is compared with.
+ * The definition, all in IEEE double unless a float is named:
+ *   L1 problem             P pose rows: the first n_local are lLocalKeyFrames, free unless fixed[i] (mnId == 0), the rest are
+ *                          lFixedCameras; M point rows; E edges (point row, pose row, key point x, y, u_right, octave); an
+ *                          edge is mono iff u_right < 0.  Every pose row has its own fx, fy, cx, cy, mbf and its own
+ *                          mvInvLevelSigma2 table.  The graph gathering of :455-504 walks pointers and stays with the caller.
+ *   L2 set-up (:522-653)   poses in as Converter::toSE3Quat of the float Tcw, points as (double) of the float position;
+ *                          information = (double)invSigma2[pose][octave]; Huber delta (float)sqrt(5.991) for mono edges,
+ *                          (float)sqrt(7.815) for stereo edges
+ *   L3 error, Jacobians    the edge error of orbgpu_pose_optimization (e = obs - projection of R Xw + t);
+ *                          J_pose = d e / d (omega, upsilon) of T <- exp(omega, upsilon) T, as there;
+ *                          J_point = -(d proj / d Pc) R
+ *   L4 system              with s = rho1 invSigma2 (Huber, no second-order term): Hpp[f] += J_pose' s J_pose and
+ *                          bp[f] -= J_pose' s e per free pose f (6x6, 6); Hll[p] += J_point' s J_point and
+ *                          bl[p] -= J_point' s e per point (3x3, 3); Hpl[e] = J_pose' s J_point per edge to a free pose (6x3);
+ *                          an edge to a fixed pose feeds Hll and bl only.  A vertex takes part (is ACTIVE) iff it has a
+ *                          level-0 edge; an inactive vertex keeps its estimate.
+ *   L5 solve               per active point inv[p] = (Hll[p] + lambda I)^-1 by the 3x3 cofactor inverse (Eigen's; no test of
+ *                          the determinant, non-finite values follow IEEE); S = Hpp + lambda I - sum Hpl inv Hpl' over the
+ *                          pairs of edges that share a point, g = bp - sum Hpl inv bl, both over 6 slots per free pose (an
+ *                          inactive free pose keeps its slot as an identity block with g = 0: x = 0, coupled to nothing);
+ *                          S xp = g by dense LL' (a pivot that is not > 0 fails the trial, x = 0);
+ *                          xl[p] = inv[p] (bl[p] - sum Hpl' xp); pose <- exp(xp) pose, point <- point + xl.  No free pose:
+ *                          xl = inv bl.
+ *   L6 optimize(k)         the Levenberg-Marquardt loop of orbgpu_pose_optimization (lambda0, nu, at most 10 trials, the rho
+ *                          rule, the termination rules) with: max diag over the diagonals of Hpp and Hll of active
+ *                          vertices, lambda added to both, scale = sum x (lambda x + b) + 1e-3 over pose and point increments
+ *   L7 two rounds (:659-707)  optimize(5) on all edges with Huber; then every edge is classified at the round's final KEPT
+ *                          state (convention (1) of the pose section): chi2 > 5.991 (mono) / 7.815 (stereo), compared in
+ *                          double, or depth not > 0 -> level 1; the kernel is dropped on every edge; optimize(10) on the
+ *                          level-0 edges CONTINUES from round 1's state with lambda re-initialised (g2o recomputes it at
+ *                          iteration 0 of each optimize)
+ *   L8 result (:714-743)   the same test on every edge at the final state: erase[e] = 1 is vToErase.  The pMP->isBad()
+ *                          skips are the caller's.
+ *   L9 stop flag           optional device-readable int32, read by one lane and broadcast: before anything (:655), at the
+ *                          start of each iteration and each trial (g2o's forceStopFlag), and between the rounds (:664).
+ *                          Non-zero at the first read: nothing is written but the result, stopped = 1.  Later: the running
+ *                          optimize ends with the state it has kept, round 2 is skipped (bDoMore), L8 still runs,
+ *                          stopped = 1.  A flag raised while the kernel runs ends it at a time that is NOT reproducible; L10
+ *                          covers runs whose flag does not change.
+ *   L10 determinism        convention (2) of the pose section: every sum over edges, edge pairs or vertices runs in a
+ *                          fixed order (per point: its edges one by one in edge order; per pose, per block of S and over
+ *                          the workgroup: per-lane partial sums, then a fixed tree; no floating-point atomics) -- the same
+ *                          problem gives the same bytes on every run, alone or anywhere in a batch, with S in LDS or in
+ *                          global memory, and agrees with the model to a tolerance, not bit for bit.
+ *   L11 out of range       an edge whose point row, pose row or octave is out of range is skipped, counted in n_bad_index
+ *                          and never read through; its erase byte is not written.
+ *   L12 out                per local pose Tcw_d and (float)Tcw_d (Converter::toCvMat), fixed ones included (the quaternion
+ *                          round trip of their input); per point the double and the float position; erase; the result. */
+#define ORBGPU_LBA_MAX_POSES 1024     /* pose rows (local + fixed cameras) */
+#define ORBGPU_LBA_MAX_FREE 96        /* free poses: the reduced system has 6 * 96 rows */
+#define ORBGPU_LBA_MAX_POINTS 16384
+#define ORBGPU_LBA_MAX_EDGES 262144
+#define ORBGPU_LBA_MAX_PAIRS (1 << 24) /* edge pairs that share a point between free poses (terms of S) */
+
+typedef struct orbgpu_local_ba_result { /* device or host, 8-byte aligned */
+    double chi2_start[2], chi2_end[2]; /* robust chi2 of the active edges per round: at its start, at its kept end */
+    int32_t n_edges;       /* edges taken (E less the out-of-range ones) */
+    int32_t n_erased;      /* erase bytes set */
+    int32_t iterations[2], trials[2]; /* LM iterations and trials per round */
+    int32_t rounds;        /* optimize calls that ran: 0, 1 or 2 */
+    int32_t stopped;       /* the stop flag was seen non-zero */
+    int32_t n_bad_index;   /* edges skipped for an out-of-range row or octave */
+    int32_t reduced_in_lds; /* 1: S lived in LDS, 0: in the global workspace */
+} orbgpu_local_ba_result;
+
+typedef struct orbgpu_local_ba_problem {
+    int32_t n_poses, n_local, n_points, n_edges, nlevels;
+    const float *Tcw;              /* HOST [n_poses][16]: GetPose(), local key frames first */
+    const uint8_t *fixed;          /* HOST [n_local]: non-zero = mnId == 0 */
+    const float *cam;              /* HOST [n_poses][5]: fx, fy, cx, cy, mbf */
+    const float *inv_level_sigma2; /* HOST [n_poses][nlevels] */
+    const float *world_pos;        /* HOST [n_points][3] */
+    const int32_t *edge_point, *edge_pose, *edge_octave; /* HOST [n_edges] */
+    const float *edge_xy;          /* HOST [n_edges][2]: mvKeysUn[...].pt */
+    const float *edge_u_right;     /* HOST [n_edges]: mvuRight[...] */
+    const int32_t *d_stop;         /* device or NULL */
+    double *d_Tcw_d;               /* device [n_local][16] */
+    float *d_Tcw;                  /* device [n_local][16] */
+    double *d_pos_d;               /* device [n_points][3] */
+    float *d_pos;                  /* device [n_points][3] */
+    uint8_t *d_erase;              /* device [n_edges]: written for taken edges only */
+    orbgpu_local_ba_result *d_result; /* device */
+} orbgpu_local_ba_problem;
+
+/* Enqueued on hip_stream, not synchronised; every HOST array is read, and the index structure the fixed summation order
+ * needs (edges sorted by point, per-pose edge lists, per-block pair lists of S) is built and uploaded, before the call
+ * returns.  Calls of one host thread share a workspace and must be ordered on one stream.  EINVAL: null pointers, negative
+ * counts, n_local > n_poses, nlevels outside [1, ORBGPU_MAX_LEVELS], more than ORBGPU_LBA_MAX_* of anything (there is no CPU
+ * fallback: the caller keeps its g2o path); EHIP without a device.  The batch form is ONE launch, one workgroup per problem,
+ * which runs both rounds and every trial without returning to the host. */
+int orbgpu_local_ba_device(const orbgpu_local_ba_problem *p, int32_t device_id, void *hip_stream);
+int orbgpu_local_ba_batch_device(int32_t n, const orbgpu_local_ba_problem *problems, int32_t device_id, void *hip_stream);
+/* Host arrays, synchronises: the d_* members of p are not read; Tcw_d / Tcw [n_local][16], pos_d / pos [n_points][3] and
+ * erase [n_edges] are in/out (a stopped call leaves them alone), any of Tcw_d, pos_d and result may be NULL.  stop: HOST
+ * int32 sampled at the call, or NULL. */
+int orbgpu_local_ba(const orbgpu_local_ba_problem *p, const int32_t *stop, double *Tcw_d, float *Tcw, double *pos_d,
+                    float *pos, uint8_t *erase, orbgpu_local_ba_result *result, int32_t device_id);
+/* Diagnostic: problems of the calling thread's most recent local bundle adjustment on device_id whose reduced system did
+ * not fit the workgroup's LDS (more than 28 free poses; ORBGPU_DEBUG_LBA_LDS_POSES=<k> lowers the limit for tests) and
+ * lived in the global workspace.  Synchronises the device. */
+int orbgpu_local_ba_last_spills(int32_t device_id, int32_t *problems_spilled);
+
 /* ---- Sim3Solver (Sim3Solver.cc, Horn 1987 + RANSAC): the Sim3 of a loop candidate on the device --------------------------
  * The second of the five steps of LoopClosing::ComputeSim3 (LoopClosing.cc:236-343); its result is the R12 / t12 / s12 that
  * orbgpu_search_by_sim3 takes.  All hypotheses of a candidate are evaluated at once, one wave each; the reference's

@@ -1,4 +1,4 @@
-// The FP64 arithmetic the device optimisers share (pose_opt.hip, sim3_opt.hip): quaternions as g2o's SE3Quat / Sim3 use
+// The FP64 arithmetic the device optimisers share (pose_opt.hip, sim3_opt.hip, local_ba.hip): quaternions as g2o's SE3Quat / Sim3 use
 // them, the Huber weights, the dense LL^T solve of the damped normal equation, its initial damping and the fixed-order
 // workgroup sum.  The definition of every function is its namesake in tests/pose_model.py, operation for operation;
 // tests/opt_math_test.cpp builds this header with g++ and tests/test_opt_math.py compares the two bit for bit.  No fused
@@ -7,6 +7,7 @@
 #pragma once
 
 #include <cmath>
+#include <cstddef>
 
 #if defined(__HIPCC__)
 #define ORBGPU_HD __host__ __device__
@@ -181,6 +182,109 @@ template <int N> ORBGPU_HD inline double lm_initial_lambda(const double (&Hu)[N 
             m = fabs(Hu[k]);
     return 1e-5 * m;
 }
+
+// ---- what the bundle adjustment with free points adds (local_ba.hip; definitions in tests/lba_model.py, host test
+// tests/opt_math_lba_test.cpp) ---------------------------------------------------------------------------------------------
+// Inverse of the symmetric 3x3 with upper triangle h = (00, 01, 02, 11, 12, 22) and lam added to its diagonal, by cofactors
+// as Eigen's 3x3 inverse: the determinant from the first column's cofactors, one reciprocal.  inv row-major, all 9 entries.
+ORBGPU_HD inline void inv3_sym(const double h[6], double lam, double inv[9])
+{
+    const double m[3][3] = {{h[0] + lam, h[1], h[2]}, {h[1], h[3] + lam, h[4]}, {h[2], h[4], h[5] + lam}};
+    double c[3][3];
+    ORBGPU_UNROLL
+    for (int i = 0; i < 3; i++)
+        ORBGPU_UNROLL
+        for (int j = 0; j < 3; j++) {
+            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+            c[i][j] = m[i1][j1] * m[i2][j2] - m[i1][j2] * m[i2][j1];
+        }
+    const double det = (c[0][0] * m[0][0] + c[1][0] * m[1][0]) + c[2][0] * m[2][0];
+    const double invdet = 1.0 / det;
+    ORBGPU_UNROLL
+    for (int i = 0; i < 3; i++)
+        ORBGPU_UNROLL
+        for (int j = 0; j < 3; j++)
+            inv[3 * i + j] = c[j][i] * invdet;
+}
+
+// VertexSBAPointXYZ::oplusImpl
+ORBGPU_HD inline void point_update(const double X[3], const double x[3], double Xn[3])
+{
+    ORBGPU_UNROLL
+    for (int i = 0; i < 3; i++)
+        Xn[i] = X[i] + x[i];
+}
+
+// position of (i, j), i >= j, in a lower triangle packed row by row
+ORBGPU_HD inline size_t tri_at(int i, int j)
+{
+    return (size_t)i * (size_t)(i + 1) / 2 + (size_t)j;
+}
+
+// A x = b by LL^T for a symmetric A of runtime size n.  A: its lower triangle packed row by row (tri_at), overwritten with
+// L below the diagonal (the diagonal keeps the pivots before their root); v: b on entry, x on return; work: 2 n doubles.
+// Written for `nt` cooperating threads (this one is `tid`) that call `barrier()` together -- a workgroup with
+// __syncthreads, or one host thread with nothing -- and every entry is computed by the same operations in the same order
+// whatever nt is: column j left-looking (k ascending), forward substitution with k ascending and back substitution with k
+// DESCENDING per row.  A, v and work are shared by the threads.  A pivot that is not > 0 (NaN included): false and x = 0;
+// the return value is the same in every thread.
+template <typename Barrier>
+ORBGPU_HD inline bool llt_solve(int n, double *A, double *v, double *work, int tid, int nt, Barrier barrier)
+{
+    double *dg = work, *y = work + n;
+    for (int j = 0; j < n; j++) {
+        const double *Lj = A + tri_at(j, 0);
+        for (int i = j + tid; i < n; i += nt) {
+            double *Li = A + tri_at(i, 0);
+            double s = Li[j];
+            for (int k = 0; k < j; k++)
+                s = s - Li[k] * Lj[k];
+            Li[j] = s;
+        }
+        barrier();
+        const double d = Lj[j];
+        if (!(d > 0.0)) {
+            barrier();  // every thread has read its pivot before v changes hands
+            for (int i = tid; i < n; i += nt)
+                v[i] = 0.0;
+            barrier();
+            return false;
+        }
+        const double sd = sqrt(d);
+        if (tid == 0)
+            dg[j] = sd;
+        for (int i = j + 1 + tid; i < n; i += nt)
+            A[tri_at(i, j)] = A[tri_at(i, j)] / sd;
+        barrier();
+    }
+    for (int i = tid; i < n; i += nt)
+        y[i] = v[i];
+    barrier();
+    for (int k = 0; k < n; k++) {
+        const double yk = y[k] / dg[k];
+        barrier();  // y[k] is read by all before its owner replaces it
+        if (tid == 0)
+            y[k] = yk;
+        for (int i = k + 1 + tid; i < n; i += nt)
+            y[i] = y[i] - A[tri_at(i, k)] * yk;
+        barrier();
+    }
+    for (int k = n - 1; k >= 0; k--) {
+        const double xk = y[k] / dg[k];
+        const double *Lk = A + tri_at(k, 0);
+        barrier();
+        if (tid == 0)
+            v[k] = xk;
+        for (int i = tid; i < k; i += nt)
+            y[i] = y[i] - Lk[i] * xk;
+        barrier();
+    }
+    return true;
+}
+
+struct NoBarrier {
+    ORBGPU_HD void operator()() const {}
+};
 
 #if defined(__HIPCC__)
 // Fixed-order sum over a workgroup of WAVES waves: shuffle tree inside each wave, then wave 0 + 1 + ... in every lane.

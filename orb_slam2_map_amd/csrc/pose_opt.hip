@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "opt_edges.h"
 #include "opt_math.h"
 #include "staging.h"
 
@@ -38,69 +39,6 @@ struct PoseProblemDev {
     double fx, fy, cx, cy, bf;
     double delta[2], delta2[2];  // Huber delta (mono, stereo) and its square
 };
-
-struct Cam {
-    double fx, fy, cx, cy, bf;
-};
-
-// T' = exp(x) * T with x = (omega, upsilon): SE3Quat::exp (its small-angle branch kept as is) and operator*
-__device__ inline void pose_update(const double q[4], const double t[3], const double x[6], double qn[4], double tn[3])
-{
-    const double w0 = x[0], w1 = x[1], w2 = x[2];
-    const double th = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
-    const double O[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
-    double O2[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++)
-            O2[3 * r + c] = (O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c]) + O[3 * r + 2] * O[6 + c];
-    double R[9], V[9];
-    if (th < 1e-5) {
-#pragma unroll
-        for (int i = 0; i < 9; i++) {
-            R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + O[i]) + O2[i];
-            V[i] = R[i];
-        }
-    } else {
-        const double sn = sin(th), cs = cos(th);
-        const double a = sn / th, b = (1.0 - cs) / (th * th), c = (th - sn) / ((th * th) * th);
-#pragma unroll
-        for (int i = 0; i < 9; i++) {
-            const double I = i % 4 == 0 ? 1.0 : 0.0;
-            R[i] = (I + a * O[i]) + b * O2[i];
-            V[i] = (I + b * O[i]) + c * O2[i];
-        }
-    }
-    double dq[4], dR[9];
-    quat_from_matrix(R, dq);
-    quat_normalize(dq);
-    quat_mul(dq, q, qn);
-    quat_normalize(qn);
-    quat_to_matrix(dq, dR);
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const double dt = (V[3 * r] * x[3] + V[3 * r + 1] * x[4]) + V[3 * r + 2] * x[5];
-        tn[r] = ((dR[3 * r] * t[0] + dR[3 * r + 1] * t[1]) + dR[3 * r + 2] * t[2]) + dt;
-    }
-}
-
-// ---- one edge ----------------------------------------------------------------------------------------------------
-// e = obs - projection (third component 0 for a mono edge), P = R Xw + t, returns chi2 = invSigma2 * e'e
-__device__ inline double edge_error(const double R[9], const double t[3], const Cam &C, const float4 a, const float4 b,
-                                    bool stereo, double e[3], double P[3])
-{
-    const double X0 = (double)a.x, X1 = (double)a.y, X2 = (double)a.z, w = (double)a.w;
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-        P[r] = ((R[3 * r] * X0 + R[3 * r + 1] * X1) + R[3 * r + 2] * X2) + t[r];
-    const double iz = 1.0 / P[2];
-    const double u = (C.fx * P[0]) * iz + C.cx;
-    e[0] = (double)b.x - u;
-    e[1] = (double)b.y - ((C.fy * P[1]) * iz + C.cy);
-    e[2] = stereo ? (double)b.z - (u - C.bf * iz) : 0.0;
-    return w * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-}
 
 // key point i is an edge (1), has an out-of-range row / octave (2), or holds no map point (0)
 __device__ inline int edge_kind(const PoseProblemDev &P, int i, int n)
@@ -220,33 +158,8 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblemDev *_
                 const double chi2 = edge_error(R, t, C, ea, eb, stereo, er, Pc);
                 double rho0, rho1;
                 huber(chi2, P.delta[stereo], P.delta2[stereo], rho0, rho1, use_kernel);
-                const double x = Pc[0], y = Pc[1], z = Pc[2];
-                const double iz = 1.0 / z, iz2 = iz * iz;
                 double J[3][6];
-                J[0][0] = ((x * y) * iz2) * C.fx;
-                J[0][1] = -(1.0 + (x * x) * iz2) * C.fx;
-                J[0][2] = (y * iz) * C.fx;
-                J[0][3] = -iz * C.fx;
-                J[0][4] = 0.0;
-                J[0][5] = (x * iz2) * C.fx;
-                J[1][0] = (1.0 + (y * y) * iz2) * C.fy;
-                J[1][1] = -((x * y) * iz2) * C.fy;
-                J[1][2] = -(x * iz) * C.fy;
-                J[1][3] = 0.0;
-                J[1][4] = -iz * C.fy;
-                J[1][5] = (y * iz2) * C.fy;
-                if (stereo) {
-                    J[2][0] = J[0][0] - (C.bf * y) * iz2;
-                    J[2][1] = J[0][1] + (C.bf * x) * iz2;
-                    J[2][2] = J[0][2];
-                    J[2][3] = J[0][3];
-                    J[2][4] = 0.0;
-                    J[2][5] = J[0][5] - C.bf * iz2;
-                } else {
-#pragma unroll
-                    for (int a = 0; a < 6; a++)
-                        J[2][a] = 0.0;
-                }
+                pose_jacobian(Pc, C, stereo, J);
                 const double s = (double)ea.w * rho1;
                 double Jw[3][6];
 #pragma unroll

@@ -119,6 +119,28 @@ class PoseProblem(C.Structure):
                 ("d_result", C.c_void_p)]
 
 
+class LocalBAResult(C.Structure):
+    _fields_ = [("chi2_start", C.c_double * 2), ("chi2_end", C.c_double * 2), ("n_edges", C.c_int32), ("n_erased", C.c_int32),
+                ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2), ("rounds", C.c_int32), ("stopped", C.c_int32),
+                ("n_bad_index", C.c_int32), ("reduced_in_lds", C.c_int32)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k in ("n_edges", "n_erased", "rounds", "stopped", "n_bad_index", "reduced_in_lds")}
+        d.update(chi2_start=list(self.chi2_start), chi2_end=list(self.chi2_end), iterations=list(self.iterations),
+                 trials=list(self.trials))
+        return d
+
+
+class LocalBAProblem(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_poses", "n_local", "n_points", "n_edges", "nlevels")] + \
+               [(k, C.c_void_p) for k in ("Tcw", "fixed", "cam", "inv_level_sigma2", "world_pos", "edge_point", "edge_pose",
+                                          "edge_octave", "edge_xy", "edge_u_right", "d_stop", "d_Tcw_d", "d_Tcw", "d_pos_d",
+                                          "d_pos", "d_erase", "d_result")]
+
+
+LBA_MAX_POSES, LBA_MAX_FREE, LBA_MAX_POINTS, LBA_MAX_EDGES = 1024, 96, 16384, 262144
+
+
 class Sim3Result(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n", "max_its", "n_bad_index", "n_bad_triple", "accepted", "n_inliers",
                                          "best_inliers", "best_iteration", "iterations", "no_more")]
@@ -241,6 +263,7 @@ ABI_SYMBOLS = [
     "orbgpu_frame_device_view", "orbgpu_search_local_points_table", "orbgpu_search_by_projection_last_table",
     "orbgpu_pose_optimization", "orbgpu_pose_optimization_device", "orbgpu_pose_optimization_batch_device",
     "orbgpu_pose_optimization_table", "orbgpu_pose_last_spills",
+    "orbgpu_local_ba", "orbgpu_local_ba_device", "orbgpu_local_ba_batch_device", "orbgpu_local_ba_last_spills",
     "orbgpu_sim3_ransac_iterations", "orbgpu_sim3_solve_device", "orbgpu_sim3_solve_batch_device", "orbgpu_sim3_solve",
     "orbgpu_sim3_solve_all",
     "orbgpu_sim3_optimize", "orbgpu_sim3_optimize_device", "orbgpu_sim3_optimize_batch_device",
@@ -1041,6 +1064,77 @@ def pose_last_spills(device_id=0):
     L.orbgpu_pose_last_spills.argtypes = [C.c_int32, C.c_void_p]
     v = C.c_int32()
     check(L.orbgpu_pose_last_spills(device_id, C.byref(v)))
+    return v.value
+
+
+_LBA_HOST = (("Tcw", np.float32), ("fixed", np.uint8), ("cam", np.float32), ("inv_level_sigma2", np.float32),
+             ("world_pos", np.float32), ("edge_point", np.int32), ("edge_pose", np.int32), ("edge_octave", np.int32),
+             ("edge_xy", np.float32), ("edge_u_right", np.float32))
+_LBA_PTRS = ("d_stop", "d_Tcw_d", "d_Tcw", "d_pos_d", "d_pos", "d_erase", "d_result")
+
+
+def local_ba_problem(p, keep):
+    """A LocalBAProblem from a dict: Tcw [P][4][4] (the n_local local key frames first, then the fixed cameras), fixed
+    [n_local], cam [P][5] (fx, fy, cx, cy, mbf), inv_level_sigma2 [P][nlevels], world_pos [M][3], edge_point / edge_pose /
+    edge_octave [E], edge_xy [E][2], edge_u_right [E] (host arrays) and the device pointers d_stop (or None), d_Tcw_d,
+    d_Tcw, d_pos_d, d_pos, d_erase, d_result (holds a LocalBAResult).  The counts follow the arrays unless the dict names
+    them (n_poses, n_points, n_edges, nlevels); keep takes the host arrays the structure points to."""
+    q = LocalBAProblem()
+    a = {k: np.ascontiguousarray(p[k], t) for k, t in _LBA_HOST}
+    keep.append(a)
+    q.n_local = int(p["n_local"])
+    q.n_poses = int(p.get("n_poses", a["Tcw"].size // 16))
+    q.n_points = int(p.get("n_points", a["world_pos"].size // 3))
+    q.n_edges = int(p.get("n_edges", a["edge_point"].size))
+    q.nlevels = int(p.get("nlevels", a["inv_level_sigma2"].size // max(q.n_poses, 1)))
+    for k, _ in _LBA_HOST:
+        setattr(q, k, a[k].ctypes.data if a[k].size else None)
+    _set_pointers(q, p, _LBA_PTRS)
+    return q
+
+
+def local_ba_batch_device(problems, stream=0, device_id=0):
+    """n independent Optimizer::LocalBundleAdjustment problems in ONE launch (orbgpu_local_ba_batch_device); enqueued, not
+    synchronised.  problems: dicts as local_ba_problem takes them."""
+    keep = []
+    _batch_device("local_ba", LocalBAProblem, lambda p: local_ba_problem(p, keep), problems, stream, device_id)
+
+
+def local_ba_device(problem, stream=0, device_id=0):
+    """One problem (orbgpu_local_ba_device); see local_ba_batch_device."""
+    keep = []
+    _one_device("local_ba", local_ba_problem(problem, keep), stream, device_id)
+
+
+def local_ba(problem, stop=None, Tcw_d=None, Tcw=None, pos_d=None, pos=None, erase=None, device_id=0):
+    """Optimizer::LocalBundleAdjustment over host arrays (orbgpu_local_ba); problem: the host part of the dict
+    local_ba_problem takes.  stop: None or an int sampled at the call.  The outputs start from the arrays given (zeros
+    by default): a stopped call and a skipped edge leave them as they were.  Returns (Tcw_d [n_local][4][4], Tcw, pos_d
+    [M][3], pos, erase [E], result dict)."""
+    keep = []
+    q = local_ba_problem(problem, keep)
+    nl, M, E = q.n_local, q.n_points, q.n_edges
+
+    def start(a, shape, t):
+        return np.zeros(shape, t) if a is None else np.array(a, t).reshape(shape).copy()
+    Td, T = start(Tcw_d, (max(nl, 1), 4, 4), np.float64), start(Tcw, (max(nl, 1), 4, 4), np.float32)
+    Xd, X = start(pos_d, (max(M, 1), 3), np.float64), start(pos, (max(M, 1), 3), np.float32)
+    er = start(erase, (max(E, 1),), np.uint8)
+    sv = None if stop is None else C.c_int32(int(stop))
+    res = LocalBAResult()
+    L = lib()
+    L.orbgpu_local_ba.argtypes = [C.c_void_p] * 8 + [C.c_int32]
+    check(L.orbgpu_local_ba(C.byref(q), None if sv is None else C.byref(sv), _p(Td), _p(T), _p(Xd), _p(X), _p(er),
+                            C.byref(res), device_id))
+    return Td[:nl], T[:nl], Xd[:M], X[:M], er[:E], res.as_dict()
+
+
+def local_ba_last_spills(device_id=0):
+    """Problems of this thread's most recent local bundle adjustment whose reduced system lived in global memory."""
+    L = lib()
+    L.orbgpu_local_ba_last_spills.argtypes = [C.c_int32, C.c_void_p]
+    v = C.c_int32()
+    check(L.orbgpu_local_ba_last_spills(device_id, C.byref(v)))
     return v.value
 
 

@@ -1068,6 +1068,100 @@ template <typename KeyFrameT, typename MapPointT> struct Sim3OptRows {
     }
 };
 
+// The graph of Optimizer::LocalBundleAdjustment as orbgpu_local_ba takes it: the breadth-first gathering of
+// Optimizer.cc:455-504 (it walks pointers, so it stays on the host) in the reference's list order, then the vertices and
+// edges of :522-652.  Pose rows: lLocalKeyFrames, then lFixedCameras; point rows: lLocalMapPoints; edges: per point in list
+// order, its observations in the order of the map GetObservations() returns.  Marks mnBALocalForKF / mnBAFixedForKF as
+// the reference does.  An observation by a key frame that is bad is no edge (:589); one by a key frame that is in neither
+// list, or at an octave outside that key frame's sigma table, keeps its row with pose / octave -1: the library skips and
+// counts it (the reference reads through a null vertex / out of range there).
+template <typename KeyFrameT, typename MapPointT> struct LocalBAGraph {
+    std::vector<KeyFrameT *> local, fixed, edge_kf;
+    std::vector<MapPointT *> points, edge_mp;
+    std::vector<int32_t> edge_point, edge_pose, edge_octave;
+    std::vector<float> edge_xy, edge_ur, Tcw, cam, inv_sigma2, world_pos;
+    std::vector<uint8_t> fixed_flag;
+    int nlevels = 1;
+
+    template <typename Access> LocalBAGraph(KeyFrameT *pKF, Access &access)
+    {
+        local.push_back(pKF);
+        pKF->mnBALocalForKF = pKF->mnId;
+        const std::vector<KeyFrameT *> vNeighKFs = pKF->GetVectorCovisibleKeyFrames();
+        for (KeyFrameT *pKFi : vNeighKFs) {
+            pKFi->mnBALocalForKF = pKF->mnId;
+            if (!pKFi->isBad())
+                local.push_back(pKFi);
+        }
+        for (KeyFrameT *pKFi : local) {
+            const std::vector<MapPointT *> vpMPs = pKFi->GetMapPointMatches();
+            for (MapPointT *pMP : vpMPs)
+                if (pMP && !pMP->isBad() && pMP->mnBALocalForKF != pKF->mnId) {
+                    points.push_back(pMP);
+                    pMP->mnBALocalForKF = pKF->mnId;
+                }
+        }
+        for (MapPointT *pMP : points) {
+            const auto observations = pMP->GetObservations();
+            for (const auto &ob : observations) {
+                KeyFrameT *pKFi = ob.first;
+                if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) {
+                    pKFi->mnBAFixedForKF = pKF->mnId;
+                    if (!pKFi->isBad())
+                        fixed.push_back(pKFi);
+                }
+            }
+        }
+        std::map<KeyFrameT *, int32_t> row;
+        nlevels = (int)std::max<size_t>(1, std::min(pKF->mvInvLevelSigma2.size(), (size_t)ORBGPU_MAX_LEVELS));
+        const size_t P = local.size() + fixed.size();
+        Tcw.assign(16 * P, 0.f), cam.assign(5 * P, 0.f), inv_sigma2.assign((size_t)nlevels * P, 0.f);
+        fixed_flag.assign(local.size(), 0);
+        for (size_t i = 0; i < P; i++) {
+            KeyFrameT *k = i < local.size() ? local[i] : fixed[i - local.size()];
+            row[k] = (int32_t)i;
+            std::memcpy(&Tcw[16 * i], access.pose(k), 64);
+            const float c[5] = {k->fx, k->fy, k->cx, k->cy, k->mbf};
+            std::memcpy(&cam[5 * i], c, sizeof(c));
+            for (size_t l = 0; l < std::min(k->mvInvLevelSigma2.size(), (size_t)nlevels); l++)
+                inv_sigma2[(size_t)nlevels * i + l] = k->mvInvLevelSigma2[l];
+            if (i < local.size())
+                fixed_flag[i] = k->mnId == 0;
+        }
+        world_pos.assign(3 * points.size() + 3, 0.f);  // one spare row so that data() is never null
+        for (size_t j = 0; j < points.size(); j++) {
+            MapPointT *pMP = points[j];
+            std::memcpy(&world_pos[3 * j], access.world_pos(pMP), 12);
+            const auto observations = pMP->GetObservations();
+            for (const auto &ob : observations) {
+                KeyFrameT *pKFi = ob.first;
+                if (pKFi->isBad())
+                    continue;
+                const auto &kpUn = pKFi->mvKeysUn[ob.second];
+                const auto it = row.find(pKFi);
+                const bool has_sigma = kpUn.octave >= 0 && (size_t)kpUn.octave < pKFi->mvInvLevelSigma2.size();
+                edge_kf.push_back(pKFi), edge_mp.push_back(pMP);
+                edge_point.push_back((int32_t)j), edge_pose.push_back(it == row.end() ? -1 : it->second);
+                edge_octave.push_back(has_sigma ? kpUn.octave : -1);
+                edge_xy.push_back(kpUn.pt.x), edge_xy.push_back(kpUn.pt.y), edge_ur.push_back(pKFi->mvuRight[ob.second]);
+            }
+        }
+    }
+
+    // the host part of the library's problem; valid while the graph lives
+    orbgpu_local_ba_problem Problem() const
+    {
+        orbgpu_local_ba_problem p;
+        std::memset(&p, 0, sizeof(p));
+        p.n_poses = (int32_t)(local.size() + fixed.size()), p.n_local = (int32_t)local.size();
+        p.n_points = (int32_t)points.size(), p.n_edges = (int32_t)edge_point.size(), p.nlevels = nlevels;
+        p.Tcw = Tcw.data(), p.fixed = fixed_flag.data(), p.cam = cam.data(), p.inv_level_sigma2 = inv_sigma2.data();
+        p.world_pos = world_pos.data(), p.edge_point = edge_point.data(), p.edge_pose = edge_pose.data();
+        p.edge_octave = edge_octave.data(), p.edge_xy = edge_xy.data(), p.edge_u_right = edge_ur.data();
+        return p;
+    }
+};
+
 template <typename FrameT, typename MapPointT> class OptimizerT {
   public:
     // host arrays: one upload per call
@@ -1187,6 +1281,62 @@ template <typename FrameT, typename MapPointT> class OptimizerT {
         if (result)
             *result = r;
         return inliers;
+    }
+
+    // Optimizer::LocalBundleAdjustment (include/Optimizer.h:50, src/Optimizer.cc:453-778): the local key frames and the
+    // points they see.  Side effects as in the reference: under pMap->mMutexMapUpdate, EraseMapPointMatch /
+    // EraseObservation for every observation the final test rejects (its map point not bad by then, :720, :735), SetPose of
+    // every local key frame, SetWorldPos + UpdateNormalAndDepth of every local point; nothing at all when *pbStopFlag is
+    // set at the call (:655).  The flag is sampled once, at the call: a flag raised later does not reach the device
+    // through this host flavour (orbgpu_local_ba_device takes a device-readable flag).  The conventions are L1-L12 of
+    // include/orbgpu.h ("g2o unpinned").  KeyFrameT needs mnId, mnBALocalForKF, mnBAFixedForKF,
+    // GetVectorCovisibleKeyFrames(), GetMapPointMatches(), isBad(), mvKeysUn, mvuRight, mvInvLevelSigma2, fx, fy, cx, cy,
+    // mbf, EraseMapPointMatch(MapPointT *); MapPointT mnId, mnBALocalForKF, isBad(), GetObservations(),
+    // EraseObservation(KeyFrameT *), UpdateNormalAndDepth(); MapT mMutexMapUpdate.  access: pose(pKF) the 16 floats of
+    // Tcw, world_pos(pMP) 3 floats (both valid until the next call of the same accessor), set_pose(pKF, T),
+    // set_world_pos(pMP, x); with a table also normal(pMP), min_dist(pMP), max_dist(pMP), read after
+    // UpdateNormalAndDepth for the batched MapPointTableT::SetWorldPos.  Beyond the library's capacities
+    // (ORBGPU_LBA_MAX_*) the call throws: the caller keeps its g2o path for such maps.
+    template <typename KeyFrameT, typename MapT, typename Access>
+    static void LocalBundleAdjustment(KeyFrameT *pKF, bool *pbStopFlag, MapT *pMap, Access access,
+                                      MapPointTableT<MapPointT> *table = nullptr, int device_id = 0,
+                                      orbgpu_local_ba_result *result = nullptr)
+    {
+        const LocalBAGraph<KeyFrameT, MapPointT> g(pKF, access);
+        const orbgpu_local_ba_problem p = g.Problem();
+        const size_t nl = g.local.size(), M = g.points.size(), E = g.edge_point.size();
+        std::vector<float> T(16 * nl), X(3 * M + 3);
+        std::vector<uint8_t> erase(E + 1, 0);
+        const int32_t stop = pbStopFlag && *pbStopFlag ? 1 : 0;
+        orbgpu_local_ba_result r;
+        check(orbgpu_local_ba(&p, pbStopFlag ? &stop : nullptr, nullptr, T.data(), nullptr, X.data(), erase.data(), &r, device_id),
+              "Optimizer::LocalBundleAdjustment");
+        if (result)
+            *result = r;
+        if (r.stopped && r.rounds == 0)
+            return;
+        std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+        std::vector<MapPointT *> touched;
+        for (size_t e = 0; e < E; e++)
+            if (erase[e] && !g.edge_mp[e]->isBad()) {
+                g.edge_kf[e]->EraseMapPointMatch(g.edge_mp[e]);
+                g.edge_mp[e]->EraseObservation(g.edge_kf[e]);
+                touched.push_back(g.edge_mp[e]);
+            }
+        for (size_t i = 0; i < nl; i++)
+            access.set_pose(g.local[i], &T[16 * i]);
+        for (size_t j = 0; j < M; j++) {
+            access.set_world_pos(g.points[j], &X[3 * j]);
+            g.points[j]->UpdateNormalAndDepth();
+        }
+        if (table) {
+            if (!touched.empty())
+                table->SetObservations(touched);
+            table->SetWorldPos(g.points, [&access](MapPointT *q) { return access.world_pos(q); },
+                               [&access](MapPointT *q) { return access.normal(q); },
+                               [&access](MapPointT *q) { return access.min_dist(q); },
+                               [&access](MapPointT *q) { return access.max_dist(q); });
+        }
     }
 };
 
