@@ -1211,6 +1211,114 @@ int orbgpu_initializer_all(const orbgpu_init_problem *p, float *scores_h, float 
                            uint64_t *masks_f, float *P3D, uint8_t *triangulated, orbgpu_init_result *result,
                            int32_t device_id);
 
+/* ---- LocalMapping::CreateNewMapPoints (LocalMapping.cc:207-452): the neighbour loop on the device ------------------------
+ * One call runs the loop for one current key frame (kf1) and nn neighbours: per neighbour SearchForTriangulation, then per
+ * match the parallax branch, the 4x4 triangulation or the stereo back-projection, and the depth, reprojection and scale
+ * gates.  Neighbour k's matcher skips the key points of kf1 that got a point from neighbours < k (ORBmatcher.cc:702-705
+ * reads GetMapPoint): a working copy of kf1's has_mp carries that on the device, all launches go onto one stream and the
+ * host is not consulted in between.  The caller chooses the neighbours, applies the baseline / median-depth test
+ * (:244-261), computes F12 and the epipole, and does the map edits (:434-449) from the outputs in (neighbour, key point)
+ * order.  vs CPU restatement; OpenCV boundary unpinned -- tests/newpts_model.py is the restatement.  Conventions:
+ *   N1 match (:268)        per neighbour exactly orbgpu_search_for_triangulation (same device code) over has_mp1 OR every
+ *                          status > 0 of earlier neighbours; the caller's has_mp array is not written.
+ *   N2 rays (:300-304)     xn = ((x - cx) * invfx, (y - cy) * invfy, 1) in float; Rwc = the transpose of Tcw's rotation (the
+ *                          reference's Rcw.t()); 3x3 . 3x1 products in float, (a b + c d) + e f, then the added term if any.
+ *   N3 parallax (:305-319) Mat::dot and cv::norm are FP64 sums over the float entries (norm: sqrt of the sum, kept in
+ *                          double); cosParallaxRays = (float)(dot / (norm1 * norm2)); cosParallaxStereo = cosRays + 1 in
+ *                          float; cos_stereo[i] = cos(2*atan2(mb/2, mvDepth[i])) comes from the caller (no libm on the
+ *                          device); kf2's is only looked at when kf1's key point is not stereo (the else-if of :313);
+ *                          `cosRays < 0.9998` compares in double.
+ *   N4 A (:322-326)        rows x * Tcw.row(2) - Tcw.row(0) etc., float, one rounding per operation.
+ *   N5 null vector (:329-337)  A'A in FP64 in row order, cyclic Jacobi in one lane (I9's jacobi4_lane), the eigenvector of
+ *                          the least eigenvalue (last of the stable descending order, sign rule), rounded to float; fourth
+ *                          component == 0 rejects; the point is the float quotient by it.
+ *   N6 UnprojectStereo (KeyFrame.cc:653-669)  z = depth[i]; x = (u - cx) * z * invfx, y likewise, float, left to right, with
+ *                          (u, v) = kp_raw[i] (mvKeys, not mvKeysUn; NULL: kp_x / kp_y); Twc's rotation times (x, y, z) plus
+ *                          its translation as N2.  Deviation D2: depth <= 0 rejects (the reference dereferences an empty Mat).
+ *   N7 finite              deviation D1: a point with a non-finite coordinate rejects (the reference keeps it: NaN fails
+ *                          every > test).
+ *   N8 depths (:354-360)   z = (float)(dot + (double)t) with dot the FP64 sum over float entries; x, y likewise.
+ *   N9 reprojection (:363-413)  invz = (float)(1.0 / (double)z); u = fx * x * invz + cx in float left to right; u_r = u -
+ *                          mbf * invz with kf1's mbf for BOTH key frames (:406 restated); the error sums in float left to
+ *                          right, compared as (double)err2 > 5.991 * (double)sigma2 (mono) or 7.8 (stereo); sigma2 =
+ *                          level_sigma2[octave] of the frame.
+ *   N10 scale (:416-431)   normal = x3D - Ow in float with Ow = Twc's translation; dist = (float)sqrt(FP64 sum); either == 0
+ *                          rejects; ratioDist = dist2 / dist1, ratioOctave = scale1[o1] / scale2[o2] in float;
+ *                          ratioDist * ratio_factor < ratioOctave || ratioDist > ratioOctave * ratio_factor rejects.
+ *   N11 outputs            [nn][n1] indexed by kf1's key point: match12 (after the rotation check), status, x3d (zeros unless
+ *                          status > 0); n_matches[nn], n_created[nn], n_done.  Two key points of kf1 may create a point on
+ *                          the same key point of kf2 (the reference's later AddMapPoint overwrites the earlier).
+ *   N12 stop flag (:239)   optional device-readable int32; a single-workgroup kernel latches go/stop once per neighbour
+ *                          before that neighbour's matcher, so a neighbour is processed completely or not at all; neighbour 0
+ *                          always is; once one is skipped all later ones are (match12 -1, status 0, x3d 0, counts 0).  The
+ *                          result is reproducible only for a flag that does not change during the call.
+ *   N13 determinism        no floating-point atomics; every device loop has a fixed bound; the same problem gives the same
+ *                          bytes.
+ *   Limits                 nn in [0, ORBGPU_NEW_POINTS_MAX_NEIGHBOURS]; key points per frame in [0, 65535]; nlevels in
+ *                          [1, ORBGPU_MAX_LEVELS].  An octave outside [0, nlevels) is EINVAL in the host flavour; the device
+ *                          flavour cannot see the arrays: such a candidate never matches and such a key point of kf1
+ *                          rejects with ORBGPU_NP_BAD_OCTAVE, nothing is read out of range. */
+#define ORBGPU_NEW_POINTS_MAX_NEIGHBOURS 32
+enum {
+    ORBGPU_NP_NONE = 0,            /* no match */
+    ORBGPU_NP_TRIANGULATED = 1,    /* :320-339 */
+    ORBGPU_NP_UNPROJECT1 = 2,      /* :342 */
+    ORBGPU_NP_UNPROJECT2 = 3,      /* :346 */
+    ORBGPU_NP_LOW_PARALLAX = -1,   /* :349 */
+    ORBGPU_NP_W_ZERO = -2,         /* :333 */
+    ORBGPU_NP_Z1 = -3,             /* :355 */
+    ORBGPU_NP_Z2 = -4,             /* :359 */
+    ORBGPU_NP_REPROJ1 = -5,        /* :374 / :385 */
+    ORBGPU_NP_REPROJ2 = -6,        /* :400 / :411 */
+    ORBGPU_NP_ZERO_DIST = -7,      /* :422 */
+    ORBGPU_NP_SCALE = -8,          /* :430 */
+    ORBGPU_NP_NON_FINITE = -9,     /* D1 */
+    ORBGPU_NP_STEREO_DEPTH = -10,  /* D2 */
+    ORBGPU_NP_BAD_OCTAVE = -11     /* device flavour only, see Limits */
+};
+/* A key frame as CreateNewMapPoints reads it; arrays [n], device pointers in the device flavour and host pointers in the
+ * host flavour.  kp_angle may be NULL without check_orientation, kp_raw may be NULL (N6).  F12 (row-major, as
+ * orbgpu_search_for_triangulation takes it) and the epipole are read for neighbours only; a neighbour's mbf is not read. */
+typedef struct orbgpu_new_points_frame {
+    int32_t n, nlevels;
+    const float *kp_x, *kp_y;   /* mvKeysUn */
+    const int32_t *kp_octave;
+    const float *kp_angle;
+    const float *u_right;       /* mvuRight */
+    const uint8_t *desc;        /* [n][32] */
+    const uint8_t *has_mp;      /* the key point has a map point */
+    const int32_t *node;        /* orbgpu_bow_transform's node_id */
+    const float *depth;         /* mvDepth */
+    const float *kp_raw;        /* [n][2] mvKeys[i].pt or NULL */
+    const float *cos_stereo;    /* N3 */
+    float Tcw[16], Twc[16];     /* both as the key frame stores them */
+    float fx, fy, cx, cy, invfx, invfy, mbf;
+    float level_sigma2[ORBGPU_MAX_LEVELS], scale_factors[ORBGPU_MAX_LEVELS];
+    float F12[9], ex, ey;
+} orbgpu_new_points_frame;
+
+typedef struct orbgpu_new_points_problem {
+    orbgpu_new_points_frame kf1;
+    const orbgpu_new_points_frame *neighbours; /* HOST array [nn] in both flavours */
+    int32_t nn;
+    int32_t only_stereo, check_orientation;
+    float ratio_factor;      /* 1.5f * mfScaleFactor */
+    const int32_t *stop;     /* N12 or NULL; the host flavour samples *stop at the call */
+    int32_t *match12;        /* [nn][n1] */
+    int32_t *status;         /* [nn][n1] */
+    float *x3d;              /* [nn][n1][3] */
+    int32_t *n_matches;      /* [nn] */
+    int32_t *n_created;      /* [nn] */
+    int32_t *n_done;         /* [1] neighbours processed */
+} orbgpu_new_points_problem;
+
+/* Device arrays, enqueued on hip_stream; workspace rules as orbgpu_pnp_solve_device (one call at a time per thread and
+ * device), but nothing is waited for: the call returns once the launches are queued.  EINVAL (nothing launched): null
+ * pointers, a limit violated.  EHIP without a device. */
+int orbgpu_create_new_map_points_device(const orbgpu_new_points_problem *p, int32_t device_id, void *hip_stream);
+/* Host arrays: one staged upload of everything, the chain, one download; synchronises. */
+int orbgpu_create_new_map_points(const orbgpu_new_points_problem *p, int32_t device_id);
+
 
 /* LastFrame members read by SearchByProjection(CurrentFrame, LastFrame, th, bMono). */
 typedef struct {

@@ -16,6 +16,7 @@
 
 #include "carve.h"
 #include "common.h"
+#include "jacobi4.h"
 #include "ransac_host.h"
 #include "staging.h"
 
@@ -23,8 +24,6 @@ namespace orbgpu {
 namespace {
 
 constexpr int INIT_MAX_N = 16384, INIT_MAX_HYP = 4096;
-constexpr int INIT_JACOBI_SWEEPS = 30;
-constexpr double INIT_JACOBI_STOP = 1e-32;
 constexpr int ILD = 12;  // row stride of the LDS matrices
 
 struct InitCtl {
@@ -628,58 +627,9 @@ __global__ __launch_bounds__(64) void k_init_select(const InitProblemDev *__rest
 }
 
 // ---- I9 ---------------------------------------------------------------------------------------------------------------------
-// Cyclic Jacobi of a symmetric 4 x 4 in the registers of one lane: the same pairs, rotations and stopping rule as
-// jacobi_wave.  Lanes diverge only in how many sweeps they need.
-__device__ inline void jacobi4_lane(double (&A)[4][4], double (&V)[4][4])
-{
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            V[i][j] = i == j ? 1.0 : 0.0;
-#pragma unroll 1
-    for (int sweep = 0; sweep < INIT_JACOBI_SWEEPS; sweep++) {
-        double off = 0.0, diag = 0.0;
-#pragma unroll
-        for (int p = 0; p < 4; p++)
-#pragma unroll
-            for (int q = p + 1; q < 4; q++)
-                off = off + A[p][q] * A[p][q];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            diag = diag + A[i][i] * A[i][i];
-        if (off <= INIT_JACOBI_STOP * (diag + 2.0 * off))
-            break;
-#pragma unroll
-        for (int p = 0; p < 4; p++)
-#pragma unroll
-            for (int q = p + 1; q < 4; q++) {
-                const double apq = A[p][q];
-                if (!(apq == 0.0)) {
-                    const double app = A[p][p], aqq = A[q][q];
-                    const double theta = (aqq - app) / (2.0 * apq);
-                    const double den = fabs(theta) + sqrt(theta * theta + 1.0);
-                    const double t = theta >= 0.0 ? 1.0 / den : -1.0 / den;
-                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        if (r != p && r != q) {
-                            const double arp = A[r][p], arq = A[r][q];
-                            const double np = c * arp - s * arq, nq = s * arp + c * arq;
-                            A[r][p] = A[p][r] = np;
-                            A[r][q] = A[q][r] = nq;
-                        }
-                        const double vrp = V[r][p], vrq = V[r][q];
-                        V[r][p] = c * vrp - s * vrq;
-                        V[r][q] = s * vrp + c * vrq;
-                    }
-                    A[p][p] = app - t * apq, A[q][q] = aqq + t * apq;
-                    A[p][q] = A[q][p] = 0.0;
-                }
-            }
-    }
-}
-
+// jacobi4_lane: jacobi4.h, shared with new_points.hip
+// (jacobi4.h's null_vector4 restates the A'A / selection / sign steps k_init_checkrt has inline below: an edit here is an edit
+// there)
 // grid (8, problems), one wave per motion
 __global__ __launch_bounds__(64) void k_init_checkrt(const InitProblemDev *__restrict__ problems)
 {

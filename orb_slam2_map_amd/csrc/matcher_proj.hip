@@ -15,6 +15,7 @@
 // only a row whose 16 cached candidates cannot decide is walked again with the claim filter.
 #include "common.h"
 #include "matcher_common.h"
+#include "tri_match.h"
 #include "staging.h"
 #include "proj_internal.h"
 #include "proj_boundary.h"  // struct Query and everything that fills one on the host
@@ -1071,18 +1072,7 @@ __global__ __launch_bounds__(256) void k_project_last_queries(int rows, const in
 }
 
 // ---- ORBmatcher::SearchForTriangulation (ORBmatcher.cc:657-823) ---------------------------------------------
-struct TriParams {
-    float F12[9];
-    float ex, ey;  // epipole in the second image (:664-670)
-    int only_stereo;
-    float sigma2[ORBGPU_MAX_LEVELS], scale[ORBGPU_MAX_LEVELS];  // of key frame 2
-};
-
-// One wave per key point of key frame 1 without a map point: its candidates are the key points of key frame 2 under
-// the same vocabulary node (node2 == node1 >= 0) without a map point; Hamming <= TH_LOW, the epipole distance test
-// for monocular pairs, the epipolar-line test (:140-157), least distance, the LAST among equals in the node's list
-// (`dist > bestDist` is the skip, :739), i.e. the largest index.  The reference never sets vbMatched2, so rows do
-// not interact.  Rotation histogram: k_tri_finish.
+// The match body lives in tri_match.h, shared with the neighbour chain of new_points.hip.
 __global__ __launch_bounds__(256) void k_tri_match(int n1, const float *__restrict__ x1, const float *__restrict__ y1,
                                                    const float *__restrict__ ur1, const uint8_t *__restrict__ has_mp1,
                                                    const int *__restrict__ node1, const uint8_t *__restrict__ desc1,
@@ -1092,60 +1082,11 @@ __global__ __launch_bounds__(256) void k_tri_match(int n1, const float *__restri
                                                    const uint8_t *__restrict__ desc2, TriParams P,
                                                    int *__restrict__ match12)
 {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n1)
-        return;
-    int best = -1;
-    const int nd = node1[i];
-    const bool stereo1 = ur1[i] >= 0;
-    if (nd >= 0 && !has_mp1[i] && !(P.only_stereo && !stereo1)) {
-        const uint64_t *pa = reinterpret_cast<const uint64_t *>(desc1) + (size_t)i * 4;
-        const uint64_t a[4] = {pa[0], pa[1], pa[2], pa[3]};
-        const float kx = x1[i], ky = y1[i];
-        // epipolar line in the second image l = x1' F12 (:143-145)
-        const float la = kx * P.F12[0] + ky * P.F12[3] + P.F12[6];
-        const float lb = kx * P.F12[1] + ky * P.F12[4] + P.F12[7];
-        const float lc = kx * P.F12[2] + ky * P.F12[5] + P.F12[8];
-        const float den = la * la + lb * lb;
-        uint32_t key = 0xFFFFFFFFu;  // distance << 16 | (65535 - idx2): least distance, then largest index
-        for (int j = lane; j < n2; j += 64) {
-            if (node2[j] != nd || has_mp2[j])
-                continue;
-            const bool stereo2 = ur2[j] >= 0;
-            if (P.only_stereo && !stereo2)
-                continue;
-            const uint64_t *pb = reinterpret_cast<const uint64_t *>(desc2) + (size_t)j * 4;
-            const uint64_t b[4] = {pb[0], pb[1], pb[2], pb[3]};
-            const int dist = hamming256(a, b);
-            if (dist > ORBGPU_TH_LOW)
-                continue;
-            const float px = x2[j], py = y2[j];
-            const int o = oct2[j];
-            if (!stereo1 && !stereo2) {
-                const float dex = P.ex - px, dey = P.ey - py;
-                if (dex * dex + dey * dey < 100 * P.scale[o])
-                    continue;
-            }
-            const float num = la * px + lb * py + lc;
-            if (den == 0)
-                continue;
-            const float dsqr = num * num / den;
-            if (!((double)dsqr < 3.84 * (double)P.sigma2[o]))
-                continue;
-            key = min(key, ((uint32_t)dist << 16) | (uint32_t)(65535 - j));
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-            key = min(key, (uint32_t)__shfl_xor((int)key, off, 64));
-        if (key != 0xFFFFFFFFu)
-            best = 65535 - (int)(key & 0xFFFFu);
-    }
-    if (lane == 0)
-        match12[i] = best;
+    tri_match_wave<false>(n1, x1, y1, ur1, has_mp1, node1, desc1, n2, x2, y2, oct2, ur2, has_mp2, node2, desc2, P, match12);
 }
 
 // rotation consistency of the accepted pairs (:772-795) and the count; one workgroup
+// (tri_match.h's tri_finish_block is a copy of this text for new_points.hip: an edit here is an edit there)
 __global__ __launch_bounds__(1024) void k_tri_finish(int n1, const float *__restrict__ angle1,
                                                      const float *__restrict__ angle2, int check_orientation,
                                                      int *__restrict__ match12, int *__restrict__ nmatches)

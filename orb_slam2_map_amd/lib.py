@@ -236,6 +236,27 @@ class InitProblem(C.Structure):
                 ("result", C.c_void_p)]
 
 
+class NewPointsFrame(C.Structure):
+    _fields_ = [("n", C.c_int32), ("nlevels", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("kp_x", "kp_y", "kp_octave", "kp_angle", "u_right", "desc", "has_mp", "node", "depth",
+                                          "kp_raw", "cos_stereo")] + \
+               [("Tcw", C.c_float * 16), ("Twc", C.c_float * 16)] + \
+               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mbf")] + \
+               [("level_sigma2", C.c_float * MAX_LEVELS), ("scale_factors", C.c_float * MAX_LEVELS), ("F12", C.c_float * 9),
+                ("ex", C.c_float), ("ey", C.c_float)]
+
+
+class NewPointsProblem(C.Structure):
+    _fields_ = [("kf1", NewPointsFrame), ("neighbours", C.c_void_p), ("nn", C.c_int32), ("only_stereo", C.c_int32),
+                ("check_orientation", C.c_int32), ("ratio_factor", C.c_float)] + \
+               [(k, C.c_void_p) for k in ("stop", "match12", "status", "x3d", "n_matches", "n_created", "n_done")]
+
+
+NEW_POINTS_MAX_NEIGHBOURS = 32
+(NP_NONE, NP_TRIANGULATED, NP_UNPROJECT1, NP_UNPROJECT2, NP_LOW_PARALLAX, NP_W_ZERO, NP_Z1, NP_Z2, NP_REPROJ1, NP_REPROJ2,
+ NP_ZERO_DIST, NP_SCALE, NP_NON_FINITE, NP_STEREO_DEPTH, NP_BAD_OCTAVE) = (0, 1, 2, 3, -1, -2, -3, -4, -5, -6, -7, -8, -9, -10, -11)
+
+
 _LIB = None
 
 # every symbol include/orbgpu.h declares (checked by tests/test_abi.py against the header text)
@@ -272,6 +293,7 @@ ABI_SYMBOLS = [
     "orbgpu_pnp_solve_all", "orbgpu_pnp_solve_table",
     "orbgpu_initializer_cos_limits", "orbgpu_initializer_device", "orbgpu_initializer_batch_device", "orbgpu_initializer",
     "orbgpu_initializer_all",
+    "orbgpu_create_new_map_points_device", "orbgpu_create_new_map_points",
     "orbgpu_keyframe_db_create", "orbgpu_keyframe_db_destroy", "orbgpu_keyframe_db_clear", "orbgpu_keyframe_db_size",
     "orbgpu_keyframe_db_add", "orbgpu_keyframe_db_erase", "orbgpu_keyframe_db_set_covisibles", "orbgpu_keyframe_db_score",
     "orbgpu_keyframe_db_detect_loop", "orbgpu_keyframe_db_detect_reloc", "orbgpu_keyframe_db_last_query",
@@ -1743,6 +1765,87 @@ def search_for_triangulation(kf1, has_mp1, node1, kf2, has_mp2, node2, F12, ex, 
     check(L.orbgpu_search_for_triangulation(C.byref(f1), _p(h1), _p(n1), C.byref(f2), _p(h2), _p(n2), _p(F), ex, ey,
                                             _p(sg), int(only_stereo), int(check_ori), _p(out), C.byref(n), device_id))
     return n.value, out[:kf1.n]
+
+
+_NP_ARRAYS = (("kp_x", np.float32), ("kp_y", np.float32), ("kp_octave", np.int32), ("kp_angle", np.float32),
+              ("u_right", np.float32), ("desc", np.uint8), ("has_mp", np.uint8), ("node", np.int32), ("depth", np.float32),
+              ("kp_raw", np.float32), ("cos_stereo", np.float32))
+
+
+def new_points_frame(f, keep, device=False):
+    """A NewPointsFrame from a dict: the arrays of include/orbgpu.h's orbgpu_new_points_frame (numpy arrays, or with
+    device=True integer device addresses plus n), Tcw, Twc (4x4), K = (fx, fy, cx, cy), mbf, level_sigma2, scale_factors,
+    and for a neighbour F12 (3x3), ex, ey.  invfx / invfy default to 1 / fx, 1 / fy in float as Frame.cc computes them.
+    kp_angle and kp_raw may be missing or None."""
+    q = NewPointsFrame()
+    if device:
+        q.n = int(f["n"])
+        for k, _ in _NP_ARRAYS:
+            setattr(q, k, f.get(k) or None)
+    else:
+        a = {k: (None if f.get(k) is None else np.ascontiguousarray(f[k], t)) for k, t in _NP_ARRAYS}
+        keep.append(a)
+        q.n = int(f.get("n", len(a["kp_x"])))
+        for k, _ in _NP_ARRAYS:
+            setattr(q, k, a[k].ctypes.data if a[k] is not None and a[k].size else None)
+    _set_floats(q.Tcw, f["Tcw"])
+    _set_floats(q.Twc, f["Twc"])
+    _set_intrinsics(q, f["K"])
+    q.invfx = float(f.get("invfx", np.float32(1.0) / np.float32(f["K"][0])))
+    q.invfy = float(f.get("invfy", np.float32(1.0) / np.float32(f["K"][1])))
+    q.mbf = float(f.get("mbf", 0.0))
+    sg, sf = np.asarray(f["level_sigma2"], np.float32), np.asarray(f["scale_factors"], np.float32)
+    q.nlevels = int(f.get("nlevels", len(sg)))
+    for l in range(min(len(sg), MAX_LEVELS)):
+        q.level_sigma2[l], q.scale_factors[l] = float(sg[l]), float(sf[l])
+    if "F12" in f:
+        _set_floats(q.F12, f["F12"])
+        q.ex, q.ey = float(f["ex"]), float(f["ey"])
+    return q
+
+
+def new_points_problem(kf1, neighbours, ratio_factor, only_stereo, check_ori, keep, device=False, **ptrs):
+    """A NewPointsProblem: kf1 and neighbours as new_points_frame takes them; ptrs: stop, match12, status, x3d, n_matches,
+    n_created, n_done as integer addresses (None = NULL)."""
+    q = NewPointsProblem()
+    q.kf1 = new_points_frame(kf1, keep, device)
+    arr = (NewPointsFrame * max(len(neighbours), 1))(*[new_points_frame(f, keep, device) for f in neighbours])
+    keep.append(arr)
+    q.neighbours = C.addressof(arr) if len(neighbours) else None
+    q.nn = int(ptrs.pop("nn", len(neighbours)))
+    q.only_stereo, q.check_orientation, q.ratio_factor = int(only_stereo), int(check_ori), float(ratio_factor)
+    _set_pointers(q, ptrs, ("stop", "match12", "status", "x3d", "n_matches", "n_created", "n_done"))
+    return q
+
+
+def create_new_map_points_device(kf1, neighbours, ratio_factor, only_stereo=False, check_ori=True, stream=0, device_id=0, **ptrs):
+    """LocalMapping::CreateNewMapPoints over device arrays (orbgpu_create_new_map_points_device); enqueued, not
+    synchronised.  Frames as new_points_frame(device=True) takes them; ptrs: the device addresses of the outputs and of
+    the optional stop flag."""
+    keep = []
+    _one_device("create_new_map_points", new_points_problem(kf1, neighbours, ratio_factor, only_stereo, check_ori, keep, True, **ptrs),
+                stream, device_id)
+
+
+def create_new_map_points(kf1, neighbours, ratio_factor, only_stereo=False, check_ori=True, stop=None, device_id=0):
+    """LocalMapping::CreateNewMapPoints (LocalMapping.cc:207-452) over host arrays (orbgpu_create_new_map_points): the whole
+    neighbour loop in one call.  stop: None or an int sampled at the call.  Returns a dict: match12, status [nn][n1], x3d
+    [nn][n1][3], n_matches, n_created [nn], n_done."""
+    keep = []
+    nn, n1 = len(neighbours), int(kf1.get("n", len(kf1["kp_x"])))
+    out = {"match12": np.full((nn, n1), -1, np.int32), "status": np.zeros((nn, n1), np.int32),
+           "x3d": np.zeros((nn, n1, 3), np.float32), "n_matches": np.zeros(nn, np.int32), "n_created": np.zeros(nn, np.int32)}
+    pad = {k: (v if v.size else np.zeros(4, v.dtype)) for k, v in out.items()}
+    done = C.c_int32(0)
+    sv = None if stop is None else C.c_int32(int(stop))
+    q = new_points_problem(kf1, neighbours, ratio_factor, only_stereo, check_ori, keep, False,
+                           stop=None if sv is None else C.addressof(sv), n_done=C.addressof(done),
+                           **{k: v.ctypes.data for k, v in pad.items()})
+    L = lib()
+    L.orbgpu_create_new_map_points.argtypes = [C.c_void_p, C.c_int32]
+    check(L.orbgpu_create_new_map_points(C.byref(q), device_id))
+    out["n_done"] = done.value
+    return out
 
 
 def search_for_initialization(f1, f2, prev_matched, window_size, nnratio=0.9, check_ori=True, device_id=0):

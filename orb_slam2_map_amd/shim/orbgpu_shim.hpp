@@ -1827,6 +1827,168 @@ template <typename FrameT> class InitializerT {
 };
 
 // --------------------------------------------------------------------------------------------
+// LocalMapping::CreateNewMapPoints (LocalMapping.cc:207-452) on the device (orbgpu_create_new_map_points): the baseline
+// test, ComputeF12 and the epipole per neighbour on the host, ONE library call for the whole neighbour loop, then the map
+// edits of :434-449 in the reference's order.  KeyFrameT needs N, mvKeys, mvKeysUn, mvuRight, mvDepth, mFeatVec,
+// GetMapPoint(i), AddMapPoint(pMP, i), fx, fy, cx, cy, invfx, invfy, mbf, mb, mvLevelSigma2, mvScaleFactors, mfScaleFactor;
+// MapPointT needs mnId, AddObservation(pKF, i), ComputeDistinctiveDescriptors(), UpdateNormalAndDepth().  access:
+//   desc_row(kf, i) -> 32 bytes;  pose(kf, float[16]) / pose_inverse(kf, float[16]) = GetPose() / GetPoseInverse();
+//   median_depth(kf) = ComputeSceneMedianDepth(2);  F12(kf1, kf2, float[9]) = LocalMapping::ComputeF12, row-major;
+//   new_map_point(const float x[3], kf1) = new MapPoint(x3D, mpCurrentKeyFrame, mpMap);
+//   add_to_map(pMP) = mpMap->AddMapPoint(pMP) and mlpRecentAddedMapPoints.push_back(pMP);
+//   with a table: world_pos / normal (3 floats), min_dist / max_dist, mp_desc (32 bytes) of a map point.
+// --------------------------------------------------------------------------------------------
+template <typename KeyFrameT> struct NewPointsFrameSoA {
+    std::vector<float> x, y, angle, uright, depth, raw, cs;
+    std::vector<int32_t> octave, node;
+    std::vector<uint8_t> desc, has;
+    orbgpu_new_points_frame f{};
+    template <typename Access> NewPointsFrameSoA(KeyFrameT *kf, Access &access)
+    {
+        const int n = kf->N;
+        x.resize(n), y.resize(n), angle.resize(n), uright.resize(n), depth.resize(n), raw.resize(2 * (size_t)n), cs.resize(n);
+        octave.resize(n), desc.resize(32 * (size_t)n), has.resize(n);
+        for (int i = 0; i < n; i++) {
+            x[i] = kf->mvKeysUn[i].pt.x, y[i] = kf->mvKeysUn[i].pt.y;
+            angle[i] = kf->mvKeysUn[i].angle, octave[i] = kf->mvKeysUn[i].octave;
+            raw[2 * i] = kf->mvKeys[i].pt.x, raw[2 * i + 1] = kf->mvKeys[i].pt.y;  // KeyFrame::UnprojectStereo reads mvKeys
+            uright[i] = kf->mvuRight[i], depth[i] = kf->mvDepth[i];
+            // :312 / :314 as written: LocalMapping.cc sees <cmath> and a using-directive for std through its headers, so
+            // cos and atan2 of float arguments are the float overloads and 2 * and / 2 stay in float
+            cs[i] = std::cos(2 * std::atan2(kf->mb / 2, kf->mvDepth[i]));
+            has[i] = kf->GetMapPoint(i) != nullptr;
+            std::memcpy(&desc[32 * (size_t)i], access.desc_row(kf, i), 32);
+        }
+        node = NodeIdsOf(kf->mFeatVec, n);
+        f.n = n, f.nlevels = (int32_t)kf->mvScaleFactors.size();
+        f.kp_x = x.data(), f.kp_y = y.data(), f.kp_octave = octave.data(), f.kp_angle = angle.data(), f.u_right = uright.data();
+        f.desc = desc.data(), f.has_mp = has.data(), f.node = node.data(), f.depth = depth.data(), f.kp_raw = raw.data();
+        f.cos_stereo = cs.data();
+        access.pose(kf, f.Tcw), access.pose_inverse(kf, f.Twc);
+        f.fx = kf->fx, f.fy = kf->fy, f.cx = kf->cx, f.cy = kf->cy, f.invfx = kf->invfx, f.invfy = kf->invfy, f.mbf = kf->mbf;
+        for (int l = 0; l < f.nlevels && l < ORBGPU_MAX_LEVELS; l++)
+            f.level_sigma2[l] = kf->mvLevelSigma2[l], f.scale_factors[l] = kf->mvScaleFactors[l];
+    }
+};
+
+template <typename KeyFrameT> struct NewPointsCall {
+    KeyFrameT *cur;
+    std::vector<KeyFrameT *> kept;  // the neighbours that pass :239 and :244-261, in the reference's order
+    std::vector<std::unique_ptr<NewPointsFrameSoA<KeyFrameT>>> frames;  // [0] the current key frame, then kept
+    std::vector<orbgpu_new_points_frame> nb;
+    std::vector<int32_t> match12, status, n_matches, n_created;
+    std::vector<float> x3d;
+    int32_t n_done = 0;
+    orbgpu_new_points_problem p{};
+
+    // stop = CheckNewKeyFrames() sampled at the call: the reference returns before neighbour i > 0 then (:239)
+    template <typename Access>
+    NewPointsCall(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vpNeighKFs, bool bMonocular, bool stop, Access &access)
+        : cur(pCurrentKF)
+    {
+        frames.emplace_back(new NewPointsFrameSoA<KeyFrameT>(cur, access));
+        const orbgpu_new_points_frame &f1 = frames[0]->f;
+        const float Ow1[3] = {f1.Twc[3], f1.Twc[7], f1.Twc[11]};
+        for (size_t i = 0; i < vpNeighKFs.size(); i++) {
+            if (i > 0 && stop)
+                break;
+            KeyFrameT *pKF2 = vpNeighKFs[i];
+            // :245-261 first, from the pose alone (a neighbour that fails is not flattened); cv::norm of the float difference
+            // as an FP64 sum
+            float Twc2[16];
+            access.pose_inverse(pKF2, Twc2);
+            const float b[3] = {Twc2[3] - Ow1[0], Twc2[7] - Ow1[1], Twc2[11] - Ow1[2]};
+            const float baseline = (float)std::sqrt(((double)b[0] * b[0] + (double)b[1] * b[1]) + (double)b[2] * b[2]);
+            if (!bMonocular) {
+                if (baseline < pKF2->mb)
+                    continue;
+            } else {
+                const float medianDepthKF2 = access.median_depth(pKF2);
+                const float ratioBaselineDepth = baseline / medianDepthKF2;
+                if (ratioBaselineDepth < 0.01)
+                    continue;
+            }
+            std::unique_ptr<NewPointsFrameSoA<KeyFrameT>> s(new NewPointsFrameSoA<KeyFrameT>(pKF2, access));
+            orbgpu_new_points_frame &f2 = s->f;
+            access.F12(cur, pKF2, f2.F12);
+            // the epipole (ORBmatcher.cc:664-670): C2 = R2w * Cw + t2w as a float 3x3 * 3x1 product, summed left to right
+            float C2[3];
+            for (int r = 0; r < 3; r++) {
+                volatile float a = f2.Tcw[4 * r] * Ow1[0], bb = f2.Tcw[4 * r + 1] * Ow1[1], c = f2.Tcw[4 * r + 2] * Ow1[2];
+                volatile float ab = a + bb;
+                volatile float abc = ab + c;
+                C2[r] = abc + f2.Tcw[4 * r + 3];
+            }
+            const float invz = 1.0f / C2[2];
+            f2.ex = pKF2->fx * C2[0] * invz + pKF2->cx;
+            f2.ey = pKF2->fy * C2[1] * invz + pKF2->cy;
+            kept.push_back(pKF2);
+            frames.push_back(std::move(s));
+        }
+        const size_t nn = kept.size(), n1 = (size_t)cur->N;
+        if (nn > (size_t)ORBGPU_NEW_POINTS_MAX_NEIGHBOURS)
+            throw std::runtime_error("CreateNewMapPoints: more neighbours than ORBGPU_NEW_POINTS_MAX_NEIGHBOURS");
+        for (size_t k = 0; k < nn; k++)
+            nb.push_back(frames[k + 1]->f);
+        match12.assign(std::max<size_t>(nn * n1, 1), -1), status.assign(std::max<size_t>(nn * n1, 1), 0);
+        x3d.assign(std::max<size_t>(3 * nn * n1, 1), 0.f), n_matches.assign(std::max<size_t>(nn, 1), 0);
+        n_created.assign(std::max<size_t>(nn, 1), 0);
+        p.kf1 = f1, p.neighbours = nb.data(), p.nn = (int32_t)nn;
+        p.only_stereo = 0, p.check_orientation = 0;  // ORBmatcher matcher(0.6, false), bOnlyStereo = false (:215, :268)
+        p.ratio_factor = 1.5f * cur->mfScaleFactor;
+        p.stop = nullptr;
+        p.match12 = match12.data(), p.status = status.data(), p.x3d = x3d.data();
+        p.n_matches = n_matches.data(), p.n_created = n_created.data(), p.n_done = &n_done;
+    }
+
+    void Run(int device_id) { check(orbgpu_create_new_map_points(&p, device_id), "CreateNewMapPoints"); }
+
+    // :434-449 per created point, neighbour ascending, key point ascending; returns nnew
+    template <typename MapPointT, typename Access>
+    int WriteBack(Access &access, MapPointTableT<MapPointT> *table, std::vector<MapPointT *> *created_out = nullptr)
+    {
+        std::vector<MapPointT *> created;
+        const size_t n1 = (size_t)cur->N;
+        for (size_t k = 0; k < kept.size(); k++)
+            for (size_t i = 0; i < n1; i++) {
+                if (status[k * n1 + i] <= 0)
+                    continue;
+                const int idx1 = (int)i, idx2 = match12[k * n1 + i];
+                MapPointT *pMP = access.new_map_point(&x3d[3 * (k * n1 + i)], cur);
+                pMP->AddObservation(cur, idx1);
+                pMP->AddObservation(kept[k], idx2);
+                cur->AddMapPoint(pMP, idx1);
+                kept[k]->AddMapPoint(pMP, idx2);
+                pMP->ComputeDistinctiveDescriptors();
+                pMP->UpdateNormalAndDepth();
+                access.add_to_map(pMP);
+                created.push_back(pMP);
+            }
+        if (table && !created.empty())
+            table->Upsert(
+                created, [&access](MapPointT *m) { return access.world_pos(m); }, [&access](MapPointT *m) { return access.normal(m); },
+                [&access](MapPointT *m) { return access.min_dist(m); }, [&access](MapPointT *m) { return access.max_dist(m); },
+                [&access](MapPointT *m) { return access.mp_desc(m); });
+        if (created_out)
+            *created_out = created;
+        return (int)created.size();
+    }
+};
+
+// void LocalMapping::CreateNewMapPoints() with its state as arguments: the neighbours are
+// mpCurrentKeyFrame->GetBestCovisibilityKeyFrames(mbMonocular ? 20 : 10), stop is CheckNewKeyFrames().  Returns nnew.
+template <typename MapPointT, typename KeyFrameT, typename Access>
+int CreateNewMapPointsT(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vpNeighKFs, bool bMonocular, bool stop,
+                        Access access, MapPointTableT<MapPointT> *table = nullptr, int device_id = 0)
+{
+    NewPointsCall<KeyFrameT> call(pCurrentKF, vpNeighKFs, bMonocular, stop, access);
+    if (call.kept.empty())
+        return 0;
+    call.Run(device_id);
+    return call.template WriteBack<MapPointT>(access, table);
+}
+
+// --------------------------------------------------------------------------------------------
 // KeyFrameDatabase (reference include/KeyFrameDatabase.h:45-75, src/KeyFrameDatabase.cc) on the device
 // (orbgpu_keyframe_db_*): add / erase / clear / DetectLoopCandidates / DetectRelocalizationCandidates with the
 // reference's signatures, candidates in the reference's order.  KeyFrameT needs mnId, mBowVec (DBoW2::BowVector: an
