@@ -7,7 +7,7 @@
 //
 // Five kernels per call: k_init_prepare (one wave per problem), k_init_hypotheses (one wave per hypothesis and model),
 // k_init_select (one wave per problem), k_init_checkrt (one wave per motion), k_init_finish (one wave per problem).
-// The Jacobi of the wave-wide steps is pnp.hip's shape (matrices in LDS, the rows of a rotation spread over the lanes);
+// The Jacobi of the wave-wide steps is jacobi.h's jacobi_wave (matrices in LDS, the rows of a rotation spread over the lanes);
 // the 4x4 of a triangulation runs in the registers of the lane that owns the pair.
 #include <algorithm>
 #include <cmath>
@@ -16,7 +16,7 @@
 
 #include "carve.h"
 #include "common.h"
-#include "jacobi4.h"
+#include "jacobi.h"
 #include "ransac_host.h"
 #include "staging.h"
 
@@ -24,7 +24,8 @@ namespace orbgpu {
 namespace {
 
 constexpr int INIT_MAX_N = 16384, INIT_MAX_HYP = 4096;
-constexpr int ILD = 12;  // row stride of the LDS matrices
+constexpr int INIT_JACOBI_SWEEPS = 30;
+constexpr int ILD = 12;  // row stride of the LDS matrices (jacobi.h)
 
 struct InitCtl {
     int32_t n, best_h, best_f, use_h, n_motions, n_inliers;
@@ -116,95 +117,12 @@ __device__ inline unsigned cos_key(float c)
 
 __device__ inline float key_cos(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
-// ---- the wave-wide Jacobi (pnp.hip's shape) ----------------------------------------------------------------------------
+// ---- the LDS of the wave-wide Jacobi (jacobi.h) --------------------------------------------------------------------------
 struct InitLds {
     double A[ILD * ILD], V[ILD * ILD], Ut[ILD * ILD], w[ILD];
     float rows[16 * 9];
     float terms[128];
 };
-
-// Cyclic Jacobi on the symmetric m x m in S.A; eigenvalues stay on its diagonal, eigenvectors in the columns of S.V.
-// Every lane computes the rotation's c, s, t from the same three entries; lane r < m updates row r of A (and the mirrored
-// column entries), lane 16 + r row r of V.
-__device__ void jacobi_wave(InitLds &S, int m, int lane)
-{
-    for (int e = lane; e < m * m; e += 64)
-        S.V[(e / m) * ILD + e % m] = (e / m == e % m) ? 1.0 : 0.0;
-    __syncthreads();
-    for (int sweep = 0; sweep < INIT_JACOBI_SWEEPS; sweep++) {
-        double off = 0.0, diag = 0.0;
-        for (int p = 0; p < m; p++)
-            for (int q = p + 1; q < m; q++)
-                off = off + S.A[p * ILD + q] * S.A[p * ILD + q];
-        for (int i = 0; i < m; i++)
-            diag = diag + S.A[i * ILD + i] * S.A[i * ILD + i];
-        if (off <= INIT_JACOBI_STOP * (diag + 2.0 * off))
-            break;
-        for (int p = 0; p < m; p++)
-            for (int q = p + 1; q < m; q++) {
-                const double apq = S.A[p * ILD + q];
-                if (apq == 0.0)
-                    continue;
-                const double app = S.A[p * ILD + p], aqq = S.A[q * ILD + q];
-                const double theta = (aqq - app) / (2.0 * apq);
-                const double den = fabs(theta) + sqrt(theta * theta + 1.0);
-                const double t = theta >= 0.0 ? 1.0 / den : -1.0 / den;
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                __syncthreads();
-                if (lane < m) {
-                    const int r = lane;
-                    if (r == p) {
-                        S.A[p * ILD + p] = app - t * apq;
-                        S.A[p * ILD + q] = 0.0;
-                    } else if (r == q) {
-                        S.A[q * ILD + q] = aqq + t * apq;
-                        S.A[q * ILD + p] = 0.0;
-                    } else {
-                        const double arp = S.A[r * ILD + p], arq = S.A[r * ILD + q];
-                        const double np = c * arp - s * arq, nq = s * arp + c * arq;
-                        S.A[r * ILD + p] = S.A[p * ILD + r] = np;
-                        S.A[r * ILD + q] = S.A[q * ILD + r] = nq;
-                    }
-                } else if (lane >= 16 && lane < 16 + m) {
-                    const int r = lane - 16;
-                    const double vrp = S.V[r * ILD + p], vrq = S.V[r * ILD + q];
-                    S.V[r * ILD + p] = c * vrp - s * vrq;
-                    S.V[r * ILD + q] = s * vrp + c * vrq;
-                }
-                __syncthreads();
-            }
-    }
-    __syncthreads();
-}
-
-// Eigenvalues descending (stable) into S.w, eigenvectors as rows of S.Ut, each flipped so that its component of largest
-// magnitude (lowest index on ties) is positive.
-__device__ void sorted_eig_wave(InitLds &S, int m, int lane)
-{
-    jacobi_wave(S, m, lane);
-    if (lane < m) {
-        const double wi = S.A[lane * ILD + lane];
-        int rank = 0;
-        for (int j = 0; j < m; j++) {
-            const double wj = S.A[j * ILD + j];
-            rank += j < lane ? !(wj < wi) : (j > lane ? wj > wi : 0);
-        }
-        rank = min(rank, m - 1);
-        double big = fabs(S.V[lane]), lead = S.V[lane];
-        for (int r = 1; r < m; r++) {
-            const double v = S.V[r * ILD + lane];
-            if (fabs(v) > big)
-                big = fabs(v), lead = v;
-        }
-        const bool flip = lead < 0.0;
-        for (int r = 0; r < m; r++) {
-            const double v = S.V[r * ILD + lane];
-            S.Ut[rank * ILD + r] = flip ? -v : v;
-        }
-        S.w[rank] = wi;
-    }
-    __syncthreads();
-}
 
 // I4: A = U diag(d) V' of a 3x3 of float entries.  U[3 i + k] = component i of u_k, Vt[3 k + j] = component j of v_k.
 // proper: u_2 takes the sign of A v_2; otherwise the sign rule.  Every lane returns the same values.
@@ -224,7 +142,7 @@ __device__ void svd3_wave(InitLds &S, const float *Af, int lane, bool proper, do
         S.A[a * ILD + b] = s;
     }
     __syncthreads();
-    sorted_eig_wave(S, 3, lane);
+    sorted_eig_wave<ILD, INIT_JACOBI_SWEEPS>(S, 3, lane);
     double av[3][3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -370,7 +288,7 @@ __global__ __launch_bounds__(64) void k_init_hypotheses(const InitProblemDev *__
         S.A[a * ILD + b] = s;
     }
     __syncthreads();
-    sorted_eig_wave(S, 9, lane);
+    sorted_eig_wave<ILD, INIT_JACOBI_SWEEPS>(S, 9, lane);
     float nv[9];
 #pragma unroll
     for (int k = 0; k < 9; k++)
@@ -627,9 +545,7 @@ __global__ __launch_bounds__(64) void k_init_select(const InitProblemDev *__rest
 }
 
 // ---- I9 ---------------------------------------------------------------------------------------------------------------------
-// jacobi4_lane: jacobi4.h, shared with new_points.hip
-// (jacobi4.h's null_vector4 restates the A'A / selection / sign steps k_init_checkrt has inline below: an edit here is an edit
-// there)
+// the triangulation of a pair is null_vector4 (jacobi.h), shared with new_points.hip
 // grid (8, problems), one wave per motion
 __global__ __launch_bounds__(64) void k_init_checkrt(const InitProblemDev *__restrict__ problems)
 {
@@ -682,37 +598,8 @@ __global__ __launch_bounds__(64) void k_init_checkrt(const InitProblemDev *__res
                 Af[2][c] = q.z * P2[2][c] - P2[0][c];
                 Af[3][c] = q.w * P2[2][c] - P2[1][c];
             }
-            double A[4][4], V[4][4];
-#pragma unroll
-            for (int a = 0; a < 4; a++)
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    double s = 0.0;
-#pragma unroll
-                    for (int r = 0; r < 4; r++)
-                        s = s + (double)Af[r][a] * (double)Af[r][b];
-                    A[a][b] = s;
-                }
-            jacobi4_lane(A, V);
-            // the last of the stable descending order, with the sign rule
-            double v[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                int rank = 0;
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    rank += j < i ? !(A[j][j] < A[i][i]) : (j > i ? A[j][j] > A[i][i] : 0);
-                if (rank >= 3)
-                    v[0] = V[0][i], v[1] = V[1][i], v[2] = V[2][i], v[3] = V[3][i];
-            }
-            double big = fabs(v[0]), lead = v[0];
-#pragma unroll
-            for (int r = 1; r < 4; r++)
-                if (fabs(v[r]) > big)
-                    big = fabs(v[r]), lead = v[r];
-            const bool flip = lead < 0.0;
-            const float x4[4] = {(float)(flip ? -v[0] : v[0]), (float)(flip ? -v[1] : v[1]), (float)(flip ? -v[2] : v[2]),
-                                 (float)(flip ? -v[3] : v[3])};
+            float x4[4];
+            null_vector4(Af, x4);
             x = fdiv(x4[0], x4[3]), y = fdiv(x4[1], x4[3]), z = fdiv(x4[2], x4[3]);
             const bool finite = (x - x == 0.f) && (y - y == 0.f) && (z - z == 0.f);
             if (finite) {

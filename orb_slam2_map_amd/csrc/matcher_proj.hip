@@ -1085,54 +1085,12 @@ __global__ __launch_bounds__(256) void k_tri_match(int n1, const float *__restri
     tri_match_wave<false>(n1, x1, y1, ur1, has_mp1, node1, desc1, n2, x2, y2, oct2, ur2, has_mp2, node2, desc2, P, match12);
 }
 
-// rotation consistency of the accepted pairs (:772-795) and the count; one workgroup
-// (tri_match.h's tri_finish_block is a copy of this text for new_points.hip: an edit here is an edit there)
+// rotation consistency of the accepted pairs (:772-795) and the count; one workgroup (tri_match.h)
 __global__ __launch_bounds__(1024) void k_tri_finish(int n1, const float *__restrict__ angle1,
                                                      const float *__restrict__ angle2, int check_orientation,
                                                      int *__restrict__ match12, int *__restrict__ nmatches)
 {
-    __shared__ int histo[ORBGPU_HISTO_LENGTH];
-    __shared__ int s_keep[3], s_count;
-    const int tid = threadIdx.x;
-    if (tid < ORBGPU_HISTO_LENGTH)
-        histo[tid] = 0;
-    if (tid == 0)
-        s_count = 0;
-    __syncthreads();
-    int cnt = 0;
-    for (int i = tid; i < n1; i += 1024) {
-        const int j = match12[i];
-        if (j < 0)
-            continue;
-        cnt++;
-        if (check_orientation)
-            atomicAdd(&histo[rot_bin(angle1[i], angle2[j])], 1);
-    }
-    __syncthreads();
-    if (check_orientation) {
-        if (tid == 0) {
-            int i1, i2, i3;
-            three_maxima(histo, ORBGPU_HISTO_LENGTH, i1, i2, i3);
-            s_keep[0] = i1, s_keep[1] = i2, s_keep[2] = i3;
-        }
-        __syncthreads();
-        for (int i = tid; i < n1; i += 1024) {
-            const int j = match12[i];
-            if (j < 0)
-                continue;
-            const int b = rot_bin(angle1[i], angle2[j]);
-            if (b != s_keep[0] && b != s_keep[1] && b != s_keep[2]) {
-                match12[i] = -1;
-                cnt--;
-            }
-        }
-    }
-    cnt = wave_reduce_add(cnt);
-    if ((tid & 63) == 0)
-        atomicAdd(&s_count, cnt);
-    __syncthreads();
-    if (tid == 0)
-        *nmatches = s_count;
+    tri_finish_block(n1, angle1, angle2, check_orientation, match12, nmatches);
 }
 
 // ---- ORBmatcher::SearchForInitialization (ORBmatcher.cc:405-520): distances of every window candidate ---------

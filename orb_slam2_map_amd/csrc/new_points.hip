@@ -8,7 +8,7 @@
 
 #include "carve.h"
 #include "common.h"
-#include "jacobi4.h"
+#include "jacobi.h"
 #include "staging.h"
 #include "tri_match.h"
 

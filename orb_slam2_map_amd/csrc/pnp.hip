@@ -15,6 +15,7 @@
 
 #include "carve.h"
 #include "common.h"
+#include "jacobi.h"
 #include "ransac_host.h"
 #include "staging.h"
 
@@ -22,8 +23,8 @@ namespace orbgpu {
 
 constexpr int PNP_MAX_N1 = 16384, PNP_MAX_HYP = 4096, PNP_MIN_SET_LO = 4, PNP_MIN_SET_HI = 64;
 constexpr int PNP_JACOBI_SWEEPS = 30;
-constexpr double PNP_JACOBI_STOP = 1e-32, PNP_CC_REL = 1e-6, PNP_LS_REL = 1e-12;
-constexpr int LD = 12;  // row stride of the LDS matrices
+constexpr double PNP_CC_REL = 1e-6, PNP_LS_REL = 1e-12;
+constexpr int LD = 12;  // row stride of the LDS matrices (jacobi.h)
 
 struct PnpCtl {
     int32_t n, min_inliers, max_its, n_use;
@@ -106,89 +107,6 @@ struct EpnpLds {
     double L[6 * 10], rho[6], g[8], n2[LD];
 };
 
-// Cyclic Jacobi on the symmetric m x m in S.A; eigenvalues stay on its diagonal, eigenvectors in the columns of S.V.
-// Every lane computes the rotation's c, s, t from the same three entries; lane r < m updates row r of A (and the mirrored
-// column entries), lane 16 + r row r of V: the entries of one rotation do not depend on each other.
-__device__ void jacobi_wave(EpnpLds &S, int m, int lane)
-{
-    for (int e = lane; e < m * m; e += 64)
-        S.V[(e / m) * LD + e % m] = (e / m == e % m) ? 1.0 : 0.0;
-    __syncthreads();
-    for (int sweep = 0; sweep < PNP_JACOBI_SWEEPS; sweep++) {
-        double off = 0.0, diag = 0.0;
-        for (int p = 0; p < m; p++)
-            for (int q = p + 1; q < m; q++)
-                off = off + S.A[p * LD + q] * S.A[p * LD + q];
-        for (int i = 0; i < m; i++)
-            diag = diag + S.A[i * LD + i] * S.A[i * LD + i];
-        if (off <= PNP_JACOBI_STOP * (diag + 2.0 * off))
-            break;
-        for (int p = 0; p < m; p++)
-            for (int q = p + 1; q < m; q++) {
-                const double apq = S.A[p * LD + q];
-                if (apq == 0.0)
-                    continue;
-                const double app = S.A[p * LD + p], aqq = S.A[q * LD + q];
-                const double theta = (aqq - app) / (2.0 * apq);
-                const double den = fabs(theta) + sqrt(theta * theta + 1.0);
-                const double t = theta >= 0.0 ? 1.0 / den : -1.0 / den;
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                __syncthreads();
-                if (lane < m) {
-                    const int r = lane;
-                    if (r == p) {
-                        S.A[p * LD + p] = app - t * apq;
-                        S.A[p * LD + q] = 0.0;
-                    } else if (r == q) {
-                        S.A[q * LD + q] = aqq + t * apq;
-                        S.A[q * LD + p] = 0.0;
-                    } else {
-                        const double arp = S.A[r * LD + p], arq = S.A[r * LD + q];
-                        const double np = c * arp - s * arq, nq = s * arp + c * arq;
-                        S.A[r * LD + p] = S.A[p * LD + r] = np;
-                        S.A[r * LD + q] = S.A[q * LD + r] = nq;
-                    }
-                } else if (lane >= 16 && lane < 16 + m) {
-                    const int r = lane - 16;
-                    const double vrp = S.V[r * LD + p], vrq = S.V[r * LD + q];
-                    S.V[r * LD + p] = c * vrp - s * vrq;
-                    S.V[r * LD + q] = s * vrp + c * vrq;
-                }
-                __syncthreads();
-            }
-    }
-    __syncthreads();
-}
-
-// Eigenvalues descending (stable) into S.w, eigenvectors as rows of S.Ut, each flipped so that its component of largest
-// magnitude (lowest index on ties) is positive.
-__device__ void sorted_eig_wave(EpnpLds &S, int m, int lane)
-{
-    jacobi_wave(S, m, lane);
-    if (lane < m) {
-        const double wi = S.A[lane * LD + lane];
-        int rank = 0;
-        for (int j = 0; j < m; j++) {
-            const double wj = S.A[j * LD + j];
-            rank += j < lane ? !(wj < wi) : (j > lane ? wj > wi : 0);
-        }
-        rank = min(rank, m - 1);
-        double big = fabs(S.V[lane]), lead = S.V[lane];
-        for (int r = 1; r < m; r++) {
-            const double v = S.V[r * LD + lane];
-            if (fabs(v) > big)
-                big = fabs(v), lead = v;
-        }
-        const bool flip = lead < 0.0;
-        for (int r = 0; r < m; r++) {
-            const double v = S.V[r * LD + lane];
-            S.Ut[rank * LD + r] = flip ? -v : v;
-        }
-        S.w[rank] = wi;
-    }
-    __syncthreads();
-}
-
 struct PnpPoint {
     double x[3], u, v;
 };
@@ -235,7 +153,7 @@ template <int KK> __device__ void lstsq_wave(EpnpLds &S, const int (&cols)[KK], 
         S.g[a] = s;
     }
     __syncthreads();
-    jacobi_wave(S, KK, lane);
+    jacobi_wave<LD, PNP_JACOBI_SWEEPS>(S, KK, lane);
     double wmax = S.A[0];
 #pragma unroll
     for (int i = 1; i < KK; i++) {
@@ -418,7 +336,7 @@ __device__ double pose_from_betas(const PnpProblemDev &P, const int32_t *list, i
         S.A[a * LD + b] = s;
     }
     __syncthreads();
-    jacobi_wave(S, 3, lane);
+    jacobi_wave<LD, PNP_JACOBI_SWEEPS>(S, 3, lane);
 #pragma unroll
     for (int e = 0; e < 9; e++)
         R[e] = 0.0;
@@ -495,7 +413,7 @@ __device__ void epnp_wave(const PnpProblemDev &P, const int32_t *list, int n, Ep
         }
         __syncthreads();
     }
-    sorted_eig_wave(S, 3, lane);
+    sorted_eig_wave<LD, PNP_JACOBI_SWEEPS>(S, 3, lane);
     double cws[4][3];
     {
         double kk[3];
@@ -552,7 +470,7 @@ __device__ void epnp_wave(const PnpProblemDev &P, const int32_t *list, int n, Ep
             }
         __syncthreads();
     }
-    sorted_eig_wave(S, 12, lane);
+    sorted_eig_wave<LD, PNP_JACOBI_SWEEPS>(S, 12, lane);
     if (lane < 48)
         S.vs[lane] = S.Ut[(11 - lane / 12) * LD + lane % 12];
     __syncthreads();

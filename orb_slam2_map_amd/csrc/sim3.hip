@@ -9,6 +9,7 @@
 
 #include "carve.h"
 #include "common.h"
+#include "jacobi.h"
 #include "ransac_host.h"
 #include "staging.h"
 
@@ -123,35 +124,7 @@ __global__ __launch_bounds__(S3_THREADS) void k_sim3_prepare(const Sim3ProblemDe
     }
 }
 
-// ---- H6 ---------------------------------------------------------------------------------------------------------------
-template <int p, int q> __device__ inline void jacobi_rotate(double (&A)[4][4], double (&V)[4][4])
-{
-    const double apq = A[p][q];
-    if (apq == 0.0)
-        return;
-    const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-    const double den = fabs(theta) + sqrt(theta * theta + 1.0);
-    const double t = theta >= 0.0 ? 1.0 / den : -1.0 / den;
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    A[p][p] = A[p][p] - t * apq;
-    A[q][q] = A[q][q] + t * apq;
-    A[p][q] = A[q][p] = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        if (r != p && r != q) {
-            const double arp = A[r][p], arq = A[r][q];
-            A[r][p] = A[p][r] = c * arp - s * arq;
-            A[r][q] = A[q][r] = s * arp + c * arq;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const double vrp = V[r][p], vrq = V[r][q];
-        V[r][p] = c * vrp - s * vrq;
-        V[r][q] = s * vrp + c * vrq;
-    }
-}
-
+// ---- H6 (the cyclic Jacobi of the 4 x 4: jacobi.h) ----------------------------------------------------------------------
 struct Sim3Hyp {
     float R[9], t[3], s, T12[16], T21[16];
 };
@@ -185,20 +158,8 @@ __device__ inline void horn(const float P1[3][3], const float P2[3][3], bool fix
     const float N22 = (float)((m00 - m11) - m22), N23 = (float)(m01 + m10), N24 = (float)(m20 + m02);
     const float N33 = (float)((-m00 + m11) - m22), N34 = (float)(m12 + m21), N44 = (float)((-m00 - m11) + m22);
     double A[4][4] = {{N11, N12, N13, N14}, {N12, N22, N23, N24}, {N13, N23, N33, N34}, {N14, N24, N34, N44}};
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    for (int sweep = 0; sweep < S3_JACOBI_SWEEPS; sweep++) {
-        const double off = ((((A[0][1] * A[0][1] + A[0][2] * A[0][2]) + A[0][3] * A[0][3]) + A[1][2] * A[1][2]) +
-                            A[1][3] * A[1][3]) + A[2][3] * A[2][3];
-        const double diag = ((A[0][0] * A[0][0] + A[1][1] * A[1][1]) + A[2][2] * A[2][2]) + A[3][3] * A[3][3];
-        if (off <= 1e-32 * (diag + 2.0 * off))
-            break;
-        jacobi_rotate<0, 1>(A, V);
-        jacobi_rotate<0, 2>(A, V);
-        jacobi_rotate<0, 3>(A, V);
-        jacobi_rotate<1, 2>(A, V);
-        jacobi_rotate<1, 3>(A, V);
-        jacobi_rotate<2, 3>(A, V);
-    }
+    double V[4][4];
+    jacobi4_lane<S3_JACOBI_SWEEPS>(A, V);
     double best = A[0][0], q[4] = {V[0][0], V[1][0], V[2][0], V[3][0]};
 #pragma unroll
     for (int k = 1; k < 4; k++)

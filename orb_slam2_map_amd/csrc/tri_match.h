@@ -1,7 +1,6 @@
 // ORBmatcher::SearchForTriangulation (ORBmatcher.cc:657-823) as device functions.  tri_match_wave is the body of k_tri_match
 // (matcher_proj.hip) and of k_np_match (new_points.hip, the neighbour chain of LocalMapping::CreateNewMapPoints), which must
-// agree byte for byte.  tri_finish_block is k_np_finish's body and a copy of k_tri_finish's text: that kernel keeps its own,
-// because moving its __shared__ variables into a function changed their layout and its instructions.
+// agree byte for byte.  tri_finish_block is the body of k_tri_finish and of k_np_finish.
 #pragma once
 
 #include "common.h"
@@ -88,7 +87,7 @@ __device__ __forceinline__ void tri_match_wave(int n1, const float *__restrict__
         match12[i] = best;
 }
 
-// rotation consistency of the accepted pairs (:772-795) and the count; one workgroup of 1024 (k_tri_finish's text)
+// rotation consistency of the accepted pairs (:772-795) and the count; one workgroup of 1024
 __device__ __forceinline__ void tri_finish_block(int n1, const float *__restrict__ angle1, const float *__restrict__ angle2,
                                                  int check_orientation, int *__restrict__ match12,
                                                  int *__restrict__ nmatches)

@@ -11,11 +11,12 @@ import math
 
 import numpy as np
 
-from pnp_model import BOUND_FACTOR, GAP, LEFT_OUT_CAP, dev, sorted_eig  # noqa: F401  (the Jacobi and the rules are shared)
+from pnp_model import BOUND_FACTOR, GAP, LEFT_OUT_CAP, dev, sorted_eig  # noqa: F401  (the rules are shared; the Jacobi: jacobi_model.py)
 from sim3_model import reference_random_int  # noqa: F401
 
 f32, f64 = np.float32, np.float64
 MAX_N, MAX_HYP = 16384, 4096
+JACOBI_SWEEPS = 30
 TH_H, TH_F = f32(5.991), f32(3.841)
 K_DEFAULT = (500.0, 500.0, 320.0, 240.0)
 
@@ -119,7 +120,7 @@ def svd3(Af, eig, proper):
         S = np.zeros(A.shape)
         for j in range(3):
             S = S + A[:, j, :, None] * A[:, j, None, :]
-        w, Vt = sorted_eig(S, eig)
+        w, Vt = sorted_eig(S, eig, JACOBI_SWEEPS)
         av = np.stack([(A[:, :, 0] * Vt[:, k, 0, None] + A[:, :, 1] * Vt[:, k, 1, None]) + A[:, :, 2] * Vt[:, k, 2, None]
                        for k in range(3)], 1)                     # [B][k][i]
         d = np.sqrt((av[:, :, 0] * av[:, :, 0] + av[:, :, 1] * av[:, :, 1]) + av[:, :, 2] * av[:, :, 2])
@@ -188,7 +189,7 @@ def null_vector(A, eig):
         S = np.zeros((len(A), 9, 9))
         for r in range(A.shape[1]):
             S = S + A[:, r, :, None] * A[:, r, None, :]
-        w, Vt = sorted_eig(S, eig)
+        w, Vt = sorted_eig(S, eig, JACOBI_SWEEPS)
         gap = (w[:, 7] - w[:, 8]) / np.abs(w[:, 0])
         return Vt[:, 8].astype(f32), np.where(np.isfinite(gap), gap, 0.0)
 
@@ -384,7 +385,7 @@ def check_rt(prep, R, t, inl, K, sigma, eig):
         S = np.zeros((len(idx), 4, 4))
         for r in range(4):
             S = S + A[:, r, :, None] * A[:, r, None, :]
-        w, Vt = sorted_eig(S, eig)
+        w, Vt = sorted_eig(S, eig, JACOBI_SWEEPS)
         gap = (w[:, 2] - w[:, 3]) / np.abs(w[:, 0])
         out["gap"] = float(np.where(np.isfinite(gap), gap, 0.0).min())
         x4 = Vt[:, 3].astype(f32)

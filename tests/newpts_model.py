@@ -2,19 +2,21 @@
 ("vs CPU restatement; OpenCV boundary unpinned"), with the synthetic scenes of the tests.
 
 Every float step is an np.float32 operation in the reference's order; the FP64 sums are Python floats.  The triangulation
-has two eigen-paths, the convention's cyclic Jacobi (jacobi4, the statement-for-statement twin of jacobi4_lane) and
+has two eigen-paths, the convention's cyclic Jacobi (jacobi4: jacobi_model.jacobi_sym, the statement-for-statement twin of jacobi4_lane) and
 numpy.linalg.eigh; their distance over the created points is the model's *spread*.
 """
 import math
 
 import numpy as np
 
+from jacobi_model import JACOBI_STOP, jacobi_sym  # noqa: F401  (the one Jacobi of the models)
+
 f32, f64 = np.float32, np.float64
 
 (NONE, TRIANGULATED, UNPROJECT1, UNPROJECT2, LOW_PARALLAX, W_ZERO, Z1, Z2, REPROJ1, REPROJ2, ZERO_DIST, SCALE, NON_FINITE,
  STEREO_DEPTH, BAD_OCTAVE) = (0, 1, 2, 3, -1, -2, -3, -4, -5, -6, -7, -8, -9, -10, -11)
 TH_LOW, HISTO_LENGTH = 50, 30
-JACOBI_SWEEPS, JACOBI_STOP = 30, 1e-32
+JACOBI_SWEEPS = 30
 EPS32 = float(np.finfo(f32).eps)
 
 # ---- what is compared ------------------------------------------------------------------------------------------------------
@@ -140,43 +142,12 @@ def match(kf1, has1, kf2, only_stereo, check_ori):
 
 # ---- N5: the 4 x 4 null vector ------------------------------------------------------------------------------------------------
 def jacobi4(A):
-    """jacobi4_lane, statement for statement; A (list of lists of Python floats) is overwritten; returns V"""
-    V = [[1.0 if i == j else 0.0 for j in range(4)] for i in range(4)]
-    for _ in range(JACOBI_SWEEPS):
-        off = diag = 0.0
-        for p in range(4):
-            for q in range(p + 1, 4):
-                off = off + A[p][q] * A[p][q]
-        for i in range(4):
-            diag = diag + A[i][i] * A[i][i]
-        if off <= JACOBI_STOP * (diag + 2.0 * off):
-            break
-        for p in range(4):
-            for q in range(p + 1, 4):
-                apq = A[p][q]
-                if apq == 0.0:
-                    continue
-                app, aqq = A[p][p], A[q][q]
-                theta = (aqq - app) / (2.0 * apq)
-                den = abs(theta) + math.sqrt(theta * theta + 1.0)
-                t = 1.0 / den if theta >= 0.0 else -1.0 / den
-                c = 1.0 / math.sqrt(t * t + 1.0)
-                s = t * c
-                for r in range(4):
-                    if r != p and r != q:
-                        arp, arq = A[r][p], A[r][q]
-                        A[r][p] = A[p][r] = c * arp - s * arq
-                        A[r][q] = A[q][r] = s * arp + c * arq
-                    vrp, vrq = V[r][p], V[r][q]
-                    V[r][p] = c * vrp - s * vrq
-                    V[r][q] = s * vrp + c * vrq
-                A[p][p], A[q][q] = app - t * apq, aqq + t * apq
-                A[p][q] = A[q][p] = 0.0
-    return V
+    """jacobi4_lane at null_vector4's sweep count; A (list of lists of Python floats) is overwritten; returns V"""
+    return jacobi_sym(A, JACOBI_SWEEPS)
 
 
 def null_vector4(Af, eig="jacobi"):
-    """the float null vector of the float 4 x 4 Af as null_vector4 (jacobi4.h) forms it"""
+    """the float null vector of the float 4 x 4 Af as null_vector4 (jacobi.h) forms it"""
     A = [[0.0] * 4 for _ in range(4)]
     for a in range(4):
         for b in range(4):

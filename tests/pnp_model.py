@@ -10,6 +10,7 @@ import math
 
 import numpy as np
 
+from jacobi_model import JACOBI_STOP, jacobi_sym_batch  # noqa: F401  (the one Jacobi of the models)
 from sim3_model import _log, iteration_cap, reference_random_int  # noqa: F401  (what the two solvers' models share)
 
 f32, f64 = np.float32, np.float64
@@ -18,7 +19,6 @@ SIGMA2 = (f32(1.2) ** np.arange(NLEVELS, dtype=f32)) ** 2
 INT_MAX = 2 ** 31 - 1
 LANES = 64
 JACOBI_SWEEPS = 30
-JACOBI_STOP = 1e-32
 CC_REL = 1e-6      # P5: 1 / k_i = 0 when k_i <= CC_REL * k_0 (the set has no extent along axis i: coplanar, collinear)
 LS_REL = 1e-12     # P5: eigenvalues of L'L at or below LS_REL x the largest are dropped from the least-squares solve
 MAX_N1, MAX_HYP, MIN_SET_LO, MIN_SET_HI = 16384, 4096, 4, 64
@@ -118,52 +118,13 @@ def wave_sum(C):
 def jacobi(A):
     """Cyclic Jacobi on symmetric [B][m][m]: pairs row by row, at most 30 sweeps, H6's stopping rule and rotation.
     Returns (eigenvalues [B][m] = the diagonal, V [B][m][m] with eigenvectors in columns), unsorted."""
-    A = np.array(A, f64)
-    B, m = A.shape[:2]
-    V = np.broadcast_to(np.eye(m), (B, m, m)).copy()
-    pairs = [(p, q) for p in range(m) for q in range(p + 1, m)]
-    with np.errstate(all="ignore"):
-        for _ in range(JACOBI_SWEEPS):
-            off = np.zeros(B)
-            for p, q in pairs:
-                off = off + A[:, p, q] * A[:, p, q]
-            diag = np.zeros(B)
-            for i in range(m):
-                diag = diag + A[:, i, i] * A[:, i, i]
-            active = ~(off <= JACOBI_STOP * (diag + 2.0 * off))
-            if not active.any():
-                break
-            for p, q in pairs:
-                apq, app, aqq = A[:, p, q].copy(), A[:, p, p].copy(), A[:, q, q].copy()
-                do = active & ~(apq == 0.0)
-                if not do.any():
-                    continue
-                theta = (aqq - app) / (2.0 * apq)
-                den = np.abs(theta) + np.sqrt(theta * theta + 1.0)
-                t = np.where(theta >= 0.0, 1.0 / den, -1.0 / den)
-                c = 1.0 / np.sqrt(t * t + 1.0)
-                s = t * c
-                arp, arq = A[:, :, p].copy(), A[:, :, q].copy()
-                newp = c[:, None] * arp - s[:, None] * arq
-                newq = s[:, None] * arp + c[:, None] * arq
-                newp[:, p], newp[:, q] = app - t * apq, 0.0
-                newq[:, q], newq[:, p] = aqq + t * apq, 0.0
-                newp = np.where(do[:, None], newp, arp)
-                newq = np.where(do[:, None], newq, arq)
-                A[:, :, p] = newp
-                A[:, p, :] = newp
-                A[:, :, q] = newq
-                A[:, q, :] = newq
-                vp, vq = V[:, :, p].copy(), V[:, :, q].copy()
-                V[:, :, p] = np.where(do[:, None], c[:, None] * vp - s[:, None] * vq, vp)
-                V[:, :, q] = np.where(do[:, None], s[:, None] * vp + c[:, None] * vq, vq)
-    return np.diagonal(A, axis1=1, axis2=2).copy(), V
+    return jacobi_sym_batch(A, JACOBI_SWEEPS)
 
 
-def sym_eig(A, eig):
+def sym_eig(A, eig, sweeps=JACOBI_SWEEPS):
     """(w, V) unsorted for the Jacobi, ascending for eigh; a matrix with a NaN or inf gives NaN in both."""
     if eig == "jacobi":
-        return jacobi(A)
+        return jacobi_sym_batch(A, sweeps)
     A = np.array(A, f64)
     B, m = A.shape[:2]
     w, V = np.full((B, m), np.nan), np.full((B, m, m), np.nan)
@@ -180,10 +141,10 @@ def sign_rule(v):
     return np.where(lead < 0.0, -v, v)
 
 
-def sorted_eig(A, eig):
+def sorted_eig(A, eig, sweeps=JACOBI_SWEEPS):
     """Eigenvalues descending (stable), eigenvectors as ROWS with the sign rule: what the SVD of a symmetric positive
     semi-definite matrix with CV_SVD_U_T hands the reference, made definite."""
-    w, V = sym_eig(A, eig)
+    w, V = sym_eig(A, eig, sweeps)
     order = np.argsort(-w, axis=1, kind="stable")
     w = np.take_along_axis(w, order, 1)
     Vt = np.take_along_axis(np.swapaxes(V, 1, 2), order[:, :, None], 1)

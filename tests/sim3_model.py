@@ -7,11 +7,11 @@ import math
 
 import numpy as np
 
+from jacobi_model import JACOBI_STOP, jacobi_sym  # noqa: F401  (the one Jacobi of the models)
+
 f32, f64 = np.float32, np.float64
 CHI2 = 9.210
 JACOBI_SWEEPS = 16
-JACOBI_PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
-JACOBI_STOP = 1e-32
 NLEVELS = 8
 SIGMA2 = (f32(1.2) ** np.arange(NLEVELS, dtype=f32)) ** 2
 INT_MAX = 2 ** 31 - 1
@@ -146,36 +146,9 @@ class RansacState:
 # ---- H6 ----------------------------------------------------------------------------------------------------------------
 def jacobi4(N):
     """Cyclic Jacobi on the symmetric 4x4 (float64).  Returns (eigenvalues = diagonal, V with eigenvectors in columns)."""
-    A = np.array(N, f64)
-    V = np.eye(4)
-    with np.errstate(all="ignore"):
-        for _ in range(JACOBI_SWEEPS):
-            off = ((((A[0, 1] * A[0, 1] + A[0, 2] * A[0, 2]) + A[0, 3] * A[0, 3]) + A[1, 2] * A[1, 2]) + A[1, 3] * A[1, 3]) + A[2, 3] * A[2, 3]
-            diag = ((A[0, 0] * A[0, 0] + A[1, 1] * A[1, 1]) + A[2, 2] * A[2, 2]) + A[3, 3] * A[3, 3]
-            if off <= JACOBI_STOP * (diag + 2.0 * off):
-                break
-            for p, q in JACOBI_PAIRS:
-                apq = A[p, q]
-                if apq == 0.0:
-                    continue
-                theta = (A[q, q] - A[p, p]) / (2.0 * apq)
-                den = abs(theta) + np.sqrt(theta * theta + 1.0)
-                t = 1.0 / den if theta >= 0.0 else -1.0 / den
-                c = 1.0 / np.sqrt(t * t + 1.0)
-                s = t * c
-                A[p, p] = A[p, p] - t * apq
-                A[q, q] = A[q, q] + t * apq
-                A[p, q] = A[q, p] = 0.0
-                for r in range(4):
-                    if r != p and r != q:
-                        arp, arq = A[r, p], A[r, q]
-                        A[r, p] = A[p, r] = c * arp - s * arq
-                        A[r, q] = A[q, r] = s * arp + c * arq
-                for r in range(4):
-                    vrp, vrq = V[r, p], V[r, q]
-                    V[r, p] = c * vrp - s * vrq
-                    V[r, q] = s * vrp + c * vrq
-    return np.diag(A).copy(), V
+    A = [[float(x) for x in row] for row in np.array(N, f64)]
+    V = jacobi_sym(A, JACOBI_SWEEPS)
+    return np.array([A[i][i] for i in range(4)], f64), np.array(V, f64)
 
 
 def top_eigenvector(N, eig="jacobi"):
