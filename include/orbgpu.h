@@ -761,6 +761,89 @@ int orbgpu_local_ba(const orbgpu_local_ba_problem *p, const int32_t *stop, doubl
  * lived in the global workspace.  Synchronises the device. */
 int orbgpu_local_ba_last_spills(int32_t device_id, int32_t *problems_spilled);
 
+/* ---- Optimizer::BundleAdjustment / GlobalBundleAdjustemnt (Optimizer.cc:41-237): full bundle adjustment on the device -------
+ * The call of Tracking::CreateInitialMapMonocular (Tracking.cc:963: two key frames, 20 iterations, robust) and of
+ * LoopClosing::RunGlobalBundleAdjustment (LoopClosing.cc:647: the whole map, 20 iterations, bRobust = false): every key
+ * frame and every point of a map in ONE optimize().  The kernel is orbgpu_local_ba's Levenberg-Marquardt loop with another
+ * round structure; tests/ba_model.py is the float64 restatement (g2o unpinned, as above).  Where a rule says no more than
+ * "as Lk", nothing differs from orbgpu_local_ba:
+ *   B1 problem             P pose rows: vpKFs without the bad ones, free unless fixed[i] (the reference fixes mnId == 0 only;
+ *                          any mask is taken, none fixed included: the gauge is then left to lambda); M point rows: vpMP
+ *                          without the bad ones; edges as L1.  Skipping the observations of key frames that are bad or whose
+ *                          mnId > maxKFid (:109) is the caller's.  Set-up as L2 but for the Huber deltas (B2).
+ *   B2 kernel (:85, :131)  robust != 0: Huber delta (float)sqrt(5.99) for mono edges -- 5.99, not L2's 5.991 -- and
+ *                          (float)sqrt(7.815) for stereo edges; robust == 0: no kernel on any edge (rho0 = chi2, rho1 = 1),
+ *                          the state L7's second round runs in.
+ *   B3 optimize            ONE optimize(n_iterations) by L3-L6 over all edges, 0 <= n_iterations <=
+ *                          ORBGPU_BA_MAX_ITERATIONS.  No classification, no level-1 edge, no second round, no erase.
+ *   B4 activity (:175-179) a point without a taken edge is vbNotIncludedMP: not_included = 1, its outputs are the round trip
+ *                          of its input, and it never reaches the inverse; every other point's byte is 0.  A pose row without
+ *                          a taken edge keeps its estimate (L4).  n_iterations == 0 writes the round trip of every input with
+ *                          iterations = trials = 0 and chi2_start = chi2_end = the robust chi2 of the input.
+ *   B5 stop flag           L9 without the read between rounds: before anything, then at each iteration and each trial.
+ *                          Non-zero at the first read: nothing is written but the result, stopped = 1.  Later: the outputs
+ *                          are the kept state, stopped = 1.
+ *   B6 determinism, range  as L10 and L11; an out-of-range edge makes no point included.
+ *   B7 out                 as L12 with not_included [M] in place of erase: Tcw_d and (float)Tcw_d for EVERY pose row (fixed
+ *                          rows: the quaternion round trip of their input), both positions per point, the result.
+ * A whole map is larger than a local one, so the capacities are the call's own (a first choice, like LBA's);
+ * the cap on edge pairs is ORBGPU_LBA_MAX_PAIRS. */
+#define ORBGPU_BA_MAX_POSES 1024
+#define ORBGPU_BA_MAX_FREE 256        /* free poses: the reduced system has 6 * 256 rows */
+#define ORBGPU_BA_MAX_POINTS 65536
+#define ORBGPU_BA_MAX_EDGES (1 << 20)
+#define ORBGPU_BA_MAX_ITERATIONS 100
+
+typedef struct orbgpu_bundle_adjustment_result { /* device or host, 8-byte aligned */
+    double chi2_start, chi2_end; /* robust chi2 of the edges at the input and at the kept end */
+    int32_t n_edges;        /* edges taken (E less the out-of-range ones) */
+    int32_t iterations, trials; /* LM iterations and trials */
+    int32_t stopped;        /* the stop flag was seen non-zero */
+    int32_t n_bad_index;    /* edges skipped for an out-of-range row or octave */
+    int32_t n_not_included; /* points without a taken edge */
+    int32_t reduced_in_lds; /* 1: S lived in LDS, 0: in the global workspace */
+    int32_t pad_;
+} orbgpu_bundle_adjustment_result;
+
+typedef struct orbgpu_bundle_adjustment_problem {
+    int32_t n_poses, n_points, n_edges, nlevels;
+    int32_t n_iterations;          /* 0 .. ORBGPU_BA_MAX_ITERATIONS */
+    int32_t robust;                /* non-zero: Huber kernel on every edge (B2) */
+    const float *Tcw;              /* HOST [n_poses][16]: GetPose() */
+    const uint8_t *fixed;          /* HOST [n_poses]: non-zero = the row is not optimised (mnId == 0) */
+    const float *cam;              /* HOST [n_poses][5]: fx, fy, cx, cy, mbf */
+    const float *inv_level_sigma2; /* HOST [n_poses][nlevels] */
+    const float *world_pos;        /* HOST [n_points][3] */
+    const int32_t *edge_point, *edge_pose, *edge_octave; /* HOST [n_edges] */
+    const float *edge_xy;          /* HOST [n_edges][2]: mvKeysUn[...].pt */
+    const float *edge_u_right;     /* HOST [n_edges]: mvuRight[...] */
+    const int32_t *d_stop;         /* device or NULL */
+    double *d_Tcw_d;               /* device [n_poses][16] */
+    float *d_Tcw;                  /* device [n_poses][16] */
+    double *d_pos_d;               /* device [n_points][3] */
+    float *d_pos;                  /* device [n_points][3] */
+    uint8_t *d_not_included;       /* device [n_points] */
+    orbgpu_bundle_adjustment_result *d_result; /* device */
+} orbgpu_bundle_adjustment_problem;
+
+/* Enqueued on hip_stream, not synchronised, under orbgpu_local_ba_device's rules (the index structure is built and uploaded
+ * before the call returns; calls of one host thread share a workspace -- not orbgpu_local_ba's -- and must be ordered on one
+ * stream).  EINVAL: null pointers, negative counts, n_iterations outside [0, ORBGPU_BA_MAX_ITERATIONS], nlevels outside
+ * [1, ORBGPU_MAX_LEVELS], more than ORBGPU_BA_MAX_* of anything or than ORBGPU_LBA_MAX_PAIRS edge pairs (no CPU fallback: the
+ * caller keeps its g2o path); EHIP without a device.  The batch form is ONE launch, one workgroup per problem. */
+int orbgpu_bundle_adjustment_device(const orbgpu_bundle_adjustment_problem *p, int32_t device_id, void *hip_stream);
+int orbgpu_bundle_adjustment_batch_device(int32_t n, const orbgpu_bundle_adjustment_problem *problems, int32_t device_id,
+                                          void *hip_stream);
+/* Host arrays, synchronises: the d_* members of p are not read; Tcw_d / Tcw [n_poses][16], pos_d / pos [n_points][3] and
+ * not_included [n_points] are in/out (a call stopped at once leaves them alone), any of Tcw_d, pos_d and result may be NULL.
+ * stop: HOST int32 sampled at the call, or NULL. */
+int orbgpu_bundle_adjustment(const orbgpu_bundle_adjustment_problem *p, const int32_t *stop, double *Tcw_d, float *Tcw,
+                             double *pos_d, float *pos, uint8_t *not_included, orbgpu_bundle_adjustment_result *result,
+                             int32_t device_id);
+/* Diagnostic, as orbgpu_local_ba_last_spills, for the calling thread's most recent bundle adjustment on device_id (the same
+ * limit of 28 free poses and the same ORBGPU_DEBUG_LBA_LDS_POSES). */
+int orbgpu_bundle_adjustment_last_spills(int32_t device_id, int32_t *problems_spilled);
+
 /* ---- Sim3Solver (Sim3Solver.cc, Horn 1987 + RANSAC): the Sim3 of a loop candidate on the device --------------------------
  * The second of the five steps of LoopClosing::ComputeSim3 (LoopClosing.cc:236-343); its result is the R12 / t12 / s12 that
  * orbgpu_search_by_sim3 takes.  All hypotheses of a candidate are evaluated at once, one wave each; the reference's

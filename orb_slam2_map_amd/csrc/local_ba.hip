@@ -6,6 +6,10 @@
 // point run edge by edge as the model's do, the sums per pose, per block of the reduced system and over the workgroup as
 // per-lane partial sums and a fixed tree.
 //
+// Optimizer::BundleAdjustment / GlobalBundleAdjustemnt (Optimizer.cc:41-237; B1-B7, tests/ba_model.py) is the same loop in
+// another round structure -- one optimize(n_iterations) over every key frame and point of a map, no classification -- and
+// shares this file's kernel text (lm_problem<FULL>) and host side; DESIGN.md 9.27.
+//
 // Memory: everything of a problem whose size follows its edges or points (the sorted edges, both copies of the state, Hll,
 // bl, Hll^-1, Hpl, the index lists) lives in the call's global workspace; only the reduced camera system S (lower triangle,
 // packed) with its three vectors lives in LDS, when the problem has at most LBA_LDS_POSES free poses.
@@ -67,6 +71,10 @@ struct LbaProblemDev {
     int32_t *spill_count;
     int32_t P, nl, M, ne, nf, n_bad_index, in_lds;
     double delta[2], delta2[2];
+    // Optimizer::BundleAdjustment only (k_bundle_adjustment): nl = P there, erase and result are null
+    uint8_t *not_included;  // [M]
+    orbgpu_bundle_adjustment_result *ba_result;
+    int32_t n_iterations, robust, n_not_included;
 };
 
 struct WorkgroupBarrier {
@@ -176,28 +184,40 @@ __device__ inline int classify(const LbaProblemDev &P, const double *poses, cons
     return *icount;
 }
 
-__global__ __launch_bounds__(LBA_THREADS) void k_local_ba(const LbaProblemDev *__restrict__ problems)
+// The one text of the Levenberg-Marquardt loop.  What the two optimisers differ in is a template argument, so that each
+// kernel compiles its round structure from constants:
+//   FULL = false  Optimizer::LocalBundleAdjustment (L1-L12): optimize(5) with Huber, classify, optimize(10) without, erase
+//   FULL = true   Optimizer::BundleAdjustment (B1-B7): ONE optimize(P.n_iterations), Huber iff P.robust, no classification;
+//                 not_included per point and the poses of every row (P.nl = P.P) out
+template <bool FULL>
+__device__ __forceinline__ void lm_problem(const LbaProblemDev &P)
 {
     __shared__ double S_lds[LBA_LDS_TRI];
     __shared__ double vec_lds[3 * LBA_LDS_ROWS];
     __shared__ double red[LBA_WAVES];
     __shared__ int flag, icount;
-    const LbaProblemDev &P = problems[blockIdx.x];
+    constexpr int N_ROUNDS = FULL ? 1 : 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = 6 * P.nf, nblk = P.nf * (P.nf + 1) / 2;
     double *S = P.in_lds ? S_lds : P.S;
     double *vec = P.in_lds ? vec_lds : P.vec;  // [n] right-hand side / solution, [2 n] work of the solve
-    orbgpu_local_ba_result *res = P.result;
 
     // Everything below that steers control flow (the flag, lam, nu, rho, the counters, which copy of the state is kept) is
     // the same in every lane -- broadcast through LDS or computed from block_sum / block_max results -- so the barriers
     // inside the loops are reached by all lanes.  Trip counts are bounded by the constants of the definition: 5 + 10
-    // iterations of at most 10 trials.
+    // iterations (FULL: n_iterations <= ORBGPU_BA_MAX_ITERATIONS, checked on the host) of at most 10 trials.
     if (stop_requested(P.stop, &flag)) {  // Optimizer.cc:655
         if (tid == 0) {
-            orbgpu_local_ba_result r{};
-            r.n_edges = P.ne, r.n_bad_index = P.n_bad_index, r.stopped = 1, r.reduced_in_lds = P.in_lds;
-            *res = r;
+            if constexpr (FULL) {
+                orbgpu_bundle_adjustment_result r{};
+                r.n_edges = P.ne, r.n_bad_index = P.n_bad_index, r.stopped = 1, r.reduced_in_lds = P.in_lds;
+                r.n_not_included = P.n_not_included;
+                *P.ba_result = r;
+            } else {
+                orbgpu_local_ba_result r{};
+                r.n_edges = P.ne, r.n_bad_index = P.n_bad_index, r.stopped = 1, r.reduced_in_lds = P.in_lds;
+                *P.result = r;
+            }
         }
         return;
     }
@@ -210,9 +230,9 @@ __global__ __launch_bounds__(LBA_THREADS) void k_local_ba(const LbaProblemDev *_
     int kept = 0;  // P.pose[kept], P.X[kept]: the state
     int rounds = 0, stopped = 0, iterations[2] = {0, 0}, trials[2] = {0, 0};
     double chi_start[2] = {0.0, 0.0}, chi_end[2] = {0.0, 0.0};
-    bool use_kernel = true;
-    for (int rnd = 0; rnd < 2 && !stopped; rnd++) {
-        if (rnd == 1) {
+    bool use_kernel = FULL ? P.robust != 0 : true;
+    for (int rnd = 0; rnd < N_ROUNDS && !stopped; rnd++) {
+        if (!FULL && rnd == 1) {
             if (stop_requested(P.stop, &flag)) {  // Optimizer.cc:664: bDoMore = false
                 stopped = 1;
                 break;
@@ -236,7 +256,9 @@ __global__ __launch_bounds__(LBA_THREADS) void k_local_ba(const LbaProblemDev *_
         __syncthreads();
 
         double lam = 0.0, nu = 2.0, cur = 0.0;
-        const int n_it = rnd == 0 ? 5 : 10;
+        const int n_it = FULL ? P.n_iterations : (rnd == 0 ? 5 : 10);
+        if (FULL && n_it == 0)  // B4: nothing runs; both chi2 members are the input's
+            chi_start[rnd] = cur = robust_chi(P, P.pose[kept], P.X[kept], use_kernel, red);
         for (int it = 0; it < n_it; it++) {
             if (stop_requested(P.stop, &flag)) {
                 stopped = 1;
@@ -550,7 +572,13 @@ __global__ __launch_bounds__(LBA_THREADS) void k_local_ba(const LbaProblemDev *_
     }
 
     // ---- L8, L12 ----
-    const int n_erased = classify(P, P.pose[kept], P.X[kept], false, &icount);
+    int n_erased = 0;
+    if constexpr (FULL) {
+        for (int p = tid; p < P.M; p += LBA_THREADS)  // B4: vbNotIncludedMP
+            P.not_included[p] = P.pt_on[p] ? 0 : 1;
+    } else {
+        n_erased = classify(P, P.pose[kept], P.X[kept], false, &icount);
+    }
     for (int i = tid; i < P.nl; i += LBA_THREADS) {
         const double *ps = P.pose[kept] + (size_t)i * LBA_POSE_STRIDE, *R = ps + 7, *t = ps + 4;
         const double T[16] = {R[0], R[1], R[2], t[0], R[3], R[4], R[5], t[1], R[6], R[7], R[8], t[2], 0.0, 0.0, 0.0, 1.0};
@@ -565,15 +593,33 @@ __global__ __launch_bounds__(LBA_THREADS) void k_local_ba(const LbaProblemDev *_
         P.pos[k] = (float)v;
     }
     if (tid == 0) {
-        orbgpu_local_ba_result r{};
-        for (int k = 0; k < 2; k++) {
-            r.chi2_start[k] = chi_start[k], r.chi2_end[k] = chi_end[k];
-            r.iterations[k] = iterations[k], r.trials[k] = trials[k];
+        if constexpr (FULL) {
+            orbgpu_bundle_adjustment_result r{};
+            r.chi2_start = chi_start[0], r.chi2_end = chi_end[0];
+            r.n_edges = P.ne, r.iterations = iterations[0], r.trials = trials[0], r.stopped = stopped;
+            r.n_bad_index = P.n_bad_index, r.n_not_included = P.n_not_included, r.reduced_in_lds = P.in_lds;
+            *P.ba_result = r;
+        } else {
+            orbgpu_local_ba_result r{};
+            for (int k = 0; k < 2; k++) {
+                r.chi2_start[k] = chi_start[k], r.chi2_end[k] = chi_end[k];
+                r.iterations[k] = iterations[k], r.trials[k] = trials[k];
+            }
+            r.n_edges = P.ne, r.n_erased = n_erased, r.rounds = rounds, r.stopped = stopped, r.n_bad_index = P.n_bad_index;
+            r.reduced_in_lds = P.in_lds;
+            *P.result = r;
         }
-        r.n_edges = P.ne, r.n_erased = n_erased, r.rounds = rounds, r.stopped = stopped, r.n_bad_index = P.n_bad_index;
-        r.reduced_in_lds = P.in_lds;
-        *res = r;
     }
+}
+
+__global__ __launch_bounds__(LBA_THREADS) void k_local_ba(const LbaProblemDev *__restrict__ problems)
+{
+    lm_problem<false>(problems[blockIdx.x]);
+}
+
+__global__ __launch_bounds__(LBA_THREADS) void k_bundle_adjustment(const LbaProblemDev *__restrict__ problems)
+{
+    lm_problem<true>(problems[blockIdx.x]);
 }
 
 // Per (thread, device) staging of the entry points (staging.h): PROBLEMS and WORK are the device flavours' (the problem
@@ -585,16 +631,36 @@ struct LbaWs : Staging<N_BUF> {
     std::vector<char> blob;
     std::vector<LbaProblemDev> records;
 };
+struct BaWs : LbaWs {};  // Optimizer::BundleAdjustment's: its calls and its spill count are its own
 
-static int check_problem(const orbgpu_local_ba_problem &p, int k)
+// The host side takes either optimiser's problem as an orbgpu_local_ba_problem (BundleAdjustment: every row local, no erase)
+// with the capacities of its entry point; what only BundleAdjustment has is read from its own structure.
+struct LbaCaps {
+    int poses, free, points, edges;
+};
+constexpr LbaCaps LBA_CAPS{ORBGPU_LBA_MAX_POSES, ORBGPU_LBA_MAX_FREE, ORBGPU_LBA_MAX_POINTS, ORBGPU_LBA_MAX_EDGES};
+constexpr LbaCaps BA_CAPS{ORBGPU_BA_MAX_POSES, ORBGPU_BA_MAX_FREE, ORBGPU_BA_MAX_POINTS, ORBGPU_BA_MAX_EDGES};
+
+static orbgpu_local_ba_problem as_local(const orbgpu_bundle_adjustment_problem &b)
+{
+    orbgpu_local_ba_problem p{};
+    p.n_poses = p.n_local = b.n_poses, p.n_points = b.n_points, p.n_edges = b.n_edges, p.nlevels = b.nlevels;
+    p.Tcw = b.Tcw, p.fixed = b.fixed, p.cam = b.cam, p.inv_level_sigma2 = b.inv_level_sigma2, p.world_pos = b.world_pos;
+    p.edge_point = b.edge_point, p.edge_pose = b.edge_pose, p.edge_octave = b.edge_octave;
+    p.edge_xy = b.edge_xy, p.edge_u_right = b.edge_u_right;
+    p.d_stop = b.d_stop, p.d_Tcw_d = b.d_Tcw_d, p.d_Tcw = b.d_Tcw, p.d_pos_d = b.d_pos_d, p.d_pos = b.d_pos;
+    return p;
+}
+
+static int check_problem(const orbgpu_local_ba_problem &p, int k, const LbaCaps &caps = LBA_CAPS)
 {
     ORBGPU_REQUIRE(p.n_poses >= 0 && p.n_local >= 0 && p.n_points >= 0 && p.n_edges >= 0, "problem %d: negative count", k);
     ORBGPU_REQUIRE(p.n_local <= p.n_poses, "problem %d: more local key frames than pose rows", k);
     ORBGPU_REQUIRE(p.nlevels >= 1 && p.nlevels <= ORBGPU_MAX_LEVELS, "problem %d: nlevels outside [1, %d]", k,
                    ORBGPU_MAX_LEVELS);
-    ORBGPU_REQUIRE(p.n_poses <= ORBGPU_LBA_MAX_POSES, "problem %d: more than %d pose rows", k, ORBGPU_LBA_MAX_POSES);
-    ORBGPU_REQUIRE(p.n_points <= ORBGPU_LBA_MAX_POINTS, "problem %d: more than %d points", k, ORBGPU_LBA_MAX_POINTS);
-    ORBGPU_REQUIRE(p.n_edges <= ORBGPU_LBA_MAX_EDGES, "problem %d: more than %d edges", k, ORBGPU_LBA_MAX_EDGES);
+    ORBGPU_REQUIRE(p.n_poses <= caps.poses, "problem %d: more than %d pose rows", k, caps.poses);
+    ORBGPU_REQUIRE(p.n_points <= caps.points, "problem %d: more than %d points", k, caps.points);
+    ORBGPU_REQUIRE(p.n_edges <= caps.edges, "problem %d: more than %d edges", k, caps.edges);
     ORBGPU_REQUIRE(p.n_poses == 0 || (p.Tcw && p.cam && p.inv_level_sigma2), "problem %d: null pose arrays", k);
     ORBGPU_REQUIRE(p.n_local == 0 || p.fixed, "problem %d: null fixed array", k);
     ORBGPU_REQUIRE(p.n_points == 0 || p.world_pos, "problem %d: null point array", k);
@@ -603,8 +669,15 @@ static int check_problem(const orbgpu_local_ba_problem &p, int k)
     int nf = 0;
     for (int i = 0; i < p.n_local; i++)
         nf += p.fixed[i] ? 0 : 1;
-    ORBGPU_REQUIRE(nf <= ORBGPU_LBA_MAX_FREE, "problem %d: %d free poses, more than %d", k, nf, ORBGPU_LBA_MAX_FREE);
+    ORBGPU_REQUIRE(nf <= caps.free, "problem %d: %d free poses, more than %d", k, nf, caps.free);
     return ORBGPU_OK;
+}
+
+static int check_problem(const orbgpu_bundle_adjustment_problem &b, int k)
+{
+    ORBGPU_REQUIRE(b.n_iterations >= 0 && b.n_iterations <= ORBGPU_BA_MAX_ITERATIONS, "problem %d: n_iterations outside [0, %d]",
+                   k, ORBGPU_BA_MAX_ITERATIONS);
+    return check_problem(as_local(b), k, BA_CAPS);
 }
 
 static int check_device_outputs(const orbgpu_local_ba_problem &p, int k)
@@ -614,6 +687,17 @@ static int check_device_outputs(const orbgpu_local_ba_problem &p, int k)
         return rc;
     ORBGPU_REQUIRE(p.d_result && (p.n_local == 0 || (p.d_Tcw_d && p.d_Tcw)) && (p.n_points == 0 || (p.d_pos_d && p.d_pos)) &&
                        (p.n_edges == 0 || p.d_erase),
+                   "problem %d: null output", k);
+    return ORBGPU_OK;
+}
+
+static int check_device_outputs(const orbgpu_bundle_adjustment_problem &b, int k)
+{
+    int rc = check_problem(b, k);
+    if (rc != ORBGPU_OK)
+        return rc;
+    ORBGPU_REQUIRE(b.d_result && (b.n_poses == 0 || (b.d_Tcw_d && b.d_Tcw)) &&
+                       (b.n_points == 0 || (b.d_pos_d && b.d_pos && b.d_not_included)),
                    "problem %d: null output", k);
     return ORBGPU_OK;
 }
@@ -713,18 +797,12 @@ static int build_index(const orbgpu_local_ba_problem &p, int k, LbaIndex &ix)
     return ORBGPU_OK;
 }
 
-} // namespace orbgpu
-
-using namespace orbgpu;
-
-extern "C" int orbgpu_local_ba_batch_device(int32_t n, const orbgpu_local_ba_problem *problems, int32_t device_id,
-                                            void *hip_stream)
+// Both *_batch_device entry points after their checks: n > 0 problems on the bound workspace ws; full: the
+// BundleAdjustment structures the problems were taken from, or null for LocalBundleAdjustment.
+static int enqueue(int32_t n, const orbgpu_local_ba_problem *problems, const orbgpu_bundle_adjustment_problem *full, LbaWs &ws,
+                   void *hip_stream)
 {
-    LbaWs *wsp;
-    int rc = batch_begin(n, problems, check_device_outputs, device_id, wsp);
-    if (rc != ORBGPU_OK || !wsp)
-        return rc;
-    LbaWs &ws = *wsp;
+    int rc = ORBGPU_OK;
     // ORBGPU_DEBUG_LBA_LDS_POSES=<k> (tests): problems with more than k free poses keep the reduced system in global memory
     const int lds_poses = debug_limit("ORBGPU_DEBUG_LBA_LDS_POSES", LBA_LDS_POSES);
     // The workspace: first what is uploaded (one copy for the whole batch), then the kernel's scratch.  Offsets first,
@@ -840,7 +918,13 @@ extern "C" int orbgpu_local_ba_batch_device(int32_t n, const orbgpu_local_ba_pro
         D.P = p.n_poses, D.nl = p.n_local, D.M = p.n_points, D.ne = (int32_t)I.edges.size(), D.nf = (int32_t)I.free_row.size();
         D.n_bad_index = I.n_bad_index;
         D.in_lds = D.nf <= lds_poses ? 1 : 0;
-        D.delta[0] = (double)(float)std::sqrt(5.991), D.delta[1] = (double)(float)std::sqrt(7.815);
+        D.delta[0] = (double)(float)std::sqrt(full ? 5.99 : 5.991), D.delta[1] = (double)(float)std::sqrt(7.815);
+        if (full) {
+            D.not_included = full[k].d_not_included, D.ba_result = full[k].d_result;
+            D.n_iterations = full[k].n_iterations, D.robust = full[k].robust;
+            for (int i = 0; i < p.n_points; i++)
+                D.n_not_included += I.point_start[i + 1] == I.point_start[i] ? 1 : 0;
+        }
         D.delta2[0] = D.delta[0] * D.delta[0], D.delta2[1] = D.delta[1] * D.delta[1];
     }
     const hipStream_t st = (hipStream_t)hip_stream;
@@ -848,9 +932,25 @@ extern "C" int orbgpu_local_ba_batch_device(int32_t n, const orbgpu_local_ba_pro
     ORBGPU_HIP_TRY(hipMemcpyAsync(ws.buf[PROBLEMS].p, hp.data(), sizeof(LbaProblemDev) * (size_t)n, hipMemcpyHostToDevice, st));
     if (upload_bytes)
         ORBGPU_HIP_TRY(hipMemcpyAsync(dev, blob.data(), upload_bytes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_local_ba, dim3(n), dim3(LBA_THREADS), 0, st, ws.as<LbaProblemDev>(PROBLEMS));
+    hipLaunchKernelGGL(full ? k_bundle_adjustment : k_local_ba, dim3(n), dim3(LBA_THREADS), 0, st,
+                       ws.as<LbaProblemDev>(PROBLEMS));
     ORBGPU_HIP_TRY(hipGetLastError());
     return ORBGPU_OK;
+}
+
+} // namespace orbgpu
+
+using namespace orbgpu;
+
+extern "C" int orbgpu_local_ba_batch_device(int32_t n, const orbgpu_local_ba_problem *problems, int32_t device_id,
+                                            void *hip_stream)
+{
+    LbaWs *wsp;
+    int rc = batch_begin(n, problems, static_cast<int (*)(const orbgpu_local_ba_problem &, int)>(check_device_outputs), device_id,
+                         wsp);
+    if (rc != ORBGPU_OK || !wsp)
+        return rc;
+    return enqueue(n, problems, nullptr, *wsp, hip_stream);
 }
 
 extern "C" int orbgpu_local_ba_device(const orbgpu_local_ba_problem *p, int32_t device_id, void *hip_stream)
@@ -917,6 +1017,93 @@ extern "C" int orbgpu_local_ba(const orbgpu_local_ba_problem *p, const int32_t *
         ws.download(pos, H_OUT, 12 * M, o_X);
     if (E)
         ws.download(erase, H_OUT, E, o_er);
+    if ((rc = ws.finish()) != ORBGPU_OK)
+        return rc;
+    if (result)
+        *result = r;
+    return ORBGPU_OK;
+}
+
+// ---- Optimizer::BundleAdjustment / GlobalBundleAdjustemnt (B1-B7): the same host side over the other kernel ----------------
+extern "C" int orbgpu_bundle_adjustment_batch_device(int32_t n, const orbgpu_bundle_adjustment_problem *problems, int32_t device_id,
+                                                     void *hip_stream)
+{
+    BaWs *wsp;
+    int rc = batch_begin(n, problems, static_cast<int (*)(const orbgpu_bundle_adjustment_problem &, int)>(check_device_outputs),
+                         device_id, wsp);
+    if (rc != ORBGPU_OK || !wsp)
+        return rc;
+    std::vector<orbgpu_local_ba_problem> local((size_t)n);
+    for (int k = 0; k < n; k++)
+        local[k] = as_local(problems[k]);
+    return enqueue(n, local.data(), problems, *wsp, hip_stream);
+}
+
+extern "C" int orbgpu_bundle_adjustment_device(const orbgpu_bundle_adjustment_problem *p, int32_t device_id, void *hip_stream)
+{
+    ORBGPU_REQUIRE(p, "null argument");
+    return orbgpu_bundle_adjustment_batch_device(1, p, device_id, hip_stream);
+}
+
+extern "C" int orbgpu_bundle_adjustment_last_spills(int32_t device_id, int32_t *problems_spilled)
+{
+    return last_spills<BaWs>(device_id, SPILL_COUNT, "no bundle adjustment recorded on this thread", problems_spilled);
+}
+
+extern "C" int orbgpu_bundle_adjustment(const orbgpu_bundle_adjustment_problem *p, const int32_t *stop, double *Tcw_d, float *Tcw,
+                                        double *pos_d, float *pos, uint8_t *not_included,
+                                        orbgpu_bundle_adjustment_result *result, int32_t device_id)
+{
+    ORBGPU_REQUIRE(p, "null argument");
+    int rc = check_problem(*p, 0);
+    if (rc != ORBGPU_OK)
+        return rc;
+    ORBGPU_REQUIRE((p->n_poses == 0 || Tcw) && (p->n_points == 0 || (pos && not_included)), "null output");
+    // one staging block for the outputs; every segment starts on a multiple of 16 bytes
+    const size_t np = (size_t)p->n_poses, M = (size_t)p->n_points;
+    Carver out(16);
+    const size_t o_res = out.take(sizeof(orbgpu_bundle_adjustment_result)), o_Td = out.take(128 * std::max<size_t>(np, 1)),
+                 o_T = out.take(64 * std::max<size_t>(np, 1)), o_Xd = out.take(24 * std::max<size_t>(M, 1)),
+                 o_X = out.take(12 * std::max<size_t>(M, 1)), o_ni = out.take(std::max<size_t>(M, 1));
+    BaWs *wsp;
+    if ((rc = host_begin(device_id, H_STOP, 16, H_OUT, out.off, wsp)) != ORBGPU_OK)
+        return rc;
+    BaWs &ws = *wsp;
+    BaWs::FinishOnError on_error{ws};
+    const int32_t stop_now = stop ? *stop : 0;
+    ws.upload(H_STOP, &stop_now, sizeof(stop_now));
+    // in/out: what a call stopped at once leaves alone goes back as it came
+    if (np && Tcw_d)
+        ws.upload(H_OUT, Tcw_d, 128 * np, o_Td);
+    if (np)
+        ws.upload(H_OUT, Tcw, 64 * np, o_T);
+    if (M && pos_d)
+        ws.upload(H_OUT, pos_d, 24 * M, o_Xd);
+    if (M)
+        ws.upload(H_OUT, pos, 12 * M, o_X);
+    if (M)
+        ws.upload(H_OUT, not_included, M, o_ni);
+    if ((rc = ws.status()) != ORBGPU_OK)
+        return rc;
+    orbgpu_bundle_adjustment_problem d = *p;
+    d.d_stop = stop ? ws.as<int32_t>(H_STOP) : nullptr;
+    d.d_Tcw_d = ws.at<double>(H_OUT, o_Td), d.d_Tcw = ws.at<float>(H_OUT, o_T);
+    d.d_pos_d = ws.at<double>(H_OUT, o_Xd), d.d_pos = ws.at<float>(H_OUT, o_X);
+    d.d_not_included = ws.at<uint8_t>(H_OUT, o_ni), d.d_result = ws.at<orbgpu_bundle_adjustment_result>(H_OUT, o_res);
+    if ((rc = orbgpu_bundle_adjustment_batch_device(1, &d, device_id, ws.stream)) != ORBGPU_OK)
+        return rc;
+    orbgpu_bundle_adjustment_result r;
+    ws.download(&r, H_OUT, sizeof(r), o_res);
+    if (np && Tcw_d)
+        ws.download(Tcw_d, H_OUT, 128 * np, o_Td);
+    if (np)
+        ws.download(Tcw, H_OUT, 64 * np, o_T);
+    if (M && pos_d)
+        ws.download(pos_d, H_OUT, 24 * M, o_Xd);
+    if (M)
+        ws.download(pos, H_OUT, 12 * M, o_X);
+    if (M)
+        ws.download(not_included, H_OUT, M, o_ni);
     if ((rc = ws.finish()) != ORBGPU_OK)
         return rc;
     if (result)

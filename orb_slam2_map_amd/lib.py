@@ -141,6 +141,25 @@ class LocalBAProblem(C.Structure):
 LBA_MAX_POSES, LBA_MAX_FREE, LBA_MAX_POINTS, LBA_MAX_EDGES = 1024, 96, 16384, 262144
 
 
+class BundleAdjustmentResult(C.Structure):
+    _fields_ = [("chi2_start", C.c_double), ("chi2_end", C.c_double)] + \
+               [(k, C.c_int32) for k in ("n_edges", "iterations", "trials", "stopped", "n_bad_index", "n_not_included",
+                                         "reduced_in_lds", "pad_")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
+class BundleAdjustmentProblem(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_poses", "n_points", "n_edges", "nlevels", "n_iterations", "robust")] + \
+               [(k, C.c_void_p) for k in ("Tcw", "fixed", "cam", "inv_level_sigma2", "world_pos", "edge_point", "edge_pose",
+                                          "edge_octave", "edge_xy", "edge_u_right", "d_stop", "d_Tcw_d", "d_Tcw", "d_pos_d",
+                                          "d_pos", "d_not_included", "d_result")]
+
+
+BA_MAX_POSES, BA_MAX_FREE, BA_MAX_POINTS, BA_MAX_EDGES, BA_MAX_ITERATIONS = 1024, 256, 65536, 1 << 20, 100
+
+
 class Sim3Result(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n", "max_its", "n_bad_index", "n_bad_triple", "accepted", "n_inliers",
                                          "best_inliers", "best_iteration", "iterations", "no_more")]
@@ -285,6 +304,8 @@ ABI_SYMBOLS = [
     "orbgpu_pose_optimization", "orbgpu_pose_optimization_device", "orbgpu_pose_optimization_batch_device",
     "orbgpu_pose_optimization_table", "orbgpu_pose_last_spills",
     "orbgpu_local_ba", "orbgpu_local_ba_device", "orbgpu_local_ba_batch_device", "orbgpu_local_ba_last_spills",
+    "orbgpu_bundle_adjustment", "orbgpu_bundle_adjustment_device", "orbgpu_bundle_adjustment_batch_device",
+    "orbgpu_bundle_adjustment_last_spills",
     "orbgpu_sim3_ransac_iterations", "orbgpu_sim3_solve_device", "orbgpu_sim3_solve_batch_device", "orbgpu_sim3_solve",
     "orbgpu_sim3_solve_all",
     "orbgpu_sim3_optimize", "orbgpu_sim3_optimize_device", "orbgpu_sim3_optimize_batch_device",
@@ -1157,6 +1178,74 @@ def local_ba_last_spills(device_id=0):
     L.orbgpu_local_ba_last_spills.argtypes = [C.c_int32, C.c_void_p]
     v = C.c_int32()
     check(L.orbgpu_local_ba_last_spills(device_id, C.byref(v)))
+    return v.value
+
+
+_BA_PTRS = ("d_stop", "d_Tcw_d", "d_Tcw", "d_pos_d", "d_pos", "d_not_included", "d_result")
+
+
+def bundle_adjustment_problem(p, keep):
+    """A BundleAdjustmentProblem from a dict: the host arrays of local_ba_problem with fixed [P] (one flag per pose row, no
+    n_local), n_iterations (default 20) and robust (default True), and the device pointers d_stop (or None), d_Tcw_d, d_Tcw
+    ([P][16]), d_pos_d, d_pos, d_not_included ([M]), d_result (holds a BundleAdjustmentResult).  The counts follow the arrays
+    unless the dict names them; keep takes the host arrays the structure points to."""
+    q = BundleAdjustmentProblem()
+    a = {k: np.ascontiguousarray(p[k], t) for k, t in _LBA_HOST}
+    keep.append(a)
+    q.n_poses = int(p.get("n_poses", a["Tcw"].size // 16))
+    q.n_points = int(p.get("n_points", a["world_pos"].size // 3))
+    q.n_edges = int(p.get("n_edges", a["edge_point"].size))
+    q.nlevels = int(p.get("nlevels", a["inv_level_sigma2"].size // max(q.n_poses, 1)))
+    q.n_iterations, q.robust = int(p.get("n_iterations", 20)), int(bool(p.get("robust", True)))
+    for k, _ in _LBA_HOST:
+        setattr(q, k, a[k].ctypes.data if a[k].size else None)
+    _set_pointers(q, p, _BA_PTRS)
+    return q
+
+
+def bundle_adjustment_batch_device(problems, stream=0, device_id=0):
+    """n independent Optimizer::BundleAdjustment problems in ONE launch (orbgpu_bundle_adjustment_batch_device); enqueued,
+    not synchronised.  problems: dicts as bundle_adjustment_problem takes them."""
+    keep = []
+    _batch_device("bundle_adjustment", BundleAdjustmentProblem, lambda p: bundle_adjustment_problem(p, keep), problems, stream,
+                  device_id)
+
+
+def bundle_adjustment_device(problem, stream=0, device_id=0):
+    """One problem (orbgpu_bundle_adjustment_device); see bundle_adjustment_batch_device."""
+    keep = []
+    _one_device("bundle_adjustment", bundle_adjustment_problem(problem, keep), stream, device_id)
+
+
+def bundle_adjustment(problem, stop=None, Tcw_d=None, Tcw=None, pos_d=None, pos=None, not_included=None, device_id=0):
+    """Optimizer::BundleAdjustment over host arrays (orbgpu_bundle_adjustment); problem: the host part of the dict
+    bundle_adjustment_problem takes.  stop: None or an int sampled at the call.  The outputs start from the arrays given
+    (zeros by default): a call stopped at once leaves them as they were.  Returns (Tcw_d [P][4][4], Tcw, pos_d [M][3], pos,
+    not_included [M], result dict)."""
+    keep = []
+    q = bundle_adjustment_problem(problem, keep)
+    P, M = q.n_poses, q.n_points
+
+    def start(a, shape, t):
+        return np.zeros(shape, t) if a is None else np.array(a, t).reshape(shape).copy()
+    Td, T = start(Tcw_d, (max(P, 1), 4, 4), np.float64), start(Tcw, (max(P, 1), 4, 4), np.float32)
+    Xd, X = start(pos_d, (max(M, 1), 3), np.float64), start(pos, (max(M, 1), 3), np.float32)
+    ni = start(not_included, (max(M, 1),), np.uint8)
+    sv = None if stop is None else C.c_int32(int(stop))
+    res = BundleAdjustmentResult()
+    L = lib()
+    L.orbgpu_bundle_adjustment.argtypes = [C.c_void_p] * 8 + [C.c_int32]
+    check(L.orbgpu_bundle_adjustment(C.byref(q), None if sv is None else C.byref(sv), _p(Td), _p(T), _p(Xd), _p(X), _p(ni),
+                                     C.byref(res), device_id))
+    return Td[:P], T[:P], Xd[:M], X[:M], ni[:M], res.as_dict()
+
+
+def bundle_adjustment_last_spills(device_id=0):
+    """Problems of this thread's most recent bundle adjustment whose reduced system lived in global memory."""
+    L = lib()
+    L.orbgpu_bundle_adjustment_last_spills.argtypes = [C.c_int32, C.c_void_p]
+    v = C.c_int32()
+    check(L.orbgpu_bundle_adjustment_last_spills(device_id, C.byref(v)))
     return v.value
 
 

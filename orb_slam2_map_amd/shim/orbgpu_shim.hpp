@@ -1162,6 +1162,85 @@ template <typename KeyFrameT, typename MapPointT> struct LocalBAGraph {
     }
 };
 
+// The graph of Optimizer::BundleAdjustment (Optimizer.cc:68-184) as orbgpu_bundle_adjustment takes it.  Pose rows: vpKFs in
+// order without the bad ones, fixed iff mnId == 0; maxKFid over those rows; point rows: vpMP in order without the bad
+// ones; edges: per point row, its observations in the order of the map GetObservations() returns, without key frames
+// that are bad or whose mnId > maxKFid (:109).  An observer that is in no row (the reference reads through a null vertex
+// there), or an octave outside that key frame's sigma table, keeps its edge with pose / octave -1: the library skips and
+// counts it.  A point whose every observation is skipped comes back not included.
+template <typename KeyFrameT, typename MapPointT> struct FullBAGraph {
+    std::vector<KeyFrameT *> rows, edge_kf;
+    std::vector<MapPointT *> points, edge_mp;
+    std::vector<int32_t> edge_point, edge_pose, edge_octave;
+    std::vector<float> edge_xy, edge_ur, Tcw, cam, inv_sigma2, world_pos;
+    std::vector<uint8_t> fixed_flag;
+    long unsigned int maxKFid = 0;
+    int nlevels = 1;
+
+    template <typename Access>
+    FullBAGraph(const std::vector<KeyFrameT *> &vpKFs, const std::vector<MapPointT *> &vpMP, Access &access)
+    {
+        std::map<KeyFrameT *, int32_t> row;
+        for (KeyFrameT *pKF : vpKFs) {
+            if (pKF->isBad())
+                continue;
+            row[pKF] = (int32_t)rows.size();
+            rows.push_back(pKF);
+            if (pKF->mnId > maxKFid)
+                maxKFid = pKF->mnId;
+        }
+        const size_t P = rows.size();
+        if (P)
+            nlevels = (int)std::max<size_t>(1, std::min(rows[0]->mvInvLevelSigma2.size(), (size_t)ORBGPU_MAX_LEVELS));
+        // one spare row each so that data() is never null
+        Tcw.assign(16 * P + 16, 0.f), cam.assign(5 * P + 5, 0.f), inv_sigma2.assign((size_t)nlevels * (P + 1), 0.f);
+        fixed_flag.assign(P + 1, 0);
+        for (size_t i = 0; i < P; i++) {
+            KeyFrameT *k = rows[i];
+            std::memcpy(&Tcw[16 * i], access.pose(k), 64);
+            const float c[5] = {k->fx, k->fy, k->cx, k->cy, k->mbf};
+            std::memcpy(&cam[5 * i], c, sizeof(c));
+            for (size_t l = 0; l < std::min(k->mvInvLevelSigma2.size(), (size_t)nlevels); l++)
+                inv_sigma2[(size_t)nlevels * i + l] = k->mvInvLevelSigma2[l];
+            fixed_flag[i] = k->mnId == 0;
+        }
+        for (MapPointT *pMP : vpMP)
+            if (!pMP->isBad())
+                points.push_back(pMP);
+        world_pos.assign(3 * points.size() + 3, 0.f);
+        for (size_t j = 0; j < points.size(); j++) {
+            MapPointT *pMP = points[j];
+            std::memcpy(&world_pos[3 * j], access.world_pos(pMP), 12);
+            const auto observations = pMP->GetObservations();
+            for (const auto &ob : observations) {
+                KeyFrameT *pKFi = ob.first;
+                if (pKFi->isBad() || pKFi->mnId > maxKFid)
+                    continue;
+                const auto &kpUn = pKFi->mvKeysUn[ob.second];
+                const auto it = row.find(pKFi);
+                const bool has_sigma = kpUn.octave >= 0 && (size_t)kpUn.octave < pKFi->mvInvLevelSigma2.size();
+                edge_kf.push_back(pKFi), edge_mp.push_back(pMP);
+                edge_point.push_back((int32_t)j), edge_pose.push_back(it == row.end() ? -1 : it->second);
+                edge_octave.push_back(has_sigma ? kpUn.octave : -1);
+                edge_xy.push_back(kpUn.pt.x), edge_xy.push_back(kpUn.pt.y), edge_ur.push_back(pKFi->mvuRight[ob.second]);
+            }
+        }
+    }
+
+    // the host part of the library's problem; valid while the graph lives
+    orbgpu_bundle_adjustment_problem Problem(int nIterations, bool bRobust) const
+    {
+        orbgpu_bundle_adjustment_problem p;
+        std::memset(&p, 0, sizeof(p));
+        p.n_poses = (int32_t)rows.size(), p.n_points = (int32_t)points.size(), p.n_edges = (int32_t)edge_point.size();
+        p.nlevels = nlevels, p.n_iterations = nIterations, p.robust = bRobust ? 1 : 0;
+        p.Tcw = Tcw.data(), p.fixed = fixed_flag.data(), p.cam = cam.data(), p.inv_level_sigma2 = inv_sigma2.data();
+        p.world_pos = world_pos.data(), p.edge_point = edge_point.data(), p.edge_pose = edge_pose.data();
+        p.edge_octave = edge_octave.data(), p.edge_xy = edge_xy.data(), p.edge_u_right = edge_ur.data();
+        return p;
+    }
+};
+
 template <typename FrameT, typename MapPointT> class OptimizerT {
   public:
     // host arrays: one upload per call
@@ -1337,6 +1416,82 @@ template <typename FrameT, typename MapPointT> class OptimizerT {
                                [&access](MapPointT *q) { return access.min_dist(q); },
                                [&access](MapPointT *q) { return access.max_dist(q); });
         }
+    }
+
+    // Optimizer::BundleAdjustment (include/Optimizer.h:41, src/Optimizer.cc:49-237): every key frame of vpKFs and every
+    // point of vpMP in one optimize(nIterations).  Write-back as :190-235: with nLoopKF == 0 SetPose of every key frame
+    // that is not bad, SetWorldPos + UpdateNormalAndDepth of every point that is not bad and was included (and the table's
+    // batched SetWorldPos); otherwise set_pose_gba / set_world_pos_gba (mTcwGBA, mPosGBA) and mnBAGlobalForKF = nLoopKF on
+    // both.  Not-included and bad entries are skipped.  The flag is sampled once, at the call, as for
+    // LocalBundleAdjustment; when it is set nothing is written back (the reference's optimize(0 iterations) would write
+    // the quaternion round trip of every estimate).  The spanning-tree propagation of LoopClosing.cc:672-733 walks
+    // pointers and stays with the caller.  The conventions are B1-B7 of include/orbgpu.h ("g2o unpinned").  KeyFrameT
+    // needs mnId, mnBAGlobalForKF, isBad(), mvKeysUn, mvuRight, mvInvLevelSigma2, fx, fy, cx, cy, mbf; MapPointT
+    // mnBAGlobalForKF, isBad(), GetObservations(), UpdateNormalAndDepth().  access: pose, world_pos, set_pose,
+    // set_world_pos as for LocalBundleAdjustment, plus set_pose_gba(pKF, T) and set_world_pos_gba(pMP, x); with a table
+    // also normal, min_dist, max_dist.  Beyond the library's capacities (ORBGPU_BA_MAX_*) the call throws: the caller
+    // keeps its g2o path for such maps.
+    template <typename KeyFrameT, typename Access>
+    static void BundleAdjustment(const std::vector<KeyFrameT *> &vpKFs, const std::vector<MapPointT *> &vpMP, int nIterations,
+                                 bool *pbStopFlag, const unsigned long nLoopKF, const bool bRobust, Access access,
+                                 MapPointTableT<MapPointT> *table = nullptr, int device_id = 0,
+                                 orbgpu_bundle_adjustment_result *result = nullptr)
+    {
+        const FullBAGraph<KeyFrameT, MapPointT> g(vpKFs, vpMP, access);
+        const orbgpu_bundle_adjustment_problem p = g.Problem(nIterations, bRobust);
+        const size_t P = g.rows.size(), M = g.points.size();
+        std::vector<float> T(16 * P + 16), X(3 * M + 3);
+        std::vector<uint8_t> not_included(M + 1, 0);
+        const int32_t stop = pbStopFlag && *pbStopFlag ? 1 : 0;
+        orbgpu_bundle_adjustment_result r;
+        check(orbgpu_bundle_adjustment(&p, pbStopFlag ? &stop : nullptr, nullptr, T.data(), nullptr, X.data(), not_included.data(),
+                                       &r, device_id),
+              "Optimizer::BundleAdjustment");
+        if (result)
+            *result = r;
+        if (r.stopped)
+            return;
+        for (size_t i = 0; i < P; i++) {
+            if (g.rows[i]->isBad())
+                continue;
+            if (nLoopKF == 0) {
+                access.set_pose(g.rows[i], &T[16 * i]);
+            } else {
+                access.set_pose_gba(g.rows[i], &T[16 * i]);
+                g.rows[i]->mnBAGlobalForKF = nLoopKF;
+            }
+        }
+        std::vector<MapPointT *> moved;
+        for (size_t j = 0; j < M; j++) {
+            if (not_included[j] || g.points[j]->isBad())
+                continue;
+            if (nLoopKF == 0) {
+                access.set_world_pos(g.points[j], &X[3 * j]);
+                g.points[j]->UpdateNormalAndDepth();
+                moved.push_back(g.points[j]);
+            } else {
+                access.set_world_pos_gba(g.points[j], &X[3 * j]);
+                g.points[j]->mnBAGlobalForKF = nLoopKF;
+            }
+        }
+        if (table && !moved.empty())
+            table->SetWorldPos(moved, [&access](MapPointT *q) { return access.world_pos(q); },
+                               [&access](MapPointT *q) { return access.normal(q); },
+                               [&access](MapPointT *q) { return access.min_dist(q); },
+                               [&access](MapPointT *q) { return access.max_dist(q); });
+    }
+
+    // Optimizer::GlobalBundleAdjustemnt (Optimizer.cc:41-46, spelt as there): BundleAdjustment over pMap->GetAllKeyFrames()
+    // and pMap->GetAllMapPoints().  Tracking.cc:963 calls it with (mpMap, 20), LoopClosing.cc:647 with
+    // (mpMap, 20, &mbStopGBA, nLoopKF, false).
+    template <typename MapT, typename Access>
+    static void GlobalBundleAdjustemnt(MapT *pMap, int nIterations, bool *pbStopFlag, const unsigned long nLoopKF, const bool bRobust,
+                                       Access access, MapPointTableT<MapPointT> *table = nullptr, int device_id = 0,
+                                       orbgpu_bundle_adjustment_result *result = nullptr)
+    {
+        const auto vpKFs = pMap->GetAllKeyFrames();
+        const std::vector<MapPointT *> vpMP = pMap->GetAllMapPoints();
+        BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust, access, table, device_id, result);
     }
 };
 

@@ -115,10 +115,25 @@ def reference(sc, n_perm, key=None):
     return out
 
 
+LBA_COUNTERS = ("n_edges", "n_erased", "rounds", "stopped", "n_bad_index", "iterations", "trials")
+
+
+def _erase_wanted(m):
+    return np.where(m["erase"] == 255, SENTINEL, m["erase"]).astype(np.uint8)
+
+
 def compare(scenes, got, n_perm=3, keys=None):
     """Model vs device for a set of scenes.  Returns a dict: compared, left_out, mismatches (list of strings), spread_pose /
     spread_point (largest model deviation under permuted summation order), dev_pose / dev_point (largest device
     deviation from the model), float_ulp."""
+    return compare_by_rule(scenes, got, reference, LBA_COUNTERS, "erase", "erase flags", _erase_wanted, n_perm, keys)
+
+
+def compare_by_rule(scenes, got, reference, counters, flags, flags_label, flags_wanted, n_perm=3, keys=None):
+    """The one text of the comparison rule, for any optimiser whose model returns poses, points and a byte array of flags.
+    reference(sc, n_perm, key) -> (model result, spread of the poses, of the points, stable); counters: the result members
+    compared exactly; flags: the name of the byte array, flags_label what a mismatch calls it, flags_wanted(model result)
+    the bytes the device has to return."""
     rep = {"compared": 0, "left_out": 0, "mismatches": [], "spread_pose": 0.0, "spread_point": 0.0, "dev_pose": 0.0,
            "dev_point": 0.0, "float_ulp": 0}
     kept = []
@@ -132,12 +147,12 @@ def compare(scenes, got, n_perm=3, keys=None):
         kept.append((i, m, r, a))
     for i, m, r, a in kept:
         tag = "scene %d (%d edges): " % (i, m["n_edges"])
-        for k in ("n_edges", "n_erased", "rounds", "stopped", "n_bad_index", "iterations", "trials"):
+        for k in counters:
             if r[k] != m[k]:
                 rep["mismatches"].append(tag + "%s %r, model %r" % (k, r[k], m[k]))
-        want = np.where(m["erase"] == 255, SENTINEL, m["erase"]).astype(np.uint8)
-        if not np.array_equal(a["erase"], want):
-            rep["mismatches"].append(tag + "%d erase flags differ" % int((a["erase"] != want).sum()))
+        want = flags_wanted(m)
+        if not np.array_equal(a[flags], want):
+            rep["mismatches"].append(tag + "%d %s differ" % (int((a[flags] != want).sum()), flags_label))
         for what, dk, fk, sk in (("pose", "Tcw_d", "Tcw", "spread_pose"), ("point", "pos_d", "pos", "spread_point")):
             dev = _dev(a[dk], m[dk])
             rep["dev_" + what] = max(rep["dev_" + what], dev)
