@@ -844,6 +844,127 @@ int orbgpu_bundle_adjustment(const orbgpu_bundle_adjustment_problem *p, const in
  * limit of 28 free poses and the same ORBGPU_DEBUG_LBA_LDS_POSES). */
 int orbgpu_bundle_adjustment_last_spills(int32_t device_id, int32_t *problems_spilled);
 
+/* ---- Optimizer::OptimizeEssentialGraph (Optimizer.cc:780-1045): the Sim3 pose graph of a loop closure on the device --------
+ * The step of LoopClosing::CorrectLoop (LoopClosing.cc:565) that spreads a detected loop's correction over every key frame
+ * and every map point: one 7-DoF vertex per key frame, one EdgeSim3 per loop connection, spanning-tree edge, old loop edge
+ * and strong covisibility edge, Levenberg-Marquardt over a sparse system of 7 rows per key frame.  g2o is not part of the
+ * reference tree: its behaviour (OptimizationAlgorithmLevenberg with setUserLambdaInit(1e-16) over BlockSolver_7_3,
+ * VertexSim3Expmap, EdgeSim3, Sim3::log) is restated, NOT read ("g2o unpinned"); tests/eg_model.py is the float64
+ * restatement every result is compared with.  All arithmetic is IEEE double, unfused, three-term sums left to right.  Where
+ * a rule says "as Ok", "as Lk" or "as Bk", nothing differs from that section:
+ *   G1 problem             V vertex rows, each with two Sim3 states of 8 doubles (qx, qy, qz, qw, tx, ty, tz, s): Scw[v] is the
+ *                          entry estimate -- CorrectedSim3[pKF] if present, else Sim3(Rcw, tcw, 1) (:818-832) -- and Snc[v] is
+ *                          NonCorrectedSim3[pKF] if present, else Scw[v].  States are used as given: nothing is normalised
+ *                          on entry or after an update (O4).  fixed[v] is a mask (the reference fixes pLoopKF only; any mask
+ *                          is taken).  E edges (i, j, kind): the measurement is Scw[j] * Scw[i]^-1 for kind 0 (the loop
+ *                          connections of :852-880) and Snc[j] * Snc[i]^-1 for any other kind (spanning tree, old loop
+ *                          edges and covisibility, :883-983).  WHICH edges exist (minFeat, sInsertedEdges, the parent /
+ *                          child / loop-edge exclusions, the mnId order) is pointer walking and stays with the caller.
+ *                          orbgpu_sim3_from_pose gives Sim3(Rcw, tcw, 1) of a float pose: O9's Smw.
+ *   G2 Sim3 algebra        S X = s (R X) + t with R the matrix of the quaternion as it is (O3);
+ *                          A * B = (qa qb, sa (Ra tb) + ta, sa sb); S^-1 = (q conjugate, R'((-1 / s) t), 1 / s).
+ *   G3 log(S)              g2o's published branches, recalled, not read, in the style of O5: sigma = log(s),
+ *                          d = 0.5 (R00 + R11 + R22 - 1), dR = (R21 - R12, R02 - R20, R10 - R01), eps = 1e-5;
+ *                          d > 1 - eps: omega = 0.5 dR; otherwise theta = acos(d), omega = (theta / (2 sqrt(1 - d d))) dR.
+ *                          C, A and B are O5's four cases with the test theta < eps replaced by d > 1 - eps and s_x by s;
+ *                          W = (A Om + B Om Om) + C I; upsilon = W^-1 t by 3x3 LU with partial pivoting (column by column a
+ *                          later row is swapped in when its entry is strictly larger in magnitude: row 1 against 0, 2
+ *                          against 0, then 2 against 1); the result is (omega, upsilon, sigma).  B of the small-angle,
+ *                          |sigma| >= eps case is kept as published, ((sigma^2 / 2 - sigma + 1) s) / sigma^3, although it is
+ *                          not the limit of the general case; with fix_scale the scale stays exactly 1,
+ *                          sigma is exactly 0 and that case is never entered.
+ *   G4 edge (EdgeSim3)     e = log((M * S_i) * S_j^-1), a 7-vector; i is vertex 0, j is vertex 1.  Information is the
+ *                          identity, chi2 = e'e summed left to right, no robust kernel.
+ *   G5 Jacobians           numeric, as O6: per non-fixed end vertex, per k = 0..6,
+ *                          (e(exp(+d 1_k) S) - e(exp(-d 1_k) S)) (1 / (2 d)) with d = 1e-9, through O4 / O5's update; with
+ *                          fix_scale x[6] is set to 0 before exp, so column 6 is exactly 0.  A fixed vertex has no Jacobian.
+ *   G6 system              H is block-symmetric with 7x7 blocks over the free ACTIVE vertices; a vertex is active when it has
+ *                          at least one taken edge.  H_ii += Ji'Ji, H_jj += Jj'Jj, H_ij += Ji'Jj, b_i -= Ji'e, b_j -= Jj'e,
+ *                          each product summed over the 7 error rows in turn.  An edge with one fixed end feeds the other
+ *                          end's diagonal block and b only; an edge between two fixed vertices feeds chi2 only; parallel
+ *                          edges accumulate; an inactive vertex keeps its estimate and has no rows.
+ *   G7 solve               (H + lambda I) x = b by LL' over the envelope of H in a reverse Cuthill-McKee order chosen on the
+ *                          host (csrc/skyline.h).  A pivot that is not > 0 fails the trial and x = 0.
+ *                          Vertex <- exp(x_v) vertex by O4.
+ *   G8 optimize            ONE optimize(n_iterations), 0 <= n_iterations <= ORBGPU_EG_MAX_ITERATIONS (the reference passes
+ *                          20): the Levenberg-Marquardt loop of orbgpu_pose_optimization (nu, at most 10 trials, the rho rule
+ *                          with scale x'(lambda x + b) + 1e-3, the same termination rules) with lambda0 = 1e-16, a constant
+ *                          (:794), and no kernel.  n_iterations == 0 writes the inputs through G10 with
+ *                          iterations = trials = 0 and chi2_start = chi2_end = the chi2 of the input.
+ *   G9 stop flag           as B5.  The reference has none here; the member exists so that a caller can abandon a long solve.
+ *   G10 poses out (:992-1010)  per vertex the optimised state Siw_d[8] and Tiw[16]: (float) of R and of t * (1 / s), last
+ *                          row 0 0 0 1 (Converter::toCvSE3 of eigR, eigt / s).  Fixed and inactive rows get their input
+ *                          state through the same formula.
+ *   G11 points out (:1013-1043)  M points with a float world position and a vertex row r[m] (the caller resolves
+ *                          mnCorrectedByKF / mnCorrectedReference / GetReferenceKeyFrame):
+ *                          out = (float)(Siw_opt[r]^-1 map (Scw[r] map (double)P)) by G2.  A row outside [0, V) leaves the
+ *                          point as it came and is counted in n_bad_ref.
+ *   G12 determinism, range as L10: every sum over edges is a per-vertex or per-block list in edge order, or per-lane
+ *                          partials plus a fixed tree; no floating-point atomics; the same problem gives the same bytes on
+ *                          every run, alone or anywhere in a batch.  An edge with i == j or with an end outside [0, V) is
+ *                          skipped, counted in n_bad_index and never read through.
+ * Capacities: a first choice, like LBA's.  Anything larger is EINVAL; there is no CPU fallback: the caller
+ * keeps its g2o path. */
+#define ORBGPU_EG_MAX_VERTICES 8192
+#define ORBGPU_EG_MAX_EDGES (1 << 18)
+#define ORBGPU_EG_MAX_POINTS (1 << 22)
+#define ORBGPU_EG_MAX_ENVELOPE (1 << 26) /* doubles of factor storage */
+#define ORBGPU_EG_MAX_ITERATIONS 100
+
+typedef struct orbgpu_essential_graph_result { /* device or host, 8-byte aligned */
+    double chi2_start, chi2_end; /* chi2 of the taken edges at the input and at the kept end */
+    int32_t iterations, trials;  /* LM iterations and trials */
+    int32_t stopped;             /* the stop flag was seen non-zero */
+    int32_t n_edges;             /* edges taken (E less the skipped ones) */
+    int32_t n_bad_index;         /* edges skipped: i == j or an end outside [0, V) */
+    int32_t n_free_active;       /* vertices with rows in H */
+    int32_t envelope;            /* doubles of the factor's envelope */
+    int32_t bandwidth;           /* the longest row of the envelope, diagonal included, in scalars */
+    int32_t n_bad_ref;           /* points left alone for a row outside [0, V) (host flavour; G11) */
+    int32_t pad_;
+} orbgpu_essential_graph_result;
+
+typedef struct orbgpu_essential_graph_problem {
+    int32_t n_vertices, n_edges;
+    int32_t n_iterations;        /* 0 .. ORBGPU_EG_MAX_ITERATIONS */
+    int32_t fix_scale;           /* non-zero: bFixScale (stereo / RGB-D) */
+    const double *Scw;           /* HOST [n_vertices][8] */
+    const double *Snc;           /* HOST [n_vertices][8] */
+    const uint8_t *fixed;        /* HOST [n_vertices] */
+    const int32_t *edge_i, *edge_j, *edge_kind; /* HOST [n_edges] */
+    const int32_t *d_stop;       /* device or NULL */
+    double *d_Siw_d;             /* device [n_vertices][8] */
+    float *d_Tiw;                /* device [n_vertices][16] */
+    orbgpu_essential_graph_result *d_result; /* device */
+} orbgpu_essential_graph_problem;
+
+/* Sim3(Rcw, tcw, 1) of a float pose as 8 doubles: quat_normalize(quat_from_matrix((double)R)), (double)t, 1.  Host only. */
+int orbgpu_sim3_from_pose(const float *Tcw, double *out);
+/* Enqueued on hip_stream, not synchronised, under orbgpu_bundle_adjustment_device's rules: every HOST array is read, and the
+ * index structure (the taken edges, the reverse Cuthill-McKee order, the envelope layout, the per-block edge lists) is built
+ * and uploaded, before the call returns; calls of one host thread share a workspace of their own and must be ordered on one
+ * stream.  EINVAL: null pointers, negative counts, n_iterations outside [0, ORBGPU_EG_MAX_ITERATIONS], more than
+ * ORBGPU_EG_MAX_* of anything, an envelope above ORBGPU_EG_MAX_ENVELOPE (all found before a device is touched); EHIP without
+ * a device.  The batch form is ONE launch, one workgroup per problem, which runs every iteration and trial without returning
+ * to the host. */
+int orbgpu_essential_graph_device(const orbgpu_essential_graph_problem *p, int32_t device_id, void *hip_stream);
+int orbgpu_essential_graph_batch_device(int32_t n, const orbgpu_essential_graph_problem *problems, int32_t device_id,
+                                        void *hip_stream);
+/* G11 alone, over device arrays, enqueued on hip_stream: d_Scw / d_Siw [n_vertices][8] (the entry states and
+ * orbgpu_essential_graph_device's d_Siw_d), d_pos_in / d_pos_out [n_points][3] (they may be the same array), d_ref
+ * [n_points].  d_n_bad_ref: device int32 the call ADDS its count to, or NULL.  EINVAL: null pointers, negative counts, more
+ * than ORBGPU_EG_MAX_VERTICES / ORBGPU_EG_MAX_POINTS. */
+int orbgpu_essential_graph_correct_points_device(int32_t n_vertices, const double *d_Scw, const double *d_Siw, int32_t n_points,
+                                                 const float *d_pos_in, const int32_t *d_ref, float *d_pos_out,
+                                                 int32_t *d_n_bad_ref, int32_t device_id, void *hip_stream);
+/* Host arrays, synchronises: the d_* members of p are not read.  Siw_d [n_vertices][8] (may be NULL) and Tiw
+ * [n_vertices][16] are in/out (a call stopped at once leaves them alone).  n_points points (world_pos [n_points][3],
+ * point_ref [n_points], HOST) are corrected on the same stream after the optimiser into pos_out [n_points][3], which may be
+ * world_pos; a call stopped at once corrects nothing.  stop: HOST int32 sampled at the call, or NULL; result may be NULL. */
+int orbgpu_essential_graph(const orbgpu_essential_graph_problem *p, const int32_t *stop, double *Siw_d, float *Tiw,
+                           int32_t n_points, const float *world_pos, const int32_t *point_ref, float *pos_out,
+                           orbgpu_essential_graph_result *result, int32_t device_id);
+
 /* ---- Sim3Solver (Sim3Solver.cc, Horn 1987 + RANSAC): the Sim3 of a loop candidate on the device --------------------------
  * The second of the five steps of LoopClosing::ComputeSim3 (LoopClosing.cc:236-343); its result is the R12 / t12 / s12 that
  * orbgpu_search_by_sim3 takes.  All hypotheses of a candidate are evaluated at once, one wave each; the reference's

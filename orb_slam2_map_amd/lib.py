@@ -160,6 +160,24 @@ class BundleAdjustmentProblem(C.Structure):
 BA_MAX_POSES, BA_MAX_FREE, BA_MAX_POINTS, BA_MAX_EDGES, BA_MAX_ITERATIONS = 1024, 256, 65536, 1 << 20, 100
 
 
+class EssentialGraphResult(C.Structure):
+    _fields_ = [("chi2_start", C.c_double), ("chi2_end", C.c_double)] + \
+               [(k, C.c_int32) for k in ("iterations", "trials", "stopped", "n_edges", "n_bad_index", "n_free_active",
+                                         "envelope", "bandwidth", "n_bad_ref", "pad_")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
+class EssentialGraphProblem(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_vertices", "n_edges", "n_iterations", "fix_scale")] + \
+               [(k, C.c_void_p) for k in ("Scw", "Snc", "fixed", "edge_i", "edge_j", "edge_kind", "d_stop", "d_Siw_d", "d_Tiw",
+                                          "d_result")]
+
+
+EG_MAX_VERTICES, EG_MAX_EDGES, EG_MAX_POINTS, EG_MAX_ENVELOPE, EG_MAX_ITERATIONS = 8192, 1 << 18, 1 << 22, 1 << 26, 100
+
+
 class Sim3Result(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n", "max_its", "n_bad_index", "n_bad_triple", "accepted", "n_inliers",
                                          "best_inliers", "best_iteration", "iterations", "no_more")]
@@ -306,6 +324,8 @@ ABI_SYMBOLS = [
     "orbgpu_local_ba", "orbgpu_local_ba_device", "orbgpu_local_ba_batch_device", "orbgpu_local_ba_last_spills",
     "orbgpu_bundle_adjustment", "orbgpu_bundle_adjustment_device", "orbgpu_bundle_adjustment_batch_device",
     "orbgpu_bundle_adjustment_last_spills",
+    "orbgpu_essential_graph", "orbgpu_essential_graph_device", "orbgpu_essential_graph_batch_device",
+    "orbgpu_essential_graph_correct_points_device", "orbgpu_sim3_from_pose",
     "orbgpu_sim3_ransac_iterations", "orbgpu_sim3_solve_device", "orbgpu_sim3_solve_batch_device", "orbgpu_sim3_solve",
     "orbgpu_sim3_solve_all",
     "orbgpu_sim3_optimize", "orbgpu_sim3_optimize_device", "orbgpu_sim3_optimize_batch_device",
@@ -1247,6 +1267,90 @@ def bundle_adjustment_last_spills(device_id=0):
     v = C.c_int32()
     check(L.orbgpu_bundle_adjustment_last_spills(device_id, C.byref(v)))
     return v.value
+
+
+_EG_HOST = (("Scw", np.float64), ("Snc", np.float64), ("fixed", np.uint8), ("edge_i", np.int32), ("edge_j", np.int32),
+            ("edge_kind", np.int32))
+_EG_PTRS = ("d_stop", "d_Siw_d", "d_Tiw", "d_result")
+
+
+def essential_graph_problem(p, keep):
+    """An EssentialGraphProblem from a dict: Scw, Snc [V][8] (qx, qy, qz, qw, tx, ty, tz, s), fixed [V], edge_i / edge_j /
+    edge_kind [E] (host arrays), n_iterations (default 20), fix_scale (default False) and the device pointers d_stop (or
+    None), d_Siw_d ([V][8]), d_Tiw ([V][16]), d_result (holds an EssentialGraphResult).  The counts follow the arrays
+    unless the dict names them (n_vertices, n_edges); keep takes the host arrays the structure points to."""
+    q = EssentialGraphProblem()
+    a = {k: np.ascontiguousarray(p[k], t) for k, t in _EG_HOST}
+    keep.append(a)
+    q.n_vertices = int(p.get("n_vertices", a["Scw"].size // 8))
+    q.n_edges = int(p.get("n_edges", a["edge_i"].size))
+    q.n_iterations, q.fix_scale = int(p.get("n_iterations", 20)), int(bool(p.get("fix_scale", False)))
+    for k, _ in _EG_HOST:
+        setattr(q, k, a[k].ctypes.data if a[k].size else None)
+    _set_pointers(q, p, _EG_PTRS)
+    return q
+
+
+def essential_graph_batch_device(problems, stream=0, device_id=0):
+    """n independent Optimizer::OptimizeEssentialGraph problems in ONE launch (orbgpu_essential_graph_batch_device);
+    enqueued, not synchronised.  problems: dicts as essential_graph_problem takes them."""
+    keep = []
+    _batch_device("essential_graph", EssentialGraphProblem, lambda p: essential_graph_problem(p, keep), problems, stream,
+                  device_id)
+
+
+def essential_graph_device(problem, stream=0, device_id=0):
+    """One problem (orbgpu_essential_graph_device); see essential_graph_batch_device."""
+    keep = []
+    _one_device("essential_graph", essential_graph_problem(problem, keep), stream, device_id)
+
+
+def essential_graph_correct_points_device(n_vertices, d_Scw, d_Siw, n_points, d_pos_in, d_ref, d_pos_out, d_n_bad_ref=None,
+                                          stream=0, device_id=0):
+    """G11 alone over device pointers (orbgpu_essential_graph_correct_points_device); enqueued, not synchronised."""
+    L = lib()
+    L.orbgpu_essential_graph_correct_points_device.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    check(L.orbgpu_essential_graph_correct_points_device(int(n_vertices), d_Scw or None, d_Siw or None, int(n_points),
+                                                         d_pos_in or None, d_ref or None, d_pos_out or None,
+                                                         d_n_bad_ref or None, device_id, stream))
+
+
+def essential_graph(problem, stop=None, Siw_d=None, Tiw=None, world_pos=None, point_ref=None, pos_out=None, device_id=0):
+    """Optimizer::OptimizeEssentialGraph over host arrays (orbgpu_essential_graph); problem: the host part of the dict
+    essential_graph_problem takes.  stop: None or an int sampled at the call.  world_pos [M][3] / point_ref [M]: the map
+    points to correct (G11), or None.  The outputs start from the arrays given (zeros by default; pos_out from world_pos):
+    a call stopped at once leaves them as they were.  Returns (Siw_d [V][8], Tiw [V][4][4], pos [M][3], result dict)."""
+    keep = []
+    q = essential_graph_problem(problem, keep)
+    V = q.n_vertices
+    X = np.zeros((0, 3), np.float32) if world_pos is None else np.ascontiguousarray(world_pos, np.float32).reshape(-1, 3)
+    M = len(X)
+    ref = np.ascontiguousarray(np.zeros(0) if point_ref is None else point_ref, np.int32)
+    if len(ref) != M:
+        raise ValueError("point_ref must have one entry per point")
+
+    def start(a, shape, t):
+        return np.zeros(shape, t) if a is None else np.array(a, t).reshape(shape).copy()
+    Sd, T = start(Siw_d, (max(V, 1), 8), np.float64), start(Tiw, (max(V, 1), 4, 4), np.float32)
+    out = start(X if pos_out is None and M else pos_out, (max(M, 1), 3), np.float32)
+    sv = None if stop is None else C.c_int32(int(stop))
+    res = EssentialGraphResult()
+    L = lib()
+    L.orbgpu_essential_graph.argtypes = [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32]
+    check(L.orbgpu_essential_graph(C.byref(q), None if sv is None else C.byref(sv), _p(Sd), _p(T), M, _p(X) if M else None,
+                                   _p(ref) if M else None, _p(out) if M else None, C.byref(res), device_id))
+    return Sd[:V], T[:V], out[:M], res.as_dict()
+
+
+def sim3_from_pose(Tcw):
+    """Sim3(Rcw, tcw, 1) of a float pose as 8 doubles (orbgpu_sim3_from_pose; host only, needs no device)."""
+    L = lib()
+    L.orbgpu_sim3_from_pose.argtypes = [C.c_void_p, C.c_void_p]
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+    out = np.zeros(8, np.float64)
+    check(L.orbgpu_sim3_from_pose(_p(T), _p(out)))
+    return out
 
 
 def sim3_ransac_iterations(n, probability, min_inliers, max_iterations):

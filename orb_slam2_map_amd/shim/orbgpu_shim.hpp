@@ -1241,6 +1241,128 @@ template <typename KeyFrameT, typename MapPointT> struct FullBAGraph {
     }
 };
 
+// The graph of Optimizer::OptimizeEssentialGraph (Optimizer.cc:796-983) as orbgpu_essential_graph takes it (G1).  Vertex
+// rows: pMap->GetAllKeyFrames() in order without the bad ones; Scw[v] = CorrectedSim3[pKF] if present, else Sim3(Rcw, tcw, 1)
+// of its pose (:818-832); Snc[v] = NonCorrectedSim3[pKF] if present, else Scw[v] -- which is what every "find in
+// NonCorrectedSim3, else vScw" of :894-967 reads; fixed iff pKF == pLoopKF.  Edges in the reference's order: first the loop
+// connections (kind 0, :852-880), then per key frame its spanning-tree edge, its older loop edges and its strong
+// covisibility edges (kind 1, :883-983); i is vertex 0 (the key frame the loop is over), j vertex 1.  A key frame that is
+// in no row (a bad one: the reference reads through a null vertex there) keeps its edge with row -1: the library skips
+// and counts it.  Point rows: pMap->GetAllMapPoints() without the bad ones, each with the row of mnCorrectedReference if
+// pCurKF corrected it, else of its reference key frame (:1023-1032); -1 when that key frame has no row.
+template <typename KeyFrameT, typename MapPointT> struct EssentialGraphT {
+    std::vector<KeyFrameT *> rows;
+    std::vector<MapPointT *> points;
+    std::vector<double> Scw, Snc;
+    std::vector<uint8_t> fixed_flag;
+    std::vector<int32_t> edge_i, edge_j, edge_kind, point_ref;
+    std::vector<float> world_pos;
+    std::map<unsigned long, int32_t> row_of_id;
+
+    int32_t Row(unsigned long id) const
+    {
+        const auto it = row_of_id.find(id);
+        return it == row_of_id.end() ? -1 : it->second;
+    }
+
+    template <typename MapT, typename PoseMap, typename Connections, typename Access>
+    EssentialGraphT(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const PoseMap &NonCorrectedSim3,
+                    const PoseMap &CorrectedSim3, const Connections &LoopConnections, Access &access)
+    {
+        const auto vpKFs = pMap->GetAllKeyFrames();
+        const auto vpMPs = pMap->GetAllMapPoints();
+        const int minFeat = 100;
+        auto put = [](std::vector<double> &to, const Sim3 &S) {
+            to.insert(to.end(), S.r, S.r + 4), to.insert(to.end(), S.t, S.t + 3), to.push_back(S.s);
+        };
+        // Set KeyFrame vertices
+        for (KeyFrameT *pKF : vpKFs) {
+            if (pKF->isBad())
+                continue;
+            row_of_id[pKF->mnId] = (int32_t)rows.size();
+            rows.push_back(pKF);
+            const auto it = CorrectedSim3.find(pKF);
+            if (it != CorrectedSim3.end()) {
+                put(Scw, it->second);
+            } else {
+                double S[8];
+                check(orbgpu_sim3_from_pose(access.pose(pKF), S), "Optimizer::OptimizeEssentialGraph");
+                Scw.insert(Scw.end(), S, S + 8);
+            }
+            const auto itn = NonCorrectedSim3.find(pKF);
+            if (itn != NonCorrectedSim3.end())
+                put(Snc, itn->second);
+            else
+                Snc.insert(Snc.end(), Scw.end() - 8, Scw.end());
+            fixed_flag.push_back(pKF == pLoopKF);
+        }
+        auto edge = [this](unsigned long idi, unsigned long idj, int kind) {
+            edge_i.push_back(Row(idi)), edge_j.push_back(Row(idj)), edge_kind.push_back(kind);
+        };
+        std::set<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+        // Set Loop edges
+        for (const auto &mit : LoopConnections) {
+            KeyFrameT *pKF = mit.first;
+            const unsigned long nIDi = pKF->mnId;
+            for (KeyFrameT *pKFj : mit.second) {
+                const unsigned long nIDj = pKFj->mnId;
+                if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(pKFj) < minFeat)
+                    continue;
+                edge(nIDi, nIDj, 0);
+                sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+            }
+        }
+        // Set normal edges
+        for (KeyFrameT *pKF : vpKFs) {
+            const unsigned long nIDi = pKF->mnId;
+            KeyFrameT *pParentKF = pKF->GetParent();
+            if (pParentKF)  // Spanning tree edge
+                edge(nIDi, pParentKF->mnId, 1);
+            const auto sLoopEdges = pKF->GetLoopEdges();  // Loop edges
+            for (KeyFrameT *pLKF : sLoopEdges)
+                if (pLKF->mnId < pKF->mnId)
+                    edge(nIDi, pLKF->mnId, 1);
+            const auto vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);  // Covisibility graph edges
+            for (KeyFrameT *pKFn : vpConnectedKFs) {
+                if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
+                    if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+                        if (sInsertedEdges.count(std::make_pair(std::min<unsigned long>(pKF->mnId, pKFn->mnId),
+                                                                std::max<unsigned long>(pKF->mnId, pKFn->mnId))))
+                            continue;
+                        edge(nIDi, pKFn->mnId, 1);
+                    }
+                }
+            }
+        }
+        // the points and the row each is corrected through
+        for (MapPointT *pMP : vpMPs) {
+            if (pMP->isBad())
+                continue;
+            points.push_back(pMP);
+            const float *x = access.world_pos(pMP);
+            world_pos.insert(world_pos.end(), x, x + 3);
+            if (pMP->mnCorrectedByKF == pCurKF->mnId) {
+                point_ref.push_back(Row(pMP->mnCorrectedReference));
+            } else {
+                KeyFrameT *pRefKF = pMP->GetReferenceKeyFrame();
+                point_ref.push_back(pRefKF ? Row(pRefKF->mnId) : -1);
+            }
+        }
+    }
+
+    // the host part of the library's problem; valid while the graph lives
+    orbgpu_essential_graph_problem Problem(bool bFixScale, int nIterations = 20) const
+    {
+        orbgpu_essential_graph_problem p;
+        std::memset(&p, 0, sizeof(p));
+        p.n_vertices = (int32_t)rows.size(), p.n_edges = (int32_t)edge_i.size();
+        p.n_iterations = nIterations, p.fix_scale = bFixScale ? 1 : 0;
+        p.Scw = Scw.data(), p.Snc = Snc.data(), p.fixed = fixed_flag.data();
+        p.edge_i = edge_i.data(), p.edge_j = edge_j.data(), p.edge_kind = edge_kind.data();
+        return p;
+    }
+};
+
 template <typename FrameT, typename MapPointT> class OptimizerT {
   public:
     // host arrays: one upload per call
@@ -1492,6 +1614,53 @@ template <typename FrameT, typename MapPointT> class OptimizerT {
         const auto vpKFs = pMap->GetAllKeyFrames();
         const std::vector<MapPointT *> vpMP = pMap->GetAllMapPoints();
         BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust, access, table, device_id, result);
+    }
+
+    // Optimizer::OptimizeEssentialGraph (include/Optimizer.h:52, src/Optimizer.cc:781-1044): the Sim3 pose graph of
+    // LoopClosing::CorrectLoop (LoopClosing.cc:565) over every key frame of the map, optimize(20), then SetPose of every key
+    // frame with [R t / s; 0 1] (:992-1010) and SetWorldPos + UpdateNormalAndDepth of every point that is not bad, moved
+    // through its reference row (:1013-1043).  The edge gathering of :847-983 is EssentialGraphT's, statement for
+    // statement; NonCorrectedSim3 / CorrectedSim3 are LoopClosing::KeyFrameAndPose with the stand-in Sim3 above in the place
+    // of g2o::Sim3 (a std::map<KeyFrameT *, Sim3> or anything with its find / end), LoopConnections the map<KeyFrame *,
+    // set<KeyFrame *>> of :556.  The reference has no stop flag here (G9): none is passed.  A point whose reference key
+    // frame has no row is left as it came (the reference would read vScw of a bad key frame's id).  The caller holds
+    // pMap->mMutexMapUpdate for the write-back, as :990 does.  The conventions are G1-G12 of include/orbgpu.h ("g2o
+    // unpinned").  KeyFrameT needs mnId, isBad(), GetParent(), GetLoopEdges(), GetCovisiblesByWeight(), hasChild(),
+    // GetWeight(); MapPointT isBad(), mnCorrectedByKF, mnCorrectedReference, GetReferenceKeyFrame(), UpdateNormalAndDepth();
+    // access: pose(pKF) (16 floats), world_pos(pMP) (3 floats), set_pose(pKF, T), set_world_pos(pMP, x); with a table also
+    // normal, min_dist, max_dist.  Beyond the library's capacities (ORBGPU_EG_MAX_*, the envelope included) the call
+    // throws: the caller keeps its g2o path for such maps.
+    template <typename MapT, typename KeyFrameT, typename PoseMap, typename Connections, typename Access>
+    static void OptimizeEssentialGraph(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const PoseMap &NonCorrectedSim3,
+                                       const PoseMap &CorrectedSim3, const Connections &LoopConnections, const bool &bFixScale,
+                                       Access access, MapPointTableT<MapPointT> *table = nullptr, int device_id = 0,
+                                       orbgpu_essential_graph_result *result = nullptr)
+    {
+        const EssentialGraphT<KeyFrameT, MapPointT> g(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, access);
+        const orbgpu_essential_graph_problem p = g.Problem(bFixScale);
+        const size_t V = g.rows.size(), M = g.points.size();
+        std::vector<float> T(16 * V + 16), X(g.world_pos);
+        X.resize(3 * M + 3);
+        orbgpu_essential_graph_result r;
+        check(orbgpu_essential_graph(&p, nullptr, nullptr, T.data(), (int32_t)M, X.data(), g.point_ref.data(), X.data(), &r, device_id),
+              "Optimizer::OptimizeEssentialGraph");
+        if (result)
+            *result = r;
+        for (size_t i = 0; i < V; i++)
+            access.set_pose(g.rows[i], &T[16 * i]);
+        std::vector<MapPointT *> moved;
+        for (size_t j = 0; j < M; j++) {
+            if (g.point_ref[j] < 0)
+                continue;
+            access.set_world_pos(g.points[j], &X[3 * j]);
+            g.points[j]->UpdateNormalAndDepth();
+            moved.push_back(g.points[j]);
+        }
+        if (table && !moved.empty())
+            table->SetWorldPos(moved, [&access](MapPointT *q) { return access.world_pos(q); },
+                               [&access](MapPointT *q) { return access.normal(q); },
+                               [&access](MapPointT *q) { return access.min_dist(q); },
+                               [&access](MapPointT *q) { return access.max_dist(q); });
     }
 };
 
