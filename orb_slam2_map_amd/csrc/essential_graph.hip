@@ -15,9 +15,9 @@
 // Memory: everything lives in the call's global workspace -- the envelope of the factor is far larger than LDS for the maps
 // this is for (an LDS-resident variant for small graphs is not written); LDS holds the reduction scratch only.
 //
-// sim3_update below is a second text of sim3_opt.hip's (O4, O5), on 8-double states.  It was not moved into a header:
-// DESIGN.md 9.26 lets shared code move only when the kernels it leaves keep their assembly, this unit must not change
-// k_sim3_opt, and the move was not tried.
+// The Sim3 arithmetic (G2-G5: product, inverse, map, logarithm, edge error, exp(x) * S) is sim3_math.h's, which k_sim3_opt
+// shares; the barrier and the stop flag are opt_math.h's.  The decision on a trial is opt_math.h's lm_trial written out:
+// calling it here cost one row of tools/bench_eg.py more than the parent's spread.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -27,6 +27,7 @@
 #include "carve.h"
 #include "common.h"
 #include "opt_math.h"
+#include "sim3_math.h"
 #include "skyline.h"
 #include "staging.h"
 
@@ -73,250 +74,6 @@ struct EgProblemDev {
     int32_t V, ne, nf, nblk, n_bad_index, n_iterations, fix_scale, bandwidth;
 };
 
-struct WorkgroupBarrier {
-    __device__ void operator()() const { __syncthreads(); }
-};
-
-// the stop flag, read by one lane and broadcast (G9)
-__device__ inline bool stop_requested(const int32_t *stop, int *flag)
-{
-    if (!stop)
-        return false;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        *flag = __hip_atomic_load(stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __syncthreads();
-    return *flag != 0;
-}
-
-// ---- G2 ------------------------------------------------------------------------------------------------------------------
-ORBGPU_HD inline void mat_vec3(const double R[9], const double v[3], double o[3])
-{
-    ORBGPU_UNROLL
-    for (int r = 0; r < 3; r++)
-        o[r] = (R[3 * r] * v[0] + R[3 * r + 1] * v[1]) + R[3 * r + 2] * v[2];
-}
-
-ORBGPU_HD inline void sim3_mul(const double A[8], const double B[8], double o[8])
-{
-    double R[9], Rt[3];
-    quat_mul(A, B, o);
-    quat_to_matrix(A, R);
-    mat_vec3(R, B + 4, Rt);
-    ORBGPU_UNROLL
-    for (int r = 0; r < 3; r++)
-        o[4 + r] = A[7] * Rt[r] + A[4 + r];
-    o[7] = A[7] * B[7];
-}
-
-ORBGPU_HD inline void sim3_inv(const double S[8], double o[8])
-{
-    double R[9];
-    quat_to_matrix(S, R);
-    const double is = 1.0 / S[7];
-    const double u0 = -is * S[4], u1 = -is * S[5], u2 = -is * S[6];
-    o[0] = -S[0], o[1] = -S[1], o[2] = -S[2], o[3] = S[3];
-    ORBGPU_UNROLL
-    for (int r = 0; r < 3; r++)
-        o[4 + r] = (R[r] * u0 + R[3 + r] * u1) + R[6 + r] * u2;
-    o[7] = is;
-}
-
-ORBGPU_HD inline void sim3_map(const double S[8], const double X[3], double o[3])
-{
-    double R[9], RX[3];
-    quat_to_matrix(S, R);
-    mat_vec3(R, X, RX);
-    ORBGPU_UNROLL
-    for (int r = 0; r < 3; r++)
-        o[r] = S[7] * RX[r] + S[4 + r];
-}
-
-// W x = t by LU with partial pivoting (G3); the swaps are selects, so that everything stays in registers
-ORBGPU_HD inline void lu_solve3(const double W[9], const double t[3], double x[3])
-{
-    double a00 = W[0], a01 = W[1], a02 = W[2], a10 = W[3], a11 = W[4], a12 = W[5], a20 = W[6], a21 = W[7], a22 = W[8];
-    double b0 = t[0], b1 = t[1], b2 = t[2];
-#define ORBGPU_EG_SWAP(p, q)            \
-    {                                   \
-        const double tp = m ? q : p;    \
-        q = m ? p : q;                  \
-        p = tp;                         \
-    }
-    {
-        const bool m = fabs(a10) > fabs(a00);
-        ORBGPU_EG_SWAP(a00, a10) ORBGPU_EG_SWAP(a01, a11) ORBGPU_EG_SWAP(a02, a12) ORBGPU_EG_SWAP(b0, b1)
-    }
-    {
-        const bool m = fabs(a20) > fabs(a00);
-        ORBGPU_EG_SWAP(a00, a20) ORBGPU_EG_SWAP(a01, a21) ORBGPU_EG_SWAP(a02, a22) ORBGPU_EG_SWAP(b0, b2)
-    }
-    const double m1 = a10 / a00;
-    a11 = a11 - m1 * a01, a12 = a12 - m1 * a02, b1 = b1 - m1 * b0;
-    const double m2 = a20 / a00;
-    a21 = a21 - m2 * a01, a22 = a22 - m2 * a02, b2 = b2 - m2 * b0;
-    {
-        const bool m = fabs(a21) > fabs(a11);
-        ORBGPU_EG_SWAP(a11, a21) ORBGPU_EG_SWAP(a12, a22) ORBGPU_EG_SWAP(b1, b2)
-    }
-#undef ORBGPU_EG_SWAP
-    const double m3 = a21 / a11;
-    a22 = a22 - m3 * a12, b2 = b2 - m3 * b1;
-    x[2] = b2 / a22;
-    x[1] = (b1 - a12 * x[2]) / a11;
-    x[0] = ((b0 - a01 * x[1]) - a02 * x[2]) / a00;
-}
-
-// G3
-ORBGPU_HD inline void sim3_log(const double S[8], double e[7])
-{
-    const double s = S[7];
-    const double sigma = log(s);
-    double R[9];
-    quat_to_matrix(S, R);
-    const double d = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
-    const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
-    const double eps = 1e-5;
-    const bool small_th = d > 1.0 - eps, small_sigma = fabs(sigma) < eps;
-    double w[3], th = 0.0;
-    if (small_th) {
-        ORBGPU_UNROLL
-        for (int r = 0; r < 3; r++)
-            w[r] = 0.5 * dR[r];
-    } else {
-        th = acos(d);
-        const double f = th / (2.0 * sqrt(1.0 - d * d));
-        ORBGPU_UNROLL
-        for (int r = 0; r < 3; r++)
-            w[r] = f * dR[r];
-    }
-    double A, B, C;
-    if (small_sigma) {
-        C = 1.0;
-        if (small_th) {
-            A = 0.5;
-            B = 1.0 / 6.0;
-        } else {
-            const double sn = sin(th), cs = cos(th), th2 = th * th;
-            A = (1.0 - cs) / th2;
-            B = (th - sn) / (th2 * th);
-        }
-    } else {
-        C = (s - 1.0) / sigma;
-        const double sigma2 = sigma * sigma;
-        if (small_th) {
-            A = ((sigma - 1.0) * s + 1.0) / sigma2;
-            B = (((0.5 * sigma2 - sigma) + 1.0) * s) / (sigma2 * sigma);  // as published (G3)
-        } else {
-            const double sn = sin(th), cs = cos(th), th2 = th * th;
-            const double a = s * sn, b = s * cs, c = th2 + sigma2;
-            A = (a * sigma + (1.0 - b) * th) / (th * c);
-            B = (C - ((b - 1.0) * sigma + a * th) / c) / th2;
-        }
-    }
-    const double O[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
-    double W[9];
-    ORBGPU_UNROLL
-    for (int r = 0; r < 3; r++)
-        ORBGPU_UNROLL
-        for (int c = 0; c < 3; c++) {
-            const double o2 = (O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c]) + O[3 * r + 2] * O[6 + c];
-            W[3 * r + c] = (A * O[3 * r + c] + B * o2) + (r == c ? C : 0.0);
-        }
-    lu_solve3(W, S + 4, e + 3);
-    e[0] = w[0], e[1] = w[1], e[2] = w[2];
-    e[6] = sigma;
-}
-
-// G4: e = log((M * S_i) * S_j^-1)
-ORBGPU_HD inline void edge_error(const double M[8], const double Si[8], const double Sj[8], double e[7])
-{
-    double A[8], Bi[8], C[8];
-    sim3_mul(M, Si, A);
-    sim3_inv(Sj, Bi);
-    sim3_mul(A, Bi, C);
-    sim3_log(C, e);
-}
-
-ORBGPU_HD inline double chi2_of(const double e[7])
-{
-    double c = e[0] * e[0];
-    ORBGPU_UNROLL
-    for (int r = 1; r < 7; r++)
-        c = c + e[r] * e[r];
-    return c;
-}
-
-// S' = exp(x) * S (O4, O5); nothing is renormalised.  A second text of sim3_opt.hip's sim3_update, on 8-double states.
-ORBGPU_HD inline void sim3_update(const double S[8], const double x[7], bool fix_scale, double Sn[8])
-{
-    const double w0 = x[0], w1 = x[1], w2 = x[2];
-    const double sigma = fix_scale ? 0.0 : x[6];
-    const double th = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
-    const double sx = exp(sigma);
-    const double O[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
-    double O2[9];
-    ORBGPU_UNROLL
-    for (int r = 0; r < 3; r++)
-        ORBGPU_UNROLL
-        for (int c = 0; c < 3; c++)
-            O2[3 * r + c] = (O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c]) + O[3 * r + 2] * O[6 + c];
-    const double eps = 1e-5;
-    const bool small_th = th < eps, small_sigma = fabs(sigma) < eps;
-    double A, B, C, ra = 1.0, rb = 1.0;  // R = (I + ra Om) + rb Om Om
-    if (small_sigma) {
-        C = 1.0;
-        if (small_th) {
-            A = 0.5;
-            B = 1.0 / 6.0;
-        } else {
-            const double sn_ = sin(th), cs = cos(th);
-            A = (1.0 - cs) / (th * th);
-            B = (th - sn_) / ((th * th) * th);
-            ra = sn_ / th;
-            rb = (1.0 - cs) / (th * th);
-        }
-    } else {
-        C = (sx - 1.0) / sigma;
-        if (small_th) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1.0) * sx + 1.0) / sigma2;
-            B = (((0.5 * sigma2 - sigma) + 1.0) * sx) / (sigma2 * sigma);
-        } else {
-            const double sn_ = sin(th), cs = cos(th);
-            ra = sn_ / th;
-            rb = (1.0 - cs) / (th * th);
-            const double a = sx * sn_, b = sx * cs, th2 = th * th, c = th2 + sigma * sigma;
-            A = (a * sigma + (1.0 - b) * th) / (th * c);
-            B = (C - ((b - 1.0) * sigma + a * th) / c) / th2;
-        }
-    }
-    double R[9], W[9];
-    ORBGPU_UNROLL
-    for (int i = 0; i < 9; i++) {
-        const bool diag = i % 4 == 0;
-        R[i] = small_th ? ((diag ? 1.0 : 0.0) + O[i]) + O2[i] : ((diag ? 1.0 : 0.0) + ra * O[i]) + rb * O2[i];
-        W[i] = (A * O[i] + B * O2[i]) + (diag ? C : 0.0);
-    }
-    double qx[4], Rx[9];
-    quat_from_matrix(R, qx);
-    quat_to_matrix(qx, Rx);
-    quat_mul(qx, S, Sn);
-    ORBGPU_UNROLL
-    for (int r = 0; r < 3; r++) {
-        const double tx = (W[3 * r] * x[3] + W[3 * r + 1] * x[4]) + W[3 * r + 2] * x[5];
-        Sn[4 + r] = sx * ((Rx[3 * r] * S[4] + Rx[3 * r + 1] * S[5]) + Rx[3 * r + 2] * S[6]) + tx;
-    }
-    Sn[7] = sx * S[7];
-}
-
-__device__ inline void load8(const double *p, double o[8])
-{
-#pragma unroll
-    for (int k = 0; k < 8; k++)
-        o[k] = p[k];
-}
-
 // errors of every edge at `states` into P.err, and their sum (the same bits in every lane)
 __device__ __noinline__ double chi2_at(const EgProblemDev &P, const double *states, double *red)
 {
@@ -327,7 +84,7 @@ __device__ __noinline__ double chi2_at(const EgProblemDev &P, const double *stat
         load8(P.meas + 8 * (size_t)e, M);
         load8(states + 8 * (size_t)E.i, Si);
         load8(states + 8 * (size_t)E.j, Sj);
-        edge_error(M, Si, Sj, er);
+        sim3_edge_error(M, Si, Sj, er);
 #pragma unroll
         for (int r = 0; r < 7; r++)
             P.err[7 * (size_t)e + r] = er[r];
@@ -427,7 +184,7 @@ __global__ __launch_bounds__(EG_THREADS) void k_essential_graph(const EgProblemD
                     Sa[a] = c == 0 || end ? Si[a] : pv;
                     Sb[a] = c == 0 || !end ? Sj[a] : pv;
                 }
-                edge_error(M, Sa, Sb, er);
+                sim3_edge_error(M, Sa, Sb, er);
 #pragma unroll
                 for (int r = 0; r < 7; r++)
                     dif[r] = sgn == 0 ? er[r] : (dif[r] - er[r]) * inv2d;
@@ -781,105 +538,59 @@ static int build_index(const orbgpu_essential_graph_problem &p, int k, EgIndex &
 static int enqueue(int32_t n, const orbgpu_essential_graph_problem *problems, std::vector<EgIndex> &ix, EgWs &ws, void *hip_stream)
 {
     int rc = ORBGPU_OK;
-    // The workspace: first what is uploaded (one copy for the whole batch), then the kernel's scratch.  Offsets first,
-    // pointers once the buffer is reserved.
-    struct Layout {
-        size_t edges, Snc, state0, slot, row_of, diag_start, diag_items, blk_start, blk_items, blk_pos, first, last, off;
-        size_t state1, meas, pert, J, err, Hd, Ho, b, A, vec;
+    // The record of problem k: every buffer of its workspace named once (carve.h's WorkPlan), then its scalars
+    auto describe = [&](int k, WorkPlan &plan, EgProblemDev &D) {
+        const orbgpu_essential_graph_problem &p = problems[k];
+        const EgIndex &I = ix[k];
+        const size_t V = (size_t)p.n_vertices, ne = I.edges.size(), nf = I.diag_start.size() - 1, nblk = I.blk_pos.size();
+        D.edges = plan.seg(ne, I.edges.data());
+        D.Snc = plan.seg(8 * V, p.Snc);
+        D.state[0] = plan.seg(8 * V, p.Scw);
+        D.slot = plan.seg(I.slot.size(), I.slot.data());
+        D.row_of = plan.seg(I.row_of.size(), I.row_of.data());
+        D.diag_start = plan.seg(I.diag_start.size(), I.diag_start.data());
+        D.diag_items = plan.seg(I.diag_items.size(), I.diag_items.data());
+        D.blk_start = plan.seg(I.blk_start.size(), I.blk_start.data());
+        D.blk_items = plan.seg(I.blk_items.size(), I.blk_items.data());
+        D.blk_pos = plan.seg(nblk, I.blk_pos.data());
+        D.first = plan.seg(I.first.size(), I.first.data());
+        D.last = plan.seg(I.last.size(), I.last.data());
+        D.off = plan.seg(I.off.size(), I.off.data());
+        D.state[1] = plan.seg<double>(8 * V);
+        D.meas = plan.seg<double>(8 * ne);
+        D.pert = plan.seg<double>(14 * 8 * V);
+        D.J = plan.seg<double>(98 * ne);
+        D.err = plan.seg<double>(7 * ne);
+        D.Hd = plan.seg<double>(49 * nf);
+        D.Ho = plan.seg<double>(49 * nblk);
+        D.b = plan.seg<double>(7 * nf);
+        D.A = plan.seg<double>((size_t)I.envelope);
+        D.vec = plan.seg<double>(21 * nf);
+        D.stop = p.d_stop;
+        D.Siw_d = p.d_Siw_d, D.Tiw = p.d_Tiw, D.result = p.d_result;
+        D.envelope = I.envelope;
+        D.V = p.n_vertices, D.ne = (int32_t)ne, D.nf = (int32_t)nf;
+        D.nblk = (int32_t)nblk, D.n_bad_index = I.n_bad_index, D.n_iterations = p.n_iterations;
+        D.fix_scale = p.fix_scale ? 1 : 0, D.bandwidth = I.bandwidth;
     };
-    std::vector<Layout> lay((size_t)n);
-    Carver carve(256);
-    auto bytes_of = [](size_t count, size_t size) { return std::max<size_t>(count, 1) * size; };
+    WorkPlan measured;
     for (int k = 0; k < n; k++) {
-        const EgIndex &I = ix[k];
-        const size_t V = (size_t)problems[k].n_vertices;
-        Layout &L = lay[k];
-        L.edges = carve.take(bytes_of(I.edges.size(), sizeof(EgEdge)));
-        L.Snc = carve.take(bytes_of(8 * V, 8));
-        L.state0 = carve.take(bytes_of(8 * V, 8));
-        L.slot = carve.take(bytes_of(I.slot.size(), 4));
-        L.row_of = carve.take(bytes_of(I.row_of.size(), 4));
-        L.diag_start = carve.take(bytes_of(I.diag_start.size(), 4));
-        L.diag_items = carve.take(bytes_of(I.diag_items.size(), 4));
-        L.blk_start = carve.take(bytes_of(I.blk_start.size(), 4));
-        L.blk_items = carve.take(bytes_of(I.blk_items.size(), 4));
-        L.blk_pos = carve.take(bytes_of(I.blk_pos.size(), sizeof(int2)));
-        L.first = carve.take(bytes_of(I.first.size(), 4));
-        L.last = carve.take(bytes_of(I.last.size(), 4));
-        L.off = carve.take(bytes_of(I.off.size(), 8));
-    }
-    const size_t upload_bytes = carve.off;
-    for (int k = 0; k < n; k++) {
-        const EgIndex &I = ix[k];
-        const size_t V = (size_t)problems[k].n_vertices, ne = I.edges.size(), nf = I.diag_start.size() - 1, nblk = I.blk_pos.size();
-        Layout &L = lay[k];
-        L.state1 = carve.take(bytes_of(8 * V, 8));
-        L.meas = carve.take(bytes_of(8 * ne, 8));
-        L.pert = carve.take(bytes_of(14 * 8 * V, 8));
-        L.J = carve.take(bytes_of(98 * ne, 8));
-        L.err = carve.take(bytes_of(7 * ne, 8));
-        L.Hd = carve.take(bytes_of(49 * nf, 8));
-        L.Ho = carve.take(bytes_of(49 * nblk, 8));
-        L.b = carve.take(bytes_of(7 * nf, 8));
-        L.A = carve.take(bytes_of((size_t)I.envelope, 8));
-        L.vec = carve.take(bytes_of(21 * nf, 8));
+        EgProblemDev unused{};
+        describe(k, measured, unused);
     }
     ws.reserve(PROBLEMS, sizeof(EgProblemDev) * (size_t)n);
-    ws.reserve(WORK, carve.off);
+    ws.reserve(WORK, measured.total());
     if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
     std::vector<char> &blob = ws.blob;
     std::vector<EgProblemDev> &hp = ws.records;
+    const size_t upload_bytes = measured.upload_bytes();
     blob.assign(upload_bytes, 0);
     hp.assign((size_t)n, EgProblemDev{});
     char *dev = ws.as<char>(WORK);
-    auto copy_in = [&](size_t off, const void *src, size_t bytes) {
-        if (bytes)
-            memcpy(blob.data() + off, src, bytes);
-    };
-    for (int k = 0; k < n; k++) {
-        const orbgpu_essential_graph_problem &p = problems[k];
-        const EgIndex &I = ix[k];
-        const Layout &L = lay[k];
-        const size_t V = (size_t)p.n_vertices;
-        copy_in(L.edges, I.edges.data(), I.edges.size() * sizeof(EgEdge));
-        copy_in(L.Snc, p.Snc, 64 * V);
-        copy_in(L.state0, p.Scw, 64 * V);
-        copy_in(L.slot, I.slot.data(), I.slot.size() * 4);
-        copy_in(L.row_of, I.row_of.data(), I.row_of.size() * 4);
-        copy_in(L.diag_start, I.diag_start.data(), I.diag_start.size() * 4);
-        copy_in(L.diag_items, I.diag_items.data(), I.diag_items.size() * 4);
-        copy_in(L.blk_start, I.blk_start.data(), I.blk_start.size() * 4);
-        copy_in(L.blk_items, I.blk_items.data(), I.blk_items.size() * 4);
-        copy_in(L.blk_pos, I.blk_pos.data(), I.blk_pos.size() * sizeof(int2));
-        copy_in(L.first, I.first.data(), I.first.size() * 4);
-        copy_in(L.last, I.last.data(), I.last.size() * 4);
-        copy_in(L.off, I.off.data(), I.off.size() * 8);
-
-        EgProblemDev &D = hp[k];
-        D.edges = reinterpret_cast<EgEdge *>(dev + L.edges);
-        D.Snc = reinterpret_cast<double *>(dev + L.Snc);
-        D.state[0] = reinterpret_cast<double *>(dev + L.state0), D.state[1] = reinterpret_cast<double *>(dev + L.state1);
-        D.slot = reinterpret_cast<int32_t *>(dev + L.slot), D.row_of = reinterpret_cast<int32_t *>(dev + L.row_of);
-        D.meas = reinterpret_cast<double *>(dev + L.meas), D.pert = reinterpret_cast<double *>(dev + L.pert);
-        D.J = reinterpret_cast<double *>(dev + L.J), D.err = reinterpret_cast<double *>(dev + L.err);
-        D.diag_start = reinterpret_cast<int32_t *>(dev + L.diag_start);
-        D.diag_items = reinterpret_cast<int32_t *>(dev + L.diag_items);
-        D.blk_start = reinterpret_cast<int32_t *>(dev + L.blk_start);
-        D.blk_items = reinterpret_cast<int32_t *>(dev + L.blk_items);
-        D.blk_pos = reinterpret_cast<int2 *>(dev + L.blk_pos);
-        D.Hd = reinterpret_cast<double *>(dev + L.Hd), D.Ho = reinterpret_cast<double *>(dev + L.Ho);
-        D.b = reinterpret_cast<double *>(dev + L.b);
-        D.first = reinterpret_cast<int32_t *>(dev + L.first), D.last = reinterpret_cast<int32_t *>(dev + L.last);
-        D.off = reinterpret_cast<int64_t *>(dev + L.off);
-        D.A = reinterpret_cast<double *>(dev + L.A), D.vec = reinterpret_cast<double *>(dev + L.vec);
-        D.stop = p.d_stop;
-        D.Siw_d = p.d_Siw_d, D.Tiw = p.d_Tiw, D.result = p.d_result;
-        D.envelope = I.envelope;
-        D.V = p.n_vertices, D.ne = (int32_t)I.edges.size(), D.nf = (int32_t)I.diag_start.size() - 1;
-        D.nblk = (int32_t)I.blk_pos.size(), D.n_bad_index = I.n_bad_index, D.n_iterations = p.n_iterations;
-        D.fix_scale = p.fix_scale ? 1 : 0, D.bandwidth = I.bandwidth;
-    }
+    WorkPlan plan(measured, dev, blob.data());
+    for (int k = 0; k < n; k++)
+        describe(k, plan, hp[k]);
     const hipStream_t st = (hipStream_t)hip_stream;
     ORBGPU_HIP_TRY(hipMemcpyAsync(ws.buf[PROBLEMS].p, hp.data(), sizeof(EgProblemDev) * (size_t)n, hipMemcpyHostToDevice, st));
     if (upload_bytes)
@@ -889,21 +600,14 @@ static int enqueue(int32_t n, const orbgpu_essential_graph_problem *problems, st
     return ORBGPU_OK;
 }
 
-// checks and index structures of a batch: everything that can be refused is refused here, before a device is touched
-static int prepare(int32_t n, const orbgpu_essential_graph_problem *problems, bool device_outputs, std::vector<EgIndex> &ix)
+// checks and index structure of problem k: everything that can be refused is refused here, before a device is touched
+static int check_and_index(const orbgpu_essential_graph_problem &p, int k, bool device_outputs, EgIndex &ix)
 {
-    ORBGPU_REQUIRE(n >= 0 && n <= 65535 && (n == 0 || problems), "bad arguments");
-    ix.resize((size_t)n);
-    for (int k = 0; k < n; k++) {
-        int rc = check_problem(problems[k], k);
-        if (rc != ORBGPU_OK)
-            return rc;
-        const orbgpu_essential_graph_problem &p = problems[k];
-        ORBGPU_REQUIRE(!device_outputs || (p.d_result && (p.n_vertices == 0 || (p.d_Siw_d && p.d_Tiw))), "problem %d: null output", k);
-        if ((rc = build_index(p, k, ix[k])) != ORBGPU_OK)
-            return rc;
-    }
-    return ORBGPU_OK;
+    int rc = check_problem(p, k);
+    if (rc != ORBGPU_OK)
+        return rc;
+    ORBGPU_REQUIRE(!device_outputs || (p.d_result && (p.n_vertices == 0 || (p.d_Siw_d && p.d_Tiw))), "problem %d: null output", k);
+    return build_index(p, k, ix);
 }
 
 static int check_points(int32_t n_vertices, int32_t n_points)
@@ -934,13 +638,17 @@ extern "C" int orbgpu_essential_graph_batch_device(int32_t n, const orbgpu_essen
                                                    void *hip_stream)
 {
     std::vector<EgIndex> ix;
-    int rc = prepare(n, problems, true, ix);
-    if (rc != ORBGPU_OK || (rc = select_device(device_id)) != ORBGPU_OK || n == 0)
+    EgWs *wsp;
+    int rc = batch_begin(
+        n, problems,
+        [&ix](const orbgpu_essential_graph_problem &p, int k) {
+            ix.emplace_back();
+            return check_and_index(p, k, true, ix.back());
+        },
+        device_id, wsp);
+    if (rc != ORBGPU_OK || !wsp)
         return rc;
-    EgWs &ws = per_device_workspace<EgWs>(device_id);
-    if ((rc = ws.bind(device_id, false)) != ORBGPU_OK)
-        return rc;
-    return enqueue(n, problems, ix, ws, hip_stream);
+    return enqueue(n, problems, ix, *wsp, hip_stream);
 }
 
 extern "C" int orbgpu_essential_graph_device(const orbgpu_essential_graph_problem *p, int32_t device_id, void *hip_stream)
@@ -971,8 +679,8 @@ extern "C" int orbgpu_essential_graph(const orbgpu_essential_graph_problem *p, c
                                       orbgpu_essential_graph_result *result, int32_t device_id)
 {
     ORBGPU_REQUIRE(p, "null argument");
-    std::vector<EgIndex> ix;
-    int rc = prepare(1, p, false, ix);
+    std::vector<EgIndex> ix(1);
+    int rc = check_and_index(*p, 0, false, ix[0]);
     if (rc != ORBGPU_OK || (rc = check_points(p->n_vertices, n_points)) != ORBGPU_OK)
         return rc;
     ORBGPU_REQUIRE((p->n_vertices == 0 || Tiw) && (n_points == 0 || (world_pos && point_ref && pos_out)), "null argument");

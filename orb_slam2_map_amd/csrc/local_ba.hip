@@ -77,53 +77,6 @@ struct LbaProblemDev {
     int32_t n_iterations, robust, n_not_included;
 };
 
-struct WorkgroupBarrier {
-    __device__ void operator()() const { __syncthreads(); }
-};
-
-// the stop flag, read by one lane and broadcast (L9)
-__device__ inline bool stop_requested(const int32_t *stop, int *flag)
-{
-    if (!stop)
-        return false;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        *flag = __hip_atomic_load(stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __syncthreads();
-    return *flag != 0;
-}
-
-// max over the workgroup, the same in every lane; NaN never wins
-__device__ inline double block_max(double m, double *red)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_down(m, off, 64);
-        if (o > m)
-            m = o;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0)
-        red[wave] = m;
-    __syncthreads();
-    m = red[0];
-#pragma unroll
-    for (int wv = 1; wv < LBA_WAVES; wv++)
-        if (red[wv] > m)
-            m = red[wv];
-    return m;
-}
-
-template <int K> __device__ inline void wave_sum(double (&v)[K])
-{
-#pragma unroll
-    for (int k = 0; k < K; k++)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-            v[k] += __shfl_down(v[k], off, 64);
-}
-
 // error of edge E at a state; returns chi2, C and R of its pose
 __device__ inline double eval_edge(const LbaProblemDev &P, const LbaEdge &E, const double *poses, const double *X, Cam &C,
                                    const double *&R, double er[3], double Pc[3])
@@ -378,7 +331,7 @@ __device__ __forceinline__ void lm_problem(const LbaProblemDev &P)
                             if (d > m)
                                 m = d;
                         }
-                lam = 1e-5 * block_max(m, red);
+                lam = 1e-5 * block_max<LBA_WAVES>(m, red);
                 nu = 2.0;
             }
             cur = robust_chi(P, poses, X, use_kernel, red);
@@ -547,20 +500,10 @@ __device__ __forceinline__ void lm_problem(const LbaProblemDev &P)
                 const double chi_n = robust_chi(P, poses_n, X_n, use_kernel, red);
                 const double tmp = ok ? chi_n : DBL_MAX;
                 const double scale = part[0] + 1e-3;
-                rho = (cur - tmp) / scale;
                 trials[rnd]++;
-                if (rho > 0 && isfinite(tmp)) {
-                    const double c = 2.0 * rho - 1.0;
-                    const double alpha = fmin(1.0 - (c * c) * c, 2.0 / 3.0);
-                    lam = lam * fmax(1.0 / 3.0, alpha);
-                    nu = 2.0;
+                if (lm_trial(cur, tmp, scale, lam, nu, rho, stop)) {
                     kept ^= 1;
                     cur = tmp;
-                } else {
-                    lam = lam * nu;
-                    nu = nu * 2.0;
-                    if (!isfinite(lam))
-                        stop = true;
                 }
                 trial++;
             } while (!stop && rho < 0 && trial < 10);
@@ -805,82 +748,42 @@ static int enqueue(int32_t n, const orbgpu_local_ba_problem *problems, const orb
     int rc = ORBGPU_OK;
     // ORBGPU_DEBUG_LBA_LDS_POSES=<k> (tests): problems with more than k free poses keep the reduced system in global memory
     const int lds_poses = debug_limit("ORBGPU_DEBUG_LBA_LDS_POSES", LBA_LDS_POSES);
-    // The workspace: first what is uploaded (one copy for the whole batch), then the kernel's scratch.  Offsets first,
-    // pointers once the buffer is reserved.
-    struct Layout {
-        size_t edges, point_start, free_of, free_row, pose_start, pose_edges, blk_start, pairs, cam, pose0, X0;
-        size_t pose1, X1, Hll, bl, inv, Hpp, bp, Hpl, S, vec, pt_on, fr_on;
-    };
     std::vector<LbaIndex> ix((size_t)n);
-    std::vector<Layout> lay((size_t)n);
-    Carver carve(256);
-    auto bytes_of = [](size_t count, size_t size) { return std::max<size_t>(count, 1) * size; };
-    for (int k = 0; k < n; k++) {
+    for (int k = 0; k < n; k++)
         if ((rc = build_index(problems[k], k, ix[k])) != ORBGPU_OK)
             return rc;
+    // The workspace (carve.h's WorkPlan): every buffer of problem k is named here, once
+    auto describe = [&](int k, WorkPlan &plan, LbaProblemDev &D) {
         const orbgpu_local_ba_problem &p = problems[k];
         const LbaIndex &I = ix[k];
-        Layout &L = lay[k];
-        L.edges = carve.take(bytes_of(I.edges.size(), sizeof(LbaEdge)));
-        L.point_start = carve.take(bytes_of(I.point_start.size(), 4));
-        L.free_of = carve.take(bytes_of(I.free_of.size(), 4));
-        L.free_row = carve.take(bytes_of(I.free_row.size(), 4));
-        L.pose_start = carve.take(bytes_of(I.pose_start.size(), 4));
-        L.pose_edges = carve.take(bytes_of(I.pose_edges.size(), 4));
-        L.blk_start = carve.take(bytes_of(I.blk_start.size(), 4));
-        L.pairs = carve.take(bytes_of(I.pairs.size(), sizeof(int2)));
-        L.cam = carve.take(bytes_of(5 * (size_t)p.n_poses, 8));
-        L.pose0 = carve.take(bytes_of(LBA_POSE_STRIDE * (size_t)p.n_poses, 8));
-        L.X0 = carve.take(bytes_of(3 * (size_t)p.n_points, 8));
-    }
-    const size_t upload_bytes = carve.off;
-    for (int k = 0; k < n; k++) {
-        const orbgpu_local_ba_problem &p = problems[k];
-        const size_t M = (size_t)p.n_points, nf = ix[k].free_row.size(), ne = ix[k].edges.size(), rows = 6 * nf;
-        Layout &L = lay[k];
-        L.pose1 = carve.take(bytes_of(LBA_POSE_STRIDE * (size_t)p.n_poses, 8));
-        L.X1 = carve.take(bytes_of(3 * M, 8));
-        L.Hll = carve.take(bytes_of(6 * M, 8));
-        L.bl = carve.take(bytes_of(3 * M, 8));
-        L.inv = carve.take(bytes_of(9 * M, 8));
-        L.Hpp = carve.take(bytes_of(21 * nf, 8));
-        L.bp = carve.take(bytes_of(6 * nf, 8));
-        L.Hpl = carve.take(bytes_of(18 * ne, 8));
+        const size_t Pn = (size_t)p.n_poses, M = (size_t)p.n_points, nf = I.free_row.size(), ne = I.edges.size(), rows = 6 * nf;
         const bool in_lds = (int)nf <= lds_poses;
-        L.S = carve.take(bytes_of(in_lds ? 0 : rows * (rows + 1) / 2, 8));
-        L.vec = carve.take(bytes_of(in_lds ? 0 : 3 * rows, 8));
-        L.pt_on = carve.take(bytes_of(M, 1));
-        L.fr_on = carve.take(bytes_of(nf, 1));
-    }
-    ws.reserve(PROBLEMS, sizeof(LbaProblemDev) * (size_t)n);
-    ws.reserve(WORK, carve.off);
-    ws.reserve(SPILL_COUNT, sizeof(int32_t));
-    if ((rc = ws.status()) != ORBGPU_OK)
-        return rc;
-    std::vector<char> &blob = ws.blob;
-    std::vector<LbaProblemDev> &hp = ws.records;
-    blob.assign(upload_bytes, 0);
-    hp.assign((size_t)n, LbaProblemDev{});
-    char *dev = ws.as<char>(WORK);
-    auto copy_in = [&](size_t off, const void *src, size_t bytes) {
-        if (bytes)
-            memcpy(blob.data() + off, src, bytes);
-    };
-    for (int k = 0; k < n; k++) {
-        const orbgpu_local_ba_problem &p = problems[k];
-        const LbaIndex &I = ix[k];
-        const Layout &L = lay[k];
-        copy_in(L.edges, I.edges.data(), I.edges.size() * sizeof(LbaEdge));
-        copy_in(L.point_start, I.point_start.data(), I.point_start.size() * 4);
-        copy_in(L.free_of, I.free_of.data(), I.free_of.size() * 4);
-        copy_in(L.free_row, I.free_row.data(), I.free_row.size() * 4);
-        copy_in(L.pose_start, I.pose_start.data(), I.pose_start.size() * 4);
-        copy_in(L.pose_edges, I.pose_edges.data(), I.pose_edges.size() * 4);
-        copy_in(L.blk_start, I.blk_start.data(), I.blk_start.size() * 4);
-        copy_in(L.pairs, I.pairs.data(), I.pairs.size() * sizeof(int2));
-        double *cam = reinterpret_cast<double *>(blob.data() + L.cam);
-        double *pose = reinterpret_cast<double *>(blob.data() + L.pose0);
-        double *X = reinterpret_cast<double *>(blob.data() + L.X0);
+        double *cam, *pose, *X;  // filled in place below; null while the plan only measures
+        D.edges = plan.seg(ne, I.edges.data());
+        D.point_start = plan.seg(I.point_start.size(), I.point_start.data());
+        D.free_of = plan.seg(I.free_of.size(), I.free_of.data());
+        D.free_row = plan.seg(nf, I.free_row.data());
+        D.pose_start = plan.seg(I.pose_start.size(), I.pose_start.data());
+        D.pose_edges = plan.seg(I.pose_edges.size(), I.pose_edges.data());
+        D.blk_start = plan.seg(I.blk_start.size(), I.blk_start.data());
+        D.pairs = plan.seg(I.pairs.size(), I.pairs.data());
+        D.cam = plan.seg_in_place(5 * Pn, cam);
+        D.pose[0] = plan.seg_in_place(LBA_POSE_STRIDE * Pn, pose);
+        D.X[0] = plan.seg_in_place(3 * M, X);
+        D.pose[1] = plan.seg<double>(LBA_POSE_STRIDE * Pn);
+        D.X[1] = plan.seg<double>(3 * M);
+        D.Hll = plan.seg<double>(6 * M);
+        D.bl = plan.seg<double>(3 * M);
+        D.inv = plan.seg<double>(9 * M);
+        D.Hpp = plan.seg<double>(21 * nf);
+        D.bp = plan.seg<double>(6 * nf);
+        D.Hpl = plan.seg<double>(18 * ne);
+        D.S = plan.seg<double>(in_lds ? 0 : rows * (rows + 1) / 2);
+        D.vec = plan.seg<double>(in_lds ? 0 : 3 * rows);
+        D.pt_on = plan.seg<uint8_t>(M);
+        D.fr_on = plan.seg<uint8_t>(nf);
+        if (!cam)
+            return;
         for (int i = 0; i < p.n_poses; i++) {
             for (int c = 0; c < 5; c++)
                 cam[5 * (size_t)i + c] = (double)p.cam[5 * (size_t)i + c];
@@ -890,28 +793,31 @@ static int enqueue(int32_t n, const orbgpu_local_ba_problem *problems, const orb
             for (int r = 0; r < 3; r++)
                 q[4 + r] = (double)p.Tcw[16 * (size_t)i + 4 * r + 3];
         }
-        for (size_t i = 0; i < 3 * (size_t)p.n_points; i++)
+        for (size_t i = 0; i < 3 * M; i++)
             X[i] = (double)p.world_pos[i];
-
+    };
+    WorkPlan measured;
+    for (int k = 0; k < n; k++) {
+        LbaProblemDev unused{};
+        describe(k, measured, unused);
+    }
+    ws.reserve(PROBLEMS, sizeof(LbaProblemDev) * (size_t)n);
+    ws.reserve(WORK, measured.total());
+    ws.reserve(SPILL_COUNT, sizeof(int32_t));
+    if ((rc = ws.status()) != ORBGPU_OK)
+        return rc;
+    std::vector<char> &blob = ws.blob;
+    std::vector<LbaProblemDev> &hp = ws.records;
+    const size_t upload_bytes = measured.upload_bytes();
+    blob.assign(upload_bytes, 0);
+    hp.assign((size_t)n, LbaProblemDev{});
+    char *dev = ws.as<char>(WORK);
+    WorkPlan plan(measured, dev, blob.data());
+    for (int k = 0; k < n; k++) {
+        const orbgpu_local_ba_problem &p = problems[k];
+        const LbaIndex &I = ix[k];
         LbaProblemDev &D = hp[k];
-        memset(&D, 0, sizeof(D));
-        D.edges = reinterpret_cast<LbaEdge *>(dev + L.edges);
-        D.point_start = reinterpret_cast<int32_t *>(dev + L.point_start);
-        D.free_of = reinterpret_cast<int32_t *>(dev + L.free_of);
-        D.free_row = reinterpret_cast<int32_t *>(dev + L.free_row);
-        D.pose_start = reinterpret_cast<int32_t *>(dev + L.pose_start);
-        D.pose_edges = reinterpret_cast<int32_t *>(dev + L.pose_edges);
-        D.blk_start = reinterpret_cast<int32_t *>(dev + L.blk_start);
-        D.pairs = reinterpret_cast<int2 *>(dev + L.pairs);
-        D.cam = reinterpret_cast<double *>(dev + L.cam);
-        D.pose[0] = reinterpret_cast<double *>(dev + L.pose0), D.pose[1] = reinterpret_cast<double *>(dev + L.pose1);
-        D.X[0] = reinterpret_cast<double *>(dev + L.X0), D.X[1] = reinterpret_cast<double *>(dev + L.X1);
-        D.Hll = reinterpret_cast<double *>(dev + L.Hll), D.bl = reinterpret_cast<double *>(dev + L.bl);
-        D.inv = reinterpret_cast<double *>(dev + L.inv);
-        D.Hpp = reinterpret_cast<double *>(dev + L.Hpp), D.bp = reinterpret_cast<double *>(dev + L.bp);
-        D.Hpl = reinterpret_cast<double *>(dev + L.Hpl);
-        D.S = reinterpret_cast<double *>(dev + L.S), D.vec = reinterpret_cast<double *>(dev + L.vec);
-        D.pt_on = reinterpret_cast<uint8_t *>(dev + L.pt_on), D.fr_on = reinterpret_cast<uint8_t *>(dev + L.fr_on);
+        describe(k, plan, D);
         D.stop = p.d_stop;
         D.Tcw_d = p.d_Tcw_d, D.Tcw = p.d_Tcw, D.pos_d = p.d_pos_d, D.pos = p.d_pos, D.erase = p.d_erase, D.result = p.d_result;
         D.spill_count = ws.as<int32_t>(SPILL_COUNT);

@@ -1,13 +1,15 @@
-// The FP64 arithmetic the device optimisers share (pose_opt.hip, sim3_opt.hip, local_ba.hip): quaternions as g2o's SE3Quat / Sim3 use
-// them, the Huber weights, the dense LL^T solve of the damped normal equation, its initial damping and the fixed-order
-// workgroup sum.  The definition of every function is its namesake in tests/pose_model.py, operation for operation;
-// tests/opt_math_test.cpp builds this header with g++ and tests/test_opt_math.py compares the two bit for bit.  No fused
-// multiply-add (-ffp-contract=off), and no expression may be re-associated: parity of the optimisers with their models
-// rests on the order written here.  Pure C++ except block_sum, which needs the wave shuffles.
+// The FP64 arithmetic the device optimisers share (pose_opt.hip, sim3_opt.hip, local_ba.hip, essential_graph.hip): quaternions
+// as g2o's SE3Quat / Sim3 use them, the Huber weights, the dense LL^T solve of the damped normal equation, its initial
+// damping, the decision on a Levenberg-Marquardt trial and the fixed-order workgroup reductions.  The definition of every
+// function is its namesake in tests/pose_model.py, operation for operation; tests/opt_math_test.cpp builds this header with
+// g++ and tests/test_opt_math.py compares the two bit for bit.  No fused multiply-add (-ffp-contract=off), and no
+// expression may be re-associated: parity of the optimisers with their models rests on the order written here.  Pure C++
+// except the part under __HIPCC__ (the workgroup reductions, the barrier and the stop flag), which needs the device.
 #pragma once
 
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 
 #if defined(__HIPCC__)
 #define ORBGPU_HD __host__ __device__
@@ -183,6 +185,28 @@ template <int N> ORBGPU_HD inline double lm_initial_lambda(const double (&Hu)[N 
     return 1e-5 * m;
 }
 
+// The decision on one trial: the robust chi2 went from cur to tmp under a step whose x'(lambda x + b) + 1e-3 is `scale`.
+// Accepted (true): lambda shrinks by max(1/3, min(1 - (2 rho - 1)^3, 2/3)) and nu restarts at 2; the caller keeps the
+// trial's state and sets cur = tmp.  Refused: lambda grows by nu, nu doubles, and a lambda that is no longer finite sets
+// stop.  The callers loop while (!stop && rho < 0 && trial < 10).
+ORBGPU_HD inline bool lm_trial(double cur, double tmp, double scale, double &lam, double &nu, double &rho, bool &stop)
+{
+    using std::isfinite;  // g++ declares it nowhere else
+    rho = (cur - tmp) / scale;
+    if (rho > 0 && isfinite(tmp)) {
+        const double c3 = 2.0 * rho - 1.0;
+        const double alpha = fmin(1.0 - (c3 * c3) * c3, 2.0 / 3.0);
+        lam = lam * fmax(1.0 / 3.0, alpha);
+        nu = 2.0;
+        return true;
+    }
+    lam = lam * nu;
+    nu = nu * 2.0;
+    if (!isfinite(lam))
+        stop = true;
+    return false;
+}
+
 // ---- what the bundle adjustment with free points adds (local_ba.hip; definitions in tests/lba_model.py, host test
 // tests/opt_math_lba_test.cpp) ---------------------------------------------------------------------------------------------
 // Inverse of the symmetric 3x3 with upper triangle h = (00, 01, 02, 11, 12, 22) and lam added to its diagonal, by cofactors
@@ -312,6 +336,55 @@ template <int WAVES, int K> __device__ inline void block_sum(double (&v)[K], dou
             s += red[wv * K + k];
         v[k] = s;
     }
+}
+
+// max over a workgroup of WAVES waves, the same in every lane; NaN never wins.  red: WAVES doubles of LDS.
+template <int WAVES> __device__ inline double block_max(double m, double *red)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_down(m, off, 64);
+        if (o > m)
+            m = o;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0)
+        red[wave] = m;
+    __syncthreads();
+    m = red[0];
+#pragma unroll
+    for (int wv = 1; wv < WAVES; wv++)
+        if (red[wv] > m)
+            m = red[wv];
+    return m;
+}
+
+// the shuffle tree alone: the sums of one wave, in its lane 0
+template <int K> __device__ inline void wave_sum(double (&v)[K])
+{
+#pragma unroll
+    for (int k = 0; k < K; k++)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1)
+            v[k] += __shfl_down(v[k], off, 64);
+}
+
+// the barrier llt_solve and skyline_llt_solve take when a workgroup runs them
+struct WorkgroupBarrier {
+    __device__ void operator()() const { __syncthreads(); }
+};
+
+// the stop flag of an optimiser (L9, G9), read by one lane and broadcast through *flag in LDS
+__device__ inline bool stop_requested(const int32_t *stop, int *flag)
+{
+    if (!stop)
+        return false;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        *flag = __hip_atomic_load(stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __syncthreads();
+    return *flag != 0;
 }
 #endif
 

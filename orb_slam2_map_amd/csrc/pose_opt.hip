@@ -218,13 +218,8 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblemDev *_
                 for (int a = 0; a < 6; a++)
                     scale = scale + x[a] * (lam * x[a] + b[a]);
                 scale = scale + 1e-3;
-                rho = (cur - tmp) / scale;
                 trials++;
-                if (rho > 0 && isfinite(tmp)) {
-                    const double c = 2.0 * rho - 1.0;
-                    const double alpha = fmin(1.0 - (c * c) * c, 2.0 / 3.0);
-                    lam = lam * fmax(1.0 / 3.0, alpha);
-                    nu = 2.0;
+                if (lm_trial(cur, tmp, scale, lam, nu, rho, stop)) {
 #pragma unroll
                     for (int i = 0; i < 4; i++)
                         q[i] = qn[i];
@@ -232,11 +227,6 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoseProblemDev *_
                     for (int i = 0; i < 3; i++)
                         t[i] = tn[i];
                     cur = tmp;
-                } else {
-                    lam = lam * nu;
-                    nu = nu * 2.0;
-                    if (!isfinite(lam))
-                        stop = true;
                 }
                 trial++;
             } while (!stop && rho < 0 && trial < 10);

@@ -4,8 +4,11 @@
 // tests/sim3opt_model.py.  FP64 throughout, no fused multiply-add (-ffp-contract=off): the per-edge arithmetic is the
 // model's operation for operation, only the order of the sums over edges differs (fixed tree here, sequential there).
 // The quaternions, the Huber weights, the Cholesky solve, the initial damping and the reduction tree are opt_math.h's,
-// shared with pose_opt.hip; the rest of the Levenberg-Marquardt bookkeeping and the two compaction passes are written out
-// in both kernels, because moving them changed the generated code.
+// shared with pose_opt.hip; exp(x) * S (O4, O5) is sim3_math.h's, shared with essential_graph.hip.  make_xf, pair_errors
+// and write_result keep their own inverse and map, on the Xf form the edges read, and the decision on a trial is
+// opt_math.h's lm_trial written out: calling it cost one row of tools/bench_sim3opt.py more than the parent's spread
+// (DESIGN.md 9.29).  The two compaction passes are written out here and in pose_opt.hip, because moving them changed the
+// generated code.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -15,6 +18,7 @@
 #include "carve.h"
 #include "common.h"
 #include "opt_math.h"
+#include "sim3_math.h"
 #include "staging.h"
 
 namespace orbgpu {
@@ -52,70 +56,6 @@ struct Sim3OptProblemDev {
 struct Xf {
     double R[9], t[3], s, is, ti[3];
 };
-
-// S' = exp(x) * S (O4, O5); nothing is renormalised
-__device__ inline void sim3_update(const double q[4], const double t[3], double s, const double x[7], bool fix_scale,
-                                   double qn[4], double tn[3], double &sn)
-{
-    const double w0 = x[0], w1 = x[1], w2 = x[2];
-    const double sigma = fix_scale ? 0.0 : x[6];
-    const double th = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
-    const double sx = exp(sigma);
-    const double O[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
-    double O2[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++)
-            O2[3 * r + c] = (O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c]) + O[3 * r + 2] * O[6 + c];
-    const double eps = 1e-5;
-    const bool small_th = th < eps, small_sigma = fabs(sigma) < eps;
-    double A, B, C, ra = 1.0, rb = 1.0;  // R = (I + ra Om) + rb Om Om
-    if (small_sigma) {
-        C = 1.0;
-        if (small_th) {
-            A = 0.5;
-            B = 1.0 / 6.0;
-        } else {
-            const double sn_ = sin(th), cs = cos(th);
-            A = (1.0 - cs) / (th * th);
-            B = (th - sn_) / ((th * th) * th);
-            ra = sn_ / th;
-            rb = (1.0 - cs) / (th * th);
-        }
-    } else {
-        C = (sx - 1.0) / sigma;
-        if (small_th) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1.0) * sx + 1.0) / sigma2;
-            B = (((0.5 * sigma2 - sigma) + 1.0) * sx) / (sigma2 * sigma);
-        } else {
-            const double sn_ = sin(th), cs = cos(th);
-            ra = sn_ / th;
-            rb = (1.0 - cs) / (th * th);
-            const double a = sx * sn_, b = sx * cs, th2 = th * th, c = th2 + sigma * sigma;
-            A = (a * sigma + (1.0 - b) * th) / (th * c);
-            B = (C - ((b - 1.0) * sigma + a * th) / c) / th2;
-        }
-    }
-    double R[9], W[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        const bool diag = i % 4 == 0;
-        R[i] = small_th ? ((diag ? 1.0 : 0.0) + O[i]) + O2[i] : ((diag ? 1.0 : 0.0) + ra * O[i]) + rb * O2[i];
-        W[i] = (A * O[i] + B * O2[i]) + (diag ? C : 0.0);
-    }
-    double qx[4], Rx[9];
-    quat_from_matrix(R, qx);
-    quat_to_matrix(qx, Rx);
-    quat_mul(qx, q, qn);
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const double tx = (W[3 * r] * x[3] + W[3 * r + 1] * x[4]) + W[3 * r + 2] * x[5];
-        tn[r] = sx * ((Rx[3 * r] * t[0] + Rx[3 * r + 1] * t[1]) + Rx[3 * r + 2] * t[2]) + tx;
-    }
-    sn = sx * s;
-}
 
 __device__ inline void make_xf(const double q[4], const double t[3], double s, Xf &F)
 {

@@ -132,9 +132,11 @@ template <int N> struct Staging {
     }
 };
 
-// ---- how the solver and optimiser entry points (pose_opt.hip, sim3.hip, sim3_opt.hip, pnp.hip) begin ----------------------
-// A *_batch_device entry: at most 65535 problems (the grid's y extent), each accepted by check(problem, index); then this
-// thread's workspace, bound without a stream.  ws stays null for an empty batch, which only selects the device.
+// ---- how the solver and optimiser entry points (pose_opt.hip, sim3.hip, sim3_opt.hip, pnp.hip, initializer.hip,
+// new_points.hip, local_ba.hip, essential_graph.hip) begin -------------------------------------------------------------------
+// A *_batch_device entry: at most 65535 problems (the grid's y extent), each accepted by check(problem, index) -- which
+// may also build what the problem needs on the host (essential_graph.hip: its index structure); then this thread's
+// workspace, bound without a stream.  ws stays null for an empty batch, which only selects the device.
 template <typename Ws, typename Problem, typename Check>
 int batch_begin(int32_t n, const Problem *problems, Check check, int32_t device_id, Ws *&ws)
 {
@@ -149,7 +151,8 @@ int batch_begin(int32_t n, const Problem *problems, Check check, int32_t device_
     return ws->bind(device_id, false);
 }
 
-// A host flavour that stages its problem in one carved block each way (sim3.hip, sim3_opt.hip, pnp.hip).  It runs on a
+// A host flavour that stages its problem in one carved block each way (sim3.hip, sim3_opt.hip, pnp.hip, initializer.hip,
+// local_ba.hip, essential_graph.hip).  It runs on a
 // stream of its own and shares the thread's workspace with the device flavours: whatever the thread enqueued through them
 // on other streams must have left it, hence the device-wide wait (pose_opt.hip's does not wait: DESIGN.md 9.21).
 template <typename Ws> int host_begin(int32_t device_id, int in, size_t in_bytes, int out, size_t out_bytes, Ws *&ws)

@@ -79,6 +79,12 @@ static bool run(const std::string &op, const std::vector<double> &a)
     } else if (op == "huber" && a.size() == 4) {
         huber(a[0], a[1], a[2], o[0], o[1], a[3] != 0.0);
         print(o, 2);
+    } else if (op == "lm_trial" && a.size() == 5) {  // cur, tmp, scale, lam, nu -> accepted, lam, nu, rho, stop
+        double lam = a[3], nu = a[4], rho = -7.0;
+        bool stop = false;
+        o[0] = lm_trial(a[0], a[1], a[2], lam, nu, rho, stop) ? 1.0 : 0.0;
+        o[1] = lam, o[2] = nu, o[3] = rho, o[4] = stop ? 1.0 : 0.0;
+        print(o, 5);
     } else if (op == "cholesky_solve6") {
         return cholesky_case<6>(a);
     } else if (op == "cholesky_solve7") {

@@ -1,7 +1,9 @@
-"""csrc/opt_math.h, the FP64 helpers pose_opt.hip and sim3_opt.hip share, against their definition in tests/pose_model.py:
-the header is compiled for the host with g++ (no contraction, AddressSanitizer + UBSan), run once over the cases below, and
-every result has to be the model's, byte for byte.  The optimisers themselves are only compared with the model through
-whole optimisations, within a multiple of its spread; this is the check of the arithmetic on its own."""
+"""csrc/opt_math.h, the FP64 helpers pose_opt.hip, sim3_opt.hip, local_ba.hip and essential_graph.hip share, against their
+definition in tests/pose_model.py: the header is compiled for the host with g++ (no contraction, AddressSanitizer + UBSan),
+run once over the cases below, and every result has to be the model's, byte for byte.  The optimisers themselves are only
+compared with the model through whole optimisations, within a multiple of its spread; this is the check of the arithmetic
+on its own.  What the bundle adjustment adds to the header is in test_opt_math_lba.py, the Sim3 algebra of sim3_math.h in
+test_sim3_math.py."""
 import os
 import subprocess
 import sys
@@ -112,6 +114,43 @@ def _cases():
 CASES = _cases()
 
 
+def _lm_trial(cur, tmp, scale, lam, nu):
+    """The decision on a trial as run_model writes it (pose_model.py, the trial loop): accepted, lam, nu, rho, stop."""
+    with np.errstate(all="ignore"):
+        cur, tmp, scale, lam, nu = (np.float64(v) for v in (cur, tmp, scale, lam, nu))
+        rho = (cur - tmp) / scale
+        if rho > 0 and np.isfinite(tmp):
+            c3 = 2.0 * rho - 1.0
+            alpha = min(1.0 - (c3 * c3) * c3, 2.0 / 3.0)
+            return [1.0, lam * max(1.0 / 3.0, alpha), 2.0, rho, 0.0]
+        lam, nu = lam * nu, nu * 2.0
+        return [0.0, lam, nu, rho, 0.0 if np.isfinite(lam) else 1.0]
+
+
+def _lm_cases():
+    """(name, line, expected): both sides of every decision of lm_trial."""
+    rows = (("accept_floor", (10.0, 1.0, 9.0, 1e-3, 8.0), 1.0, False),        # rho = 1: 1 - 1 = 0, held at 1 / 3
+            ("accept_cap", (10.0, 9.0, 2.0, 1e-3, 8.0), 1.0, False),          # rho = 1 / 2: 1 - 0 = 1, held at 2 / 3
+            ("accept_between", (10.0, 2.5, 8.5, 1e-3, 2.0), 1.0, False),      # rho = 0.88...: the cube itself
+            ("accept_tiny_rho", (10.0, 10.0 - 1e-9, 5.0, 1e-3, 4.0), 1.0, False),
+            ("reject_worse", (10.0, 12.0, 3.0, 1e-3, 2.0), 0.0, False),
+            ("reject_equal", (10.0, 10.0, 3.0, 1e-3, 4.0), 0.0, False),       # rho = 0 is not > 0
+            ("reject_failed_solve", (10.0, M.DBL_MAX, 3.0, 1e-3, 2.0), 0.0, False),
+            ("reject_inf", (10.0, -np.inf, 3.0, 1e-3, 2.0), 0.0, False),      # rho > 0, but the trial's chi2 is not finite
+            ("reject_nan", (10.0, np.nan, 3.0, 1e-3, 2.0), 0.0, False),
+            ("reject_lambda_overflows", (10.0, 12.0, 3.0, 1e300, 1e10), 0.0, True))
+    cases = []
+    for name, args, accepted, stop in rows:
+        want = _lm_trial(*args)
+        assert want[0] == accepted and want[4] == float(stop), name
+        cases.append((name, "lm_trial " + " ".join(float(v).hex() if np.isfinite(v) else repr(float(v)) for v in args),
+                      np.asarray(want, np.float64)))
+    return cases
+
+
+LM_CASES = _lm_cases()
+
+
 @pytest.fixture(scope="module")
 def results(tmp_path_factory):
     d = tmp_path_factory.mktemp("opt_math")
@@ -119,13 +158,22 @@ def results(tmp_path_factory):
     subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                     "-I" + os.path.join(ROOT, "orb_slam2_map_amd", "csrc"), os.path.join(ROOT, "tests", "opt_math_test.cpp"),
                     "-o", exe], check=True)
+    every = CASES + LM_CASES
     with open(inp, "w") as f:
-        f.write("".join(line + "\n" for _, line, _ in CASES))
+        f.write("".join(line + "\n" for _, line, _ in every))
     r = subprocess.run([exe, inp], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0 and not r.stderr, r.stderr  # no sanitizer report either
     lines = r.stdout.splitlines()
-    assert len(lines) == len(CASES)
-    return {name: np.array([float.fromhex(t) for t in out.split()], np.float64) for (name, _, _), out in zip(CASES, lines)}
+    assert len(lines) == len(every)
+    return {name: np.array([float.fromhex(t) for t in out.split()], np.float64) for (name, _, _), out in zip(every, lines)}
+
+
+@pytest.mark.parametrize("name", [name for name, _, _ in LM_CASES])
+def test_lm_trial_equals_the_models_decision(results, name):
+    expected = next(e for n, _, e in LM_CASES if n == name)
+    got = results[name]
+    nan = np.isnan(expected)
+    assert np.array_equal(np.isnan(got), nan) and got[~nan].tobytes() == expected[~nan].tobytes(), (name, got, expected)
 
 
 def test_case_list_covers_the_issue():

@@ -148,13 +148,13 @@ def test_ransac_max_iterations_equals_both_models(tmp_path):
 
 
 def test_solver_entry_points_share_one_host_scaffold():
-    """The four solver / optimiser units keep no layout arithmetic, no entry prologue and no iteration-cap expression of
+    """The solver / optimiser units keep no layout arithmetic, no entry prologue and no iteration-cap expression of
     their own: the offsets are carve.h's, the typed pointers and the two beginnings staging.h's, the cap ransac_host.h's --
     and the two new headers stay compilable without HIP."""
     import re
     csrc = os.path.join(ROOT, "orb_slam2_map_amd", "csrc")
     read = lambda name: open(os.path.join(csrc, name)).read()  # noqa: E731
-    for name in ("pose_opt.hip", "sim3.hip", "sim3_opt.hip", "pnp.hip"):
+    for name in ("pose_opt.hip", "sim3.hip", "sim3_opt.hip", "pnp.hip", "local_ba.hip", "essential_graph.hip"):
         src = read(name)
         assert "auto pad =" not in src, name
         assert not re.search(r"reinterpret_cast<[^>]*>\s*\(\s*d(in|out)\b", src), name
@@ -162,6 +162,8 @@ def test_solver_entry_points_share_one_host_scaffold():
     for name in ("sim3.hip", "sim3_opt.hip", "pnp.hip"):
         src = read(name)
         assert "hipDeviceSynchronize" not in src and "host_begin(" in src and "Carver in(16), out(16);" in src, name
+    for name in ("local_ba.hip", "essential_graph.hip"):  # one staging block for the outputs (local_ba) or each way
+        assert "hipDeviceSynchronize" not in read(name) and "host_begin(" in read(name), name
     for name in ("sim3.hip", "pnp.hip"):
         assert "std::pow(" not in read(name) and "ransac_max_iterations(" in read(name), name
     for name in ("sim3.hip", "pnp.hip", "map_table.hip"):
