@@ -684,57 +684,40 @@ extern "C" int orbgpu_essential_graph(const orbgpu_essential_graph_problem *p, c
     if (rc != ORBGPU_OK || (rc = check_points(p->n_vertices, n_points)) != ORBGPU_OK)
         return rc;
     ORBGPU_REQUIRE((p->n_vertices == 0 || Tiw) && (n_points == 0 || (world_pos && point_ref && pos_out)), "null argument");
-    // one staging block each way; every segment starts on a multiple of 16 bytes
+    // the stop flag as sampled now and one staging block each way; the outputs are in/out: what a call stopped at once leaves
+    // alone goes back as it came
     const size_t V = (size_t)p->n_vertices, M = (size_t)n_points;
-    Carver in(16), out(16);
-    const size_t i_scw = in.take(64 * std::max<size_t>(V, 1)), i_pos = in.take(12 * std::max<size_t>(M, 1)),
-                 i_ref = in.take(4 * std::max<size_t>(M, 1));
-    const size_t o_res = out.take(sizeof(orbgpu_essential_graph_result)), o_Sd = out.take(64 * std::max<size_t>(V, 1)),
-                 o_T = out.take(64 * std::max<size_t>(V, 1)), o_X = out.take(12 * std::max<size_t>(M, 1));
+    const int32_t stop_now = stop ? *stop : 0;
+    orbgpu_essential_graph_result r;
+    HostPlan<N_BUF> plan;
+    const auto i_stop = plan.in(H_STOP, &stop_now, 1);
+    const auto i_scw = plan.in(H_IN, p->Scw, V, 8);
+    const auto i_pos = plan.in(H_IN, world_pos, M, 3);
+    const auto i_ref = plan.in(H_IN, point_ref, M);
+    const auto o_res = plan.out(H_OUT, &r, 1);
+    const auto o_Sd = plan.inout(H_OUT, Siw_d, V, 8);
+    const auto o_T = plan.inout(H_OUT, Tiw, V, 16), o_X = plan.inout(H_OUT, pos_out, M, 3);
     EgWs *wsp;
-    if ((rc = host_begin(device_id, H_IN, in.off, H_OUT, out.off, wsp)) != ORBGPU_OK)
+    if ((rc = host_begin(device_id, plan, wsp)) != ORBGPU_OK)
         return rc;
     EgWs &ws = *wsp;
     EgWs::FinishOnError on_error{ws};
-    ws.reserve(H_STOP, 16);
-    const int32_t stop_now = stop ? *stop : 0;
-    ws.upload(H_STOP, &stop_now, sizeof(stop_now));
-    if (V)
-        ws.upload(H_IN, p->Scw, 64 * V, i_scw);
-    if (M) {
-        ws.upload(H_IN, world_pos, 12 * M, i_pos);
-        ws.upload(H_IN, point_ref, 4 * M, i_ref);
-    }
-    // in/out: what a call stopped at once leaves alone goes back as it came
-    if (V && Siw_d)
-        ws.upload(H_OUT, Siw_d, 64 * V, o_Sd);
-    if (V)
-        ws.upload(H_OUT, Tiw, 64 * V, o_T);
-    if (M)
-        ws.upload(H_OUT, pos_out, 12 * M, o_X);
+    plan.upload(ws);
     if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
     orbgpu_essential_graph_problem d = *p;
-    d.d_stop = stop ? ws.as<int32_t>(H_STOP) : nullptr;
-    d.d_Siw_d = ws.at<double>(H_OUT, o_Sd), d.d_Tiw = ws.at<float>(H_OUT, o_T);
-    d.d_result = ws.at<orbgpu_essential_graph_result>(H_OUT, o_res);
+    d.d_stop = stop ? ws.at(i_stop) : nullptr;
+    d.d_Siw_d = ws.at(o_Sd), d.d_Tiw = ws.at(o_T);
+    d.d_result = ws.at(o_res);
     if ((rc = enqueue(1, &d, ix, ws, ws.stream)) != ORBGPU_OK)
         return rc;
     // the sampled flag is the one the kernel reads first: a call stopped at once has written no state to correct with
     if (M && !stop_now &&
-        (rc = orbgpu_essential_graph_correct_points_device(p->n_vertices, ws.at<double>(H_IN, i_scw), d.d_Siw_d, n_points,
-                                                           ws.at<float>(H_IN, i_pos), ws.at<int32_t>(H_IN, i_ref),
-                                                           ws.at<float>(H_OUT, o_X), &d.d_result->n_bad_ref, device_id,
+        (rc = orbgpu_essential_graph_correct_points_device(p->n_vertices, ws.at(i_scw), d.d_Siw_d, n_points, ws.at(i_pos),
+                                                           ws.at(i_ref), ws.at(o_X), &d.d_result->n_bad_ref, device_id,
                                                            ws.stream)) != ORBGPU_OK)
         return rc;
-    orbgpu_essential_graph_result r;
-    ws.download(&r, H_OUT, sizeof(r), o_res);
-    if (V && Siw_d)
-        ws.download(Siw_d, H_OUT, 64 * V, o_Sd);
-    if (V)
-        ws.download(Tiw, H_OUT, 64 * V, o_T);
-    if (M)
-        ws.download(pos_out, H_OUT, 12 * M, o_X);
+    plan.download(ws);
     if ((rc = ws.finish()) != ORBGPU_OK)
         return rc;
     if (result)

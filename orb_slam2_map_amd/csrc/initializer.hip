@@ -892,53 +892,36 @@ static int init_host(const orbgpu_init_problem *p, float *scores_h, float *score
             for (int k = 0; k < 8; k++)
                 ORBGPU_REQUIRE(p->sets[(size_t)h * 8 + k] >= 0 && p->sets[(size_t)h * 8 + k] < N, "set %d: index %d outside [0, %d)", h,
                                p->sets[(size_t)h * 8 + k], N);
-    const size_t words = (size_t)(n1 + 63) / 64, c1 = (size_t)std::max(n1, 1), c2 = (size_t)std::max(n2, 1), cH = (size_t)std::max(H, 1),
-                 w1 = std::max<size_t>(words, 1);
-    Carver in(16), out(16);
-    const size_t i_k1 = in.take(8 * c1), i_k2 = in.take(8 * c2), i_m = in.take(4 * c1), i_s = in.take(32 * cH);
-    const size_t o_res = out.take(sizeof(orbgpu_init_result)), o_p = out.take(12 * c1), o_t = out.take(c1), o_sh = out.take(4 * cH),
-                 o_sf = out.take(4 * cH), o_mh = out.take(8 * cH * w1), o_mf = out.take(8 * cH * w1);
+    // one staging block each way
+    const size_t words = (size_t)(n1 + 63) / 64;
+    orbgpu_init_result r;
+    HostPlan<N_BUF> plan;
+    const auto i_k1 = plan.in(H_IN, p->kp1, n1, 2), i_k2 = plan.in(H_IN, p->kp2, n2, 2);
+    const auto i_m = plan.in(H_IN, p->matches12, n1), i_s = plan.in(H_IN, p->sets, H, 8);
+    const auto o_res = plan.out(H_OUT, &r, 1);
+    const auto o_p = plan.out(H_OUT, P3D, n1, 3);
+    const auto o_t = plan.out(H_OUT, triangulated, n1);
+    const auto o_sh = plan.out(H_OUT, all ? scores_h : nullptr, H), o_sf = plan.out(H_OUT, all ? scores_f : nullptr, H);
+    const auto o_mh = plan.out(H_OUT, all ? masks_h : nullptr, H, words), o_mf = plan.out(H_OUT, all ? masks_f : nullptr, H, words);
     InitWs *wsp;
-    if ((rc = host_begin(device_id, H_IN, in.off, H_OUT, out.off, wsp)) != ORBGPU_OK)
+    if ((rc = host_begin(device_id, plan, wsp)) != ORBGPU_OK)
         return rc;
     InitWs &ws = *wsp;
     InitWs::FinishOnError on_error{ws};
-    if (n1 > 0) {
-        ws.upload(H_IN, p->kp1, 8 * (size_t)n1, i_k1);
-        ws.upload(H_IN, p->matches12, 4 * (size_t)n1, i_m);
-    }
-    if (n2 > 0)
-        ws.upload(H_IN, p->kp2, 8 * (size_t)n2, i_k2);
-    if (H > 0)
-        ws.upload(H_IN, p->sets, 32 * (size_t)H, i_s);
+    plan.upload(ws);
     if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
-    ORBGPU_HIP_TRY(hipMemsetAsync(ws.as<char>(H_OUT), 0, out.off, ws.stream));
+    ORBGPU_HIP_TRY(hipMemsetAsync(ws.as<char>(H_OUT), 0, plan.bytes(H_OUT), ws.stream));
     orbgpu_init_problem d = *p;
-    d.kp1 = ws.at<float>(H_IN, i_k1), d.kp2 = ws.at<float>(H_IN, i_k2), d.matches12 = ws.at<int32_t>(H_IN, i_m);
-    d.sets = ws.at<int32_t>(H_IN, i_s);
-    d.result = ws.at<orbgpu_init_result>(H_OUT, o_res), d.P3D = ws.at<float>(H_OUT, o_p), d.triangulated = ws.at<uint8_t>(H_OUT, o_t);
-    d.scores_h = ws.at<float>(H_OUT, o_sh), d.scores_f = ws.at<float>(H_OUT, o_sf);
-    d.masks_h = ws.at<uint64_t>(H_OUT, o_mh), d.masks_f = ws.at<uint64_t>(H_OUT, o_mf);
+    d.kp1 = ws.at(i_k1), d.kp2 = ws.at(i_k2), d.matches12 = ws.at(i_m);
+    d.sets = ws.at(i_s);
+    d.result = ws.at(o_res), d.P3D = ws.at(o_p), d.triangulated = ws.at(o_t);
+    d.scores_h = ws.at(o_sh), d.scores_f = ws.at(o_sf);
+    d.masks_h = ws.at(o_mh), d.masks_f = ws.at(o_mf);
     d.R21 = d.t21 = nullptr;
     if ((rc = orbgpu_initializer_batch_device(1, &d, device_id, ws.stream)) != ORBGPU_OK)
         return rc;
-    orbgpu_init_result r;
-    ws.download(&r, H_OUT, sizeof(r), o_res);
-    if (P3D && n1 > 0)
-        ws.download(P3D, H_OUT, 12 * (size_t)n1, o_p);
-    if (triangulated && n1 > 0)
-        ws.download(triangulated, H_OUT, (size_t)n1, o_t);
-    if (all && H > 0) {
-        if (scores_h)
-            ws.download(scores_h, H_OUT, 4 * (size_t)H, o_sh);
-        if (scores_f)
-            ws.download(scores_f, H_OUT, 4 * (size_t)H, o_sf);
-        if (masks_h && words > 0)
-            ws.download(masks_h, H_OUT, 8 * words * (size_t)H, o_mh);
-        if (masks_f && words > 0)
-            ws.download(masks_f, H_OUT, 8 * words * (size_t)H, o_mf);
-    }
+    plan.download(ws);
     if ((rc = ws.finish()) != ORBGPU_OK)
         return rc;
     if (r.best_motion >= 0 && r.n_good[r.best_motion] > 0)

@@ -870,6 +870,47 @@ extern "C" int orbgpu_local_ba_last_spills(int32_t device_id, int32_t *problems_
     return last_spills<LbaWs>(device_id, SPILL_COUNT, "no local bundle adjustment recorded on this thread", problems_spilled);
 }
 
+// The host flavour of either bundle adjustment: the stop flag as sampled now, and one staging block for the outputs -- all
+// in/out, so that what a stopped call or a skipped edge leaves alone goes back as it came.  `flag` is erase [n_edges] or
+// not_included [n_points], at the problem's member d_flag; `batch` the family's *_batch_device.
+template <typename Ws, typename Problem, typename Result>
+static int ba_host(const Problem &p, size_t n_rows, uint8_t *flag, size_t n_flag, uint8_t *Problem::*d_flag,
+                   int (*batch)(int32_t, const Problem *, int32_t, void *), const int32_t *stop, double *Tcw_d, float *Tcw,
+                   double *pos_d, float *pos, Result *result, int32_t device_id)
+{
+    const int32_t stop_now = stop ? *stop : 0;
+    Result r;
+    HostPlan<N_BUF> plan;
+    const auto i_stop = plan.in(H_STOP, &stop_now, 1);
+    const auto o_res = plan.out(H_OUT, &r, 1);
+    const auto o_Td = plan.inout(H_OUT, Tcw_d, n_rows, 16);
+    const auto o_T = plan.inout(H_OUT, Tcw, n_rows, 16);
+    const auto o_Xd = plan.inout(H_OUT, pos_d, (size_t)p.n_points, 3);
+    const auto o_X = plan.inout(H_OUT, pos, (size_t)p.n_points, 3);
+    const auto o_flag = plan.inout(H_OUT, flag, n_flag);
+    Ws *wsp;
+    int rc = host_begin(device_id, plan, wsp);
+    if (rc != ORBGPU_OK)
+        return rc;
+    Ws &ws = *wsp;
+    typename Ws::FinishOnError on_error{ws};
+    plan.upload(ws);
+    if ((rc = ws.status()) != ORBGPU_OK)
+        return rc;
+    Problem d = p;
+    d.d_stop = stop ? ws.at(i_stop) : nullptr;
+    d.d_Tcw_d = ws.at(o_Td), d.d_Tcw = ws.at(o_T), d.d_pos_d = ws.at(o_Xd), d.d_pos = ws.at(o_X);
+    d.*d_flag = ws.at(o_flag), d.d_result = ws.at(o_res);
+    if ((rc = batch(1, &d, device_id, ws.stream)) != ORBGPU_OK)
+        return rc;
+    plan.download(ws);
+    if ((rc = ws.finish()) != ORBGPU_OK)
+        return rc;
+    if (result)
+        *result = r;
+    return ORBGPU_OK;
+}
+
 extern "C" int orbgpu_local_ba(const orbgpu_local_ba_problem *p, const int32_t *stop, double *Tcw_d, float *Tcw, double *pos_d,
                                float *pos, uint8_t *erase, orbgpu_local_ba_result *result, int32_t device_id)
 {
@@ -878,56 +919,8 @@ extern "C" int orbgpu_local_ba(const orbgpu_local_ba_problem *p, const int32_t *
     if (rc != ORBGPU_OK)
         return rc;
     ORBGPU_REQUIRE((p->n_local == 0 || Tcw) && (p->n_points == 0 || pos) && (p->n_edges == 0 || erase), "null output");
-    // one staging block for the outputs; every segment starts on a multiple of 16 bytes
-    const size_t nl = (size_t)p->n_local, M = (size_t)p->n_points, E = (size_t)p->n_edges;
-    Carver out(16);
-    const size_t o_res = out.take(sizeof(orbgpu_local_ba_result)), o_Td = out.take(128 * std::max<size_t>(nl, 1)),
-                 o_T = out.take(64 * std::max<size_t>(nl, 1)), o_Xd = out.take(24 * std::max<size_t>(M, 1)),
-                 o_X = out.take(12 * std::max<size_t>(M, 1)), o_er = out.take(std::max<size_t>(E, 1));
-    LbaWs *wsp;
-    if ((rc = host_begin(device_id, H_STOP, 16, H_OUT, out.off, wsp)) != ORBGPU_OK)
-        return rc;
-    LbaWs &ws = *wsp;
-    LbaWs::FinishOnError on_error{ws};
-    const int32_t stop_now = stop ? *stop : 0;
-    ws.upload(H_STOP, &stop_now, sizeof(stop_now));
-    // in/out: what a stopped call or a skipped edge leaves alone goes back as it came
-    if (nl && Tcw_d)
-        ws.upload(H_OUT, Tcw_d, 128 * nl, o_Td);
-    if (nl)
-        ws.upload(H_OUT, Tcw, 64 * nl, o_T);
-    if (M && pos_d)
-        ws.upload(H_OUT, pos_d, 24 * M, o_Xd);
-    if (M)
-        ws.upload(H_OUT, pos, 12 * M, o_X);
-    if (E)
-        ws.upload(H_OUT, erase, E, o_er);
-    if ((rc = ws.status()) != ORBGPU_OK)
-        return rc;
-    orbgpu_local_ba_problem d = *p;
-    d.d_stop = stop ? ws.as<int32_t>(H_STOP) : nullptr;
-    d.d_Tcw_d = ws.at<double>(H_OUT, o_Td), d.d_Tcw = ws.at<float>(H_OUT, o_T);
-    d.d_pos_d = ws.at<double>(H_OUT, o_Xd), d.d_pos = ws.at<float>(H_OUT, o_X);
-    d.d_erase = ws.at<uint8_t>(H_OUT, o_er), d.d_result = ws.at<orbgpu_local_ba_result>(H_OUT, o_res);
-    if ((rc = orbgpu_local_ba_batch_device(1, &d, device_id, ws.stream)) != ORBGPU_OK)
-        return rc;
-    orbgpu_local_ba_result r;
-    ws.download(&r, H_OUT, sizeof(r), o_res);
-    if (nl && Tcw_d)
-        ws.download(Tcw_d, H_OUT, 128 * nl, o_Td);
-    if (nl)
-        ws.download(Tcw, H_OUT, 64 * nl, o_T);
-    if (M && pos_d)
-        ws.download(pos_d, H_OUT, 24 * M, o_Xd);
-    if (M)
-        ws.download(pos, H_OUT, 12 * M, o_X);
-    if (E)
-        ws.download(erase, H_OUT, E, o_er);
-    if ((rc = ws.finish()) != ORBGPU_OK)
-        return rc;
-    if (result)
-        *result = r;
-    return ORBGPU_OK;
+    return ba_host<LbaWs>(*p, (size_t)p->n_local, erase, (size_t)p->n_edges, &orbgpu_local_ba_problem::d_erase,
+                          orbgpu_local_ba_batch_device, stop, Tcw_d, Tcw, pos_d, pos, result, device_id);
 }
 
 // ---- Optimizer::BundleAdjustment / GlobalBundleAdjustemnt (B1-B7): the same host side over the other kernel ----------------
@@ -965,54 +958,7 @@ extern "C" int orbgpu_bundle_adjustment(const orbgpu_bundle_adjustment_problem *
     if (rc != ORBGPU_OK)
         return rc;
     ORBGPU_REQUIRE((p->n_poses == 0 || Tcw) && (p->n_points == 0 || (pos && not_included)), "null output");
-    // one staging block for the outputs; every segment starts on a multiple of 16 bytes
-    const size_t np = (size_t)p->n_poses, M = (size_t)p->n_points;
-    Carver out(16);
-    const size_t o_res = out.take(sizeof(orbgpu_bundle_adjustment_result)), o_Td = out.take(128 * std::max<size_t>(np, 1)),
-                 o_T = out.take(64 * std::max<size_t>(np, 1)), o_Xd = out.take(24 * std::max<size_t>(M, 1)),
-                 o_X = out.take(12 * std::max<size_t>(M, 1)), o_ni = out.take(std::max<size_t>(M, 1));
-    BaWs *wsp;
-    if ((rc = host_begin(device_id, H_STOP, 16, H_OUT, out.off, wsp)) != ORBGPU_OK)
-        return rc;
-    BaWs &ws = *wsp;
-    BaWs::FinishOnError on_error{ws};
-    const int32_t stop_now = stop ? *stop : 0;
-    ws.upload(H_STOP, &stop_now, sizeof(stop_now));
-    // in/out: what a call stopped at once leaves alone goes back as it came
-    if (np && Tcw_d)
-        ws.upload(H_OUT, Tcw_d, 128 * np, o_Td);
-    if (np)
-        ws.upload(H_OUT, Tcw, 64 * np, o_T);
-    if (M && pos_d)
-        ws.upload(H_OUT, pos_d, 24 * M, o_Xd);
-    if (M)
-        ws.upload(H_OUT, pos, 12 * M, o_X);
-    if (M)
-        ws.upload(H_OUT, not_included, M, o_ni);
-    if ((rc = ws.status()) != ORBGPU_OK)
-        return rc;
-    orbgpu_bundle_adjustment_problem d = *p;
-    d.d_stop = stop ? ws.as<int32_t>(H_STOP) : nullptr;
-    d.d_Tcw_d = ws.at<double>(H_OUT, o_Td), d.d_Tcw = ws.at<float>(H_OUT, o_T);
-    d.d_pos_d = ws.at<double>(H_OUT, o_Xd), d.d_pos = ws.at<float>(H_OUT, o_X);
-    d.d_not_included = ws.at<uint8_t>(H_OUT, o_ni), d.d_result = ws.at<orbgpu_bundle_adjustment_result>(H_OUT, o_res);
-    if ((rc = orbgpu_bundle_adjustment_batch_device(1, &d, device_id, ws.stream)) != ORBGPU_OK)
-        return rc;
-    orbgpu_bundle_adjustment_result r;
-    ws.download(&r, H_OUT, sizeof(r), o_res);
-    if (np && Tcw_d)
-        ws.download(Tcw_d, H_OUT, 128 * np, o_Td);
-    if (np)
-        ws.download(Tcw, H_OUT, 64 * np, o_T);
-    if (M && pos_d)
-        ws.download(pos_d, H_OUT, 24 * M, o_Xd);
-    if (M)
-        ws.download(pos, H_OUT, 12 * M, o_X);
-    if (M)
-        ws.download(not_included, H_OUT, M, o_ni);
-    if ((rc = ws.finish()) != ORBGPU_OK)
-        return rc;
-    if (result)
-        *result = r;
-    return ORBGPU_OK;
+    return ba_host<BaWs>(*p, (size_t)p->n_poses, not_included, (size_t)p->n_points,
+                         &orbgpu_bundle_adjustment_problem::d_not_included, orbgpu_bundle_adjustment_batch_device, stop, Tcw_d, Tcw,
+                         pos_d, pos, result, device_id);
 }

@@ -926,49 +926,37 @@ static int solve_host(const orbgpu_pnp_problem *p, int32_t *counts, float *Tcw, 
         for (int k = 0; k < ms; k++)
             ORBGPU_REQUIRE(p->sets[(size_t)h * ms + k] >= 0 && p->sets[(size_t)h * ms + k] < N, "set %d: index %d outside [0, %d)", h,
                            p->sets[(size_t)h * ms + k], N);
-    const size_t words = (size_t)(n1 + 63) / 64, c1 = (size_t)std::max(n1, 1), cH = (size_t)std::max(H, 1), w1 = std::max<size_t>(words, 1);
-    Carver in(16), out(16);
-    const size_t i_valid = in.take(c1), i_x = in.take(12 * c1), i_kp = in.take(8 * c1), i_o = in.take(4 * c1),
-                 i_s = in.take(4 * cH * (size_t)ms);
-    const size_t o_res = out.take(sizeof(orbgpu_pnp_result)), o_cnt = out.take(4 * cH), o_T = out.take(64 * cH),
-                 o_rm = out.take(8 * w1), o_m = out.take(8 * cH * w1);
+    // one staging block each way; the words of the returned mask land in `mask` in either flavour
+    const size_t words = (size_t)(n1 + 63) / 64;
+    orbgpu_pnp_result r;
+    std::vector<uint64_t> mask(std::max<size_t>(words, 1), 0);
+    HostPlan<N_BUF> plan;
+    const auto i_valid = plan.in(H_IN, p->valid, n1);
+    const auto i_x = plan.in(H_IN, p->Xw, n1, 3), i_kp = plan.in(H_IN, p->kp, n1, 2);
+    const auto i_o = plan.in(H_IN, p->octave, n1), i_s = plan.in(H_IN, p->sets, H, ms);
+    const auto o_res = plan.out(H_OUT, &r, 1);
+    const auto o_cnt = plan.out(H_OUT, counts, H);
+    const auto o_T = plan.out(H_OUT, all ? Tcw : nullptr, H, 16);
+    const auto o_rm = plan.out(H_OUT, mask.data(), 1, words), o_m = plan.out(H_OUT, masks, H, words);
     PnpWs *wsp;
-    if ((rc = host_begin(device_id, H_IN, in.off, H_OUT, out.off, wsp)) != ORBGPU_OK)
+    if ((rc = host_begin(device_id, plan, wsp)) != ORBGPU_OK)
         return rc;
     PnpWs &ws = *wsp;
     PnpWs::FinishOnError on_error{ws};
-    if (n1 > 0) {
-        ws.upload(H_IN, p->valid, (size_t)n1, i_valid);
-        ws.upload(H_IN, p->Xw, 12 * (size_t)n1, i_x);
-        ws.upload(H_IN, p->kp, 8 * (size_t)n1, i_kp);
-        ws.upload(H_IN, p->octave, 4 * (size_t)n1, i_o);
-    }
-    if (H > 0)
-        ws.upload(H_IN, p->sets, 4 * (size_t)H * (size_t)ms, i_s);
+    plan.upload(ws);
     if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
-    ORBGPU_HIP_TRY(hipMemsetAsync(ws.as<char>(H_OUT), 0, out.off, ws.stream));  // hypotheses beyond n_use come back as zeros
+    // hypotheses beyond n_use come back as zeros
+    ORBGPU_HIP_TRY(hipMemsetAsync(ws.as<char>(H_OUT), 0, plan.bytes(H_OUT), ws.stream));
     orbgpu_pnp_problem d = *p;
-    d.valid = ws.at<uint8_t>(H_IN, i_valid), d.Xw = ws.at<float>(H_IN, i_x), d.kp = ws.at<float>(H_IN, i_kp);
-    d.octave = ws.at<int32_t>(H_IN, i_o), d.sets = ws.at<int32_t>(H_IN, i_s);
-    d.result = ws.at<orbgpu_pnp_result>(H_OUT, o_res), d.counts = ws.at<int32_t>(H_OUT, o_cnt), d.Tcw = ws.at<float>(H_OUT, o_T);
-    d.refined_mask = ws.at<uint64_t>(H_OUT, o_rm), d.masks = ws.at<uint64_t>(H_OUT, o_m);
+    d.valid = ws.at(i_valid), d.Xw = ws.at(i_x), d.kp = ws.at(i_kp);
+    d.octave = ws.at(i_o), d.sets = ws.at(i_s);
+    d.result = ws.at(o_res), d.counts = ws.at(o_cnt), d.Tcw = ws.at(o_T);
+    d.refined_mask = ws.at(o_rm), d.masks = ws.at(o_m);
     d.indices = nullptr;
     if ((rc = orbgpu_pnp_solve_batch_device(1, &d, device_id, ws.stream)) != ORBGPU_OK)
         return rc;
-    orbgpu_pnp_result r;
-    std::vector<uint64_t> mask(w1, 0);
-    ws.download(&r, H_OUT, sizeof(r), o_res);
-    if (counts && H > 0)
-        ws.download(counts, H_OUT, 4 * (size_t)H, o_cnt);
-    if (words > 0)
-        ws.download(mask.data(), H_OUT, 8 * words, o_rm);
-    if (all && H > 0) {
-        if (Tcw)
-            ws.download(Tcw, H_OUT, 64 * (size_t)H, o_T);
-        if (masks && words > 0)
-            ws.download(masks, H_OUT, 8 * words * (size_t)H, o_m);
-    }
+    plan.download(ws);
     if ((rc = ws.finish()) != ORBGPU_OK)
         return rc;
     if (all) {

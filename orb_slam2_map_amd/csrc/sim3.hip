@@ -500,57 +500,39 @@ static int solve_host(const orbgpu_sim3_problem *p, int32_t *counts, float *R, f
         for (int k = 0; k < 3; k++)
             ORBGPU_REQUIRE(p->triples[3 * h + k] >= 0 && p->triples[3 * h + k] < N, "triple %d: index %d outside [0, %d)", h,
                            p->triples[3 * h + k], N);
-    // one staging block each way; every segment starts on a multiple of 16 bytes
-    const size_t words = (size_t)(n1 + 63) / 64, c1 = (size_t)std::max(n1, 1), cH = (size_t)std::max(H, 1);
-    Carver in(16), out(16);
-    const size_t i_valid = in.take(c1), i_x1 = in.take(12 * c1), i_x2 = in.take(12 * c1), i_o1 = in.take(4 * c1),
-                 i_o2 = in.take(4 * c1), i_tr = in.take(12 * cH);
-    const size_t o_res = out.take(sizeof(orbgpu_sim3_result)), o_cnt = out.take(4 * cH), o_R = out.take(36 * cH),
-                 o_t = out.take(12 * cH), o_s = out.take(4 * cH), o_T = out.take(64 * cH),
-                 o_m = out.take(8 * cH * std::max<size_t>(words, 1));
+    // one staging block each way; all = false fetches its rows of R / t / s / T12 / masks after the launch, below
+    const size_t words = (size_t)(n1 + 63) / 64;
+    orbgpu_sim3_result r;
+    HostPlan<N_BUF> plan;
+    const auto i_valid = plan.in(H_IN, p->valid, n1);
+    const auto i_x1 = plan.in(H_IN, p->Xw1, n1, 3), i_x2 = plan.in(H_IN, p->Xw2, n1, 3);
+    const auto i_o1 = plan.in(H_IN, p->octave1, n1), i_o2 = plan.in(H_IN, p->octave2, n1);
+    const auto i_tr = plan.in(H_IN, p->triples, H, 3);
+    const auto o_res = plan.out(H_OUT, &r, 1);
+    const auto o_cnt = plan.out(H_OUT, counts, H);
+    const auto o_R = plan.out(H_OUT, all ? R : nullptr, H, 9), o_t = plan.out(H_OUT, all ? t : nullptr, H, 3);
+    const auto o_s = plan.out(H_OUT, all ? s : nullptr, H), o_T = plan.out(H_OUT, all ? T12 : nullptr, H, 16);
+    const auto o_m = plan.out(H_OUT, masks, H, words);
     Sim3Ws *wsp;
-    if ((rc = host_begin(device_id, H_IN, in.off, H_OUT, out.off, wsp)) != ORBGPU_OK)
+    if ((rc = host_begin(device_id, plan, wsp)) != ORBGPU_OK)
         return rc;
     Sim3Ws &ws = *wsp;
     Sim3Ws::FinishOnError on_error{ws};
-    if (n1 > 0) {
-        ws.upload(H_IN, p->valid, (size_t)n1, i_valid);
-        ws.upload(H_IN, p->Xw1, 12 * (size_t)n1, i_x1);
-        ws.upload(H_IN, p->Xw2, 12 * (size_t)n1, i_x2);
-        ws.upload(H_IN, p->octave1, 4 * (size_t)n1, i_o1);
-        ws.upload(H_IN, p->octave2, 4 * (size_t)n1, i_o2);
-    }
-    if (H > 0)
-        ws.upload(H_IN, p->triples, 12 * (size_t)H, i_tr);
+    plan.upload(ws);
     if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
     if (all)  // hypotheses beyond n_use are not written by the kernels: they come back as zeros
-        ORBGPU_HIP_TRY(hipMemsetAsync(ws.as<char>(H_OUT), 0, out.off, ws.stream));
+        ORBGPU_HIP_TRY(hipMemsetAsync(ws.as<char>(H_OUT), 0, plan.bytes(H_OUT), ws.stream));
     orbgpu_sim3_problem d = *p;
-    d.valid = ws.at<uint8_t>(H_IN, i_valid), d.Xw1 = ws.at<float>(H_IN, i_x1), d.Xw2 = ws.at<float>(H_IN, i_x2);
-    d.octave1 = ws.at<int32_t>(H_IN, i_o1), d.octave2 = ws.at<int32_t>(H_IN, i_o2), d.triples = ws.at<int32_t>(H_IN, i_tr);
-    d.result = ws.at<orbgpu_sim3_result>(H_OUT, o_res), d.counts = ws.at<int32_t>(H_OUT, o_cnt);
-    d.R = ws.at<float>(H_OUT, o_R), d.t = ws.at<float>(H_OUT, o_t), d.s = ws.at<float>(H_OUT, o_s);
-    d.T12 = ws.at<float>(H_OUT, o_T), d.masks = ws.at<uint64_t>(H_OUT, o_m);
+    d.valid = ws.at(i_valid), d.Xw1 = ws.at(i_x1), d.Xw2 = ws.at(i_x2);
+    d.octave1 = ws.at(i_o1), d.octave2 = ws.at(i_o2), d.triples = ws.at(i_tr);
+    d.result = ws.at(o_res), d.counts = ws.at(o_cnt);
+    d.R = ws.at(o_R), d.t = ws.at(o_t), d.s = ws.at(o_s);
+    d.T12 = ws.at(o_T), d.masks = ws.at(o_m);
     d.indices1 = nullptr;
     if ((rc = orbgpu_sim3_solve_batch_device(1, &d, device_id, ws.stream)) != ORBGPU_OK)
         return rc;
-    orbgpu_sim3_result r;
-    ws.download(&r, H_OUT, sizeof(r), o_res);
-    if (counts && H > 0)
-        ws.download(counts, H_OUT, 4 * (size_t)H, o_cnt);
-    if (all && H > 0) {
-        if (R)
-            ws.download(R, H_OUT, 36 * (size_t)H, o_R);
-        if (t)
-            ws.download(t, H_OUT, 12 * (size_t)H, o_t);
-        if (s)
-            ws.download(s, H_OUT, 4 * (size_t)H, o_s);
-        if (T12)
-            ws.download(T12, H_OUT, 64 * (size_t)H, o_T);
-        if (masks && words > 0)
-            ws.download(masks, H_OUT, 8 * words * (size_t)H, o_m);
-    }
+    plan.download(ws);
     if ((rc = ws.finish()) != ORBGPU_OK)
         return rc;
     if (all) {
@@ -560,17 +542,17 @@ static int solve_host(const orbgpu_sim3_problem *p, int32_t *counts, float *R, f
     const int b = r.best_iteration;
     if (b >= 0 && b < H) {
         if (R)
-            ws.download(R, H_OUT, 36, o_R + 36 * (size_t)b);
+            ws.download(R, H_OUT, 36, o_R.off + 36 * (size_t)b);
         if (t)
-            ws.download(t, H_OUT, 12, o_t + 12 * (size_t)b);
+            ws.download(t, H_OUT, 12, o_t.off + 12 * (size_t)b);
         if (s)
-            ws.download(s, H_OUT, 4, o_s + 4 * (size_t)b);
+            ws.download(s, H_OUT, 4, o_s.off + 4 * (size_t)b);
         if (T12)
-            ws.download(T12, H_OUT, 64, o_T + 64 * (size_t)b);
+            ws.download(T12, H_OUT, 64, o_T.off + 64 * (size_t)b);
     }
     std::vector<uint64_t> mask(std::max<size_t>(words, 1), 0);
     if (r.accepted >= 0 && words > 0)
-        ws.download(mask.data(), H_OUT, 8 * words, o_m + 8 * words * (size_t)r.accepted);
+        ws.download(mask.data(), H_OUT, 8 * words, o_m.off + 8 * words * (size_t)r.accepted);
     if ((rc = ws.finish()) != ORBGPU_OK)
         return rc;
     if (inliers)

@@ -560,41 +560,32 @@ extern "C" int orbgpu_sim3_optimize(const orbgpu_sim3_opt_problem *p, uint8_t *i
     if (rc != ORBGPU_OK)
         return rc;
     ORBGPU_REQUIRE(p->n1 == 0 || inlier, "null inlier array");
-    // one staging block each way; every segment starts on a multiple of 16 bytes
+    // one staging block each way
     const int n1 = p->n1;
-    const size_t c1 = (size_t)std::max(n1, 1);
-    Carver in(16), out(16);
-    const size_t i_valid = in.take(c1), i_x1 = in.take(12 * c1), i_x2 = in.take(12 * c1), i_o1 = in.take(4 * c1),
-                 i_o2 = in.take(4 * c1), i_k1 = in.take(8 * c1), i_k2 = in.take(8 * c1);
-    const size_t o_res = out.take(sizeof(orbgpu_sim3_opt_result)), o_inl = out.take(c1);
+    orbgpu_sim3_opt_result r;
+    HostPlan<N_BUF> plan;
+    const auto i_valid = plan.in(H_IN, p->valid, n1);
+    const auto i_x1 = plan.in(H_IN, p->Xw1, n1, 3), i_x2 = plan.in(H_IN, p->Xw2, n1, 3);
+    const auto i_o1 = plan.in(H_IN, p->octave1, n1), i_o2 = plan.in(H_IN, p->octave2, n1);
+    const auto i_k1 = plan.in(H_IN, p->kp1_xy, n1, 2), i_k2 = plan.in(H_IN, p->kp2_xy, n1, 2);
+    const auto o_res = plan.out(H_OUT, &r, 1);
+    const auto o_inl = plan.inout(H_OUT, inlier, n1);
     Sim3OptWs *wsp;
-    if ((rc = host_begin(device_id, H_IN, in.off, H_OUT, out.off, wsp)) != ORBGPU_OK)
+    if ((rc = host_begin(device_id, plan, wsp)) != ORBGPU_OK)
         return rc;
     Sim3OptWs &ws = *wsp;
     Sim3OptWs::FinishOnError on_error{ws};
-    if (n1 > 0) {
-        ws.upload(H_IN, p->valid, (size_t)n1, i_valid);
-        ws.upload(H_IN, p->Xw1, 12 * (size_t)n1, i_x1);
-        ws.upload(H_IN, p->Xw2, 12 * (size_t)n1, i_x2);
-        ws.upload(H_IN, p->octave1, 4 * (size_t)n1, i_o1);
-        ws.upload(H_IN, p->octave2, 4 * (size_t)n1, i_o2);
-        ws.upload(H_IN, p->kp1_xy, 8 * (size_t)n1, i_k1);
-        ws.upload(H_IN, p->kp2_xy, 8 * (size_t)n1, i_k2);
-        ws.upload(H_OUT, inlier, (size_t)n1, o_inl);
-    }
+    plan.upload(ws);
     if ((rc = ws.status()) != ORBGPU_OK)
         return rc;
     orbgpu_sim3_opt_problem d = *p;
-    d.valid = ws.at<uint8_t>(H_IN, i_valid), d.Xw1 = ws.at<float>(H_IN, i_x1), d.Xw2 = ws.at<float>(H_IN, i_x2);
-    d.octave1 = ws.at<int32_t>(H_IN, i_o1), d.octave2 = ws.at<int32_t>(H_IN, i_o2);
-    d.kp1_xy = ws.at<float>(H_IN, i_k1), d.kp2_xy = ws.at<float>(H_IN, i_k2);
-    d.inlier = ws.at<uint8_t>(H_OUT, o_inl), d.result = ws.at<orbgpu_sim3_opt_result>(H_OUT, o_res);
+    d.valid = ws.at(i_valid), d.Xw1 = ws.at(i_x1), d.Xw2 = ws.at(i_x2);
+    d.octave1 = ws.at(i_o1), d.octave2 = ws.at(i_o2);
+    d.kp1_xy = ws.at(i_k1), d.kp2_xy = ws.at(i_k2);
+    d.inlier = ws.at(o_inl), d.result = ws.at(o_res);
     if ((rc = orbgpu_sim3_optimize_batch_device(1, &d, device_id, ws.stream)) != ORBGPU_OK)
         return rc;
-    orbgpu_sim3_opt_result r;
-    ws.download(&r, H_OUT, sizeof(r), o_res);
-    if (n1 > 0)
-        ws.download(inlier, H_OUT, (size_t)n1, o_inl);
+    plan.download(ws);
     if ((rc = ws.finish()) != ORBGPU_OK)
         return rc;
     *n_inliers = r.n_inliers;

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 
+#include "carve.h"
 #include "common.h"
 #include "workspace.h"
 
@@ -46,6 +47,7 @@ template <int N> struct Staging {
     template <typename T> T *as(int i) const { return buf[i].template as<T>(); }
     // the segment of buf[i] that starts `offset` bytes in (carve.h hands out the offsets)
     template <typename T> T *at(int i, size_t offset) const { return reinterpret_cast<T *>(as<char>(i) + offset); }
+    template <typename T> T *at(Seg<T> s) const { return at<T>(s.buf, s.off); }
     int status() const { return rc; }
     void reserve(int i, size_t bytes)
     {
@@ -151,21 +153,38 @@ int batch_begin(int32_t n, const Problem *problems, Check check, int32_t device_
     return ws->bind(device_id, false);
 }
 
-// A host flavour that stages its problem in one carved block each way (sim3.hip, sim3_opt.hip, pnp.hip, initializer.hip,
-// local_ba.hip, essential_graph.hip).  It runs on a
-// stream of its own and shares the thread's workspace with the device flavours: whatever the thread enqueued through them
-// on other streams must have left it, hence the device-wide wait (pose_opt.hip's does not wait: DESIGN.md 9.21).
-template <typename Ws> int host_begin(int32_t device_id, int in, size_t in_bytes, int out, size_t out_bytes, Ws *&ws)
+// A host flavour that stages its problem in carved blocks (sim3.hip, sim3_opt.hip, pnp.hip, initializer.hip, local_ba.hip,
+// essential_graph.hip: a HostPlan's; new_points.hip: one block each way).  It runs on a stream of its own and shares the
+// thread's workspace with the device flavours: whatever the thread enqueued through them on other streams must have left
+// it, hence the device-wide wait (pose_opt.hip's does not wait: DESIGN.md 9.21).
+template <typename Ws> int host_begin(int32_t device_id, Ws *&ws)
 {
     int rc = select_device(device_id);
     if (rc != ORBGPU_OK)
         return rc;
     ORBGPU_HIP_TRY(hipDeviceSynchronize());
     ws = &per_device_workspace<Ws>(device_id);
-    if ((rc = ws->bind(device_id, true)) != ORBGPU_OK)
+    return ws->bind(device_id, true);
+}
+template <typename Ws> int host_begin(int32_t device_id, int in, size_t in_bytes, int out, size_t out_bytes, Ws *&ws)
+{
+    int rc = host_begin(device_id, ws);
+    if (rc != ORBGPU_OK)
         return rc;
     ws->reserve(in, in_bytes);
     ws->reserve(out, out_bytes);
+    return ws->status();
+}
+// every buffer the plan carved from, in the order of the workspace's enum
+template <typename Ws, int N> int host_begin(int32_t device_id, const HostPlan<N> &plan, Ws *&ws)
+{
+    ORBGPU_REQUIRE(plan.ok(), "staging plan: more than %d copies", plan.MAX_SEGS);
+    int rc = host_begin(device_id, ws);
+    if (rc != ORBGPU_OK)
+        return rc;
+    for (int i = 0; i < N; i++)
+        if (plan.bytes(i))
+            ws->reserve(i, plan.bytes(i));
     return ws->status();
 }
 

@@ -1121,19 +1121,42 @@ def pose_optimization_table(dframe, table, kp_ids, Tcw, inv_level_sigma2, fx, fy
     return ni.value, T, out[:n], res.as_dict()
 
 
+def _last_spills(name, device_id):
+    fn = getattr(lib(), "orbgpu_%s_last_spills" % name)
+    fn.argtypes = [C.c_int32, C.c_void_p]
+    v = C.c_int32()
+    check(fn(device_id, C.byref(v)))
+    return v.value
+
+
 def pose_last_spills(device_id=0):
     """Problems of this thread's most recent pose optimisation that took the global-memory spill path."""
-    L = lib()
-    L.orbgpu_pose_last_spills.argtypes = [C.c_int32, C.c_void_p]
-    v = C.c_int32()
-    check(L.orbgpu_pose_last_spills(device_id, C.byref(v)))
-    return v.value
+    return _last_spills("pose", device_id)
+
+
+def _start(a, shape, t):
+    """An in/out array of a host flavour: zeros, or a copy of what the caller starts from"""
+    return np.zeros(shape, t) if a is None else np.array(a, t).reshape(shape).copy()
 
 
 _LBA_HOST = (("Tcw", np.float32), ("fixed", np.uint8), ("cam", np.float32), ("inv_level_sigma2", np.float32),
              ("world_pos", np.float32), ("edge_point", np.int32), ("edge_pose", np.int32), ("edge_octave", np.int32),
              ("edge_xy", np.float32), ("edge_u_right", np.float32))
 _LBA_PTRS = ("d_stop", "d_Tcw_d", "d_Tcw", "d_pos_d", "d_pos", "d_erase", "d_result")
+
+
+def _fill_ba_problem(q, p, keep, ptrs):
+    """The ten host arrays, the counts that follow them and the device pointers `ptrs` of either bundle adjustment"""
+    a = {k: np.ascontiguousarray(p[k], t) for k, t in _LBA_HOST}
+    keep.append(a)
+    q.n_poses = int(p.get("n_poses", a["Tcw"].size // 16))
+    q.n_points = int(p.get("n_points", a["world_pos"].size // 3))
+    q.n_edges = int(p.get("n_edges", a["edge_point"].size))
+    q.nlevels = int(p.get("nlevels", a["inv_level_sigma2"].size // max(q.n_poses, 1)))
+    for k, _ in _LBA_HOST:
+        setattr(q, k, a[k].ctypes.data if a[k].size else None)
+    _set_pointers(q, p, ptrs)
+    return q
 
 
 def local_ba_problem(p, keep):
@@ -1143,17 +1166,8 @@ def local_ba_problem(p, keep):
     d_Tcw, d_pos_d, d_pos, d_erase, d_result (holds a LocalBAResult).  The counts follow the arrays unless the dict names
     them (n_poses, n_points, n_edges, nlevels); keep takes the host arrays the structure points to."""
     q = LocalBAProblem()
-    a = {k: np.ascontiguousarray(p[k], t) for k, t in _LBA_HOST}
-    keep.append(a)
     q.n_local = int(p["n_local"])
-    q.n_poses = int(p.get("n_poses", a["Tcw"].size // 16))
-    q.n_points = int(p.get("n_points", a["world_pos"].size // 3))
-    q.n_edges = int(p.get("n_edges", a["edge_point"].size))
-    q.nlevels = int(p.get("nlevels", a["inv_level_sigma2"].size // max(q.n_poses, 1)))
-    for k, _ in _LBA_HOST:
-        setattr(q, k, a[k].ctypes.data if a[k].size else None)
-    _set_pointers(q, p, _LBA_PTRS)
-    return q
+    return _fill_ba_problem(q, p, keep, _LBA_PTRS)
 
 
 def local_ba_batch_device(problems, stream=0, device_id=0):
@@ -1177,12 +1191,9 @@ def local_ba(problem, stop=None, Tcw_d=None, Tcw=None, pos_d=None, pos=None, era
     keep = []
     q = local_ba_problem(problem, keep)
     nl, M, E = q.n_local, q.n_points, q.n_edges
-
-    def start(a, shape, t):
-        return np.zeros(shape, t) if a is None else np.array(a, t).reshape(shape).copy()
-    Td, T = start(Tcw_d, (max(nl, 1), 4, 4), np.float64), start(Tcw, (max(nl, 1), 4, 4), np.float32)
-    Xd, X = start(pos_d, (max(M, 1), 3), np.float64), start(pos, (max(M, 1), 3), np.float32)
-    er = start(erase, (max(E, 1),), np.uint8)
+    Td, T = _start(Tcw_d, (max(nl, 1), 4, 4), np.float64), _start(Tcw, (max(nl, 1), 4, 4), np.float32)
+    Xd, X = _start(pos_d, (max(M, 1), 3), np.float64), _start(pos, (max(M, 1), 3), np.float32)
+    er = _start(erase, (max(E, 1),), np.uint8)
     sv = None if stop is None else C.c_int32(int(stop))
     res = LocalBAResult()
     L = lib()
@@ -1194,11 +1205,7 @@ def local_ba(problem, stop=None, Tcw_d=None, Tcw=None, pos_d=None, pos=None, era
 
 def local_ba_last_spills(device_id=0):
     """Problems of this thread's most recent local bundle adjustment whose reduced system lived in global memory."""
-    L = lib()
-    L.orbgpu_local_ba_last_spills.argtypes = [C.c_int32, C.c_void_p]
-    v = C.c_int32()
-    check(L.orbgpu_local_ba_last_spills(device_id, C.byref(v)))
-    return v.value
+    return _last_spills("local_ba", device_id)
 
 
 _BA_PTRS = ("d_stop", "d_Tcw_d", "d_Tcw", "d_pos_d", "d_pos", "d_not_included", "d_result")
@@ -1210,17 +1217,8 @@ def bundle_adjustment_problem(p, keep):
     ([P][16]), d_pos_d, d_pos, d_not_included ([M]), d_result (holds a BundleAdjustmentResult).  The counts follow the arrays
     unless the dict names them; keep takes the host arrays the structure points to."""
     q = BundleAdjustmentProblem()
-    a = {k: np.ascontiguousarray(p[k], t) for k, t in _LBA_HOST}
-    keep.append(a)
-    q.n_poses = int(p.get("n_poses", a["Tcw"].size // 16))
-    q.n_points = int(p.get("n_points", a["world_pos"].size // 3))
-    q.n_edges = int(p.get("n_edges", a["edge_point"].size))
-    q.nlevels = int(p.get("nlevels", a["inv_level_sigma2"].size // max(q.n_poses, 1)))
     q.n_iterations, q.robust = int(p.get("n_iterations", 20)), int(bool(p.get("robust", True)))
-    for k, _ in _LBA_HOST:
-        setattr(q, k, a[k].ctypes.data if a[k].size else None)
-    _set_pointers(q, p, _BA_PTRS)
-    return q
+    return _fill_ba_problem(q, p, keep, _BA_PTRS)
 
 
 def bundle_adjustment_batch_device(problems, stream=0, device_id=0):
@@ -1245,12 +1243,9 @@ def bundle_adjustment(problem, stop=None, Tcw_d=None, Tcw=None, pos_d=None, pos=
     keep = []
     q = bundle_adjustment_problem(problem, keep)
     P, M = q.n_poses, q.n_points
-
-    def start(a, shape, t):
-        return np.zeros(shape, t) if a is None else np.array(a, t).reshape(shape).copy()
-    Td, T = start(Tcw_d, (max(P, 1), 4, 4), np.float64), start(Tcw, (max(P, 1), 4, 4), np.float32)
-    Xd, X = start(pos_d, (max(M, 1), 3), np.float64), start(pos, (max(M, 1), 3), np.float32)
-    ni = start(not_included, (max(M, 1),), np.uint8)
+    Td, T = _start(Tcw_d, (max(P, 1), 4, 4), np.float64), _start(Tcw, (max(P, 1), 4, 4), np.float32)
+    Xd, X = _start(pos_d, (max(M, 1), 3), np.float64), _start(pos, (max(M, 1), 3), np.float32)
+    ni = _start(not_included, (max(M, 1),), np.uint8)
     sv = None if stop is None else C.c_int32(int(stop))
     res = BundleAdjustmentResult()
     L = lib()
@@ -1262,11 +1257,7 @@ def bundle_adjustment(problem, stop=None, Tcw_d=None, Tcw=None, pos_d=None, pos=
 
 def bundle_adjustment_last_spills(device_id=0):
     """Problems of this thread's most recent bundle adjustment whose reduced system lived in global memory."""
-    L = lib()
-    L.orbgpu_bundle_adjustment_last_spills.argtypes = [C.c_int32, C.c_void_p]
-    v = C.c_int32()
-    check(L.orbgpu_bundle_adjustment_last_spills(device_id, C.byref(v)))
-    return v.value
+    return _last_spills("bundle_adjustment", device_id)
 
 
 _EG_HOST = (("Scw", np.float64), ("Snc", np.float64), ("fixed", np.uint8), ("edge_i", np.int32), ("edge_j", np.int32),
@@ -1329,11 +1320,8 @@ def essential_graph(problem, stop=None, Siw_d=None, Tiw=None, world_pos=None, po
     ref = np.ascontiguousarray(np.zeros(0) if point_ref is None else point_ref, np.int32)
     if len(ref) != M:
         raise ValueError("point_ref must have one entry per point")
-
-    def start(a, shape, t):
-        return np.zeros(shape, t) if a is None else np.array(a, t).reshape(shape).copy()
-    Sd, T = start(Siw_d, (max(V, 1), 8), np.float64), start(Tiw, (max(V, 1), 4, 4), np.float32)
-    out = start(X if pos_out is None and M else pos_out, (max(M, 1), 3), np.float32)
+    Sd, T = _start(Siw_d, (max(V, 1), 8), np.float64), _start(Tiw, (max(V, 1), 4, 4), np.float32)
+    out = _start(X if pos_out is None and M else pos_out, (max(M, 1), 3), np.float32)
     sv = None if stop is None else C.c_int32(int(stop))
     res = EssentialGraphResult()
     L = lib()
@@ -1506,11 +1494,7 @@ def sim3_optimize(valid, Xw1, Xw2, octave1, octave2, kp1_xy, kp2_xy, T1w, T2w, K
 
 def sim3_opt_last_spills(device_id=0):
     """Problems of this thread's most recent Sim3 optimisation that took the global-memory spill path."""
-    L = lib()
-    L.orbgpu_sim3_opt_last_spills.argtypes = [C.c_int32, C.c_void_p]
-    v = C.c_int32()
-    check(L.orbgpu_sim3_opt_last_spills(device_id, C.byref(v)))
-    return v.value
+    return _last_spills("sim3_opt", device_id)
 
 
 def pnp_ransac_parameters(n, probability, min_inliers, max_iterations, min_set, epsilon):

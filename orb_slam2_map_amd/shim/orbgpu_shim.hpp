@@ -422,6 +422,12 @@ template <typename MapPointT> class MapPointTableT {
                                            nullptr),
               "SetWorldPos (batch)");
     }
+    // the same through an accessor with world_pos(p), normal(p), min_dist(p), max_dist(p): the optimisers' write-backs
+    template <typename Access> void SetWorldPos(const std::vector<MapPointT *> &pts, Access &access)
+    {
+        SetWorldPos(pts, [&access](MapPointT *q) { return access.world_pos(q); }, [&access](MapPointT *q) { return access.normal(q); },
+                    [&access](MapPointT *q) { return access.min_dist(q); }, [&access](MapPointT *q) { return access.max_dist(q); });
+    }
     void SetObservations(const std::vector<MapPointT *> &pts)
     {
         std::lock_guard<std::mutex> g(mu_);
@@ -1068,20 +1074,88 @@ template <typename KeyFrameT, typename MapPointT> struct Sim3OptRows {
     }
 };
 
-// The graph of Optimizer::LocalBundleAdjustment as orbgpu_local_ba takes it: the breadth-first gathering of
-// Optimizer.cc:455-504 (it walks pointers, so it stays on the host) in the reference's list order, then the vertices and
-// edges of :522-652.  Pose rows: lLocalKeyFrames, then lFixedCameras; point rows: lLocalMapPoints; edges: per point in list
-// order, its observations in the order of the map GetObservations() returns.  Marks mnBALocalForKF / mnBAFixedForKF as
-// the reference does.  An observation by a key frame that is bad is no edge (:589); one by a key frame that is in neither
-// list, or at an octave outside that key frame's sigma table, keeps its row with pose / octave -1: the library skips and
-// counts it (the reference reads through a null vertex / out of range there).
-template <typename KeyFrameT, typename MapPointT> struct LocalBAGraph {
-    std::vector<KeyFrameT *> local, fixed, edge_kf;
+// What the graphs of the two bundle adjustments share: the arrays of the library's problem, the pose rows, and the edges --
+// per point row, its observations in the order of the map GetObservations() returns.  An observer that is in no pose row
+// (the reference reads through a null vertex there), or an octave outside that key frame's sigma table, keeps its edge with
+// pose / octave -1: the library skips and counts it.  Every array but fixed_flag keeps one spare row, and fixed_flag at
+// least one element, so that data() is never null.
+template <typename KeyFrameT, typename MapPointT> struct BAGraphBase {
+    std::vector<KeyFrameT *> edge_kf;
     std::vector<MapPointT *> points, edge_mp;
     std::vector<int32_t> edge_point, edge_pose, edge_octave;
     std::vector<float> edge_xy, edge_ur, Tcw, cam, inv_sigma2, world_pos;
     std::vector<uint8_t> fixed_flag;
     int nlevels = 1;
+
+  protected:
+    std::map<KeyFrameT *, int32_t> row;
+    size_t n_rows = 0;
+
+    // pose rows row_kf(0 .. P-1): pose, camera, sigma table (as many levels as `levels_of` has, if there is one); the first
+    // n_flags of them carry a fixed flag, set iff mnId == 0
+    template <typename RowKF, typename Access> void fill_poses(size_t P, RowKF row_kf, size_t n_flags, KeyFrameT *levels_of, Access &access)
+    {
+        if (levels_of)
+            nlevels = (int)std::max<size_t>(1, std::min(levels_of->mvInvLevelSigma2.size(), (size_t)ORBGPU_MAX_LEVELS));
+        Tcw.assign(16 * P + 16, 0.f), cam.assign(5 * P + 5, 0.f), inv_sigma2.assign((size_t)nlevels * (P + 1), 0.f);
+        fixed_flag.assign(std::max<size_t>(n_flags, 1), 0);  // one per flagged row: callers walk the vector
+        n_rows = P;
+        for (size_t i = 0; i < P; i++) {
+            KeyFrameT *k = row_kf(i);
+            row[k] = (int32_t)i;
+            std::memcpy(&Tcw[16 * i], access.pose(k), 64);
+            const float c[5] = {k->fx, k->fy, k->cx, k->cy, k->mbf};
+            std::memcpy(&cam[5 * i], c, sizeof(c));
+            for (size_t l = 0; l < std::min(k->mvInvLevelSigma2.size(), (size_t)nlevels); l++)
+                inv_sigma2[(size_t)nlevels * i + l] = k->mvInvLevelSigma2[l];
+            if (i < n_flags)
+                fixed_flag[i] = k->mnId == 0;
+        }
+    }
+
+    // the point rows' positions and their edges; skipped(pKFi): this observer is no edge
+    template <typename Skipped, typename Access> void gather_edges(Skipped skipped, Access &access)
+    {
+        world_pos.assign(3 * points.size() + 3, 0.f);
+        for (size_t j = 0; j < points.size(); j++) {
+            MapPointT *pMP = points[j];
+            std::memcpy(&world_pos[3 * j], access.world_pos(pMP), 12);
+            const auto observations = pMP->GetObservations();
+            for (const auto &ob : observations) {
+                KeyFrameT *pKFi = ob.first;
+                if (skipped(pKFi))
+                    continue;
+                const auto &kpUn = pKFi->mvKeysUn[ob.second];
+                const auto it = row.find(pKFi);
+                const bool has_sigma = kpUn.octave >= 0 && (size_t)kpUn.octave < pKFi->mvInvLevelSigma2.size();
+                edge_kf.push_back(pKFi), edge_mp.push_back(pMP);
+                edge_point.push_back((int32_t)j), edge_pose.push_back(it == row.end() ? -1 : it->second);
+                edge_octave.push_back(has_sigma ? kpUn.octave : -1);
+                edge_xy.push_back(kpUn.pt.x), edge_xy.push_back(kpUn.pt.y), edge_ur.push_back(pKFi->mvuRight[ob.second]);
+            }
+        }
+    }
+
+    // the host part both problems have; valid while the graph lives
+    template <typename Problem> Problem HostPart() const
+    {
+        Problem p;
+        std::memset(&p, 0, sizeof(p));
+        p.n_poses = (int32_t)n_rows, p.n_points = (int32_t)points.size(), p.n_edges = (int32_t)edge_point.size();
+        p.nlevels = nlevels;
+        p.Tcw = Tcw.data(), p.fixed = fixed_flag.data(), p.cam = cam.data(), p.inv_level_sigma2 = inv_sigma2.data();
+        p.world_pos = world_pos.data(), p.edge_point = edge_point.data(), p.edge_pose = edge_pose.data();
+        p.edge_octave = edge_octave.data(), p.edge_xy = edge_xy.data(), p.edge_u_right = edge_ur.data();
+        return p;
+    }
+};
+
+// The graph of Optimizer::LocalBundleAdjustment as orbgpu_local_ba takes it: the breadth-first gathering of
+// Optimizer.cc:455-504 (it walks pointers, so it stays on the host) in the reference's list order, then the vertices and
+// edges of :522-652.  Pose rows: lLocalKeyFrames, then lFixedCameras; point rows: lLocalMapPoints.  Marks mnBALocalForKF /
+// mnBAFixedForKF as the reference does.  An observation by a key frame that is bad is no edge (:589).
+template <typename KeyFrameT, typename MapPointT> struct LocalBAGraph : BAGraphBase<KeyFrameT, MapPointT> {
+    std::vector<KeyFrameT *> local, fixed;
 
     template <typename Access> LocalBAGraph(KeyFrameT *pKF, Access &access)
     {
@@ -1097,11 +1171,11 @@ template <typename KeyFrameT, typename MapPointT> struct LocalBAGraph {
             const std::vector<MapPointT *> vpMPs = pKFi->GetMapPointMatches();
             for (MapPointT *pMP : vpMPs)
                 if (pMP && !pMP->isBad() && pMP->mnBALocalForKF != pKF->mnId) {
-                    points.push_back(pMP);
+                    this->points.push_back(pMP);
                     pMP->mnBALocalForKF = pKF->mnId;
                 }
         }
-        for (MapPointT *pMP : points) {
+        for (MapPointT *pMP : this->points) {
             const auto observations = pMP->GetObservations();
             for (const auto &ob : observations) {
                 KeyFrameT *pKFi = ob.first;
@@ -1112,131 +1186,48 @@ template <typename KeyFrameT, typename MapPointT> struct LocalBAGraph {
                 }
             }
         }
-        std::map<KeyFrameT *, int32_t> row;
-        nlevels = (int)std::max<size_t>(1, std::min(pKF->mvInvLevelSigma2.size(), (size_t)ORBGPU_MAX_LEVELS));
-        const size_t P = local.size() + fixed.size();
-        Tcw.assign(16 * P, 0.f), cam.assign(5 * P, 0.f), inv_sigma2.assign((size_t)nlevels * P, 0.f);
-        fixed_flag.assign(local.size(), 0);
-        for (size_t i = 0; i < P; i++) {
-            KeyFrameT *k = i < local.size() ? local[i] : fixed[i - local.size()];
-            row[k] = (int32_t)i;
-            std::memcpy(&Tcw[16 * i], access.pose(k), 64);
-            const float c[5] = {k->fx, k->fy, k->cx, k->cy, k->mbf};
-            std::memcpy(&cam[5 * i], c, sizeof(c));
-            for (size_t l = 0; l < std::min(k->mvInvLevelSigma2.size(), (size_t)nlevels); l++)
-                inv_sigma2[(size_t)nlevels * i + l] = k->mvInvLevelSigma2[l];
-            if (i < local.size())
-                fixed_flag[i] = k->mnId == 0;
-        }
-        world_pos.assign(3 * points.size() + 3, 0.f);  // one spare row so that data() is never null
-        for (size_t j = 0; j < points.size(); j++) {
-            MapPointT *pMP = points[j];
-            std::memcpy(&world_pos[3 * j], access.world_pos(pMP), 12);
-            const auto observations = pMP->GetObservations();
-            for (const auto &ob : observations) {
-                KeyFrameT *pKFi = ob.first;
-                if (pKFi->isBad())
-                    continue;
-                const auto &kpUn = pKFi->mvKeysUn[ob.second];
-                const auto it = row.find(pKFi);
-                const bool has_sigma = kpUn.octave >= 0 && (size_t)kpUn.octave < pKFi->mvInvLevelSigma2.size();
-                edge_kf.push_back(pKFi), edge_mp.push_back(pMP);
-                edge_point.push_back((int32_t)j), edge_pose.push_back(it == row.end() ? -1 : it->second);
-                edge_octave.push_back(has_sigma ? kpUn.octave : -1);
-                edge_xy.push_back(kpUn.pt.x), edge_xy.push_back(kpUn.pt.y), edge_ur.push_back(pKFi->mvuRight[ob.second]);
-            }
-        }
+        this->fill_poses(local.size() + fixed.size(), [this](size_t i) { return i < local.size() ? local[i] : fixed[i - local.size()]; },
+                         local.size(), pKF, access);
+        this->gather_edges([](KeyFrameT *pKFi) { return pKFi->isBad(); }, access);
     }
 
-    // the host part of the library's problem; valid while the graph lives
     orbgpu_local_ba_problem Problem() const
     {
-        orbgpu_local_ba_problem p;
-        std::memset(&p, 0, sizeof(p));
-        p.n_poses = (int32_t)(local.size() + fixed.size()), p.n_local = (int32_t)local.size();
-        p.n_points = (int32_t)points.size(), p.n_edges = (int32_t)edge_point.size(), p.nlevels = nlevels;
-        p.Tcw = Tcw.data(), p.fixed = fixed_flag.data(), p.cam = cam.data(), p.inv_level_sigma2 = inv_sigma2.data();
-        p.world_pos = world_pos.data(), p.edge_point = edge_point.data(), p.edge_pose = edge_pose.data();
-        p.edge_octave = edge_octave.data(), p.edge_xy = edge_xy.data(), p.edge_u_right = edge_ur.data();
+        orbgpu_local_ba_problem p = this->template HostPart<orbgpu_local_ba_problem>();
+        p.n_local = (int32_t)local.size();
         return p;
     }
 };
 
 // The graph of Optimizer::BundleAdjustment (Optimizer.cc:68-184) as orbgpu_bundle_adjustment takes it.  Pose rows: vpKFs in
 // order without the bad ones, fixed iff mnId == 0; maxKFid over those rows; point rows: vpMP in order without the bad
-// ones; edges: per point row, its observations in the order of the map GetObservations() returns, without key frames
-// that are bad or whose mnId > maxKFid (:109).  An observer that is in no row (the reference reads through a null vertex
-// there), or an octave outside that key frame's sigma table, keeps its edge with pose / octave -1: the library skips and
-// counts it.  A point whose every observation is skipped comes back not included.
-template <typename KeyFrameT, typename MapPointT> struct FullBAGraph {
-    std::vector<KeyFrameT *> rows, edge_kf;
-    std::vector<MapPointT *> points, edge_mp;
-    std::vector<int32_t> edge_point, edge_pose, edge_octave;
-    std::vector<float> edge_xy, edge_ur, Tcw, cam, inv_sigma2, world_pos;
-    std::vector<uint8_t> fixed_flag;
+// ones; no edge for an observer that is bad or whose mnId > maxKFid (:109).  A point whose every observation is skipped
+// comes back not included.
+template <typename KeyFrameT, typename MapPointT> struct FullBAGraph : BAGraphBase<KeyFrameT, MapPointT> {
+    std::vector<KeyFrameT *> rows;
     long unsigned int maxKFid = 0;
-    int nlevels = 1;
 
     template <typename Access>
     FullBAGraph(const std::vector<KeyFrameT *> &vpKFs, const std::vector<MapPointT *> &vpMP, Access &access)
     {
-        std::map<KeyFrameT *, int32_t> row;
         for (KeyFrameT *pKF : vpKFs) {
             if (pKF->isBad())
                 continue;
-            row[pKF] = (int32_t)rows.size();
             rows.push_back(pKF);
             if (pKF->mnId > maxKFid)
                 maxKFid = pKF->mnId;
         }
-        const size_t P = rows.size();
-        if (P)
-            nlevels = (int)std::max<size_t>(1, std::min(rows[0]->mvInvLevelSigma2.size(), (size_t)ORBGPU_MAX_LEVELS));
-        // one spare row each so that data() is never null
-        Tcw.assign(16 * P + 16, 0.f), cam.assign(5 * P + 5, 0.f), inv_sigma2.assign((size_t)nlevels * (P + 1), 0.f);
-        fixed_flag.assign(P + 1, 0);
-        for (size_t i = 0; i < P; i++) {
-            KeyFrameT *k = rows[i];
-            std::memcpy(&Tcw[16 * i], access.pose(k), 64);
-            const float c[5] = {k->fx, k->fy, k->cx, k->cy, k->mbf};
-            std::memcpy(&cam[5 * i], c, sizeof(c));
-            for (size_t l = 0; l < std::min(k->mvInvLevelSigma2.size(), (size_t)nlevels); l++)
-                inv_sigma2[(size_t)nlevels * i + l] = k->mvInvLevelSigma2[l];
-            fixed_flag[i] = k->mnId == 0;
-        }
+        this->fill_poses(rows.size(), [this](size_t i) { return rows[i]; }, rows.size(), rows.empty() ? nullptr : rows[0], access);
         for (MapPointT *pMP : vpMP)
             if (!pMP->isBad())
-                points.push_back(pMP);
-        world_pos.assign(3 * points.size() + 3, 0.f);
-        for (size_t j = 0; j < points.size(); j++) {
-            MapPointT *pMP = points[j];
-            std::memcpy(&world_pos[3 * j], access.world_pos(pMP), 12);
-            const auto observations = pMP->GetObservations();
-            for (const auto &ob : observations) {
-                KeyFrameT *pKFi = ob.first;
-                if (pKFi->isBad() || pKFi->mnId > maxKFid)
-                    continue;
-                const auto &kpUn = pKFi->mvKeysUn[ob.second];
-                const auto it = row.find(pKFi);
-                const bool has_sigma = kpUn.octave >= 0 && (size_t)kpUn.octave < pKFi->mvInvLevelSigma2.size();
-                edge_kf.push_back(pKFi), edge_mp.push_back(pMP);
-                edge_point.push_back((int32_t)j), edge_pose.push_back(it == row.end() ? -1 : it->second);
-                edge_octave.push_back(has_sigma ? kpUn.octave : -1);
-                edge_xy.push_back(kpUn.pt.x), edge_xy.push_back(kpUn.pt.y), edge_ur.push_back(pKFi->mvuRight[ob.second]);
-            }
-        }
+                this->points.push_back(pMP);
+        this->gather_edges([this](KeyFrameT *pKFi) { return pKFi->isBad() || pKFi->mnId > maxKFid; }, access);
     }
 
-    // the host part of the library's problem; valid while the graph lives
     orbgpu_bundle_adjustment_problem Problem(int nIterations, bool bRobust) const
     {
-        orbgpu_bundle_adjustment_problem p;
-        std::memset(&p, 0, sizeof(p));
-        p.n_poses = (int32_t)rows.size(), p.n_points = (int32_t)points.size(), p.n_edges = (int32_t)edge_point.size();
-        p.nlevels = nlevels, p.n_iterations = nIterations, p.robust = bRobust ? 1 : 0;
-        p.Tcw = Tcw.data(), p.fixed = fixed_flag.data(), p.cam = cam.data(), p.inv_level_sigma2 = inv_sigma2.data();
-        p.world_pos = world_pos.data(), p.edge_point = edge_point.data(), p.edge_pose = edge_pose.data();
-        p.edge_octave = edge_octave.data(), p.edge_xy = edge_xy.data(), p.edge_u_right = edge_ur.data();
+        orbgpu_bundle_adjustment_problem p = this->template HostPart<orbgpu_bundle_adjustment_problem>();
+        p.n_iterations = nIterations, p.robust = bRobust ? 1 : 0;
         return p;
     }
 };
@@ -1533,10 +1524,7 @@ template <typename FrameT, typename MapPointT> class OptimizerT {
         if (table) {
             if (!touched.empty())
                 table->SetObservations(touched);
-            table->SetWorldPos(g.points, [&access](MapPointT *q) { return access.world_pos(q); },
-                               [&access](MapPointT *q) { return access.normal(q); },
-                               [&access](MapPointT *q) { return access.min_dist(q); },
-                               [&access](MapPointT *q) { return access.max_dist(q); });
+            table->SetWorldPos(g.points, access);
         }
     }
 
@@ -1597,10 +1585,7 @@ template <typename FrameT, typename MapPointT> class OptimizerT {
             }
         }
         if (table && !moved.empty())
-            table->SetWorldPos(moved, [&access](MapPointT *q) { return access.world_pos(q); },
-                               [&access](MapPointT *q) { return access.normal(q); },
-                               [&access](MapPointT *q) { return access.min_dist(q); },
-                               [&access](MapPointT *q) { return access.max_dist(q); });
+            table->SetWorldPos(moved, access);
     }
 
     // Optimizer::GlobalBundleAdjustemnt (Optimizer.cc:41-46, spelt as there): BundleAdjustment over pMap->GetAllKeyFrames()
@@ -1657,10 +1642,7 @@ template <typename FrameT, typename MapPointT> class OptimizerT {
             moved.push_back(g.points[j]);
         }
         if (table && !moved.empty())
-            table->SetWorldPos(moved, [&access](MapPointT *q) { return access.world_pos(q); },
-                               [&access](MapPointT *q) { return access.normal(q); },
-                               [&access](MapPointT *q) { return access.min_dist(q); },
-                               [&access](MapPointT *q) { return access.max_dist(q); });
+            table->SetWorldPos(moved, access);
     }
 };
 

@@ -1,6 +1,7 @@
 """The shared parts of the device optimisers are written once: the Sim3 exponential and algebra in
 sim3_math.h, the barrier, the stop flag, the workgroup reductions and the decision on a Levenberg-Marquardt trial in
-opt_math.h, and each workspace buffer of the two graph optimisers named once through carve.h's WorkPlan."""
+opt_math.h, and each workspace buffer of the two graph optimisers named once through carve.h's WorkPlan; and each staging
+segment of the host flavours is declared once on carve.h's HostPlan."""
 import os
 import re
 
@@ -65,3 +66,27 @@ def test_each_workspace_buffer_is_named_once():
         assert "void **" not in src, n
     assert "struct WorkPlan" in SRC["carve.h"] and "#include <hip" not in SRC["carve.h"]
     assert "EG_THREADS = 512" in SRC["essential_graph.hip"]
+
+
+HOST_FLAVOURS = ("sim3.hip", "sim3_opt.hip", "pnp.hip", "initializer.hip", "local_ba.hip", "essential_graph.hip")
+
+
+def test_the_host_flavours_declare_each_staging_segment_once():
+    """the seven host flavours keep no take() list and no copy with a byte count of its own -- a segment's
+    reservation, copies and device pointer all come from its one declaration on carve.h's HostPlan -- except the rows
+    orbgpu_sim3_solve fetches after it has read the result, whose offsets are the handles'."""
+    for n in HOST_FLAVOURS:
+        src = SRC[n]
+        assert "Carver in(16)" not in src and "Carver out(16)" not in src and "out.take(" not in src and "in.take(" not in src, n
+        assert "HostPlan<N_BUF> plan;" in src and "host_begin(device_id, plan, wsp)" in src, n
+        assert "plan.upload(ws);" in src and "plan.download(ws);" in src, n
+        assert "ws.upload(" not in src, n
+        assert ("ws.download(" in src) == (n == "sim3.hip"), n
+    second_phase = re.findall(r"ws\.download\((\w+(?:\.data\(\))?), H_OUT, ([^,]+), (\w+)\.off \+ ", SRC["sim3.hip"])
+    assert [(host, seg) for host, _, seg in second_phase] == [("R", "o_R"), ("t", "o_t"), ("s", "o_s"), ("T12", "o_T"),
+                                                              ("mask.data()", "o_m")]
+    assert SRC["sim3.hip"].count("ws.download(") == len(second_phase)
+    # one body above the two bundle adjustment kernels
+    assert SRC["local_ba.hip"].count("HostPlan<N_BUF> plan;") == 1 and SRC["local_ba.hip"].count("return ba_host<") == 2
+    assert "struct HostPlan" in SRC["carve.h"] and "#include <hip" not in SRC["carve.h"] and '#include "common.h"' not in SRC["carve.h"]
+    assert "void **" not in SRC["carve.h"]

@@ -94,8 +94,13 @@ def _host_program(tmp_path, name, *flags):
 
 def test_carver_offsets_and_the_host_flavours_layouts(tmp_path):
     """carve.h at alignments 16 and 256 over the sizes 0, 1, 15, 16, 17, 255, 256, 257 in sequence (aligned, no overlap,
-    each offset (prev + bytes + A - 1) & ~(A - 1)), and the staging layouts of the three host flavours at n1 in {0, 1, 15,
-    16, 17, 64, 65} x H in {0, 1, 3} x min_set in {4, 5} against the hand-summed formulas the entry points held before."""
+    each offset (prev + bytes + A - 1) & ~(A - 1)), and HostPlan through a recording workspace whose blocks and caller
+    arrays are heap blocks of exactly the reserved and the documented lengths: the segment lists of the seven host
+    flavours at n1 in {0, 1, 15, 16, 17, 64, 65} x H in {0, 1, 3} x min_set in {4, 5} x n2 in {0, 1, 17}, n_local / n_poses
+    in {0, 1, 3} x M in {0, 1, 5} x E in {0, 1, 7}, V in {0, 1, 3}, optional outputs given and null -- offsets and block
+    sizes against the hand-summed formulas the entry points held before, the copies (direction, buffer, offset, bytes,
+    host address) against the guards they held, none for a null pointer, rows == 0 or words == 0; and one copy more than
+    the plan holds."""
     r = subprocess.run([_host_program(tmp_path, "carve_test")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0 and "carve_test ok" in r.stdout, r.stdout
 
@@ -161,7 +166,7 @@ def test_solver_entry_points_share_one_host_scaffold():
         assert "batch_begin(" in src and "n <= 65535" not in src, name
     for name in ("sim3.hip", "sim3_opt.hip", "pnp.hip"):
         src = read(name)
-        assert "hipDeviceSynchronize" not in src and "host_begin(" in src and "Carver in(16), out(16);" in src, name
+        assert "hipDeviceSynchronize" not in src and "host_begin(" in src and "HostPlan<N_BUF> plan;" in src, name
     for name in ("local_ba.hip", "essential_graph.hip"):  # one staging block for the outputs (local_ba) or each way
         assert "hipDeviceSynchronize" not in read(name) and "host_begin(" in read(name), name
     for name in ("sim3.hip", "pnp.hip"):
