@@ -1809,6 +1809,92 @@ int orbgpu_keyframe_db_last_query(orbgpu_keyframe_db *db, int32_t capacity, int6
 int orbgpu_keyframe_db_debug_global_queries(const orbgpu_keyframe_db *db, int64_t *n);
 
 /* ======================================================================================
+ * Observation graph  (Tracking::UpdateLocalMap, Tracking.cc:1499-1643; KeyFrame::UpdateConnections, KeyFrame.cc:327-417)
+ * ======================================================================================
+ * The relation between key frames and map points, device-resident and keyed by KeyFrame::mnId, and the two votes over
+ * it: the frame's map points vote for the key frames that observe them (the local map of Tracking::TrackLocalMap), and a
+ * key frame's own points vote for the other key frames (its covisibility weights).  Conventions V1-V7 (DESIGN.md
+ * section 2); all of it is integer work and the results are equal to tests/covis_model.py's, entry for entry.
+ *   V1 rows    one row per key frame, n_slots (the frame's N, 0 allowed) fixed at add; the slots lie in one pool,
+ *              key-frame-major, one int64 each: the id of the map point at that key-point index, -1 for none.  A row has
+ *              a bad flag, a parent id (-1: none), up to 10 best-covisible ids in the caller's order (stored as ids and
+ *              resolved when a query runs) and a per-query stamp (mnTrackReferenceForFrame).  Rows are in add order.
+ *   V2 one relation   slot (kf, idx) = p stands for both "kf holds p at idx" (KeyFrame::mvpMapPoints) and "p is observed
+ *              by kf at idx" (MapPoint::mObservations).  The hooks keep it so: a bad point holds no slot, a bad key frame
+ *              holds no slot.  Deviations: the window between AddMapPoint and AddObservation is not represented; a bad key
+ *              frame's slots are cleared, where KeyFrame::SetBadFlag leaves mvpMapPoints alone -- the reference would list
+ *              the stale points of a bad parent (Tracking.cc:1625-1634 has no isBad test), the library lists none of them
+ *              but still appends the bad parent itself; a point that sits in two slots of one row counts twice
+ *              (MapPoint::AddObservation's guard excludes that, and the hook goes behind the guard).
+ *   V3 children are derived   the children of k are the rows whose parent is k, in ascending id (AddChild / ChangeParent
+ *              keep mspChildrens equal to that set).
+ *   V4 pointer order unpinned   wherever the reference iterates a std::map<KeyFrame*, ..> or std::set<KeyFrame*> by address,
+ *              the library iterates by ascending id.
+ *   V5 vote    for a query list q (ids; -1 skipped, duplicates kept), count(row) = sum over the row's slots of the
+ *              multiplicity of the slot's id in q: keyframeCounter[it->first]++ per key point.  (Saturates at 2^31 - 1.)
+ *   V6 local_map     UpdateLocalKeyFrames + UpdateLocalPoints.  kp_ids: the frame's map point ids per key point, bad ones
+ *              already -1 (Tracking.cc:1552).  K1 = the not-bad rows with count > 0 in ascending id, each stamped; ref_kf
+ *              = the first of K1 with the strictly greatest count, max_votes that count.  If no row has a vote the
+ *              previous list is kept (:1557-1558), its unknown ids skipped and counted, and kept_previous = 1.  Otherwise
+ *              the extension runs over the positions of K1 only, in order (:1586-1636); at the top of a step it stops if
+ *              the list holds more than 80 entries; then (a) the first stored covisible that is known, not bad and not
+ *              stamped is appended and stamped, (b) the first child (V3) that is not bad and not stamped likewise, (c) the
+ *              parent, if known and not stamped, is appended and stamped with no bad test, and THE WHOLE EXTENSION ENDS
+ *              THERE (the break at :1632 belongs to the outer loop).  Points: over the final list in order, slots in
+ *              ascending index, ids >= 0, first occurrence kept.  point_ids is what orbgpu_search_local_points_table takes.
+ *   V7 connections   the counting half of UpdateConnections: q = the row's own slots, every other row is counted.  ids /
+ *              counts: the full counter in ascending id (mConnectedKeyFrameWeights).  ordered_*: the entries with count >=
+ *              th, or -- if there are none but a row was counted -- the single first-strictly-greatest entry, in descending
+ *              (weight, id): sort(vPairs) reversed, id standing for the pointer.  An unknown or bad kf gives empty outputs;
+ *              the graph is not modified.  AddConnection, mpParent and the set_covisibles / set_parent hooks stay with the
+ *              caller (CovisibilityGraphT::UpdateConnections does them).
+ * Edits (HOST arrays; every call returns synchronised; ONE host thread at a time -- CovisibilityGraphT serialises):
+ *   add_keyframe    mp_ids NULL: every slot empty
+ *   set_slots       batched and applied in order (later entries win); mp_id -1 clears a slot; an unknown kf id is ignored,
+ *                   *known counts the entries whose key frame is a row; an entry on a bad row is known and changes nothing.
+ *                   The hook of AddObservation / EraseObservation / EraseMapPointMatch / ReplaceMapPointMatch; for
+ *                   MapPoint::SetBadFlag and Replace pass the observation list those functions hold.
+ *   set_bad         sets the flag, clears the row's slots, forgets its covisibles; the row and its parent value stay.
+ *                   *known counts the entries whose key frame is a row.
+ *   set_parent      the parent may be unknown or -1; for a kf that is no row yet the value is kept until it is added
+ *   set_covisibles  orbgpu_keyframe_db_set_covisibles's rule: a list for an id that is no row yet is kept until it is
+ *                   added; a bad row ignores the call
+ * Refused with ORBGPU_EINVAL before any device is touched, nothing changed: an id that is present (bad rows included), a
+ * negative id, idx outside the row, a map point id below -1, n_slots (or a query) above ORBGPU_COVIS_MAX_SLOTS, more than
+ * 10 covisibles, more than 2^20 rows or 2^30 pool slots (first choices, not measured limits).  A local map of more than
+ * 2^22 points returns ORBGPU_ECAPACITY.  The pool space of a bad row comes back on clear only (no compaction yet).
+ * Counts are always the full ones; at most `capacity` entries of a list are written.  prev_kf_ids and kf_ids may be one
+ * array.  Without a device the calls that compute or store return ORBGPU_EHIP (no CPU fallback). */
+#define ORBGPU_COVIS_MAX_SLOTS 65536
+#define ORBGPU_COVIS_MAX_COVISIBLES 10
+typedef struct orbgpu_covis_graph orbgpu_covis_graph;
+typedef struct orbgpu_covis_local_map_result {
+    int64_t ref_kf;             /* -1: no row has a vote (mpReferenceKF stays) */
+    int32_t n_kfs, n_points;    /* full lengths of the two lists */
+    int32_t max_votes, n_voted; /* n_voted = |K1| */
+    int32_t kept_previous, n_unknown_previous;
+} orbgpu_covis_local_map_result;
+int orbgpu_covis_graph_create(int32_t device_id, int32_t initial_rows, int64_t initial_slots, orbgpu_covis_graph **out);
+int orbgpu_covis_graph_destroy(orbgpu_covis_graph *g);
+int orbgpu_covis_graph_clear(orbgpu_covis_graph *g);
+/* Rows that are not bad, rows that are. */
+int orbgpu_covis_graph_size(const orbgpu_covis_graph *g, int32_t *alive, int32_t *bad);
+int orbgpu_covis_graph_add_keyframe(orbgpu_covis_graph *g, int64_t id, int32_t n_slots, const int64_t *mp_ids);
+int orbgpu_covis_graph_set_slots(orbgpu_covis_graph *g, int32_t n, const int64_t *kf_ids, const int32_t *idx, const int64_t *mp_ids,
+                                 int32_t *known);
+int orbgpu_covis_graph_set_bad(orbgpu_covis_graph *g, int32_t n, const int64_t *kf_ids, int32_t *known);
+int orbgpu_covis_graph_set_parent(orbgpu_covis_graph *g, int64_t kf_id, int64_t parent_id);
+int orbgpu_covis_graph_set_covisibles(orbgpu_covis_graph *g, int64_t kf_id, int32_t n, const int64_t *ids);
+int orbgpu_covis_local_map(orbgpu_covis_graph *g, int32_t n_kp, const int64_t *kp_ids, int32_t n_prev, const int64_t *prev_kf_ids,
+                           int32_t kf_capacity, int64_t *kf_ids, int32_t point_capacity, int64_t *point_ids,
+                           orbgpu_covis_local_map_result *res);
+int orbgpu_covis_connections(orbgpu_covis_graph *g, int64_t kf_id, int32_t th, int32_t capacity, int64_t *ids, int32_t *counts,
+                             int32_t *n, int32_t ordered_capacity, int64_t *ordered_ids, int32_t *ordered_weights, int32_t *n_ordered);
+/* Tests: how many vote launches of this handle read the query from global memory (more distinct ids than the LDS staging
+ * holds, or than ORBGPU_DEBUG_COVIS_LDS_IDS=<k>, read when the handle is created). */
+int orbgpu_covis_graph_debug_global_queries(const orbgpu_covis_graph *g, int64_t *n);
+
+/* ======================================================================================
  * On-disk formats of the end-of-run artefacts: host serialisers, byte for byte.
  * ====================================================================================== */
 /* Map::_WriteMapPoint (Map.cc:123-130): id (u64) + world position (3 x f32) = 20 bytes. */

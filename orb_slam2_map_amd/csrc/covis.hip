@@ -1,0 +1,1187 @@
+// Device-resident observation graph: the relation between key frames and map points, and the two votes over it.
+//
+// Tracking::UpdateLocalMap (Tracking.cc:1499-1643) lets every map point of the frame vote for the key frames that observe
+// it (std::map copies taken under a mutex), extends the voted key frames by neighbours, children and parents, and gathers
+// the map points of all of them; KeyFrame::UpdateConnections (KeyFrame.cc:327-417) is the same vote with the key frame's own
+// points as the query.  Here a key frame is a row keyed by KeyFrame::mnId (id_table.h); its slots -- the id of the map
+// point at every key-point index, -1 for none -- lie in one pool, key-frame-major, one int64 per slot.  That one relation
+// stands for both KeyFrame::mvpMapPoints and MapPoint::mObservations (V2), and a vote streams the pool once, 8 bytes per
+// slot, instead of chasing per-point maps:
+//   k_covis_vote     one wave per row: a lane takes a slot and binary-searches the query's distinct ids (sorted, with
+//                    multiplicities; staged in LDS, or read from global memory when the query is longer than the staging);
+//                    the wave adds up the multiplicities (V5).  Integers only.
+//   k_covis_list     one workgroup: the voted rows compacted in ascending id (through the id-order column), the row with
+//                    the strictly greatest count (V6), the <= 80-step extension with its candidate tests spread over the
+//                    lanes, and the slot prefix of the final list.
+//   k_covis_insert / k_covis_count / k_covis_scan / k_covis_emit / k_covis_unhash
+//                    the point gather: every slot of the list enters a device hash of 64-bit ids (integer atomicCAS on
+//                    the key, atomicMin on the position in the gather order); a slot whose position is the minimum is the
+//                    id's first occurrence; chunk counts, one scan and an order-preserving write follow.  The last kernel
+//                    empties exactly the hash slots the call used.  The result does not depend on scheduling.
+// No host decision lies between the vote and the points; a query waits twice (sizes, then lists).  Every call returns
+// synchronised; the caller serialises (CovisibilityGraphT does).  Refusals are answered before any device is touched.
+#include "common.h"
+#include "id_table.h"
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <new>
+#include <unordered_map>
+#include <vector>
+
+namespace orbgpu {
+
+constexpr int CV_MAX_NB = ORBGPU_COVIS_MAX_COVISIBLES;  // GetBestCovisibilityKeyFrames(10)
+constexpr int CV_MAX_SLOTS = ORBGPU_COVIS_MAX_SLOTS;    // slots of a row, key points of a query
+constexpr int CV_MAX_ROWS = 1 << 20;                    // first choices, as local BA's caps were
+constexpr int64_t CV_MAX_POOL = (int64_t)1 << 30;
+constexpr int CV_MAX_CALL = 1 << 20;                    // entries of a batched edit, ids of a previous list
+constexpr int CV_MAX_POINTS = 1 << 22;                  // local map points of one query
+constexpr int CV_MAX_LOCAL_KFS = 80;                    // Tracking.cc:1589
+constexpr int CV_LDS_IDS = 4096;                        // distinct query ids staged per block (8 + 4 bytes each: 48 KiB)
+constexpr int CV_BLOCK = 256;
+constexpr int CV_WAVES = CV_BLOCK / 64;
+constexpr int CV_LIST_BLOCK = 1024;
+constexpr int CV_CHUNK = 1024;  // gather positions per chunk: four steps of a 256-thread block
+constexpr int32_t CV_POS_NONE = 0x7F7F7F7F;  // (hipMemset's byte pattern) above every gather position (< 2^30)
+
+struct CvRow {  // 120 bytes; the host keeps a mirror and uploads the part an edit changes
+    int64_t id;
+    int64_t parent;  // -1: none; need not be a row
+    int64_t off;     // the row's slots in the pool
+    int32_t n_slots, bad;
+    int32_t nn, pad;
+    int64_t nb[CV_MAX_NB];
+};
+
+// header of a query, written by the kernels and downloaded with the first wait
+enum { CH_LIST = 0, CH_VOTED, CH_REF, CH_MAX, CH_KEPT, CH_SLOTS, CH_POINTS, CH_USED, CH_OVERFLOW, CH_RANGE, CH_WORDS };
+
+// exclusive prefix of v over the block in thread order, and the block's total; every thread of the block calls it
+__device__ __forceinline__ int block_scan_excl(int v, int *s_w, int &total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(incl, off, 64);
+        if (lane >= off)
+            incl += o;
+    }
+    __syncthreads();  // the previous call's reads of s_w are over
+    if (lane == 63)
+        s_w[wave] = incl;
+    __syncthreads();
+    int base = 0, all = 0;
+    for (int i = 0; i < nw; i++) {
+        if (i < wave)
+            base += s_w[i];
+        all += s_w[i];
+    }
+    total = all;
+    return base + incl - v;
+}
+
+__global__ __launch_bounds__(256) void k_covis_scatter(int n, const int64_t *__restrict__ addr, const int64_t *__restrict__ val,
+                                                       int64_t pool_used, int64_t *__restrict__ pool)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && addr[i] >= 0 && addr[i] < pool_used)  // (addresses are distinct: the host keeps the last entry of each)
+        pool[addr[i]] = val[i];
+}
+
+// count[row] = sum over the row's slots of the multiplicity of the slot's id in the query (V5); 0 for a bad row and for
+// `exclude_row` (orbgpu_covis_connections: the key frame itself).  Saturates at INT_MAX.
+template <bool LDS>
+__global__ __launch_bounds__(CV_BLOCK) void k_covis_vote(int n_rows, const CvRow *__restrict__ rows, const int64_t *__restrict__ pool,
+                                                         int64_t pool_used, int nq, const int64_t *__restrict__ q_ids,
+                                                         const int32_t *__restrict__ q_mult, int exclude_row,
+                                                         int32_t *__restrict__ count)
+{
+    extern __shared__ int64_t s_cv[];
+    const int64_t *q = q_ids;
+    const int32_t *m = q_mult;
+    if (LDS) {  // a template constant: the barrier is under workgroup-uniform control flow
+        int32_t *s_m = reinterpret_cast<int32_t *>(s_cv + nq);
+        for (int i = threadIdx.x; i < nq; i += CV_BLOCK) {
+            s_cv[i] = q_ids[i];
+            s_m[i] = q_mult[i];
+        }
+        __syncthreads();
+        q = s_cv;
+        m = s_m;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int row = blockIdx.x * CV_WAVES + wave; row < n_rows; row += gridDim.x * CV_WAVES) {  // wave-uniform
+        const int64_t off = rows[row].off;
+        const int len = rows[row].n_slots;
+        const bool live = !rows[row].bad && row != exclude_row && off >= 0 && len >= 0 && off + len <= pool_used;
+        unsigned sum = 0;  // per lane at most 2^10 slots of multiplicity 2^16
+        if (live && nq > 0) {
+            for (int e = lane; e < len; e += 64) {
+                const int64_t id = pool[off + e];
+                if (id < 0)
+                    continue;
+                int lo = 0, hi = nq;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (q[mid] < id)
+                        lo = mid + 1;
+                    else
+                        hi = mid;
+                }
+                if (lo < nq && q[lo] == id)
+                    sum += (unsigned)m[lo];
+            }
+        }
+        long long total = sum;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1)
+            total += __shfl_down(total, o, 64);
+        if (lane == 0)
+            count[row] = (int32_t)(total > INT_MAX ? INT_MAX : total);
+    }
+}
+
+struct CvList {  // the list a query builds, in the call's staging
+    int cap;
+    int32_t *rows;
+    int64_t *ids;
+    int32_t *counts;
+    int32_t *prefix;  // cap + 1: slots before every entry, then their total
+};
+
+__device__ __forceinline__ void covis_append(const CvList &l, int k, int r, const CvRow *rows, const int32_t *count, int32_t *stamp,
+                                             int cur)
+{
+    if (k < l.cap) {
+        l.rows[k] = r;
+        l.ids[k] = rows[r].id;
+        l.counts[k] = count[r];
+    }
+    stamp[r] = cur;
+}
+
+// mode 0: orbgpu_covis_local_map (V6).  mode 1: orbgpu_covis_connections (V7): the counter only, nothing stamped.
+__global__ __launch_bounds__(CV_LIST_BLOCK) void k_covis_list(int mode, int n_rows, const CvRow *__restrict__ rows,
+                                                              const int32_t *__restrict__ order, const int32_t *__restrict__ count,
+                                                              int32_t *stamp, int cur, const int64_t *__restrict__ hkeys,
+                                                              const int32_t *__restrict__ hvals, int log2cap, int n_prev,
+                                                              const int32_t *__restrict__ prev_rows, CvList l, long long *hdr)
+{
+    __shared__ int s_w[CV_LIST_BLOCK / 64];
+    __shared__ unsigned long long s_best[CV_LIST_BLOCK / 64];
+    __shared__ int s_cand, s_nb[CV_MAX_NB];
+    const int tid = threadIdx.x;
+    // K1: the not-bad rows with a vote, in ascending id; the first of them with the strictly greatest count
+    int n = 0;
+    unsigned long long best = 0;
+    for (int base = 0; base < n_rows; base += CV_LIST_BLOCK) {
+        const int p = base + tid;
+        int r = -1;
+        if (p < n_rows) {
+            const int o = order[p];
+            if (o >= 0 && o < n_rows && !rows[o].bad && count[o] > 0)
+                r = o;
+        }
+        int total;
+        const int k = n + block_scan_excl(r >= 0, s_w, total);
+        if (r >= 0) {
+            if (k < l.cap) {
+                l.rows[k] = r;
+                l.ids[k] = rows[r].id;
+                l.counts[k] = count[r];
+            }
+            if (mode == 0)
+                stamp[r] = cur;
+            const unsigned long long key = ((unsigned long long)(unsigned)count[r] << 32) | (0xFFFFFFFFu - (unsigned)k);
+            best = key > best ? key : best;
+        }
+        n += total;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_down(best, off, 64);
+        best = o > best ? o : best;
+    }
+    if ((tid & 63) == 0)
+        s_best[tid >> 6] = best;
+    __syncthreads();  // (also: the list and the stamps written above are visible to the whole workgroup)
+    best = s_best[0];
+    for (int i = 1; i < CV_LIST_BLOCK / 64; i++)
+        best = s_best[i] > best ? s_best[i] : best;
+    n = min(n, l.cap);
+    int L = n, kept = 0;
+    if (mode == 0 && n == 0) {  // Tracking.cc:1557-1558: no vote, the previous list stays
+        kept = 1;
+        L = min(n_prev, l.cap);
+        for (int i = tid; i < L; i += CV_LIST_BLOCK) {
+            const int r = min(max(prev_rows[i], 0), n_rows - 1);
+            l.rows[i] = r;
+            l.ids[i] = rows[r].id;
+            l.counts[i] = 0;
+        }
+    } else if (mode == 0) {
+        // Tracking.cc:1586-1636 over the positions of K1 only; the list grows behind them
+        for (int pos = 0; pos < n && pos <= CV_MAX_LOCAL_KFS; pos++) {
+            if (L > CV_MAX_LOCAL_KFS)
+                break;
+            __syncthreads();
+            const int r = l.rows[pos];
+            // (a) the first stored covisible that is known, not bad and not stamped
+            if (tid == 0)
+                s_cand = INT_MAX;
+            __syncthreads();
+            if (tid < CV_MAX_NB && tid < rows[r].nn) {
+                const int r2 = id_hash_lookup(hkeys, hvals, log2cap, rows[r].nb[tid]);
+                s_nb[tid] = r2;
+                if (r2 >= 0 && r2 < n_rows && !rows[r2].bad && stamp[r2] != cur)
+                    atomicMin(&s_cand, tid);
+            }
+            __syncthreads();
+            if (s_cand != INT_MAX) {
+                if (tid == 0)
+                    covis_append(l, L, s_nb[s_cand], rows, count, stamp, cur);
+                L++;
+            }
+            __syncthreads();
+            // (b) the first child (V3: rows whose parent is this one, ascending id) that is not bad and not stamped
+            if (tid == 0)
+                s_cand = INT_MAX;
+            __syncthreads();
+            const int64_t id = rows[r].id;
+            for (int p = tid; p < n_rows; p += CV_LIST_BLOCK) {
+                const int r2 = order[p];
+                if (r2 >= 0 && r2 < n_rows && rows[r2].parent == id && !rows[r2].bad && stamp[r2] != cur) {
+                    atomicMin(&s_cand, p);
+                    break;  // a thread's positions ascend
+                }
+            }
+            __syncthreads();
+            if (s_cand != INT_MAX) {
+                if (tid == 0)
+                    covis_append(l, L, order[s_cand], rows, count, stamp, cur);
+                L++;
+            }
+            __syncthreads();
+            // (c) the parent, with no bad test; the `break` of Tracking.cc:1632 leaves the OUTER loop
+            if (tid == 0) {
+                const int r2 = id_hash_lookup(hkeys, hvals, log2cap, rows[r].parent);
+                s_cand = r2 >= 0 && r2 < n_rows && stamp[r2] != cur ? r2 : -1;
+            }
+            __syncthreads();
+            if (s_cand >= 0) {
+                if (tid == 0)
+                    covis_append(l, L, s_cand, rows, count, stamp, cur);
+                L++;
+                break;
+            }
+        }
+        L = min(L, l.cap);
+    }
+    __syncthreads();
+    // slots before every entry of the final list (the gather order of the points)
+    int run = 0;
+    if (mode == 0)
+        for (int base = 0; base < L; base += CV_LIST_BLOCK) {
+            const int i = base + tid;
+            int v = 0;
+            if (i < L) {
+                const int r = l.rows[i];
+                v = r >= 0 && r < n_rows ? min(max(rows[r].n_slots, 0), CV_MAX_SLOTS) : 0;
+            }
+            int total;
+            const int ex = block_scan_excl(v, s_w, total);
+            if (i < L)
+                l.prefix[i] = run + ex;
+            if (total > (1 << 30) - run) {  // (the host bounds the sum; an overflow would be a bug, not a fault)
+                total = 0;
+                if (tid == 0)
+                    hdr[CH_RANGE] = 1;
+            }
+            run += total;
+        }
+    if (tid == 0) {
+        if (mode == 0)
+            l.prefix[L] = run;
+        const int kb = (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull));
+        hdr[CH_LIST] = L;
+        hdr[CH_VOTED] = n;
+        hdr[CH_REF] = n > 0 && kb >= 0 && kb < n ? l.ids[kb] : -1;
+        hdr[CH_MAX] = n > 0 ? (long long)(best >> 32) : 0;
+        hdr[CH_KEPT] = kept;
+        hdr[CH_SLOTS] = run;
+    }
+}
+
+// gather position p -> the id in that slot; false for an empty slot (and for an index outside its range)
+__device__ __forceinline__ bool covis_slot_at(int p, int L, const CvList &l, int n_rows, const CvRow *__restrict__ rows,
+                                              const int64_t *__restrict__ pool, int64_t pool_used, int64_t &id)
+{
+    int lo = 0, hi = L;  // prefix[lo] <= p < prefix[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (l.prefix[mid] <= p)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const int r = l.rows[lo];
+    if (r < 0 || r >= n_rows)
+        return false;
+    const int idx = p - l.prefix[lo];
+    const int64_t a = rows[r].off + idx;
+    if (idx < 0 || idx >= rows[r].n_slots || a < 0 || a >= pool_used)
+        return false;
+    id = pool[a];
+    return id >= 0;
+}
+
+struct CvPointHash {
+    int log2cap;
+    int limit;  // entries the call may make (<= capacity / 2)
+    int64_t *keys;
+    int32_t *pos;
+    int32_t *used;  // the slots the call filled, in any order: k_covis_unhash empties them
+};
+
+__global__ __launch_bounds__(CV_BLOCK) void k_covis_insert(CvList l, int n_rows, const CvRow *__restrict__ rows,
+                                                           const int64_t *__restrict__ pool, int64_t pool_used, CvPointHash h,
+                                                           long long *hdr)
+{
+    const int L = (int)hdr[CH_LIST], T = (int)hdr[CH_SLOTS];
+    const uint32_t mask = (1u << h.log2cap) - 1u;
+    for (int p = blockIdx.x * CV_BLOCK + threadIdx.x; p < T; p += gridDim.x * CV_BLOCK) {
+        int64_t id;
+        if (!covis_slot_at(p, L, l, n_rows, rows, pool, pool_used, id))
+            continue;
+        uint32_t s = id_hash_slot(id, h.log2cap);
+        bool placed = false;
+        for (uint32_t probe = 0; probe <= mask && !placed; probe++, s = (s + 1) & mask) {
+            const unsigned long long was = atomicCAS(reinterpret_cast<unsigned long long *>(h.keys + s),
+                                                     (unsigned long long)ID_HASH_EMPTY, (unsigned long long)id);
+            if (was == (unsigned long long)ID_HASH_EMPTY) {
+                const unsigned long long k = atomicAdd(reinterpret_cast<unsigned long long *>(hdr + CH_USED), 1ull);
+                if (k < (unsigned long long)h.limit)
+                    h.used[k] = (int32_t)s;
+                else
+                    hdr[CH_OVERFLOW] = 1;
+            }
+            if (was == (unsigned long long)ID_HASH_EMPTY || was == (unsigned long long)id) {
+                atomicMin(h.pos + s, p);
+                placed = true;
+            }
+        }
+        if (!placed)
+            hdr[CH_OVERFLOW] = 1;
+    }
+}
+
+// is gather position p the first occurrence of its id?
+__device__ __forceinline__ bool covis_first_at(int p, int L, const CvList &l, int n_rows, const CvRow *__restrict__ rows,
+                                               const int64_t *__restrict__ pool, int64_t pool_used, const CvPointHash &h, int64_t &id)
+{
+    if (!covis_slot_at(p, L, l, n_rows, rows, pool, pool_used, id))
+        return false;
+    const uint32_t mask = (1u << h.log2cap) - 1u;
+    uint32_t s = id_hash_slot(id, h.log2cap);
+    for (uint32_t probe = 0; probe <= mask; probe++, s = (s + 1) & mask) {
+        const int64_t k = h.keys[s];
+        if (k == id)
+            return h.pos[s] == p;
+        if (k == ID_HASH_EMPTY)
+            return false;
+    }
+    return false;
+}
+
+__global__ __launch_bounds__(CV_BLOCK) void k_covis_count(CvList l, int n_rows, const CvRow *__restrict__ rows,
+                                                          const int64_t *__restrict__ pool, int64_t pool_used, CvPointHash h,
+                                                          const long long *__restrict__ hdr, int n_chunks_cap,
+                                                          int32_t *__restrict__ chunks)
+{
+    __shared__ int s_n;
+    const int L = (int)hdr[CH_LIST], T = (int)hdr[CH_SLOTS];
+    const int n_chunks = min((T + CV_CHUNK - 1) / CV_CHUNK, n_chunks_cap);
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {  // workgroup-uniform
+        if (threadIdx.x == 0)
+            s_n = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int p = c * CV_CHUNK + threadIdx.x; p < min((c + 1) * CV_CHUNK, T); p += CV_BLOCK) {
+            int64_t id;
+            mine += covis_first_at(p, L, l, n_rows, rows, pool, pool_used, h, id);
+        }
+        mine = wave_reduce_add(mine);
+        if ((threadIdx.x & 63) == 0)
+            atomicAdd(&s_n, mine);  // an integer sum: the same in any order
+        __syncthreads();
+        if (threadIdx.x == 0)
+            chunks[c] = s_n;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(CV_LIST_BLOCK) void k_covis_scan(int n_chunks_cap, int32_t *chunks, long long *hdr)
+{
+    __shared__ int s_w[CV_LIST_BLOCK / 64];
+    const int T = (int)hdr[CH_SLOTS];
+    const int n_chunks = min((T + CV_CHUNK - 1) / CV_CHUNK, n_chunks_cap);
+    int run = 0;
+    for (int base = 0; base < n_chunks; base += CV_LIST_BLOCK) {
+        const int c = base + threadIdx.x;
+        const int v = c < n_chunks ? chunks[c] : 0;
+        int total;
+        const int ex = block_scan_excl(v, s_w, total);
+        if (c < n_chunks)
+            chunks[c] = run + ex;
+        run += total;
+    }
+    if (threadIdx.x == 0)
+        hdr[CH_POINTS] = run;
+}
+
+__global__ __launch_bounds__(CV_BLOCK) void k_covis_emit(CvList l, int n_rows, const CvRow *__restrict__ rows,
+                                                         const int64_t *__restrict__ pool, int64_t pool_used, CvPointHash h,
+                                                         const long long *__restrict__ hdr, int n_chunks_cap,
+                                                         const int32_t *__restrict__ chunks, int out_cap, int64_t *__restrict__ out)
+{
+    __shared__ int s_w[CV_WAVES];
+    const int L = (int)hdr[CH_LIST], T = (int)hdr[CH_SLOTS];
+    const int n_chunks = min((T + CV_CHUNK - 1) / CV_CHUNK, n_chunks_cap);
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {  // workgroup-uniform
+        int run = chunks[c];
+        for (int step = 0; step < CV_CHUNK / CV_BLOCK; step++) {
+            const int p = c * CV_CHUNK + step * CV_BLOCK + threadIdx.x;
+            int64_t id = -1;
+            const bool first = p < T && covis_first_at(p, L, l, n_rows, rows, pool, pool_used, h, id);
+            int total;
+            const int k = run + block_scan_excl(first, s_w, total);
+            if (first && k >= 0 && k < out_cap)
+                out[k] = id;
+            run += total;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_covis_unhash(CvPointHash h, const long long *__restrict__ hdr)
+{
+    const int n = (int)min(hdr[CH_USED], (long long)h.limit);
+    const uint32_t mask = (1u << h.log2cap) - 1u;
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
+        const uint32_t s = (uint32_t)h.used[k] & mask;
+        h.keys[s] = ID_HASH_EMPTY;
+        h.pos[s] = CV_POS_NONE;
+    }
+}
+
+constexpr int CV_ROW_COLS = 4;  // the per-row arrays of orbgpu_covis_graph
+
+} // namespace orbgpu
+
+using namespace orbgpu;
+
+struct orbgpu_covis_graph {
+    int device_id = 0, initial_rows = 0;
+    int64_t initial_slots = 0;
+    bool bound = false;  // device selected, stream created, first buffers allocated
+    hipStream_t stream = nullptr;
+    int rows = 0, row_cap = 0, n_bad = 0;
+    int64_t pool_used = 0, pool_cap = 0;
+    // per row, all carried over by a growth: the row, its vote, its query stamp (mnTrackReferenceForFrame), and the rows in
+    // ascending id (position p holds the row of the p-th smallest id)
+    DevBuf d_rows, d_count, d_stamp, d_order;
+    const IdColumn<DevBuf> row_cols[CV_ROW_COLS] = {{&d_rows, sizeof(CvRow)}, {&d_count, 4}, {&d_stamp, 4}, {&d_order, 4}};
+    orbgpu_covis_graph() = default;
+    orbgpu_covis_graph(const orbgpu_covis_graph &) = delete;
+    DevBuf d_pool, d_hkeys, d_hvals, d_stage, d_hdr, d_pkeys, d_ppos, d_used, d_chunks, d_points;
+    IdHash hash;  // id -> row (bad rows included); the device holds a byte-identical copy
+    std::vector<CvRow> h_rows;
+    std::vector<int64_t> h_pool;   // the slots, as the device holds them
+    std::vector<int32_t> h_order;  // rows in ascending id
+    std::unordered_map<int64_t, std::vector<int64_t>> covis;  // lists set for ids that are not rows yet
+    std::unordered_map<int64_t, int64_t> parents;             // parents set for ids that are not rows yet
+    std::vector<char> stage;
+    int stamp = 0;
+    int lds_ids = CV_LDS_IDS;    // ORBGPU_DEBUG_COVIS_LDS_IDS, read at creation
+    int point_log2 = 0;          // the point hash as allocated
+    bool point_dirty = true;     // it may hold entries: emptied as a whole before its next use
+    int64_t global_queries = 0;  // vote launches that read the query from global memory (tests)
+};
+
+namespace orbgpu {
+
+static int cv_grow_rows(orbgpu_covis_graph *g, int want)
+{
+    if (want <= g->row_cap)
+        return ORBGPU_OK;
+    int ncap = std::max(g->row_cap, 1);
+    while (ncap < want)
+        ncap *= 2;
+    TableStreamOps ops{g->stream, "growing the covisibility graph"};
+    const IdTableParts<DevBuf> parts{g->row_cols, CV_ROW_COLS, CV_ROW_COLS, &g->d_hkeys, &g->d_hvals, &g->hash, &g->row_cap};
+    return id_table_grow(parts, g->rows, ncap, ops);
+}
+
+static int cv_grow_pool(orbgpu_covis_graph *g, int64_t want)
+{
+    if (want <= g->pool_cap)
+        return ORBGPU_OK;
+    int64_t ncap = std::max<int64_t>(g->pool_cap, 1024);
+    while (ncap < want)
+        ncap *= 2;
+    DevBuf np;
+    int rc = np.reserve(8 * (size_t)ncap);
+    if (rc == ORBGPU_OK && g->pool_used > 0) {
+        hipError_t he = hipMemcpyAsync(np.p, g->d_pool.p, 8 * (size_t)g->pool_used, hipMemcpyDeviceToDevice, g->stream);
+        if (he == hipSuccess)
+            he = hipStreamSynchronize(g->stream);
+        if (he != hipSuccess) {
+            set_error("growing the slot pool: %s", hipGetErrorString(he));
+            rc = ORBGPU_EHIP;
+        }
+    }
+    if (rc != ORBGPU_OK) {
+        (void)hipStreamSynchronize(g->stream);
+        np.release();
+        return rc;
+    }
+    std::swap(g->d_pool, np);
+    np.release();
+    g->pool_cap = ncap;
+    return ORBGPU_OK;
+}
+
+// Growth after the first call: under the lifecycle lock, on the growing branch only (id_table.h).
+static int cv_grow_locked(orbgpu_covis_graph *g, int rows, int64_t pool)
+{
+    return lifecycle_locked_unless(rows <= g->row_cap && pool <= g->pool_cap, lifecycle_mutex(), [&] {
+        const int rc = cv_grow_rows(g, rows);
+        return rc != ORBGPU_OK ? rc : cv_grow_pool(g, pool);
+    });
+}
+static int cv_reserve_locked(DevBuf &b, size_t bytes)
+{
+    return lifecycle_locked_unless(bytes <= b.bytes, lifecycle_mutex(), [&] { return b.reserve(bytes); });
+}
+
+// first call that needs the device: select it, create the stream, allocate for initial_rows / initial_slots
+static int cv_bind(orbgpu_covis_graph *g)
+{
+    int rc = select_device(g->device_id);
+    if (rc != ORBGPU_OK || g->bound)
+        return rc;
+    std::lock_guard<std::mutex> lifecycle(lifecycle_mutex());
+    if (!g->stream) {
+        hipError_t he = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
+        if (he != hipSuccess) {
+            g->stream = nullptr;
+            set_error("hipStreamCreate: %s", hipGetErrorString(he));
+            return ORBGPU_EHIP;
+        }
+    }
+    const int rows0 = g->initial_rows > 0 ? g->initial_rows : 1024;
+    const int64_t slots0 = g->initial_slots > 0 ? g->initial_slots : std::min<int64_t>((int64_t)rows0 * 1024, 1 << 22);
+    if ((rc = cv_grow_rows(g, rows0)) != ORBGPU_OK || (rc = cv_grow_pool(g, slots0)) != ORBGPU_OK)
+        return rc;
+    if ((rc = g->d_hdr.reserve(8 * CH_WORDS)) != ORBGPU_OK)
+        return rc;
+    g->bound = true;
+    return ORBGPU_OK;
+}
+
+static int cv_sync_or_fail(orbgpu_covis_graph *g, hipError_t he, const char *what)
+{
+    const hipError_t se = hipStreamSynchronize(g->stream);  // also after a failed enqueue: copies read the caller's arrays
+    if (he == hipSuccess)
+        he = se;
+    if (he != hipSuccess) {
+        set_error("%s: %s", what, hipGetErrorString(he));
+        return ORBGPU_EHIP;
+    }
+    return ORBGPU_OK;
+}
+
+// the distinct ids >= 0 of a query in ascending order, with their multiplicities
+static void cv_query(int n, const int64_t *ids, std::vector<int64_t> &q, std::vector<int32_t> &mult)
+{
+    std::vector<int64_t> s;
+    for (int i = 0; i < n; i++)
+        if (ids[i] >= 0)
+            s.push_back(ids[i]);
+    std::sort(s.begin(), s.end());
+    q.clear();
+    mult.clear();
+    for (size_t i = 0; i < s.size(); i++) {
+        if (i == 0 || s[i] != s[i - 1]) {
+            q.push_back(s[i]);
+            mult.push_back(0);
+        }
+        mult.back()++;
+    }
+}
+
+static void cv_launch_vote(orbgpu_covis_graph *g, int nq, const int64_t *q_ids, const int32_t *q_mult, int exclude_row)
+{
+    const int grid = std::min((g->rows + CV_WAVES - 1) / CV_WAVES, 4096);
+    const CvRow *rows = g->d_rows.as<CvRow>();
+    if (nq <= g->lds_ids)
+        hipLaunchKernelGGL(k_covis_vote<true>, dim3(grid), dim3(CV_BLOCK), 12 * (size_t)std::max(nq, 1), g->stream, g->rows, rows,
+                           g->d_pool.as<int64_t>(), g->pool_used, nq, q_ids, q_mult, exclude_row, g->d_count.as<int32_t>());
+    else {
+        g->global_queries++;
+        hipLaunchKernelGGL(k_covis_vote<false>, dim3(grid), dim3(CV_BLOCK), 0, g->stream, g->rows, rows, g->d_pool.as<int64_t>(),
+                           g->pool_used, nq, q_ids, q_mult, exclude_row, g->d_count.as<int32_t>());
+    }
+}
+
+// A query: stage the inputs, vote, build the list and -- local map only -- gather the points; first wait: the header.
+struct CvStaged {
+    size_t o_q = 0, o_mult = 0, o_prev = 0, in_bytes = 0, o_rows = 0, o_ids = 0, o_counts = 0, o_prefix = 0;
+    int list_cap = 0, point_cap = 0;
+    long long hdr[CH_WORDS] = {};
+};
+
+static int cv_run(orbgpu_covis_graph *g, int mode, const std::vector<int64_t> &q, const std::vector<int32_t> &mult, int exclude_row,
+                  const std::vector<int32_t> &prev_rows, int64_t prev_slots, CvStaged &s)
+{
+    const int nq = (int)q.size(), np = (int)prev_rows.size();
+    s.list_cap = std::max(g->rows, np) + 1;
+    Carver c;
+    s.o_q = c.take(8 * (size_t)std::max(nq, 1));
+    s.o_mult = c.take(4 * (size_t)std::max(nq, 1));
+    s.o_prev = c.take(4 * (size_t)std::max(np, 1));
+    s.in_bytes = c.off;
+    s.o_rows = c.take(4 * (size_t)s.list_cap);
+    s.o_ids = c.take(8 * (size_t)s.list_cap);
+    s.o_counts = c.take(4 * (size_t)s.list_cap);
+    s.o_prefix = c.take(4 * ((size_t)s.list_cap + 1));
+    int rc = cv_reserve_locked(g->d_stage, c.off);
+    if (rc != ORBGPU_OK)
+        return rc;
+    // the gather: at most `bound` slots (every row once, or the previous list), at most CV_MAX_POINTS distinct ids
+    const int64_t bound = std::max<int64_t>(std::max(g->pool_used, prev_slots), 1);
+    const int n_chunks = (int)((bound + CV_CHUNK - 1) / CV_CHUNK) + 1;
+    CvPointHash h{};
+    if (mode == 0) {
+        s.point_cap = (int)std::min<int64_t>(bound, CV_MAX_POINTS);
+        const int l2 = id_hash_log2cap(std::max(s.point_cap, 512));
+        if (l2 > g->point_log2) {
+            if ((rc = cv_reserve_locked(g->d_pkeys, sizeof(int64_t) << l2)) != ORBGPU_OK)
+                return rc;
+            g->point_dirty = true;  // (one of the two may be new)
+            if ((rc = cv_reserve_locked(g->d_ppos, sizeof(int32_t) << l2)) != ORBGPU_OK)
+                return rc;
+            g->point_log2 = l2;
+        }
+        if ((rc = cv_reserve_locked(g->d_used, 4 * (size_t)s.point_cap)) != ORBGPU_OK ||
+            (rc = cv_reserve_locked(g->d_points, 8 * (size_t)s.point_cap)) != ORBGPU_OK ||
+            (rc = cv_reserve_locked(g->d_chunks, 4 * (size_t)n_chunks)) != ORBGPU_OK)
+            return rc;
+        h = CvPointHash{g->point_log2, s.point_cap, g->d_pkeys.as<int64_t>(), g->d_ppos.as<int32_t>(), g->d_used.as<int32_t>()};
+    }
+    g->stage.resize(s.in_bytes);
+    if (nq) {
+        memcpy(g->stage.data() + s.o_q, q.data(), 8 * (size_t)nq);
+        memcpy(g->stage.data() + s.o_mult, mult.data(), 4 * (size_t)nq);
+    }
+    if (np)
+        memcpy(g->stage.data() + s.o_prev, prev_rows.data(), 4 * (size_t)np);
+    hipError_t he = hipSuccess;
+    if (mode == 0) {
+        if (g->stamp == INT_MAX) {  // the stamps of 2^31 queries are used up: start again
+            he = hipMemsetAsync(g->d_stamp.p, 0, 4 * (size_t)g->row_cap, g->stream);
+            g->stamp = 0;
+        }
+        g->stamp++;
+        if (he == hipSuccess && g->point_dirty) {
+            he = hipMemsetAsync(g->d_pkeys.p, 0xFF, sizeof(int64_t) << g->point_log2, g->stream);  // ID_HASH_EMPTY
+            if (he == hipSuccess)
+                he = hipMemsetAsync(g->d_ppos.p, 0x7F, sizeof(int32_t) << g->point_log2, g->stream);  // CV_POS_NONE
+        }
+        g->point_dirty = true;  // until this call has emptied what it filled
+    }
+    char *st = g->d_stage.as<char>();
+    long long *hdr = g->d_hdr.as<long long>();
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(st, g->stage.data(), s.in_bytes, hipMemcpyHostToDevice, g->stream);
+    if (he == hipSuccess)
+        he = hipMemsetAsync(hdr, 0, 8 * CH_WORDS, g->stream);
+    if (he == hipSuccess) {
+        const CvRow *rows = g->d_rows.as<CvRow>();
+        const int64_t *pool = g->d_pool.as<int64_t>();
+        const CvList l{s.list_cap, reinterpret_cast<int32_t *>(st + s.o_rows), reinterpret_cast<int64_t *>(st + s.o_ids),
+                       reinterpret_cast<int32_t *>(st + s.o_counts), reinterpret_cast<int32_t *>(st + s.o_prefix)};
+        cv_launch_vote(g, nq, reinterpret_cast<const int64_t *>(st + s.o_q), reinterpret_cast<const int32_t *>(st + s.o_mult),
+                       exclude_row);
+        hipLaunchKernelGGL(k_covis_list, dim3(1), dim3(CV_LIST_BLOCK), 0, g->stream, mode, g->rows, rows, g->d_order.as<int32_t>(),
+                           g->d_count.as<int32_t>(), g->d_stamp.as<int32_t>(), g->stamp, g->d_hkeys.as<int64_t>(),
+                           g->d_hvals.as<int32_t>(), g->hash.log2cap, np, reinterpret_cast<const int32_t *>(st + s.o_prev), l, hdr);
+        if (mode == 0) {
+            const int grid = (int)std::min<int64_t>((bound + CV_CHUNK - 1) / CV_CHUNK, 2048);
+            hipLaunchKernelGGL(k_covis_insert, dim3(grid), dim3(CV_BLOCK), 0, g->stream, l, g->rows, rows, pool, g->pool_used, h, hdr);
+            hipLaunchKernelGGL(k_covis_count, dim3(grid), dim3(CV_BLOCK), 0, g->stream, l, g->rows, rows, pool, g->pool_used, h, hdr,
+                               n_chunks, g->d_chunks.as<int32_t>());
+            hipLaunchKernelGGL(k_covis_scan, dim3(1), dim3(CV_LIST_BLOCK), 0, g->stream, n_chunks, g->d_chunks.as<int32_t>(), hdr);
+            hipLaunchKernelGGL(k_covis_emit, dim3(grid), dim3(CV_BLOCK), 0, g->stream, l, g->rows, rows, pool, g->pool_used, h, hdr,
+                               n_chunks, g->d_chunks.as<int32_t>(), s.point_cap, g->d_points.as<int64_t>());
+            hipLaunchKernelGGL(k_covis_unhash, dim3(std::min((s.point_cap + 255) / 256, 1024)), dim3(256), 0, g->stream, h, hdr);
+        }
+        he = hipGetLastError();
+        if (he == hipSuccess)
+            he = hipMemcpyAsync(s.hdr, hdr, 8 * CH_WORDS, hipMemcpyDeviceToHost, g->stream);
+    }
+    if ((rc = cv_sync_or_fail(g, he, mode == 0 ? "local map query" : "connections query")) != ORBGPU_OK)
+        return rc;
+    if (s.hdr[CH_RANGE] || s.hdr[CH_LIST] < 0 || s.hdr[CH_LIST] > s.list_cap) {
+        set_error("covisibility graph: an index left its range on the device");
+        return ORBGPU_EHIP;
+    }
+    if (mode == 0 && !s.hdr[CH_OVERFLOW])
+        g->point_dirty = false;
+    return ORBGPU_OK;
+}
+
+static int cv_destroy(orbgpu_covis_graph *g)
+{
+    if (!g)
+        return ORBGPU_OK;
+    if (g->bound || g->stream) {
+        (void)hipSetDevice(g->device_id);
+        if (g->stream) {
+            (void)hipStreamSynchronize(g->stream);
+            (void)hipStreamDestroy(g->stream);
+        }
+        for (const IdColumn<DevBuf> &c : g->row_cols)
+            c.buf->release();
+        for (DevBuf *b : {&g->d_pool, &g->d_hkeys, &g->d_hvals, &g->d_stage, &g->d_hdr, &g->d_pkeys, &g->d_ppos, &g->d_used,
+                          &g->d_chunks, &g->d_points})
+            b->release();
+    }
+    delete g;
+    return ORBGPU_OK;
+}
+
+} // namespace orbgpu
+
+extern "C" {
+
+int orbgpu_covis_graph_create(int32_t device_id, int32_t initial_rows, int64_t initial_slots, orbgpu_covis_graph **out)
+{
+    ORBGPU_REQUIRE(out, "null argument");
+    ORBGPU_REQUIRE(device_id >= 0, "device_id = %d", device_id);
+    ORBGPU_REQUIRE(initial_rows >= 0 && initial_rows <= CV_MAX_ROWS, "initial_rows = %d (at most %d)", initial_rows, CV_MAX_ROWS);
+    ORBGPU_REQUIRE(initial_slots >= 0 && initial_slots <= CV_MAX_POOL, "initial_slots = %lld (at most %lld)",
+                   (long long)initial_slots, (long long)CV_MAX_POOL);
+    orbgpu_covis_graph *g = new (std::nothrow) orbgpu_covis_graph();
+    if (!g) {
+        set_error("out of host memory");
+        return ORBGPU_ENOMEM;
+    }
+    g->device_id = device_id;
+    g->initial_rows = initial_rows;
+    g->initial_slots = initial_slots;
+    // ORBGPU_DEBUG_COVIS_LDS_IDS=<k> (tests): a query of more than k distinct ids takes the global-memory path
+    if (const char *e = getenv("ORBGPU_DEBUG_COVIS_LDS_IDS"))
+        g->lds_ids = std::min(std::max(atoi(e), 0), CV_LDS_IDS);
+    *out = g;
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_graph_destroy(orbgpu_covis_graph *g)
+{
+    std::lock_guard<std::mutex> lifecycle(orbgpu::lifecycle_mutex());
+    return cv_destroy(g);
+}
+
+int orbgpu_covis_graph_clear(orbgpu_covis_graph *g)
+{
+    ORBGPU_REQUIRE(g, "null argument");
+    if (g->bound) {
+        int rc = select_device(g->device_id);
+        if (rc != ORBGPU_OK)
+            return rc;
+        hipError_t he = hipMemsetAsync(g->d_hkeys.p, 0xFF, sizeof(int64_t) << g->hash.log2cap, g->stream);  // ID_HASH_EMPTY
+        if ((rc = cv_sync_or_fail(g, he, "clearing the covisibility graph")) != ORBGPU_OK)
+            return rc;
+    }
+    g->hash.clear();
+    g->h_rows.clear();
+    g->h_pool.clear();
+    g->h_order.clear();
+    g->covis.clear();
+    g->parents.clear();
+    g->rows = g->n_bad = 0;
+    g->pool_used = 0;
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_graph_size(const orbgpu_covis_graph *g, int32_t *alive, int32_t *bad)
+{
+    ORBGPU_REQUIRE(g && alive && bad, "null argument");
+    *alive = g->rows - g->n_bad;
+    *bad = g->n_bad;
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_graph_add_keyframe(orbgpu_covis_graph *g, int64_t id, int32_t n_slots, const int64_t *mp_ids)
+{
+    ORBGPU_REQUIRE(g, "null argument");
+    ORBGPU_REQUIRE(id >= 0, "key frame id %lld", (long long)id);
+    ORBGPU_REQUIRE(n_slots >= 0 && n_slots <= CV_MAX_SLOTS, "n_slots = %d (at most %d)", n_slots, CV_MAX_SLOTS);
+    for (int i = 0; mp_ids && i < n_slots; i++)
+        ORBGPU_REQUIRE(mp_ids[i] >= -1, "map point id %lld at slot %d", (long long)mp_ids[i], i);
+    ORBGPU_REQUIRE(g->hash.find(id) < 0, "key frame %lld is in the graph", (long long)id);
+    ORBGPU_REQUIRE(g->rows < CV_MAX_ROWS, "more than %d rows", CV_MAX_ROWS);
+    ORBGPU_REQUIRE(g->pool_used + n_slots <= CV_MAX_POOL, "more than %lld pool slots", (long long)CV_MAX_POOL);
+    int rc = cv_bind(g);
+    if (rc != ORBGPU_OK || (rc = cv_grow_locked(g, g->rows + 1, g->pool_used + n_slots)) != ORBGPU_OK)
+        return rc;
+    CvRow row{};
+    row.id = id;
+    row.parent = -1;
+    row.off = g->pool_used;
+    row.n_slots = n_slots;
+    for (int k = 0; k < CV_MAX_NB; k++)
+        row.nb[k] = -1;
+    const auto ic = g->covis.find(id);
+    if (ic != g->covis.end()) {
+        row.nn = (int32_t)ic->second.size();
+        std::copy(ic->second.begin(), ic->second.end(), row.nb);
+    }
+    const auto ip = g->parents.find(id);
+    if (ip != g->parents.end())
+        row.parent = ip->second;
+    const int r = g->rows;
+    const uint32_t slot = g->hash.slot_for(id);
+    // the rows in ascending id: the new one usually goes last
+    const size_t at = (size_t)(std::lower_bound(g->h_order.begin(), g->h_order.end(), id,
+                                                [g](int32_t a, int64_t v) { return g->h_rows[(size_t)a].id < v; }) -
+                               g->h_order.begin());
+    std::vector<int32_t> tail;
+    tail.push_back(r);
+    tail.insert(tail.end(), g->h_order.begin() + (ptrdiff_t)at, g->h_order.end());
+    std::vector<int64_t> slots((size_t)n_slots, -1);
+    if (mp_ids && n_slots)
+        memcpy(slots.data(), mp_ids, 8 * (size_t)n_slots);
+    hipError_t he = hipSuccess;
+    if (n_slots > 0)
+        he = hipMemcpyAsync(g->d_pool.as<int64_t>() + g->pool_used, slots.data(), 8 * (size_t)n_slots, hipMemcpyHostToDevice, g->stream);
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(g->d_order.as<int32_t>() + at, tail.data(), 4 * tail.size(), hipMemcpyHostToDevice, g->stream);
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(g->d_rows.as<CvRow>() + r, &row, sizeof(row), hipMemcpyHostToDevice, g->stream);
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(g->d_hvals.as<int32_t>() + slot, &r, 4, hipMemcpyHostToDevice, g->stream);
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(g->d_hkeys.as<int64_t>() + slot, &id, 8, hipMemcpyHostToDevice, g->stream);
+    if ((rc = cv_sync_or_fail(g, he, "adding a key frame")) != ORBGPU_OK) {
+        if (at < g->h_order.size())  // the order column as it was (best effort: the failure is reported either way)
+            (void)hipMemcpy(g->d_order.as<int32_t>() + at, g->h_order.data() + at, 4 * (g->h_order.size() - at), hipMemcpyHostToDevice);
+        return rc;
+    }
+    g->hash.keys[slot] = id;
+    g->hash.vals[slot] = r;
+    g->h_rows.push_back(row);
+    g->h_order.insert(g->h_order.begin() + (ptrdiff_t)at, r);
+    g->h_pool.insert(g->h_pool.end(), slots.begin(), slots.end());
+    g->covis.erase(id);
+    g->parents.erase(id);
+    g->pool_used += n_slots;
+    g->rows++;
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_graph_set_slots(orbgpu_covis_graph *g, int32_t n, const int64_t *kf_ids, const int32_t *idx, const int64_t *mp_ids,
+                                 int32_t *known)
+{
+    ORBGPU_REQUIRE(g && n >= 0 && n <= CV_MAX_CALL && (n == 0 || (kf_ids && idx && mp_ids)), "bad argument");
+    std::vector<int64_t> addr;
+    int n_known = 0;
+    for (int i = 0; i < n; i++) {
+        ORBGPU_REQUIRE(mp_ids[i] >= -1, "map point id %lld (entry %d)", (long long)mp_ids[i], i);
+        const int r = g->hash.find(kf_ids[i]);
+        if (r < 0) {
+            addr.push_back(-1);
+            continue;  // an unknown key frame: ignored
+        }
+        const CvRow &row = g->h_rows[(size_t)r];
+        ORBGPU_REQUIRE(idx[i] >= 0 && idx[i] < row.n_slots, "slot %d outside key frame %lld (%d slots, entry %d)", idx[i],
+                       (long long)row.id, row.n_slots, i);
+        n_known++;
+        addr.push_back(row.bad ? -1 : row.off + idx[i]);  // V2: a bad key frame holds no slot
+    }
+    if (known)
+        *known = n_known;
+    // applied in order to the mirror (later entries win); the device gets the final value of every slot touched
+    std::vector<std::pair<int64_t, int64_t>> undo;
+    for (int i = 0; i < n; i++)
+        if (addr[(size_t)i] >= 0) {
+            undo.emplace_back(addr[(size_t)i], g->h_pool[(size_t)addr[(size_t)i]]);
+            g->h_pool[(size_t)addr[(size_t)i]] = mp_ids[i];
+        }
+    if (undo.empty())
+        return ORBGPU_OK;
+    std::vector<int64_t> a;
+    for (const auto &u : undo)
+        a.push_back(u.first);
+    std::sort(a.begin(), a.end());
+    a.erase(std::unique(a.begin(), a.end()), a.end());
+    const int m = (int)a.size();
+    auto fail = [&](int rc) {
+        for (size_t k = undo.size(); k-- > 0;)
+            g->h_pool[(size_t)undo[k].first] = undo[k].second;
+        return rc;
+    };
+    int rc = cv_bind(g);
+    if (rc != ORBGPU_OK)
+        return fail(rc);
+    Carver c;
+    const size_t o_a = c.take(8 * (size_t)m), o_v = c.take(8 * (size_t)m);
+    if ((rc = cv_reserve_locked(g->d_stage, c.off)) != ORBGPU_OK)
+        return fail(rc);
+    g->stage.resize(c.off);
+    memcpy(g->stage.data() + o_a, a.data(), 8 * (size_t)m);
+    int64_t *v = reinterpret_cast<int64_t *>(g->stage.data() + o_v);
+    for (int k = 0; k < m; k++)
+        v[k] = g->h_pool[(size_t)a[(size_t)k]];
+    char *st = g->d_stage.as<char>();
+    hipError_t he = hipMemcpyAsync(st, g->stage.data(), c.off, hipMemcpyHostToDevice, g->stream);
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(k_covis_scatter, dim3((m + 255) / 256), dim3(256), 0, g->stream, m, reinterpret_cast<const int64_t *>(st + o_a),
+                           reinterpret_cast<const int64_t *>(st + o_v), g->pool_used, g->d_pool.as<int64_t>());
+        he = hipGetLastError();
+    }
+    if ((rc = cv_sync_or_fail(g, he, "setting slots")) != ORBGPU_OK)
+        return fail(rc);
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_graph_set_bad(orbgpu_covis_graph *g, int32_t n, const int64_t *kf_ids, int32_t *known)
+{
+    ORBGPU_REQUIRE(g && n >= 0 && n <= CV_MAX_CALL && (n == 0 || kf_ids), "bad argument");
+    if (known)
+        *known = 0;
+    std::vector<int> todo;
+    int n_known = 0;
+    for (int i = 0; i < n; i++) {
+        const int r = g->hash.find(kf_ids[i]);
+        if (r < 0)
+            continue;
+        n_known++;
+        if (!g->h_rows[(size_t)r].bad && std::find(todo.begin(), todo.end(), r) == todo.end())
+            todo.push_back(r);
+    }
+    if (!todo.empty()) {
+        int rc = cv_bind(g);
+        if (rc != ORBGPU_OK)
+            return rc;
+        std::vector<CvRow> nr;
+        for (int r : todo) {
+            CvRow row = g->h_rows[(size_t)r];
+            row.bad = 1;
+            row.nn = 0;
+            for (int k = 0; k < CV_MAX_NB; k++)
+                row.nb[k] = -1;
+            nr.push_back(row);
+        }
+        hipError_t he = hipSuccess;
+        for (size_t k = 0; k < todo.size() && he == hipSuccess; k++) {
+            he = hipMemcpyAsync(g->d_rows.as<CvRow>() + todo[k], &nr[k], sizeof(CvRow), hipMemcpyHostToDevice, g->stream);
+            if (he == hipSuccess && nr[k].n_slots > 0)
+                he = hipMemsetAsync(g->d_pool.as<int64_t>() + nr[k].off, 0xFF, 8 * (size_t)nr[k].n_slots, g->stream);  // -1
+        }
+        if ((rc = cv_sync_or_fail(g, he, "setting key frames bad")) != ORBGPU_OK) {
+            // put back what may have been written: rows and slots as the mirror has them
+            for (size_t k = 0; k < todo.size(); k++) {
+                const CvRow &row = g->h_rows[(size_t)todo[k]];
+                (void)hipMemcpy(g->d_rows.as<CvRow>() + todo[k], &row, sizeof(CvRow), hipMemcpyHostToDevice);
+                if (row.n_slots > 0)
+                    (void)hipMemcpy(g->d_pool.as<int64_t>() + row.off, g->h_pool.data() + row.off, 8 * (size_t)row.n_slots,
+                                    hipMemcpyHostToDevice);
+            }
+            return rc;
+        }
+        for (size_t k = 0; k < todo.size(); k++) {
+            g->h_rows[(size_t)todo[k]] = nr[k];
+            std::fill(g->h_pool.begin() + (ptrdiff_t)nr[k].off, g->h_pool.begin() + (ptrdiff_t)(nr[k].off + nr[k].n_slots), (int64_t)-1);
+        }
+        g->n_bad += (int)todo.size();
+    }
+    if (known)
+        *known = n_known;
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_graph_set_parent(orbgpu_covis_graph *g, int64_t kf_id, int64_t parent_id)
+{
+    ORBGPU_REQUIRE(g, "null argument");
+    ORBGPU_REQUIRE(kf_id >= 0 && parent_id >= -1, "key frame %lld, parent %lld", (long long)kf_id, (long long)parent_id);
+    const int r = g->hash.find(kf_id);
+    if (r < 0) {
+        g->parents[kf_id] = parent_id;  // kept for when the key frame is added
+        return ORBGPU_OK;
+    }
+    int rc = cv_bind(g);
+    if (rc != ORBGPU_OK)
+        return rc;
+    hipError_t he = hipMemcpyAsync(reinterpret_cast<char *>(g->d_rows.as<CvRow>() + r) + offsetof(CvRow, parent), &parent_id, 8,
+                                   hipMemcpyHostToDevice, g->stream);
+    if ((rc = cv_sync_or_fail(g, he, "setting a parent")) != ORBGPU_OK)
+        return rc;
+    g->h_rows[(size_t)r].parent = parent_id;
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_graph_set_covisibles(orbgpu_covis_graph *g, int64_t kf_id, int32_t n, const int64_t *ids)
+{
+    ORBGPU_REQUIRE(g, "null argument");
+    ORBGPU_REQUIRE(kf_id >= 0, "key frame id %lld", (long long)kf_id);
+    ORBGPU_REQUIRE(n >= 0 && n <= CV_MAX_NB && (n == 0 || ids), "%d covisibles (at most %d)", n, CV_MAX_NB);
+    for (int k = 0; k < n; k++)
+        ORBGPU_REQUIRE(ids[k] >= 0, "covisible id %lld", (long long)ids[k]);
+    const int r = g->hash.find(kf_id);
+    if (r < 0) {
+        g->covis[kf_id].assign(ids, ids + n);  // kept for when the key frame is added
+        return ORBGPU_OK;
+    }
+    if (g->h_rows[(size_t)r].bad)
+        return ORBGPU_OK;  // a bad key frame has forgotten its covisibles and learns no new ones
+    int rc = cv_bind(g);
+    if (rc != ORBGPU_OK)
+        return rc;
+    CvRow row = g->h_rows[(size_t)r];
+    row.nn = n;
+    for (int k = 0; k < CV_MAX_NB; k++)
+        row.nb[k] = k < n ? ids[k] : -1;
+    const size_t o = offsetof(CvRow, nn);
+    hipError_t he = hipMemcpyAsync(reinterpret_cast<char *>(g->d_rows.as<CvRow>() + r) + o, reinterpret_cast<const char *>(&row) + o,
+                                   sizeof(CvRow) - o, hipMemcpyHostToDevice, g->stream);
+    if ((rc = cv_sync_or_fail(g, he, "setting covisible key frames")) != ORBGPU_OK)
+        return rc;
+    g->h_rows[(size_t)r] = row;
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_graph_debug_global_queries(const orbgpu_covis_graph *g, int64_t *n)
+{
+    ORBGPU_REQUIRE(g && n, "null argument");
+    *n = g->global_queries;
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_local_map(orbgpu_covis_graph *g, int32_t n_kp, const int64_t *kp_ids, int32_t n_prev, const int64_t *prev_kf_ids,
+                           int32_t kf_capacity, int64_t *kf_ids, int32_t point_capacity, int64_t *point_ids,
+                           orbgpu_covis_local_map_result *res)
+{
+    ORBGPU_REQUIRE(g && res, "null argument");
+    ORBGPU_REQUIRE(n_kp >= 0 && n_kp <= CV_MAX_SLOTS && (n_kp == 0 || kp_ids), "n_kp = %d (at most %d)", n_kp, CV_MAX_SLOTS);
+    ORBGPU_REQUIRE(n_prev >= 0 && n_prev <= CV_MAX_CALL && (n_prev == 0 || prev_kf_ids), "n_prev = %d (at most %d)", n_prev, CV_MAX_CALL);
+    ORBGPU_REQUIRE(kf_capacity >= 0 && (kf_capacity == 0 || kf_ids) && point_capacity >= 0 && (point_capacity == 0 || point_ids),
+                   "bad output capacity");
+    std::vector<int32_t> prev_rows;
+    int64_t prev_slots = 0;
+    for (int i = 0; i < n_prev; i++) {
+        const int r = g->hash.find(prev_kf_ids[i]);
+        if (r < 0)
+            continue;
+        prev_rows.push_back(r);
+        prev_slots += g->h_rows[(size_t)r].n_slots;
+    }
+    ORBGPU_REQUIRE(prev_slots <= CV_MAX_POOL, "the previous list holds more than %lld slots", (long long)CV_MAX_POOL);
+    memset(res, 0, sizeof(*res));
+    res->ref_kf = -1;
+    res->kept_previous = 1;
+    res->n_unknown_previous = n_prev - (int32_t)prev_rows.size();
+    if (g->rows == 0)
+        return ORBGPU_OK;  // every previous id is unknown: an empty list, no device needed
+    std::vector<int64_t> q;
+    std::vector<int32_t> mult;
+    cv_query(n_kp, kp_ids, q, mult);
+    int rc = cv_bind(g);
+    if (rc != ORBGPU_OK)
+        return rc;
+    CvStaged s;
+    if ((rc = cv_run(g, 0, q, mult, -1, prev_rows, prev_slots, s)) != ORBGPU_OK)
+        return rc;
+    if (s.hdr[CH_OVERFLOW] || s.hdr[CH_POINTS] > CV_MAX_POINTS) {
+        set_error("a local map of more than %d points", CV_MAX_POINTS);
+        return ORBGPU_ECAPACITY;
+    }
+    res->n_kfs = (int32_t)s.hdr[CH_LIST];
+    res->n_voted = (int32_t)s.hdr[CH_VOTED];
+    res->ref_kf = s.hdr[CH_REF];
+    res->max_votes = (int32_t)s.hdr[CH_MAX];
+    res->kept_previous = (int32_t)s.hdr[CH_KEPT];
+    res->n_points = (int32_t)std::min<long long>(s.hdr[CH_POINTS], s.point_cap);
+    // second wait: the lists, as long as the caller's arrays
+    const int nk = std::min(res->n_kfs, kf_capacity), npt = std::min(res->n_points, point_capacity);
+    if (nk > 0 || npt > 0) {
+        hipError_t he = hipSuccess;
+        if (nk > 0)
+            he = hipMemcpyAsync(kf_ids, g->d_stage.as<char>() + s.o_ids, 8 * (size_t)nk, hipMemcpyDeviceToHost, g->stream);
+        if (he == hipSuccess && npt > 0)
+            he = hipMemcpyAsync(point_ids, g->d_points.p, 8 * (size_t)npt, hipMemcpyDeviceToHost, g->stream);
+        if ((rc = cv_sync_or_fail(g, he, "local map query (lists)")) != ORBGPU_OK)
+            return rc;
+    }
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_connections(orbgpu_covis_graph *g, int64_t kf_id, int32_t th, int32_t capacity, int64_t *ids, int32_t *counts,
+                             int32_t *n, int32_t ordered_capacity, int64_t *ordered_ids, int32_t *ordered_weights, int32_t *n_ordered)
+{
+    ORBGPU_REQUIRE(g && n && n_ordered, "null argument");
+    ORBGPU_REQUIRE(capacity >= 0 && (capacity == 0 || (ids && counts)) && ordered_capacity >= 0 &&
+                       (ordered_capacity == 0 || (ordered_ids && ordered_weights)),
+                   "bad output capacity");
+    *n = *n_ordered = 0;
+    const int r = g->hash.find(kf_id);
+    if (r < 0 || g->h_rows[(size_t)r].bad)
+        return ORBGPU_OK;
+    const CvRow &row = g->h_rows[(size_t)r];
+    std::vector<int64_t> q;
+    std::vector<int32_t> mult;
+    cv_query(row.n_slots, g->h_pool.data() + row.off, q, mult);
+    if (q.empty())
+        return ORBGPU_OK;
+    int rc = cv_bind(g);
+    if (rc != ORBGPU_OK)
+        return rc;
+    CvStaged s;
+    if ((rc = cv_run(g, 1, q, mult, r, std::vector<int32_t>(), 0, s)) != ORBGPU_OK)
+        return rc;
+    const int nc = (int)s.hdr[CH_LIST];
+    if (nc == 0)
+        return ORBGPU_OK;
+    std::vector<int64_t> c_ids((size_t)nc);
+    std::vector<int32_t> c_n((size_t)nc);
+    hipError_t he = hipMemcpyAsync(c_ids.data(), g->d_stage.as<char>() + s.o_ids, 8 * (size_t)nc, hipMemcpyDeviceToHost, g->stream);
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(c_n.data(), g->d_stage.as<char>() + s.o_counts, 4 * (size_t)nc, hipMemcpyDeviceToHost, g->stream);
+    if ((rc = cv_sync_or_fail(g, he, "connections query (lists)")) != ORBGPU_OK)
+        return rc;
+    *n = nc;
+    for (int k = 0; k < nc && k < capacity; k++) {
+        ids[k] = c_ids[(size_t)k];
+        counts[k] = c_n[(size_t)k];
+    }
+    // KeyFrame.cc:364-399: the entries at the threshold, or the single first-strictly-greatest one; descending (weight, id)
+    std::vector<std::pair<int32_t, int64_t>> pairs;
+    for (int k = 0; k < nc; k++)
+        if (c_n[(size_t)k] >= th)
+            pairs.emplace_back(c_n[(size_t)k], c_ids[(size_t)k]);
+    if (pairs.empty())
+        pairs.emplace_back((int32_t)s.hdr[CH_MAX], (int64_t)s.hdr[CH_REF]);
+    std::sort(pairs.begin(), pairs.end());
+    std::reverse(pairs.begin(), pairs.end());
+    *n_ordered = (int32_t)pairs.size();
+    for (int k = 0; k < (int)pairs.size() && k < ordered_capacity; k++) {
+        ordered_ids[k] = pairs[(size_t)k].second;
+        ordered_weights[k] = pairs[(size_t)k].first;
+    }
+    return ORBGPU_OK;
+}
+
+} // extern "C"

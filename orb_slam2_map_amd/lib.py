@@ -297,6 +297,12 @@ NEW_POINTS_MAX_NEIGHBOURS = 32
 _LIB = None
 
 # every symbol include/orbgpu.h declares (checked by tests/test_abi.py against the header text)
+class CovisLocalMapResult(C.Structure):
+    """orbgpu_covis_local_map_result"""
+    _fields_ = [("ref_kf", C.c_int64), ("n_kfs", C.c_int32), ("n_points", C.c_int32), ("max_votes", C.c_int32),
+                ("n_voted", C.c_int32), ("kept_previous", C.c_int32), ("n_unknown_previous", C.c_int32)]
+
+
 ABI_SYMBOLS = [
     "orbgpu_last_error_string", "orbgpu_abi_version", "orbgpu_device_count", "orbgpu_measure_copy_bandwidth",
     "orbgpu_set_trig_mode", "orbgpu_get_trig_mode", "orbgpu_trig_table_info", "orbgpu_trig_host_eval", "orbgpu_trig_eval",
@@ -339,6 +345,10 @@ ABI_SYMBOLS = [
     "orbgpu_keyframe_db_add", "orbgpu_keyframe_db_erase", "orbgpu_keyframe_db_set_covisibles", "orbgpu_keyframe_db_score",
     "orbgpu_keyframe_db_detect_loop", "orbgpu_keyframe_db_detect_reloc", "orbgpu_keyframe_db_last_query",
     "orbgpu_keyframe_db_debug_global_queries",
+    "orbgpu_covis_graph_create", "orbgpu_covis_graph_destroy", "orbgpu_covis_graph_clear", "orbgpu_covis_graph_size",
+    "orbgpu_covis_graph_add_keyframe", "orbgpu_covis_graph_set_slots", "orbgpu_covis_graph_set_bad",
+    "orbgpu_covis_graph_set_parent", "orbgpu_covis_graph_set_covisibles", "orbgpu_covis_local_map",
+    "orbgpu_covis_connections", "orbgpu_covis_graph_debug_global_queries",
     "orbgpu_vocabulary_create", "orbgpu_vocabulary_destroy", "orbgpu_vocabulary_size", "orbgpu_bow_transform",
     "orbgpu_bow_transform_batch_device", "orbgpu_search_by_bow", "orbgpu_search_by_bow_batch_device",
     "orbgpu_search_by_bow_keyframes", "orbgpu_search_for_triangulation", "orbgpu_search_for_initialization", "orbgpu_fuse", "orbgpu_fuse_sim3",
@@ -449,6 +459,18 @@ def lib():
         "orbgpu_keyframe_db_detect_reloc": [vp, i32, vp, vp, i32, vp, vp],
         "orbgpu_keyframe_db_last_query": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
         "orbgpu_keyframe_db_debug_global_queries": [vp, vp],
+        "orbgpu_covis_graph_create": [i32, i32, C.c_int64, vp],
+        "orbgpu_covis_graph_destroy": [vp],
+        "orbgpu_covis_graph_clear": [vp],
+        "orbgpu_covis_graph_size": [vp, vp, vp],
+        "orbgpu_covis_graph_add_keyframe": [vp, C.c_int64, i32, vp],
+        "orbgpu_covis_graph_set_slots": [vp, i32, vp, vp, vp, vp],
+        "orbgpu_covis_graph_set_bad": [vp, i32, vp, vp],
+        "orbgpu_covis_graph_set_parent": [vp, C.c_int64, C.c_int64],
+        "orbgpu_covis_graph_set_covisibles": [vp, C.c_int64, i32, vp],
+        "orbgpu_covis_local_map": [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp],
+        "orbgpu_covis_connections": [vp, C.c_int64, i32, i32, vp, vp, vp, i32, vp, vp, vp],
+        "orbgpu_covis_graph_debug_global_queries": [vp, vp],
     }
     for name, args in sigs.items():
         fn = getattr(L, name, None)
@@ -2303,6 +2325,108 @@ class KeyFrameDatabase:
         check(self.L.orbgpu_keyframe_db_last_query(self.h, n.value, _p(cols["id"]), _p(cols["words"]), _p(cols["first_word"]),
                                                    _p(cols["score"]), _p(cols["acc"]), _p(cols["best_id"]), C.byref(n)))
         return {k: v[:n.value] for k, v in cols.items()}
+
+
+class CovisibilityGraph:
+    """Device-resident observation graph keyed by KeyFrame::mnId (orbgpu_covis_*): the relation between key frames and map
+    points, the local map of Tracking::UpdateLocalMap and the counter of KeyFrame::UpdateConnections (conventions V1-V7 of
+    include/orbgpu.h).  All ids are int64; the device is bound by the first call that needs it."""
+    MAX_SLOTS = 65536
+    MAX_COVISIBLES = 10
+
+    def __init__(self, initial_rows=0, initial_slots=0, device_id=0):
+        self.L = lib()
+        self.h = C.c_void_p()
+        check(self.L.orbgpu_covis_graph_create(device_id, int(initial_rows), int(initial_slots), C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.orbgpu_covis_graph_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _ids(a):
+        return np.ascontiguousarray(a, np.int64).reshape(-1)
+
+    def clear(self):
+        check(self.L.orbgpu_covis_graph_clear(self.h))
+
+    def size(self):
+        """(rows that are not bad, rows that are)"""
+        a, b = C.c_int32(), C.c_int32()
+        check(self.L.orbgpu_covis_graph_size(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def add_keyframe(self, kf_id, n_slots, mp_ids=None):
+        if mp_ids is not None:
+            mp_ids = self._ids(mp_ids)
+            if len(mp_ids) != int(n_slots):
+                raise ValueError("mp_ids holds one id per slot")
+        check(self.L.orbgpu_covis_graph_add_keyframe(self.h, int(kf_id), int(n_slots), _p(mp_ids)))
+
+    def set_slots(self, kf_ids, idx, mp_ids):
+        """returns how many entries named a key frame of the graph"""
+        kf_ids, mp_ids = self._ids(kf_ids), self._ids(mp_ids)
+        idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        if not len(kf_ids) == len(idx) == len(mp_ids):
+            raise ValueError("set_slots takes three arrays of one length")
+        k = C.c_int32()
+        check(self.L.orbgpu_covis_graph_set_slots(self.h, len(kf_ids), _p(kf_ids), _p(idx), _p(mp_ids), C.byref(k)))
+        return k.value
+
+    def set_bad(self, kf_ids):
+        kf_ids = self._ids(np.atleast_1d(kf_ids))
+        k = C.c_int32()
+        check(self.L.orbgpu_covis_graph_set_bad(self.h, len(kf_ids), _p(kf_ids), C.byref(k)))
+        return k.value
+
+    def set_parent(self, kf_id, parent_id):
+        check(self.L.orbgpu_covis_graph_set_parent(self.h, int(kf_id), int(parent_id)))
+
+    def set_covisibles(self, kf_id, ids):
+        ids = self._ids(ids)
+        check(self.L.orbgpu_covis_graph_set_covisibles(self.h, int(kf_id), len(ids), _p(ids)))
+
+    def local_map(self, kp_ids, prev_kf_ids=(), kf_capacity=None, point_capacity=None):
+        """UpdateLocalKeyFrames + UpdateLocalPoints: dict of kf_ids, point_ids (as long as the capacities allow) and the
+        fields of orbgpu_covis_local_map_result"""
+        kp, prev = self._ids(kp_ids), self._ids(prev_kf_ids)
+        res = CovisLocalMapResult()
+        if kf_capacity is None or point_capacity is None:  # the full lengths first
+            check(self.L.orbgpu_covis_local_map(self.h, len(kp), _p(kp), len(prev), _p(prev), 0, None, 0, None, C.byref(res)))
+            kf_capacity = res.n_kfs if kf_capacity is None else kf_capacity
+            point_capacity = res.n_points if point_capacity is None else point_capacity
+        kfs, pts = np.zeros(max(int(kf_capacity), 1), np.int64), np.zeros(max(int(point_capacity), 1), np.int64)
+        check(self.L.orbgpu_covis_local_map(self.h, len(kp), _p(kp), len(prev), _p(prev), int(kf_capacity), _p(kfs),
+                                            int(point_capacity), _p(pts), C.byref(res)))
+        out = {name: getattr(res, name) for name, _ in CovisLocalMapResult._fields_}
+        out["kf_ids"] = kfs[:min(res.n_kfs, int(kf_capacity))].copy()
+        out["point_ids"] = pts[:min(res.n_points, int(point_capacity))].copy()
+        return out
+
+    def connections(self, kf_id, th=15, capacity=None, ordered_capacity=None):
+        """UpdateConnections' counter: dict of ids, counts (ascending id), ordered_ids, ordered_weights and n, n_ordered"""
+        cap = sum(self.size()) if capacity is None else int(capacity)
+        ocap = cap if ordered_capacity is None else int(ordered_capacity)
+        ids, counts = np.zeros(max(cap, 1), np.int64), np.zeros(max(cap, 1), np.int32)
+        oids, ow = np.zeros(max(ocap, 1), np.int64), np.zeros(max(ocap, 1), np.int32)
+        n, no = C.c_int32(), C.c_int32()
+        check(self.L.orbgpu_covis_connections(self.h, int(kf_id), int(th), cap, _p(ids), _p(counts), C.byref(n), ocap, _p(oids),
+                                              _p(ow), C.byref(no)))
+        return dict(n=n.value, n_ordered=no.value, ids=ids[:min(n.value, cap)].copy(), counts=counts[:min(n.value, cap)].copy(),
+                    ordered_ids=oids[:min(no.value, ocap)].copy(), ordered_weights=ow[:min(no.value, ocap)].copy())
+
+    def debug_global_queries(self):
+        """vote launches of this handle that read the query from global memory, not from LDS"""
+        n = C.c_int64()
+        check(self.L.orbgpu_covis_graph_debug_global_queries(self.h, C.byref(n)))
+        return n.value
 
 
 def search_by_bow(desc_kf, angle_kf, valid_kf, node_kf, desc_f, angle_f, node_f, th_low=TH_LOW, nnratio=0.7,

@@ -2453,6 +2453,254 @@ template <typename KeyFrameT> class KeyFrameDatabaseT {
 };
 
 // --------------------------------------------------------------------------------------------
+// Observation graph (orbgpu_covis_*): Tracking::UpdateLocalMap and the counting half of KeyFrame::UpdateConnections over
+// the device-resident relation between key frames and map points (include/orbgpu.h, conventions V1-V7).
+// KeyFrameT needs mnId, N, GetMapPointMatches(), GetMapPoint(idx), AddConnection(KeyFrameT *, int), isBad() and
+// mnTrackReferenceForFrame; MapPointT needs mnId, isBad() and mnTrackReferenceForFrame; the frame passed to UpdateLocalMap
+// needs N, mnId, mvpMapPoints and mpReferenceKF.  The class keeps id -> pointer maps of the key frames it was given and of
+// the map points its hooks have seen (ORB-SLAM2 never deletes either), so that the lists hold the caller's pointers.
+// It serialises its calls with a mutex of its own, as MapPointTableT does, and never calls into a key frame or a map
+// point while it holds it -- except the lock-free reads named at each hook.  INTEGRATION.md 2o lists the hook sites.
+// --------------------------------------------------------------------------------------------
+template <typename KeyFrameT, typename MapPointT> class CovisibilityGraphT {
+  public:
+    struct SlotEdit {
+        KeyFrameT *kf;
+        size_t idx;
+        MapPointT *mp;  // nullptr clears the slot
+    };
+    struct Connections {
+        std::vector<std::pair<KeyFrameT *, int>> counter;  // ascending mnId: mConnectedKeyFrameWeights
+        std::vector<KeyFrameT *> ordered;                  // mvpOrderedConnectedKeyFrames
+        std::vector<int> weights;                          // mvOrderedWeights
+    };
+
+    explicit CovisibilityGraphT(int device_id = 0, int initial_rows = 0, int64_t initial_slots = 0)
+    {
+        check(orbgpu_covis_graph_create(device_id, initial_rows, initial_slots, &h_), "CovisibilityGraph");
+    }
+    ~CovisibilityGraphT() { orbgpu_covis_graph_destroy(h_); }
+    CovisibilityGraphT(const CovisibilityGraphT &) = delete;
+    CovisibilityGraphT &operator=(const CovisibilityGraphT &) = delete;
+    orbgpu_covis_graph *handle() const { return h_; }
+
+    // the ids of a key frame's mvpMapPoints: -1 for an empty slot and for a bad point (V2: a bad point holds no slot)
+    static std::vector<int64_t> SlotIds(const std::vector<MapPointT *> &mps)
+    {
+        std::vector<int64_t> ids(mps.size(), -1);
+        for (size_t i = 0; i < mps.size(); i++)
+            if (mps[i] && !mps[i]->isBad())
+                ids[i] = (int64_t)mps[i]->mnId;
+        return ids;
+    }
+
+    // hook: where a key frame enters the map (Map::AddKeyFrame), with the matches it holds at that moment
+    void AddKeyFrame(KeyFrameT *pKF)
+    {
+        const std::vector<MapPointT *> mps = pKF->GetMapPointMatches();
+        const std::vector<int64_t> ids = SlotIds(mps);
+        std::lock_guard<std::mutex> g(mu_);
+        check(orbgpu_covis_graph_add_keyframe(h_, (int64_t)pKF->mnId, (int32_t)ids.size(), ids.data()), "CovisibilityGraph::AddKeyFrame");
+        kfs_.put((int64_t)pKF->mnId, pKF);
+        for (MapPointT *p : mps)
+            if (p)
+                mps_.put((int64_t)p->mnId, p);
+    }
+    // hook: AddObservation / EraseObservation / EraseMapPointMatch / ReplaceMapPointMatch, batched: one call per key frame
+    // from ProcessNewKeyFrame, from NewPointsCall::WriteBack and from the Fuse edit loop.  Applied in order.
+    void SetSlots(const std::vector<SlotEdit> &edits)
+    {
+        if (edits.empty())
+            return;
+        std::lock_guard<std::mutex> g(mu_);
+        Marshal(edits);
+        check(orbgpu_covis_graph_set_slots(h_, (int32_t)ids_.size(), ids_.data(), idx_.data(), vals_.data(), nullptr),
+              "CovisibilityGraph::SetSlots");
+        for (const SlotEdit &e : edits)
+            if (e.mp)
+                mps_.put((int64_t)e.mp->mnId, e.mp);
+    }
+    void SetSlot(KeyFrameT *pKF, size_t idx, MapPointT *pMP) { SetSlots({SlotEdit{pKF, idx, pMP}}); }
+    // hook: the end of MapPoint::SetBadFlag and of MapPoint::Replace, with the observation list those functions copied
+    // (`obs`): every slot it names takes what the reference's loop left there -- nothing, or the replacing point.
+    template <typename ObservationsT> void SyncObservations(const ObservationsT &obs)
+    {
+        std::vector<SlotEdit> edits;
+        for (const auto &kv : obs) {
+            MapPointT *now = kv.first->GetMapPoint(kv.second);
+            edits.push_back(SlotEdit{kv.first, (size_t)kv.second, now && !now->isBad() ? now : nullptr});
+        }
+        SetSlots(edits);
+    }
+    // hook: the end of KeyFrame::SetBadFlag (after mbBad = true); the children's ChangeParent calls reach SetParent
+    void SetKeyFrameBad(KeyFrameT *pKF)
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        const int64_t id = (int64_t)pKF->mnId;
+        check(orbgpu_covis_graph_set_bad(h_, 1, &id, nullptr), "CovisibilityGraph::SetKeyFrameBad");
+    }
+    // hook: KeyFrame::ChangeParent and the first connection of UpdateConnections
+    void SetParent(KeyFrameT *pKF, KeyFrameT *pParent)
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        check(orbgpu_covis_graph_set_parent(h_, (int64_t)pKF->mnId, pParent ? (int64_t)pParent->mnId : -1), "CovisibilityGraph::SetParent");
+    }
+    // hook: the end of KeyFrame::UpdateBestCovisibles, inside the function (KeyFrameDatabaseT::UpdateCovisibles's place)
+    void UpdateCovisibles(KeyFrameT *pKF, const std::vector<KeyFrameT *> &ordered)
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        ids_.clear();
+        for (size_t i = 0; i < ordered.size() && i < ORBGPU_COVIS_MAX_COVISIBLES; i++)
+            ids_.push_back((int64_t)ordered[i]->mnId);
+        check(orbgpu_covis_graph_set_covisibles(h_, (int64_t)pKF->mnId, (int32_t)ids_.size(), ids_.data()),
+              "CovisibilityGraph::UpdateCovisibles");
+    }
+    void clear()  // Map::clear
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        check(orbgpu_covis_graph_clear(h_), "CovisibilityGraph::clear");
+        kfs_.clear();
+        mps_.clear();
+    }
+    size_t KeyFrames() const
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        return kfs_.size();
+    }
+
+    // Tracking::UpdateLocalMap (Tracking.cc:1499-1643) with the reference's side effects: bad points leave the frame
+    // (:1552), the listed key frames and points are stamped with the frame's id, the reference key frame is set on the
+    // tracker and on the frame if a key frame was voted for; without a vote mvpLocalKeyFrames stays as it is (:1557-1558).
+    template <typename FrameT>
+    void UpdateLocalMap(FrameT &F, std::vector<KeyFrameT *> &mvpLocalKeyFrames, std::vector<MapPointT *> &mvpLocalMapPoints,
+                        KeyFrameT *&mpReferenceKF)
+    {
+        std::vector<int64_t> kp((size_t)F.N, -1), prev;
+        for (int i = 0; i < F.N; i++)
+            if (F.mvpMapPoints[(size_t)i]) {
+                if (!F.mvpMapPoints[(size_t)i]->isBad())
+                    kp[(size_t)i] = (int64_t)F.mvpMapPoints[(size_t)i]->mnId;
+                else
+                    F.mvpMapPoints[(size_t)i] = nullptr;
+            }
+        for (KeyFrameT *p : mvpLocalKeyFrames)
+            prev.push_back((int64_t)p->mnId);
+        std::vector<KeyFrameT *> kfs;
+        std::vector<MapPointT *> mps;
+        orbgpu_covis_local_map_result res;
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            // the lists never outnumber the key frames (plus the previous list) and the slots: one call returns them all
+            ids_.assign(kfs_.size() + prev.size() + 1, -1);
+            vals_.assign(std::max<size_t>(last_points_ * 2, 4096), -1);
+            for (int attempt = 0; attempt < 2; attempt++) {
+                check(orbgpu_covis_local_map(h_, (int32_t)kp.size(), kp.data(), (int32_t)prev.size(), prev.data(), (int32_t)ids_.size(),
+                                             ids_.data(), (int32_t)vals_.size(), vals_.data(), &res),
+                      "CovisibilityGraph::UpdateLocalMap");
+                if ((size_t)res.n_points <= vals_.size())
+                    break;
+                vals_.assign((size_t)res.n_points, -1);  // (a local map that more than doubled: once more, with room)
+            }
+            last_points_ = (size_t)res.n_points;
+            kfs = kfs_.Resolve(ids_.data(), std::min((size_t)res.n_kfs, ids_.size()));
+            mps = mps_.Resolve(vals_.data(), std::min((size_t)res.n_points, vals_.size()));
+        }
+        if (!res.kept_previous)
+            mvpLocalKeyFrames.swap(kfs);
+        for (KeyFrameT *p : mvpLocalKeyFrames)
+            p->mnTrackReferenceForFrame = F.mnId;
+        mvpLocalMapPoints.swap(mps);
+        for (MapPointT *p : mvpLocalMapPoints)
+            p->mnTrackReferenceForFrame = F.mnId;
+        if (res.ref_kf >= 0) {
+            const std::vector<KeyFrameT *> ref = [&] {
+                std::lock_guard<std::mutex> g(mu_);
+                return kfs_.Resolve(&res.ref_kf, 1);
+            }();
+            if (!ref.empty()) {
+                mpReferenceKF = ref[0];
+                F.mpReferenceKF = ref[0];
+            }
+        }
+    }
+
+    // The counting half of KeyFrame::UpdateConnections (KeyFrame.cc:327-399) and its host half: the counter, AddConnection
+    // on the key frames at the threshold (or on the single best one), the ordered vectors.  `apply(connections)` runs where
+    // the reference takes mMutexConnections (:401-416): it stores the three containers and returns the new parent if this
+    // was the first connection (nullptr otherwise).  The two hooks follow.  Returns false if no key frame was counted
+    // (:361-362: nothing changes).
+    template <typename Apply> bool UpdateConnections(KeyFrameT *pKF, Apply apply, int th = 15)
+    {
+        Connections c;
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            const int32_t cap = (int32_t)std::max<size_t>(kfs_.size(), 1);
+            ids_.assign((size_t)cap, -1);
+            vals_.assign((size_t)cap, -1);
+            std::vector<int32_t> counts((size_t)cap), weights((size_t)cap);
+            int32_t n = 0, n_ordered = 0;
+            check(orbgpu_covis_connections(h_, (int64_t)pKF->mnId, th, cap, ids_.data(), counts.data(), &n, cap, vals_.data(),
+                                           weights.data(), &n_ordered),
+                  "CovisibilityGraph::UpdateConnections");
+            c = MakeConnections(kfs_, ids_.data(), counts.data(), (size_t)std::min(n, cap), vals_.data(), weights.data(),
+                                (size_t)std::min(n_ordered, cap));
+        }
+        if (c.counter.empty() || c.ordered.empty())
+            return false;
+        KeyFrameT *parent = HostHalf(pKF, c, apply);
+        UpdateCovisibles(pKF, c.ordered);
+        if (parent)
+            SetParent(pKF, parent);
+        return true;
+    }
+
+    // host only: a batch of slot edits as the ABI's three arrays
+    static void MarshalSlots(const std::vector<SlotEdit> &edits, std::vector<int64_t> &kf_ids, std::vector<int32_t> &idx,
+                             std::vector<int64_t> &mp_ids)
+    {
+        kf_ids.clear(), idx.clear(), mp_ids.clear();
+        for (const SlotEdit &e : edits) {
+            kf_ids.push_back((int64_t)e.kf->mnId);
+            idx.push_back((int32_t)e.idx);
+            mp_ids.push_back(e.mp ? (int64_t)e.mp->mnId : -1);
+        }
+    }
+    // host only: the lists of orbgpu_covis_connections as the reference's containers (an id the map does not hold is skipped)
+    static Connections MakeConnections(const IdPtrMap<KeyFrameT> &kfs, const int64_t *ids, const int32_t *counts, size_t n,
+                                       const int64_t *ordered_ids, const int32_t *weights, size_t n_ordered)
+    {
+        Connections c;
+        for (size_t i = 0; i < n; i++)
+            for (KeyFrameT *p : kfs.Resolve(ids + i, 1))
+                c.counter.emplace_back(p, (int)counts[i]);
+        for (size_t i = 0; i < n_ordered; i++)
+            for (KeyFrameT *p : kfs.Resolve(ordered_ids + i, 1)) {
+                c.ordered.push_back(p);
+                c.weights.push_back((int)weights[i]);
+            }
+        return c;
+    }
+    // host only: KeyFrame.cc:382 / :389 (AddConnection on every listed key frame; the order among them does not matter)
+    // and :401-416 through `apply`
+    template <typename Apply> static KeyFrameT *HostHalf(KeyFrameT *pKF, const Connections &c, Apply apply)
+    {
+        for (size_t i = 0; i < c.ordered.size(); i++)
+            c.ordered[i]->AddConnection(pKF, c.weights[i]);
+        return apply(c);
+    }
+
+  private:
+    void Marshal(const std::vector<SlotEdit> &edits) { MarshalSlots(edits, ids_, idx_, vals_); }
+    orbgpu_covis_graph *h_ = nullptr;
+    mutable std::mutex mu_;
+    IdPtrMap<KeyFrameT> kfs_;
+    IdPtrMap<MapPointT> mps_;
+    std::vector<int64_t> ids_, vals_;
+    std::vector<int32_t> idx_;
+    size_t last_points_ = 0;
+};
+
+// --------------------------------------------------------------------------------------------
 // PointCloudMapping (reference include/PointCloudMap.h:41-88, src/PointCloudMap.cc)
 // Keeps the reference's thread / condition-variable protocol; the per-key-frame arithmetic runs on
 // the GPU.  KeyFrameT needs mImDep (float depth), mImRGB (8UC3), fx, fy, cx, cy and GetPose();
