@@ -1809,16 +1809,24 @@ int orbgpu_keyframe_db_last_query(orbgpu_keyframe_db *db, int32_t capacity, int6
 int orbgpu_keyframe_db_debug_global_queries(const orbgpu_keyframe_db *db, int64_t *n);
 
 /* ======================================================================================
- * Observation graph  (Tracking::UpdateLocalMap, Tracking.cc:1499-1643; KeyFrame::UpdateConnections, KeyFrame.cc:327-417)
+ * Observation graph  (Tracking::UpdateLocalMap, Tracking.cc:1499-1643; KeyFrame::UpdateConnections, KeyFrame.cc:327-417;
+ *                     LocalMapping::KeyFrameCulling, LocalMapping.cc:632-698)
  * ======================================================================================
  * The relation between key frames and map points, device-resident and keyed by KeyFrame::mnId, and the two votes over
  * it: the frame's map points vote for the key frames that observe them (the local map of Tracking::TrackLocalMap), and a
- * key frame's own points vote for the other key frames (its covisibility weights).  Conventions V1-V7 (DESIGN.md
- * section 2); all of it is integer work and the results are equal to tests/covis_model.py's, entry for entry.
+ * key frame's own points vote for the other key frames (its covisibility weights); and the redundancy test of
+ * KeyFrameCulling over the same relation.  Conventions V1-V8; all of it is integer work and the
+ * results are equal to tests/covis_model.py's and tests/cull_model.py's, entry for entry.
  *   V1 rows    one row per key frame, n_slots (the frame's N, 0 allowed) fixed at add; the slots lie in one pool,
  *              key-frame-major, one int64 each: the id of the map point at that key-point index, -1 for none.  A row has
  *              a bad flag, a parent id (-1: none), up to 10 best-covisible ids in the caller's order (stored as ids and
  *              resolved when a query runs) and a per-query stamp (mnTrackReferenceForFrame).  Rows are in add order.
+ *              A second pool column holds one attribute byte per slot, set once per key frame (set_keypoints): bits 0-3 the
+ *              key point's octave (mvKeysUn[idx].octave, below ORBGPU_COVIS_MAX_LEVELS), ORBGPU_COVIS_KP_STEREO if
+ *              mvuRight[idx] >= 0 (the observation weighs 2 in MapPoint::nObs, MapPoint.cc:105-108), ORBGPU_COVIS_KP_FAR if
+ *              !mbMonocular && (mvDepth[idx] > mThDepth || mvDepth[idx] < 0) (LocalMapping.cc:660-664); bits 4-5 are
+ *              reserved and refused.  Every slot of a new row holds 0: octave 0, monocular, close.  Only V8 and
+ *              orbgpu_covis_observations read the column; the votes of V5-V7 do not.
  *   V2 one relation   slot (kf, idx) = p stands for both "kf holds p at idx" (KeyFrame::mvpMapPoints) and "p is observed
  *              by kf at idx" (MapPoint::mObservations).  The hooks keep it so: a bad point holds no slot, a bad key frame
  *              holds no slot.  Deviations: the window between AddMapPoint and AddObservation is not represented; a bad key
@@ -1848,6 +1856,29 @@ int orbgpu_keyframe_db_debug_global_queries(const orbgpu_keyframe_db *db, int64_
  *              (weight, id): sort(vPairs) reversed, id standing for the pointer.  An unknown or bad kf gives empty outputs;
  *              the graph is not modified.  AddConnection, mpParent and the set_covisibles / set_parent hooks stay with the
  *              caller (CovisibilityGraphT::UpdateConnections does them).
+ *   V8 keyframe_culling   LocalMapping::KeyFrameCulling (LocalMapping.cc:632-698).  kf_ids: GetVectorCovisibleKeyFrames()
+ *              of the current key frame, in that order; th_obs: thObs (3 for every sensor in this reference, :647-650).
+ *              S is the relation at the start of the call, the weight of a slot is 2 if it is STEREO and 1 otherwise,
+ *              Obs_S(p) is the weight sum of p's slots in S (MapPoint::Observations() under V2).  For k = 0 .. n-1 in order:
+ *              kf_ids[k] is SKIPPED (verdict -1, n_mps = n_redundant = 0) if it is 0 (:643), no row, a bad row, or got
+ *              verdict 1 earlier in this call; an id that was not culled and occurs again is evaluated again.  Otherwise,
+ *              over the row's slots that hold a point p still in S: a FAR slot is passed over; else n_mps++, and if
+ *              Obs_S(p) > th_obs and at least th_obs slots of S on OTHER rows hold p with octave <= own octave + 1, then
+ *              n_redundant++ (every slot counts as an observation -- V2's deviation for a point in two slots of one row --
+ *              and all slots of the candidate's own row are excluded).  The candidate is culled iff
+ *              (double)n_redundant > 0.9 * (double)n_mps (:695; never with n_mps == 0).  Not culled: verdict 0.  Culled with
+ *              not_erase[k] != 0: verdict 2 (mbToBeErased, KeyFrame.cc:497-501), S unchanged.  Otherwise verdict 1: every
+ *              slot of the row leaves S and Obs_S(p) drops by the slot's weight; every point that thereby reaches
+ *              Obs_S(p) <= 2 is bad (MapPoint.cc:130) and all its slots on every row leave S.  bad_point_ids: those points
+ *              in ascending id.  n_query_points: the distinct points in the slots of the candidates that are rows, not bad
+ *              and not id 0.  THE GRAPH IS NOT MODIFIED: S lives in per-call scratch; the caller runs
+ *              KeyFrame::SetBadFlag on every key frame with verdict 1, whose hooks (set_bad, set_slots, set_parent) bring
+ *              the graph to the state the call predicted (CovisibilityGraphT::KeyFrameCulling does).  Deviations: the
+ *              reference's early `break` at nObs >= thObs changes no count; a covisible list never holds a bad key frame,
+ *              the library skips one; mbNotErase is sampled by the caller before the call, not at each SetBadFlag.
+ *   observations   n_obs[i] = Obs(mp_ids[i]) over the rows that are not bad, n_slots[i] = the unweighted number of those
+ *              slots; an id of -1 or one held nowhere gives 0, duplicates are allowed.  What MapPointCulling
+ *              (LocalMapping.cc:195) and KeyFrame::TrackedMapPoints read.  The graph is not modified.
  * Edits (HOST arrays; every call returns synchronised; ONE host thread at a time -- CovisibilityGraphT serialises):
  *   add_keyframe    mp_ids NULL: every slot empty
  *   set_slots       batched and applied in order (later entries win); mp_id -1 clears a slot; an unknown kf id is ignored,
@@ -1859,6 +1890,12 @@ int orbgpu_keyframe_db_debug_global_queries(const orbgpu_keyframe_db *db, int64_
  *   set_parent      the parent may be unknown or -1; for a kf that is no row yet the value is kept until it is added
  *   set_covisibles  orbgpu_keyframe_db_set_covisibles's rule: a list for an id that is no row yet is kept until it is
  *                   added; a bad row ignores the call
+ *   set_keypoints   the whole attribute row (V1), once after add_keyframe: key points do not change.  Refused: an unknown
+ *                   id, n_slots different from the row's, a byte with bit 4 or 5 set, a null array with n_slots > 0.  A bad
+ *                   row ignores the call.
+ * keyframe_culling refuses null required outputs, n < 0 or above 2^16, th_obs outside [1, 255] and a negative id;
+ * observations refuses ids below -1 and more than 2^20 of them.  Candidates that hold more than 2^20 distinct points
+ * return ORBGPU_ECAPACITY (64 bytes of counters per point; a first choice, not a measured limit).
  * Refused with ORBGPU_EINVAL before any device is touched, nothing changed: an id that is present (bad rows included), a
  * negative id, idx outside the row, a map point id below -1, n_slots (or a query) above ORBGPU_COVIS_MAX_SLOTS, more than
  * 10 covisibles, more than 2^20 rows or 2^30 pool slots (first choices, not measured limits).  A local map of more than
@@ -1893,6 +1930,21 @@ int orbgpu_covis_connections(orbgpu_covis_graph *g, int64_t kf_id, int32_t th, i
 /* Tests: how many vote launches of this handle read the query from global memory (more distinct ids than the LDS staging
  * holds, or than ORBGPU_DEBUG_COVIS_LDS_IDS=<k>, read when the handle is created). */
 int orbgpu_covis_graph_debug_global_queries(const orbgpu_covis_graph *g, int64_t *n);
+#define ORBGPU_COVIS_MAX_LEVELS 16
+#define ORBGPU_COVIS_KP_STEREO 0x40
+#define ORBGPU_COVIS_KP_FAR 0x80
+typedef struct orbgpu_covis_culling_result {
+    int32_t n_culled, n_to_be_erased, n_skipped; /* verdicts 1, 2, -1 */
+    int32_t n_points_bad;                        /* full length of bad_point_ids */
+    int32_t n_query_points;                      /* distinct map points in the candidates' slots */
+} orbgpu_covis_culling_result;
+int orbgpu_covis_graph_set_keypoints(orbgpu_covis_graph *g, int64_t kf_id, int32_t n_slots, const uint8_t *kp);
+int orbgpu_covis_observations(orbgpu_covis_graph *g, int32_t n, const int64_t *mp_ids, int32_t *n_obs, int32_t *n_slots);
+/* not_erase NULL: none.  verdict, n_mps, n_redundant: n entries each.  The query of its counting launch goes through LDS or
+ * global memory as the vote's does (orbgpu_covis_graph_debug_global_queries counts both). */
+int orbgpu_covis_keyframe_culling(orbgpu_covis_graph *g, int32_t n, const int64_t *kf_ids, const uint8_t *not_erase, int32_t th_obs,
+                                  int8_t *verdict, int32_t *n_mps, int32_t *n_redundant, int32_t point_capacity,
+                                  int64_t *bad_point_ids, orbgpu_covis_culling_result *res);
 
 /* ======================================================================================
  * On-disk formats of the end-of-run artefacts: host serialisers, byte for byte.

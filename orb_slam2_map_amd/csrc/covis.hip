@@ -20,6 +20,19 @@
 //                    empties exactly the hash slots the call used.  The result does not depend on scheduling.
 // No host decision lies between the vote and the points; a query waits twice (sizes, then lists).  Every call returns
 // synchronised; the caller serialises (CovisibilityGraphT does).  Refusals are answered before any device is touched.
+//
+// LocalMapping::KeyFrameCulling (LocalMapping.cc:632-698) runs over the same pool and a second column beside it, one byte
+// per slot: the key point's octave and its STEREO / FAR flags (V1).  The query is the distinct points of the candidates'
+// slots (built from the host mirror, as orbgpu_covis_connections builds its own):
+//   k_covis_cull_count    k_covis_vote's shape: one wave per row, a lane takes a slot and binary-searches the query; a hit
+//                         adds the slot's weight to obs[q] and 1 to cnt[q][octave] (integer atomics).  With one level it is
+//                         orbgpu_covis_observations.
+//   k_covis_cull_resolve  one workgroup walks the candidates in the caller's order (V8): the row's own slots leave cnt, the
+//                         lanes evaluate the slots, the verdict goes through LDS to every lane, and the slots either come
+//                         back or stay out while obs drops and points at <= 2 die.  Every barrier is reached by the whole
+//                         workgroup.
+//   k_covis_cull_emit     the dead points in query order, which is ascending id.
+// One wait per call; the graph is not modified.
 #include "common.h"
 #include "id_table.h"
 
@@ -45,6 +58,10 @@ constexpr int CV_WAVES = CV_BLOCK / 64;
 constexpr int CV_LIST_BLOCK = 1024;
 constexpr int CV_CHUNK = 1024;  // gather positions per chunk: four steps of a 256-thread block
 constexpr int32_t CV_POS_NONE = 0x7F7F7F7F;  // (hipMemset's byte pattern) above every gather position (< 2^30)
+constexpr int CV_LEVELS = ORBGPU_COVIS_MAX_LEVELS;
+constexpr int CV_MAX_CANDIDATES = 1 << 16;      // key frames of one culling call
+constexpr int CV_MAX_QUERY_POINTS = 1 << 20;    // distinct points of their slots (64 bytes of counters each); a first choice
+static_assert(CV_LEVELS == 16 && (ORBGPU_COVIS_KP_STEREO | ORBGPU_COVIS_KP_FAR) == 0xC0, "the attribute byte of V1");
 
 struct CvRow {  // 120 bytes; the host keeps a mirror and uploads the part an edit changes
     int64_t id;
@@ -476,6 +493,201 @@ __global__ __launch_bounds__(256) void k_covis_unhash(CvPointHash h, const long 
     }
 }
 
+// header of a culling call
+enum { CU_CULLED = 0, CU_TO_BE_ERASED, CU_SKIPPED, CU_BAD, CU_WORDS };
+static_assert(CU_WORDS <= CH_WORDS, "the culling header lies in the query header's buffer");
+
+// the position of id in the sorted distinct ids q[0..nq), -1 if it is not there
+__device__ __forceinline__ int covis_find(const int64_t *q, int nq, int64_t id)
+{
+    int lo = 0, hi = nq;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (q[mid] < id)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo < nq && q[lo] == id ? lo : -1;
+}
+
+// Over every slot of every row that is not bad and holds a query point q: obs[q] += the slot's weight (2 if STEREO),
+// cnt[q * levels + (octave & (levels - 1))] += 1.  levels is 16 (culling) or 1 (orbgpu_covis_observations: the number of
+// slots).  obs and cnt start at zero; integer atomics, so the sums do not depend on the order.
+template <bool LDS>
+__global__ __launch_bounds__(CV_BLOCK) void k_covis_cull_count(int n_rows, const CvRow *__restrict__ rows, const int64_t *__restrict__ pool,
+                                                               const uint8_t *__restrict__ kp, int64_t pool_used, int nq,
+                                                               const int64_t *__restrict__ q_ids, int levels, int32_t *obs, int32_t *cnt)
+{
+    extern __shared__ int64_t s_cv[];
+    const int64_t *q = q_ids;
+    if (LDS) {  // a template constant: the barrier is under workgroup-uniform control flow
+        for (int i = threadIdx.x; i < nq; i += CV_BLOCK)
+            s_cv[i] = q_ids[i];
+        __syncthreads();
+        q = s_cv;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int row = blockIdx.x * CV_WAVES + wave; row < n_rows; row += gridDim.x * CV_WAVES) {  // wave-uniform
+        const int64_t off = rows[row].off;
+        const int len = rows[row].n_slots;
+        if (rows[row].bad || off < 0 || len < 0 || off + len > pool_used)
+            continue;
+        for (int e = lane; e < len; e += 64) {
+            const int64_t id = pool[off + e];
+            if (id < 0)
+                continue;
+            const int k = covis_find(q, nq, id);
+            if (k < 0)
+                continue;
+            const unsigned a = kp[off + e];
+            atomicAdd(obs + k, (a & ORBGPU_COVIS_KP_STEREO) ? 2 : 1);
+            atomicAdd(cnt + (size_t)k * levels + (a & (unsigned)(levels - 1)), 1);
+        }
+    }
+}
+
+struct CvCull {  // a culling call's arrays, in the handle's staging
+    int n, nq, th;
+    const int64_t *q;         // the query: sorted distinct point ids
+    const int32_t *cand_row;  // per candidate: its row, -1 for one the host knows to be skipped (id 0, no row, a bad row)
+    const int32_t *first;     // per candidate: the first position that names the same row
+    const uint8_t *not_erase;
+    int32_t *obs, *cnt;       // Obs_S(q); slots of S that hold q, per octave
+    uint8_t *dead, *culled;   // per query point; per candidate position (indexed by `first`)
+    int8_t *verdict;
+    int32_t *n_mps, *n_red;
+    int slot_cap;             // the longest candidate row
+    int32_t *slot_q;          // the current candidate's slots as query positions, -1 for none
+};
+
+// V8: the candidates in order, one workgroup.  s_row / s_verdict carry the two decisions to every lane, so that every
+// barrier below stands under workgroup-uniform control flow.
+__global__ __launch_bounds__(CV_LIST_BLOCK) void k_covis_cull_resolve(CvCull c, int n_rows, const CvRow *__restrict__ rows,
+                                                                      const int64_t *__restrict__ pool, const uint8_t *__restrict__ kp,
+                                                                      int64_t pool_used, long long *hdr)
+{
+    __shared__ int s_row, s_verdict, s_mps, s_red;
+    const int tid = threadIdx.x;
+    int n_culled = 0, n_keep = 0, n_skip = 0;  // thread 0's
+    for (int k = 0; k < c.n; k++) {
+        if (tid == 0) {
+            int r = c.cand_row[k];
+            const int f = c.first[k];
+            if (r < 0 || r >= n_rows || f < 0 || f > k || c.culled[f])
+                r = -1;
+            else if (rows[r].bad || rows[r].off < 0 || rows[r].n_slots < 0 || rows[r].n_slots > c.slot_cap ||
+                     rows[r].off + rows[r].n_slots > pool_used)
+                r = -1;
+            s_row = r;
+            s_mps = s_red = 0;
+        }
+        __syncthreads();
+        const int r = s_row;
+        if (r < 0) {  // workgroup-uniform
+            if (tid == 0) {
+                c.verdict[k] = -1;
+                c.n_mps[k] = c.n_red[k] = 0;
+                n_skip++;
+            }
+            __syncthreads();  // s_row has been read
+            continue;
+        }
+        const int64_t off = rows[r].off;
+        const int len = rows[r].n_slots;
+        // A lane looks its slots up once; in every phase below it takes the same slots, so it reads back its own stores.
+        // The row's own slots leave the counts (pKFi == pKF).
+        for (int e = tid; e < len; e += CV_LIST_BLOCK) {
+            const int64_t id = pool[off + e];
+            const int qi = id >= 0 ? covis_find(c.q, c.nq, id) : -1;
+            c.slot_q[e] = qi;
+            if (qi >= 0)
+                atomicSub(c.cnt + (size_t)qi * CV_LEVELS + (kp[off + e] & (CV_LEVELS - 1)), 1);
+        }
+        __syncthreads();
+        int mps = 0, red = 0;
+        for (int e = tid; e < len; e += CV_LIST_BLOCK) {
+            const int qi = c.slot_q[e];
+            const unsigned a = kp[off + e];
+            if (qi < 0 || c.dead[qi] || (a & ORBGPU_COVIS_KP_FAR))
+                continue;
+            mps++;
+            if (c.obs[qi] > c.th) {
+                const int top = min((int)(a & (CV_LEVELS - 1)) + 1, CV_LEVELS - 1);
+                int others = 0;
+                for (int l = 0; l <= top; l++)
+                    others += c.cnt[(size_t)qi * CV_LEVELS + l];
+                red += others >= c.th;
+            }
+        }
+        mps = wave_reduce_add(mps);
+        red = wave_reduce_add(red);
+        if ((tid & 63) == 0) {
+            atomicAdd(&s_mps, mps);  // integer sums: the same in any order
+            atomicAdd(&s_red, red);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int v = (double)s_red > 0.9 * (double)s_mps ? 1 : 0;  // LocalMapping.cc:695, in FP64 as written
+            if (v && c.not_erase[k])
+                v = 2;
+            if (v == 1) {
+                c.culled[c.first[k]] = 1;
+                n_culled++;
+            }
+            n_keep += v == 2;
+            c.verdict[k] = (int8_t)v;
+            c.n_mps[k] = s_mps;
+            c.n_red[k] = s_red;
+            s_verdict = v;
+        }
+        __syncthreads();
+        const bool gone = s_verdict == 1;  // read by every lane before the branch
+        for (int e = tid; e < len; e += CV_LIST_BLOCK) {
+            const int qi = c.slot_q[e];
+            if (qi < 0)
+                continue;
+            const unsigned a = kp[off + e];
+            if (gone)
+                atomicSub(c.obs + qi, (a & ORBGPU_COVIS_KP_STEREO) ? 2 : 1);  // the slot has left S
+            else
+                atomicAdd(c.cnt + (size_t)qi * CV_LEVELS + (a & (CV_LEVELS - 1)), 1);
+        }
+        __syncthreads();
+        if (gone)
+            for (int e = tid; e < len; e += CV_LIST_BLOCK) {
+                const int qi = c.slot_q[e];
+                if (qi >= 0 && !c.dead[qi] && c.obs[qi] <= 2)
+                    c.dead[qi] = 1;  // MapPoint.cc:130 (lanes that meet in one point write the same value)
+            }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        hdr[CU_CULLED] = n_culled;
+        hdr[CU_TO_BE_ERASED] = n_keep;
+        hdr[CU_SKIPPED] = n_skip;
+    }
+}
+
+// the dead points in query order (ascending id); at most out_cap are written, the count is full
+__global__ __launch_bounds__(CV_LIST_BLOCK) void k_covis_cull_emit(int nq, const int64_t *__restrict__ q, const uint8_t *__restrict__ dead,
+                                                                   int out_cap, int64_t *__restrict__ out, long long *hdr)
+{
+    __shared__ int s_w[CV_LIST_BLOCK / 64];
+    int run = 0;
+    for (int base = 0; base < nq; base += CV_LIST_BLOCK) {
+        const int i = base + threadIdx.x;
+        const bool d = i < nq && dead[i];
+        int total;
+        const int k = run + block_scan_excl(d, s_w, total);
+        if (d && k < out_cap)
+            out[k] = q[i];
+        run += total;
+    }
+    if (threadIdx.x == 0)
+        hdr[CU_BAD] = run;
+}
+
 constexpr int CV_ROW_COLS = 4;  // the per-row arrays of orbgpu_covis_graph
 
 } // namespace orbgpu
@@ -495,10 +707,11 @@ struct orbgpu_covis_graph {
     const IdColumn<DevBuf> row_cols[CV_ROW_COLS] = {{&d_rows, sizeof(CvRow)}, {&d_count, 4}, {&d_stamp, 4}, {&d_order, 4}};
     orbgpu_covis_graph() = default;
     orbgpu_covis_graph(const orbgpu_covis_graph &) = delete;
-    DevBuf d_pool, d_hkeys, d_hvals, d_stage, d_hdr, d_pkeys, d_ppos, d_used, d_chunks, d_points;
+    DevBuf d_pool, d_kp, d_hkeys, d_hvals, d_stage, d_hdr, d_pkeys, d_ppos, d_used, d_chunks, d_points;
     IdHash hash;  // id -> row (bad rows included); the device holds a byte-identical copy
     std::vector<CvRow> h_rows;
     std::vector<int64_t> h_pool;   // the slots, as the device holds them
+    std::vector<uint8_t> h_kp;     // the key-point attribute of every slot (V1), as the device holds it
     std::vector<int32_t> h_order;  // rows in ascending id
     std::unordered_map<int64_t, std::vector<int64_t>> covis;  // lists set for ids that are not rows yet
     std::unordered_map<int64_t, int64_t> parents;             // parents set for ids that are not rows yet
@@ -507,7 +720,7 @@ struct orbgpu_covis_graph {
     int lds_ids = CV_LDS_IDS;    // ORBGPU_DEBUG_COVIS_LDS_IDS, read at creation
     int point_log2 = 0;          // the point hash as allocated
     bool point_dirty = true;     // it may hold entries: emptied as a whole before its next use
-    int64_t global_queries = 0;  // vote launches that read the query from global memory (tests)
+    int64_t global_queries = 0;  // vote and culling-count launches that read the query from global memory (tests)
 };
 
 namespace orbgpu {
@@ -531,10 +744,14 @@ static int cv_grow_pool(orbgpu_covis_graph *g, int64_t want)
     int64_t ncap = std::max<int64_t>(g->pool_cap, 1024);
     while (ncap < want)
         ncap *= 2;
-    DevBuf np;
+    DevBuf np, nk;  // both columns or neither: nothing is swapped before both copies have arrived
     int rc = np.reserve(8 * (size_t)ncap);
+    if (rc == ORBGPU_OK)
+        rc = nk.reserve((size_t)ncap);
     if (rc == ORBGPU_OK && g->pool_used > 0) {
         hipError_t he = hipMemcpyAsync(np.p, g->d_pool.p, 8 * (size_t)g->pool_used, hipMemcpyDeviceToDevice, g->stream);
+        if (he == hipSuccess)
+            he = hipMemcpyAsync(nk.p, g->d_kp.p, (size_t)g->pool_used, hipMemcpyDeviceToDevice, g->stream);
         if (he == hipSuccess)
             he = hipStreamSynchronize(g->stream);
         if (he != hipSuccess) {
@@ -545,10 +762,13 @@ static int cv_grow_pool(orbgpu_covis_graph *g, int64_t want)
     if (rc != ORBGPU_OK) {
         (void)hipStreamSynchronize(g->stream);
         np.release();
+        nk.release();
         return rc;
     }
     std::swap(g->d_pool, np);
+    std::swap(g->d_kp, nk);
     np.release();
+    nk.release();
     g->pool_cap = ncap;
     return ORBGPU_OK;
 }
@@ -633,6 +853,21 @@ static void cv_launch_vote(orbgpu_covis_graph *g, int nq, const int64_t *q_ids, 
         g->global_queries++;
         hipLaunchKernelGGL(k_covis_vote<false>, dim3(grid), dim3(CV_BLOCK), 0, g->stream, g->rows, rows, g->d_pool.as<int64_t>(),
                            g->pool_used, nq, q_ids, q_mult, exclude_row, g->d_count.as<int32_t>());
+    }
+}
+
+// obs and cnt (levels per query point) are zero; the query goes through LDS or global memory as the vote's does
+static void cv_launch_cull_count(orbgpu_covis_graph *g, int nq, const int64_t *q_ids, int levels, int32_t *obs, int32_t *cnt)
+{
+    const int grid = std::min((g->rows + CV_WAVES - 1) / CV_WAVES, 4096);
+    const CvRow *rows = g->d_rows.as<CvRow>();
+    if (nq <= g->lds_ids)
+        hipLaunchKernelGGL(k_covis_cull_count<true>, dim3(grid), dim3(CV_BLOCK), 8 * (size_t)std::max(nq, 1), g->stream, g->rows, rows,
+                           g->d_pool.as<int64_t>(), g->d_kp.as<uint8_t>(), g->pool_used, nq, q_ids, levels, obs, cnt);
+    else {
+        g->global_queries++;
+        hipLaunchKernelGGL(k_covis_cull_count<false>, dim3(grid), dim3(CV_BLOCK), 0, g->stream, g->rows, rows, g->d_pool.as<int64_t>(),
+                           g->d_kp.as<uint8_t>(), g->pool_used, nq, q_ids, levels, obs, cnt);
     }
 }
 
@@ -755,7 +990,7 @@ static int cv_destroy(orbgpu_covis_graph *g)
         }
         for (const IdColumn<DevBuf> &c : g->row_cols)
             c.buf->release();
-        for (DevBuf *b : {&g->d_pool, &g->d_hkeys, &g->d_hvals, &g->d_stage, &g->d_hdr, &g->d_pkeys, &g->d_ppos, &g->d_used,
+        for (DevBuf *b : {&g->d_pool, &g->d_kp, &g->d_hkeys, &g->d_hvals, &g->d_stage, &g->d_hdr, &g->d_pkeys, &g->d_ppos, &g->d_used,
                           &g->d_chunks, &g->d_points})
             b->release();
     }
@@ -809,6 +1044,7 @@ int orbgpu_covis_graph_clear(orbgpu_covis_graph *g)
     g->hash.clear();
     g->h_rows.clear();
     g->h_pool.clear();
+    g->h_kp.clear();
     g->h_order.clear();
     g->covis.clear();
     g->parents.clear();
@@ -868,6 +1104,8 @@ int orbgpu_covis_graph_add_keyframe(orbgpu_covis_graph *g, int64_t id, int32_t n
     hipError_t he = hipSuccess;
     if (n_slots > 0)
         he = hipMemcpyAsync(g->d_pool.as<int64_t>() + g->pool_used, slots.data(), 8 * (size_t)n_slots, hipMemcpyHostToDevice, g->stream);
+    if (he == hipSuccess && n_slots > 0)
+        he = hipMemsetAsync(g->d_kp.as<uint8_t>() + g->pool_used, 0, (size_t)n_slots, g->stream);  // octave 0, monocular, close
     if (he == hipSuccess)
         he = hipMemcpyAsync(g->d_order.as<int32_t>() + at, tail.data(), 4 * tail.size(), hipMemcpyHostToDevice, g->stream);
     if (he == hipSuccess)
@@ -886,6 +1124,7 @@ int orbgpu_covis_graph_add_keyframe(orbgpu_covis_graph *g, int64_t id, int32_t n
     g->h_rows.push_back(row);
     g->h_order.insert(g->h_order.begin() + (ptrdiff_t)at, r);
     g->h_pool.insert(g->h_pool.end(), slots.begin(), slots.end());
+    g->h_kp.insert(g->h_kp.end(), (size_t)n_slots, (uint8_t)0);
     g->covis.erase(id);
     g->parents.erase(id);
     g->pool_used += n_slots;
@@ -1180,6 +1419,201 @@ int orbgpu_covis_connections(orbgpu_covis_graph *g, int64_t kf_id, int32_t th, i
     for (int k = 0; k < (int)pairs.size() && k < ordered_capacity; k++) {
         ordered_ids[k] = pairs[(size_t)k].second;
         ordered_weights[k] = pairs[(size_t)k].first;
+    }
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_graph_set_keypoints(orbgpu_covis_graph *g, int64_t kf_id, int32_t n_slots, const uint8_t *kp)
+{
+    ORBGPU_REQUIRE(g, "null argument");
+    const int r = g->hash.find(kf_id);
+    ORBGPU_REQUIRE(r >= 0, "key frame %lld is not in the graph", (long long)kf_id);
+    const CvRow &row = g->h_rows[(size_t)r];
+    ORBGPU_REQUIRE(n_slots == row.n_slots, "n_slots = %d, key frame %lld has %d", n_slots, (long long)kf_id, row.n_slots);
+    ORBGPU_REQUIRE(n_slots == 0 || kp, "null argument");
+    for (int i = 0; i < n_slots; i++)
+        ORBGPU_REQUIRE(!(kp[i] & 0x30), "key-point attribute 0x%02x at slot %d (bits 4-5 are reserved)", kp[i], i);
+    if (row.bad || n_slots == 0)
+        return ORBGPU_OK;  // a bad key frame holds no slot (V2)
+    int rc = cv_bind(g);
+    if (rc != ORBGPU_OK)
+        return rc;
+    hipError_t he = hipMemcpyAsync(g->d_kp.as<uint8_t>() + row.off, kp, (size_t)n_slots, hipMemcpyHostToDevice, g->stream);
+    if ((rc = cv_sync_or_fail(g, he, "setting key-point attributes")) != ORBGPU_OK) {
+        (void)hipMemcpy(g->d_kp.as<uint8_t>() + row.off, g->h_kp.data() + row.off, (size_t)n_slots, hipMemcpyHostToDevice);
+        return rc;
+    }
+    memcpy(g->h_kp.data() + row.off, kp, (size_t)n_slots);
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_observations(orbgpu_covis_graph *g, int32_t n, const int64_t *mp_ids, int32_t *n_obs, int32_t *n_slots)
+{
+    ORBGPU_REQUIRE(g && n >= 0 && n <= CV_MAX_CALL && (n == 0 || (mp_ids && n_obs && n_slots)), "bad argument");
+    for (int i = 0; i < n; i++)
+        ORBGPU_REQUIRE(mp_ids[i] >= -1, "map point id %lld (entry %d)", (long long)mp_ids[i], i);
+    std::vector<int64_t> q;
+    std::vector<int32_t> mult;
+    cv_query(n, mp_ids, q, mult);
+    const int nq = (int)q.size();
+    for (int i = 0; i < n; i++)
+        n_obs[i] = n_slots[i] = 0;
+    if (nq == 0 || g->rows == g->n_bad)
+        return ORBGPU_OK;  // nothing is held anywhere: no device needed
+    int rc = cv_bind(g);
+    if (rc != ORBGPU_OK)
+        return rc;
+    Carver c;
+    const size_t o_q = c.take(8 * (size_t)nq), o_obs = c.take(4 * (size_t)nq), o_cnt = c.take(4 * (size_t)nq);
+    if ((rc = cv_reserve_locked(g->d_stage, c.off)) != ORBGPU_OK)
+        return rc;
+    char *st = g->d_stage.as<char>();
+    std::vector<int32_t> obs((size_t)nq), cnt((size_t)nq);
+    hipError_t he = hipMemcpyAsync(st + o_q, q.data(), 8 * (size_t)nq, hipMemcpyHostToDevice, g->stream);
+    if (he == hipSuccess)
+        he = hipMemsetAsync(st + o_obs, 0, c.off - o_obs, g->stream);
+    if (he == hipSuccess) {
+        cv_launch_cull_count(g, nq, reinterpret_cast<const int64_t *>(st + o_q), 1, reinterpret_cast<int32_t *>(st + o_obs),
+                             reinterpret_cast<int32_t *>(st + o_cnt));
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(obs.data(), st + o_obs, 4 * (size_t)nq, hipMemcpyDeviceToHost, g->stream);
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(cnt.data(), st + o_cnt, 4 * (size_t)nq, hipMemcpyDeviceToHost, g->stream);
+    if ((rc = cv_sync_or_fail(g, he, "observations query")) != ORBGPU_OK)
+        return rc;
+    for (int i = 0; i < n; i++) {
+        if (mp_ids[i] < 0)
+            continue;
+        const size_t k = (size_t)(std::lower_bound(q.begin(), q.end(), mp_ids[i]) - q.begin());
+        n_obs[i] = obs[k];
+        n_slots[i] = cnt[k];
+    }
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_keyframe_culling(orbgpu_covis_graph *g, int32_t n, const int64_t *kf_ids, const uint8_t *not_erase, int32_t th_obs,
+                                  int8_t *verdict, int32_t *n_mps, int32_t *n_redundant, int32_t point_capacity,
+                                  int64_t *bad_point_ids, orbgpu_covis_culling_result *res)
+{
+    ORBGPU_REQUIRE(g && res, "null argument");
+    ORBGPU_REQUIRE(n >= 0 && n <= CV_MAX_CANDIDATES, "n = %d (at most %d)", n, CV_MAX_CANDIDATES);
+    ORBGPU_REQUIRE(n == 0 || (kf_ids && verdict && n_mps && n_redundant), "null argument");
+    ORBGPU_REQUIRE(th_obs >= 1 && th_obs <= 255, "th_obs = %d (1 to 255)", th_obs);
+    ORBGPU_REQUIRE(point_capacity >= 0 && (point_capacity == 0 || bad_point_ids), "bad output capacity");
+    for (int k = 0; k < n; k++)
+        ORBGPU_REQUIRE(kf_ids[k] >= 0, "key frame id %lld (entry %d)", (long long)kf_ids[k], k);
+    // what the host knows of a candidate: its row, unless LocalMapping.cc:643 or V8 skips it whatever came before; and the
+    // first position that names the same row, where the device records a verdict 1
+    std::vector<int32_t> cand((size_t)n, -1), first((size_t)n, 0);
+    std::unordered_map<int, int> seen;
+    std::vector<int64_t> slots;
+    int slot_cap = 1;
+    for (int k = 0; k < n; k++) {
+        const int r = kf_ids[k] == 0 ? -1 : g->hash.find(kf_ids[k]);
+        first[(size_t)k] = k;
+        if (r < 0 || g->h_rows[(size_t)r].bad)
+            continue;
+        cand[(size_t)k] = r;
+        const auto it = seen.find(r);
+        if (it != seen.end()) {
+            first[(size_t)k] = it->second;
+            continue;
+        }
+        seen.emplace(r, k);
+        const CvRow &row = g->h_rows[(size_t)r];
+        slot_cap = std::max(slot_cap, row.n_slots);
+        for (int e = 0; e < row.n_slots; e++)
+            if (g->h_pool[(size_t)(row.off + e)] >= 0)
+                slots.push_back(g->h_pool[(size_t)(row.off + e)]);
+    }
+    std::sort(slots.begin(), slots.end());
+    slots.erase(std::unique(slots.begin(), slots.end()), slots.end());
+    if (slots.size() > (size_t)CV_MAX_QUERY_POINTS) {
+        set_error("the candidates hold %zu distinct map points (at most %d)", slots.size(), CV_MAX_QUERY_POINTS);
+        return ORBGPU_ECAPACITY;
+    }
+    const int nq = (int)slots.size();
+    memset(res, 0, sizeof(*res));
+    res->n_query_points = nq;
+    if (seen.empty()) {  // every candidate is skipped: no device needed
+        for (int k = 0; k < n; k++) {
+            verdict[k] = -1;
+            n_mps[k] = n_redundant[k] = 0;
+        }
+        res->n_skipped = n;
+        return ORBGPU_OK;
+    }
+    int rc = cv_bind(g);
+    if (rc != ORBGPU_OK)
+        return rc;
+    // uploaded | zeroed | written by the kernels
+    Carver c;
+    const size_t nq1 = (size_t)std::max(nq, 1);
+    const size_t o_q = c.take(8 * nq1), o_cand = c.take(4 * (size_t)n), o_first = c.take(4 * (size_t)n), o_ne = c.take((size_t)n);
+    const size_t in_bytes = c.off;
+    const size_t o_obs = c.take(4 * nq1), o_cnt = c.take(4 * nq1 * CV_LEVELS), o_dead = c.take(nq1), o_culled = c.take((size_t)n);
+    const size_t zero_end = c.off;
+    const size_t o_verdict = c.take((size_t)n), o_mps = c.take(4 * (size_t)n), o_red = c.take(4 * (size_t)n), o_bad = c.take(8 * nq1);
+    const size_t o_slotq = c.take(4 * (size_t)slot_cap);
+    if ((rc = cv_reserve_locked(g->d_stage, c.off)) != ORBGPU_OK)
+        return rc;
+    g->stage.assign(in_bytes, 0);
+    if (nq)
+        memcpy(g->stage.data() + o_q, slots.data(), 8 * (size_t)nq);
+    memcpy(g->stage.data() + o_cand, cand.data(), 4 * (size_t)n);
+    memcpy(g->stage.data() + o_first, first.data(), 4 * (size_t)n);
+    for (int k = 0; not_erase && k < n; k++)
+        g->stage[o_ne + (size_t)k] = not_erase[k] != 0;
+    char *st = g->d_stage.as<char>();
+    long long *hdr = g->d_hdr.as<long long>();
+    long long h[CU_WORDS] = {};
+    hipError_t he = hipMemcpyAsync(st, g->stage.data(), in_bytes, hipMemcpyHostToDevice, g->stream);
+    if (he == hipSuccess)
+        he = hipMemsetAsync(st + o_obs, 0, zero_end - o_obs, g->stream);
+    if (he == hipSuccess)
+        he = hipMemsetAsync(hdr, 0, 8 * CH_WORDS, g->stream);
+    if (he == hipSuccess) {
+        const int64_t *q = reinterpret_cast<const int64_t *>(st + o_q);
+        const CvCull cu{n, nq, th_obs, q, reinterpret_cast<const int32_t *>(st + o_cand), reinterpret_cast<const int32_t *>(st + o_first),
+                        reinterpret_cast<const uint8_t *>(st + o_ne), reinterpret_cast<int32_t *>(st + o_obs),
+                        reinterpret_cast<int32_t *>(st + o_cnt), reinterpret_cast<uint8_t *>(st + o_dead),
+                        reinterpret_cast<uint8_t *>(st + o_culled), reinterpret_cast<int8_t *>(st + o_verdict),
+                        reinterpret_cast<int32_t *>(st + o_mps), reinterpret_cast<int32_t *>(st + o_red), slot_cap,
+                        reinterpret_cast<int32_t *>(st + o_slotq)};
+        cv_launch_cull_count(g, nq, q, CV_LEVELS, cu.obs, cu.cnt);
+        hipLaunchKernelGGL(k_covis_cull_resolve, dim3(1), dim3(CV_LIST_BLOCK), 0, g->stream, cu, g->rows, g->d_rows.as<CvRow>(),
+                           g->d_pool.as<int64_t>(), g->d_kp.as<uint8_t>(), g->pool_used, hdr);
+        hipLaunchKernelGGL(k_covis_cull_emit, dim3(1), dim3(CV_LIST_BLOCK), 0, g->stream, nq, q, cu.dead, nq,
+                           reinterpret_cast<int64_t *>(st + o_bad), hdr);
+        he = hipGetLastError();
+    }
+    // first wait: the header and the per-candidate outputs
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(h, hdr, 8 * CU_WORDS, hipMemcpyDeviceToHost, g->stream);
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(verdict, st + o_verdict, (size_t)n, hipMemcpyDeviceToHost, g->stream);
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(n_mps, st + o_mps, 4 * (size_t)n, hipMemcpyDeviceToHost, g->stream);
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(n_redundant, st + o_red, 4 * (size_t)n, hipMemcpyDeviceToHost, g->stream);
+    if ((rc = cv_sync_or_fail(g, he, "key frame culling")) != ORBGPU_OK)
+        return rc;
+    if (h[CU_BAD] < 0 || h[CU_BAD] > nq) {
+        set_error("covisibility graph: an index left its range on the device");
+        return ORBGPU_EHIP;
+    }
+    res->n_culled = (int32_t)h[CU_CULLED];
+    res->n_to_be_erased = (int32_t)h[CU_TO_BE_ERASED];
+    res->n_skipped = (int32_t)h[CU_SKIPPED];
+    res->n_points_bad = (int32_t)h[CU_BAD];
+    // second wait: the bad points, as long as the caller's array
+    const int nb = std::min(res->n_points_bad, point_capacity);
+    if (nb > 0) {
+        he = hipMemcpyAsync(bad_point_ids, st + o_bad, 8 * (size_t)nb, hipMemcpyDeviceToHost, g->stream);
+        if ((rc = cv_sync_or_fail(g, he, "key frame culling (bad points)")) != ORBGPU_OK)
+            return rc;
     }
     return ORBGPU_OK;
 }

@@ -303,6 +303,12 @@ class CovisLocalMapResult(C.Structure):
                 ("n_voted", C.c_int32), ("kept_previous", C.c_int32), ("n_unknown_previous", C.c_int32)]
 
 
+class CovisCullingResult(C.Structure):
+    """orbgpu_covis_culling_result"""
+    _fields_ = [("n_culled", C.c_int32), ("n_to_be_erased", C.c_int32), ("n_skipped", C.c_int32), ("n_points_bad", C.c_int32),
+                ("n_query_points", C.c_int32)]
+
+
 ABI_SYMBOLS = [
     "orbgpu_last_error_string", "orbgpu_abi_version", "orbgpu_device_count", "orbgpu_measure_copy_bandwidth",
     "orbgpu_set_trig_mode", "orbgpu_get_trig_mode", "orbgpu_trig_table_info", "orbgpu_trig_host_eval", "orbgpu_trig_eval",
@@ -349,6 +355,7 @@ ABI_SYMBOLS = [
     "orbgpu_covis_graph_add_keyframe", "orbgpu_covis_graph_set_slots", "orbgpu_covis_graph_set_bad",
     "orbgpu_covis_graph_set_parent", "orbgpu_covis_graph_set_covisibles", "orbgpu_covis_local_map",
     "orbgpu_covis_connections", "orbgpu_covis_graph_debug_global_queries",
+    "orbgpu_covis_graph_set_keypoints", "orbgpu_covis_observations", "orbgpu_covis_keyframe_culling",
     "orbgpu_vocabulary_create", "orbgpu_vocabulary_destroy", "orbgpu_vocabulary_size", "orbgpu_bow_transform",
     "orbgpu_bow_transform_batch_device", "orbgpu_search_by_bow", "orbgpu_search_by_bow_batch_device",
     "orbgpu_search_by_bow_keyframes", "orbgpu_search_for_triangulation", "orbgpu_search_for_initialization", "orbgpu_fuse", "orbgpu_fuse_sim3",
@@ -471,6 +478,9 @@ def lib():
         "orbgpu_covis_local_map": [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp],
         "orbgpu_covis_connections": [vp, C.c_int64, i32, i32, vp, vp, vp, i32, vp, vp, vp],
         "orbgpu_covis_graph_debug_global_queries": [vp, vp],
+        "orbgpu_covis_graph_set_keypoints": [vp, C.c_int64, i32, vp],
+        "orbgpu_covis_observations": [vp, i32, vp, vp, vp],
+        "orbgpu_covis_keyframe_culling": [vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp],
     }
     for name, args in sigs.items():
         fn = getattr(L, name, None)
@@ -2329,7 +2339,7 @@ class KeyFrameDatabase:
 
 class CovisibilityGraph:
     """Device-resident observation graph keyed by KeyFrame::mnId (orbgpu_covis_*): the relation between key frames and map
-    points, the local map of Tracking::UpdateLocalMap and the counter of KeyFrame::UpdateConnections (conventions V1-V7 of
+    points, the local map of Tracking::UpdateLocalMap and the counter of KeyFrame::UpdateConnections and LocalMapping::KeyFrameCulling (conventions V1-V8 of
     include/orbgpu.h).  All ids are int64; the device is bound by the first call that needs it."""
     MAX_SLOTS = 65536
     MAX_COVISIBLES = 10
@@ -2427,6 +2437,48 @@ class CovisibilityGraph:
         n = C.c_int64()
         check(self.L.orbgpu_covis_graph_debug_global_queries(self.h, C.byref(n)))
         return n.value
+
+    MAX_LEVELS = 16
+    KP_STEREO = 0x40
+    KP_FAR = 0x80
+
+    def set_keypoints(self, kf_id, kp):
+        """the attribute byte of every slot of a key frame (V1): octave | KP_STEREO | KP_FAR"""
+        kp = np.ascontiguousarray([] if kp is None else kp, np.uint8).reshape(-1)
+        check(self.L.orbgpu_covis_graph_set_keypoints(self.h, int(kf_id), len(kp), _p(kp)))
+
+    def observations(self, mp_ids):
+        """(n_obs, n_slots) per id: the weighted MapPoint::Observations() and the number of slots that hold the point"""
+        ids = self._ids(mp_ids)
+        n_obs, n_slots = np.zeros(max(len(ids), 1), np.int32), np.zeros(max(len(ids), 1), np.int32)
+        check(self.L.orbgpu_covis_observations(self.h, len(ids), _p(ids), _p(n_obs), _p(n_slots)))
+        return n_obs[:len(ids)].copy(), n_slots[:len(ids)].copy()
+
+    def keyframe_culling(self, kf_ids, not_erase=None, th_obs=3, point_capacity=None):
+        """LocalMapping::KeyFrameCulling (V8): dict of verdict, n_mps, n_redundant (per candidate), bad_point_ids (as long
+        as point_capacity allows) and the fields of orbgpu_covis_culling_result.  The graph is not modified."""
+        ids = self._ids(kf_ids)
+        n = len(ids)
+        ne = None
+        if not_erase is not None:
+            ne = np.ascontiguousarray(not_erase, np.uint8).reshape(-1)
+            if len(ne) != n:
+                raise ValueError("not_erase holds one flag per candidate")
+        verdict, n_mps, n_red = np.zeros(max(n, 1), np.int8), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        res = CovisCullingResult()
+
+        def call(cap, out):
+            check(self.L.orbgpu_covis_keyframe_culling(self.h, n, _p(ids), _p(ne), int(th_obs), _p(verdict), _p(n_mps), _p(n_red),
+                                                       int(cap), _p(out), C.byref(res)))
+        if point_capacity is None:  # the full length first
+            call(0, None)
+            point_capacity = res.n_points_bad
+        bad = np.zeros(max(int(point_capacity), 1), np.int64)
+        call(point_capacity, bad)
+        out = {name: getattr(res, name) for name, _ in CovisCullingResult._fields_}
+        out.update(verdict=verdict[:n].copy(), n_mps=n_mps[:n].copy(), n_redundant=n_red[:n].copy(),
+                   bad_point_ids=bad[:min(res.n_points_bad, int(point_capacity))].copy())
+        return out
 
 
 def search_by_bow(desc_kf, angle_kf, valid_kf, node_kf, desc_f, angle_f, node_f, th_low=TH_LOW, nnratio=0.7,

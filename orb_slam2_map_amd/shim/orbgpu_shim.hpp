@@ -2454,9 +2454,11 @@ template <typename KeyFrameT> class KeyFrameDatabaseT {
 
 // --------------------------------------------------------------------------------------------
 // Observation graph (orbgpu_covis_*): Tracking::UpdateLocalMap and the counting half of KeyFrame::UpdateConnections over
-// the device-resident relation between key frames and map points (include/orbgpu.h, conventions V1-V7).
+// the device-resident relation between key frames and map points (include/orbgpu.h, conventions V1-V8), and
+// LocalMapping::KeyFrameCulling over it.
 // KeyFrameT needs mnId, N, GetMapPointMatches(), GetMapPoint(idx), AddConnection(KeyFrameT *, int), isBad() and
-// mnTrackReferenceForFrame; MapPointT needs mnId, isBad() and mnTrackReferenceForFrame; the frame passed to UpdateLocalMap
+// mnTrackReferenceForFrame -- and, for SetKeyPoints and KeyFrameCulling only, mvKeysUn, mvuRight, mvDepth, mThDepth,
+// GetVectorCovisibleKeyFrames() and SetBadFlag(); MapPointT needs mnId, isBad() and mnTrackReferenceForFrame; the frame passed to UpdateLocalMap
 // needs N, mnId, mvpMapPoints and mpReferenceKF.  The class keeps id -> pointer maps of the key frames it was given and of
 // the map points its hooks have seen (ORB-SLAM2 never deletes either), so that the lists hold the caller's pointers.
 // It serialises its calls with a mutex of its own, as MapPointTableT does, and never calls into a key frame or a map
@@ -2652,6 +2654,74 @@ template <typename KeyFrameT, typename MapPointT> class CovisibilityGraphT {
         if (parent)
             SetParent(pKF, parent);
         return true;
+    }
+
+    // host only: V1's attribute byte of every key point.  KeyFrameT needs mvKeysUn (elements with .octave), mvuRight,
+    // mvDepth and mThDepth; bMonocular is LocalMapping's mbMonocular (LocalMapping.cc:660-664).
+    static std::vector<uint8_t> KeyPointBytes(const KeyFrameT &kf, bool bMonocular)
+    {
+        std::vector<uint8_t> kp(kf.mvKeysUn.size());
+        for (size_t i = 0; i < kp.size(); i++) {
+            const int octave = std::min(std::max((int)kf.mvKeysUn[i].octave, 0), ORBGPU_COVIS_MAX_LEVELS - 1);
+            const bool stereo = kf.mvuRight[i] >= 0;
+            const bool far_point = !bMonocular && (kf.mvDepth[i] > kf.mThDepth || kf.mvDepth[i] < 0);
+            kp[i] = (uint8_t)(octave | (stereo ? ORBGPU_COVIS_KP_STEREO : 0) | (far_point ? ORBGPU_COVIS_KP_FAR : 0));
+        }
+        return kp;
+    }
+    // hook: after AddKeyFrame(pKF), once -- key points do not change (reads const members only: no lock of the key frame)
+    void SetKeyPoints(KeyFrameT *pKF, bool bMonocular)
+    {
+        const std::vector<uint8_t> kp = KeyPointBytes(*pKF, bMonocular);
+        std::lock_guard<std::mutex> g(mu_);
+        check(orbgpu_covis_graph_set_keypoints(h_, (int64_t)pKF->mnId, (int32_t)kp.size(), kp.data()), "CovisibilityGraph::SetKeyPoints");
+    }
+    // MapPoint::Observations() of every point of pts (0 for a null or bad one), read from the graph: what
+    // LocalMapping::MapPointCulling (LocalMapping.cc:195) and KeyFrame::TrackedMapPoints compare with their thresholds
+    std::vector<int> Observations(const std::vector<MapPointT *> &pts)
+    {
+        std::vector<int64_t> ids(pts.size(), -1);
+        for (size_t i = 0; i < pts.size(); i++)
+            if (pts[i] && !pts[i]->isBad())
+                ids[i] = (int64_t)pts[i]->mnId;
+        std::vector<int32_t> n_obs(pts.size()), n_slots(pts.size());
+        std::lock_guard<std::mutex> g(mu_);
+        check(orbgpu_covis_observations(h_, (int32_t)ids.size(), ids.data(), n_obs.data(), n_slots.data()), "CovisibilityGraph::Observations");
+        return std::vector<int>(n_obs.begin(), n_obs.end());
+    }
+    // LocalMapping::KeyFrameCulling (LocalMapping.cc:632-698, V8) over pCurrentKF->GetVectorCovisibleKeyFrames();
+    // not_erase(pKF) reads the key frame's mbNotErase (under its
+    // mMutexConnections, outside this class's mutex).  The library decides; SetBadFlag() then runs on every key frame with
+    // verdict 1, in order, outside the mutex -- its hooks (SetKeyFrameBad, SyncObservations, SetParent) bring the graph to
+    // the state the call predicted; a key frame with verdict 2 gets SetBadFlag() too, which only sets mbToBeErased
+    // (KeyFrame.cc:497-501).  Returns the culled key frames.
+    template <typename NotErase> std::vector<KeyFrameT *> KeyFrameCulling(KeyFrameT *pCurrentKF, NotErase not_erase, int thObs = 3)
+    {
+        const std::vector<KeyFrameT *> vpLocalKeyFrames = pCurrentKF->GetVectorCovisibleKeyFrames();
+        const size_t n = vpLocalKeyFrames.size();
+        std::vector<int64_t> ids(n);
+        std::vector<uint8_t> keep(n);
+        for (size_t i = 0; i < n; i++) {
+            ids[i] = (int64_t)vpLocalKeyFrames[i]->mnId;
+            keep[i] = not_erase(vpLocalKeyFrames[i]) ? 1 : 0;
+        }
+        std::vector<int8_t> verdict(n);
+        std::vector<int32_t> n_mps(n), n_red(n);
+        orbgpu_covis_culling_result res;
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            check(orbgpu_covis_keyframe_culling(h_, (int32_t)n, ids.data(), keep.data(), thObs, verdict.data(), n_mps.data(), n_red.data(), 0,
+                                                nullptr, &res),
+                  "CovisibilityGraph::KeyFrameCulling");
+        }
+        std::vector<KeyFrameT *> culled;
+        for (size_t i = 0; i < n; i++)
+            if (verdict[i] == 1 || verdict[i] == 2) {
+                vpLocalKeyFrames[i]->SetBadFlag();
+                if (verdict[i] == 1)
+                    culled.push_back(vpLocalKeyFrames[i]);
+            }
+        return culled;
     }
 
     // host only: a batch of slot edits as the ABI's three arrays
