@@ -565,7 +565,8 @@ __device__ __forceinline__ pk16 pkmax(pk16 a, pk16 b) { return __builtin_element
 //   E[j]  = ext'(v[j-1], v[j+8])                                 (8 ops)
 //   T[j]  = ext3(M4[j], M4[j+4], E[j])                           (8 ops)
 // and the reduction over the 8 pairs 4 more: 36 packed ops per polarity (40 with one 3-input window per arc, 59
-// with the two-input van Herk prefix/suffix scheme before that, 79 at the start).
+// with the two-input van Herk prefix/suffix scheme before that, 79 at the start).  Only one of the
+// two polarities is evaluated for a pixel (above fast_score_pk).
 typedef _Float16 pkh __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ pkh as_h(pk16 v) { return __builtin_bit_cast(pkh, v); }
 __device__ __forceinline__ pk16 h_as_pk(pkh v) { return __builtin_bit_cast(pk16, v); }
@@ -578,40 +579,52 @@ __device__ __forceinline__ pkh hmin3(pkh a, pkh b, pkh c)
     return __builtin_elementwise_minimum(__builtin_elementwise_minimum(a, b), c);
 }
 
+// ONE network per pixel pair, its polarity chosen up front (fast_polarity.h has the scalar form of both scores and
+// tests/test_fast_polarity.py compares them).  Two arcs of 9 on a ring of 16 always intersect, so a pixel cannot
+// have an arc that is entirely above c and another that is entirely below c: at most one of B - c and c - A is
+// positive.  The pairs that decide which one are pairs the bright network already forms.  Let
+//   Eraw[i] = max(v[2i], v[(2i+9) & 15]), i = 0..7,   H = min_i Eraw[i].
+//   - Every 9-arc holds at least one element of each such pair: the 7 pixels outside the arc cannot hold two ring
+//     positions that are 9 apart.  So a bright arc implies H > c.
+//   - Every 9-arc holds both elements of one such pair: arc start a contains the pair m in {a+7, a+8}, and one of
+//     those is even.  So a dark arc implies H < c.
+// Hence the score is max(B - c, 0) if H > c and max(c - A, 0) otherwise (at H == c it is 0 either way, which is why the
+// mask below may test H < c: one subtraction and one shift).  In the second case complementing the bytes
+// (e = v ^ 0xFF, c' = c ^ 0xFF) turns it into the first: max over arcs of min(e) - c' = c - A.  The complemented
+// values stay in 0..255, so the f16 bit-pattern ordering above still holds.  The polarity is a per-half mask, never
+// control flow.  12 + 2 + 17 + 36 + 1 = 68 operations per pixel pair, 48 of them half-rate extrema, against 75 (72).
 __device__ __forceinline__ pk16 fast_score_pk(pk16 c, const pk16 p[16])
 {
-    pkh v[16], m2[8], m4[8], t[8];
+    pkh v[16], e[16], m2[8], m4[8], t[8];
 #pragma unroll
     for (int k = 0; k < 16; k++)
         v[k] = as_h(p[k]);
-    // ---- dark arcs: A = min over windows of the window maximum (index i stands for j = 2 i + 1)
+    // ---- selector: H = min over the 8 pairs of the pair maximum; mask = 0x00FF in a half with H < c (dark), else 0
 #pragma unroll
     for (int i = 0; i < 8; i++)
-        m2[i] = __builtin_elementwise_maximum(v[2 * i + 1], v[(2 * i + 2) & 15]);
+        t[i] = __builtin_elementwise_maximum(v[2 * i], v[(2 * i + 9) & 15]);
+    const pkh H = __builtin_elementwise_minimum(hmin3(hmin3(t[0], t[1], t[2]), hmin3(t[3], t[4], t[5]), t[6]), t[7]);
+    typedef unsigned short pku16 __attribute__((ext_vector_type(2)));
+    const pku16 mk = __builtin_bit_cast(pku16, (pk16)(h_as_pk(H) - c)) >> (pku16)8;  // H - c in -255..-1: high byte 0xFF
+    const uint32_t mask = __builtin_bit_cast(uint32_t, mk);
+    // ---- complement where dark, then bright arcs only: B = max over windows of the window minimum (index i stands
+    //      for j = 2 i + 1)
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+        e[k] = as_h(as_pk(as_u32(p[k]) ^ mask));
 #pragma unroll
     for (int i = 0; i < 8; i++)
-        m4[i] = __builtin_elementwise_maximum(m2[i], m2[(i + 1) & 7]);
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-        t[i] = hmax3(m4[i], m4[(i + 2) & 7], __builtin_elementwise_minimum(v[2 * i], v[(2 * i + 9) & 15]));
-    const pkh A = __builtin_elementwise_minimum(hmin3(hmin3(t[0], t[1], t[2]), hmin3(t[3], t[4], t[5]), t[6]), t[7]);
-    // ---- bright arcs: B = max over windows of the window minimum
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-        m2[i] = __builtin_elementwise_minimum(v[2 * i + 1], v[(2 * i + 2) & 15]);
+        m2[i] = __builtin_elementwise_minimum(e[2 * i + 1], e[(2 * i + 2) & 15]);
 #pragma unroll
     for (int i = 0; i < 8; i++)
         m4[i] = __builtin_elementwise_minimum(m2[i], m2[(i + 1) & 7]);
 #pragma unroll
     for (int i = 0; i < 8; i++)
-        t[i] = hmin3(m4[i], m4[(i + 2) & 7], __builtin_elementwise_maximum(v[2 * i], v[(2 * i + 9) & 15]));
+        t[i] = hmin3(m4[i], m4[(i + 2) & 7], __builtin_elementwise_maximum(e[2 * i], e[(2 * i + 9) & 15]));
     const pkh B = __builtin_elementwise_maximum(hmax3(hmax3(t[0], t[1], t[2]), hmax3(t[3], t[4], t[5]), t[6]), t[7]);
-    // max(c - A, B - c, 0) with saturating unsigned subtractions (v_pk_sub_u16 clamp): 3 operations instead of 4
-    typedef unsigned short pku16 __attribute__((ext_vector_type(2)));
-    const pku16 cu = __builtin_bit_cast(pku16, c);
-    const pku16 dk = __builtin_elementwise_sub_sat(cu, __builtin_bit_cast(pku16, A));
-    const pku16 br = __builtin_elementwise_sub_sat(__builtin_bit_cast(pku16, B), cu);
-    return __builtin_bit_cast(pk16, __builtin_elementwise_max(dk, br));  // values are in [0,255]
+    // max(B - c', 0) with a saturating unsigned subtraction (v_pk_sub_u16 clamp); values are in [0,255]
+    const pku16 cu = __builtin_bit_cast(pku16, as_u32(c) ^ mask);
+    return __builtin_bit_cast(pk16, __builtin_elementwise_sub_sat(__builtin_bit_cast(pku16, B), cu));
 }
 
 // v_perm selectors that zero-extend bytes (o, o+2) resp. (o+1, o+3) of the 8-byte pair {lo,hi}
@@ -674,7 +687,7 @@ __device__ __forceinline__ pk16 fast_score_half(const RowU &r0, const RowU &r1, 
 //   bright score <= max over adjacent pairs of min(p_a, p_b) - c,   dark score <= c - min over adjacent pairs of max(p_a, p_b).
 // Returns the sign bits of the lanes' two pixels that MAY exceed the threshold (0 = neither can be a corner at t, whose
 // score may then be written as 0 without changing any output: a non-corner's score is only ever compared as "<= t").
-// 18 packed operations against the 72 of the two score networks of a pixel pair.
+// 18 packed operations against the 68 of the selector and the score network of a pixel pair.
 template <int ODD>
 __device__ __forceinline__ uint32_t fast_maybe_half(const RowU &r0, const RowU &r3, const RowU &r6, pkh tpk)
 {
@@ -723,7 +736,8 @@ struct StripGeom {  // strips of all levels, flattened (k_blur)
 // Measured (B = 256, 640x480): 375 us against 324 + 158 us for the score-map / per-cell pair it replaces, and
 // 1.8 MB per frame less HBM traffic (143 VGPRs, three waves per SIMD, every window row unpacked once; 390 us with raw
 // rows in 128 VGPRs and 30 v_perm_b32 per step instead of 8); 338 us with the paired-window score network below, which
-// also fits four waves per SIMD (121 VGPRs).
+// also fits four waves per SIMD (121 VGPRs).  With ONE score network per pixel pair, its polarity chosen by the selector
+// of fast_score_pk (124 VGPRs, still four waves): 0.621 -> 0.574 ms per 512 frames.
 // ---------------------------------------------------------------------------------------------
 constexpr int FD_OWN = 62;    // columns a wave owns (lanes 1..62)
 constexpr int FD_QCAP = 512;  // row records a wave can queue before it falls back to emitting them directly
