@@ -727,8 +727,8 @@ struct StripGeom {  // strips of all levels, flattened (k_blur)
 // is one NMS for both thresholds: a survivor at the lower threshold with s > t_hi is also a survivor at t_hi (a
 // neighbour with s_n <= t_hi cannot beat it), so cv::FAST(iniThFAST) of a cell is the subset of its survivors with
 // s > iniThFAST and the fallback to minThFAST (ORBextractor.cc:809-816) is a per-cell choice k_quadtree makes from two
-// counts.  A row with survivors is queued in LDS as one record (4 score bytes, 4 survivor flags, row, lane) -- 8
-// instructions in the scoring loop -- and the wave turns its records into keys when its band is done: per-wave
+// counts.  A row with survivors is queued in LDS as one record (4 score bytes; bit 7 of byte p: pixel p survives, bits
+// 0-6 the row, bits 8-13 the lane) -- 7 instructions in the scoring loop -- and the wave turns its records into keys when its band is done: per-wave
 // per-cell counts in LDS, one global atomic per (wave, cell) on the cell's counter (low half = survivors above the
 // lower threshold, high half = those above iniThFAST) to reserve slots, positions handed out from LDS.  The keys of
 // a cell land in no particular order: nothing downstream depends on it (k_quadtree's "first maximum" rule rebuilds
@@ -769,9 +769,9 @@ struct DetectLane {  // what the key emission needs to know about the lane that 
 template <typename F>
 __device__ __forceinline__ void detect_record(uint32_t sc4, uint32_t rec, const DetectLane &dl, F &&fn)
 {
-    uint32_t m = rec & 0x01010101u;
+    uint32_t m = rec & 0x80808080u;
     while (m) {
-        const int b = __ffs((int)m) - 1;  // 8 p
+        const int b = __ffs((int)m) - 8;  // 8 p
         m &= m - 1u;
         fn(b >> 3, (int)((sc4 >> b) & 255u), dl.cell_base + (int)((dl.cellj >> b) & 255u));
     }
@@ -818,17 +818,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // (fetch_max; a lane without rows reads the first rows of the plane) -- and its scores are masked to zero, which is what
     // "rows outside the band count as 0" asks for anyway.  Uniform control flow costs no copies at branch joins and lets
     // the record queue count in a scalar register.
-    int wrows = rows;
+    // wmin: the shortest band among the lanes that have rows.  Up to there no lane with rows needs its band mask or the
+    // clamp of its row fetch, so the steps below it run neither (a wave whose lanes share one band height -- the common
+    // one -- meets them in its last two steps only).
+    int wrows = rows, wmin = rows > 0 ? rows : 0x7fff;
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
+    for (int off = 32; off > 0; off >>= 1) {
         wrows = max(wrows, __shfl_xor(wrows, off, 64));
+        wmin = min(wmin, __shfl_xor(wmin, off, 64));
+    }
     wrows = __builtin_amdgcn_readfirstlane(wrows);
+    wmin = __builtin_amdgcn_readfirstlane(wmin);
     const int fetch_max = rows + 5;  // the last input row the lane's band needs
     const uint8_t *fsrc = wave_dir0 ? s0.p + (size_t)f * s0.frame_stride : pyr + (size_t)f * frame_pyr;
     const int lpitch = dir0 ? (int)s0.pitch : g.pitch;
-    const uint32_t src0 = rows == 0 ? 0u
-                          : dir0    ? (uint32_t)(y0 - 3) * (uint32_t)lpitch + (uint32_t)(xs - 4)
-                                    : (uint32_t)g.plane_off + (uint32_t)(y0 + EDGE - 3) * (uint32_t)lpitch + (uint32_t)(xs + EDGE - 4);
+    // The row fetch walks a 32-bit offset from the wave's plane: one pitch per requested row up to fetch_max, where it
+    // stays.  A lane without rows never moves (step 0): it reads the first 12 bytes of the plane every time, so the seven
+    // rows of its window are equal.  Ring positions 0 and 8 sit in the centre's column, every arc of 9 holds one of
+    // them, and the score of such a window is therefore exactly 0 without a mask -- as is its compass bound.
+    uint32_t foff = rows == 0 ? 0u
+                    : dir0    ? (uint32_t)(y0 - 3) * (uint32_t)lpitch + (uint32_t)(xs - 4)
+                              : (uint32_t)g.plane_off + (uint32_t)(y0 + EDGE - 3) * (uint32_t)lpitch + (uint32_t)(xs + EDGE - 4);
+    const uint32_t fstep = rows == 0 ? 0u : (uint32_t)lpitch;
     uint32_t *fslots = slots + (size_t)f * frame_slots;
     int *fcnt = cell_cnt + (size_t)f * (ncells_total + ORBGPU_MAX_LEVELS);  // per-cell counters ...
     int *lcnt = fcnt + ncells_total;                                         // ... then the stored keys of every level
@@ -854,7 +865,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const bool own = lane >= 1 && lane <= FD_OWN;
     const uint32_t vE = own ? ((flag(0) ? 0x8000u : 0u) | (flag(2) ? 0x80000000u : 0u)) : 0u;
     const uint32_t vO = own ? ((flag(1) ? 0x8000u : 0u) | (flag(3) ? 0x80000000u : 0u)) : 0u;
-    const uint32_t lane_tag = (uint32_t)lane << 9;
+    const uint32_t lane_tag = (uint32_t)lane << 8;
     const uint32_t tl = (uint32_t)max(t_lo, 1);
     const pkh tpk = __builtin_bit_cast(pkh, tl | (tl << 16));
 
@@ -862,30 +873,42 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // (H = max(left, right, t)); S of row k-1 (packed pairs)
     uint32_t TpE = 0u, TpO = 0u, TcE = 0u, TcO = 0u, HcE = 0u, HcO = 0u, ScE = 0u, ScO = 0u;
     int qn = 0;  // records the wave has queued: wave-uniform, the row loop's control flow is
+    uint2 *const wq = s_q[__builtin_amdgcn_readfirstlane(wave)];
     auto finish_row = [&](uint32_t TnE, uint32_t TnO, int row) {
         const pkh nbE = hmax3(__builtin_bit_cast(pkh, HcE), __builtin_bit_cast(pkh, TpE), __builtin_bit_cast(pkh, TnE));
         const pkh nbO = hmax3(__builtin_bit_cast(pkh, HcO), __builtin_bit_cast(pkh, TpO), __builtin_bit_cast(pkh, TnO));
         // x > y  <=>  sign(y - x) for values in [0,255]: survivor <=> s > max(every neighbour, t)
         const uint32_t sE = as_u32(h_as_pk(nbE) - as_pk(ScE)) & vE;
         const uint32_t sO = as_u32(h_as_pk(nbO) - as_pk(ScO)) & vO;
+        // sE / sO hold nothing but the two sign bits, so one v_perm_b32 of their odd bytes is the record's flag bytes in
+        // pixel order (bit 7 of byte p: pixel p survives), and it is also what the ballot tests
+        const uint32_t sg = __builtin_amdgcn_perm(sO, sE, 0x07030501u);
         // a lane's slot in the wave's queue: the fill count + the survivor lanes below it (the compare that feeds the branch
         // is the ballot; until round 4 an LDS atomic with return that nearly every row of this stream waited for)
-        const unsigned long long srv = __ballot((sE | sO) != 0u);
-        if (sE | sO) {
-            const uint32_t sg = (sE >> 15) | (sO >> 7);  // flag bytes in pixel order: px0 bit 0, px1 bit 8, px2 bit 16, px3 bit 24
+        const unsigned long long srv = __ballot(sg != 0u);
+        const int qnext = qn + (int)__popcll(srv);
+        if (sg) {
             const uint32_t sc4 = __builtin_amdgcn_perm(ScO, ScE, 0x06020400u);
-            const uint32_t rec = sg | ((uint32_t)row << 1) | lane_tag;
-            const int slot = qn + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(srv >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)srv, 0u));
-            if (slot < qcap)
-                s_q[wave][slot] = make_uint2(sc4, rec);
-            else
-                detect_record(sc4, rec, s_lane[wave][lane], [&](int p, int sc, int cell) {  // queue full: two atomics per key
-                    const DetectLane &dl = s_lane[wave][lane];
-                    atomicAdd(&fcnt[cell], 1 + (sc > t_ini ? 65536 : 0));
-                    fslots[geom[level].slot_off + atomicAdd(&lcnt[level], 1)] = pack_key(dl.xrel + p, dl.yrel + row, sc - 1);
-                });
+            const uint32_t rec = sg | (uint32_t)row | lane_tag;
+            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(srv >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)srv, 0u));
+            uint2 *qrow = wq + qn;  // (scalar: the wave's queue and its fill count)
+            // whether the whole row still fits is the wave's question: the hot path compares nothing per lane
+            if (__builtin_expect(qnext <= qcap, 1))
+                qrow[below] = make_uint2(sc4, rec);
+            else {
+                asm volatile("; queue full" ::: "memory");  // (keeps this arm a branch: merged with the one above, its compare runs on every row)
+                const uint32_t slot = (uint32_t)qn + below;
+                if (slot < (uint32_t)qcap)
+                    wq[slot] = make_uint2(sc4, rec);
+                else
+                    detect_record(sc4, rec, s_lane[wave][lane], [&](int p, int sc, int cell) {  // queue full: two atomics per key
+                        const DetectLane &dl = s_lane[wave][lane];
+                        atomicAdd(&fcnt[cell], 1 + (sc > t_ini ? 65536 : 0));
+                        fslots[geom[level].slot_off + atomicAdd(&lcnt[level], 1)] = pack_key(dl.xrel + p, dl.yrel + row, sc - 1);
+                    });
+            }
         }
-        qn += (int)__popcll(srv);
+        qn = qnext;
     };
     auto nms_row = [&](uint32_t se, uint32_t so, int k) {
         // wave-wide lane shifts (DPP wave_shr:1 / wave_shl:1): an inactive or missing source lane yields 0
@@ -909,40 +932,76 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     };
 
     RowU r0, r1, r2, r3, r4, r5, r6;
-#define FD_FETCH(row)                                                                                        \
+    // (an empty statement the compiler may not move: it keeps the tail arms behind their scalar branch instead of turning
+    // them into per-lane selects that every step would run)
+#define FD_TAIL asm volatile("; band tail" ::: "memory");
+    // the row at the running offset; `more`: the lane may request the row after it (always false for a lane without rows)
+#define FD_FETCH(more)                                                                                       \
     {                                                                                                        \
-        const uint32_t *qq = reinterpret_cast<const uint32_t *>(fsrc + (src0 + rowoff(min((int)(row), fetch_max), lpitch))); \
+        const uint32_t *qq = reinterpret_cast<const uint32_t *>(fsrc + foff);                                \
         nx.d[0] = qq[0];                                                                                     \
         nx.d[1] = qq[1];                                                                                     \
         nx.d[2] = qq[2];                                                                                     \
+        foff += (more) ? fstep : 0u;                                                                         \
+    }
+    // ... in a row step: the offset always advances, and the tail arm takes the step back first where the lane may not
+    // request another row (an update in place: no copy at the join)
+#define FD_FETCH_STEP(k, tail)                                                                               \
+    {                                                                                                        \
+        const uint32_t *qq = reinterpret_cast<const uint32_t *>(fsrc + foff);                                \
+        nx.d[0] = qq[0];                                                                                     \
+        nx.d[1] = qq[1];                                                                                     \
+        nx.d[2] = qq[2];                                                                                     \
+        if (__builtin_expect(tail, 0)) {                                                                     \
+            FD_TAIL                                                                                          \
+            foff -= (k) + 2 < rows ? 0u : fstep;                                                             \
+        }                                                                                                    \
+        foff += fstep;                                                                                       \
     }
 #define FD_LOAD(R, row)                                                                                      \
     {                                                                                                        \
-        FD_FETCH(row)                                                                                        \
+        FD_FETCH((row) < fetch_max)                                                                          \
         unpack_row(nx, R);                                                                                   \
     }
+    // One row step; the caller leaves the loop after the wave's last row, so the NMS state is renamed from step to step
+    // instead of being copied at a join.  `tail` (wave-uniform): some lane with rows is within two rows of its band's
+    // end -- only then the fetch of row k + 7 is clamped per lane (it advances while k + 7 < fetch_max) and the scores
+    // of the lanes past their band are masked.
 #define FD_STEP(A, B, C, D, E, F, G, k)                                                                      \
-    if ((k) < wrows) {                                                                                       \
+    {                                                                                                        \
+        const bool tail = (k) + 2 >= wmin;                                                                   \
         unpack_row(nx, G);                                                                                   \
-        FD_FETCH((k) + 7)                                                                                    \
-        const uint32_t lm = (uint32_t)(((k) - rows) >> 31);  /* all ones while the lane's own band lasts */   \
-        pk16 se = {0, 0}, so = {0, 0};                                                                       \
+        FD_FETCH_STEP(k, tail)                                                                               \
+        uint32_t se = 0u, so = 0u;                                                                           \
         bool runE = true, runO = true;                                                                       \
         if (EARLY) {                                                                                         \
             if (hold == 0) {                                                                                 \
-                runE = __builtin_amdgcn_ballot_w64((fast_maybe_half<0>(A, D, G, tpk) & lm) != 0u) != 0ull;   \
-                runO = __builtin_amdgcn_ballot_w64((fast_maybe_half<1>(A, D, G, tpk) & lm) != 0u) != 0ull;   \
+                uint32_t mE = fast_maybe_half<0>(A, D, G, tpk), mO = fast_maybe_half<1>(A, D, G, tpk);       \
+                if (__builtin_expect(tail, 0)) {                                                             \
+                    FD_TAIL                                                                                  \
+                    const uint32_t lm = (uint32_t)(((k) - rows) >> 31);                                      \
+                    mE &= lm;                                                                                \
+                    mO &= lm;                                                                                \
+                }                                                                                            \
+                runE = __builtin_amdgcn_ballot_w64(mE != 0u) != 0ull;                                        \
+                runO = __builtin_amdgcn_ballot_w64(mO != 0u) != 0ull;                                        \
                 hold = (runE && runO) ? FD_EARLY_HOLD : 0;                                                   \
             } else                                                                                           \
                 hold--;                                                                                      \
         }                                                                                                    \
         if (runE)                                                                                            \
-            se = fast_score_half<0>(A, B, C, D, E, F, G);                                                    \
+            se = as_u32(fast_score_half<0>(A, B, C, D, E, F, G));                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
         if (runO)                                                                                            \
-            so = fast_score_half<1>(A, B, C, D, E, F, G);                                                    \
+            so = as_u32(fast_score_half<1>(A, B, C, D, E, F, G));                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
-        nms_row(as_u32(se) & lm, as_u32(so) & lm, (k));                                                      \
+        if (__builtin_expect(tail, 0)) {                                                                     \
+            FD_TAIL                                                                                          \
+            const uint32_t lm = (uint32_t)(((k) - rows) >> 31);  /* all ones while the lane's own band lasts */ \
+            se &= lm;                                                                                        \
+            so &= lm;                                                                                        \
+        }                                                                                                    \
+        nms_row(se, so, (k));                                                                                \
     }
     // EARLY: rows to go before the bound is evaluated again -- after a row whose segment was NOT clear the next
     // FD_EARLY_HOLD rows run the network untested (textured regions pay a quarter of the test), after a clear one every row is
@@ -955,23 +1014,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         r0.f[o] = r1.f[o] = r2.f[o] = r3.f[o] = r4.f[o] = r5.f[o] = r6.f[o] = 0u;
     if (wrows > 0) {
         FD_LOAD(r0, 0) FD_LOAD(r1, 1) FD_LOAD(r2, 2) FD_LOAD(r3, 3) FD_LOAD(r4, 4) FD_LOAD(r5, 5)
-        FD_FETCH(6)
-    }
+        FD_FETCH(6 < fetch_max)
 #pragma unroll 1
-    for (int k = 0; k < wrows; k += 7) {
-        FD_STEP(r0, r1, r2, r3, r4, r5, r6, k)
-        FD_STEP(r1, r2, r3, r4, r5, r6, r0, k + 1)
-        FD_STEP(r2, r3, r4, r5, r6, r0, r1, k + 2)
-        FD_STEP(r3, r4, r5, r6, r0, r1, r2, k + 3)
-        FD_STEP(r4, r5, r6, r0, r1, r2, r3, k + 4)
-        FD_STEP(r5, r6, r0, r1, r2, r3, r4, k + 5)
-        FD_STEP(r6, r0, r1, r2, r3, r4, r5, k + 6)
+        for (int k = 0;; k += 7) {
+            FD_STEP(r0, r1, r2, r3, r4, r5, r6, k)
+            if (k + 1 >= wrows)
+                break;
+            FD_STEP(r1, r2, r3, r4, r5, r6, r0, k + 1)
+            if (k + 2 >= wrows)
+                break;
+            FD_STEP(r2, r3, r4, r5, r6, r0, r1, k + 2)
+            if (k + 3 >= wrows)
+                break;
+            FD_STEP(r3, r4, r5, r6, r0, r1, r2, k + 3)
+            if (k + 4 >= wrows)
+                break;
+            FD_STEP(r4, r5, r6, r0, r1, r2, r3, k + 4)
+            if (k + 5 >= wrows)
+                break;
+            FD_STEP(r5, r6, r0, r1, r2, r3, r4, k + 5)
+            if (k + 6 >= wrows)
+                break;
+            FD_STEP(r6, r0, r1, r2, r3, r4, r5, k + 6)
+            if (k + 7 >= wrows)
+                break;
+        }
+        finish_row(0u, 0u, wrows - 1);  // the row below the band counts as 0 (a shorter band was finished inside the loop)
     }
 #undef FD_STEP
+#undef FD_TAIL
 #undef FD_LOAD
 #undef FD_FETCH
-    if (wrows > 0)
-        finish_row(0u, 0u, wrows - 1);  // the row below the band counts as 0 (a shorter band was finished inside the loop)
+#undef FD_FETCH_STEP
 
     // ---- the wave's records become keys.  The cells a wave touches are a contiguous range of at most FD_CELLS ids
     //      (host-checked), so id mod FD_CELLS addresses per-wave counters in LDS.  Per (wave, cell): one global atomic
@@ -984,7 +1058,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int nrec = min(qn, qcap);
     for (int e = lane; e < nrec; e += 64) {
         const uint2 r = s_q[wave][e];
-        detect_record(r.x, r.y, s_lane[wave][(r.y >> 9) & 63u], [&](int, int sc, int cell) {
+        detect_record(r.x, r.y, s_lane[wave][(r.y >> 8) & 63u], [&](int, int sc, int cell) {
             atomicAdd(&s_cc[wave][cell & (FD_CELLS - 1)], 1 + (sc > t_ini ? 65536 : 0));
             s_cid[wave][cell & (FD_CELLS - 1)] = cell;
         });
@@ -1029,8 +1103,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     for (int e = lane; e < nrec; e += 64) {
         const uint2 r = s_q[wave][e];
-        const DetectLane dl = s_lane[wave][(r.y >> 9) & 63u];
-        const int row = (int)((r.y >> 1) & 127u);
+        const DetectLane dl = s_lane[wave][(r.y >> 8) & 63u];
+        const int row = (int)(r.y & 127u);
         detect_record(r.x, r.y, dl, [&](int p, int sc, int cell) {
             const int pos = atomicAdd(&s_cc[wave][cell & (FD_CELLS - 1)], 1);
             fslots[pos] = pack_key(dl.xrel + p, dl.yrel + row, sc - 1);
