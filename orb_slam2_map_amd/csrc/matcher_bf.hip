@@ -92,6 +92,7 @@ constexpr int BF_TILE_STRIDE = 272;                // bytes per expanded B row i
 constexpr int BF_TILE_ROWS = 64;                   // B rows staged per iteration
 constexpr int BF_TOPK_THREADS = 512;               // 8 waves = 256 A rows share every staged B tile
 constexpr int BF_TOPK_ROWS = BF_TOPK_THREADS / 64 * 32;
+constexpr int BF_SEL_DONE = INT_MIN / 2;           // "no candidate left" of k_bf_topk's selection (see there)
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(BF_TOPK_THREADS) void k_bf_topk(int cap, const uint
             tag[reg] = (15 - reg) - sa16;
     }
     uint32_t t[4] = {BF_KEY_NONE, BF_KEY_NONE, BF_KEY_NONE, BF_KEY_NONE};
-    int lim = acc_min;  // accumulator value a distance must reach to be inserted
+    int lim16 = acc_min * 16;  // tagged accumulator value a candidate must reach to be inserted
     uint32_t d_next = 0;
     if (ntiles > 0)
         stage(fetch(0), 0);
@@ -220,38 +221,47 @@ __global__ __launch_bounds__(BF_TOPK_THREADS) void k_bf_topk(int cap, const uint
         // lane of the wave and are dismissed with 8 v_max3 and one branch.
         // Selection.  A lane's 16 values per row block rarely hold anything that beats its list, but SOME lane of the
         // wave nearly always does, so a test-and-branch per value would run every insert body for the whole wave.
-        // Instead each value is tagged with its register index (e = acc << 4 | 15 - reg: larger = closer, then lower
+        // Instead each value is tagged with its register index (acc = dot << 4 | 15 - reg: larger = closer, then lower
         // B row), a lane's best candidate is one v_max3 tree away, and the wave loops only while some lane still has
         // a candidate above its bar: one insert per lane per trip, typically one or two trips per block.
+        // A lane's 16 values are pairwise distinct and the trips take them in descending order, so after the trip that
+        // took m the values left are those below m, and the next one is m + max_u32(acc[reg] - m): a value below m wraps
+        // to a large unsigned difference, the closest one to the largest, a value taken already gives a small one.  acc
+        // is never written, and no compare stands in the walk.  BF_SEL_DONE, a 17th operand below every value and every
+        // bar, is what the walk arrives at when nothing is left (its difference lies between the two kinds: |acc| < 2^13).
+        // The bar is compared on the tagged value (lim16 = 16 * bar; the tag bits lie below it).
+        // Scalar form, next to the blanking loop this replaced: bf_select.h (tests/bf_select_test.cpp).
         const int jlast = jend - 1;
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             const v16i &acc = u ? acc1 : acc0;
-            int e[16];
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++)
-                e[reg] = acc[reg];
             const int j0 = jbeg + tile * BF_TILE_ROWS + 32 * u + 4 * h;
-            for (;;) {
-                int m = max(max(e[0], e[1]), e[2]);
+            int m = max(max(acc[0], acc[1]), acc[2]);
 #pragma unroll
-                for (int reg = 3; reg < 15; reg += 2)
-                    m = max(max(m, e[reg]), e[reg + 1]);
-                m = max(m, e[15]);
-                const bool hit = (m >> 4) >= lim;
+            for (int reg = 3; reg < 15; reg += 2)
+                m = max(max(m, acc[reg]), acc[reg + 1]);
+            m = max(m, acc[15]);
+            for (;;) {
+                const bool hit = m >= lim16;
                 if (!__any(hit))
                     break;
                 if (hit) {
                     const int reg = 15 - (m & 15);
                     const int j = j0 + (reg & 3) + 8 * (reg >> 2);
                     if (j <= jlast && (!NODES || nodes_b[j] == my_node)) {
-                        top4_insert(t, (uint32_t)(((256 - (m >> 4)) << 11) + j));  // (2 ham) << 11 = ham << 12
-                        if (t[3] != BF_KEY_NONE)
-                            lim = max(lim, 256 - 2 * (int)(t[3] >> 12));  // a full list admits distances <= its last
+                        const uint32_t k = (uint32_t)(((256 - (m >> 4)) << 11) + j);  // (2 ham) << 11 = ham << 12
+                        if (k < t[3]) {
+                            top4_insert(t, k);
+                            // a full list admits distances <= its last; BF_KEY_NONE >> 12 gives a bar far below acc_min
+                            lim16 = max(lim16, (256 - 2 * (int)(t[3] >> 12)) * 16);
+                        }
                     }
+                    uint32_t n = max(max((uint32_t)BF_SEL_DONE - (uint32_t)m, (uint32_t)acc[0] - (uint32_t)m),
+                                     (uint32_t)acc[1] - (uint32_t)m);
 #pragma unroll
-                    for (int r2 = 0; r2 < 16; r2++)
-                        e[r2] = e[r2] == m ? INT_MIN : e[r2];  // taken
+                    for (int reg2 = 2; reg2 < 16; reg2 += 2)
+                        n = max(max(n, (uint32_t)acc[reg2] - (uint32_t)m), (uint32_t)acc[reg2 + 1] - (uint32_t)m);
+                    m = (int)((uint32_t)m + n);
                 }
             }
         }
