@@ -15,7 +15,7 @@
 #include <utility>
 #include "trig_base.h"
 #include "pyramid_view.h"
-#include "resize_tables.h"
+#include "extractor_plan.h"  // the geometry structs the kernels read, their constants, the host-side plan
 
 #include <algorithm>
 #include <cfloat>
@@ -26,46 +26,6 @@
 
 namespace orbgpu {
 
-constexpr int EDGE = 19;           // EDGE_THRESHOLD, ORBextractor.cc:74
-static_assert(EDGE == RS_EDGE, "resize_tables.h builds its tables for this border");
-constexpr int BORDER0 = EDGE - 3;  // minBorderX/Y, ORBextractor.cc:775-776
-constexpr int HALF_PATCH = 15;     // HALF_PATCH_SIZE, ORBextractor.cc:73
-constexpr int PATCH = 31;          // PATCH_SIZE
-constexpr float CELL_W = 30.f;     // W, ORBextractor.cc:769
-
-// ---------------------------------------------------------------------------------------------
-// Geometry tables (host-built, device-read)
-// ---------------------------------------------------------------------------------------------
-struct LevelGeom {
-    int w, h, pitch;     // level size; padded row pitch in bytes (multiple of 64)
-    int plane_off;       // byte offset of the padded plane inside one frame's pyramid block
-    int max_bx, max_by;  // maxBorderX/Y = w-16, h-16
-    int ncols, nrows, wcell, hcell;
-    int cell_first, ncells;  // this level's (non-skipped) cells in the cell table
-    int slot_off, slot_cnt;  // this level's key slots inside one frame's slot block (u32 units)
-    int quota, sel_cap, sel_off;
-    int n_ini;
-    float hx;
-    float scale;
-    int patch;
-    int xtab_off, ytab_off;  // resize tables (levels >= 1)
-    int rs_off, rs_fast;     // fast-path strip tables (k_resize_fast); rs_fast = 0 -> k_resize_level
-    int ncols_eff;           // cell columns that are not skipped (ORBextractor.cc:797)
-    uint32_t inv_wcell, inv_hcell;  // mul_hi(v, inv) == v / wcell (hcell) for every key coordinate (host-verified)
-    int yrow_off;                   // k_resize_fast: first YRow of the level (one per PADDED output row)
-};
-
-struct CellDesc {
-    short level;
-    short x0, y0, x1, y1;  // sub-image [x0,x1) x [y0,y1) in level coordinates (FAST apron included)
-    short addx, addy;      // j*wCell, i*hCell  (ORBextractor.cc:822-823)
-    short cap;             // slot capacity
-    int slot_off;          // offset of this cell's slots inside one frame's slot block
-    int pitch, plane_off;  // copies of the level's LevelGeom fields
-    int pad[1];
-};
-static_assert(sizeof(CellDesc) == 32, "CellDesc is read as two 16-byte words");
-
 // packed FAST key: y[31:20] x[19:8] response[7:0]; x,y relative to (minBorderX,minBorderY)
 __host__ __device__ __forceinline__ uint32_t pack_key(int x, int y, int resp)
 {
@@ -74,16 +34,6 @@ __host__ __device__ __forceinline__ uint32_t pack_key(int x, int y, int resp)
 __host__ __device__ __forceinline__ int key_x(uint32_t k) { return (int)((k >> 8) & 0xFFF); }
 __host__ __device__ __forceinline__ int key_y(uint32_t k) { return (int)(k >> 20); }
 __host__ __device__ __forceinline__ int key_resp(uint32_t k) { return (int)(k & 0xFF); }
-
-__host__ __device__ __forceinline__ int reflect101(int p, int len)
-{
-    // single bounce is enough: every level is >= 62 px and the border is 19 px
-    if (p < 0)
-        p = -p;
-    else if (p >= len)
-        p = 2 * (len - 1) - p;
-    return p;
-}
 
 // Level 0 read straight from the caller's image ("direct" mode).  ComputePyramid's level 0 is copyMakeBorder(image) into a
 // padded plane (ORBextractor.cc:1125-1129) -- 0.67 MB of traffic per 640x480 frame that no stage needs: FAST, the
@@ -105,8 +55,6 @@ constexpr int BLUR0_OX = EDGE + 1;  // direct mode: column of pixel 0 in the BLU
 // byte offset of a row inside a padded plane: rows and pitches are < 2^24, so a 24-bit multiply (full rate) is exact;
 // the 64-bit (size_t) product the obvious expression asks for costs two quarter-rate multiplies per use
 __device__ __forceinline__ uint32_t rowoff(int row, int pitch) { return __umul24((unsigned)row, (unsigned)pitch); }
-
-constexpr int PYR_ROWS = 8;  // padded rows per thread in the pyramid kernels
 
 __global__ __launch_bounds__(256) void k_border0(const uint8_t *__restrict__ src, size_t stride,
                                                  size_t frame_stride, uint8_t *__restrict__ pyr,
@@ -154,11 +102,6 @@ __global__ __launch_bounds__(256) void k_border0(const uint8_t *__restrict__ src
 // adjacent source dwords, picked by one v_perm_b32 with a selector that only depends on the column (BorderCol, built
 // on the host).  No per-byte path and no divergence: a thread owns 16 output bytes x BORDER_ROWS rows.
 constexpr int BORDER_ROWS = 4;
-
-struct BorderCol {
-    uint32_t d;    // first of the two adjacent source dwords
-    uint32_t sel;  // v_perm_b32 selector over {src[d+1], src[d]}
-};
 
 __global__ __launch_bounds__(256) void k_border0_fast(const uint8_t *__restrict__ src, size_t stride, size_t frame_stride,
                                                       uint8_t *__restrict__ pyr, size_t frame_pyr,
@@ -497,10 +440,6 @@ __global__ __launch_bounds__(256) void k_resize_fast(uint8_t *__restrict__ pyr, 
 // plain copies of the plane's own interior pixels.  One thread per frame pixel: the 2 ring rows above and below the image
 // (corners included), then the 2 ring columns beside every image row.  Not on the hot path (k_resize_fast writes the
 // 3 px the blur reads itself): ring = EDGE when a full padded plane is handed out.
-struct RingGeom {
-    int first[ORBGPU_MAX_LEVELS + 1];  // first item of level l (first[1] = 0); first[nlevels] = items per frame
-    int nlevels;
-};
 __global__ __launch_bounds__(256) void k_ring_fill(uint8_t *__restrict__ pyr, size_t frame_pyr,
                                                     const LevelGeom *__restrict__ geom, RingGeom rgm, int ring)
 {
@@ -543,8 +482,6 @@ __global__ __launch_bounds__(256) void k_ring_fill(uint8_t *__restrict__ pyr, si
 // three-input packed extrema
 // (v_pk_maximum3_f16 / v_pk_minimum3_f16 on the integer bit patterns: two pixels per instruction, no divergence).
 // ---------------------------------------------------------------------------------------------
-constexpr int MAX_CELL = 66;  // max cell interior edge
-
 typedef short pk16 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ pk16 as_pk(uint32_t u) { return __builtin_bit_cast(pk16, u); }
 __device__ __forceinline__ uint32_t as_u32(pk16 v) { return __builtin_bit_cast(uint32_t, v); }
@@ -704,13 +641,6 @@ __device__ __forceinline__ uint32_t fast_maybe_half(const RowU &r0, const RowU &
     return (eb | ed) & 0x80008000u;
 }
 
-struct StripGeom {  // strips of all levels, flattened (k_blur)
-    int first[ORBGPU_MAX_LEVELS + 1];  // first strip index of each level
-    int nsx[ORBGPU_MAX_LEVELS];        // strips per row of strips
-    int nlevels;
-};
-
-
 // ---------------------------------------------------------------------------------------------
 // k_fast_detect: corner score, in-cell 3x3 non-maximum suppression and key emission in one pass over the pyramid --
 // the score map never reaches memory.
@@ -739,25 +669,8 @@ struct StripGeom {  // strips of all levels, flattened (k_blur)
 // also fits four waves per SIMD (121 VGPRs).  With ONE score network per pixel pair, its polarity chosen by the selector
 // of fast_score_pk (124 VGPRs, still four waves): 0.621 -> 0.574 ms per 512 frames.
 // ---------------------------------------------------------------------------------------------
-constexpr int FD_OWN = 62;    // columns a wave owns (lanes 1..62)
 constexpr int FD_QCAP = 512;  // row records a wave can queue before it falls back to emitting them directly
-constexpr int FD_CELLS = 32;  // cells a wave's 64 columns can touch (consecutive ids)
 constexpr int FD_EARLY_HOLD = 3;  // k_fast_detect<true>: rows scored without the early-out test after a test that found work
-
-struct DetectGeom {
-    int first[ORBGPU_MAX_LEVELS + 1];  // first flat column strip of each level (bands x dword columns)
-    int nsx[ORBGPU_MAX_LEVELS];        // dword columns per band: padded dwords 9 .. (w-1)/4
-    int ncols[ORBGPU_MAX_LEVELS];      // cell columns of the level's cell grid (skipped ones excluded)
-    int ctab_off[ORBGPU_MAX_LEVELS];   // first ColumnInfo of the level
-    int xfirst[ORBGPU_MAX_LEVELS];     // image column of pixel 0 of the level's first strip: 17 for a padded plane (its aligned
-                                       // dword 9), 16 for level 0 read directly from the image (Src0: aligned to the image)
-    int nlevels;
-};
-
-struct ColumnInfo {
-    uint32_t cellj;  // byte p: cell column of pixel p of the dword (0xFF: outside every cell interior)
-    uint32_t flags;  // bit p: pixel p lies in a cell interior; bit 4+p: first column of its cell; bit 8+p: last column
-};
 
 struct DetectLane {  // what the key emission needs to know about the lane that queued a record
     int xrel, yrel;  // key coordinates of pixel 0 / row 0 of the strip (relative to minBorderX/Y)
@@ -1152,14 +1065,8 @@ __device__ __forceinline__ int quadrant_at(uint32_t key, uint32_t split)
     return (x < (int)(split & 0xFFFFu) ? 0 : 1) + (y < (int)(split >> 16) ? 0 : 2);
 }
 
-// workgroup size of k_quadtree: a single frame is bound by the latency of its level-0 workgroup (more threads per
-// key loop help), a full batch by barrier cost and workgroups per CU (fewer threads help): 155 -> 122 us at B = 256
-constexpr int QT_THREADS = 1024, QT_THREADS_SMALL = 512, QT_THREADS_BATCH = 256, QT_BATCH_MIN = 32;
-constexpr int QT_LARGE_PIXELS = 700000;  // single frames from about 1024x768 use QT_THREADS (measured: 137 -> 128 us at 1280x960, 51 -> 54 us at 640x480)
-
 // Node lists up to this length are processed by one wave (k_quadtree, sections (2)..(6))
 constexpr int QT_SOLO_MAX = 128;
-constexpr int QT_LDS_MAX = 160 * 1024 - 1024;  // dynamic LDS k_quadtree may be launched with (the CU has 160 KB)
 
 // LDS traffic of one wave is ordered; this keeps the compiler from moving accesses across the point and drains the queue
 __device__ __forceinline__ void qt_wave_sync()
@@ -1261,7 +1168,6 @@ constexpr int QT_ILP = 4;  // keys a thread carries through a sweep side by side
 // leaves in `aux`: [0] the number of kept keys, [1 + 4 b + q] the kept keys of initial node (bin) b that fall into its
 // quadrant q.  k_quadtree<true> reads and re-arms them.  Batches keep the in-kernel step 0 (one workgroup per (frame,
 // level) is already thousands of workgroups there).
-constexpr int QT_INI_MAX = 80;                       // initial nodes of a level this path supports (round(width / height))
 constexpr int QT_AUX_LEVEL = 1 + 4 * QT_INI_MAX;     // ints per (frame, level)
 constexpr int QT_AUX_FRAME = QT_AUX_LEVEL * ORBGPU_MAX_LEVELS;
 constexpr int QT_PRE_KEYS = 256 * QT_ILP;            // stored keys a workgroup of the prefilter takes per trip
@@ -1904,10 +1810,6 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x)
     return a;
 }
 
-struct UMax {
-    int v[16];
-};
-
 // Half a wave (32 lanes) per selected key point, lane = one row v of the radius-15 disc.  A lane
 // reads its row as 9 aligned dwords and reduces it with v_dot4_u32_u8 against per-(alignment, |v|)
 // byte-weight tables (built on the host, copied to LDS by every workgroup): W10 holds (u+16) inside the disc (0 outside),
@@ -1915,7 +1817,6 @@ struct UMax {
 // Integer moments: exact in any summation order.
 constexpr int OR_ITERS = 4;  // key points per half wave for full batches (1 below OR_BATCH_MIN frames: latency)
 constexpr int OR_BATCH_MIN = 32;
-constexpr int PYR_BATCH_MIN = 32;  // frames per call from which every level of the resize chain runs PYR_ROWS rows per item (REUSE)
 
 __global__ __launch_bounds__(256) void k_orient(const uint8_t *__restrict__ pyr, size_t frame_pyr,
                                                 const LevelGeom *__restrict__ geom, int nlevels,
@@ -2097,8 +1998,6 @@ __global__ __launch_bounds__(256) void k_trig(KpAux *__restrict__ aux, const int
 // 12-byte loads and 4-byte stores: 176 us against 166 us; a second input row in flight: no gain.)
 // HBM-bound: each pixel is fetched once from HBM (neighbouring strips re-read through L1/L2).
 // ---------------------------------------------------------------------------------------------
-constexpr int BLUR_ROWS = 30;  // output rows per strip (5 x 6: the 6-slot register ring of row pairs unrolls evenly)
-
 __device__ __forceinline__ void blur_hsum(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t h[4])
 {
     // window bytes 0..11 = padded columns 4s-4 .. 4s+7; output pixel p has its centre at byte 4+p, its taps at bytes
@@ -2408,10 +2307,6 @@ __global__ void k_unpack_keys(const uint32_t *__restrict__ keys, int n, int *__r
 // ---------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------
-static const int8_t k_pattern_host[1024] = {
-#include "orbgpu_pattern.inc"
-};
-
 enum Stage { ST_PYRAMID = 0, ST_BLUR, ST_FAST, ST_QUADTREE, ST_ORIENT, ST_DESCRIBE, ST_COUNT };  // in launch order
 static const char *k_stage_names[ST_COUNT] = {"pyramid", "blur", "fast", "quadtree", "orient", "describe"};
 
@@ -2443,36 +2338,32 @@ using namespace orbgpu;
 
 struct orbgpu_extractor {
     orbgpu_extractor_params prm;
-    double scale_factor_d;
     int nlevels;
-    float scale[ORBGPU_MAX_LEVELS], inv_scale[ORBGPU_MAX_LEVELS], sigma2[ORBGPU_MAX_LEVELS],
-        inv_sigma2[ORBGPU_MAX_LEVELS];
-    int quota[ORBGPU_MAX_LEVELS];
-    UMax umax;
-    // geometry of the configured image size
-    int cfg_w = 0, cfg_h = 0, cfg_batch = 0;
-    std::vector<LevelGeom> geom;
-    std::vector<CellDesc> cells;
-    StripGeom blur_geom;
-    DetectGeom det_geom;
-    size_t frame_pyr = 0, frame_slots = 0;
-    int sel_cap_total = 0, ncap = 0, max_kp = 0;
-    size_t qt_lds = 0;
-    int qt_kcap = 0;  // keys of a level k_quadtree<true> keeps in LDS
+    ExtractorConsts consts;  // constructor tables (extractor_plan.h)
+    // geometry of the configured image size (plan.w == 0: none) and the batch its per-frame buffers hold
+    ExtractorPlan plan;
+    int cfg_batch = 0;
     // device state
-    DevBuf d_geom, d_cells, d_xtab, d_ytab, d_yrow, d_pattern, d_rstrip, d_rsel, d_rwt, d_ctab, d_bcol;
+    DevBuf d_tables;  // the plan's constant tables: plan.blob, one upload
     DevBuf d_pyr, d_blur, d_slots, d_cellcnt, d_dkey, d_dnode, d_sel, d_nsel, d_ncand, d_aux;
     mutable DevBuf d_stereo;  // scratch of the readers of the pyramid view (stereo.hip), created on first use
     DevBuf d_qtaux;  // k_qt_prefilter -> k_quadtree<true> (single frames): QT_AUX_FRAME ints per frame, < QT_BATCH_MIN frames
-    bool qt_prefilter = false;  // every level has <= QT_INI_MAX initial nodes
-    int max_slots_level = 0;
     DevBuf d_in, d_kps, d_desc, d_nout;  // staging for the host entry points
     void *h_pin = nullptr;               // ... and its pinned host side (input images | counts | key points | descriptors)
     size_t h_pin_bytes = 0;
     bool pinned_staging = true;          // ORBGPU_DEBUG_NO_PINNED: the runtime's pageable copies instead (A/B)
     DevBuf d_dbg;
     hipStream_t stream = nullptr;
-    int last_batch = 0, last_cap = 0;
+    // What the last call left behind, for the getters.  batch == 0: nothing to read.  src.direct != 0: the call ran in direct
+    // mode; level0_materialized: d_pyr holds its level 0 (false after a direct-mode call until a getter asks);
+    // borders_materialized: the planes of levels >= 1 hold their whole 19-px border (k_resize_fast writes plane interiors and
+    // the 3 px the blur reads, k_ring_fill the rest when a getter asks).
+    struct LastCall {
+        Src0 src = {nullptr, 0, 0u, 0};
+        int batch = 0, cap = 0;
+        bool level0_materialized = true, borders_materialized = true;
+    };
+    LastCall last;
     // profiling: one event set per profiled call (up to PROF_SLOTS), averaged by stage_times()
     static constexpr int PROF_SLOTS = 256;
     bool profiling = false;
@@ -2482,11 +2373,8 @@ struct orbgpu_extractor {
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     uint64_t graph_key = 0;
-    // what launch_pipeline recorded as the last call's bookkeeping while the graph was recorded: a replay restores it
-    Src0 graph_src = {nullptr, 0, 0u, 0};
-    int graph_batch = 0, graph_cap = 0;
+    LastCall graph_last;  // what launch_pipeline noted while the graph was recorded: a replay restores it
     int graph_records = 0, graph_replays = 0;  // ORBGPU_DBG_GRAPH_COUNTS (tests)
-    bool border_fast = false;  // level-0 column table present (width % 4 == 0)
     hipEvent_t stage_signal[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // caller's events
     hipEvent_t pipe_signal[8] = {};  // the same for an orbgpu_pipeline that owns this handle (stagger of its parts)
     bool counters_dirty = false;  // the cell counters may hold counts no k_quadtree has consumed
@@ -2501,73 +2389,26 @@ struct orbgpu_extractor {
     bool fast_early_out = false;   // k_fast_detect<true>: exact wave-level early-out (orbgpu_extractor_set_fast_early_out; ORBGPU_FAST_EARLY_OUT=1 at creation)
     int graph_state = 0;  // 0 = not tried, 1 = usable, -1 = capture failed: plain launches from then on
     // direct mode (Src0): level 0 read from the caller's image, no padded copy
-    bool direct0_ok = false;       // the configured geometry has the tables for it (width % 8 == 0, >= 2 levels on the fast resize path)
     bool no_early_blur0 = false;   // ORBGPU_DEBUG_NO_EARLY_BLUR0: concurrent blur forks after the pyramid for level 0 too (A/B)
     int direct0_min_batch = 8;     // frames per call from which direct mode is used (ORBGPU_DEBUG_DIRECT0_MIN)
     bool no_direct0 = false;       // ORBGPU_DEBUG_NO_DIRECT0 (read at creation): always make the padded copy (tests, A/B)
-    int rs_off_direct = 0;         // level 1's strip tables for the unpadded source
-    int r8_off[ORBGPU_MAX_LEVELS] = {};  // 8-pixel form of k_resize_fast: first item of the level, -1 = the level keeps the 4-pixel form
-    int r8_off_direct = -1;              // ... of level 1 for the unpadded source
-    bool r8_share[ORBGPU_MAX_LEVELS] = {}, r8_share_direct = false;  // some item of the level has R8_SHARE set
-    DevBuf d_r8item, d_r8sel, d_r8wt;
-    DetectGeom det_geom_direct;    // k_fast_detect's strips with level 0 aligned to the image
-    Src0 last_src = {nullptr, 0, 0u, 0};  // level-0 source of the last call (direct != 0: the call ran in direct mode)
-    bool level0_materialized = true;      // d_pyr holds level 0 of the last call (false after a direct-mode call until a getter asks)
-    // k_resize_fast writes plane interiors and the 3 px of border the blur reads; k_ring_fill the full border on demand
-    bool interior_resize = false;      // some level >= 1 of the configured geometry goes through k_resize_fast
-    bool borders_materialized = true;  // the planes of levels >= 1 hold their whole 19-px border (false after a call until a getter asks)
     bool poison_pyramid = false;       // ORBGPU_DEBUG_POISON_PYRAMID (read at creation): 0xA5 over both plane buffers before every call (tests)
     TrigTable trig = {nullptr, nullptr, nullptr, 0u};  // the host libm's cosf / sinf exceptions (trig.hip); none in ORBGPU_TRIG_ROUNDED_DOUBLE mode
 
+    // a constant table of the plan on the device
+    template <typename T> const T *tab(const PlanTable &t) const { return reinterpret_cast<const T *>(d_tables.as<uint8_t>() + t.off); }
+    const LevelGeom *d_geom() const { return tab<LevelGeom>(plan.t_geom); }
+    // every device buffer the handle owns
+    std::vector<DevBuf *> buffers()
+    {
+        return {&d_tables, &d_pyr, &d_blur, &d_slots, &d_cellcnt, &d_dkey, &d_dnode, &d_sel, &d_nsel, &d_ncand, &d_aux,
+                &d_stereo, &d_qtaux, &d_in, &d_kps, &d_desc, &d_nout, &d_dbg};
+    }
 };
 
 namespace orbgpu {
 
 int trig_table_for_device(int device_id, TrigTable *out);  // trig.hip
-
-// E0: constructor tables, ORBextractor.cc:410-470
-static void build_tables(orbgpu_extractor *e)
-{
-    const int nl = e->nlevels;
-    e->scale_factor_d = (double)e->prm.scale_factor;  // ORBextractor.h:98 keeps a double
-    e->scale[0] = 1.0f;
-    e->sigma2[0] = 1.0f;
-    for (int i = 1; i < nl; i++) {
-        e->scale[i] = (float)((double)e->scale[i - 1] * e->scale_factor_d);
-        e->sigma2[i] = e->scale[i] * e->scale[i];
-    }
-    for (int i = 0; i < nl; i++) {
-        e->inv_scale[i] = 1.0f / e->scale[i];
-        e->inv_sigma2[i] = 1.0f / e->sigma2[i];
-    }
-    const float factor = (float)(1.0 / e->scale_factor_d);
-    float desired = (float)e->prm.nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)nl));
-    int sum = 0;
-    for (int l = 0; l < nl - 1; l++) {
-        e->quota[l] = cv_round_host(desired);
-        sum += e->quota[l];
-        desired *= factor;
-    }
-    e->quota[nl - 1] = std::max(e->prm.nfeatures - sum, 0);
-
-    int *um = e->umax.v;
-    const int vmax = (int)floor(HALF_PATCH * sqrtf(2.f) / 2 + 1);
-    const int vmin = (int)ceil(HALF_PATCH * sqrtf(2.f) / 2);
-    const double hp2 = HALF_PATCH * HALF_PATCH;
-    for (int v = 0; v <= vmax; ++v)
-        um[v] = cv_round_host(sqrt(hp2 - v * v));
-    for (int v = HALF_PATCH, v0 = 0; v >= vmin; --v) {
-        while (um[v0] == um[v0 + 1])
-            ++v0;
-        um[v] = v0;
-        ++v0;
-    }
-    // k_orient's "third piece" rule is written for these values (half widths 15 up to |v| = 3, >= 14 up to |v| = 6)
-    static const int expect[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
-    for (int v = 0; v <= HALF_PATCH; v++)
-        if (um[v] != expect[v])
-            abort();
-}
 
 // Forgets the recorded graph of the host entry points: the next host call of a configuration launches plainly, the one
 // after it records again.
@@ -2584,397 +2425,83 @@ static void drop_graph(orbgpu_extractor *e)
 
 // The getters of the last call have nothing to read (its planes, or the buffer its lazy level 0 would be made from, are
 // being replaced): they answer EINVAL until the next call has launched.
-static void forget_last_call(orbgpu_extractor *e)
+static void forget_last_call(orbgpu_extractor *e) { e->last = orbgpu_extractor::LastCall(); }
+
+// The one place a call's bookkeeping is written (launch_pipeline; a graph replay restores the copy saved at its recording).
+static void note_call(orbgpu_extractor *e, const Src0 &s0, int batch, int cap)
 {
-    e->last_batch = e->last_cap = 0;
-    e->last_src = Src0{nullptr, 0, 0u, 0};
-    e->level0_materialized = true;
-    e->borders_materialized = true;
+    e->last.src = s0;
+    e->last.batch = batch;
+    e->last.cap = cap;
+    e->last.level0_materialized = !s0.direct;
+    e->last.borders_materialized = !e->plan.interior_resize;
 }
 
-
-// Level sizes, FAST cell grid, resize tables, slot layout for one image size.
+// Plans one image size (extractor_plan.h), sizes the handle's buffers for it and uploads the plan's tables.
 static int configure(orbgpu_extractor *e, int w, int h, int batch)
 {
-    if (e->cfg_w == w && e->cfg_h == h && batch <= e->cfg_batch)
+    if (e->plan.w == w && e->plan.h == h && batch <= e->cfg_batch)
         return ORBGPU_OK;
     // a real reconfigure rewrites tables that kernels of an earlier call (on the caller's stream) may still read
-    if (e->cfg_w != 0)
+    if (e->plan.w != 0)
         ORBGPU_HIP_TRY(hipDeviceSynchronize());
     // From here on the handle is unconfigured until the end of this function: every return below leaves it so, and the
     // next call configures again from scratch (a failed reservation has already freed the old buffer).  No recorded graph
     // outlives the buffers it baked in, and no getter reads a last call whose geometry and planes are being replaced.
-    e->cfg_w = e->cfg_h = e->cfg_batch = 0;
+    e->plan = ExtractorPlan();
+    e->cfg_batch = 0;
     drop_graph(e);
     forget_last_call(e);
-    const int nl = e->nlevels;
-    std::vector<LevelGeom> geom(nl);
-    std::vector<CellDesc> cells;
-    ResizeTables rt;
-    std::vector<ResizeLevel> rlev(nl);
-    size_t plane_off = 0;
-    int slot_off = 0, sel_off = 0, max_cells_level = 0, ncap = 0;
-    for (int l = 0; l < nl; l++) {
-        LevelGeom &g = geom[l];
-        memset(&g, 0, sizeof(g));
-        g.w = cv_round_host((float)w * e->inv_scale[l]);  // :1112
-        g.h = cv_round_host((float)h * e->inv_scale[l]);
-        g.max_bx = g.w - EDGE + 3;
-        g.max_by = g.h - EDGE + 3;
-        const float width = (float)(g.max_bx - BORDER0), height = (float)(g.max_by - BORDER0);
-        g.ncols = (int)(width / CELL_W);
-        g.nrows = (int)(height / CELL_W);
-        ORBGPU_REQUIRE(g.ncols >= 1 && g.nrows >= 1 && g.w < 4096 + BORDER0 && g.h < 4096 + BORDER0,
-                       "image %dx%d: pyramid level %d (%dx%d) is outside the supported range "
-                       "(each level needs >= 62 px per side and < 4112 px)",
-                       w, h, l, g.w, g.h);
-        g.wcell = (int)ceilf(width / g.ncols);
-        g.hcell = (int)ceilf(height / g.nrows);
-        ORBGPU_REQUIRE(g.wcell <= MAX_CELL && g.hcell <= MAX_CELL, "FAST cell %dx%d too large", g.wcell, g.hcell);
-        g.pitch = ((g.w + 2 * EDGE + 63) / 64) * 64;
-        g.plane_off = (int)plane_off;
-        plane_off += (((size_t)g.pitch * (g.h + 2 * EDGE) + 255) / 256) * 256;
-        g.quota = e->quota[l];
-        g.scale = e->scale[l];
-        g.patch = (int)(PATCH * e->scale[l]);  // :837
-        // DistributeOctTree initial nodes, :542-544
-        g.n_ini = (int)roundf(width / height);
-        ORBGPU_REQUIRE(g.n_ini >= 1, "level %d aspect ratio unsupported (nIni = 0 divides by zero in the reference)", l);
-        g.hx = width / (float)g.n_ini;
-        // cells, :789-808
-        g.cell_first = (int)cells.size();
-        g.slot_off = slot_off;
-        for (int i = 0; i < g.nrows; i++) {
-            const float iniY = (float)(BORDER0 + i * g.hcell);
-            float maxY = iniY + g.hcell + 6;
-            if (iniY >= g.max_by - 3)
-                continue;
-            if (maxY > g.max_by)
-                maxY = (float)g.max_by;
-            for (int j = 0; j < g.ncols; j++) {
-                const float iniX = (float)(BORDER0 + j * g.wcell);
-                float maxX = iniX + g.wcell + 6;
-                if (iniX >= g.max_bx - 6)
-                    continue;
-                if (maxX > g.max_bx)
-                    maxX = (float)g.max_bx;
-                CellDesc c;
-                c.level = (short)l;
-                c.x0 = (short)iniX;
-                c.x1 = (short)maxX;
-                c.y0 = (short)iniY;
-                c.y1 = (short)maxY;
-                c.addx = (short)(j * g.wcell);
-                c.addy = (short)(i * g.hcell);
-                const int iw = std::max(c.x1 - c.x0 - 6, 0), ih = std::max(c.y1 - c.y0 - 6, 0);
-                // strict 3x3 NMS: no two survivors are 8-neighbours
-                c.cap = (short)(((iw + 1) / 2) * ((ih + 1) / 2));
-                c.slot_off = slot_off;
-                c.pitch = g.pitch;
-                c.plane_off = g.plane_off;
-                c.pad[0] = 0;
-                slot_off += c.cap;
-                cells.push_back(c);
-            }
-        }
-        g.ncells = (int)cells.size() - g.cell_first;
-        g.slot_cnt = slot_off - g.slot_off;
-        max_cells_level = std::max(max_cells_level, g.ncells);
-        // E3': a level yields at most max(4*nIni, quota+2) key points
-        g.sel_cap = std::max(4 * g.n_ini, g.quota + 3) + 1;
-        g.sel_off = sel_off;
-        sel_off += g.sel_cap;
-        ncap = std::max(ncap, g.sel_cap);
-        // resize tables (cv::resize INTER_LINEAR 8U, A2) and the item tables of k_resize_fast: resize_tables.h
-        if (l > 0) {
-            rlev[l] = resize_add_level(rt, geom[l - 1].w, geom[l - 1].h, geom[l - 1].pitch, g.w, g.h, g.pitch);
-            g.xtab_off = rlev[l].xtab_off;
-            g.ytab_off = rlev[l].ytab_off;
-            g.yrow_off = rlev[l].yrow_off;
-            g.rs_off = rlev[l].rs_off;
-            g.rs_fast = rlev[l].fast4 ? 1 : 0;
-        }
+    ExtractorPlan plan;
+    std::string why;
+    PlanHooks hooks;
+    hooks.qt_keys = e->qt_keys_hook;
+    hooks.qt_no_prefilter = e->qt_no_prefilter;
+    int rc = plan_extractor(e->consts, w, h, hooks, &plan, &why);
+    if (rc != ORBGPU_OK) {
+        set_error("%s", why.c_str());
+        return rc;
     }
-    // direct mode: level 1's items once more, for source columns counted from the image's own column 0 (Src0)
-    bool direct_ok = nl >= 2 && w % 8 == 0 && w >= 64 && geom[std::min(1, nl - 1)].rs_fast != 0;
-    ResizeLevel rdirect;
-    if (direct_ok) {
-        rdirect = resize_add_direct(rt, rlev[1], geom[0].w, geom[1].w, geom[1].pitch);
-        direct_ok = rdirect.fast4;
-    }
-    const int rs_off_direct = rdirect.rs_off;
-    const std::vector<XTab> &xtab = rt.xtab;
-    const std::vector<YTab> &ytab = rt.ytab;
-    const std::vector<YRow> &yrow = rt.yrow;
-    const std::vector<ResizeStrip> &rstrip = rt.strip;
-    const std::vector<RsQuad> &rsel = rt.sel, &rwt = rt.wt;
-    ncap = std::max(ncap, (max_cells_level + 3) / 4);  // the cell scan reuses the [ncap*4] child-count array
-    ncap = ((ncap + 7) / 8) * 8;
-    const size_t qt_lds = (size_t)ncap * (2 * sizeof(short4) + 2 * sizeof(int) + 8 * sizeof(int) + 2 * sizeof(int) +
-                                          4 * sizeof(uint16_t) + 4 * sizeof(uint16_t) + 1 + 2 * sizeof(uint32_t)) + 64;
-    // single frames: keys (4 B) and node ids (2 B) of a level in LDS, as many as fit (never more than a level can hold)
-    int max_slots_level = 0;
-    for (int l = 0; l < nl; l++)
-        max_slots_level = std::max(max_slots_level, geom[l].slot_cnt);
-    int qt_kcap = max_slots_level;
-    if (e->qt_keys_hook >= 0)  // test hook: forces the mixed LDS / memory path
-        qt_kcap = e->qt_keys_hook;
-    qt_kcap = (int)std::min<size_t>((size_t)(qt_kcap + 7) / 8 * 8, qt_lds < 150 * 1024 ? (150 * 1024 - qt_lds) / 6 / 8 * 8 : 0);
-    ORBGPU_REQUIRE(qt_lds <= (size_t)QT_LDS_MAX, "nfeatures too large for the quadtree kernel (needs %zu B of LDS)", qt_lds);
-    ORBGPU_REQUIRE((size_t)slot_off < (1u << 23), "too many FAST key slots per frame");
-
-    e->geom = geom;
-    e->cells = cells;
-    {
-        StripGeom &bgm = e->blur_geom;
-        memset(&bgm, 0, sizeof(bgm));
-        bgm.nlevels = nl;
-        int acc = 0;
-        for (int l = 0; l < nl; l++) {
-            // 8-pixel strips (two dwords) start at padded dword 4 (bytes 16..19 hold image column 0) and must cover
-            // column w-1
-            const int nsx = ((geom[l].w + EDGE - 1) / 4 - 4 + 1 + 1) / 2;
-            const int nsy = (geom[l].h + BLUR_ROWS - 1) / BLUR_ROWS;
-            bgm.first[l] = acc;
-            bgm.nsx[l] = nsx;
-            acc += nsx * nsy;
-        }
-        for (int l = nl; l <= ORBGPU_MAX_LEVELS; l++)
-            bgm.first[l] = acc;
-    }
-    // k_fast_detect: bands (rows of cells) x dword columns, and what every dword column knows about the cell grid.  Built
-    // twice: every level a padded plane (strips = its aligned dwords from dword 9: image column 17), and with level 0 read
-    // from the image itself (direct mode: strips aligned to the image, from column 16)
-    std::vector<ColumnInfo> ctab;
-    for (int l = 0; l < nl; l++) {
-        const LevelGeom &g = geom[l];
-        int ncols_eff = 0;  // cell columns that are not skipped (ORBextractor.cc:797: iniX >= maxBorderX-6)
-        for (int j = 0; j < g.ncols; j++)
-            if (BORDER0 + j * g.wcell < g.max_bx - 6)
-                ncols_eff++;
-        const int nbands = (g.h - 2 * EDGE + g.hcell - 1) / g.hcell;  // bands with interior rows
-        ORBGPU_REQUIRE(ncols_eff > 0 && g.ncells % ncols_eff == 0 && nbands <= g.ncells / ncols_eff && ncols_eff < 255 &&
-                           g.ncells / ncols_eff < 256 && g.hcell < 128,
-                       "unexpected cell grid at level %d", l);
-        geom[l].ncols_eff = ncols_eff;
-        for (int which = 0; which < 2; which++) {
-            const int d = which ? g.hcell : g.wcell;
-            const uint32_t m = (uint32_t)(((1ull << 32) + (uint64_t)d - 1u) / (uint64_t)d);
-            for (uint32_t v = 0; v < 8192u; v++)
-                ORBGPU_REQUIRE((uint32_t)(((uint64_t)v * m) >> 32) == v / (uint32_t)d, "cell size %d at level %d has no exact reciprocal", d, l);
-            (which ? geom[l].inv_hcell : geom[l].inv_wcell) = m;
-        }
-    }
-    auto build_detect = [&](bool direct0, DetectGeom &dgm) -> bool {
-        memset(&dgm, 0, sizeof(dgm));
-        dgm.nlevels = nl;
-        int acc = 0;
-        for (int l = 0; l < nl; l++) {
-            const LevelGeom &g = geom[l];
-            const bool dir = direct0 && l == 0;
-            const int xfirst = dir ? 16 : 9 * 4 - EDGE;
-            // strips must reach the last scored column, w - 20 (padded planes: up to their aligned dword (w-1)/4)
-            const int nsx = dir ? (g.w - 20 - xfirst) / 4 + 1 : (g.w - 1) / 4 - 9 + 1;
-            const int nbands = (g.h - 2 * EDGE + g.hcell - 1) / g.hcell;
-            dgm.first[l] = acc;
-            dgm.nsx[l] = nsx;
-            dgm.ncols[l] = g.ncols_eff;
-            dgm.ctab_off[l] = (int)ctab.size();
-            dgm.xfirst[l] = xfirst;
-            acc += nsx * nbands;
-            if (dir)  // level 0's strips end on a wave boundary: a wave of k_fast_detect then reads ONE plane (image or pyramid)
-                acc = (acc + FD_OWN - 1) / FD_OWN * FD_OWN;
-            for (int sx = 0; sx < nsx; sx++) {
-                ColumnInfo c{0u, 0u};
-                for (int p = 0; p < 4; p++) {
-                    const int x = xfirst + 4 * sx + p;  // image column
-                    int j = 0xFF;
-                    if (x >= EDGE && x < g.w - EDGE) {
-                        j = (x - EDGE) / g.wcell;
-                        const int xs = EDGE + j * g.wcell, xe = std::min(xs + g.wcell, g.w - EDGE);  // interior [xs, xe)
-                        if (j < g.ncols_eff) {
-                            c.flags |= 1u << p;
-                            if (x == xs)
-                                c.flags |= 16u << p;
-                            if (x == xe - 1)
-                                c.flags |= 256u << p;
-                        } else
-                            j = 0xFF;
-                    }
-                    c.cellj |= (uint32_t)j << (8 * p);
-                }
-                ctab.push_back(c);
-            }
-        }
-        for (int l = nl; l <= ORBGPU_MAX_LEVELS; l++)
-            dgm.first[l] = acc;
-        // the key emission of k_fast_detect addresses per-wave counters with (cell id mod FD_CELLS): the cells of the
-        // columns a wave owns must be a range of at most FD_CELLS consecutive ids
-        std::vector<std::pair<int, int>> strip_cells;  // per flat strip: lowest / highest cell id (-1: none)
-        for (int l = 0; l < nl; l++) {
-            const LevelGeom &g = geom[l];
-            const int nbands = (g.h - 2 * EDGE + g.hcell - 1) / g.hcell;
-            strip_cells.resize((size_t)dgm.first[l], {-1, -1});  // (the padding strips in front of this level)
-            for (int b = 0; b < nbands; b++)
-                for (int sx = 0; sx < dgm.nsx[l]; sx++) {
-                    const ColumnInfo &c = ctab[dgm.ctab_off[l] + sx];
-                    int lo = -1, hi = -1;
-                    for (int p = 0; p < 4; p++)
-                        if ((c.flags >> p) & 1u) {
-                            const int id = g.cell_first + b * dgm.ncols[l] + (int)((c.cellj >> (8 * p)) & 255u);
-                            lo = lo < 0 ? id : std::min(lo, id);
-                            hi = std::max(hi, id);
-                        }
-                    strip_cells.push_back({lo, hi});
-                }
-        }
-        for (size_t w0 = 0; w0 < strip_cells.size(); w0 += FD_OWN) {
-            int lo = -1, hi = -1;
-            for (size_t q = w0; q < std::min(w0 + FD_OWN, strip_cells.size()); q++)
-                if (strip_cells[q].first >= 0) {
-                    lo = lo < 0 ? strip_cells[q].first : std::min(lo, strip_cells[q].first);
-                    hi = std::max(hi, strip_cells[q].second);
-                }
-            if (hi - lo >= FD_CELLS)
-                return false;
-        }
-        return true;
+    const size_t B = (size_t)batch, nl = (size_t)e->nlevels;
+    // per frame: cell counters, then one stored-key counter per level
+    const size_t cellcnt_bytes = sizeof(int) * ((size_t)plan.ncells + ORBGPU_MAX_LEVELS) * B;
+    const std::pair<DevBuf *, size_t> reservations[] = {
+        {&e->d_tables, plan.blob.size()},
+        {&e->d_pyr, plan.frame_pyr * B},
+        {&e->d_blur, plan.frame_pyr * B},
+        {&e->d_slots, sizeof(uint32_t) * plan.frame_slots * B},
+        {&e->d_cellcnt, cellcnt_bytes},
+        {&e->d_dkey, sizeof(uint32_t) * plan.frame_slots * B},
+        {&e->d_dnode, sizeof(uint16_t) * plan.frame_slots * B},
+        {&e->d_sel, sizeof(uint32_t) * (size_t)plan.sel_cap_total * B},
+        {&e->d_nsel, sizeof(int) * nl * B},
+        {&e->d_ncand, sizeof(int) * nl * B},
+        {&e->d_qtaux, sizeof(int) * QT_AUX_FRAME * QT_BATCH_MIN},
     };
-    ORBGPU_REQUIRE(build_detect(false, e->det_geom), "image too small for the FAST kernel's cell bookkeeping (more than %d cells in one wave)", FD_CELLS);
-    if (direct_ok)
-        direct_ok = build_detect(true, e->det_geom_direct);
-    e->direct0_ok = direct_ok;
-    e->rs_off_direct = rs_off_direct;
-    for (int l = 0; l < ORBGPU_MAX_LEVELS; l++)
-        e->r8_off[l] = l >= 1 && l < nl && rlev[l].fast8 ? rlev[l].r8_off : -1;
-    e->r8_off_direct = direct_ok && rdirect.fast8 ? rdirect.r8_off : -1;
-    for (int l = 0; l < ORBGPU_MAX_LEVELS; l++)
-        e->r8_share[l] = l >= 1 && l < nl && rlev[l].share8;
-    e->r8_share_direct = rdirect.share8;
-    e->interior_resize = false;
-    for (int l = 1; l < nl; l++)
-        e->interior_resize = e->interior_resize || geom[l].rs_fast != 0;
-    e->borders_materialized = true;
-    e->geom = geom;  // (with the cell-grid fields filled in above)
-    // k_border0_fast: per aligned dword of the padded level-0 row, the two adjacent source dwords and the byte selector
-    std::vector<BorderCol> bcol;
-    if (w % 4 == 0 && w >= 8) {
-        const LevelGeom &g0 = geom[0];
-        for (int c = 0; c < g0.pitch / 4; c++) {
-            int sx[4], lo = 1 << 30, hi = 0;
-            for (int k = 0; k < 4; k++) {
-                sx[k] = reflect101(std::min(c * 4 + k, g0.w + 2 * EDGE - 1) - EDGE, g0.w);
-                lo = std::min(lo, sx[k]);
-                hi = std::max(hi, sx[k]);
-            }
-            const int d = std::min(lo / 4, g0.w / 4 - 2);  // src[d + 1] stays inside the row
-            ORBGPU_REQUIRE(hi < d * 4 + 8 && lo >= d * 4, "level-0 border table: span of column %d", c);
-            BorderCol bc{(uint32_t)d, 0u};
-            for (int k = 0; k < 4; k++)
-                bc.sel |= (uint32_t)(sx[k] - d * 4) << (8 * k);  // bytes 0..3 = src[d], 4..7 = src[d+1]
-            bcol.push_back(bc);
-        }
-    }
-    e->frame_pyr = plane_off;
-    e->frame_slots = (size_t)slot_off;
-    e->sel_cap_total = sel_off;
-    e->ncap = ncap;
-    e->qt_lds = qt_lds;
-    e->qt_kcap = qt_kcap;
-    e->max_slots_level = max_slots_level;
-    e->qt_prefilter = !e->qt_no_prefilter;
-    for (int l = 0; l < nl; l++)
-        e->qt_prefilter = e->qt_prefilter && geom[l].n_ini <= QT_INI_MAX;
-    int max_kp = 0;
-    for (int l = 0; l < nl; l++)
-        max_kp += geom[l].sel_cap - 1;
-    e->max_kp = max_kp;
-
-    int rc;
-#define RSV(buf, n) if ((rc = (buf).reserve(n)) != ORBGPU_OK) return rc
-    RSV(e->d_geom, sizeof(LevelGeom) * nl);
-    RSV(e->d_cells, sizeof(CellDesc) * cells.size());
-    RSV(e->d_ctab, sizeof(ColumnInfo) * ctab.size());
-    RSV(e->d_bcol, sizeof(BorderCol) * std::max<size_t>(bcol.size(), 1));
-    RSV(e->d_xtab, sizeof(XTab) * std::max<size_t>(xtab.size(), 1));
-    RSV(e->d_ytab, sizeof(YTab) * std::max<size_t>(ytab.size(), 1));
-    RSV(e->d_yrow, sizeof(YRow) * std::max<size_t>(yrow.size(), 1));
-    RSV(e->d_rstrip, sizeof(ResizeStrip) * std::max<size_t>(rstrip.size(), 1));
-    RSV(e->d_rsel, sizeof(uint4) * std::max<size_t>(rsel.size(), 1));
-    RSV(e->d_rwt, sizeof(uint4) * std::max<size_t>(rwt.size(), 1));
-    RSV(e->d_r8item, sizeof(uint32_t) * std::max<size_t>(rt.item8.size(), 1));
-    RSV(e->d_r8sel, sizeof(RsQuad) * std::max<size_t>(rt.sel8.size(), 1));
-    RSV(e->d_r8wt, sizeof(RsQuad) * std::max<size_t>(rt.wt8.size(), 1));
-    RSV(e->d_pattern, 1024 + 2 * 4 * 16 * 9 * sizeof(uint32_t));  // rBRIEF pattern, then k_orient's weight tables
-    const size_t B = (size_t)batch;
-    RSV(e->d_pyr, e->frame_pyr * B);
-    RSV(e->d_blur, e->frame_pyr * B);
-    RSV(e->d_slots, sizeof(uint32_t) * e->frame_slots * B);
-    RSV(e->d_cellcnt, sizeof(int) * (cells.size() + ORBGPU_MAX_LEVELS) * B);  // per frame: cell counters, then one stored-key counter per level
-    RSV(e->d_dkey, sizeof(uint32_t) * e->frame_slots * B);
-    RSV(e->d_dnode, sizeof(uint16_t) * e->frame_slots * B);
-    RSV(e->d_sel, sizeof(uint32_t) * (size_t)sel_off * B);
-    RSV(e->d_nsel, sizeof(int) * nl * B);
-    RSV(e->d_ncand, sizeof(int) * nl * B);
-    RSV(e->d_qtaux, sizeof(int) * QT_AUX_FRAME * QT_BATCH_MIN);
-#undef RSV
+    for (const auto &r : reservations)
+        if ((rc = r.first->reserve(r.second)) != ORBGPU_OK)
+            return rc;
     // Tables and initial values go through the handle's OWN stream and are waited for below.  The synchronous forms are
     // not a substitute: hipMemset (like cudaMemset) is asynchronous with respect to the host and runs on the null stream,
     // which the handle's non-blocking stream is not ordered with -- under load (several host threads making their first
     // calls at once) the zeroing of the blurred planes and of the cell counters arrived AFTER k_blur / k_fast_detect had
     // written them: descriptors of zeros, wrong key points, once a memory fault (round 4, tools/stress_first_calls.py).
-    ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_geom.p, geom.data(), sizeof(LevelGeom) * nl, hipMemcpyHostToDevice, e->stream));
-    ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_cells.p, cells.data(), sizeof(CellDesc) * cells.size(), hipMemcpyHostToDevice, e->stream));
-    ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_ctab.p, ctab.data(), sizeof(ColumnInfo) * ctab.size(), hipMemcpyHostToDevice, e->stream));
-    if (!bcol.empty())
-        ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_bcol.p, bcol.data(), sizeof(BorderCol) * bcol.size(), hipMemcpyHostToDevice, e->stream));
-    e->border_fast = !bcol.empty();
-    if (!xtab.empty()) {
-        ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_xtab.p, xtab.data(), sizeof(XTab) * xtab.size(), hipMemcpyHostToDevice, e->stream));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_ytab.p, ytab.data(), sizeof(YTab) * ytab.size(), hipMemcpyHostToDevice, e->stream));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_yrow.p, yrow.data(), sizeof(YRow) * yrow.size(), hipMemcpyHostToDevice, e->stream));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_rstrip.p, rstrip.data(), sizeof(ResizeStrip) * rstrip.size(), hipMemcpyHostToDevice, e->stream));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_rsel.p, rsel.data(), sizeof(uint4) * rsel.size(), hipMemcpyHostToDevice, e->stream));
-        ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_rwt.p, rwt.data(), sizeof(uint4) * rwt.size(), hipMemcpyHostToDevice, e->stream));
-        if (!rt.item8.empty()) {
-            ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_r8item.p, rt.item8.data(), sizeof(uint32_t) * rt.item8.size(), hipMemcpyHostToDevice, e->stream));
-            ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_r8sel.p, rt.sel8.data(), sizeof(RsQuad) * rt.sel8.size(), hipMemcpyHostToDevice, e->stream));
-            ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_r8wt.p, rt.wt8.data(), sizeof(RsQuad) * rt.wt8.size(), hipMemcpyHostToDevice, e->stream));
-        }
-    }
-    ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_pattern.p, k_pattern_host, 1024, hipMemcpyHostToDevice, e->stream));
-    {
-        // k_orient's byte-weight tables per (alignment a of the disc's first column, |v|, dword j of the 9-dword row):
-        // W10 holds u + 16 inside the disc (0 outside), M01 holds 1 inside the disc
-        std::vector<uint32_t> orw(2 * 4 * 16 * 9, 0u);
-        for (int i = 0; i < 4 * 16 * 9; i++) {
-            const int a = i / (16 * 9), av = (i / 9) % 16, j = i % 9;
-            for (int k = 0; k < 4; k++) {
-                const int u = 4 * j + k - a - HALF_PATCH;
-                if (std::abs(u) <= e->umax.v[av]) {
-                    orw[i] |= (uint32_t)(u + 16) << (8 * k);
-                    orw[4 * 16 * 9 + i] |= 1u << (8 * k);
-                }
-            }
-        }
-        ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_pattern.as<uint8_t>() + 1024, orw.data(), orw.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-        ORBGPU_HIP_TRY(hipStreamSynchronize(e->stream));  // (orw leaves scope)
-    }
+    ORBGPU_HIP_TRY(hipMemcpyAsync(e->d_tables.p, plan.blob.data(), plan.blob.size(), hipMemcpyHostToDevice, e->stream));
     // the blurred planes are only written inside the image; define the rest once
-    ORBGPU_HIP_TRY(hipMemsetAsync(e->d_blur.p, 0, e->frame_pyr * B, e->stream));
+    ORBGPU_HIP_TRY(hipMemsetAsync(e->d_blur.p, 0, plan.frame_pyr * B, e->stream));
     // cell counters start at zero; k_quadtree re-arms them after reading
-    ORBGPU_HIP_TRY(hipMemsetAsync(e->d_cellcnt.p, 0, sizeof(int) * (cells.size() + ORBGPU_MAX_LEVELS) * B, e->stream));
+    ORBGPU_HIP_TRY(hipMemsetAsync(e->d_cellcnt.p, 0, cellcnt_bytes, e->stream));
     ORBGPU_HIP_TRY(hipMemsetAsync(e->d_qtaux.p, 0, e->d_qtaux.bytes, e->stream));  // likewise (k_quadtree<true> re-arms what it reads)
-    ORBGPU_HIP_TRY(hipStreamSynchronize(e->stream));  // ... before any stream (the caller's, for the device entry points) reads them
+    // ... before any stream (the caller's, for the device entry points) reads them, and before `plan` may move
+    ORBGPU_HIP_TRY(hipStreamSynchronize(e->stream));
     // The attribute belongs to the function (per device), not to this handle: another handle with a larger geometry may
     // have raised it and still launch, so it is set once to the most the kernel can ever be launched with here
-    // (qt_lds <= 159 KB and qt_lds + 6 qt_kcap <= 150 KB are enforced above; the static part is < 200 B).
+    // (qt_lds <= 159 KB and qt_lds + 6 qt_kcap <= 150 KB are enforced by the plan; the static part is < 200 B).
     ORBGPU_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_quadtree<false>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, QT_LDS_MAX));
     ORBGPU_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_quadtree<true>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, QT_LDS_MAX));
-    e->cfg_w = w;
-    e->cfg_h = h;
+    e->plan = std::move(plan);
     e->cfg_batch = batch;
     return ORBGPU_OK;
 }
@@ -3049,33 +2576,30 @@ private:
 // not aligned for direct mode; otherwise only when mvImagePyramid[0] is asked for (the getters below).
 static int materialize_level0(orbgpu_extractor *e, const Src0 &s0, int batch, Launcher &L)
 {
-    const LevelGeom &g = e->geom[0];
-    const LevelGeom *dg = e->d_geom.as<LevelGeom>();
+    const LevelGeom &g = e->plan.geom[0];
+    const LevelGeom *dg = e->d_geom();
     uint8_t *pyr = e->d_pyr.as<uint8_t>();
     const size_t stride = s0.pitch;
-    if (e->border_fast && stride % 4 == 0 && s0.frame_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(s0.p) & 3) == 0) {
+    if (e->plan.border_fast && stride % 4 == 0 && s0.frame_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(s0.p) & 3) == 0) {
         dim3 gridf(((g.pitch / 16) * ((g.h + 2 * EDGE + BORDER_ROWS - 1) / BORDER_ROWS) + 255) / 256, batch);
-        L.launch(k_border0_fast, gridf, dim3(256), 0, s0.p, stride, s0.frame_stride, pyr, e->frame_pyr, dg,
-                           e->d_bcol.as<BorderCol>());
+        L.launch(k_border0_fast, gridf, dim3(256), 0, s0.p, stride, s0.frame_stride, pyr, e->plan.frame_pyr, dg,
+                           e->tab<BorderCol>(e->plan.t_bcol));
     } else {
         dim3 grid(((g.pitch / 4) * ((g.h + 2 * EDGE + PYR_ROWS - 1) / PYR_ROWS) + 255) / 256, batch);
-        L.launch(k_border0, grid, dim3(256), 0, s0.p, stride, s0.frame_stride, pyr, e->frame_pyr, dg);
+        L.launch(k_border0, grid, dim3(256), 0, s0.p, stride, s0.frame_stride, pyr, e->plan.frame_pyr, dg);
     }
     if (!L.graph)
         ORBGPU_HIP_TRY(hipGetLastError());
     return ORBGPU_OK;
 }
 
-// REFLECT_101 frame of `ring` pixels around the interiors k_resize_fast wrote (levels >= 1)
-static void launch_ring_fill(orbgpu_extractor *e, int batch, Launcher &L, int ring)
+// REFLECT_101 frame of EDGE pixels around the interiors k_resize_fast wrote (levels >= 1)
+static void launch_ring_fill(orbgpu_extractor *e, int batch, Launcher &L)
 {
-    RingGeom rg = {};
-    rg.nlevels = e->nlevels;
-    for (int l = 1; l < e->nlevels; l++)
-        rg.first[l + 1] = rg.first[l] + 2 * ring * (e->geom[l].w + 2 * ring) + 2 * ring * e->geom[l].h;
+    const RingGeom &rg = e->plan.ring_full;
     if (rg.first[e->nlevels] > 0)
         L.launch(k_ring_fill, dim3((rg.first[e->nlevels] + 255) / 256, batch), dim3(256), 0, e->d_pyr.as<uint8_t>(),
-                 e->frame_pyr, e->d_geom.as<LevelGeom>(), rg, ring);
+                 e->plan.frame_pyr, e->d_geom(), rg, EDGE);
 }
 
 // the blur of all levels: one launch, or -- direct mode -- level 0 from the image (k_blur0_direct) + the other levels
@@ -3083,21 +2607,21 @@ static void launch_ring_fill(orbgpu_extractor *e, int batch, Launcher &L, int ri
 static void launch_blur(orbgpu_extractor *e, const Src0 &s0, int batch, Launcher &L, int which = 0)
 {
     const int nl = e->nlevels;
-    const LevelGeom *dg = e->d_geom.as<LevelGeom>();
+    const LevelGeom *dg = e->d_geom();
     uint8_t *pyr = e->d_pyr.as<uint8_t>(), *blur = e->d_blur.as<uint8_t>();
     int strip0 = 0;
     if (s0.direct) {
-        const LevelGeom &g = e->geom[0];
+        const LevelGeom &g = e->plan.geom[0];
         const int nstrips = (g.w / 8) * ((g.h + BLUR_ROWS - 1) / BLUR_ROWS);
         if (which != 2)
-            L.launch(k_blur0_direct, dim3((nstrips + 255) / 256, batch), dim3(256), 0, s0, blur, e->frame_pyr, dg);
-        strip0 = e->blur_geom.first[1];
+            L.launch(k_blur0_direct, dim3((nstrips + 255) / 256, batch), dim3(256), 0, s0, blur, e->plan.frame_pyr, dg);
+        strip0 = e->plan.blur_geom.first[1];
     }
     if (which == 1)
         return;
-    if (e->blur_geom.first[nl] > strip0)
-        L.launch(k_blur, dim3((e->blur_geom.first[nl] - strip0 + 255) / 256, batch), dim3(256), 0, pyr, blur,
-                           e->frame_pyr, dg, e->blur_geom, strip0);
+    if (e->plan.blur_geom.first[nl] > strip0)
+        L.launch(k_blur, dim3((e->plan.blur_geom.first[nl] - strip0 + 255) / 256, batch), dim3(256), 0, pyr, blur,
+                           e->plan.frame_pyr, dg, e->plan.blur_geom, strip0);
 }
 
 static int launch_pipeline(orbgpu_extractor *e, const uint8_t *d_gray, int batch, int w, int h, size_t stride,
@@ -3106,7 +2630,7 @@ static int launch_pipeline(orbgpu_extractor *e, const uint8_t *d_gray, int batch
 {
     hipStream_t st = L.st;  // (events and the side stream below: plain launches only)
     const int nl = e->nlevels;
-    const LevelGeom *dg = e->d_geom.as<LevelGeom>();
+    const LevelGeom *dg = e->d_geom();
     uint8_t *pyr = e->d_pyr.as<uint8_t>();
     uint8_t *blur = e->d_blur.as<uint8_t>();
     int rc = e->d_aux.reserve(sizeof(KpAux) * (size_t)cap * batch);
@@ -3137,15 +2661,13 @@ static int launch_pipeline(orbgpu_extractor *e, const uint8_t *d_gray, int batch
     // ... and a batch: for a handful of frames the kernels are latency-bound, the traffic direct mode saves is served from
     // L2 anyway, and its second blur launch costs more (0.030 against 0.016 ms for one 640x480 frame) than the border kernel
     // it removes (0.036 against 0.039 ms); ORBGPU_DEBUG_DIRECT0_MIN overrides the threshold (tests run batch 1 - 3 in direct mode)
-    const bool direct = e->direct0_ok && !e->no_direct0 && aligned4 && batch >= e->direct0_min_batch;
+    const bool direct = e->plan.direct0_ok && !e->no_direct0 && aligned4 && batch >= e->direct0_min_batch;
     const Src0 s0{d_gray, frame_stride, (uint32_t)stride, direct ? 1 : 0};
-    e->last_src = s0;
-    e->level0_materialized = !direct;
-    e->borders_materialized = !e->interior_resize;
+    note_call(e, s0, batch, cap);
     if (e->poison_pyramid) {  // a stage that reads a pixel this call does not write reads 0xA5
-        int rcp = L.memset32(pyr, e->frame_pyr * batch, 0xA5);
+        int rcp = L.memset32(pyr, e->plan.frame_pyr * batch, 0xA5);
         if (rcp == ORBGPU_OK)
-            rcp = L.memset32(blur, e->frame_pyr * batch, 0xA5);
+            rcp = L.memset32(blur, e->plan.frame_pyr * batch, 0xA5);
         if (rcp != ORBGPU_OK)
             return rcp;
     }
@@ -3169,35 +2691,26 @@ static int launch_pipeline(orbgpu_extractor *e, const uint8_t *d_gray, int batch
                 return rcb;
         }
         for (int l = 1; l < nl; l++) {
-            const LevelGeom &gl = e->geom[l];
-            dim3 gr((gl.pitch / 4 + 255) / 256, gl.h + 2 * EDGE, batch);
-            // rows per thread: 8 on the large levels; the small ones of a few frames get more (shorter) threads to hide
-            // latency with.  A batch has threads enough: every level takes full items and keeps its horizontal passes.
-            const int ndw_l = (gl.pitch / 4) * (gl.h + 2 * EDGE);
-            const int rows = batch >= PYR_BATCH_MIN || ndw_l >= 32768 ? PYR_ROWS : ndw_l >= 16384 ? PYR_ROWS / 2 : PYR_ROWS / 4;
-            dim3 grf((resize_ndw(gl.w) * ((gl.h + rows - 1) / rows) + 255) / 256, batch);
-            if (gl.rs_fast) {
-                const bool dir1 = direct && l == 1;  // level 1 straight from the image
-                // a batch: eight pixels per item where the level's taps fit the 16-byte window (resize_tables.h)
-                const int r8 = batch >= PYR_BATCH_MIN ? (dir1 ? e->r8_off_direct : e->r8_off[l]) : -1;
-                if (r8 >= 0) {
-                    dim3 gr8((resize_n8(gl.w) * ((gl.h + PYR_ROWS - 1) / PYR_ROWS) + 255) / 256, batch);
-                    const bool shr = dir1 ? e->r8_share_direct : e->r8_share[l];
-                    L.launch(dir1 ? (shr ? k_resize_fast<true, true, 8, true> : k_resize_fast<true, true, 8, false>)
-                                  : (shr ? k_resize_fast<true, false, 8, true> : k_resize_fast<true, false, 8, false>), gr8, dim3(256), 0, pyr,
-                             e->frame_pyr, dg, l, e->d_r8item.as<ResizeStrip>(), e->d_r8sel.as<uint4>(), e->d_r8wt.as<uint4>(),
-                             e->d_yrow.as<YRow>(), r8, PYR_ROWS, s0);
-                    continue;
-                }
-                auto kern = dir1 ? (rows == PYR_ROWS ? k_resize_fast<true, true, 4> : k_resize_fast<false, true, 4>)
-                                 : (rows == PYR_ROWS ? k_resize_fast<true, false, 4> : k_resize_fast<false, false, 4>);
-                L.launch(kern, grf, dim3(256), 0, pyr, e->frame_pyr, dg, l, e->d_rstrip.as<ResizeStrip>(),
-                                   e->d_rsel.as<uint4>(), e->d_rwt.as<uint4>(), e->d_yrow.as<YRow>(),
-                                   dir1 ? e->rs_off_direct : gl.rs_off, rows, s0);
+            const LevelGeom &gl = e->plan.geom[l];
+            const ResizeLaunch rl = resize_launch(e->plan, l, batch, direct);  // the form the level takes (extractor_plan.h)
+            if (rl.px == 8) {
+                dim3 gr8((resize_n8(gl.w) * ((gl.h + rl.rows - 1) / rl.rows) + 255) / 256, batch);
+                L.launch(rl.dir1 ? (rl.share ? k_resize_fast<true, true, 8, true> : k_resize_fast<true, true, 8, false>)
+                                 : (rl.share ? k_resize_fast<true, false, 8, true> : k_resize_fast<true, false, 8, false>), gr8, dim3(256), 0, pyr,
+                         e->plan.frame_pyr, dg, l, e->tab<ResizeStrip>(e->plan.t_r8item), e->tab<uint4>(e->plan.t_r8sel), e->tab<uint4>(e->plan.t_r8wt),
+                         e->tab<YRow>(e->plan.t_yrow), rl.off, rl.rows, s0);
+            } else if (rl.px == 4) {
+                dim3 grf((resize_ndw(gl.w) * ((gl.h + rl.rows - 1) / rl.rows) + 255) / 256, batch);
+                auto kern = rl.dir1 ? (rl.rows == PYR_ROWS ? k_resize_fast<true, true, 4> : k_resize_fast<false, true, 4>)
+                                    : (rl.rows == PYR_ROWS ? k_resize_fast<true, false, 4> : k_resize_fast<false, false, 4>);
+                L.launch(kern, grf, dim3(256), 0, pyr, e->plan.frame_pyr, dg, l, e->tab<ResizeStrip>(e->plan.t_rstrip),
+                                   e->tab<uint4>(e->plan.t_rsel), e->tab<uint4>(e->plan.t_rwt), e->tab<YRow>(e->plan.t_yrow),
+                                   rl.off, rl.rows, s0);
+            } else {
+                dim3 gr((gl.pitch / 4 + 255) / 256, gl.h + 2 * EDGE, batch);
+                L.launch(k_resize_level, gr, dim3(256), 0, pyr, e->plan.frame_pyr, dg, l,
+                                   e->tab<XTab>(e->plan.t_xtab), e->tab<YTab>(e->plan.t_ytab));
             }
-            else
-                L.launch(k_resize_level, gr, dim3(256), 0, pyr, e->frame_pyr, dg, l,
-                                   e->d_xtab.as<XTab>(), e->d_ytab.as<YTab>());
         }
     }
     END(ST_PYRAMID, st);
@@ -3229,32 +2742,28 @@ static int launch_pipeline(orbgpu_extractor *e, const uint8_t *d_gray, int batch
     e->counters_dirty = true;
     {
         const int t_ini = std::max(e->prm.ini_th_fast, 1), t_min = std::max(e->prm.min_th_fast, 1);
-        const DetectGeom &dgeo = direct ? e->det_geom_direct : e->det_geom;
+        const DetectGeom &dgeo = direct ? e->plan.det_geom_direct : e->plan.det_geom;
         const int nwaves = (dgeo.first[nl] + FD_OWN - 1) / FD_OWN;
-        L.launch(e->fast_early_out ? k_fast_detect<true> : k_fast_detect<false>, dim3((nwaves + 3) / 4, batch), dim3(256), 0, pyr, e->frame_pyr, dg,
-                           dgeo, e->d_ctab.as<ColumnInfo>(), e->d_cells.as<CellDesc>(), (int)e->cells.size(),
-                           e->d_slots.as<uint32_t>(), e->frame_slots, e->d_cellcnt.as<int>(), std::min(t_ini, t_min),
+        L.launch(e->fast_early_out ? k_fast_detect<true> : k_fast_detect<false>, dim3((nwaves + 3) / 4, batch), dim3(256), 0, pyr, e->plan.frame_pyr, dg,
+                           dgeo, e->tab<ColumnInfo>(e->plan.t_ctab), e->tab<CellDesc>(e->plan.t_cells), e->plan.ncells,
+                           e->d_slots.as<uint32_t>(), e->plan.frame_slots, e->d_cellcnt.as<int>(), std::min(t_ini, t_min),
                            t_ini, e->fast_queue_cap, s0);
     }
     END(ST_FAST, st);
     BEGIN(ST_QUADTREE, st);
-    if (batch >= QT_BATCH_MIN || e->force_batch_quadtree)
-        L.launch(k_quadtree<false>, dim3(batch, nl), dim3(QT_THREADS_BATCH), e->qt_lds, dg,
-                           e->d_cells.as<CellDesc>(), (int)e->cells.size(), e->d_slots.as<uint32_t>(), e->frame_slots,
-                           e->d_cellcnt.as<int>(), e->d_dkey.as<uint32_t>(), e->d_dnode.as<uint16_t>(),
-                           e->d_sel.as<uint32_t>(), e->sel_cap_total, e->d_nsel.as<int>(), e->d_ncand.as<int>(), nl,
-                           e->ncap, std::max(e->prm.ini_th_fast, 1), 0, qt_dbg(), (int *)nullptr);
-    else {
-        // the filtering / counting sweep over the stored keys of every level first, spread over the device
-        if (e->qt_prefilter)
-            L.launch(k_qt_prefilter, dim3(std::min((e->max_slots_level + QT_PRE_KEYS - 1) / QT_PRE_KEYS, QT_PRE_GRID), nl, batch), dim3(256), 0, dg, (int)e->cells.size(), e->d_slots.as<uint32_t>(), e->frame_slots, e->d_cellcnt.as<int>(),
+    {
+        const QuadtreeLaunch ql = quadtree_launch(e->plan, batch, e->force_batch_quadtree);  // extractor_plan.h
+        // single frames: the filtering / counting sweep over the stored keys of every level first, spread over the device
+        const bool pre = ql.lds_keys && e->plan.qt_prefilter;
+        if (pre)
+            L.launch(k_qt_prefilter, dim3(std::min((e->plan.max_slots_level + QT_PRE_KEYS - 1) / QT_PRE_KEYS, QT_PRE_GRID), nl, batch), dim3(256), 0, dg, e->plan.ncells, e->d_slots.as<uint32_t>(), e->plan.frame_slots, e->d_cellcnt.as<int>(),
                                e->d_dkey.as<uint32_t>(), e->d_qtaux.as<int>(), std::max(e->prm.ini_th_fast, 1));
-        L.launch(k_quadtree<true>, dim3(batch, nl), dim3(w * h >= QT_LARGE_PIXELS ? QT_THREADS : QT_THREADS_SMALL), e->qt_lds + (size_t)e->qt_kcap * 6, dg,
-                           e->d_cells.as<CellDesc>(), (int)e->cells.size(), e->d_slots.as<uint32_t>(), e->frame_slots,
+        L.launch(ql.lds_keys ? k_quadtree<true> : k_quadtree<false>, dim3(batch, nl), dim3(ql.threads), ql.lds_bytes, dg,
+                           e->tab<CellDesc>(e->plan.t_cells), e->plan.ncells, e->d_slots.as<uint32_t>(), e->plan.frame_slots,
                            e->d_cellcnt.as<int>(), e->d_dkey.as<uint32_t>(), e->d_dnode.as<uint16_t>(),
-                           e->d_sel.as<uint32_t>(), e->sel_cap_total, e->d_nsel.as<int>(), e->d_ncand.as<int>(), nl,
-                           e->ncap, std::max(e->prm.ini_th_fast, 1), e->qt_kcap, qt_dbg(),
-                           e->qt_prefilter ? e->d_qtaux.as<int>() : (int *)nullptr);
+                           e->d_sel.as<uint32_t>(), e->plan.sel_cap_total, e->d_nsel.as<int>(), e->d_ncand.as<int>(), nl,
+                           e->plan.ncap, std::max(e->prm.ini_th_fast, 1), ql.kcap, qt_dbg(),
+                           pre ? e->d_qtaux.as<int>() : (int *)nullptr);
     }
     if (!rec)
         ORBGPU_HIP_TRY(hipGetLastError());
@@ -3262,18 +2771,18 @@ static int launch_pipeline(orbgpu_extractor *e, const uint8_t *d_gray, int batch
     END(ST_QUADTREE, st);
     BEGIN(ST_ORIENT, st);
     const int or_iters = batch >= OR_BATCH_MIN ? OR_ITERS : 1;
-    L.launch(k_orient, dim3((e->sel_cap_total + 8 * or_iters - 1) / (8 * or_iters), batch), dim3(256), 0, pyr, e->frame_pyr, dg, nl,
-                       e->d_sel.as<uint32_t>(), e->sel_cap_total, e->d_nsel.as<int>(),
-                       reinterpret_cast<const uint32_t *>(e->d_pattern.as<uint8_t>() + 1024), d_kps,
+    L.launch(k_orient, dim3((e->plan.sel_cap_total + 8 * or_iters - 1) / (8 * or_iters), batch), dim3(256), 0, pyr, e->plan.frame_pyr, dg, nl,
+                       e->d_sel.as<uint32_t>(), e->plan.sel_cap_total, e->d_nsel.as<int>(),
+                       e->tab<uint32_t>(e->plan.t_orient), d_kps,
                        e->d_aux.as<KpAux>(), cap, d_n_out, or_iters, s0);
-    L.launch(k_trig, dim3((std::min(cap, e->max_kp) + 255) / 256, batch), dim3(256), 0,
+    L.launch(k_trig, dim3((std::min(cap, e->plan.max_kp) + 255) / 256, batch), dim3(256), 0,
                        e->d_aux.as<KpAux>(), d_n_out, cap, e->trig);
     END(ST_ORIENT, st);
     BEGIN(ST_DESCRIBE, st);
     if (side_blur)
         ORBGPU_HIP_TRY(hipStreamWaitEvent(st, e->ev_join, 0));  // join: the descriptors read the blurred planes
-    L.launch(k_describe, dim3((std::min(cap, e->max_kp) + 7) / 8, batch), dim3(256), 0, blur,
-                       e->frame_pyr, dg, e->d_aux.as<KpAux>(), d_n_out, cap, e->d_pattern.as<int8_t>(), d_desc);
+    L.launch(k_describe, dim3((std::min(cap, e->plan.max_kp) + 7) / 8, batch), dim3(256), 0, blur,
+                       e->plan.frame_pyr, dg, e->d_aux.as<KpAux>(), d_n_out, cap, e->tab<int8_t>(e->plan.t_pattern), d_desc);
     END(ST_DESCRIBE, st);
 #undef BEGIN
 #undef END
@@ -3285,8 +2794,6 @@ static int launch_pipeline(orbgpu_extractor *e, const uint8_t *d_gray, int batch
     }
     if (prof)
         e->prof_calls++;
-    e->last_batch = batch;
-    e->last_cap = cap;
     (void)w;
     (void)h;
     return ORBGPU_OK;
@@ -3307,12 +2814,12 @@ int extractor_pyramid_view(const orbgpu_extractor *e, PyramidView *v)
     v->device_id = e->prm.device_id;
     v->nlevels = e->nlevels;
     v->scale_factor = e->prm.scale_factor;
-    v->last_batch = (int)e->geom.size() == e->nlevels ? e->last_batch : 0;
+    v->last_batch = (int)e->plan.geom.size() == e->nlevels ? e->last.batch : 0;
     for (int l = 0; l < e->nlevels; l++) {
-        v->scale[l] = e->scale[l];
-        v->inv_scale[l] = e->inv_scale[l];
+        v->scale[l] = e->consts.scale[l];
+        v->inv_scale[l] = e->consts.inv_scale[l];
         if (v->last_batch > 0) {
-            const LevelGeom &g = e->geom[l];
+            const LevelGeom &g = e->plan.geom[l];
             v->w[l] = g.w;
             v->h[l] = g.h;
             v->pitch[l] = g.pitch;
@@ -3320,12 +2827,12 @@ int extractor_pyramid_view(const orbgpu_extractor *e, PyramidView *v)
         }
     }
     v->pyr = e->d_pyr.as<uint8_t>();
-    v->frame_pyr = e->frame_pyr;
+    v->frame_pyr = e->plan.frame_pyr;
     v->border = EDGE;
-    v->direct = v->last_batch > 0 && e->last_src.direct ? 1 : 0;
-    v->l0 = v->direct ? e->last_src.p : nullptr;
-    v->l0_frame_stride = v->direct ? e->last_src.frame_stride : 0;
-    v->l0_pitch = v->direct ? e->last_src.pitch : 0;
+    v->direct = v->last_batch > 0 && e->last.src.direct ? 1 : 0;
+    v->l0 = v->direct ? e->last.src.p : nullptr;
+    v->l0_frame_stride = v->direct ? e->last.src.frame_stride : 0;
+    v->l0_pitch = v->direct ? e->last.src.pitch : 0;
     v->scratch = &e->d_stereo;
     return ORBGPU_OK;
 }
@@ -3333,6 +2840,34 @@ int extractor_pyramid_view(const orbgpu_extractor *e, PyramidView *v)
 } // namespace orbgpu
 
 extern "C" {
+
+// Everything a handle owns, in whatever state its creation or its calls left it (orbgpu_extractor_create's failure
+// paths, orbgpu_extractor_destroy).
+static void free_handle(orbgpu_extractor *e)
+{
+    for (DevBuf *b : e->buffers())
+        b->release();
+    for (auto &x : e->ev)
+        if (x)
+            (void)hipEventDestroy(x);
+    if (e->graph_exec)
+        (void)hipGraphExecDestroy(e->graph_exec);
+    if (e->graph)
+        (void)hipGraphDestroy(e->graph);
+    if (e->h_pin)
+        (void)hipHostFree(e->h_pin);
+    if (e->stream)
+        (void)hipStreamDestroy(e->stream);
+    if (e->side)
+        (void)hipStreamDestroy(e->side);
+    if (e->ev_fork)
+        (void)hipEventDestroy(e->ev_fork);
+    if (e->ev_fork0)
+        (void)hipEventDestroy(e->ev_fork0);
+    if (e->ev_join)
+        (void)hipEventDestroy(e->ev_join);
+    delete e;
+}
 
 int orbgpu_extractor_create(const orbgpu_extractor_params *p, orbgpu_extractor **out)
 {
@@ -3371,17 +2906,21 @@ int orbgpu_extractor_create(const orbgpu_extractor_params *p, orbgpu_extractor *
     if (const char *q = getenv("ORBGPU_DEBUG_FAST_QUEUE"))  // test hook: forces k_fast_detect's queue-full path
         e->fast_queue_cap = std::min(std::max(atoi(q), 0), FD_QCAP);
     e->nlevels = p->nlevels;
-    build_tables(e);
+    std::string why;
+    if ((rc = build_consts(p->nfeatures, p->scale_factor, p->nlevels, &e->consts, &why)) != ORBGPU_OK) {
+        set_error("%s", why.c_str());
+        free_handle(e);
+        return rc;
+    }
     hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
     if (he != hipSuccess) {
         set_error("hipStreamCreate: %s", hipGetErrorString(he));
-        delete e;
+        free_handle(e);
         return ORBGPU_EHIP;
     }
     rc = trig_table_for_device(p->device_id, &e->trig);
     if (rc != ORBGPU_OK) {
-        (void)hipStreamDestroy(e->stream);
-        delete e;
+        free_handle(e);
         return rc;
     }
     *out = e;
@@ -3395,32 +2934,7 @@ int orbgpu_extractor_destroy(orbgpu_extractor *e)
         return ORBGPU_OK;
     (void)hipSetDevice(e->prm.device_id);
     (void)hipDeviceSynchronize();
-    DevBuf *bufs[] = {&e->d_geom, &e->d_cells, &e->d_xtab, &e->d_ytab, &e->d_yrow, &e->d_pattern, &e->d_rstrip, &e->d_rsel,
-                      &e->d_rwt, &e->d_ctab, &e->d_bcol, &e->d_pyr,
-                      &e->d_blur, &e->d_slots, &e->d_cellcnt, &e->d_dkey, &e->d_dnode, &e->d_sel, &e->d_nsel,
-                      &e->d_ncand, &e->d_aux, &e->d_in, &e->d_kps, &e->d_desc, &e->d_nout, &e->d_dbg, &e->d_qtaux, &e->d_stereo};
-    for (DevBuf *b : bufs)
-        b->release();
-    for (auto &x : e->ev)
-        if (x)
-            (void)hipEventDestroy(x);
-    if (e->graph_exec)
-        (void)hipGraphExecDestroy(e->graph_exec);
-    if (e->graph)
-        (void)hipGraphDestroy(e->graph);
-    if (e->h_pin)
-        (void)hipHostFree(e->h_pin);
-    if (e->stream)
-        (void)hipStreamDestroy(e->stream);
-    if (e->side)
-        (void)hipStreamDestroy(e->side);
-    if (e->ev_fork)
-        (void)hipEventDestroy(e->ev_fork);
-    if (e->ev_fork0)
-        (void)hipEventDestroy(e->ev_fork0);
-    if (e->ev_join)
-        (void)hipEventDestroy(e->ev_join);
-    delete e;
+    free_handle(e);
     return ORBGPU_OK;
 }
 
@@ -3433,7 +2947,7 @@ int orbgpu_extractor_get_levels(const orbgpu_extractor *e, int32_t *n)
 int orbgpu_extractor_get_scale_factor(const orbgpu_extractor *e, float *s)
 {
     ORBGPU_REQUIRE(e && s, "null argument");
-    *s = (float)e->scale_factor_d;
+    *s = (float)e->consts.scale_factor_d;
     return ORBGPU_OK;
 }
 #define ORBGPU_GETTER(name, field, T)                                                                        \
@@ -3441,7 +2955,7 @@ int orbgpu_extractor_get_scale_factor(const orbgpu_extractor *e, float *s)
     {                                                                                                        \
         ORBGPU_REQUIRE(e && out, "null argument");                                                           \
         for (int i = 0; i < e->nlevels; i++)                                                                 \
-            out[i] = e->field[i];                                                                            \
+            out[i] = e->consts.field[i];                                                                            \
         return ORBGPU_OK;                                                                                    \
     }
 ORBGPU_GETTER(orbgpu_extractor_get_scale_factors, scale, float)
@@ -3457,11 +2971,9 @@ int orbgpu_extractor_max_keypoints(const orbgpu_extractor *e, int32_t w, int32_t
     ORBGPU_REQUIRE(w > 0 && h > 0, "empty image");
     int total = 0;
     for (int l = 0; l < e->nlevels; l++) {
-        const int lw = cv_round_host((float)w * e->inv_scale[l]), lh = cv_round_host((float)h * e->inv_scale[l]);
-        const float width = (float)(lw - 2 * BORDER0), height = (float)(lh - 2 * BORDER0);
-        ORBGPU_REQUIRE(width >= 30 && height >= 30, "pyramid level %d too small", l);
-        const int n_ini = (int)roundf(width / height);
-        total += std::max(4 * n_ini, e->quota[l] + 3);
+        const LevelSize ls = level_size(e->consts, w, h, l);
+        ORBGPU_REQUIRE(ls.width >= 30 && ls.height >= 30, "pyramid level %d too small", l);
+        total += level_max_keypoints(level_n_ini(ls), e->consts.quota[l]);
     }
     *cap = total;
     return ORBGPU_OK;
@@ -3569,11 +3081,7 @@ int orbgpu_extract_batch(orbgpu_extractor *e, const uint8_t *gray, int32_t batch
                 launched = true;
                 // the replay did what launch_pipeline did while recording: its bookkeeping, not that of whatever call
                 // (a device entry point on the caller's buffer, say) came in between
-                e->last_src = e->graph_src;
-                e->last_batch = e->graph_batch;
-                e->last_cap = e->graph_cap;
-                e->level0_materialized = !e->graph_src.direct;
-                e->borders_materialized = !e->interior_resize;
+                e->last = e->graph_last;
                 e->graph_replays++;
             } else
                 e->graph_state = -1;
@@ -3599,14 +3107,10 @@ int orbgpu_extract_batch(orbgpu_extractor *e, const uint8_t *gray, int32_t batch
                 e->graph = g;
                 e->graph_exec = ge;
                 e->graph_state = 1;
-                e->graph_src = e->last_src;  // (set by the recording launch_pipeline above)
-                e->graph_batch = e->last_batch;
-                e->graph_cap = e->last_cap;
+                e->graph_last = e->last;  // (noted by the recording launch_pipeline above)
                 e->graph_records++;
                 ok = hipGraphLaunch(e->graph_exec, e->stream) == hipSuccess;
                 launched = ok;
-                e->level0_materialized = !e->last_src.direct;
-                e->borders_materialized = !e->interior_resize;
             }
             if (!ok) {
                 (void)hipGetLastError();
@@ -3666,15 +3170,15 @@ int orbgpu_extract(orbgpu_extractor *e, const uint8_t *gray, int32_t w, int32_t 
 // orbgpu_extract_batch_device (which must still hold the images: orbgpu.h).
 static int ensure_level0(orbgpu_extractor *e)
 {
-    if (e->level0_materialized)
+    if (e->last.level0_materialized)
         return ORBGPU_OK;
     ORBGPU_HIP_TRY(hipDeviceSynchronize());
     Launcher L0(nullptr);
-    int rc = materialize_level0(e, e->last_src, e->last_batch, L0);
+    int rc = materialize_level0(e, e->last.src, e->last.batch, L0);
     if (rc != ORBGPU_OK)
         return rc;
     ORBGPU_HIP_TRY(hipDeviceSynchronize());
-    e->level0_materialized = true;
+    e->last.level0_materialized = true;
     return ORBGPU_OK;
 }
 
@@ -3682,14 +3186,14 @@ static int ensure_level0(orbgpu_extractor *e)
 // plane is handed out.
 static int ensure_borders(orbgpu_extractor *e)
 {
-    if (e->borders_materialized)
+    if (e->last.borders_materialized)
         return ORBGPU_OK;
     ORBGPU_HIP_TRY(hipDeviceSynchronize());
     Launcher L0(nullptr);
-    launch_ring_fill(e, e->last_batch, L0, EDGE);
+    launch_ring_fill(e, e->last.batch, L0);
     ORBGPU_HIP_TRY(hipGetLastError());
     ORBGPU_HIP_TRY(hipDeviceSynchronize());
-    e->borders_materialized = true;
+    e->last.borders_materialized = true;
     return ORBGPU_OK;
 }
 
@@ -3697,9 +3201,9 @@ int orbgpu_extractor_get_pyramid_level(orbgpu_extractor *e, int32_t frame, int32
                                        size_t dst_stride, int32_t *width, int32_t *height)
 {
     ORBGPU_REQUIRE(e && dst, "null argument");
-    ORBGPU_REQUIRE(e->last_batch > 0 && frame >= 0 && frame < e->last_batch && level >= 0 && level < e->nlevels,
+    ORBGPU_REQUIRE(e->last.batch > 0 && frame >= 0 && frame < e->last.batch && level >= 0 && level < e->nlevels,
                    "no such frame/level in the last call");
-    const LevelGeom &g = e->geom[level];
+    const LevelGeom &g = e->plan.geom[level];
     ORBGPU_REQUIRE(dst_stride >= (size_t)g.w, "bad dst_stride");
     int rc = select_device(e->prm.device_id);
     if (rc != ORBGPU_OK)
@@ -3708,7 +3212,7 @@ int orbgpu_extractor_get_pyramid_level(orbgpu_extractor *e, int32_t frame, int32
         return rc;
     if (level > 0 && (rc = ensure_borders(e)) != ORBGPU_OK)
         return rc;
-    const uint8_t *src = e->d_pyr.as<uint8_t>() + e->frame_pyr * frame + g.plane_off + (size_t)EDGE * g.pitch + EDGE;
+    const uint8_t *src = e->d_pyr.as<uint8_t>() + e->plan.frame_pyr * frame + g.plane_off + (size_t)EDGE * g.pitch + EDGE;
     ORBGPU_HIP_TRY(hipDeviceSynchronize());
     ORBGPU_HIP_TRY(hipMemcpy2D(dst, dst_stride, src, (size_t)g.pitch, (size_t)g.w, (size_t)g.h, hipMemcpyDeviceToHost));
     if (width)
@@ -3731,13 +3235,13 @@ int orbgpu_extractor_debug_read(orbgpu_extractor *e, int32_t what, int32_t frame
             *aux = 0;
         return ORBGPU_OK;
     }
-    ORBGPU_REQUIRE(e->last_batch > 0 && frame >= 0 && frame < e->last_batch && level >= 0 && level < e->nlevels,
+    ORBGPU_REQUIRE(e->last.batch > 0 && frame >= 0 && frame < e->last.batch && level >= 0 && level < e->nlevels,
                    "no such frame/level in the last call");
     int rc = select_device(e->prm.device_id);
     if (rc != ORBGPU_OK)
         return rc;
     ORBGPU_HIP_TRY(hipDeviceSynchronize());
-    const LevelGeom &g = e->geom[level];
+    const LevelGeom &g = e->plan.geom[level];
     if (what == ORBGPU_DBG_PYRAMID_PADDED || what == ORBGPU_DBG_BLURRED_PADDED) {
         const size_t bytes = (size_t)g.pitch * (g.h + 2 * EDGE);
         ORBGPU_REQUIRE(dst_bytes >= bytes, "dst too small (%zu needed)", bytes);
@@ -3746,8 +3250,8 @@ int orbgpu_extractor_debug_read(orbgpu_extractor *e, int32_t what, int32_t frame
         if (what == ORBGPU_DBG_PYRAMID_PADDED && level > 0 && (rc = ensure_borders(e)) != ORBGPU_OK)
             return rc;
         const uint8_t *base = (what == ORBGPU_DBG_PYRAMID_PADDED ? e->d_pyr : e->d_blur).as<uint8_t>();
-        ORBGPU_HIP_TRY(hipMemcpy(dst, base + e->frame_pyr * frame + g.plane_off, bytes, hipMemcpyDeviceToHost));
-        if (what == ORBGPU_DBG_BLURRED_PADDED && level == 0 && e->last_src.direct) {
+        ORBGPU_HIP_TRY(hipMemcpy(dst, base + e->plan.frame_pyr * frame + g.plane_off, bytes, hipMemcpyDeviceToHost));
+        if (what == ORBGPU_DBG_BLURRED_PADDED && level == 0 && e->last.src.direct) {
             // direct mode keeps the blurred level 0 with pixel 0 at column BLUR0_OX: present it in the common layout
             uint8_t *rowp = static_cast<uint8_t *>(dst);
             for (int r = 0; r < g.h + 2 * EDGE; r++, rowp += g.pitch)
@@ -3765,8 +3269,8 @@ int orbgpu_extractor_debug_read(orbgpu_extractor *e, int32_t what, int32_t frame
         ORBGPU_REQUIRE(cnt >= 0, "stage reported failure (%d)", cnt);
         ORBGPU_REQUIRE(dst_bytes >= (size_t)cnt * 12, "dst too small (%zu needed)", (size_t)cnt * 12);
         const uint32_t *keys = what == ORBGPU_DBG_CANDIDATES
-                                   ? e->d_dkey.as<uint32_t>() + e->frame_slots * frame + g.slot_off
-                                   : e->d_sel.as<uint32_t>() + (size_t)e->sel_cap_total * frame + g.sel_off;
+                                   ? e->d_dkey.as<uint32_t>() + e->plan.frame_slots * frame + g.slot_off
+                                   : e->d_sel.as<uint32_t>() + (size_t)e->plan.sel_cap_total * frame + g.sel_off;
         if (cnt > 0) {
             if ((rc = e->d_dbg.reserve((size_t)cnt * 12)) != ORBGPU_OK)
                 return rc;
@@ -3992,11 +3496,11 @@ int orbgpu_extractor_debug_quadtree_config(const orbgpu_extractor *e, int32_t ba
                                            int32_t *lds_bytes)
 {
     ORBGPU_REQUIRE(e && lds_keys && threads && lds_bytes, "null argument");
-    ORBGPU_REQUIRE(e->cfg_w > 0, "no image size configured yet (call an extraction first)");
-    const bool batch_variant = batch >= QT_BATCH_MIN || e->force_batch_quadtree;
-    *lds_keys = batch_variant ? 0 : e->qt_kcap;
-    *threads = batch_variant ? QT_THREADS_BATCH : (e->cfg_w * e->cfg_h >= QT_LARGE_PIXELS ? QT_THREADS : QT_THREADS_SMALL);
-    *lds_bytes = (int32_t)(e->qt_lds + (batch_variant ? 0 : (size_t)e->qt_kcap * 6));
+    ORBGPU_REQUIRE(e->plan.w > 0, "no image size configured yet (call an extraction first)");
+    const QuadtreeLaunch ql = quadtree_launch(e->plan, batch, e->force_batch_quadtree);
+    *lds_keys = ql.kcap;
+    *threads = ql.threads;
+    *lds_bytes = (int32_t)ql.lds_bytes;
     return ORBGPU_OK;
 }
 int orbgpu_extractor_stage_count(void) { return ST_COUNT; }
