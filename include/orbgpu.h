@@ -1946,6 +1946,99 @@ int orbgpu_covis_keyframe_culling(orbgpu_covis_graph *g, int32_t n, const int64_
                                   int8_t *verdict, int32_t *n_mps, int32_t *n_redundant, int32_t point_capacity,
                                   int64_t *bad_point_ids, orbgpu_covis_culling_result *res);
 
+/* MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:242-307) and MapPoint::UpdateNormalAndDepth (:330-371) for a batch of
+ * map points, over the observation graph: the step that ends every chain that edits the map.  Three more columns carry what
+ * the two functions read besides the relation itself (edited from HOST arrays, returning synchronised, refusals answered
+ * with ORBGPU_EINVAL before any device is touched and with nothing changed):
+ *   set_scale_factors   KeyFrame::mvScaleFactors, one table per graph (it is the same for every key frame of a map);
+ *                       n_levels in [1, ORBGPU_COVIS_MAX_LEVELS]; may be called again; a value that is not finite or not
+ *                       positive is refused.  Held on the host and handed to the kernels by value.
+ *   set_descriptors     mDescriptors of one key frame, 32 bytes per slot, once behind add_keyframe.  Refused: an unknown id,
+ *                       n_slots different from the row's, a null array with n_slots > 0; a bad row ignores the call.  A third
+ *                       pool column beside the slots and the attribute bytes, allocated by the first call of this function
+ *                       and not before; from then on the pool grows three columns or none.  The row records that it has
+ *                       descriptors.
+ *   set_centres         KeyFrame::GetCameraCenter() of n key frames, centres [n][3], applied in order (later entries win);
+ *                       the hook of KeyFrame::SetPose and of the bundle adjustments' write-backs.  An unknown id is ignored
+ *                       (*known, optional, counts the entries whose key frame is a row), a bad row changes nothing.
+ *                       A row column of its own: the centre and a "has centre"
+ *                       flag.  set_bad leaves the centre alone.
+ *   clear               forgets the contents of all three.
+ * Conventions R1-R8; tests/refresh_model.py restates them and is compared bit for bit, floats as
+ * their 32-bit patterns.
+ *   R1 observations   the observations of p are the slots of rows that are not bad and that hold p (V2), ordered by
+ *              ascending key-frame id, then ascending slot index (V4: the reference iterates std::map<KeyFrame*, size_t> by
+ *              address).  A point in two slots of one row counts twice (V2's deviation); a bad key frame holds no slot,
+ *              which is also what the isBad() test at :265 leaves.
+ *   R2 none    no observation: status NO_OBS, everything untouched (:256, :345).
+ *   R3 capacity   more than ORBGPU_COVIS_REFRESH_MAX_OBS observations: status OVERFLOW, everything untouched, n_slots still
+ *              exact (a first choice, not a measured limit; the reference's float Distances[N][N] on the stack fails long
+ *              before).
+ *   R4 descriptor   if any observing row has no descriptors: status NO_DESC, descriptor untouched.  Otherwise desc is the
+ *              observation's row with the least median Hamming distance to all of them, itself included; the median is the
+ *              sorted distance row at index (N - 1) >> 1; the first minimum in R1's order wins
+ *              (orbgpu_distinctive_descriptors' rule).  desc_kf / desc_idx name the key frame and key-point index chosen.
+ *   R5 normal  if any observing row has no centre: status NO_CENTRE, normal and depth untouched.  Otherwise, per
+ *              observation in R1's order and per component: d = P - Ow in float; nrm = sqrt((double)dx * dx + (double)dy *
+ *              dy + (double)dz * dz), summed left to right in FP64; inv = (float)(1.0 / nrm); acc = acc + d * inv (two
+ *              float roundings, acc starting at 0); finally normal = acc * (float)(1.0 / (double)N).  This restates how
+ *              cv::norm and the Mat / double, Mat + Mat * s expressions evaluate for CV_32F; OpenCV is not part of the
+ *              reference tree, so the boundary is unpinned and tests/refresh_model.py is the definition.  A zero norm
+ *              follows IEEE arithmetic (a NaN normal); it is not a refusal.
+ *   R6 depth   ref_kf_ids[i] = mpRefKF->mnId must be a row that is not bad and holds p (the lowest slot index counts if it
+ *              holds p twice), level = the octave bits of that slot's attribute byte (V1) must be below n_levels, and a
+ *              scale table must be set; otherwise status NO_REF, normal AND depth untouched.  dist = (float)nrm of P -
+ *              Ow_ref as in R5; max_dist = dist * sf[level]; min_dist = max_dist / sf[n_levels - 1]: the raw mfMaxDistance /
+ *              mfMinDistance, not the 0.8 / 1.2 forms.  Deviation: the reference's observations[pRefKF] default-inserts 0
+ *              for a reference key frame that does not observe the point and reads key point 0's octave;
+ *              MapPoint::EraseObservation (:111-149) keeps mpRefKF an observer, so the flow never gets there.
+ *   R7 independence   the descriptor half (ORBGPU_REFRESH_DESCRIPTOR) and the normal / depth half
+ *              (ORBGPU_REFRESH_NORMAL_DEPTH) are independent: a status bit of one leaves the other to run; a half that
+ *              `what` leaves out sets no bit and writes nothing.  NO_CENTRE and NO_REF are tested separately (both may be
+ *              set).
+ *   R8 the graph is not modified, and the result does not depend on scheduling: atomics decide where an entry of an
+ *              observation list lands, never the order of its use.
+ * refresh_points: mp_ids >= 0 and distinct within a call, at most 2^20 of them; world_pos [n][3].  normal [n][3], min_dist,
+ * max_dist, desc [n][32] are in/out (an entry the rules leave untouched keeps the caller's bytes) and may be NULL, as may
+ * desc_kf / desc_idx (-1 where the descriptor was left untouched); n_slots (the number of observations) and status are
+ * required.  Refused: a null required argument, n < 0 or above 2^20, `what` zero or with other bits, a negative or repeated
+ * id.  One wait per call: the observation lists are bounded by the pool slots in use, so their buffer is sized without
+ * asking the device (scratch as large as the slot column).
+ * orbgpu_mappoint_table_refresh: the same query with the positions gathered from the table's rows on the device and the
+ * results written into the table's rows on the device (no orbgpu_mappoint_table_upsert afterwards).  An id the table does
+ * not know gives status UNKNOWN, a row flagged bad gives BAD (mbBad returns at :251 / :338); both leave the point untouched
+ * (n_slots is still exact).  The host outputs are optional copies of what was written (in/out as above); with all of them
+ * NULL only the status bytes, n_slots and the result record come back.  Table and graph must live on one device; each has
+ * its own stream, the call synchronises between the gather and the graph's kernels and returns synchronised; THE CALLER
+ * SERIALISES BOTH HANDLES for the duration of the call. */
+#define ORBGPU_COVIS_REFRESH_MAX_OBS 1024
+#define ORBGPU_REFRESH_DESCRIPTOR 1
+#define ORBGPU_REFRESH_NORMAL_DEPTH 2
+#define ORBGPU_REFRESH_NO_OBS 0x01
+#define ORBGPU_REFRESH_OVERFLOW 0x02
+#define ORBGPU_REFRESH_NO_DESC 0x04
+#define ORBGPU_REFRESH_NO_CENTRE 0x08
+#define ORBGPU_REFRESH_NO_REF 0x10
+#define ORBGPU_REFRESH_UNKNOWN 0x20
+#define ORBGPU_REFRESH_BAD 0x40
+typedef struct orbgpu_covis_refresh_result {
+    int32_t n_descriptors, n_normals; /* points whose descriptor / whose normal and depth were written */
+    int32_t n_no_obs, n_overflow, n_no_desc, n_no_centre, n_no_ref, n_unknown, n_bad; /* points per status bit */
+    int32_t max_obs;                  /* the longest observation list (overflowing ones included) */
+    int64_t n_entries;                /* entries of all lists that were built */
+} orbgpu_covis_refresh_result;
+int orbgpu_covis_graph_set_scale_factors(orbgpu_covis_graph *g, int32_t n_levels, const float *scale_factors);
+int orbgpu_covis_graph_set_descriptors(orbgpu_covis_graph *g, int64_t kf_id, int32_t n_slots, const uint8_t *desc);
+int orbgpu_covis_graph_set_centres(orbgpu_covis_graph *g, int32_t n, const int64_t *kf_ids, const float *centres, int32_t *known);
+int orbgpu_covis_refresh_points(orbgpu_covis_graph *g, int32_t n, const int64_t *mp_ids, const int64_t *ref_kf_ids,
+                                const float *world_pos, uint32_t what, float *normal, float *min_dist, float *max_dist,
+                                uint8_t *desc, int64_t *desc_kf, int32_t *desc_idx, int32_t *n_slots, uint8_t *status,
+                                orbgpu_covis_refresh_result *res);
+int orbgpu_mappoint_table_refresh(orbgpu_mappoint_table *t, orbgpu_covis_graph *g, int32_t n, const int64_t *mp_ids,
+                                  const int64_t *ref_kf_ids, uint32_t what, float *normal, float *min_dist, float *max_dist,
+                                  uint8_t *desc, int64_t *desc_kf, int32_t *desc_idx, int32_t *n_slots, uint8_t *status,
+                                  orbgpu_covis_refresh_result *res);
+
 /* ======================================================================================
  * On-disk formats of the end-of-run artefacts: host serialisers, byte for byte.
  * ====================================================================================== */

@@ -33,11 +33,32 @@
 //                         workgroup.
 //   k_covis_cull_emit     the dead points in query order, which is ascending id.
 // One wait per call; the graph is not modified.
+//
+// MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth (MapPoint.cc:242-307, :330-371) for a batch of points
+// (R1-R8) run over the same pool, a third pool column (the key frames' descriptors, 32 bytes per slot, allocated by the first
+// orbgpu_covis_graph_set_descriptors), a row column (the camera centres) and the scale-factor table the host hands over
+// by value:
+//   k_covis_cull_count    with one level: the observations per query point.
+//   k_covis_refresh_scan  one workgroup: each point's start in the entry buffer (points without observations, over the cap
+//                         or excluded by the table take no space), the list of points with <= 64 observations and the list
+//                         of those with more, the status of every point that is not refreshed.
+//   k_covis_refresh_fill  the vote's shape again: a hit takes atomicAdd(cursor[q], 1) and stores (row, slot index).
+//   k_covis_refresh       two launches over the two lists: one wave per point (a 64-thread workgroup), or 256 threads per
+//                         point with four entries each.  A thread ranks its (key-frame id, slot index) among the point's
+//                         entries through LDS (R1's order, whatever order the atomics left), puts its descriptor and its
+//                         normal term into LDS at its rank, finds the median of its distance row by bisection on the value
+//                         (or from a stored row: ORBGPU_DEBUG_REFRESH_SELECT=rows, wave path), the least (median, rank) is
+//                         reduced over the wave and the workgroup, and thread 0 sums the normal terms in rank order.  Every
+//                         barrier stands under workgroup-uniform control flow; all global writes are plain vector stores.
+// The entry buffer is as long as the pool slots in use -- a slot holds one id and the query's ids are distinct, so no call
+// needs more -- which spares the wait for the total: one wait per call.  The graph is not modified.
 #include "common.h"
 #include "id_table.h"
+#include "refresh_internal.h"
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <unordered_map>
@@ -68,7 +89,7 @@ struct CvRow {  // 120 bytes; the host keeps a mirror and uploads the part an ed
     int64_t parent;  // -1: none; need not be a row
     int64_t off;     // the row's slots in the pool
     int32_t n_slots, bad;
-    int32_t nn, pad;
+    int32_t nn, has_desc;  // has_desc: orbgpu_covis_graph_set_descriptors has filled the row's part of the third pool column
     int64_t nb[CV_MAX_NB];
 };
 
@@ -688,7 +709,353 @@ __global__ __launch_bounds__(CV_LIST_BLOCK) void k_covis_cull_emit(int nq, const
         hdr[CU_BAD] = run;
 }
 
-constexpr int CV_ROW_COLS = 4;  // the per-row arrays of orbgpu_covis_graph
+// ---- the refresh of descriptor, normal and depth (R1-R8) ------------------------------------------------------------------
+constexpr int CV_REFRESH_MAX_OBS = ORBGPU_COVIS_REFRESH_MAX_OBS;
+constexpr int CV_REFRESH_MAX_POINTS = 1 << 20;  // ids of one call; a first choice, like CV_MAX_QUERY_POINTS
+constexpr int CV_REFRESH_WAVE = 64;             // observations the one-wave path takes
+constexpr unsigned CV_REFRESH_HALVES = ORBGPU_REFRESH_DESCRIPTOR | ORBGPU_REFRESH_NORMAL_DEPTH;
+enum { RH_ENTRIES = 0, RH_WAVE, RH_GROUP, RH_RANGE, RH_WORDS };  // header of a refresh (the first words of d_hdr)
+static_assert(RH_WORDS <= CH_WORDS, "the refresh header lies in d_hdr");
+static_assert(CV_MAX_POOL <= INT_MAX, "entry positions (CvRefresh::start, and its sums with a cursor) are 32-bit");
+
+struct CvCentre {  // the row column: KeyFrame::GetCameraCenter()
+    float x, y, z;
+    int32_t has;
+};
+
+struct CvScale {  // KeyFrame::mvScaleFactors, by value
+    int32_t n_levels;  // 0: not set
+    float sf[CV_LEVELS];
+};
+
+struct CvEntry {  // an observation: the row and the slot index
+    int32_t row, idx;
+};
+
+struct CvRefresh {  // a refresh call's arrays, in the handle's staging
+    int nq;
+    unsigned what;
+    const int64_t *q;        // the query: sorted distinct point ids
+    const int32_t *perm;     // sorted position -> the caller's index; every array below `cursor` goes by the caller's index
+    const int32_t *ref_row;  // the row of mpRefKF, -1 for an unknown or bad one
+    const float *pos;        // [n][3]
+    const uint8_t *pre;      // table form: ORBGPU_REFRESH_UNKNOWN / ORBGPU_REFRESH_BAD; nullptr otherwise
+    const int32_t *t_row;    // table form: the table row that takes the results
+    float *t_normal, *t_min, *t_max;
+    uint8_t *t_desc;
+    int32_t *obs, *cnt, *cursor, *start;  // per sorted position: k_covis_cull_count's two sums, entries stored, first entry
+    int32_t *list_w, *list_g;             // sorted positions with <= 64 observations, with more
+    float *normal, *min_dist, *max_dist;  // the results, by the caller's index
+    uint8_t *desc;
+    int64_t *desc_kf;
+    int32_t *desc_idx, *n_slots;
+    uint8_t *status;
+    int64_t ent_cap;
+    CvEntry *ents;
+};
+
+__global__ __launch_bounds__(CV_LIST_BLOCK) void k_covis_refresh_scan(CvRefresh c, long long *hdr)
+{
+    __shared__ int s_w[CV_LIST_BLOCK / 64];
+    long long run_e = 0;
+    int run_w = 0, run_g = 0;
+    for (int base = 0; base < c.nq; base += CV_LIST_BLOCK) {
+        const int k = base + threadIdx.x;
+        int n = 0, st = 0, ci = 0;
+        if (k < c.nq) {
+            ci = c.perm[k];
+            n = c.cnt[k];
+            const int pre = c.pre ? c.pre[ci] : 0;
+            st = pre ? pre : n == 0 ? ORBGPU_REFRESH_NO_OBS : n > CV_REFRESH_MAX_OBS ? ORBGPU_REFRESH_OVERFLOW : 0;
+        }
+        const bool live = k < c.nq && st == 0;
+        const bool wave = live && n <= CV_REFRESH_WAVE, group = live && n > CV_REFRESH_WAVE;
+        int te, tw, tg;
+        const int xe = block_scan_excl(live ? n : 0, s_w, te);  // (at most 2^10 points of 2^10 entries per step)
+        const int xw = block_scan_excl(wave, s_w, tw);
+        const int xg = block_scan_excl(group, s_w, tg);
+        if (k < c.nq) {
+            c.start[k] = live ? (int)(run_e + xe) : -1;  // (below ent_cap <= CV_MAX_POOL, which fits: see the assertion)
+            if (wave)
+                c.list_w[run_w + xw] = k;
+            if (group)
+                c.list_g[run_g + xg] = k;
+            c.status[ci] = (uint8_t)st;  // (k_covis_refresh writes a refreshed point's again)
+            c.n_slots[ci] = n;
+            c.desc_kf[ci] = -1;
+            c.desc_idx[ci] = -1;
+        }
+        run_e += te;
+        run_w += tw;
+        run_g += tg;
+    }
+    if (threadIdx.x == 0) {
+        hdr[RH_ENTRIES] = run_e;
+        hdr[RH_WAVE] = run_w;
+        hdr[RH_GROUP] = run_g;
+        if (run_e > c.ent_cap)
+            hdr[RH_RANGE] = 1;
+    }
+}
+
+// Every slot of a row that is not bad and holds a point with a list: (row, slot index) goes to the point's next free entry.
+template <bool LDS>
+__global__ __launch_bounds__(CV_BLOCK) void k_covis_refresh_fill(int n_rows, const CvRow *__restrict__ rows, const int64_t *__restrict__ pool,
+                                                                 int64_t pool_used, CvRefresh c, long long *hdr)
+{
+    extern __shared__ int64_t s_cv[];
+    const int64_t *q = c.q;
+    if (LDS) {  // a template constant: the barrier is under workgroup-uniform control flow
+        for (int i = threadIdx.x; i < c.nq; i += CV_BLOCK)
+            s_cv[i] = c.q[i];
+        __syncthreads();
+        q = s_cv;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int row = blockIdx.x * CV_WAVES + wave; row < n_rows; row += gridDim.x * CV_WAVES) {  // wave-uniform
+        const int64_t off = rows[row].off;
+        const int len = rows[row].n_slots;
+        if (rows[row].bad || off < 0 || len < 0 || off + len > pool_used)
+            continue;
+        for (int e = lane; e < len; e += 64) {
+            const int64_t id = pool[off + e];
+            if (id < 0)
+                continue;
+            const int k = covis_find(q, c.nq, id);
+            if (k < 0)
+                continue;
+            const int s = c.start[k];
+            if (s < 0)
+                continue;
+            const int p = atomicAdd(c.cursor + k, 1);  // R8: where the entry lands; k_covis_refresh orders the list itself
+            if (p >= c.cnt[k] || (int64_t)s + p >= c.ent_cap) {
+                hdr[RH_RANGE] = 1;
+                continue;
+            }
+            c.ents[s + p] = CvEntry{row, e};
+        }
+    }
+}
+
+// the k-th smallest of the n distances of a to the descriptors sd[0..n) (a is one of them), k = (n - 1) >> 1: the smallest
+// v with #{j : d_j <= v} >= k + 1, by bisection on [0, 256] (k_distinctive's).  dist != nullptr: the row was stored there.
+__device__ __forceinline__ int refresh_median(const uint64_t a[4], const uint64_t *sd, int n, const uint16_t *dist)
+{
+    const int k = (n - 1) >> 1;
+    int lo = 0, hi = 256;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        int cnt = 0;
+        for (int j = 0; j < n; j++) {
+            int d;
+            if (dist)
+                d = dist[j];
+            else {
+                const uint64_t b[4] = {sd[j * 4], sd[j * 4 + 1], sd[j * 4 + 2], sd[j * 4 + 3]};
+                d = hamming256(a, b);
+            }
+            cnt += d <= mid ? 1 : 0;
+        }
+        if (cnt >= k + 1)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    return lo;
+}
+
+// One workgroup of BLOCK threads per point of the list (`group`: list_g, otherwise list_w), PER entries per thread; the
+// scan put a point on a list whose BLOCK * PER holds its observations.  ROWS (one wave, one entry per thread): the distance
+// row is stored in LDS once and the bisection counts over it.
+template <int BLOCK, int PER, bool ROWS>
+__global__ __launch_bounds__(BLOCK) void k_covis_refresh(int group, const CvRow *__restrict__ rows, const uint8_t *__restrict__ kp,
+                                                         const uint8_t *__restrict__ descs, const CvCentre *__restrict__ centres,
+                                                         CvScale sc, CvRefresh c, const long long *__restrict__ hdr)
+{
+    constexpr int CAP = BLOCK * PER;
+    constexpr int DSTRIDE = CAP + 2;  // halfwords: an odd number of words, so that the lanes' rows fall into distinct banks
+    static_assert(!ROWS || (BLOCK == 64 && PER == 1), "the stored distance row is the one-wave path's");
+    __shared__ int64_t s_kf[CAP];
+    __shared__ int32_t s_e[CAP];
+    __shared__ __align__(16) uint64_t s_d[CAP * 4];
+    __shared__ float s_t[CAP * 3];
+    __shared__ uint16_t s_dist[ROWS ? CAP * DSTRIDE : 1];
+    __shared__ unsigned long long s_best;
+    __shared__ int s_flags, s_ref_e, s_ref_level;
+    __shared__ float s_ref_dist;
+    const int tid = threadIdx.x;
+    if (hdr[RH_RANGE])  // an index left its range in the scan or the fill: the host reports it, nothing is read
+        return;
+    const int n_list = (int)hdr[group ? RH_GROUP : RH_WAVE];
+    const int32_t *list = group ? c.list_g : c.list_w;
+    for (int li = blockIdx.x; li < n_list; li += gridDim.x) {  // workgroup-uniform, as is everything a barrier stands under
+        const int k = list[li];
+        const int n = min(c.cnt[k], CAP), base = c.start[k], ci = c.perm[k];
+        const int ref = c.ref_row[ci];
+        const float px = c.pos[3 * (size_t)ci], py = c.pos[3 * (size_t)ci + 1], pz = c.pos[3 * (size_t)ci + 2];
+        if (tid == 0) {
+            s_best = ~0ull;
+            s_flags = 0;
+            s_ref_e = INT_MAX;
+        }
+        int row[PER], e[PER], rank[PER];
+        int64_t kf[PER], off[PER];
+        float tx[PER], ty[PER], tz[PER], dist[PER];
+        int flags = 0;
+#pragma unroll
+        for (int m = 0; m < PER; m++) {
+            const int t = tid + m * BLOCK;
+            row[m] = -1;
+            if (t < n) {
+                const CvEntry en = c.ents[base + t];
+                row[m] = en.row;
+                e[m] = en.idx;
+                kf[m] = rows[en.row].id;
+                off[m] = rows[en.row].off;
+                s_kf[t] = kf[m];
+                s_e[t] = en.idx;
+                if (!rows[en.row].has_desc)
+                    flags |= 1;
+                const CvCentre ce = centres[en.row];
+                if (!ce.has)
+                    flags |= 2;
+                // R5: d = P - Ow in float, the norm in FP64, its inverse rounded to float, the term rounded again
+                const float dx = px - ce.x, dy = py - ce.y, dz = pz - ce.z;
+                const double nrm = sqrt((double)dx * (double)dx + (double)dy * (double)dy + (double)dz * (double)dz);
+                const float inv = (float)(1.0 / nrm);
+                tx[m] = dx * inv;
+                ty[m] = dy * inv;
+                tz[m] = dz * inv;
+                dist[m] = (float)nrm;
+            }
+        }
+        __syncthreads();  // the keys; s_best, s_flags, s_ref_e
+        if (flags)
+            atomicOr(&s_flags, flags);
+#pragma unroll
+        for (int m = 0; m < PER; m++) {
+            if (row[m] < 0)
+                continue;
+            int r = 0;  // R1: the entries before this one in (key-frame id, slot index); the keys are distinct
+            for (int j = 0; j < n; j++)
+                r += s_kf[j] < kf[m] || (s_kf[j] == kf[m] && s_e[j] < e[m]) ? 1 : 0;
+            rank[m] = r;
+            if (row[m] == ref)
+                atomicMin(&s_ref_e, e[m]);  // R6: the lowest slot of the reference row
+        }
+        __syncthreads();
+        const int fl = s_flags, ref_e = s_ref_e;
+        if ((c.what & ORBGPU_REFRESH_DESCRIPTOR) && !(fl & 1)) {  // R4
+#pragma unroll
+            for (int m = 0; m < PER; m++)
+                if (row[m] >= 0) {
+                    const uint4 *src = reinterpret_cast<const uint4 *>(descs + 32 * (size_t)(off[m] + e[m]));
+                    uint4 *dst = reinterpret_cast<uint4 *>(s_d + 4 * rank[m]);
+                    dst[0] = src[0];
+                    dst[1] = src[1];
+                }
+            __syncthreads();
+            unsigned long long mine = ~0ull;
+#pragma unroll
+            for (int m = 0; m < PER; m++)
+                if (row[m] >= 0) {
+                    const uint64_t *own = s_d + 4 * rank[m];
+                    const uint64_t a[4] = {own[0], own[1], own[2], own[3]};
+                    const uint16_t *stored = nullptr;
+                    if (ROWS) {
+                        uint16_t *dr = s_dist + tid * DSTRIDE;
+                        for (int j = 0; j < n; j++) {
+                            const uint64_t b[4] = {s_d[j * 4], s_d[j * 4 + 1], s_d[j * 4 + 2], s_d[j * 4 + 3]};
+                            dr[j] = (uint16_t)hamming256(a, b);
+                        }
+                        stored = dr;
+                    }
+                    const unsigned long long key =
+                        ((unsigned long long)refresh_median(a, s_d, n, stored) << 32) | (unsigned)rank[m];  // least median, then R1's order
+                    mine = key < mine ? key : mine;
+                }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long other = __shfl_xor(mine, o, 64);
+                mine = other < mine ? other : mine;
+            }
+            if ((tid & 63) == 0)
+                atomicMin(&s_best, mine);
+            __syncthreads();
+            const int best = (int)(s_best & 0xFFFFFFFFull);
+#pragma unroll
+            for (int m = 0; m < PER; m++)
+                if (row[m] >= 0 && rank[m] == best) {
+                    const uint4 *own = reinterpret_cast<const uint4 *>(s_d + 4 * best);
+                    uint4 *out = reinterpret_cast<uint4 *>(c.desc + 32 * (size_t)ci);
+                    out[0] = own[0];
+                    out[1] = own[1];
+                    if (c.t_row) {
+                        uint4 *tout = reinterpret_cast<uint4 *>(c.t_desc + 32 * (size_t)c.t_row[ci]);
+                        tout[0] = own[0];
+                        tout[1] = own[1];
+                    }
+                    c.desc_kf[ci] = kf[m];
+                    c.desc_idx[ci] = e[m];
+                }
+        }
+        if (c.what & ORBGPU_REFRESH_NORMAL_DEPTH) {
+#pragma unroll
+            for (int m = 0; m < PER; m++)
+                if (row[m] >= 0) {
+                    s_t[3 * rank[m]] = tx[m];
+                    s_t[3 * rank[m] + 1] = ty[m];
+                    s_t[3 * rank[m] + 2] = tz[m];
+                    if (row[m] == ref && e[m] == ref_e) {
+                        s_ref_dist = dist[m];
+                        s_ref_level = kp[off[m] + e[m]] & (CV_LEVELS - 1);
+                    }
+                }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int st = 0;
+            if ((c.what & ORBGPU_REFRESH_DESCRIPTOR) && (fl & 1))
+                st |= ORBGPU_REFRESH_NO_DESC;
+            if (c.what & ORBGPU_REFRESH_NORMAL_DEPTH) {
+                const bool ref_ok = ref_e != INT_MAX && s_ref_level < sc.n_levels;  // (n_levels = 0: no table)
+                if (fl & 2)
+                    st |= ORBGPU_REFRESH_NO_CENTRE;
+                if (!ref_ok)
+                    st |= ORBGPU_REFRESH_NO_REF;
+                if (!(fl & 2) && ref_ok) {
+                    float ax = 0.f, ay = 0.f, az = 0.f;  // R5: in R1's order
+                    for (int j = 0; j < n; j++) {
+                        ax = ax + s_t[3 * j];
+                        ay = ay + s_t[3 * j + 1];
+                        az = az + s_t[3 * j + 2];
+                    }
+                    const float inv_n = (float)(1.0 / (double)n);
+                    const float nx = ax * inv_n, ny = ay * inv_n, nz = az * inv_n;
+                    const float mx = s_ref_dist * sc.sf[s_ref_level];  // R6
+                    const float mn = mx / sc.sf[sc.n_levels - 1];
+                    c.normal[3 * (size_t)ci] = nx;
+                    c.normal[3 * (size_t)ci + 1] = ny;
+                    c.normal[3 * (size_t)ci + 2] = nz;
+                    c.min_dist[ci] = mn;
+                    c.max_dist[ci] = mx;
+                    if (c.t_row) {
+                        const size_t tr = (size_t)c.t_row[ci];
+                        c.t_normal[3 * tr] = nx;
+                        c.t_normal[3 * tr + 1] = ny;
+                        c.t_normal[3 * tr + 2] = nz;
+                        c.t_min[tr] = mn;
+                        c.t_max[tr] = mx;
+                    }
+                }
+            }
+            c.status[ci] = (uint8_t)st;
+        }
+        __syncthreads();  // the next point takes the arrays over
+    }
+}
+
+constexpr int CV_ROW_COLS = 5;  // the per-row arrays of orbgpu_covis_graph
 
 } // namespace orbgpu
 
@@ -703,8 +1070,9 @@ struct orbgpu_covis_graph {
     int64_t pool_used = 0, pool_cap = 0;
     // per row, all carried over by a growth: the row, its vote, its query stamp (mnTrackReferenceForFrame), and the rows in
     // ascending id (position p holds the row of the p-th smallest id)
-    DevBuf d_rows, d_count, d_stamp, d_order;
-    const IdColumn<DevBuf> row_cols[CV_ROW_COLS] = {{&d_rows, sizeof(CvRow)}, {&d_count, 4}, {&d_stamp, 4}, {&d_order, 4}};
+    DevBuf d_rows, d_count, d_stamp, d_order, d_centre;  // d_centre: the camera centres (R5), zero until set_centres
+    const IdColumn<DevBuf> row_cols[CV_ROW_COLS] = {
+        {&d_rows, sizeof(CvRow)}, {&d_count, 4}, {&d_stamp, 4}, {&d_order, 4}, {&d_centre, sizeof(CvCentre)}};
     orbgpu_covis_graph() = default;
     orbgpu_covis_graph(const orbgpu_covis_graph &) = delete;
     DevBuf d_pool, d_kp, d_hkeys, d_hvals, d_stage, d_hdr, d_pkeys, d_ppos, d_used, d_chunks, d_points;
@@ -721,6 +1089,14 @@ struct orbgpu_covis_graph {
     int point_log2 = 0;          // the point hash as allocated
     bool point_dirty = true;     // it may hold entries: emptied as a whole before its next use
     int64_t global_queries = 0;  // vote and culling-count launches that read the query from global memory (tests)
+    // the refresh (R1-R8)
+    DevBuf d_desc;                   // the third pool column, 32 bytes per slot; empty until the first set_descriptors
+    bool has_desc_col = false;       // d_desc is as long as the pool and grows with it
+    DevBuf d_ents;                   // a call's observation lists
+    std::vector<CvCentre> h_centre;  // the centre column, as the device holds it
+    bool centres_set = false;        // the column may hold something other than zeros
+    CvScale scale = {};
+    bool refresh_rows = false;       // ORBGPU_DEBUG_REFRESH_SELECT=rows, read at creation
 };
 
 namespace orbgpu {
@@ -744,14 +1120,19 @@ static int cv_grow_pool(orbgpu_covis_graph *g, int64_t want)
     int64_t ncap = std::max<int64_t>(g->pool_cap, 1024);
     while (ncap < want)
         ncap *= 2;
-    DevBuf np, nk;  // both columns or neither: nothing is swapped before both copies have arrived
+    DevBuf np, nk, nd;  // every column or none: nothing is swapped before all copies have arrived (the descriptor column
+                        // takes part once it exists)
     int rc = np.reserve(8 * (size_t)ncap);
     if (rc == ORBGPU_OK)
         rc = nk.reserve((size_t)ncap);
+    if (rc == ORBGPU_OK && g->has_desc_col)
+        rc = nd.reserve(32 * (size_t)ncap);
     if (rc == ORBGPU_OK && g->pool_used > 0) {
         hipError_t he = hipMemcpyAsync(np.p, g->d_pool.p, 8 * (size_t)g->pool_used, hipMemcpyDeviceToDevice, g->stream);
         if (he == hipSuccess)
             he = hipMemcpyAsync(nk.p, g->d_kp.p, (size_t)g->pool_used, hipMemcpyDeviceToDevice, g->stream);
+        if (he == hipSuccess && g->has_desc_col)
+            he = hipMemcpyAsync(nd.p, g->d_desc.p, 32 * (size_t)g->pool_used, hipMemcpyDeviceToDevice, g->stream);
         if (he == hipSuccess)
             he = hipStreamSynchronize(g->stream);
         if (he != hipSuccess) {
@@ -763,12 +1144,16 @@ static int cv_grow_pool(orbgpu_covis_graph *g, int64_t want)
         (void)hipStreamSynchronize(g->stream);
         np.release();
         nk.release();
+        nd.release();
         return rc;
     }
     std::swap(g->d_pool, np);
     std::swap(g->d_kp, nk);
+    if (g->has_desc_col)
+        std::swap(g->d_desc, nd);
     np.release();
     nk.release();
+    nd.release();
     g->pool_cap = ncap;
     return ORBGPU_OK;
 }
@@ -991,7 +1376,7 @@ static int cv_destroy(orbgpu_covis_graph *g)
         for (const IdColumn<DevBuf> &c : g->row_cols)
             c.buf->release();
         for (DevBuf *b : {&g->d_pool, &g->d_kp, &g->d_hkeys, &g->d_hvals, &g->d_stage, &g->d_hdr, &g->d_pkeys, &g->d_ppos, &g->d_used,
-                          &g->d_chunks, &g->d_points})
+                          &g->d_chunks, &g->d_points, &g->d_desc, &g->d_ents})
             b->release();
     }
     delete g;
@@ -1020,6 +1405,9 @@ int orbgpu_covis_graph_create(int32_t device_id, int32_t initial_rows, int64_t i
     // ORBGPU_DEBUG_COVIS_LDS_IDS=<k> (tests): a query of more than k distinct ids takes the global-memory path
     if (const char *e = getenv("ORBGPU_DEBUG_COVIS_LDS_IDS"))
         g->lds_ids = std::min(std::max(atoi(e), 0), CV_LDS_IDS);
+    // ORBGPU_DEBUG_REFRESH_SELECT=rows (measurements): the one-wave refresh keeps its distance rows in LDS
+    if (const char *e = getenv("ORBGPU_DEBUG_REFRESH_SELECT"))
+        g->refresh_rows = !strcmp(e, "rows");
     *out = g;
     return ORBGPU_OK;
 }
@@ -1038,6 +1426,8 @@ int orbgpu_covis_graph_clear(orbgpu_covis_graph *g)
         if (rc != ORBGPU_OK)
             return rc;
         hipError_t he = hipMemsetAsync(g->d_hkeys.p, 0xFF, sizeof(int64_t) << g->hash.log2cap, g->stream);  // ID_HASH_EMPTY
+        if (he == hipSuccess && g->centres_set)  // a row added later starts without a centre
+            he = hipMemsetAsync(g->d_centre.p, 0, sizeof(CvCentre) * (size_t)g->row_cap, g->stream);
         if ((rc = cv_sync_or_fail(g, he, "clearing the covisibility graph")) != ORBGPU_OK)
             return rc;
     }
@@ -1046,6 +1436,9 @@ int orbgpu_covis_graph_clear(orbgpu_covis_graph *g)
     g->h_pool.clear();
     g->h_kp.clear();
     g->h_order.clear();
+    g->h_centre.clear();  // (descriptors go with the rows' flags)
+    g->centres_set = false;
+    g->scale = CvScale{};
     g->covis.clear();
     g->parents.clear();
     g->rows = g->n_bad = 0;
@@ -1125,6 +1518,7 @@ int orbgpu_covis_graph_add_keyframe(orbgpu_covis_graph *g, int64_t id, int32_t n
     g->h_order.insert(g->h_order.begin() + (ptrdiff_t)at, r);
     g->h_pool.insert(g->h_pool.end(), slots.begin(), slots.end());
     g->h_kp.insert(g->h_kp.end(), (size_t)n_slots, (uint8_t)0);
+    g->h_centre.push_back(CvCentre{});
     g->covis.erase(id);
     g->parents.erase(id);
     g->pool_used += n_slots;
@@ -1618,4 +2012,332 @@ int orbgpu_covis_keyframe_culling(orbgpu_covis_graph *g, int32_t n, const int64_
     return ORBGPU_OK;
 }
 
+int orbgpu_covis_graph_set_scale_factors(orbgpu_covis_graph *g, int32_t n_levels, const float *scale_factors)
+{
+    ORBGPU_REQUIRE(g, "null argument");
+    ORBGPU_REQUIRE(n_levels >= 1 && n_levels <= CV_LEVELS, "n_levels = %d (1 to %d)", n_levels, CV_LEVELS);
+    ORBGPU_REQUIRE(scale_factors, "null argument");
+    for (int l = 0; l < n_levels; l++)
+        ORBGPU_REQUIRE(std::isfinite(scale_factors[l]) && scale_factors[l] > 0.f, "scale factor %g at level %d", (double)scale_factors[l], l);
+    g->scale = CvScale{};  // host only: the kernels take the table by value
+    g->scale.n_levels = n_levels;
+    std::copy(scale_factors, scale_factors + n_levels, g->scale.sf);
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_graph_set_descriptors(orbgpu_covis_graph *g, int64_t kf_id, int32_t n_slots, const uint8_t *desc)
+{
+    ORBGPU_REQUIRE(g, "null argument");
+    const int r = g->hash.find(kf_id);
+    ORBGPU_REQUIRE(r >= 0, "key frame %lld is not in the graph", (long long)kf_id);
+    const CvRow &row = g->h_rows[(size_t)r];
+    ORBGPU_REQUIRE(n_slots == row.n_slots, "n_slots = %d, key frame %lld has %d", n_slots, (long long)kf_id, row.n_slots);
+    ORBGPU_REQUIRE(n_slots == 0 || desc, "null argument");
+    if (row.bad || n_slots == 0)
+        return ORBGPU_OK;  // a bad key frame holds no slot (V2)
+    int rc = cv_bind(g);
+    if (rc != ORBGPU_OK)
+        return rc;
+    // the column comes with its first use; until then cv_grow_pool carries two columns
+    rc = lifecycle_locked_unless(g->has_desc_col, lifecycle_mutex(), [&] {
+        const int rr = g->d_desc.reserve(32 * (size_t)g->pool_cap);
+        g->has_desc_col = rr == ORBGPU_OK;
+        return rr;
+    });
+    if (rc != ORBGPU_OK)
+        return rc;
+    CvRow nr = row;
+    nr.has_desc = 1;
+    hipError_t he = hipMemcpyAsync(g->d_desc.as<uint8_t>() + 32 * (size_t)row.off, desc, 32 * (size_t)n_slots, hipMemcpyHostToDevice, g->stream);
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(g->d_rows.as<CvRow>() + r, &nr, sizeof(CvRow), hipMemcpyHostToDevice, g->stream);
+    if ((rc = cv_sync_or_fail(g, he, "setting descriptors")) != ORBGPU_OK) {
+        (void)hipMemcpy(g->d_rows.as<CvRow>() + r, &row, sizeof(CvRow), hipMemcpyHostToDevice);  // the flag as it was
+        return rc;
+    }
+    g->h_rows[(size_t)r] = nr;
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_graph_set_centres(orbgpu_covis_graph *g, int32_t n, const int64_t *kf_ids, const float *centres, int32_t *known)
+{
+    ORBGPU_REQUIRE(g && n >= 0 && n <= CV_MAX_CALL && (n == 0 || (kf_ids && centres)), "bad argument");
+    if (known)
+        *known = 0;
+    // applied in order to the mirror (later entries win); the device gets the rows from the first to the last one touched
+    std::vector<std::pair<int, CvCentre>> undo;
+    int n_known = 0, lo = INT_MAX, hi = -1;
+    for (int i = 0; i < n; i++) {
+        const int r = g->hash.find(kf_ids[i]);
+        if (r < 0)
+            continue;  // an unknown key frame: ignored
+        n_known++;
+        if (g->h_rows[(size_t)r].bad)
+            continue;
+        undo.emplace_back(r, g->h_centre[(size_t)r]);
+        g->h_centre[(size_t)r] = CvCentre{centres[3 * (size_t)i], centres[3 * (size_t)i + 1], centres[3 * (size_t)i + 2], 1};
+        lo = std::min(lo, r);
+        hi = std::max(hi, r);
+    }
+    if (!undo.empty()) {
+        auto fail = [&](int rc) {
+            for (size_t k = undo.size(); k-- > 0;)
+                g->h_centre[(size_t)undo[k].first] = undo[k].second;
+            return rc;
+        };
+        int rc = cv_bind(g);
+        if (rc != ORBGPU_OK)
+            return fail(rc);
+        const hipError_t he = hipMemcpyAsync(g->d_centre.as<CvCentre>() + lo, g->h_centre.data() + lo, sizeof(CvCentre) * (size_t)(hi - lo + 1),
+                                             hipMemcpyHostToDevice, g->stream);
+        if ((rc = cv_sync_or_fail(g, he, "setting camera centres")) != ORBGPU_OK) {
+            fail(rc);
+            (void)hipMemcpy(g->d_centre.as<CvCentre>() + lo, g->h_centre.data() + lo, sizeof(CvCentre) * (size_t)(hi - lo + 1), hipMemcpyHostToDevice);
+            return rc;
+        }
+        g->centres_set = true;
+    }
+    if (known)
+        *known = n_known;
+    return ORBGPU_OK;
+}
+
+int orbgpu_covis_refresh_points(orbgpu_covis_graph *g, int32_t n, const int64_t *mp_ids, const int64_t *ref_kf_ids,
+                                const float *world_pos, uint32_t what, float *normal, float *min_dist, float *max_dist,
+                                uint8_t *desc, int64_t *desc_kf, int32_t *desc_idx, int32_t *n_slots, uint8_t *status,
+                                orbgpu_covis_refresh_result *res)
+{
+    std::vector<int32_t> perm;
+    const int rc = covis_refresh_check(g, n, mp_ids, ref_kf_ids, what, n_slots, status, res, perm);
+    if (rc != ORBGPU_OK)
+        return rc;
+    ORBGPU_REQUIRE(n == 0 || world_pos, "null argument");
+    return covis_refresh_run(g, n, mp_ids, ref_kf_ids, world_pos, what, normal, min_dist, max_dist, desc, desc_kf, desc_idx, n_slots,
+                             status, res, perm, nullptr);
+}
+
 } // extern "C"
+
+namespace orbgpu {
+
+int covis_refresh_device_id(const orbgpu_covis_graph *g) { return g->device_id; }
+
+int covis_refresh_check(const orbgpu_covis_graph *g, int32_t n, const int64_t *mp_ids, const int64_t *ref_kf_ids, uint32_t what,
+                        const int32_t *n_slots, const uint8_t *status, const orbgpu_covis_refresh_result *res, std::vector<int32_t> &perm)
+{
+    ORBGPU_REQUIRE(g && res, "null argument");
+    ORBGPU_REQUIRE(n >= 0 && n <= CV_REFRESH_MAX_POINTS, "n = %d (at most %d)", n, CV_REFRESH_MAX_POINTS);
+    ORBGPU_REQUIRE(what != 0 && !(what & ~CV_REFRESH_HALVES), "what = 0x%x (ORBGPU_REFRESH_DESCRIPTOR | ORBGPU_REFRESH_NORMAL_DEPTH)", what);
+    ORBGPU_REQUIRE(n == 0 || (mp_ids && ref_kf_ids && n_slots && status), "null argument");
+    for (int i = 0; i < n; i++)
+        ORBGPU_REQUIRE(mp_ids[i] >= 0, "map point id %lld (entry %d)", (long long)mp_ids[i], i);
+    // the one sort of the call: the query in ascending id, as positions in the caller's arrays; equal ids end up adjacent
+    std::vector<int32_t> p((size_t)n);
+    for (int i = 0; i < n; i++)
+        p[(size_t)i] = i;
+    std::sort(p.begin(), p.end(), [mp_ids](int32_t a, int32_t b) { return mp_ids[a] < mp_ids[b]; });
+    const auto dup = std::adjacent_find(p.begin(), p.end(), [mp_ids](int32_t a, int32_t b) { return mp_ids[a] == mp_ids[b]; });
+    ORBGPU_REQUIRE(dup == p.end(), "map point id %lld appears twice in one refresh call", (long long)mp_ids[*dup]);
+    perm.swap(p);
+    return ORBGPU_OK;
+}
+
+int covis_refresh_run(orbgpu_covis_graph *g, int32_t n, const int64_t *mp_ids, const int64_t *ref_kf_ids, const float *world_pos,
+                      uint32_t what, float *normal, float *min_dist, float *max_dist, uint8_t *desc, int64_t *desc_kf,
+                      int32_t *desc_idx, int32_t *n_slots, uint8_t *status, orbgpu_covis_refresh_result *res,
+                      const std::vector<int32_t> &perm, const RefreshTableIO *tio)
+{
+    memset(res, 0, sizeof(*res));
+    if (n == 0)
+        return ORBGPU_OK;
+    const size_t nn = (size_t)n;
+    if (!tio && g->rows == g->n_bad) {  // nothing is held anywhere (R2): no device needed
+        for (int i = 0; i < n; i++) {
+            status[i] = ORBGPU_REFRESH_NO_OBS;
+            n_slots[i] = 0;
+            if (desc_kf)
+                desc_kf[i] = -1;
+            if (desc_idx)
+                desc_idx[i] = -1;
+        }
+        res->n_no_obs = n;
+        return ORBGPU_OK;
+    }
+    int rc = cv_bind(g);
+    if (rc != ORBGPU_OK)
+        return rc;
+    // the query in ascending id: the permutation is covis_refresh_check's; the results come back in the caller's order
+    // uploaded | zeroed | written by the kernels
+    Carver c;
+    const size_t o_q = c.take(8 * nn), o_perm = c.take(4 * nn), o_ref = c.take(4 * nn), o_pos = c.take(tio ? 0 : 12 * nn);
+    const size_t in_bytes = c.off;
+    const size_t o_obs = c.take(4 * nn), o_cnt = c.take(4 * nn), o_cursor = c.take(4 * nn);
+    const size_t zero_end = c.off;
+    const size_t o_start = c.take(4 * nn), o_lw = c.take(4 * nn), o_lg = c.take(4 * nn);
+    const size_t o_status = c.take(nn), o_ns = c.take(4 * nn), o_dkf = c.take(8 * nn), o_didx = c.take(4 * nn);
+    const size_t o_nr = c.take(12 * nn), o_mn = c.take(4 * nn), o_mx = c.take(4 * nn), o_ds = c.take(32 * nn);
+    const int64_t ent_cap = std::max<int64_t>(g->pool_used, 1);  // a slot holds one id, the query's ids are distinct
+    if ((rc = cv_reserve_locked(g->d_stage, c.off)) != ORBGPU_OK ||
+        (rc = cv_reserve_locked(g->d_ents, sizeof(CvEntry) * (size_t)ent_cap)) != ORBGPU_OK)
+        return rc;
+    g->stage.assign(in_bytes, 0);
+    int64_t *h_q = reinterpret_cast<int64_t *>(g->stage.data() + o_q);
+    int32_t *h_ref = reinterpret_cast<int32_t *>(g->stage.data() + o_ref);
+    for (int k = 0; k < n; k++)
+        h_q[k] = mp_ids[perm[(size_t)k]];
+    memcpy(g->stage.data() + o_perm, perm.data(), 4 * nn);
+    for (int i = 0; i < n; i++) {
+        const int r = g->hash.find(ref_kf_ids[i]);
+        h_ref[i] = r >= 0 && !g->h_rows[(size_t)r].bad ? r : -1;
+    }
+    if (!tio)
+        memcpy(g->stage.data() + o_pos, world_pos, 12 * nn);
+    char *st = g->d_stage.as<char>();
+    long long *hdr = g->d_hdr.as<long long>();
+    long long h[RH_WORDS] = {};
+    std::vector<uint8_t> h_status(nn), h_desc;
+    std::vector<int32_t> h_ns(nn), h_didx;
+    std::vector<int64_t> h_dkf;
+    std::vector<float> h_nr, h_mn, h_mx;
+    hipError_t he = hipMemcpyAsync(st, g->stage.data(), in_bytes, hipMemcpyHostToDevice, g->stream);
+    if (he == hipSuccess)
+        he = hipMemsetAsync(st + o_obs, 0, zero_end - o_obs, g->stream);
+    if (he == hipSuccess)
+        he = hipMemsetAsync(hdr, 0, 8 * CH_WORDS, g->stream);
+    if (he == hipSuccess) {
+        CvRefresh cr{};
+        cr.nq = n;
+        cr.what = what;
+        cr.q = reinterpret_cast<const int64_t *>(st + o_q);
+        cr.perm = reinterpret_cast<const int32_t *>(st + o_perm);
+        cr.ref_row = reinterpret_cast<const int32_t *>(st + o_ref);
+        cr.pos = tio ? tio->pos : reinterpret_cast<const float *>(st + o_pos);
+        if (tio) {
+            cr.pre = tio->pre;
+            cr.t_row = tio->row;
+            cr.t_normal = tio->normal;
+            cr.t_min = tio->min_dist;
+            cr.t_max = tio->max_dist;
+            cr.t_desc = tio->desc;
+        }
+        cr.obs = reinterpret_cast<int32_t *>(st + o_obs);
+        cr.cnt = reinterpret_cast<int32_t *>(st + o_cnt);
+        cr.cursor = reinterpret_cast<int32_t *>(st + o_cursor);
+        cr.start = reinterpret_cast<int32_t *>(st + o_start);
+        cr.list_w = reinterpret_cast<int32_t *>(st + o_lw);
+        cr.list_g = reinterpret_cast<int32_t *>(st + o_lg);
+        cr.normal = reinterpret_cast<float *>(st + o_nr);
+        cr.min_dist = reinterpret_cast<float *>(st + o_mn);
+        cr.max_dist = reinterpret_cast<float *>(st + o_mx);
+        cr.desc = reinterpret_cast<uint8_t *>(st + o_ds);
+        cr.desc_kf = reinterpret_cast<int64_t *>(st + o_dkf);
+        cr.desc_idx = reinterpret_cast<int32_t *>(st + o_didx);
+        cr.n_slots = reinterpret_cast<int32_t *>(st + o_ns);
+        cr.status = reinterpret_cast<uint8_t *>(st + o_status);
+        cr.ent_cap = ent_cap;
+        cr.ents = g->d_ents.as<CvEntry>();
+        const CvRow *rows = g->d_rows.as<CvRow>();
+        if (g->rows > 0)
+            cv_launch_cull_count(g, n, cr.q, 1, cr.obs, cr.cnt);
+        hipLaunchKernelGGL(k_covis_refresh_scan, dim3(1), dim3(CV_LIST_BLOCK), 0, g->stream, cr, hdr);
+        if (g->rows > 0) {
+            const int grid = std::min((g->rows + CV_WAVES - 1) / CV_WAVES, 4096);
+            if (n <= g->lds_ids)
+                hipLaunchKernelGGL(k_covis_refresh_fill<true>, dim3(grid), dim3(CV_BLOCK), 8 * nn, g->stream, g->rows, rows,
+                                   g->d_pool.as<int64_t>(), g->pool_used, cr, hdr);
+            else {
+                g->global_queries++;
+                hipLaunchKernelGGL(k_covis_refresh_fill<false>, dim3(grid), dim3(CV_BLOCK), 0, g->stream, g->rows, rows,
+                                   g->d_pool.as<int64_t>(), g->pool_used, cr, hdr);
+            }
+            // the lists' lengths stay on the device: grids by their bounds, a workgroup past the end returns at once
+            const int grid_w = std::min(n, 16384);
+            const int grid_g = (int)std::min<int64_t>(std::min<int64_t>(n, g->pool_used / (CV_REFRESH_WAVE + 1) + 1), 4096);
+            const uint8_t *kp = g->d_kp.as<uint8_t>(), *descs = g->d_desc.as<uint8_t>();
+            const CvCentre *centres = g->d_centre.as<CvCentre>();
+            if (g->refresh_rows)
+                hipLaunchKernelGGL((k_covis_refresh<64, 1, true>), dim3(grid_w), dim3(64), 0, g->stream, 0, rows, kp, descs, centres,
+                                   g->scale, cr, hdr);
+            else
+                hipLaunchKernelGGL((k_covis_refresh<64, 1, false>), dim3(grid_w), dim3(64), 0, g->stream, 0, rows, kp, descs, centres,
+                                   g->scale, cr, hdr);
+            hipLaunchKernelGGL((k_covis_refresh<256, 4, false>), dim3(grid_g), dim3(256), 0, g->stream, 1, rows, kp, descs, centres,
+                               g->scale, cr, hdr);
+        }
+        he = hipGetLastError();
+    }
+    // the one wait: the header, status and n_slots, and what the caller asked for
+    auto fetch = [&](void *dst, size_t off, size_t bytes) {
+        if (he == hipSuccess)
+            he = hipMemcpyAsync(dst, st + off, bytes, hipMemcpyDeviceToHost, g->stream);
+    };
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(h, hdr, 8 * RH_WORDS, hipMemcpyDeviceToHost, g->stream);
+    fetch(h_status.data(), o_status, nn);
+    fetch(h_ns.data(), o_ns, 4 * nn);
+    if (desc_kf) {
+        h_dkf.resize(nn);
+        fetch(h_dkf.data(), o_dkf, 8 * nn);
+    }
+    if (desc_idx) {
+        h_didx.resize(nn);
+        fetch(h_didx.data(), o_didx, 4 * nn);
+    }
+    if (normal && (what & ORBGPU_REFRESH_NORMAL_DEPTH)) {
+        h_nr.resize(3 * nn);
+        fetch(h_nr.data(), o_nr, 12 * nn);
+    }
+    if (min_dist && (what & ORBGPU_REFRESH_NORMAL_DEPTH)) {
+        h_mn.resize(nn);
+        fetch(h_mn.data(), o_mn, 4 * nn);
+    }
+    if (max_dist && (what & ORBGPU_REFRESH_NORMAL_DEPTH)) {
+        h_mx.resize(nn);
+        fetch(h_mx.data(), o_mx, 4 * nn);
+    }
+    if (desc && (what & ORBGPU_REFRESH_DESCRIPTOR)) {
+        h_desc.resize(32 * nn);
+        fetch(h_desc.data(), o_ds, 32 * nn);
+    }
+    if ((rc = cv_sync_or_fail(g, he, "refresh query")) != ORBGPU_OK)
+        return rc;
+    if (h[RH_RANGE] || h[RH_ENTRIES] < 0 || h[RH_ENTRIES] > ent_cap) {
+        set_error("covisibility graph: an index left its range on the device");
+        return ORBGPU_EHIP;
+    }
+    // in/out: an entry the rules leave untouched keeps the caller's bytes
+    const unsigned no_point = ORBGPU_REFRESH_NO_OBS | ORBGPU_REFRESH_OVERFLOW | ORBGPU_REFRESH_UNKNOWN | ORBGPU_REFRESH_BAD;
+    res->n_entries = h[RH_ENTRIES];
+    for (int i = 0; i < n; i++) {
+        const unsigned s = h_status[(size_t)i];
+        status[i] = (uint8_t)s;
+        n_slots[i] = h_ns[(size_t)i];
+        res->max_obs = std::max(res->max_obs, n_slots[i]);
+        res->n_no_obs += (s & ORBGPU_REFRESH_NO_OBS) != 0;
+        res->n_overflow += (s & ORBGPU_REFRESH_OVERFLOW) != 0;
+        res->n_no_desc += (s & ORBGPU_REFRESH_NO_DESC) != 0;
+        res->n_no_centre += (s & ORBGPU_REFRESH_NO_CENTRE) != 0;
+        res->n_no_ref += (s & ORBGPU_REFRESH_NO_REF) != 0;
+        res->n_unknown += (s & ORBGPU_REFRESH_UNKNOWN) != 0;
+        res->n_bad += (s & ORBGPU_REFRESH_BAD) != 0;
+        const bool wrote_desc = (what & ORBGPU_REFRESH_DESCRIPTOR) && !(s & (no_point | ORBGPU_REFRESH_NO_DESC));
+        const bool wrote_nd = (what & ORBGPU_REFRESH_NORMAL_DEPTH) && !(s & (no_point | ORBGPU_REFRESH_NO_CENTRE | ORBGPU_REFRESH_NO_REF));
+        res->n_descriptors += wrote_desc;
+        res->n_normals += wrote_nd;
+        if (desc_kf)
+            desc_kf[i] = h_dkf[(size_t)i];
+        if (desc_idx)
+            desc_idx[i] = h_didx[(size_t)i];
+        if (wrote_desc && desc)
+            memcpy(desc + 32 * (size_t)i, h_desc.data() + 32 * (size_t)i, 32);
+        if (wrote_nd && normal)
+            memcpy(normal + 3 * (size_t)i, h_nr.data() + 3 * (size_t)i, 12);
+        if (wrote_nd && min_dist)
+            min_dist[i] = h_mn[(size_t)i];
+        if (wrote_nd && max_dist)
+            max_dist[i] = h_mx[(size_t)i];
+    }
+    return ORBGPU_OK;
+}
+
+} // namespace orbgpu

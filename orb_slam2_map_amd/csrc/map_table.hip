@@ -16,6 +16,7 @@
 #include "proj_internal.h"
 #include "id_table.h"
 #include "ransac_host.h"
+#include "refresh_internal.h"
 
 #include <algorithm>
 #include <climits>
@@ -126,6 +127,23 @@ __global__ __launch_bounds__(256) void k_table_compact(int n, const int32_t *__r
     d.bad[i] = o.bad[r];
     d.obs[i] = o.obs[r];
     d.id[i] = o.id[r];
+}
+
+// orbgpu_mappoint_table_refresh: what the observation graph's query reads of the table, entry i for the caller's i-th id
+// (row[i] < 0: the table does not know it)
+__global__ __launch_bounds__(256) void k_table_refresh_gather(int n, const int32_t *__restrict__ row, const float *__restrict__ world_pos,
+                                                              const uint8_t *__restrict__ bad, float *__restrict__ pos,
+                                                              uint8_t *__restrict__ pre)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const int r = row[i];
+    const bool ok = r >= 0 && !bad[r];
+    pre[i] = r < 0 ? ORBGPU_REFRESH_UNKNOWN : ok ? 0 : ORBGPU_REFRESH_BAD;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+        pos[3 * (size_t)i + a] = ok ? world_pos[3 * (size_t)r + a] : 0.f;
 }
 
 // The call's local map: thread i < m looks up ids[i] and copies the row into the call's arrays (what
@@ -692,6 +710,47 @@ int orbgpu_mappoint_table_read(orbgpu_mappoint_table *t, int64_t id, float *worl
     if (bad)
         *bad = b1;
     return ORBGPU_OK;
+}
+
+// MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth over the observation graph, from the table's positions
+// into the table's rows (R1-R8).  The gather runs on the table's stream and is waited for; the graph's kernels then run on
+// the graph's stream and write the table's columns; the caller serialises both handles.
+int orbgpu_mappoint_table_refresh(orbgpu_mappoint_table *t, orbgpu_covis_graph *g, int32_t n, const int64_t *mp_ids,
+                                  const int64_t *ref_kf_ids, uint32_t what, float *normal, float *min_dist, float *max_dist,
+                                  uint8_t *desc, int64_t *desc_kf, int32_t *desc_idx, int32_t *n_slots, uint8_t *status,
+                                  orbgpu_covis_refresh_result *res)
+{
+    ORBGPU_REQUIRE(t && g, "null argument");
+    std::vector<int32_t> perm;
+    int rc = covis_refresh_check(g, n, mp_ids, ref_kf_ids, what, n_slots, status, res, perm);
+    if (rc != ORBGPU_OK)
+        return rc;
+    ORBGPU_REQUIRE(covis_refresh_device_id(g) == t->device_id, "the table lives on device %d, the graph on device %d", t->device_id,
+                   covis_refresh_device_id(g));
+    if (n == 0)
+        return covis_refresh_run(g, 0, mp_ids, ref_kf_ids, nullptr, what, normal, min_dist, max_dist, desc, desc_kf, desc_idx, n_slots,
+                                 status, res, perm, nullptr);
+    if ((rc = select_device(t->device_id)) != ORBGPU_OK)
+        return rc;
+    Carver cv;
+    const size_t o_row = cv.take(4 * (size_t)n);
+    const size_t in_bytes = cv.off;
+    const size_t o_pos = cv.take(12 * (size_t)n), o_pre = cv.take((size_t)n);
+    if ((rc = t->stage.reserve(in_bytes)) != ORBGPU_OK || (rc = t->d_stage.reserve(cv.off)) != ORBGPU_OK)
+        return rc;
+    int32_t *h_row = (int32_t *)t->stage.p;
+    for (int i = 0; i < n; i++)
+        h_row[i] = host_find(t, mp_ids[i]);
+    uint8_t *d = t->d_stage.as<uint8_t>();
+    ORBGPU_HIP_TRY(hipMemcpyAsync(d, h_row, in_bytes, hipMemcpyHostToDevice, t->stream));
+    hipLaunchKernelGGL(k_table_refresh_gather, dim3((n + 255) / 256), dim3(256), 0, t->stream, n, (const int32_t *)(d + o_row),
+                       t->world_pos.as<float>(), t->bad.as<uint8_t>(), (float *)(d + o_pos), d + o_pre);
+    ORBGPU_HIP_TRY(hipGetLastError());
+    ORBGPU_HIP_TRY(hipStreamSynchronize(t->stream));  // the graph's stream takes over
+    const RefreshTableIO tio{(const float *)(d + o_pos), d + o_pre, (const int32_t *)(d + o_row), t->normal.as<float>(),
+                             t->min_dist.as<float>(), t->max_dist.as<float>(), t->desc.as<uint8_t>()};
+    return covis_refresh_run(g, n, mp_ids, ref_kf_ids, nullptr, what, normal, min_dist, max_dist, desc, desc_kf, desc_idx, n_slots, status,
+                             res, perm, &tio);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

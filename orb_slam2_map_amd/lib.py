@@ -309,6 +309,49 @@ class CovisCullingResult(C.Structure):
                 ("n_query_points", C.c_int32)]
 
 
+class CovisRefreshResult(C.Structure):
+    """orbgpu_covis_refresh_result"""
+    _fields_ = [("n_descriptors", C.c_int32), ("n_normals", C.c_int32), ("n_no_obs", C.c_int32), ("n_overflow", C.c_int32),
+                ("n_no_desc", C.c_int32), ("n_no_centre", C.c_int32), ("n_no_ref", C.c_int32), ("n_unknown", C.c_int32),
+                ("n_bad", C.c_int32), ("max_obs", C.c_int32), ("n_entries", C.c_int64)]
+
+
+REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH = 1, 2
+REFRESH_NO_OBS, REFRESH_OVERFLOW, REFRESH_NO_DESC, REFRESH_NO_CENTRE = 0x01, 0x02, 0x04, 0x08
+REFRESH_NO_REF, REFRESH_UNKNOWN, REFRESH_BAD = 0x10, 0x20, 0x40
+COVIS_REFRESH_MAX_OBS = 1024
+
+
+def _refresh_call(fn, head, ids, ref_kf_ids, mid, what, outputs, initial):
+    """the shared tail of CovisibilityGraph.refresh_points and MapPointTable.refresh: the in/out arrays (copies of `initial`
+    where given, zeros otherwise; None where `outputs` leaves them out), the call -- `head` before n, `mid` before `what` --
+    and the result as a dict"""
+    n = len(ids)
+    ref = np.ascontiguousarray(ref_kf_ids, np.int64).reshape(-1)
+    if len(ref) != n:
+        raise ValueError("one reference key frame per map point")
+    shapes = dict(normal=((n, 3), np.float32), min_dist=((n,), np.float32), max_dist=((n,), np.float32), desc=((n, 32), np.uint8),
+                  desc_kf=((n,), np.int64), desc_idx=((n,), np.int32))
+    out = {}
+    for name, (shape, dt) in shapes.items():
+        if name not in outputs:
+            out[name] = None
+        elif initial is not None and name in initial:
+            out[name] = np.array(initial[name], dt).reshape(shape)
+        else:
+            out[name] = np.zeros(shape, dt)
+    n_slots, status = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+    res = CovisRefreshResult()
+    check(fn(*head, n, _p(ids), _p(ref), *mid, int(what), _p(out["normal"]), _p(out["min_dist"]), _p(out["max_dist"]), _p(out["desc"]),
+             _p(out["desc_kf"]), _p(out["desc_idx"]), _p(n_slots), _p(status), C.byref(res)))
+    out = {k: v for k, v in out.items() if v is not None}
+    out.update(n_slots=n_slots[:n].copy(), status=status[:n].copy())
+    out.update({name: getattr(res, name) for name, _ in CovisRefreshResult._fields_})
+    return out
+
+
+REFRESH_OUTPUTS = ("normal", "min_dist", "max_dist", "desc", "desc_kf", "desc_idx")
+
 ABI_SYMBOLS = [
     "orbgpu_last_error_string", "orbgpu_abi_version", "orbgpu_device_count", "orbgpu_measure_copy_bandwidth",
     "orbgpu_set_trig_mode", "orbgpu_get_trig_mode", "orbgpu_trig_table_info", "orbgpu_trig_host_eval", "orbgpu_trig_eval",
@@ -356,6 +399,8 @@ ABI_SYMBOLS = [
     "orbgpu_covis_graph_set_parent", "orbgpu_covis_graph_set_covisibles", "orbgpu_covis_local_map",
     "orbgpu_covis_connections", "orbgpu_covis_graph_debug_global_queries",
     "orbgpu_covis_graph_set_keypoints", "orbgpu_covis_observations", "orbgpu_covis_keyframe_culling",
+    "orbgpu_covis_graph_set_scale_factors", "orbgpu_covis_graph_set_descriptors", "orbgpu_covis_graph_set_centres",
+    "orbgpu_covis_refresh_points", "orbgpu_mappoint_table_refresh",
     "orbgpu_vocabulary_create", "orbgpu_vocabulary_destroy", "orbgpu_vocabulary_size", "orbgpu_bow_transform",
     "orbgpu_bow_transform_batch_device", "orbgpu_search_by_bow", "orbgpu_search_by_bow_batch_device",
     "orbgpu_search_by_bow_keyframes", "orbgpu_search_for_triangulation", "orbgpu_search_for_initialization", "orbgpu_fuse", "orbgpu_fuse_sim3",
@@ -481,6 +526,11 @@ def lib():
         "orbgpu_covis_graph_set_keypoints": [vp, C.c_int64, i32, vp],
         "orbgpu_covis_observations": [vp, i32, vp, vp, vp],
         "orbgpu_covis_keyframe_culling": [vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp],
+        "orbgpu_covis_graph_set_scale_factors": [vp, i32, vp],
+        "orbgpu_covis_graph_set_descriptors": [vp, C.c_int64, i32, vp],
+        "orbgpu_covis_graph_set_centres": [vp, i32, vp, vp, vp],
+        "orbgpu_covis_refresh_points": [vp, i32, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "orbgpu_mappoint_table_refresh": [vp, vp, i32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     }
     for name, args in sigs.items():
         fn = getattr(L, name, None)
@@ -988,6 +1038,13 @@ class MapPointTable:
                                                 C.byref(bad)))
         return {"world_pos": wp, "normal": nr, "min_dist": mn.value, "max_dist": mx.value, "desc": ds,
                 "has_observations": ob.value, "bad": bad.value}
+
+    def refresh(self, graph, mp_ids, ref_kf_ids, what=REFRESH_DESCRIPTOR | REFRESH_NORMAL_DEPTH, outputs=(), initial=None):
+        """CovisibilityGraph.refresh_points with the positions taken from the table's rows and the results written into
+        them on the device; `outputs` names the optional host copies (REFRESH_OUTPUTS for all).  The caller serialises both
+        handles."""
+        ids = np.ascontiguousarray(mp_ids, np.int64).reshape(-1)
+        return _refresh_call(self.L.orbgpu_mappoint_table_refresh, (self.h, graph.h), ids, ref_kf_ids, (), what, outputs, initial)
 
 
 class DeviceFrame:
@@ -2479,6 +2536,37 @@ class CovisibilityGraph:
         out.update(verdict=verdict[:n].copy(), n_mps=n_mps[:n].copy(), n_redundant=n_red[:n].copy(),
                    bad_point_ids=bad[:min(res.n_points_bad, int(point_capacity))].copy())
         return out
+
+    def set_scale_factors(self, scale_factors):
+        """KeyFrame::mvScaleFactors, one table per graph (R6)"""
+        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        check(self.L.orbgpu_covis_graph_set_scale_factors(self.h, len(sf), _p(sf)))
+
+    def set_descriptors(self, kf_id, desc):
+        """mDescriptors of a key frame, [n_slots][32] bytes, once behind add_keyframe (R4)"""
+        d = np.ascontiguousarray(np.zeros((0, 32), np.uint8) if desc is None else desc, np.uint8).reshape(-1, 32)
+        check(self.L.orbgpu_covis_graph_set_descriptors(self.h, int(kf_id), len(d), _p(d)))
+
+    def set_centres(self, kf_ids, centres):
+        """KeyFrame::GetCameraCenter() of a batch of key frames (R5); returns how many ids named a key frame of the graph"""
+        kf_ids = self._ids(np.atleast_1d(kf_ids))
+        c = np.ascontiguousarray(centres, np.float32).reshape(-1, 3)
+        if len(c) != len(kf_ids):
+            raise ValueError("one centre per key frame")
+        k = C.c_int32()
+        check(self.L.orbgpu_covis_graph_set_centres(self.h, len(kf_ids), _p(kf_ids), _p(c), C.byref(k)))
+        return k.value
+
+    def refresh_points(self, mp_ids, ref_kf_ids, world_pos, what=REFRESH_DESCRIPTOR | REFRESH_NORMAL_DEPTH, outputs=REFRESH_OUTPUTS,
+                       initial=None):
+        """MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth for a batch of points (R1-R8): dict of the
+        outputs named in `outputs` (in/out ones start from `initial[name]` where given), n_slots, status and the fields of
+        orbgpu_covis_refresh_result.  The graph is not modified."""
+        ids = self._ids(mp_ids)
+        pos = np.ascontiguousarray(world_pos, np.float32).reshape(-1, 3)
+        if len(pos) != len(ids):
+            raise ValueError("one position per map point")
+        return _refresh_call(self.L.orbgpu_covis_refresh_points, (self.h,), ids, ref_kf_ids, (_p(pos),), what, outputs, initial)
 
 
 def search_by_bow(desc_kf, angle_kf, valid_kf, node_kf, desc_f, angle_f, node_f, th_low=TH_LOW, nnratio=0.7,

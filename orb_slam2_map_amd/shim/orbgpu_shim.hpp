@@ -2724,6 +2724,103 @@ template <typename KeyFrameT, typename MapPointT> class CovisibilityGraphT {
         return culled;
     }
 
+    // ---- MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth over the graph (R1-R8) ----
+    // hook: once per map, KeyFrame::mvScaleFactors (the same for every key frame)
+    void SetScaleFactors(const std::vector<float> &v)
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        check(orbgpu_covis_graph_set_scale_factors(h_, (int32_t)v.size(), v.data()), "CovisibilityGraph::SetScaleFactors");
+    }
+    // hook: behind SetKeyPoints(pKF), once -- descriptors do not change.  desc_row(pKF, i) -> the 32 bytes of
+    // mDescriptors.row(i) (a const member: no lock of the key frame)
+    template <typename DescRow> void SetDescriptors(KeyFrameT *pKF, DescRow desc_row)
+    {
+        const size_t n = (size_t)pKF->N;
+        std::vector<uint8_t> d(32 * n);
+        for (size_t i = 0; i < n; i++)
+            std::memcpy(&d[32 * i], desc_row(pKF, i), 32);
+        std::lock_guard<std::mutex> g(mu_);
+        check(orbgpu_covis_graph_set_descriptors(h_, (int64_t)pKF->mnId, (int32_t)n, d.data()), "CovisibilityGraph::SetDescriptors");
+    }
+    // hook: KeyFrame::SetPose (one key frame), and after the write-back of a bundle adjustment or of the essential graph
+    // (every key frame it moved, one call).  centre(pKF, out[3]) writes GetCameraCenter(); it runs outside the mutex.
+    template <typename Centre> void SetCentres(const std::vector<KeyFrameT *> &keyframes, Centre centre)
+    {
+        std::vector<int64_t> ids(keyframes.size());
+        std::vector<float> ow(3 * keyframes.size());
+        for (size_t i = 0; i < keyframes.size(); i++) {
+            ids[i] = (int64_t)keyframes[i]->mnId;
+            centre(keyframes[i], &ow[3 * i]);
+        }
+        std::lock_guard<std::mutex> g(mu_);
+        check(orbgpu_covis_graph_set_centres(h_, (int32_t)ids.size(), ids.data(), ow.data(), nullptr), "CovisibilityGraph::SetCentres");
+    }
+    // The two calls that end every chain that edits the map, for a batch of points.  `what`: ORBGPU_REFRESH_DESCRIPTOR |
+    // ORBGPU_REFRESH_NORMAL_DEPTH.  access supplies ref_kf(pMP) -> KeyFrameT * (mpRefKF), world_pos(pMP) -> const float *
+    // (read before the call; unused with a table) and set_refreshed(pMP, normal, minDist, maxDist, desc): normal is null
+    // where the status left normal and depth untouched, desc is null where it left the descriptor untouched; a point with
+    // neither is not called.  Null, bad and repeated points are passed over (mbBad returns at MapPoint.cc:251 / :338).
+    // With a table the positions come from its rows and the results go into its rows on the device -- no Upsert afterwards;
+    // its mutex is taken first, then this class's, and both are released before set_refreshed runs.
+    template <typename Access>
+    orbgpu_covis_refresh_result RefreshMapPoints(const std::vector<MapPointT *> &points, unsigned what, Access &access,
+                                                 MapPointTableT<MapPointT> *table = nullptr)
+    {
+        std::vector<MapPointT *> pts;
+        std::vector<int64_t> ids, refs;
+        std::vector<float> pos;
+        {
+            std::vector<int64_t> seen;
+            for (MapPointT *p : points)
+                if (p && !p->isBad())
+                    seen.push_back((int64_t)p->mnId);
+            std::sort(seen.begin(), seen.end());
+            std::vector<char> taken(seen.size(), 0);
+            for (MapPointT *p : points) {
+                if (!p || p->isBad())
+                    continue;
+                const size_t at = (size_t)(std::lower_bound(seen.begin(), seen.end(), (int64_t)p->mnId) - seen.begin());
+                if (taken[at])
+                    continue;
+                taken[at] = 1;
+                KeyFrameT *ref = access.ref_kf(p);
+                pts.push_back(p);
+                ids.push_back((int64_t)p->mnId);
+                refs.push_back(ref ? (int64_t)ref->mnId : -1);
+                if (!table) {
+                    const float *w = access.world_pos(p);
+                    pos.insert(pos.end(), w, w + 3);
+                }
+            }
+        }
+        const size_t n = pts.size();
+        std::vector<float> normal(3 * n), mn(n), mx(n);
+        std::vector<uint8_t> desc(32 * n), status(n);
+        std::vector<int32_t> n_slots(n);
+        orbgpu_covis_refresh_result res;
+        if (table) {
+            std::lock_guard<std::mutex> table_lock(table->mutex());
+            std::lock_guard<std::mutex> g(mu_);
+            check(orbgpu_mappoint_table_refresh(table->handle(), h_, (int32_t)n, ids.data(), refs.data(), what, normal.data(), mn.data(),
+                                                mx.data(), desc.data(), nullptr, nullptr, n_slots.data(), status.data(), &res),
+                  "CovisibilityGraph::RefreshMapPoints (table)");
+        } else {
+            std::lock_guard<std::mutex> g(mu_);
+            check(orbgpu_covis_refresh_points(h_, (int32_t)n, ids.data(), refs.data(), pos.data(), what, normal.data(), mn.data(), mx.data(),
+                                              desc.data(), nullptr, nullptr, n_slots.data(), status.data(), &res),
+                  "CovisibilityGraph::RefreshMapPoints");
+        }
+        const unsigned no_point = ORBGPU_REFRESH_NO_OBS | ORBGPU_REFRESH_OVERFLOW | ORBGPU_REFRESH_UNKNOWN | ORBGPU_REFRESH_BAD;
+        for (size_t i = 0; i < n; i++) {
+            const unsigned s = status[i];
+            const bool has_desc = (what & ORBGPU_REFRESH_DESCRIPTOR) && !(s & (no_point | ORBGPU_REFRESH_NO_DESC));
+            const bool has_normal = (what & ORBGPU_REFRESH_NORMAL_DEPTH) && !(s & (no_point | ORBGPU_REFRESH_NO_CENTRE | ORBGPU_REFRESH_NO_REF));
+            if (has_desc || has_normal)
+                access.set_refreshed(pts[i], has_normal ? &normal[3 * i] : nullptr, mn[i], mx[i], has_desc ? &desc[32 * i] : nullptr);
+        }
+        return res;
+    }
+
     // host only: a batch of slot edits as the ABI's three arrays
     static void MarshalSlots(const std::vector<SlotEdit> &edits, std::vector<int64_t> &kf_ids, std::vector<int32_t> &idx,
                              std::vector<int64_t> &mp_ids)
