@@ -1779,8 +1779,27 @@ int orbgpu_statistical_outlier_removal(const orbgpu_point_xyzrgba *in, int64_t n
  * *n_candidates is always the full count: if `capacity` is smaller the call writes `capacity` ids and still returns
  * ORBGPU_OK.  The device is bound by the first call that computes or stores; without one those calls return ORBGPU_EHIP
  * (no CPU fallback).  A database is used by ONE host thread at a time (KeyFrameDatabaseT serialises); every call returns
- * synchronised.  Limits: 2^24 rows between two clears (an erased row is dead, rows and pool space come back on clear),
- * 2^24 entries per vector, 2^30 entries in all. */
+ * synchronised.  Limits: 2^24 rows between two clears or compactions (an erased row is dead; rows and pool space come
+ * back on clear and on orbgpu_keyframe_db_compact), 2^24 entries per vector, 2^30 entries in all.
+ * Compaction (orbgpu_keyframe_db_compact; an edit: host call, one host thread at a time, returns synchronised; it takes the
+ * lifecycle lock because it always allocates when it does anything), D1-D4:
+ *   D1  rows that were erased are dropped; the live rows stay in add order, each with its BoW vector, its neighbour list,
+ *       its add sequence number (K1 orders by it) and its relocalisation score register (K5).
+ *   D2  invisible to add, erase, score, detect_loop, detect_reloc, set_covisibles and size: tests/kfdb_model.py has no dead
+ *       rows.  The one exception: last_query reports n = 0 after a compact call until the next detect call, as after clear
+ *       (its per-row columns describe rows that may be gone; the same after a call that found nothing to drop, so that
+ *       the model needs no dead rows to say when).
+ *   D3  afterwards row and pool capacity are what the doubling rules give a fresh database with the same creation
+ *       arguments once it holds rows_after rows and slots_after entries: the memory comes back.
+ *   D4  nothing erased since the last clear or compaction: compacted = 0, no allocation, no device call, also on a handle
+ *       that was never bound.  A failure (ORBGPU_ENOMEM, ORBGPU_EHIP) leaves the database bit for bit as it was. */
+typedef struct orbgpu_compact_result {
+    int32_t compacted;               /* 0: nothing to drop, the handle was not touched */
+    int32_t rows_before, rows_after; /* rows of the handle, dead / bad ones included */
+    int32_t rows_bad_kept;           /* graph: bad rows kept by C1; database: 0 */
+    int32_t row_capacity;
+    int64_t slots_before, slots_after, slot_capacity; /* pool entries in use / allocated */
+} orbgpu_compact_result;
 typedef struct orbgpu_keyframe_db orbgpu_keyframe_db;
 int orbgpu_keyframe_db_create(int32_t n_words, int32_t scoring, int32_t device_id, int32_t initial_rows,
                               orbgpu_keyframe_db **out);
@@ -1807,6 +1826,8 @@ int orbgpu_keyframe_db_last_query(orbgpu_keyframe_db *db, int32_t capacity, int6
 /* Tests: how many score launches of this handle read the query from global memory (a query longer than the LDS staging, or
  * ORBGPU_DEBUG_KFDB_LDS_WORDS=<k> in the environment: a query of more than k words takes that path). */
 int orbgpu_keyframe_db_debug_global_queries(const orbgpu_keyframe_db *db, int64_t *n);
+/* D1-D4 above.  res may be NULL. */
+int orbgpu_keyframe_db_compact(orbgpu_keyframe_db *db, orbgpu_compact_result *res);
 
 /* ======================================================================================
  * Observation graph  (Tracking::UpdateLocalMap, Tracking.cc:1499-1643; KeyFrame::UpdateConnections, KeyFrame.cc:327-417;
@@ -1899,7 +1920,33 @@ int orbgpu_keyframe_db_debug_global_queries(const orbgpu_keyframe_db *db, int64_
  * Refused with ORBGPU_EINVAL before any device is touched, nothing changed: an id that is present (bad rows included), a
  * negative id, idx outside the row, a map point id below -1, n_slots (or a query) above ORBGPU_COVIS_MAX_SLOTS, more than
  * 10 covisibles, more than 2^20 rows or 2^30 pool slots (first choices, not measured limits).  A local map of more than
- * 2^22 points returns ORBGPU_ECAPACITY.  The pool space of a bad row comes back on clear only (no compaction yet).
+ * 2^22 points returns ORBGPU_ECAPACITY.  The rows and the pool space of bad rows come back on clear and on
+ * orbgpu_covis_graph_compact (41 bytes per slot once descriptors are set).
+ * Compaction (orbgpu_covis_graph_compact; an edit in the sense above; it takes the lifecycle lock because it always
+ * allocates when it does anything), C1-C7:
+ *   C1 kept rows   every row that is not bad; a bad row if and only if at least one not-bad row's parent value equals its
+ *              id (V6(c) appends a known parent with no bad test, so such a row must stay a row).  Kept rows keep their
+ *              relative add order; all other bad rows are dropped.
+ *   C2 a dropped id is an unknown id from then on, for every call: add_keyframe accepts it again, as a new empty row at the
+ *              end; set_bad and set_slots no longer count it in *known; local_map counts it in n_unknown_previous if the
+ *              previous list holds it; set_parent and set_covisibles for it go to the pending maps as for any id that is
+ *              no row; set_keypoints, set_descriptors refuse it.  Deviation: a later set_parent(live, dropped_id) stores
+ *              an unknown parent, which V6(c) does not append -- without compaction the bad row would be appended (the
+ *              reference's ChangeParent never hands out a bad parent).  Stored covisible lists and parent values of kept
+ *              rows are not rewritten: they are ids, resolved when a query runs.
+ *   C3 a kept row is what it was: id, parent, bad, covisibles, descriptor flag, n_slots, centre, stamp and count.  The
+ *              slots, attribute bytes and descriptors of a not-bad row are the same bytes at a new offset, the exclusive
+ *              prefix sum of n_slots over the kept not-bad rows in order.  A kept bad row owns no pool space afterwards;
+ *              its n_slots stays (the refusals of set_slots, set_keypoints and set_descriptors read it), and its pool
+ *              offset is a negative value that every reader takes for "no slot": the point gather of V6 does read the
+ *              offset of a bad parent it appended and finds all its slots outside the pool, as it found them empty before.
+ *   C4 untouched: the pending covisible / parent values of ids that are no rows, the scale factors, the query stamp, the
+ *              descriptor column's existence, per-call scratch.
+ *   C5 capacities  afterwards row and pool capacity are what the doubling rules give a fresh graph with the same creation
+ *              arguments once it holds rows_after rows and slots_after slots: the memory comes back.
+ *   C6 nothing to do   no row would be dropped and no kept bad row owns pool space: compacted = 0, no allocation, no
+ *              device call, also on a handle that was never bound (all zeros on an empty one).
+ *   C7 all or nothing   a failure (ORBGPU_ENOMEM, ORBGPU_EHIP) leaves the graph bit for bit as it was.
  * Counts are always the full ones; at most `capacity` entries of a list are written.  prev_kf_ids and kf_ids may be one
  * array.  Without a device the calls that compute or store return ORBGPU_EHIP (no CPU fallback). */
 #define ORBGPU_COVIS_MAX_SLOTS 65536
@@ -1930,6 +1977,8 @@ int orbgpu_covis_connections(orbgpu_covis_graph *g, int64_t kf_id, int32_t th, i
 /* Tests: how many vote launches of this handle read the query from global memory (more distinct ids than the LDS staging
  * holds, or than ORBGPU_DEBUG_COVIS_LDS_IDS=<k>, read when the handle is created). */
 int orbgpu_covis_graph_debug_global_queries(const orbgpu_covis_graph *g, int64_t *n);
+/* C1-C7 above.  res may be NULL. */
+int orbgpu_covis_graph_compact(orbgpu_covis_graph *g, orbgpu_compact_result *res);
 #define ORBGPU_COVIS_MAX_LEVELS 16
 #define ORBGPU_COVIS_KP_STEREO 0x40
 #define ORBGPU_COVIS_KP_FAR 0x80

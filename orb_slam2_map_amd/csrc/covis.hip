@@ -53,6 +53,8 @@
 // The entry buffer is as long as the pool slots in use -- a slot holds one id and the query's ids are distinct, so no call
 // needs more -- which spares the wait for the total: one wait per call.  The graph is not modified.
 #include "common.h"
+#include "compact_kernels.h"
+#include "compact_plan.h"
 #include "id_table.h"
 #include "refresh_internal.h"
 
@@ -81,6 +83,7 @@ constexpr int CV_CHUNK = 1024;  // gather positions per chunk: four steps of a 2
 constexpr int32_t CV_POS_NONE = 0x7F7F7F7F;  // (hipMemset's byte pattern) above every gather position (< 2^30)
 constexpr int CV_LEVELS = ORBGPU_COVIS_MAX_LEVELS;
 constexpr int CV_MAX_CANDIDATES = 1 << 16;      // key frames of one culling call
+constexpr int64_t CV_OFF_NONE = INT64_MIN / 2;  // CvRow::off of a bad row a compaction kept (C3): off + idx < 0 for every slot index
 constexpr int CV_MAX_QUERY_POINTS = 1 << 20;    // distinct points of their slots (64 bytes of counters each); a first choice
 static_assert(CV_LEVELS == 16 && (ORBGPU_COVIS_KP_STEREO | ORBGPU_COVIS_KP_FAR) == 0xC0, "the attribute byte of V1");
 
@@ -1171,6 +1174,13 @@ static int cv_reserve_locked(DevBuf &b, size_t bytes)
     return lifecycle_locked_unless(bytes <= b.bytes, lifecycle_mutex(), [&] { return b.reserve(bytes); });
 }
 
+// what the first call allocates for (the creation arguments, or their defaults); orbgpu_covis_graph_compact returns to it (C5)
+static int cv_initial_rows(const orbgpu_covis_graph *g) { return g->initial_rows > 0 ? g->initial_rows : 1024; }
+static int64_t cv_initial_slots(const orbgpu_covis_graph *g)
+{
+    return g->initial_slots > 0 ? g->initial_slots : std::min<int64_t>((int64_t)cv_initial_rows(g) * 1024, 1 << 22);
+}
+
 // first call that needs the device: select it, create the stream, allocate for initial_rows / initial_slots
 static int cv_bind(orbgpu_covis_graph *g)
 {
@@ -1186,8 +1196,8 @@ static int cv_bind(orbgpu_covis_graph *g)
             return ORBGPU_EHIP;
         }
     }
-    const int rows0 = g->initial_rows > 0 ? g->initial_rows : 1024;
-    const int64_t slots0 = g->initial_slots > 0 ? g->initial_slots : std::min<int64_t>((int64_t)rows0 * 1024, 1 << 22);
+    const int rows0 = cv_initial_rows(g);
+    const int64_t slots0 = cv_initial_slots(g);
     if ((rc = cv_grow_rows(g, rows0)) != ORBGPU_OK || (rc = cv_grow_pool(g, slots0)) != ORBGPU_OK)
         return rc;
     if ((rc = g->d_hdr.reserve(8 * CH_WORDS)) != ORBGPU_OK)
@@ -1701,6 +1711,145 @@ int orbgpu_covis_graph_debug_global_queries(const orbgpu_covis_graph *g, int64_t
 {
     ORBGPU_REQUIRE(g && n, "null argument");
     *n = g->global_queries;
+    return ORBGPU_OK;
+}
+
+// C1-C7 (orbgpu.h).  The plan is host work over the mirror (compact_plan.h); the copies run inside the transaction of
+// id_table.h, which swaps rows, hash and pool columns only after everything has arrived.
+int orbgpu_covis_graph_compact(orbgpu_covis_graph *g, orbgpu_compact_result *res)
+{
+    ORBGPU_REQUIRE(g, "null argument");
+    const int n = g->rows;
+    std::vector<int32_t> bad((size_t)n), len((size_t)n);
+    std::vector<int64_t> ids((size_t)n), par((size_t)n);
+    std::vector<uint8_t> owns((size_t)n);
+    for (int r = 0; r < n; r++) {
+        const CvRow &row = g->h_rows[(size_t)r];
+        bad[(size_t)r] = row.bad;
+        len[(size_t)r] = row.n_slots;
+        ids[(size_t)r] = row.id;
+        par[(size_t)r] = row.parent;
+        owns[(size_t)r] = !row.bad;
+    }
+    const std::vector<uint8_t> keep = compact_keep_graph(n, bad.data(), ids.data(), par.data());
+    const CompactPlan plan = compact_plan(n, len.data(), keep.data(), owns.data(), g->pool_used, CV_OFF_NONE);
+    const int m = (int)plan.src.size();
+    orbgpu_compact_result out{};
+    out.rows_before = out.rows_after = n;
+    out.rows_bad_kept = g->n_bad;
+    out.row_capacity = g->row_cap;
+    out.slots_before = out.slots_after = g->pool_used;
+    out.slot_capacity = g->pool_cap;
+    if (!plan.needed) {  // C6
+        if (res)
+            *res = out;
+        return ORBGPU_OK;
+    }
+    int rc = cv_bind(g);  // (a graph with rows is bound: this selects the device)
+    if (rc != ORBGPU_OK)
+        return rc;
+    const int ncap = (int)compact_capacity(1, cv_initial_rows(g), m);
+    const int64_t pcap = compact_capacity(1024, cv_initial_slots(g), plan.pool_after);
+    // the mirrors as they will be, built before anything is touched
+    std::vector<CvRow> n_rows((size_t)m);
+    std::vector<CvCentre> n_centre((size_t)m);
+    std::vector<int64_t> n_pool((size_t)plan.pool_after), old_off((size_t)m);
+    std::vector<uint8_t> n_kp((size_t)plan.pool_after);
+    std::vector<int32_t> n_order, new_of((size_t)n, -1);
+    int n_bad = 0;
+    for (int i = 0; i < m; i++) {
+        const size_t r = (size_t)plan.src[(size_t)i];
+        const int64_t off = plan.off[(size_t)i];
+        const int32_t l = plan.len[(size_t)i];
+        n_rows[(size_t)i] = g->h_rows[r];
+        n_rows[(size_t)i].off = off;
+        n_centre[(size_t)i] = g->h_centre[r];
+        old_off[(size_t)i] = g->h_rows[r].off;
+        new_of[r] = i;
+        n_bad += g->h_rows[r].bad != 0;
+        if (l > 0) {
+            std::copy_n(g->h_pool.begin() + (ptrdiff_t)g->h_rows[r].off, l, n_pool.begin() + (ptrdiff_t)off);
+            std::copy_n(g->h_kp.begin() + (ptrdiff_t)g->h_rows[r].off, l, n_kp.begin() + (ptrdiff_t)off);
+        }
+    }
+    n_order.reserve((size_t)m);
+    for (int32_t r : g->h_order)  // ascending id stays ascending id
+        if (new_of[(size_t)r] >= 0)
+            n_order.push_back(new_of[(size_t)r]);
+    Carver c;
+    const size_t o_old = c.take(8 * (size_t)std::max(m, 1)), o_new = c.take(8 * (size_t)std::max(m, 1)),
+                 o_src = c.take(4 * (size_t)std::max(m, 1)), o_len = c.take(4 * (size_t)std::max(m, 1));
+    std::vector<char> stage(c.off);
+    if (m > 0) {
+        memcpy(stage.data() + o_old, old_off.data(), 8 * (size_t)m);
+        memcpy(stage.data() + o_new, plan.off.data(), 8 * (size_t)m);
+        memcpy(stage.data() + o_src, plan.src.data(), 4 * (size_t)m);
+        memcpy(stage.data() + o_len, plan.len.data(), 4 * (size_t)m);
+    }
+    TableStreamOps ops{g->stream, "compacting the covisibility graph"};
+    const IdColumn<DevBuf> pool_cols[3] = {{&g->d_pool, 8}, {&g->d_kp, 1}, {&g->d_desc, 32}};
+    const int n_pool_cols = g->has_desc_col ? 3 : 2;
+    // d_stage, which carries the plan, is per-call scratch outside the transaction (as in orbgpu_mappoint_table_retain)
+    auto fill = [&](const DevBuf *nb, const DevBuf *np, int l2, IdHash &nh) -> int {
+        if (m > 0) {
+            const int rr = g->d_stage.reserve(c.off);
+            if (rr != ORBGPU_OK)
+                return rr;
+            char *st = g->d_stage.as<char>();
+            if (ops.upload(st, stage.data(), c.off) || ops.upload(nb[3].p, n_order.data(), 4 * (size_t)m))
+                return ORBGPU_EHIP;
+            const int32_t *src = reinterpret_cast<const int32_t *>(st + o_src);
+            const int64_t *noff = reinterpret_cast<const int64_t *>(st + o_new);
+            const dim3 grid((unsigned)((m + 255) / 256)), block(256);
+            hipLaunchKernelGGL(k_compact_rows<CvRow>, grid, block, 0, g->stream, m, src, noff, n, g->d_rows.as<CvRow>(),
+                               static_cast<CvRow *>(nb[0].p));
+            hipLaunchKernelGGL(k_compact_gather<int32_t>, grid, block, 0, g->stream, m, src, n, g->d_count.as<int32_t>(),
+                               static_cast<int32_t *>(nb[1].p));
+            hipLaunchKernelGGL(k_compact_gather<int32_t>, grid, block, 0, g->stream, m, src, n, g->d_stamp.as<int32_t>(),
+                               static_cast<int32_t *>(nb[2].p));
+            hipLaunchKernelGGL(k_compact_gather<CvCentre>, grid, block, 0, g->stream, m, src, n, g->d_centre.as<CvCentre>(),
+                               static_cast<CvCentre *>(nb[4].p));
+            if (plan.pool_after > 0) {
+                CompactPool<3> p{};
+                for (int k = 0; k < n_pool_cols; k++) {
+                    p.src[k] = static_cast<const uint8_t *>(pool_cols[k].buf->p);
+                    p.dst[k] = static_cast<uint8_t *>(np[k].p);
+                }
+                hipLaunchKernelGGL((k_compact_pool<8, 1, 32>), dim3((unsigned)compact_pool_grid(m)), dim3(COMPACT_BLOCK), 0, g->stream, m,
+                                   reinterpret_cast<const int64_t *>(st + o_old), noff, reinterpret_cast<const int32_t *>(st + o_len),
+                                   g->pool_used, pcap, p);
+            }
+            if (ops.done(hipGetLastError()))
+                return ORBGPU_EHIP;
+        }
+        nh.rebuild(l2);
+        for (int i = 0; i < m; i++)
+            nh.insert(n_rows[(size_t)i].id, i);
+        return ORBGPU_OK;
+    };
+    {
+        std::lock_guard<std::mutex> lifecycle(lifecycle_mutex());
+        const IdTableParts<DevBuf> parts{g->row_cols, CV_ROW_COLS, CV_ROW_COLS, &g->d_hkeys, &g->d_hvals, &g->hash, &g->row_cap};
+        if ((rc = id_table_compact(parts, ncap, pool_cols, n_pool_cols, (size_t)pcap, ops, fill)) != ORBGPU_OK)
+            return rc;
+    }
+    g->h_rows.swap(n_rows);
+    g->h_centre.swap(n_centre);
+    g->h_pool.swap(n_pool);
+    g->h_kp.swap(n_kp);
+    g->h_order.swap(n_order);
+    g->rows = m;
+    g->n_bad = n_bad;
+    g->pool_used = plan.pool_after;
+    g->pool_cap = pcap;
+    out.compacted = 1;
+    out.rows_after = m;
+    out.rows_bad_kept = n_bad;
+    out.row_capacity = g->row_cap;
+    out.slots_after = g->pool_used;
+    out.slot_capacity = g->pool_cap;
+    if (res)
+        *res = out;
     return ORBGPU_OK;
 }
 

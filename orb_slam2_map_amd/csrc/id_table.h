@@ -14,6 +14,9 @@
 // new buffer and returns the first failure's code (ORBGPU_ENOMEM: an allocation, ORBGPU_EHIP: an operation); the table is
 // then bit for bit what it was -- pointers, sizes, capacity, rows, host hash.
 //
+// id_table_compact is the same transaction for a table whose rows own ranges of a pool (observation graph, key-frame
+// database; compact_plan.h plans it): the pool columns are replaced with the rows, all or nothing.
+//
 // The lifecycle lock (common.h) guards what allocates and frees device memory.  A call that may grow a table takes it
 // on the growing branch only (lifecycle_locked_unless); creation, which holds it already, calls the unlocked form.
 #pragma once
@@ -106,6 +109,28 @@ template <typename Buf, typename Ops> int id_table_grow(const IdTableParts<Buf> 
         nh.rebuild(l2);
         return (int)ORBGPU_OK;
     });
+}
+
+// Compaction of a table whose rows own ranges of a pool (observation graph, key-frame database): the row columns and the
+// hash are replaced at capacity `ncap` as above, and with them the pool columns at `pool_cap` entries.  The new pool
+// buffers are allocated first; fill(new columns, new pool columns, log2cap, new hash) writes rows, pool and hash; the
+// pool columns are swapped in only after the row swap has succeeded (id_table_replace has synchronised by then, so every
+// copy has arrived) and released on every failure path.  A failure leaves table and pool bit for bit as they were.
+template <typename Buf, typename Ops, typename Fill>
+int id_table_compact(const IdTableParts<Buf> &t, int ncap, const IdColumn<Buf> *pool, int n_pool, size_t pool_cap, Ops &ops, Fill fill)
+{
+    std::vector<Buf> np((size_t)n_pool);
+    int rc = ORBGPU_OK;
+    for (int i = 0; i < n_pool && rc == ORBGPU_OK; i++)
+        rc = np[(size_t)i].reserve(pool[i].elt * pool_cap);
+    if (rc == ORBGPU_OK)
+        rc = id_table_replace(t, ncap, ops, [&](const Buf *nb, int l2, IdHash &nh) { return fill(nb, np.data(), l2, nh); });
+    if (rc == ORBGPU_OK)
+        for (int i = 0; i < n_pool; i++)
+            std::swap(*pool[i].buf, np[(size_t)i]);
+    for (Buf &b : np)  // the new buffers of a failure, the old ones of a success
+        b.release();
+    return rc;
 }
 
 } // namespace orbgpu

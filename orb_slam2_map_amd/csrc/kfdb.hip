@@ -19,6 +19,8 @@
 // entry point.  Every call returns synchronised; the caller serialises (KeyFrameDatabaseT does).  The device is bound at
 // the first call that needs it, so that refusals (K8) are answered without one.
 #include "common.h"
+#include "compact_kernels.h"
+#include "compact_plan.h"
 #include "id_table.h"
 
 #include <algorithm>
@@ -32,7 +34,7 @@
 namespace orbgpu {
 
 constexpr int KF_MAX_NB = 10;             // GetBestCovisibilityKeyFrames(10)
-constexpr int KF_MAX_ROWS = 1 << 24;      // rows of a database between two clears
+constexpr int KF_MAX_ROWS = 1 << 24;      // rows of a database between two clears or compactions
 constexpr int KF_MAX_BOW = 1 << 24;       // entries of one BoW vector
 constexpr int64_t KF_MAX_POOL = 1 << 30;  // entries of the pool
 constexpr int KF_MAX_CALL = 1 << 24;      // ids per call
@@ -354,6 +356,10 @@ static int reserve_locked(DevBuf &b, size_t bytes)
     return lifecycle_locked_unless(bytes <= b.bytes, lifecycle_mutex(), [&] { return b.reserve(bytes); });
 }
 
+// what the first call allocates for (the creation argument, or its default); orbgpu_keyframe_db_compact returns to it (D3)
+static int initial_rows(const orbgpu_keyframe_db *db) { return db->initial_rows > 0 ? db->initial_rows : 1024; }
+static int64_t initial_pool(const orbgpu_keyframe_db *db) { return std::min<int64_t>((int64_t)initial_rows(db) * 512, KF_INITIAL_POOL); }
+
 // first call that needs the device: select it, create the stream, allocate for initial_rows
 static int bind(orbgpu_keyframe_db *db)
 {
@@ -369,10 +375,9 @@ static int bind(orbgpu_keyframe_db *db)
             return ORBGPU_EHIP;
         }
     }
-    const int rows0 = db->initial_rows > 0 ? db->initial_rows : 1024;
-    if ((rc = grow_rows(db, rows0)) != ORBGPU_OK)
+    if ((rc = grow_rows(db, initial_rows(db))) != ORBGPU_OK)
         return rc;
-    if ((rc = grow_pool(db, std::min<int64_t>((int64_t)rows0 * 512, KF_INITIAL_POOL))) != ORBGPU_OK)
+    if ((rc = grow_pool(db, initial_pool(db))) != ORBGPU_OK)
         return rc;
     if ((rc = db->d_ctr.reserve(64)) != ORBGPU_OK)
         return rc;
@@ -690,6 +695,111 @@ int orbgpu_keyframe_db_debug_global_queries(const orbgpu_keyframe_db *db, int64_
 {
     ORBGPU_REQUIRE(db && n, "null argument");
     *n = db->global_queries;
+    return ORBGPU_OK;
+}
+
+// D1-D4 (orbgpu.h).  The rows are gathered on the device: the relocalisation score register of K5 lives there only.
+int orbgpu_keyframe_db_compact(orbgpu_keyframe_db *db, orbgpu_compact_result *res)
+{
+    ORBGPU_REQUIRE(db, "null argument");
+    const int n = db->rows;
+    std::vector<int32_t> len((size_t)n);
+    std::vector<uint8_t> keep((size_t)n);
+    for (int r = 0; r < n; r++) {
+        len[(size_t)r] = db->h_rows[(size_t)r].len;
+        keep[(size_t)r] = db->h_rows[(size_t)r].alive != 0;
+    }
+    const CompactPlan plan = compact_plan(n, len.data(), keep.data(), keep.data(), db->pool_used, -1);
+    const int m = (int)plan.src.size();
+    orbgpu_compact_result out{};
+    out.rows_before = out.rows_after = n;
+    out.row_capacity = db->row_cap;
+    out.slots_before = out.slots_after = db->pool_used;
+    out.slot_capacity = db->pool_cap;
+    if (!plan.needed) {  // D4
+        db->last_rows = 0;  // D2: last_query starts over with every compact call that succeeds, as tests/compact_model.py has it
+        if (res)
+            *res = out;
+        return ORBGPU_OK;
+    }
+    int rc = bind(db);  // (a database with rows is bound: this selects the device)
+    if (rc != ORBGPU_OK)
+        return rc;
+    const int ncap = (int)compact_capacity(1, initial_rows(db), m);
+    const int64_t pcap = compact_capacity(1024, initial_pool(db), plan.pool_after);
+    std::vector<KfRow> n_rows((size_t)m);
+    std::vector<int64_t> n_seq((size_t)m), old_off((size_t)m);
+    for (int i = 0; i < m; i++) {
+        const size_t r = (size_t)plan.src[(size_t)i];
+        n_rows[(size_t)i] = db->h_rows[r];
+        n_rows[(size_t)i].off = (int32_t)plan.off[(size_t)i];
+        n_seq[(size_t)i] = db->h_seq[r];
+        old_off[(size_t)i] = db->h_rows[r].off;
+    }
+    Carver c;
+    const size_t o_old = c.take(8 * (size_t)std::max(m, 1)), o_new = c.take(8 * (size_t)std::max(m, 1)),
+                 o_src = c.take(4 * (size_t)std::max(m, 1)), o_len = c.take(4 * (size_t)std::max(m, 1));
+    std::vector<char> stage(c.off);
+    if (m > 0) {
+        memcpy(stage.data() + o_old, old_off.data(), 8 * (size_t)m);
+        memcpy(stage.data() + o_new, plan.off.data(), 8 * (size_t)m);
+        memcpy(stage.data() + o_src, plan.src.data(), 4 * (size_t)m);
+        memcpy(stage.data() + o_len, plan.len.data(), 4 * (size_t)m);
+    }
+    TableStreamOps ops{db->stream, "compacting the key-frame database"};
+    const IdColumn<DevBuf> pool_cols[2] = {{&db->d_pool_ids, 4}, {&db->d_pool_vals, 8}};
+    // d_stage, which carries the plan, is per-call scratch outside the transaction.  Of the row columns only the rows
+    // are carried: the others describe the last query, which last_query no longer reports (D2), and start as zeros -- no
+    // stamp of d_excl is 0 when a query reads it.
+    auto fill = [&](const DevBuf *nb, const DevBuf *np, int l2, IdHash &nh) -> int {
+        if (m > 0) {
+            const int rr = db->d_stage.reserve(c.off);
+            if (rr != ORBGPU_OK)
+                return rr;
+            char *st = db->d_stage.as<char>();
+            if (ops.upload(st, stage.data(), c.off))
+                return ORBGPU_EHIP;
+            const int64_t *noff = reinterpret_cast<const int64_t *>(st + o_new);
+            hipLaunchKernelGGL(k_compact_rows<KfRow>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, db->stream, m,
+                               reinterpret_cast<const int32_t *>(st + o_src), noff, n, db->d_rows.as<KfRow>(),
+                               static_cast<KfRow *>(nb[0].p));
+            if (plan.pool_after > 0) {
+                CompactPool<2> p{};
+                for (int k = 0; k < 2; k++) {
+                    p.src[k] = static_cast<const uint8_t *>(pool_cols[k].buf->p);
+                    p.dst[k] = static_cast<uint8_t *>(np[k].p);
+                }
+                hipLaunchKernelGGL((k_compact_pool<4, 8>), dim3((unsigned)compact_pool_grid(m)), dim3(COMPACT_BLOCK), 0, db->stream, m,
+                                   reinterpret_cast<const int64_t *>(st + o_old), noff, reinterpret_cast<const int32_t *>(st + o_len),
+                                   db->pool_used, pcap, p);
+            }
+            if (ops.done(hipGetLastError()))
+                return ORBGPU_EHIP;
+        }
+        nh.rebuild(l2);
+        for (int i = 0; i < m; i++)
+            nh.insert(n_rows[(size_t)i].id, i);
+        return ORBGPU_OK;
+    };
+    {
+        std::lock_guard<std::mutex> lifecycle(lifecycle_mutex());
+        const IdTableParts<DevBuf> parts{db->row_cols, KF_ROW_COLS, KF_ROW_COLS, &db->d_hkeys, &db->d_hvals, &db->hash, &db->row_cap};
+        if ((rc = id_table_compact(parts, ncap, pool_cols, 2, (size_t)pcap, ops, fill)) != ORBGPU_OK)
+            return rc;
+    }
+    db->h_rows.swap(n_rows);
+    db->h_seq.swap(n_seq);
+    db->rows = m;
+    db->pool_used = plan.pool_after;
+    db->pool_cap = pcap;
+    db->last_rows = 0;
+    out.compacted = 1;
+    out.rows_after = m;
+    out.row_capacity = db->row_cap;
+    out.slots_after = db->pool_used;
+    out.slot_capacity = db->pool_cap;
+    if (res)
+        *res = out;
     return ORBGPU_OK;
 }
 

@@ -316,6 +316,18 @@ class CovisRefreshResult(C.Structure):
                 ("n_bad", C.c_int32), ("max_obs", C.c_int32), ("n_entries", C.c_int64)]
 
 
+class CompactResult(C.Structure):
+    """orbgpu_compact_result"""
+    _fields_ = [("compacted", C.c_int32), ("rows_before", C.c_int32), ("rows_after", C.c_int32), ("rows_bad_kept", C.c_int32),
+                ("row_capacity", C.c_int32), ("slots_before", C.c_int64), ("slots_after", C.c_int64), ("slot_capacity", C.c_int64)]
+
+
+def _compact_call(fn, h):
+    res = CompactResult()
+    check(fn(h, C.byref(res)))
+    return {name: getattr(res, name) for name, _ in CompactResult._fields_}
+
+
 REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH = 1, 2
 REFRESH_NO_OBS, REFRESH_OVERFLOW, REFRESH_NO_DESC, REFRESH_NO_CENTRE = 0x01, 0x02, 0x04, 0x08
 REFRESH_NO_REF, REFRESH_UNKNOWN, REFRESH_BAD = 0x10, 0x20, 0x40
@@ -393,11 +405,11 @@ ABI_SYMBOLS = [
     "orbgpu_keyframe_db_create", "orbgpu_keyframe_db_destroy", "orbgpu_keyframe_db_clear", "orbgpu_keyframe_db_size",
     "orbgpu_keyframe_db_add", "orbgpu_keyframe_db_erase", "orbgpu_keyframe_db_set_covisibles", "orbgpu_keyframe_db_score",
     "orbgpu_keyframe_db_detect_loop", "orbgpu_keyframe_db_detect_reloc", "orbgpu_keyframe_db_last_query",
-    "orbgpu_keyframe_db_debug_global_queries",
+    "orbgpu_keyframe_db_debug_global_queries", "orbgpu_keyframe_db_compact",
     "orbgpu_covis_graph_create", "orbgpu_covis_graph_destroy", "orbgpu_covis_graph_clear", "orbgpu_covis_graph_size",
     "orbgpu_covis_graph_add_keyframe", "orbgpu_covis_graph_set_slots", "orbgpu_covis_graph_set_bad",
     "orbgpu_covis_graph_set_parent", "orbgpu_covis_graph_set_covisibles", "orbgpu_covis_local_map",
-    "orbgpu_covis_connections", "orbgpu_covis_graph_debug_global_queries",
+    "orbgpu_covis_connections", "orbgpu_covis_graph_debug_global_queries", "orbgpu_covis_graph_compact",
     "orbgpu_covis_graph_set_keypoints", "orbgpu_covis_observations", "orbgpu_covis_keyframe_culling",
     "orbgpu_covis_graph_set_scale_factors", "orbgpu_covis_graph_set_descriptors", "orbgpu_covis_graph_set_centres",
     "orbgpu_covis_refresh_points", "orbgpu_mappoint_table_refresh",
@@ -511,6 +523,7 @@ def lib():
         "orbgpu_keyframe_db_detect_reloc": [vp, i32, vp, vp, i32, vp, vp],
         "orbgpu_keyframe_db_last_query": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
         "orbgpu_keyframe_db_debug_global_queries": [vp, vp],
+        "orbgpu_keyframe_db_compact": [vp, vp],
         "orbgpu_covis_graph_create": [i32, i32, C.c_int64, vp],
         "orbgpu_covis_graph_destroy": [vp],
         "orbgpu_covis_graph_clear": [vp],
@@ -523,6 +536,7 @@ def lib():
         "orbgpu_covis_local_map": [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp],
         "orbgpu_covis_connections": [vp, C.c_int64, i32, i32, vp, vp, vp, i32, vp, vp, vp],
         "orbgpu_covis_graph_debug_global_queries": [vp, vp],
+        "orbgpu_covis_graph_compact": [vp, vp],
         "orbgpu_covis_graph_set_keypoints": [vp, C.c_int64, i32, vp],
         "orbgpu_covis_observations": [vp, i32, vp, vp, vp],
         "orbgpu_covis_keyframe_culling": [vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp],
@@ -2382,6 +2396,10 @@ class KeyFrameDatabase:
         check(self.L.orbgpu_keyframe_db_debug_global_queries(self.h, C.byref(n)))
         return n.value
 
+    def compact(self):
+        """drops the erased rows and gives their space back (D1-D4): dict of the fields of orbgpu_compact_result"""
+        return _compact_call(self.L.orbgpu_keyframe_db_compact, self.h)
+
     def last_query(self):
         """the sharing list of the most recent detect call (K1 order): dict of id, words, first_word, score, acc, best_id"""
         n = C.c_int32()
@@ -2494,6 +2512,11 @@ class CovisibilityGraph:
         n = C.c_int64()
         check(self.L.orbgpu_covis_graph_debug_global_queries(self.h, C.byref(n)))
         return n.value
+
+    def compact(self):
+        """drops the bad rows no live row names as parent and gives their space back (C1-C7): dict of the fields of
+        orbgpu_compact_result"""
+        return _compact_call(self.L.orbgpu_covis_graph_compact, self.h)
 
     MAX_LEVELS = 16
     KP_STEREO = 0x40

@@ -2373,6 +2373,15 @@ template <typename KeyFrameT> class KeyFrameDatabaseT {
         check(orbgpu_keyframe_db_clear(h_), "KeyFrameDatabase::clear");
         kfs_.clear();
     }
+    // Drops the rows of erased key frames and gives their rows and pool space back (D1-D4 of orbgpu.h); invisible to every
+    // other function of this class.  No function of this class calls it: INTEGRATION.md 2h says where a caller puts it.
+    orbgpu_compact_result Compact()
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        orbgpu_compact_result res;
+        check(orbgpu_keyframe_db_compact(h_, &res), "KeyFrameDatabase::Compact");
+        return res;
+    }
     int size() const
     {
         std::lock_guard<std::mutex> g(mu_);
@@ -2563,6 +2572,17 @@ template <typename KeyFrameT, typename MapPointT> class CovisibilityGraphT {
         check(orbgpu_covis_graph_clear(h_), "CovisibilityGraph::clear");
         kfs_.clear();
         mps_.clear();
+    }
+    // Drops the bad rows that no live row names as its parent and gives their rows and pool space back (C1-C7 of
+    // orbgpu.h).  No function of this class calls it: KeyFrameCulling and the hooks behave as they did.  The caller decides
+    // when -- INTEGRATION.md 2o: after the SetBadFlag loop that follows KeyFrameCulling.  A dropped key frame stays in this
+    // class's id map (the reference never deletes a KeyFrame), where no answer of the graph names it any more.
+    orbgpu_compact_result Compact()
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        orbgpu_compact_result res;
+        check(orbgpu_covis_graph_compact(h_, &res), "CovisibilityGraph::Compact");
+        return res;
     }
     size_t KeyFrames() const
     {
