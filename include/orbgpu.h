@@ -575,7 +575,9 @@ int orbgpu_search_local_points_table(const orbgpu_frame *fr, orbgpu_mappoint_tab
 /* ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cc:1328-1470) over the table: both
  * frames are device-resident; last_ids [last n] (host) = mnId of LastFrame.mvpMapPoints[i] or -1, last_outlier [last n]
  * or NULL = LastFrame.mvbOutlier, cur_kp_ids [cur n] or NULL = mnId of CurrentFrame.mvpMapPoints[j] or -1.
- * kp_to_mp [cur n] (host, out): index i of the last-frame key point whose map point key point j now holds, -1, -2. */
+ * kp_to_mp [cur n] (host, out): index i of the last-frame key point whose map point key point j now holds, -1, -2.
+ * ORBGPU_ELEVEL, with nothing written, if a last-frame key point whose map point projects into the image has an octave
+ * outside [0, nlevels), as orbgpu_search_by_projection_last. */
 int orbgpu_search_by_projection_last_table(const orbgpu_frame *cur, const float *cur_Tcw, const orbgpu_frame *last,
                                            const float *last_Tcw, orbgpu_mappoint_table *t, const int64_t *last_ids,
                                            const uint8_t *last_outlier, const int64_t *cur_kp_ids, float fx, float fy,

@@ -377,9 +377,10 @@ def search_by_projection(frame, mp, th, nnratio, kp_to_mp):
 
 
 def search_local_points(frame, Tcw, fx, fy, cx, cy, mbf, table, log_sf, th=3.0, nnratio=0.8, cos_limit=0.5, kp_to_mp=None,
-                        libpath=None):
+                        libpath=None, want_track=False):
     """Tracking::SearchLocalPoints for a fresh frame (Tracking.cc:1447-1497).  table: dict with world_pos, normal, min_dist,
-    max_dist, desc, skip, obs_pos.  Returns (nmatches, kp_to_mp, in_view, levels_out_of_range)."""
+    max_dist, desc, skip, obs_pos.  Returns (nmatches, kp_to_mp, in_view, levels_out_of_range) and, with want_track, the dict
+    of the scratch arrays proj_x, proj_y, proj_xr, level, view_cos (zero on rows that are not in view)."""
     L = lib(libpath)
     L.ora_search_local_points.argtypes = [C.c_void_p] * 2 + [C.c_float] * 5 + [C.c_int] + [C.c_void_p] * 7 + \
         [C.c_float] * 4 + [C.c_void_p] * 8
@@ -398,6 +399,8 @@ def search_local_points(frame, Tcw, fx, fy, cx, cy, mbf, table, log_sf, th=3.0, 
                                   _p(keep["min_dist"]), _p(keep["max_dist"]), _p(keep["skip"]), _p(keep["obs_pos"]),
                                   _p(keep["desc"]), log_sf, cos_limit, th, nnratio, _p(in_view), _p(px), _p(py), _p(pxr),
                                   _p(lvl), _p(vc), _p(out), C.addressof(nlo))
+    if want_track:
+        return n, out, in_view, nlo.value, {"proj_x": px, "proj_y": py, "proj_xr": pxr, "level": lvl, "view_cos": vc}
     return n, out, in_view, nlo.value
 
 

@@ -6,6 +6,7 @@
  */
 #include "orb_oracle.h"
 
+#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -204,6 +205,17 @@ int ora_get_features_in_area(const ora_frame_view *f, float x, float y, float r,
         }
     }
     return n;
+}
+
+/* MapPoint::PredictScale, MapPoint.cc:385-394.  The float is tested before it is converted: a level that no int holds (NaN
+ * or infinite: a non-finite position or distance, or a distance of 0) is INT_MIN or INT_MAX, outside every range of levels,
+ * and not whatever the conversion happens to give. */
+static int predicted_level(float ratio, float log_scale_factor)
+{
+    const float level = ceilf(logf(ratio) / log_scale_factor);
+    if (!(level > -2147483648.f))
+        return INT_MIN;
+    return level < 2147483648.f ? (int)level : INT_MAX;
 }
 
 /* ------------------------------------------------------------------ M2 */
@@ -434,7 +446,7 @@ int ora_search_by_projection_keyframe(const ora_frame_view *cur, const float *cu
         if (dist3D < minDistance || dist3D > maxDistance)
             continue;
         float ratio = kf->max_dist[i] / dist3D;
-        int lvl = (int)ceilf(logf(ratio) / log_scale_factor); /* MapPoint::PredictScale */
+        int lvl = predicted_level(ratio, log_scale_factor); /* MapPoint::PredictScale */
         if (lvl < 0 || lvl >= cur->nlevels) {
             nmatches = -1;
             goto done;
@@ -542,7 +554,7 @@ int ora_search_by_projection_sim3(const ora_frame_view *kf, const float *Scw, fl
         if (dot < 0.5 * dist)
             continue;
         const float ratio = pts->max_dist[i] / dist;
-        const int lvl = (int)ceilf(logf(ratio) / log_scale_factor);
+        const int lvl = predicted_level(ratio, log_scale_factor);
         if (lvl < 0 || lvl >= kf->nlevels) {
             nmatches = -1;
             goto done;
@@ -634,7 +646,7 @@ int ora_is_in_frustum(const float *Tcw, float fx, float fy, float cx, float cy, 
     if (viewCos < cos_limit)
         return 0;
     float ratio = max_dist / dist;
-    const int nPredictedLevel = (int)ceilf(logf(ratio) / log_scale_factor);
+    const int nPredictedLevel = predicted_level(ratio, log_scale_factor);
     *proj_x = u;
     *proj_xr = u - mbf * invz;
     *proj_y = v;
@@ -808,7 +820,7 @@ int ora_fuse(const ora_frame_view *kf, const float *Tcw, float fx, float fy, flo
         if (dot < 0.5 * dist3D)
             continue;
         const float ratio = pts->max_dist[i] / dist3D;
-        const int lvl = (int)ceilf(logf(ratio) / log_scale_factor);
+        const int lvl = predicted_level(ratio, log_scale_factor);
         if (lvl < 0 || lvl >= kf->nlevels) {
             n = -1;
             break;
@@ -860,7 +872,7 @@ int ora_fuse_sim3(const ora_frame_view *kf, const float *Scw, float fx, float fy
         if (dot < 0.5 * dist3D)
             continue;
         const float ratio = pts->max_dist[i] / dist3D;
-        const int lvl = (int)ceilf(logf(ratio) / log_scale_factor);
+        const int lvl = predicted_level(ratio, log_scale_factor);
         if (lvl < 0 || lvl >= kf->nlevels) {
             n = -1;
             break;
@@ -909,7 +921,7 @@ static int sim3_direction(const ora_frame_view *kfB, const float *Taw, const flo
         if (dist3D < minDistance || dist3D > maxDistance)
             continue;
         const float ratio = ptsA->max_dist[i] / dist3D;
-        const int lvl = (int)ceilf(logf(ratio) / log_sfB);
+        const int lvl = predicted_level(ratio, log_sfB);
         if (lvl < 0 || lvl >= kfB->nlevels) {
             rc = -1;
             break;

@@ -1040,6 +1040,10 @@ int orbgpu_search_by_projection_last_table(const orbgpu_frame *cur, const float 
     ORBGPU_HIP_TRY(hipStreamSynchronize(st));
     const int32_t *cnt = (const int32_t *)(h + (r_cnt - r_beg));
     t->last_unknown_list = cnt[2], t->last_unknown_kp = cnt[3];  // skipped rows / held key points, not an error (see above)
+    if (cnt[1]) {  // k_project_last_queries left those rows out; the reference reads mvScaleFactors out of range (:1381)
+        set_error("%d last-frame key point(s) with an octave outside [0,%d)", cnt[1], cur->nlevels);
+        return ORBGPU_ELEVEL;  // as orbgpu_search_by_projection_last (H5)
+    }
     std::memcpy(kp_to_mp, h + (r_k2m - r_beg), 4 * (size_t)n);
     *nmatches = cnt[0];
     return ORBGPU_OK;

@@ -75,7 +75,8 @@ __device__ __forceinline__ void top4_insert64(uint64_t t[4], uint64_t k)
 // Walks the grid window of one row (Frame::GetFeaturesInArea, Frame.cc:327-380, and the candidate
 // filters of ORBmatcher.cc:82-97 / 1399-1412) with one wave: lanes take the window's cells in the
 // reference's visiting order (ix outer, iy inner), and every surviving candidate becomes a key
-//   distance << 44 | cell sequence << 32 | position in cell << 20 | key point index,
+//   distance << 44 | cell sequence << 32 | position in cell << 16 | key point index,
+// (12, 16 and 16 bits under the distance: 3072 cells, and a frame's 16384 key points may all lie in one cell)
 // whose ascending order is exactly the order in which the sequential loop would prefer candidates.
 // `claim` == nullptr: no claim filtering (pass 1); otherwise key points with claim[idx] < i are hidden.
 // sink(key, octave) is called by the lane that found the candidate.
@@ -135,7 +136,7 @@ __device__ __forceinline__ void proj_walk_each(const Query &Q, const uint64_t a[
             const uint64_t *db = reinterpret_cast<const uint64_t *>(F.desc) + (size_t)idx * 4;
             uint64_t b[4] = {db[0], db[1], db[2], db[3]};
             const uint64_t d = (uint64_t)hamming256(a, b);
-            sink((d << 44) | ((uint64_t)seq << 32) | ((uint64_t)(p - beg) << 20) | (uint64_t)idx, oct);
+            sink((d << 44) | ((uint64_t)seq << 32) | ((uint64_t)(p - beg) << 16) | (uint64_t)idx, oct);
         }
     }
 }
@@ -255,11 +256,11 @@ __device__ __forceinline__ int proj_accept(uint64_t k1, uint64_t k2, const Frame
     const int bestDist = (int)(k1 >> 44);
     if (bestDist > th_dist)
         return -1;
-    const int bestIdx = (int)(k1 & 0xFFFFF);
+    const int bestIdx = (int)(k1 & 0xFFFF);
     if (MODE == 0) {
         const int bestDist2 = (int)(k2 >> 44);
         const int bestLevel = F.kp_octave[bestIdx * F.kp_stride];
-        const int bestLevel2 = bestDist2 < 256 ? F.kp_octave[(int)(k2 & 0xFFFFF) * F.kp_stride] : -1;
+        const int bestLevel2 = bestDist2 < 256 ? F.kp_octave[(int)(k2 & 0xFFFF) * F.kp_stride] : -1;
         if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2)
             return -1;
     }
@@ -637,7 +638,7 @@ int validate_frame(const orbgpu_frame_view *f)
     ORBGPU_REQUIRE(f->cell_start[0] == 0 && f->cell_start[nc] <= f->n, "grid CSR inconsistent");
     for (int c = 0; c < nc; c++) {
         const int cnt = f->cell_start[c + 1] - f->cell_start[c];
-        ORBGPU_REQUIRE(cnt >= 0 && cnt < 4096, "grid cell %d holds %d items (limit 4095)", c, cnt);
+        ORBGPU_REQUIRE(cnt >= 0, "grid CSR not monotone at cell %d (%d)", c, cnt);  // a cell holds at most n <= 16384: 16 bits
     }
     for (int t = 0; t < f->cell_start[nc]; t++)
         ORBGPU_REQUIRE(f->cell_items[t] >= 0 && f->cell_items[t] < f->n, "grid item out of range");
@@ -807,6 +808,7 @@ __device__ __forceinline__ void frustum_queries_body(int m, const float *__restr
     bool in_view = false;
     float u = 0.f, v = 0.f, ur = 0.f, view_cos = 0.f;
     int level = 0;
+    bool level_ok = false;
     if (!(skip && skip[i])) {
         const float X = world_pos[3 * i], Y = world_pos[3 * i + 1], Z = world_pos[3 * i + 2];
         // mRcw*P + mtcw: float products summed left to right, then the translation (same convention as the host
@@ -835,12 +837,16 @@ __device__ __forceinline__ void frustum_queries_body(int m, const float *__restr
                 break;
             const float ratio = max_dist[i] / dist;
             // std::log(float): evaluated in double and rounded, which is the correctly rounded float logarithm
-            level = (int)ceilf((float)log((double)ratio) / P.log_sf);
+            const float flevel = ceilf((float)log((double)ratio) / P.log_sf);
+            // tested as a float, before the conversion: a NaN or infinite level (a non-finite position or max_dist,
+            // dist == 0) is a level out of range, whatever a float-to-int conversion would make of it
+            level_ok = flevel >= 0.f && flevel < (float)P.nlevels;
+            level = level_ok ? (int)flevel : 0;
             ur = u - P.mbf * invz;
             in_view = true;
         } while (0);
     }
-    if (in_view && (level < 0 || level >= P.nlevels)) {
+    if (in_view && !level_ok) {
         // the reference indexes mvScaleFactors out of range here (undefined); such points are left unmatched
         atomicAdd(bad_levels, 1);
         in_view = false;
@@ -1095,8 +1101,8 @@ __global__ __launch_bounds__(1024) void k_tri_finish(int n1, const float *__rest
 
 // ---- ORBmatcher::SearchForInitialization (ORBmatcher.cc:405-520): distances of every window candidate ---------
 // One wave per level-0 key point of F1: all key points of F2 inside its window (GetFeaturesInArea(x, y, windowSize,
-// 0, 0)) with their Hamming distance, as 64-bit keys distance << 44 | cell sequence << 32 | position in cell << 20
-// | index (the visiting order of the reference is the order of bits 43..20).  The steal-if-strictly-closer
+// 0, 0)) with their Hamming distance, as 64-bit keys distance << 44 | cell sequence << 32 | position in cell << 16
+// | index (the visiting order of the reference is the order of bits 43..16).  The steal-if-strictly-closer
 // bookkeeping (:441-470) is a sequential dependency between rows and runs on the host over these lists.
 __global__ __launch_bounds__(256) void k_window_candidates(int rows, const Query *__restrict__ q,
                                                            const uint8_t *__restrict__ row_desc, FrameDev F, int cap,
@@ -1778,10 +1784,10 @@ int orbgpu_search_for_initialization(const orbgpu_frame_view *f1, const orbgpu_f
         uint64_t *b = &keys[off[r]], *e = b + counts[r];
         if (b == e)
             continue;  // :426-427
-        std::sort(b, e, [](uint64_t x, uint64_t y) { return ((x >> 20) & 0xFFFFFFull) < ((y >> 20) & 0xFFFFFFull); });
+        std::sort(b, e, [](uint64_t x, uint64_t y) { return ((x >> 16) & 0xFFFFFFFull) < ((y >> 16) & 0xFFFFFFFull); });
         int bestDist = INT_MAX, bestDist2 = INT_MAX, bestIdx2 = -1;
         for (uint64_t *p = b; p != e; ++p) {
-            const int i2 = (int)(*p & 0xFFFFF), dist = (int)(*p >> 44);
+            const int i2 = (int)(*p & 0xFFFF), dist = (int)(*p >> 44);
             if (vMatchedDistance[i2] <= dist)
                 continue;
             if (dist < bestDist) {

@@ -146,8 +146,16 @@ inline float cam_distance(const float *Pw, const float *Ow, float *PO)
     PO[0] = Pw[0] - Ow[0], PO[1] = Pw[1] - Ow[1], PO[2] = Pw[2] - Ow[2];
     return norm3(PO);
 }
-// MapPoint::PredictScale (MapPoint.cc:385-394); the caller checks the range
-inline int predict_level(float max_dist, float dist, float log_sf) { return (int)ceilf(logf(max_dist / dist) / log_sf); }
+// MapPoint::PredictScale (MapPoint.cc:385-394); the caller checks the range.  The float is tested before it is converted:
+// a level that no int holds (NaN or infinite, from a non-finite position or max_dist, or dist == 0) comes back as INT_MIN
+// or INT_MAX, out of every range, and not as whatever the conversion happens to give.
+inline int predict_level(float max_dist, float dist, float log_sf)
+{
+    const float level = ceilf(logf(max_dist / dist) / log_sf);
+    if (!(level > -2147483648.f))
+        return INT_MIN;
+    return level < 2147483648.f ? (int)level : INT_MAX;
+}
 
 // ---- claim tables --------------------------------------------------------------------------------------------
 // kp_to_mp -> claim_init where only rows with Observations()>0 hold their key point (:87-89, :1403-1405): -2 and a held

@@ -941,7 +941,7 @@ def search_local_points_device(frame_view, table, Tcw, fx, fy, cx, cy, mbf, log_
 def search_local_points_batch_device(problems, cos_limit, th, nnratio, stream=0, device_id=0):
     """n independent Tracking::SearchLocalPoints problems in one call (orbgpu_search_local_points_batch_device).
     problems: list of dicts with frame (DeviceFrameView), table (DeviceMapPointTable), Tcw (4x4), fx, fy, cx, cy, mbf,
-    log_sf, d_kp_to_mp, d_counts (device pointers)."""
+    log_sf, d_kp_to_mp, d_counts (device pointers) and optionally track (TrackScratch)."""
     n = len(problems)
     arr = (LocalPointsProblem * max(n, 1))()
     keep = []
@@ -953,7 +953,9 @@ def search_local_points_batch_device(problems, cos_limit, th, nnratio, stream=0,
         arr[k].Tcw = T.ctypes.data
         arr[k].fx, arr[k].fy, arr[k].cx, arr[k].cy, arr[k].mbf = p["fx"], p["fy"], p["cx"], p["cy"], p["mbf"]
         arr[k].log_scale_factor = p["log_sf"]
-        arr[k].d_kp_to_mp, arr[k].d_counts, arr[k].d_track = p["d_kp_to_mp"], p["d_counts"], None
+        track = p.get("track")  # optional TrackScratch of device arrays, as search_local_points_device takes it
+        arr[k].d_kp_to_mp, arr[k].d_counts = p["d_kp_to_mp"], p["d_counts"]
+        arr[k].d_track = C.addressof(track) if track is not None else None
     L = lib()
     L.orbgpu_search_local_points_batch_device.argtypes = [C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int32,
                                                           C.c_void_p]

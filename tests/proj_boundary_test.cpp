@@ -218,6 +218,41 @@ static void test_level_out_of_range()
     CHECK(is_level_error(queries_local(&FRAME, &mp, 1.f, q), 1, -1));
 }
 
+// A level that is no number: PredictScale of a NaN or infinite ratio.  predict_level tests the float and answers INT_MIN /
+// INT_MAX, so the row is out of range by the builders' own check and never by what a conversion of NaN returns.
+static void test_level_not_a_number()
+{
+    const float nan = nanf(""), inf = INFINITY;
+    CHECK(predict_level(nan, 2.f, LOG_SF) == INT_MIN && predict_level(3.f, nan, LOG_SF) == INT_MIN);
+    CHECK(predict_level(3.f, 0.f, LOG_SF) == INT_MAX);   // ratio inf, log inf
+    CHECK(predict_level(0.f, 2.f, LOG_SF) == INT_MIN);   // ratio 0, log -inf
+    CHECK(predict_level(inf, inf, LOG_SF) == INT_MIN);   // inf / inf
+    CHECK(predict_level(3.f, 2.f, LOG_SF) == 3 && predict_level(8.f, 2.f, LOG_SF) == 8);
+    CHECK(predict_level(1.67f, 2.f, LOG_SF) == 0);       // ceil(-0.99) = -0
+    std::vector<Query> q;
+    const float nan_pos[3] = {nan, 0, 2}, inf_pos[3] = {inf, 0, 2}, origin[3] = {0, 0, 0};
+    for (int f = 0; f < N_FLAVOURS; f++) {
+        Points P;
+        P.add(A), P.add(A, 0.5f, nan);  // `dist3D > 1.2f*NaN` is false: the row reaches PredictScale
+        CHECK(is_level_error(build((Flavour)f, P, q), 1, INT_MIN));
+        // a non-finite position projects to NaN (0*inf for the other coordinates), which KeyFrame::IsInImage refuses
+        Points R;
+        R.add(A), R.add(nan_pos), R.add(inf_pos), R.add(origin, 0.f);
+        CHECK(build((Flavour)f, R, q).status == ORBGPU_OK);
+        CHECK(q[0].active && !q[1].active && !q[2].active && !q[3].active);
+    }
+    // the key-frame flavour's bounds let a NaN pass (:1507-1510), and so does its distance range
+    const struct { const float *pos; float numerator; int level; } rows[] = {
+        {nan_pos, 3.f, INT_MIN}, {A, nan, INT_MIN}, {origin, 3.f, INT_MAX}};
+    for (const auto &r : rows) {
+        Points P;
+        P.add(A, 0.f, 10.f), P.add(r.pos, 0.f, 10.f);
+        const std::vector<float> numerator = {3.f, r.numerator};
+        const orbgpu_keyframe_view kf = P.keyframe(numerator);
+        CHECK(is_level_error(queries_keyframe(&FRAME, I44, K, LOG_SF, &kf, 1.f, q), 1, r.level));
+    }
+}
+
 static void test_claim_init()
 {
     std::vector<int> init;
@@ -323,6 +358,7 @@ int main()
     test_distance_range_and_normal();
     test_levels_and_flags();
     test_level_out_of_range();
+    test_level_not_a_number();
     test_claim_init();
     test_sim3_to_rt();
     test_rotation_check_on_the_host();
