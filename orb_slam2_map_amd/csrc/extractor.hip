@@ -1817,63 +1817,121 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x)
 // Integer moments: exact in any summation order.
 constexpr int OR_ITERS = 4;  // key points per half wave for full batches (1 below OR_BATCH_MIN frames: latency)
 constexpr int OR_BATCH_MIN = 32;
+struct OrientLevel {  // what k_orient needs of one level of its frame (LDS, formed once per workgroup)
+    int sel_off, cnt;  // the level's first selection slot; key points k_quadtree selected (nsel)
+    int out_off;       // key points of the levels below: the level's first output row
+    int plane_off, pitch, patch;
+    float scale;
+    int pad;
+};
+static_assert(sizeof(OrientLevel) == 32, "OrientLevel is read as two 16-byte words");
+
+// Integer sum over the 32 lanes of a half wave (all of them active), left in each: DPP adds inside a row of 16
+// (quad_perm [1,0,3,2] and [2,3,0,1], row_ror 4 and 8), one swizzle (lane ^ 16) between the two rows
+__device__ __forceinline__ int or_sum32(int v)
+{
+    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x124, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, false);
+    return v + __builtin_amdgcn_ds_swizzle(v, 0x401F);
+}
 
 __global__ __launch_bounds__(256) void k_orient(const uint8_t *__restrict__ pyr, size_t frame_pyr,
                                                 const LevelGeom *__restrict__ geom, int nlevels,
                                                 const uint32_t *__restrict__ sel, int sel_cap_total,
                                                 const int *__restrict__ nsel, const uint32_t *__restrict__ orw,
+                                                const uint8_t *__restrict__ slot_lev,
                                                 orbgpu_keypoint *__restrict__ kps, KpAux *__restrict__ aux,
                                                 int cap, int *__restrict__ n_out, int iters, Src0 s0)
 {
-    __shared__ uint32_t W10[4 * 16 * 9], M01[4 * 16 * 9];
+    // per (a, |v|) one row of OR_WM dwords: the 9 (W10, M01) dword pairs of the row, read as four 16-byte words and one of 8
+    constexpr int OR_WM = 20;
+    __shared__ __align__(16) uint32_t WM[4 * 16 * OR_WM];
     __shared__ __align__(16) uint8_t stage[8][31 * 48];
-    // the weight tables are built once on the host (orient_tables): a workgroup only copies them
-    for (int i = threadIdx.x; i < 4 * 16 * 9; i += 256) {
-        W10[i] = orw[i];
-        M01[i] = orw[4 * 16 * 9 + i];
+    __shared__ __align__(16) OrientLevel lev[ORBGPU_MAX_LEVELS];
+    __shared__ int s_total, s_bad;
+    int bx, f;
+    xcd_frame_block(bx, f);
+    f = serpentine(f);
+    // the weight tables are built once on the host (orient_tables): a workgroup only copies them, four threads per row
+    {
+        const int row = threadIdx.x >> 2, part = threadIdx.x & 3;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int q = part + 4 * k;
+            if (q < 9) {
+                WM[row * OR_WM + 2 * q] = orw[row * 9 + q];
+                WM[row * OR_WM + 2 * q + 1] = orw[4 * 16 * 9 + row * 9 + q];
+            }
+        }
+    }
+    // The frame's level records, once per workgroup: lane l of the first wave loads level l's count and geometry (one
+    // round trip for all levels), a prefix sum over the lanes gives the level's first output row, the last level's
+    // lane the frame's total and whether some level failed.
+    static_assert(ORBGPU_MAX_LEVELS <= 16, "the prefix sum below covers 16 lanes");
+    if (threadIdx.x < 64) {
+        const int l = threadIdx.x;
+        const bool has = l < nlevels;
+        const int c = has ? nsel[(size_t)f * nlevels + l] : 0;
+        const int pos = max(c, 0);
+        int incl = pos;
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) {
+            const int t = __shfl_up(incl, off, 64);
+            if (l >= off)
+                incl += t;
+        }
+        const bool bad = __ballot(c < 0) != 0;
+        if (has) {
+            const LevelGeom &G = geom[l];
+            OrientLevel r;
+            r.sel_off = G.sel_off;
+            r.cnt = c;
+            r.out_off = incl - pos;
+            r.plane_off = G.plane_off;
+            r.pitch = G.pitch;
+            r.patch = G.patch;
+            r.scale = G.scale;
+            r.pad = 0;
+            lev[l] = r;
+            if (l == nlevels - 1) {
+                s_total = incl;
+                s_bad = bad ? 1 : 0;
+            }
+        }
     }
     __syncthreads();
 
     const int hl = threadIdx.x & 31;  // lane inside the half wave = disc row index
-    int bx, f;
-    xcd_frame_block(bx, f);
-    f = serpentine(f);
-    const int *ns = nsel + (size_t)f * nlevels;
-    // `iters` slots per half wave: the weight tables above are built once per 8 * iters key points
-    for (int it = 0; it < iters; it++) {
-    const int slot = (bx * iters + it) * 8 + (threadIdx.x >> 5);
-    // locate (level, j) of this slot and the output offset
-    int level = -1, j = 0, out_off = 0, total = 0, cnt_l = 0;
-    bool bad = false;
-    // the level's geometry is picked up while the (wave-uniform, scalar) level records are walked anyway, so the
-    // key load below does not wait for a per-lane LevelGeom fetch
-    struct {
-        int plane_off, pitch, sel_off, patch;
-        float scale;
-    } g = {0, 0, 0, 0, 1.f};
-    for (int l = 0; l < nlevels; l++) {
-        const int c = ns[l];
-        if (c < 0)
-            bad = true;
-        const int so = geom[l].sel_off;
-        if (slot >= so && slot < so + geom[l].sel_cap) {
-            level = l;
-            j = slot - so;
-            out_off = total;
-            cnt_l = c;
-            g.plane_off = geom[l].plane_off;
-            g.pitch = geom[l].pitch;
-            g.sel_off = so;
-            g.patch = geom[l].patch;
-            g.scale = geom[l].scale;
-        }
-        total += max(c, 0);
-    }
-    if (slot == 0 && hl == 0)
+    const int half = threadIdx.x >> 5;
+    const int total = s_total;
+    const bool bad = s_bad != 0;
+    if (bx == 0 && threadIdx.x == 0)  // (slot 0's first lane)
         n_out[f] = bad ? -1 - total : (total > cap ? -1 - total : total);
-    if (level < 0 || bad || total > cap || j >= cnt_l)
+    if (bad || total > cap)
+        return;
+    // `iters` slots per half wave: the tables above are built once per 8 * iters key points.  Lane `it` of a half wave owns
+    // the slot of iteration `it`: it fetches the slot's level (slot_level(), one byte) and key up front, hands both to
+    // its half wave when the iteration comes, keeps the moments and writes the key point behind the loop -- eight
+    // key points of a wave in one pass through fast_atan2_deg and the record stores.
+    int my_level = -1;
+    uint32_t my_key = 0;
+    const int my_slot = (bx * iters + hl) * 8 + half;
+    if (hl < iters && my_slot < sel_cap_total) {
+        const int l = slot_lev[my_slot];
+        my_key = sel[(size_t)f * sel_cap_total + my_slot];  // (= the level's sel_off + j)
+        my_level = my_slot - lev[l].sel_off < lev[l].cnt ? l : -1;
+    }
+    int my_m10 = 0, my_m01 = 0;
+    for (int it = 0; it < iters; it++) {
+    const int level = __shfl(my_level, it, 32);
+    const uint32_t key = __shfl(my_key, it, 32);
+    if (level < 0)
         continue;
-    const uint32_t key = sel[(size_t)f * sel_cap_total + g.sel_off + j];
+    struct {
+        int plane_off, pitch;
+    } g = {lev[level].plane_off, lev[level].pitch};
     const int x = key_x(key) + BORDER0, y = key_y(key) + BORDER0;
     // the key point's plane: the padded level, or -- level 0 in direct mode -- the caller's image (pixel 0 at column 0)
     const bool dir0 = s0.direct != 0 && level == 0;
@@ -1920,13 +1978,17 @@ __global__ __launch_bounds__(256) void k_orient(const uint8_t *__restrict__ pyr,
         if (hl < 31) {
             const int av = v < 0 ? -v : v;
             const uint32_t *row = reinterpret_cast<const uint32_t *>(stage[threadIdx.x >> 5]) + hl * 12;
-            const uint32_t *w = &W10[(a * 16 + av) * 9], *m = &M01[(a * 16 + av) * 9];
+            const uint4 *wm4 = reinterpret_cast<const uint4 *>(&WM[(a * 16 + av) * OR_WM]);
+            const uint4 p0 = wm4[0], p1 = wm4[1], p2 = wm4[2], p3 = wm4[3];
+            const uint2 p4 = *reinterpret_cast<const uint2 *>(&wm4[4]);
+            const uint32_t wm[18] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w, p2.x,
+                                     p2.y, p2.z, p2.w, p3.x, p3.y, p3.z, p3.w, p4.x, p4.y};
             uint32_t sw = 0, sm = 0;
 #pragma unroll
             for (int q = 0; q < 9; q++) {
                 const uint32_t d = row[q];
-                sw = __builtin_amdgcn_udot4(d, w[q], sw, false);
-                sm = __builtin_amdgcn_udot4(d, m[q], sm, false);
+                sw = __builtin_amdgcn_udot4(d, wm[2 * q], sw, false);
+                sm = __builtin_amdgcn_udot4(d, wm[2 * q + 1], sm, false);
             }
             m10 = (int)sw - 16 * (int)sm;
             m01 = v * (int)sm;
@@ -1934,35 +1996,43 @@ __global__ __launch_bounds__(256) void k_orient(const uint8_t *__restrict__ pyr,
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the next item overwrites the slot
         __builtin_amdgcn_wave_barrier();
     }
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) {
-        m10 += __shfl_xor(m10, off, 64);
-        m01 += __shfl_xor(m01, off, 64);
+    // sum over the half wave, left in every lane of it: inside a quad, over the four quads of a row of 16 (rotations:
+    // the sums are integers, any order gives the same), then the other row
+    m10 = or_sum32(m10);
+    m01 = or_sum32(m01);
+    if (hl == it) {
+        my_m10 = m10;
+        my_m01 = m01;
     }
-    if (hl == 0) {
-        const float angle = fast_atan2_deg((float)m01, (float)m10);
+    }
+    if (my_level >= 0) {
+        const int level = my_level;
+        const OrientLevel my = lev[level];
+        const int my_j = my_slot - my.sel_off;
+        const int x = key_x(my_key) + BORDER0, y = key_y(my_key) + BORDER0;
+        const bool dir0 = s0.direct != 0 && level == 0;
+        const float angle = fast_atan2_deg((float)my_m01, (float)my_m10);
         orbgpu_keypoint kp;
         kp.x = (float)x;
         kp.y = (float)y;
         if (level != 0) {
-            kp.x *= g.scale;
-            kp.y *= g.scale;
+            kp.x *= my.scale;
+            kp.y *= my.scale;
         }
-        kp.size = (float)g.patch;
+        kp.size = (float)my.patch;
         kp.angle = angle;
-        kp.response = (float)key_resp(key);
+        kp.response = (float)key_resp(my_key);
         kp.octave = level;
         kp.class_id = -1;
-        kps[(size_t)f * cap + out_off + j] = kp;
+        kps[(size_t)f * cap + my.out_off + my_j] = kp;
         KpAux ax;
         ax.x = x + (dir0 ? BLUR0_OX - EDGE : 0);  // k_describe reads the BLURRED plane: column x + EDGE there (direct level 0: BLUR0_OX)
         ax.y = y;
         ax.level = level;
-        ax.plane_off = g.plane_off;
-        ax.pitch = g.pitch;
+        ax.plane_off = my.plane_off;
+        ax.pitch = my.pitch;
         ax.angle = angle;
-        aux[(size_t)f * cap + out_off + j] = ax;
-    }
+        aux[(size_t)f * cap + my.out_off + my_j] = ax;
     }
 }
 // computeOrbDescriptor's  a = (float)cos(angle), b = (float)sin(angle)  (ORBextractor.cc:112-113): std::cos(float) /
@@ -2773,7 +2843,7 @@ static int launch_pipeline(orbgpu_extractor *e, const uint8_t *d_gray, int batch
     const int or_iters = batch >= OR_BATCH_MIN ? OR_ITERS : 1;
     L.launch(k_orient, dim3((e->plan.sel_cap_total + 8 * or_iters - 1) / (8 * or_iters), batch), dim3(256), 0, pyr, e->plan.frame_pyr, dg, nl,
                        e->d_sel.as<uint32_t>(), e->plan.sel_cap_total, e->d_nsel.as<int>(),
-                       e->tab<uint32_t>(e->plan.t_orient), d_kps,
+                       e->tab<uint32_t>(e->plan.t_orient), e->tab<uint8_t>(e->plan.t_slot_level), d_kps,
                        e->d_aux.as<KpAux>(), cap, d_n_out, or_iters, s0);
     L.launch(k_trig, dim3((std::min(cap, e->plan.max_kp) + 255) / 256, batch), dim3(256), 0,
                        e->d_aux.as<KpAux>(), d_n_out, cap, e->trig);

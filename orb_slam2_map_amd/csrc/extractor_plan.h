@@ -283,7 +283,8 @@ struct ExtractorPlan {
     // an offset and no bytes)
     std::vector<uint8_t> blob;
     PlanTable t_geom, t_cells, t_ctab, t_bcol, t_xtab, t_ytab, t_yrow, t_rstrip, t_rsel, t_rwt, t_r8item, t_r8sel, t_r8wt,
-        t_pattern, t_orient;  // t_pattern: rBRIEF pattern; t_orient: k_orient's byte-weight tables
+        t_pattern, t_orient, t_slot_level;  // t_pattern: rBRIEF pattern; t_orient: k_orient's byte-weight tables;
+                                            // t_slot_level: slot_level() of every selection slot, one byte each
     template <typename T> const T *table(const PlanTable &t) const { return reinterpret_cast<const T *>(blob.data() + t.off); }
     template <typename T> size_t count(const PlanTable &t) const { return t.bytes / sizeof(T); }
 };
@@ -297,6 +298,18 @@ template <typename T> inline PlanTable plan_add_table(std::vector<uint8_t> &blob
     if (t.bytes)
         memcpy(blob.data() + t.off, data, t.bytes);
     return t;
+}
+
+// The level whose selection range [sel_off, sel_off + sel_cap) holds `slot`: the ranges are contiguous and ascending from 0
+// (plan_extractor), so it is the number of levels >= 1 that start at or below the slot.  -1 for a slot outside every range.
+inline int slot_level(const std::vector<LevelGeom> &geom, int slot)
+{
+    if (slot < 0 || geom.empty() || slot >= geom.back().sel_off + geom.back().sel_cap)
+        return -1;
+    int level = 0;
+    for (size_t l = 1; l < geom.size(); l++)
+        level += slot >= geom[l].sel_off ? 1 : 0;
+    return level;
 }
 
 // k_fast_detect: bands (rows of cells) x dword columns, and what every dword column knows about the cell grid.  Every
@@ -613,6 +626,11 @@ inline int plan_extractor(const ExtractorConsts &cst, int w, int h, const PlanHo
     P.t_r8wt = plan_add_table(b, rt.wt8.data(), rt.wt8.size());
     P.t_pattern = plan_add_table(b, k_pattern_host, sizeof(k_pattern_host));
     P.t_orient = plan_add_table(b, orw.data(), orw.size());
+    // k_orient: the level of every selection slot of a frame (a kernel finds its level with one byte load)
+    std::vector<uint8_t> slot_lev((size_t)sel_off);
+    for (int s = 0; s < sel_off; s++)
+        slot_lev[(size_t)s] = (uint8_t)slot_level(geom, s);
+    P.t_slot_level = plan_add_table(b, slot_lev.data(), slot_lev.size());
     return ORBGPU_OK;
 }
 
