@@ -247,7 +247,12 @@ int orbgpu_distinctive_descriptors(int32_t groups, const int32_t *offsets, const
  * features share one vocabulary node (the reference has no other brute-force matcher).
  * For each valid A row in index order: best/second-best over B rows not yet claimed; accept iff
  * best <= th_low and (float)best < nnratio*(float)second; claim.  match_b[j] = A index or -1.
- * valid_a may be NULL.  angle_* are cv::KeyPoint::angle (degrees), used iff check_orientation. */
+ * valid_a may be NULL.  angle_* are cv::KeyPoint::angle (degrees), used iff check_orientation.
+ * Angles are not validated, here or in any other matcher of this header.  The rotation bin of a pair is
+ * roundf(rot / 30) with rot = angle_a - angle_b, plus 360 when negative (ORBmatcher.cc:238-243; 30 folds onto 0).  A
+ * pair whose rounded quotient is not in [0, 30] -- a difference of 915 degrees or more or of -375 or less, a NaN or an
+ * infinite angle -- has no bin (the reference asserts there): it casts no vote in the histogram and, with
+ * check_orientation, is removed like a pair outside the three maxima.  The status stays ORBGPU_OK. */
 int orbgpu_match_bf(const uint8_t *desc_a, const float *angle_a, const uint8_t *valid_a, int32_t na,
                     const uint8_t *desc_b, const float *angle_b, int32_t nb, int32_t th_low, float nnratio,
                     int32_t check_orientation, int32_t *match_b, int32_t *nmatches, int32_t device_id);

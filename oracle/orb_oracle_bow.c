@@ -222,10 +222,14 @@ static int bow_rot_bin(float angle_a, float angle_b)
     float rot = angle_a - angle_b;
     if (rot < 0.0)
         rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == ORA_HISTO_LENGTH)
-        bin = 0;
-    return bin;
+    /* the reference asserts bin in [0, HISTO_LENGTH) here; the float is tested before it is converted, and a pair whose
+     * rounded quotient is not in [0, HISTO_LENGTH] (NaN and +-inf included) has no bin: it casts no vote and the
+     * rotation check removes it */
+    const float r = roundf(rot * factor);
+    if (!(r >= 0.0f && r <= (float)ORA_HISTO_LENGTH))
+        return -1;
+    const int bin = (int)r;
+    return bin == ORA_HISTO_LENGTH ? 0 : bin;
 }
 
 /* ORBmatcher::ComputeThreeMaxima, ORBmatcher.cc:1601-1642 (on the bin counts) */
@@ -275,7 +279,7 @@ int ora_search_by_bow(const uint8_t *desc_kf, const float *angle_kf, const uint8
     int *bin_of = (int *)malloc(sizeof(int) * (size_t)(nf > 0 ? nf : 1));
     for (int j = 0; j < nf; j++) {
         match_f[j] = -1;
-        bin_of[j] = -1;
+        bin_of[j] = -2; /* no pair */
     }
     int a = 0, b = 0;
     while (a < n_fv_kf && b < n_fv_f) {
@@ -307,7 +311,8 @@ int ora_search_by_bow(const uint8_t *desc_kf, const float *angle_kf, const uint8
                         if (check_orientation) {
                             const int bin = bow_rot_bin(angle_kf[realIdxKF], angle_f[bestIdxF]);
                             bin_of[bestIdxF] = bin;
-                            histo[bin]++;
+                            if (bin >= 0) /* a pair without a bin casts no vote */
+                                histo[bin]++;
                         }
                         nmatches++;
                     }
@@ -328,7 +333,7 @@ int ora_search_by_bow(const uint8_t *desc_kf, const float *angle_kf, const uint8
         bow_three_maxima(histo, ORA_HISTO_LENGTH, &i1, &i2, &i3);
         for (int j = 0; j < nf; j++) {
             const int bn = bin_of[j];
-            if (bn < 0 || bn == i1 || bn == i2 || bn == i3)
+            if (bn == -2 || (bn >= 0 && (bn == i1 || bn == i2 || bn == i3)))
                 continue;
             match_f[j] = -1;
             nmatches--;

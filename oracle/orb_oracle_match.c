@@ -67,10 +67,14 @@ static int rot_bin(float angle_a, float angle_b)
     float rot = angle_a - angle_b;
     if (rot < 0.0)
         rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == ORA_HISTO_LENGTH)
-        bin = 0;
-    return bin;
+    /* the reference asserts bin in [0, HISTO_LENGTH) here; the float is tested before it is converted, and a pair whose
+     * rounded quotient is not in [0, HISTO_LENGTH] (NaN and +-inf included) has no bin: it casts no vote and the
+     * rotation check removes it */
+    const float r = roundf(rot * factor);
+    if (!(r >= 0.0f && r <= (float)ORA_HISTO_LENGTH))
+        return -1;
+    const int bin = (int)r;
+    return bin == ORA_HISTO_LENGTH ? 0 : bin;
 }
 
 /* ------------------------------------------------------------------ M4 */
@@ -84,7 +88,7 @@ int ora_match_bf(const uint8_t *desc_a, const float *angle_a, const uint8_t *val
     memset(histo, 0, sizeof(histo));
     for (int j = 0; j < nb; j++) {
         match_b[j] = -1;
-        bin_of[j] = -1;
+        bin_of[j] = -2; /* no pair */
     }
     for (int i = 0; i < na; i++) {
         if (valid_a && !valid_a[i])
@@ -111,7 +115,8 @@ int ora_match_bf(const uint8_t *desc_a, const float *angle_a, const uint8_t *val
                 if (check_orientation) {
                     int bin = rot_bin(angle_a[i], angle_b[bestIdx]);
                     bin_of[bestIdx] = bin;
-                    histo[bin]++;
+                    if (bin >= 0) /* a pair without a bin casts no vote */
+                        histo[bin]++;
                 }
                 nmatches++;
             }
@@ -122,7 +127,7 @@ int ora_match_bf(const uint8_t *desc_a, const float *angle_a, const uint8_t *val
         three_maxima(histo, ORA_HISTO_LENGTH, &i1, &i2, &i3);
         for (int j = 0; j < nb; j++) {
             int b = bin_of[j];
-            if (b < 0 || b == i1 || b == i2 || b == i3)
+            if (b == -2 || (b >= 0 && (b == i1 || b == i2 || b == i3)))
                 continue;
             match_b[j] = -1;
             nmatches--;
@@ -386,7 +391,8 @@ int ora_search_by_projection_last(const ora_frame_view *cur, const float *cur_Tc
                 int bin = rot_bin(last->kp_angle[i], cur->kp_angle[bestIdx2]);
                 push_idx[npush] = bestIdx2;
                 push_bin[npush++] = bin;
-                histo[bin]++;
+                if (bin >= 0) /* a pair without a bin casts no vote */
+                    histo[bin]++;
             }
         }
     }
@@ -395,7 +401,7 @@ int ora_search_by_projection_last(const ora_frame_view *cur, const float *cur_Tc
         three_maxima(histo, ORA_HISTO_LENGTH, &i1, &i2, &i3);
         for (int k = 0; k < npush; k++) {
             int b = push_bin[k];
-            if (b == i1 || b == i2 || b == i3)
+            if (b >= 0 && (b == i1 || b == i2 || b == i3))
                 continue;
             kp_to_mp[push_idx[k]] = -1;
             nmatches--;
@@ -474,7 +480,8 @@ int ora_search_by_projection_keyframe(const ora_frame_view *cur, const float *cu
                 int bin = rot_bin(kf->kp_angle[i], cur->kp_angle[bestIdx2]);
                 push_idx[npush] = bestIdx2;
                 push_bin[npush++] = bin;
-                histo[bin]++;
+                if (bin >= 0) /* a pair without a bin casts no vote */
+                    histo[bin]++;
             }
         }
     }
@@ -483,7 +490,7 @@ int ora_search_by_projection_keyframe(const ora_frame_view *cur, const float *cu
         three_maxima(histo, ORA_HISTO_LENGTH, &i1, &i2, &i3);
         for (int k = 0; k < npush; k++) {
             int b = push_bin[k];
-            if (b == i1 || b == i2 || b == i3)
+            if (b >= 0 && (b == i1 || b == i2 || b == i3))
                 continue;
             kp_to_mp[push_idx[k]] = -1;
             nmatches--;
@@ -1009,7 +1016,7 @@ int ora_search_for_triangulation(const ora_frame_view *kf1, const uint8_t *has_m
     int *bin_of = (int *)malloc(sizeof(int) * (size_t)(kf1->n > 0 ? kf1->n : 1));
     for (int i = 0; i < kf1->n; i++) {
         match12[i] = -1;
-        bin_of[i] = -1;
+        bin_of[i] = -2; /* no pair */
     }
     int a = 0, b = 0;
     while (a < n_fv1 && b < n_fv2) {
@@ -1049,7 +1056,8 @@ int ora_search_for_triangulation(const ora_frame_view *kf1, const uint8_t *has_m
                     if (check_orientation) {
                         const int bin = rot_bin(kf1->kp_angle[idx1], kf2->kp_angle[bestIdx2]);
                         bin_of[idx1] = bin;
-                        histo[bin]++;
+                        if (bin >= 0) /* a pair without a bin casts no vote */
+                            histo[bin]++;
                     }
                 }
             }
@@ -1068,7 +1076,7 @@ int ora_search_for_triangulation(const ora_frame_view *kf1, const uint8_t *has_m
         three_maxima(histo, ORA_HISTO_LENGTH, &i1, &i2, &i3);
         for (int i = 0; i < kf1->n; i++) {
             const int bn = bin_of[i];
-            if (bn < 0 || bn == i1 || bn == i2 || bn == i3)
+            if (bn == -2 || (bn >= 0 && (bn == i1 || bn == i2 || bn == i3)))
                 continue;
             match12[i] = -1;
             nmatches--;
@@ -1094,7 +1102,7 @@ int ora_search_by_bow_kf(const uint8_t *desc1, const float *angle1, const uint8_
     uint8_t *matched2 = (uint8_t *)calloc((size_t)(n2 > 0 ? n2 : 1), 1);
     for (int i = 0; i < n1; i++) {
         match12[i] = -1;
-        bin_of[i] = -1;
+        bin_of[i] = -2; /* no pair */
     }
     int a = 0, b = 0;
     while (a < n_fv1 && b < n_fv2) {
@@ -1124,7 +1132,8 @@ int ora_search_by_bow_kf(const uint8_t *desc1, const float *angle1, const uint8_
                         if (check_orientation) {
                             const int bin = rot_bin(angle1[idx1], angle2[bestIdx2]);
                             bin_of[idx1] = bin;
-                            histo[bin]++;
+                            if (bin >= 0) /* a pair without a bin casts no vote */
+                                histo[bin]++;
                         }
                         nmatches++;
                     }
@@ -1145,7 +1154,7 @@ int ora_search_by_bow_kf(const uint8_t *desc1, const float *angle1, const uint8_
         three_maxima(histo, ORA_HISTO_LENGTH, &i1, &i2, &i3);
         for (int i = 0; i < n1; i++) {
             const int bn = bin_of[i];
-            if (bn < 0 || bn == i1 || bn == i2 || bn == i3)
+            if (bn == -2 || (bn >= 0 && (bn == i1 || bn == i2 || bn == i3)))
                 continue;
             match12[i] = -1;
             nmatches--;
@@ -1218,7 +1227,8 @@ int ora_search_for_initialization(const ora_frame_view *f1, const ora_frame_view
                     hist_items[npush] = i1;
                     hist_bin[npush] = bin;
                     npush++;
-                    histo[bin]++;
+                    if (bin >= 0) /* a pair without a bin casts no vote */
+                        histo[bin]++;
                 }
             }
         }
@@ -1228,7 +1238,7 @@ int ora_search_for_initialization(const ora_frame_view *f1, const ora_frame_view
         three_maxima(histo, ORA_HISTO_LENGTH, &i1m, &i2m, &i3m);
         for (int p = 0; p < npush; p++) {
             const int b = hist_bin[p];
-            if (b == i1m || b == i2m || b == i3m)
+            if (b >= 0 && (b == i1m || b == i2m || b == i3m))
                 continue;
             const int idx1 = hist_items[p];
             if (matches12[idx1] >= 0) { /* :497-501: a stolen match is already gone */

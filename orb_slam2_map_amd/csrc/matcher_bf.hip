@@ -499,7 +499,9 @@ __global__ __launch_bounds__(1024) void k_bf_resolve(int cap, const uint8_t *__r
         if (check_orientation) {
             const float fa = *reinterpret_cast<const float *>(aa + (size_t)i * angle_stride);
             const float fb = *reinterpret_cast<const float *>(ab + (size_t)j * angle_stride);
-            atomicAdd(&histo[rot_bin(fa, fb)], 1);
+            const int b = rot_bin(fa, fb);
+            if (b >= 0)  // a pair without a bin casts no vote
+                atomicAdd(&histo[b], 1);
         }
     }
     __syncthreads();
@@ -521,7 +523,7 @@ __global__ __launch_bounds__(1024) void k_bf_resolve(int cap, const uint8_t *__r
             const float fa = *reinterpret_cast<const float *>(aa + (size_t)i * angle_stride);
             const float fb = *reinterpret_cast<const float *>(ab + (size_t)j * angle_stride);
             const int b = rot_bin(fa, fb);
-            keep = (b == s_keep[0] || b == s_keep[1] || b == s_keep[2]);
+            keep = rot_bin_kept(b, s_keep[0], s_keep[1], s_keep[2]);
         }
         if (keep)
             mb[j] = i;

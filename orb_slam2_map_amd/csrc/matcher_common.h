@@ -44,17 +44,28 @@ ORBGPU_HD inline void three_maxima(const int *histo, int L, int &ind1, int &ind2
     }
 }
 
-// rotation bin, ORBmatcher.cc:238-243
+// rotation bin, ORBmatcher.cc:238-243.  The reference asserts bin in [0, HISTO_LENGTH) behind the conversion; angles are
+// the caller's, so here the float is tested before it is converted: a pair whose roundf(rot * factor) is not in
+// [0, HISTO_LENGTH] (a difference of 915 or more, of -375 or less, NaN, +-inf) has no bin, -1.  Such a pair casts no vote
+// and, when the orientation is checked, is removed like a pair outside the three maxima (rot_bin_kept).
 ORBGPU_HD inline int rot_bin(float angle_a, float angle_b)
 {
     const float factor = 1.0f / ORBGPU_HISTO_LENGTH;
     float rot = angle_a - angle_b;
     if (rot < 0.0f)
         rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == ORBGPU_HISTO_LENGTH)
-        bin = 0;
-    return bin;
+    const float r = roundf(rot * factor);
+    if (!(r >= 0.0f && r <= (float)ORBGPU_HISTO_LENGTH))
+        return -1;
+    const int bin = (int)r;
+    return bin == ORBGPU_HISTO_LENGTH ? 0 : bin;
+}
+
+// whether a pair of bin `bin` survives the rotation check; ind1..3 of three_maxima, where -1 stands for "no such maximum"
+// and must not keep a pair that has no bin
+ORBGPU_HD inline bool rot_bin_kept(int bin, int ind1, int ind2, int ind3)
+{
+    return bin >= 0 && (bin == ind1 || bin == ind2 || bin == ind3);
 }
 
 } // namespace orbgpu

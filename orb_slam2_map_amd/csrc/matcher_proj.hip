@@ -538,8 +538,11 @@ __device__ __forceinline__ void proj_resolve_body(int m, const Query *__restrict
             continue;
         cnt++;
         atomicMax(&last_claim[j], i);
-        if (check_orientation)
-            atomicAdd(&histo[rot_bin(row_angle[(size_t)i * row_angle_stride], kp_angle[j * kp_angle_stride])], 1);
+        if (check_orientation) {
+            const int b = rot_bin(row_angle[(size_t)i * row_angle_stride], kp_angle[j * kp_angle_stride]);
+            if (b >= 0)  // a pair without a bin casts no vote
+                atomicAdd(&histo[b], 1);
+        }
     }
     __syncthreads();
     for (int j = tid; j < n; j += nt)
@@ -560,7 +563,7 @@ __device__ __forceinline__ void proj_resolve_body(int m, const Query *__restrict
             if (j < 0)
                 continue;
             const int b = rot_bin(row_angle[(size_t)i * row_angle_stride], kp_angle[j * kp_angle_stride]);
-            if (b != s_keep[0] && b != s_keep[1] && b != s_keep[2]) {
+            if (!rot_bin_kept(b, s_keep[0], s_keep[1], s_keep[2])) {
                 kp_to_mp[j] = -1;
                 cnt--;
             }
@@ -1810,7 +1813,8 @@ int orbgpu_search_for_initialization(const orbgpu_frame_view *f1, const orbgpu_f
             if (check_orientation) {
                 const int bin = rot_bin(f1->kp_angle[i1], f2->kp_angle[bestIdx2]);
                 pushes.emplace_back(bin, i1);
-                histo[bin]++;
+                if (bin >= 0)  // a pair without a bin casts no vote
+                    histo[bin]++;
             }
         }
     }
@@ -1818,7 +1822,7 @@ int orbgpu_search_for_initialization(const orbgpu_frame_view *f1, const orbgpu_f
         int ind1, ind2, ind3;
         three_maxima(histo, ORBGPU_HISTO_LENGTH, ind1, ind2, ind3);
         for (const auto &pr : pushes) {
-            if (pr.first == ind1 || pr.first == ind2 || pr.first == ind3)
+            if (rot_bin_kept(pr.first, ind1, ind2, ind3))
                 continue;
             if (matches12[pr.second] >= 0) {
                 matches12[pr.second] = -1;

@@ -106,8 +106,11 @@ __device__ __forceinline__ void tri_finish_block(int n1, const float *__restrict
         if (j < 0)
             continue;
         cnt++;
-        if (check_orientation)
-            atomicAdd(&histo[rot_bin(angle1[i], angle2[j])], 1);
+        if (check_orientation) {
+            const int b = rot_bin(angle1[i], angle2[j]);
+            if (b >= 0)  // a pair without a bin casts no vote
+                atomicAdd(&histo[b], 1);
+        }
     }
     __syncthreads();
     if (check_orientation) {
@@ -122,7 +125,7 @@ __device__ __forceinline__ void tri_finish_block(int n1, const float *__restrict
             if (j < 0)
                 continue;
             const int b = rot_bin(angle1[i], angle2[j]);
-            if (b != s_keep[0] && b != s_keep[1] && b != s_keep[2]) {
+            if (!rot_bin_kept(b, s_keep[0], s_keep[1], s_keep[2])) {
                 match12[i] = -1;
                 cnt--;
             }
