@@ -323,7 +323,17 @@ int orbgpu_undistort_points(int32_t n, const float *xy_in, const orbgpu_camera *
  * distorted key point, mvuRight = kpUn.x - mbf/d, mvDepth = d where d > 0, else -1) and
  * Frame::AssignFeaturesToGrid (Frame.cc:230-245, on mvKeysUn) as CSR per frame (cell_start[batch][COLS*ROWS+1],
  * cell_items[batch][cap], items in insertion order).  d_depth may be NULL (no stereo outputs); depth strides are
- * in floats.  All pointers except cam are device pointers; nothing is synchronised. */
+ * in floats.  All pointers except cam are device pointers; nothing is synchronised.
+ * Preconditions and conventions, the first one shared with the reference:
+ *  - with d_depth, the distorted position (x, y) of every counted key point must be finite and inside the depth image,
+ *    0 <= (int)x < width and 0 <= (int)y < height: the lookup depth[(int)y][(int)x] is not checked, as imDepth.at is not;
+ *  - d_n[f] is clamped to [0, cap]; only the first n rows of frame f are read;
+ *  - rows at and beyond n of d_kps_un, d_u_right and d_kp_depth are not written, nor is d_cell_items beyond
+ *    cell_start[f][COLS*ROWS]; d_cell_start is written whole (all zero for n = 0);
+ *  - the mvKeysUn copy and the grid follow the reference's gate: only dist[0] != 0 undistorts, whatever dist[1..4] hold
+ *    (Frame.cc:406), while orbgpu_undistort_points applies all five coefficients;
+ *  - a key point whose rounded grid coordinate is NaN, +-inf or beyond the grid has no cell (the reference converts to
+ *    int first, which C leaves undefined for these); orbgpu_assign_features_to_grid does the same. */
 int orbgpu_frame_glue_batch_device(int32_t device_id, int32_t batch, int32_t cap, const orbgpu_keypoint *d_kps,
                                    const int32_t *d_n, const float *d_depth, size_t depth_stride,
                                    size_t depth_frame_stride, const orbgpu_camera *cam, orbgpu_keypoint *d_kps_un,

@@ -5,6 +5,7 @@
 // for a batch of frames whose key points were just written by orbgpu_extract_batch_device, so that
 // extract -> mvKeysUn -> mvuRight/mvDepth -> mGrid needs no host round trip.
 #include "common.h"
+#include "matcher_common.h"  // grid_cell: PosInGrid, shared with the host entry orbgpu_assign_features_to_grid
 
 namespace orbgpu {
 
@@ -96,9 +97,9 @@ __global__ __launch_bounds__(1024) void k_frame_glue(const orbgpu_keypoint *__re
             u_right[(size_t)f * cap + i] = ur;
             kp_depth[(size_t)f * cap + i] = dz;
         }
-        const int px = (int)roundf((xu - min_x) * inv_w), py = (int)roundf((yu - min_y) * inv_h);
-        if (px >= 0 && px < FG_COLS && py >= 0 && py < FG_ROWS)
-            atomicAdd(&cnt[px * FG_ROWS + py], 1);
+        const int cell = grid_cell(xu, yu, min_x, min_y, inv_w, inv_h);
+        if (cell >= 0)
+            atomicAdd(&cnt[cell], 1);
     }
     __syncthreads();
     // exclusive scan of cnt[0..FG_CELLS) (3072 = 3 per thread at 1024 threads)
@@ -141,9 +142,9 @@ __global__ __launch_bounds__(1024) void k_frame_glue(const orbgpu_keypoint *__re
     for (int c = tid; c <= FG_CELLS; c += nt)
         cs[c] = cnt[c];
     for (int i = tid; i < n; i += nt) {
-        const int px = (int)roundf((kun[i].x - min_x) * inv_w), py = (int)roundf((kun[i].y - min_y) * inv_h);
-        if (px >= 0 && px < FG_COLS && py >= 0 && py < FG_ROWS)
-            items[atomicAdd(&pos[px * FG_ROWS + py], 1)] = i;
+        const int cell = grid_cell(kun[i].x, kun[i].y, min_x, min_y, inv_w, inv_h);
+        if (cell >= 0)
+            items[atomicAdd(&pos[cell], 1)] = i;
     }
     __syncthreads();
     // restore insertion order inside every cell (lists are short: insertion sort by one thread per cell)

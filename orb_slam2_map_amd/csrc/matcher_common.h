@@ -68,4 +68,17 @@ ORBGPU_HD inline bool rot_bin_kept(int bin, int ind1, int ind2, int ind3)
     return bin >= 0 && (bin == ind1 || bin == ind2 || bin == ind3);
 }
 
+// Frame::PosInGrid (Frame.cc:382-392) as the CSR cell px * ROWS + py, or -1 where the reference refuses the point.  The
+// reference converts round(...) to int before it tests the range; a NaN or a value beyond int has no int (on x86 the
+// conversion gives INT_MIN, which the test refuses; on the device it gives 0 for NaN, a cell that would be kept).
+// Positions are the caller's, so here the rounded float is tested before it is converted: NaN, +-inf and anything
+// beyond the grid have no cell.  For every value the reference defines, the result is the reference's.
+ORBGPU_HD inline int grid_cell(float x, float y, float min_x, float min_y, float inv_w, float inv_h)
+{
+    const float px = roundf((x - min_x) * inv_w), py = roundf((y - min_y) * inv_h);
+    if (!(px >= 0.0f && px < (float)ORBGPU_GRID_COLS && py >= 0.0f && py < (float)ORBGPU_GRID_ROWS))
+        return -1;
+    return (int)px * ORBGPU_GRID_ROWS + (int)py;
+}
+
 } // namespace orbgpu

@@ -1152,14 +1152,9 @@ int orbgpu_assign_features_to_grid(int32_t n, const float *kp_x, const float *kp
     for (int c = 0; c <= NC; c++)
         cell_start[c] = 0;
     for (int i = 0; i < n; i++) {
-        const int px = (int)roundf((kp_x[i] - min_x) * inv_w);
-        const int py = (int)roundf((kp_y[i] - min_y) * inv_h);
-        if (px < 0 || px >= GC || py < 0 || py >= GR) {
-            cell_of[i] = -1;
-            continue;
-        }
-        cell_of[i] = px * GR + py;
-        cell_start[cell_of[i] + 1]++;
+        cell_of[i] = grid_cell(kp_x[i], kp_y[i], min_x, min_y, inv_w, inv_h);
+        if (cell_of[i] >= 0)
+            cell_start[cell_of[i] + 1]++;
     }
     for (int c = 0; c < NC; c++)
         cell_start[c + 1] += cell_start[c];

@@ -1,5 +1,5 @@
 // csrc/matcher_common.h on the host: rot_bin and three_maxima against literals worked out from ORBmatcher.cc:238-243 and
-// :1601-1642.  Built by test_matcher_common.py with AddressSanitizer, UBSan and float-cast-overflow, no recovery: a bin
+// :1601-1642, grid_cell against literals worked out from Frame.cc:382-392.  Built by test_matcher_common.py with AddressSanitizer, UBSan and float-cast-overflow, no recovery: a bin
 // that was converted from a float outside int's range, or that indexed the histogram below outside [0, 30), ends the run.
 //
 // The reference's factor is 1.0f / HISTO_LENGTH = 1 / 30, so angles in [0, 360) use the bins 0..12 only:
@@ -39,9 +39,38 @@ static void expect_kept(const char *what, int bin, int i1, int i2, int i3, bool 
     g_fail += got != want;
 }
 
+// grid_cell on 512 x 384 with bounds = image (cells of 8 x 8 pixels, inv = 0.125 exactly): column * 48 + row, or -1
+static void expect_cell(const char *what, float x, float y, int want)
+{
+    int grid[ORBGPU_GRID_COLS * ORBGPU_GRID_ROWS] = {0};
+    const int got = orbgpu::grid_cell(x, y, 0.f, 0.f, 0.125f, 0.125f);
+    if (got >= 0)
+        grid[got]++;  // under ASan: a cell outside the grid is a stack overflow here
+    const bool ok = got == want && (got < 0 || grid[got] == 1);
+    printf("%s grid_cell %s: %d, expected %d\n", ok ? "ok" : "FAIL", what, got, want);
+    g_fail += !ok;
+}
+
 int main()
 {
     const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
+    // PosInGrid, Frame.cc:382-392: round half away from zero, kept iff 0 <= column < 64 and 0 <= row < 48
+    expect_cell("(4, 100)", 4.f, 100.f, 1 * 48 + 13);                       // 0.5 -> 1, 12.5 -> 13
+    expect_cell("(4-, 100)", std::nextafter(4.f, 0.f), 100.f, 13);          // 0.49999997 -> 0
+    expect_cell("(508-, 380-)", std::nextafter(508.f, 0.f), std::nextafter(380.f, 0.f), 63 * 48 + 47);
+    expect_cell("(508, 100)", 508.f, 100.f, -1);                            // 63.5 -> 64
+    expect_cell("(100, 380)", 100.f, 380.f, -1);                            // 47.5 -> 48
+    expect_cell("(-4, 100)", -4.f, 100.f, -1);                              // -0.5 -> -1
+    expect_cell("(-4+, -4+)", std::nextafter(-4.f, 0.f), std::nextafter(-4.f, 0.f), 0);  // -0.49999997 -> -0.0
+    expect_cell("(-0, -0)", -0.f, -0.f, 0);
+    expect_cell("(NaN, 100)", nan, 100.f, -1);
+    expect_cell("(100, NaN)", 100.f, nan, -1);
+    expect_cell("(+inf, 100)", inf, 100.f, -1);
+    expect_cell("(100, -inf)", 100.f, -inf, -1);
+    expect_cell("(1e30, 100)", 1e30f, 100.f, -1);                           // finite, far outside int
+    expect_cell("(100, -1e30)", 100.f, -1e30f, -1);
+    expect_cell("(3.5e10, 100)", 3.5e10f, 100.f, -1);                       // 4.4e9: wraps to a small int modulo 2^32
+
     // rot / 30, rounded half away from zero (roundf)
     expect_bin("0", 0.f, 0.f, 0);
     expect_bin("14.99", 14.99f, 0.f, 0);       // 0.4997

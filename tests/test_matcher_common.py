@@ -40,6 +40,14 @@ def test_three_maxima_is_covered(lines):
         assert any(ln.startswith("ok three_maxima %s:" % what) for ln in lines), what
 
 
+def test_grid_cell_is_covered(lines):
+    """grid_cell (Frame::PosInGrid for the frame glue and orbgpu_assign_features_to_grid): half away from zero on both
+    edges of both axes, and NaN, +-inf and values beyond int come back as -1 without a conversion outside int's range."""
+    for what in ("(4, 100)", "(4-, 100)", "(508-, 380-)", "(508, 100)", "(100, 380)", "(-4, 100)", "(-4+, -4+)",
+                 "(NaN, 100)", "(100, NaN)", "(+inf, 100)", "(100, -inf)", "(1e30, 100)", "(3.5e10, 100)"):
+        assert any(ln.startswith("ok grid_cell %s:" % what) for ln in lines), what
+
+
 def test_header_is_pure_cxx():
     """The header is what the host loop of orbgpu_search_for_initialization compiles too: nothing of HIP outside the
     __HIPCC__ branch."""
